@@ -7,8 +7,8 @@ nz=128 f_width=64 f_depth=5, B=65536 rows of synthetic z per evaluation (BASELIN
 
 A step = one pass of the hot path over one batch: the fused forward launch (z -> z1, logdet, ll, and sum_b ll
 accumulated in the kernel's epilogue, train.py:320) and -- for N > 1 -- the single RCCL all-reduce of that sum,
-one per evaluation (asynchronous).  Steps are independent batches and rotate over `--streams` HIP streams; the
-single-stream figure is reported beside it.  z, the prepared weights and all outputs are resident in HBM when the
+one per evaluation (asynchronous).  Steps are independent batches and rotate over `--streams` HIP streams; with
+`--full` the single-stream figure is reported beside it.  z, the prepared weights and all outputs are resident in HBM when the
 timed region starts.
 
 Arithmetic of the headline (`--math`, default bf16x3): every GEMM operand is split error-free into three bf16 terms
@@ -17,19 +17,27 @@ reference's fp32 matmuls (model.py:187,326,347).  `--math fp32` runs the fp32-MF
 terms, 22 bits) is an opt-in mode and never the headline.
 
 N > 1: the headline is STRONG scaling -- the 65 536 rows of one evaluation sharded contiguously
-over the ranks (`parallel.shard_bounds`), every evaluation all-reduced, `--strong-bucket` (8) evaluations per asynchronous collective -- and the same run also times WEAK scaling
-(65 536 rows per GPU, `--weak-bucket` evaluations per collective) and reports it as `weak_scaling`.
+over the ranks (`parallel.shard_bounds`), every evaluation all-reduced, `--strong-bucket` (8) evaluations per asynchronous collective -- and with
+`--full` the same run also times WEAK scaling (65 536 rows per GPU, `--weak-bucket` evaluations per collective) and reports it
+as `weak_scaling`.
 
-Spread ("median and p10/p90"): the K-step timed region is repeated R = max(5, ceil(200 / K)) times behind ONE
-clock ramp and ONE warm-up; `ms_per_step` is the MEDIAN of the R repetitions, `ms_per_step_p10` / `_p90` ride beside it (same
-for the single-stream figure); the kernel-only loop of the roofline is timed per launch with HIP events and reports its median.
+A plain run (no `--full`) measures the headline and nothing else: set-up, clock ramp, W warm-up steps, ONE timed region of
+exactly K steps (`ms_per_step` = its time / K), then the result line.  `--dump-outputs DIR` writes what the last timed step
+computed (z1, logdet, ll as float32, the [sum ll, sum logdet, rows] of its stats as float64) to DIR/<name>.npy after the timed
+region; z and the weights are seeded, so two builds given the same arguments can be compared output for output.
+
+`--full` adds everything beside the headline: the single-stream figure, the other scaling form (N > 1), the kernel-only
+roofline loops, the other arithmetic modes, the cost of prepare() and the CPU baseline -- and the spread ("median
+and p10/p90"): the K-step timed region is repeated R = max(5, ceil(200 / K)) times behind ONE clock ramp and ONE warm-up;
+`ms_per_step` is then the MEDIAN of the R repetitions, `ms_per_step_p10` / `_p90` ride beside it (same for the single-stream
+figure); the kernel-only loop of the roofline is timed per launch with HIP events and reports its median.
 
 `--shard-of N` (one GPU): what ONE GPU of an N-GPU strong-scaling job does per step -- rows = 65 536 / N, same stream
 rotation, in-kernel sums, the same reducer protocol -- next to the full-size step of the same run; prints the per-shard ms/step and
 the N-GPU ceiling it implies (65 536 rows / shard time: no communication, no straggler), i.e. the bound on strong scaling that
 one GPU decides.
 
-Prints ONE JSON line on rank 0, including
+Prints ONE JSON line on rank 0; with `--full` it includes
   "roofline":     the forward kernel's ALGORITHMIC FLOP/s (327 680 FLOP/sample x rows / HIP-event time of a
                   single-stream kernel-only loop, measured in this run) against the dense peak of the matrix pipe it
                   runs on, plus the same rate against the fp32-MFMA peak and the executed-flops pipe utilisation;
@@ -44,6 +52,7 @@ import subprocess
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -81,7 +90,6 @@ MATH_TEXT = {
 def synth_weights(seed=1):
     """Reference-style init (orthogonal W, 0.05 N(0,1) elsewhere) + 0.05 N(0,1) on fc_zeros, built
     with torch/numpy RNG only (no oracle import on the product path)."""
-    import numpy as np
     g = torch.Generator().manual_seed(seed)
     rs = np.random.RandomState(seed)
     half = NZ // 2
@@ -271,7 +279,13 @@ def main():
                          "steps replays at 22 us per step in the one-rank rehearsal.  auto = off: collectives inside a captured graph "
                          "could only be rehearsed with one rank on this pool (a multi-stream capture around them crashed), so the "
                          "default stays the eager loop that has run on every backend")
-    ap.add_argument("--reps", type=int, default=0, help="repetitions of the K-step timed region (default max(5, ceil(200 / K)))")
+    ap.add_argument("--reps", type=int, default=0, help="repetitions of the K-step timed region (default 1; with --full "
+                    "max(5, ceil(200 / K)))")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: spread over repeated timed regions, single-stream figure, "
+                         "the other scaling form (N > 1), kernel-only roofline, other arithmetic modes, prepare() cost, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (z1, logdet, ll, sums) as DIR/<name>.npy")
     ap.add_argument("--selftest-launcher", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
 
@@ -326,8 +340,11 @@ def main():
         calls = [lsnf_amd.flow.BoundForward(plan, z, o) for o in outs]
         return z, outs, reducers, streams, calls
 
-    reps = args.reps if args.reps > 0 else max(5, -(-200 // max(1, args.steps)))
+    # a plain run times ONE region of exactly K steps; the spread over repeated regions is part of --full (and of --shard-of)
+    spread = args.full or args.shard_of
+    reps = args.reps if args.reps > 0 else (max(5, -(-200 // max(1, args.steps))) if spread else 1)
     graph_used = []
+    last_step = {}                              # buffers of the last step issued: its outputs and the reducer of its stream
 
     def timed(run, steps, warmup):
         """clock ramp (untimed, not steps) + W untimed steps, then `reps` x (K timed steps); returns the list of seconds per
@@ -341,6 +358,7 @@ def main():
             k = counter[0] % len(streams)
             counter[0] += 1
             red = reducers[k]
+            last_step["out"], last_step["red"] = outs[k], red
             if red.touches_stream():                # first / last evaluation of a bank: the reducer waits for / issues a collective
                 with torch.cuda.stream(streams[k]):
                     stats = red.next_buffer()
@@ -447,39 +465,108 @@ def main():
     gen = torch.Generator().manual_seed(1234 + rank)
     z_weak = torch.randn(B_GLOBAL, NZ, generator=gen).to(dev)                  # 65 536 rows on every GPU
     if args.shard_of:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs writes the outputs of the headline run; --shard-of prints its own line only")
         raise SystemExit(shard_mode(args, world, rank, dev, z_weak, make_run, timed, summarize, ramp_out, reps,
                                     side_streams if n_streams > 1 else [main_stream], main_stream, MODES[args.math]["dtype"]))
     lo, hi = parallel.shard_bounds(B_GLOBAL, world, rank)
     z_strong = z_weak[: hi - lo].contiguous() if world > 1 else z_weak         # this rank's slab of ONE 65 536-row evaluation
-    tmp = (torch.empty_like(z_weak), torch.empty(B_GLOBAL, device=dev), torch.empty(B_GLOBAL, device=dev))
-    forms = ["strong", "weak"] if world > 1 else ["single"]
+    headline = "single" if world == 1 else args.scaling
+    # a plain run times the headline form only; --full times both forms at N > 1 and every form on one stream too
+    forms = (["strong", "weak"] if world > 1 else ["single"]) if args.full else [headline]
     runs = {}
     for form in forms:
         z = z_strong if form == "strong" else z_weak
         bucket = max(1, args.strong_bucket) if form != "weak" else max(1, args.weak_bucket)
         if world == 1:
             bucket = 1                                                         # (one GPU: no collective, the reducer only rotates its banks)
-        runs[form] = (make_run(z, bucket, side_streams if n_streams > 1 else [main_stream]), make_run(z, bucket, [main_stream]), bucket)
+        runs[form] = (make_run(z, bucket, side_streams if n_streams > 1 else [main_stream]),
+                      make_run(z, bucket, [main_stream]) if args.full else None, bucket)
     torch.cuda.synchronize()
 
     results = {}
+    outputs = None
     for form in forms:
         multi, single, bucket = runs[form]
         z = multi[0]
         ramp_out(z.shape[0])                          # (allocated before the ramp)
         els = timed(multi, args.steps, args.warmup)
-        els1 = timed(single, args.steps, args.warmup)
+        if form == headline and args.dump_outputs:
+            # what a caller of the timed path receives from its last step: the three output arrays and the (reduced) sums
+            (o_z1, o_logdet, o_ll), sums = last_step["out"], last_step["red"].finish()
+            torch.cuda.synchronize()
+            outputs = {"z1": o_z1.float().cpu().numpy(), "logdet": o_logdet.float().cpu().numpy(),
+                       "ll": o_ll.float().cpu().numpy(), "sums": sums.double().cpu().numpy()}
         rows_all = B_GLOBAL if form != "weak" else world * B_GLOBAL
         results[form] = dict(summarize(els, args.steps, rows_all))
-        one = summarize(els1, args.steps, rows_all)
-        results[form].update({"ms_per_step_single_stream": one["ms_per_step"], "ms_per_step_single_stream_p10": one["ms_per_step_p10"],
-                              "ms_per_step_single_stream_p90": one["ms_per_step_p90"], "value_single_stream": one["value"],
-                              "timed_regions": reps, "rows_per_gpu": z.shape[0], "global_rows_per_step": rows_all,
+        results[form].update({"timed_regions": reps, "rows_per_gpu": z.shape[0], "global_rows_per_step": rows_all,
                               "evaluations_per_collective": bucket if world > 1 else None})
-    head = results["single"] if world == 1 else results[args.scaling]
+        if single is not None:
+            one = summarize(timed(single, args.steps, args.warmup), args.steps, rows_all)
+            results[form].update({"ms_per_step_single_stream": one["ms_per_step"], "ms_per_step_single_stream_p10": one["ms_per_step_p10"],
+                                  "ms_per_step_single_stream_p90": one["ms_per_step_p90"], "value_single_stream": one["value"]})
+    head = results[headline]
+    if outputs is not None and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
 
+    extra = full_measurements(args, rank, dev, plan, weights, z_weak, MATH, pct) if args.full else None
+    if rank == 0:
+        mode = MODES[args.math]
+        line = {
+            "metric": "latent-samples/sec through flow+logdet, nz=128 B=65536",
+            "value": head["value"], "unit": "latent-samples/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": head["ms_per_step"]}
+        if args.full or reps > 1:
+            line.update({"ms_per_step_p10": head["ms_per_step_p10"], "ms_per_step_p90": head["ms_per_step_p90"]})
+        line.update({
+            "timed_regions": reps, "higher_is_better": True,
+            # (strong at every N, N = 1 included: the 65 536 rows of one evaluation are what is fixed)
+            "scaling": "strong" if world == 1 else args.scaling,
+            "vs_baseline": None, "dtype": mode["dtype"], "data": "synthetic"})
+        if args.full:
+            line.update({k: head[k] for k in ("ms_per_step_single_stream", "ms_per_step_single_stream_p10",
+                                              "ms_per_step_single_stream_p90", "value_single_stream")})
+        config = {"workload": "CIFAR-10 flow prior nz=128 f_width=64 f_depth=5 affine, forward+logdet+log-prob, "
+                              "B=65536 synthetic z per evaluation (BASELINE.json configs[2])",
+                  "rows_per_gpu": head["rows_per_gpu"], "global_rows": head["global_rows_per_step"],
+                  "parallelism": (f"dp{world}, {args.scaling} scaling: rows sharded, weights replicated; sum ll / sum logdet / "
+                                  f"rows of every evaluation all-reduced ({head['evaluations_per_collective']} "
+                                  f"evaluation(s) per collective, backend {args.backend})") if world > 1 else "single GPU",
+                  "streams": n_streams, "clock_ramp_launches_before_warmup": max(0, args.ramp)}
+        if extra:
+            config["prepare_ms_not_in_step"] = extra["prepare_ms_not_in_step"]
+        config["math"] = MATH_TEXT[args.math]
+        if extra:
+            config["other_math_modes"] = extra["other_math_modes"]
+        line.update({
+            "untimed_launches_before_timed_region": max(0, args.ramp) + args.warmup,
+            "steps_issued_from": "one captured HIP graph per timed region (forward launches + all-reduces)" if (graph_used and graph_used[0]) else "Python, one call per launch",
+            "config": config})
+        if extra:
+            line["roofline"] = extra["roofline"]
+            if world > 1:
+                other_form = "weak" if args.scaling == "strong" else "strong"
+                line[other_form + "_scaling"] = results[other_form]
+        if world > 1:
+            line["ranks_seen_by_backend"] = dist.get_world_size()
+        if outputs is not None:
+            line["outputs_dumped"] = {"dir": args.dump_outputs, "arrays": sorted(outputs)}
+        if args.full and world == 1 and not args.no_cpu_baseline:
+            line["cpu_baseline"] = cpu_baseline(weights)
+        print(json.dumps(line), flush=True)
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_measurements(args, rank, dev, plan, weights, z_weak, MATH, pct):
+    """--full: the kernel-only roofline loops in every arithmetic mode and the cost of prepare() (every rank runs them);
+    returns, on rank 0, the roofline and the per-mode figures for the result line."""
+    import lsnf_amd
     # kernel-only loop for the roofline: HIP events on the launch stream around back-to-back launches of one stream
-    z1, logdet, ll = tmp
+    z1, logdet, ll = (torch.empty_like(z_weak), torch.empty(B_GLOBAL, device=dev), torch.empty(B_GLOBAL, device=dev))
 
     def kernel_ms(mode, spread=None):
         """single-stream kernel-only loop of 200 back-to-back launches between two HIP events: ms per launch (what the
@@ -571,42 +658,8 @@ def main():
                       "accurate product costs exec_per_alg MFMAs on that pipe, so frac <= 1/exec_per_alg; "
                       "matrix_pipe_utilisation prices the executed flops",
               "carried": carried}
-        line = {
-            "metric": "latent-samples/sec through flow+logdet, nz=128 B=65536",
-            "value": head["value"], "unit": "latent-samples/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": head["ms_per_step"], "ms_per_step_p10": head["ms_per_step_p10"],
-            "ms_per_step_p90": head["ms_per_step_p90"], "timed_regions": reps, "higher_is_better": True,
-            # (strong at every N, N = 1 included: the 65 536 rows of one evaluation are what is fixed)
-            "scaling": "strong" if world == 1 else args.scaling,
-            "vs_baseline": None, "dtype": mode["dtype"], "data": "synthetic",
-            "ms_per_step_single_stream": head["ms_per_step_single_stream"],
-            "ms_per_step_single_stream_p10": head["ms_per_step_single_stream_p10"],
-            "ms_per_step_single_stream_p90": head["ms_per_step_single_stream_p90"],
-            "value_single_stream": head["value_single_stream"],
-            "untimed_launches_before_timed_region": max(0, args.ramp) + args.warmup,
-            "steps_issued_from": "one captured HIP graph per timed region (forward launches + all-reduces)" if (graph_used and graph_used[0]) else "Python, one call per launch",
-            "config": {"workload": "CIFAR-10 flow prior nz=128 f_width=64 f_depth=5 affine, forward+logdet+log-prob, "
-                                   "B=65536 synthetic z per evaluation (BASELINE.json configs[2])",
-                       "rows_per_gpu": head["rows_per_gpu"], "global_rows": head["global_rows_per_step"],
-                       "parallelism": (f"dp{world}, {args.scaling} scaling: rows sharded, weights replicated; sum ll / sum logdet / "
-                                       f"rows of every evaluation all-reduced ({head['evaluations_per_collective']} "
-                                       f"evaluation(s) per collective, backend {args.backend})") if world > 1 else "single GPU",
-                       "streams": n_streams, "clock_ramp_launches_before_warmup": max(0, args.ramp),
-                       "prepare_ms_not_in_step": prep_ms, "math": MATH_TEXT[args.math],
-                       "other_math_modes": others},
-            "roofline": rl,
-        }
-        if world > 1:
-            other_form = "weak" if args.scaling == "strong" else "strong"
-            line[other_form + "_scaling"] = results[other_form]
-            line["ranks_seen_by_backend"] = dist.get_world_size()
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(weights)
-        print(json.dumps(line), flush=True)
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
-
+        return {"roofline": rl, "other_math_modes": others, "prepare_ms_not_in_step": prep_ms}
+    return None
 
 if __name__ == "__main__":
     main()

@@ -27,7 +27,7 @@ for key, name in (("lsnf_fwd2h", "lsnf_fwd2h_kernel<Fwd3Cfg<2,2>, 8>"), ("lsnf_f
         if e:
             out["lsnf_fwd3b_kernel as the early-exit fix-up pass behind lsnf_fwd2h_kernel"] = {
                 "dispatches_in_trace": len(e), "kernel_only_loop_last_200_avg_us": sum(e[-200:]) / min(200, len(e)), "min_us": min(e), "max_us": max(e)}
-out["note"] = ("per-dispatch durations from rocprofv3 --kernel-trace of `python3 bench.py --steps 300 --warmup 100 --no-cpu-baseline`; "
+out["note"] = ("per-dispatch durations from rocprofv3 --kernel-trace of `python3 bench.py --full --steps 300 --warmup 100 --no-cpu-baseline`; "
                "the timed steps alternate over 2 HIP streams, so their kernels overlap and the all-dispatch average of the "
                "kernel_stats csv is NOT a kernel duration; bench.py's roofline uses its single-stream kernel-only loop "
                "(the last 200 dispatches of each kernel), which is what is averaged here")

@@ -32,7 +32,7 @@ for key, name in (("lsnf_fwd3q", "lsnf_fwd3q_kernel<2, 8, 2>"), ("lsnf_fwd3b", "
         continue
     # bench.py's kernel-only loops run last, single stream: fp32, fp16x2 (+ its fix-up), then the measured mode
     out[name] = {"dispatches_in_trace": len(d), "kernel_only_loop_last_200_avg_us": sum(d[-200:]) / 200, "min_us": min(d[-200:]), "max_us": max(d[-200:])}
-out["note"] = ("per-dispatch durations from rocprofv3 --kernel-trace of `python3 bench.py --steps 300 --warmup 100 --no-cpu-baseline` (default --math "
+out["note"] = ("per-dispatch durations from rocprofv3 --kernel-trace of `python3 bench.py --full --steps 300 --warmup 100 --no-cpu-baseline` (default --math "
                "bf16x3); the timed steps rotate over 3 HIP streams, so their kernels overlap and the all-dispatch average of the kernel_stats csv is NOT "
                "a kernel duration; bench.py's roofline uses its single-stream kernel-only loop (the last 200 dispatches of each kernel), which is what "
                "is averaged here")

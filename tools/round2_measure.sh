@@ -7,12 +7,12 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/round2
 mkdir -p $O
 cd $R
-timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err || exit 2
-timeout -k 10 400 python bench.py --math fp32 --no-cpu-baseline > $O/bench_fp32.json 2> $O/bench_fp32.err || exit 3
-timeout -k 10 400 python bench.py --math fp16x2 --no-cpu-baseline > $O/bench_fp16x2.json 2> $O/bench_fp16x2.err || exit 3
-timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_args.json 2> $O/bench_driver_args.err || exit 3
+timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err || exit 2
+timeout -k 10 400 python bench.py --full --math fp32 --no-cpu-baseline > $O/bench_fp32.json 2> $O/bench_fp32.err || exit 3
+timeout -k 10 400 python bench.py --full --math fp16x2 --no-cpu-baseline > $O/bench_fp16x2.json 2> $O/bench_fp16x2.err || exit 3
+timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_args.json 2> $O/bench_driver_args.err || exit 3
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python3 $R/bench.py --steps 300 --warmup 100 --no-cpu-baseline > $O/prof_bench.log 2>&1 || exit 4
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python3 $R/bench.py --full --steps 300 --warmup 100 --no-cpu-baseline > $O/prof_bench.log 2>&1 || exit 4
 cd $R
 timeout -k 10 600 bash tools/pmc_fwd.sh > $O/pmc.log 2>&1 || exit 5
 rm -rf $O/pmc && mv $R/gpurun_out/pmc $O/pmc

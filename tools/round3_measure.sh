@@ -7,15 +7,15 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/round3
 mkdir -p $O
 cd $R
-timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err || exit 2
-timeout -k 10 400 python bench.py --math fp32 --no-cpu-baseline > $O/bench_fp32.json 2> $O/bench_fp32.err || exit 3
-timeout -k 10 400 python bench.py --math fp16x2 --no-cpu-baseline > $O/bench_fp16x2.json 2> $O/bench_fp16x2.err || exit 3
-timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_args.json 2> $O/bench_driver_args.err || exit 3
+timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err || exit 2
+timeout -k 10 400 python bench.py --full --math fp32 --no-cpu-baseline > $O/bench_fp32.json 2> $O/bench_fp32.err || exit 3
+timeout -k 10 400 python bench.py --full --math fp16x2 --no-cpu-baseline > $O/bench_fp16x2.json 2> $O/bench_fp16x2.err || exit 3
+timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_args.json 2> $O/bench_driver_args.err || exit 3
 # one GPU's shard of an N-GPU strong-scaling step + the kernel trace of the N = 8 shard
 for n in 8 4 2; do timeout -k 10 200 python bench.py --shard-of $n > $O/shard_of_$n.json 2> $O/shard_of_$n.err || exit 3; done
 timeout -k 10 200 python tools/shard_times.py > $O/shard_times.txt 2>&1 || exit 3
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python3 $R/bench.py --steps 300 --warmup 100 --no-cpu-baseline > $O/prof_bench.log 2>&1 || exit 4
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python3 $R/bench.py --full --steps 300 --warmup 100 --no-cpu-baseline > $O/prof_bench.log 2>&1 || exit 4
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_shard8 -o shard8 -- python3 $R/bench.py --shard-of 8 --steps 300 --warmup 100 > $O/prof_shard8.log 2>&1 || exit 4
 cd $R
 timeout -k 10 600 bash tools/pmc_fwd.sh > $O/pmc.log 2>&1 || exit 5
