@@ -130,6 +130,21 @@ size_t lsnf_prepare_scratch_bytes(int nz, int width, int depth);
 int lsnf_prepare(const float* const* params_host, int nz, int width, int depth, int coupling,
                  float* plan, void* scratch, void* stream);
 
+/* ---- data-dependent actnorm init: replaces `_netF.forward(z, objective, init=True)`'s parameter writes ---------
+ * (actnorm_center / actnorm_scale with init=True, model.py:238-241,253-262, threaded through revnet2d_step.forward
+ * model.py:389-422 and fc.forward model.py:324-331; Glow's initialisation).  For block k in order, on that block's input
+ * (z_in for k = 0, else block k-1's output under its NEW parameters): block actnorm b := -mean x, logs := log(1 / (sqrt(
+ * mean (x+b)^2) + 1e-6)) / 3; then the same for fc_1.actnorm on y[:, :nz/2] @ fc_1.w and for fc_2.actnorm on
+ * relu(fc_1 actnorm) @ fc_2.w.  Writes tensors 0, 1, 4, 5, 7, 8 of every block IN PLACE (params_host: same order as
+ * lsnf_prepare's array); reads the other six.  fp32 products (FMA), fp64 batch statistics from per-workgroup partial sums
+ * reduced in a fixed order (no atomics): bit-for-bit reproducible, and independent of the two tuning knobs and of the
+ * actnorm values the call starts from.  B >= 1 (B = 1 gives b = -z, logs = log(1e6)/3).
+ * workspace: device, 16-byte aligned, lsnf_actnorm_init_workspace_bytes() bytes (0 on bad geometry or B < 1).
+ * Plans prepared before the call are stale afterwards: run lsnf_prepare again. */
+size_t lsnf_actnorm_init_workspace_bytes(int nz, int width, int depth, int coupling, int B);
+int lsnf_actnorm_init(float* const* params_host, int nz, int width, int depth, int coupling, int B,
+                      const float* z_in, void* workspace, void* stream);
+
 /* ---- forward: replaces `_netF.forward(z, objective)` (model.py:473-483) -----------------
  * Runs blocks [first_block, first_block+n_blocks) of the stack (model.py:357-360; one block =
  * revnet2d_step.forward model.py:391-422) on B rows in ONE launch.

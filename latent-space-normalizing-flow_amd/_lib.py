@@ -30,6 +30,8 @@ _SIGNATURES = {
     "lsnf_plan_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
     "lsnf_prepare_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
     "lsnf_prepare": (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "lsnf_actnorm_init_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "lsnf_actnorm_init": (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "lsnf_forward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lsnf_params_fast_path": (c_int, []),

@@ -89,6 +89,9 @@ hipError_t lsnf_launch_backward_params(const LsnfGeo& g, const float* plan, cons
                                        const float* z_saved, const float* g_z1, const float* g_logdet, int ll_mode,
                                        float ll_scale, float* g_z_in, float* workspace, int vec4, int small_batch,
                                        hipStream_t stream, const float* act_saved);
+size_t lsnf_init_workspace_bytes(const LsnfGeo& g, int B);
+hipError_t lsnf_launch_actnorm_init(const LsnfGeo& g, float* const* params_host, int B, const float* z_in, void* workspace,
+                                    hipStream_t stream);
 
 namespace {
 thread_local char g_err[512] = "";
@@ -222,6 +225,29 @@ int lsnf_prepare(const float* const* params_host, int nz, int width, int depth, 
                         i / LSNF_PARAMS_PER_BLOCK, i % LSNF_PARAMS_PER_BLOCK);
     hipError_t e = lsnf_launch_prepare(g, params_host, plan, scratch, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "lsnf_prepare launch");
+    return LSNF_OK;
+}
+
+size_t lsnf_actnorm_init_workspace_bytes(int nz, int width, int depth, int coupling, int B) {
+    LsnfGeo g;
+    if (lsnf_geo_init(&g, nz, width, depth, coupling) || B < 1 || B > (1 << 28)) return 0;
+    return lsnf_init_workspace_bytes(g, B);
+}
+
+int lsnf_actnorm_init(float* const* params_host, int nz, int width, int depth, int coupling, int B, const float* z_in,
+                      void* workspace, void* stream) {
+    LsnfGeo g;
+    if (int rc = geo_or_fail(&g, nz, width, depth, coupling)) return rc;
+    if (B < 1 || B > (1 << 28)) return fail(LSNF_E_ARG, "lsnf_actnorm_init: B=%d out of range", B);
+    if (!params_host || !z_in || !workspace) return fail(LSNF_E_ARG, "lsnf_actnorm_init: NULL argument");
+    if (!aligned16(workspace)) return fail(LSNF_E_ARG, "lsnf_actnorm_init: workspace must be 16-byte aligned");
+    if (!aligned4(z_in)) return fail(LSNF_E_ARG, "lsnf_actnorm_init: z_in must be 4-byte aligned");
+    for (int i = 0; i < depth * LSNF_PARAMS_PER_BLOCK; ++i)
+        if (!params_host[i] || !aligned4(params_host[i]))
+            return fail(LSNF_E_ARG, "lsnf_actnorm_init: parameter pointer %d (block %d, slot %d) is NULL or misaligned", i,
+                        i / LSNF_PARAMS_PER_BLOCK, i % LSNF_PARAMS_PER_BLOCK);
+    hipError_t e = lsnf_launch_actnorm_init(g, params_host, B, z_in, workspace, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "lsnf_actnorm_init launch");
     return LSNF_OK;
 }
 

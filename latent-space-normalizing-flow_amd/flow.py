@@ -119,6 +119,68 @@ def prepare(params: Sequence[torch.Tensor], nz: int, width: int, depth: int, cou
     return plan
 
 
+def _param_shapes(nz: int, width: int, coupling: int) -> List[Tuple[int, ...]]:
+    """Shapes of one block's 12 live tensors as the reference registers them (vectors are (1, n))."""
+    half = nz // 2
+    n_out = nz if coupling == 1 else half
+    return [(1, nz), (1, nz), (nz, nz), (half, width), (1, width), (1, width), (width, width), (1, width), (1, width),
+            (width, n_out), (1, n_out), (1, n_out)]
+
+
+def actnorm_init_workspace_bytes(nz: int, width: int, depth: int, coupling: int, B: int) -> int:
+    """Bytes of device workspace `actnorm_init` needs (0 on an unsupported geometry or B < 1)."""
+    return int(_lib.load().lsnf_actnorm_init_workspace_bytes(int(nz), int(width), int(depth), int(coupling), int(B)))
+
+
+def actnorm_init(params: Sequence[torch.Tensor], z: torch.Tensor, nz: int, width: int, depth: int, coupling: int = 1,
+                 workspace: Optional[torch.Tensor] = None) -> None:
+    """Data-dependent actnorm init (reference `_netF.forward(z, objective, init=True)`, model.py:238-241,253-262): fits
+    every block's actnorm and its two fc actnorms to the batch z, in place -- tensors 0, 1, 4, 5, 7, 8 of each block
+    (BLOCK_PARAM_KEYS order) are overwritten, the other six are read.  Asynchronous on the current stream.  Plans
+    prepared from these tensors are stale afterwards (`prepare` again).
+    workspace: None (allocated here) or a device buffer of at least `actnorm_init_workspace_bytes()` bytes.
+    Every argument is checked before anything is launched; a bad one raises LsnfError."""
+    lib = _lib.load()
+    nz, width, depth, coupling = int(nz), int(width), int(depth), int(coupling)
+    need = lib.lsnf_actnorm_init_workspace_bytes(nz, width, depth, coupling, 1)
+    if need == 0:
+        raise LsnfError(f"unsupported geometry nz={nz} width={width} depth={depth} coupling={coupling}")
+    _need_cuda(z, "z")
+    if z.dim() != 2 or z.shape[1] != nz:
+        raise LsnfError(f"z must be (B, {nz}), got {tuple(z.shape)}")
+    B = z.shape[0]
+    if B < 1:
+        raise LsnfError("actnorm_init needs a non-empty batch")
+    if len(params) != depth * LSNF_PARAMS_PER_BLOCK:
+        raise LsnfError(f"expected {depth * LSNF_PARAMS_PER_BLOCK} parameter tensors, got {len(params)}")
+    shapes = _param_shapes(nz, width, coupling)
+    for i, t in enumerate(params):
+        name = f"param[{i}] ({BLOCK_PARAM_KEYS[i % LSNF_PARAMS_PER_BLOCK]})"
+        _need_cuda(t, name)
+        if t.device != z.device:
+            raise LsnfError(f"{name} lives on {t.device}, z on {z.device}")
+        want = shapes[i % LSNF_PARAMS_PER_BLOCK]
+        if tuple(t.shape) != want:
+            raise LsnfError(f"{name} has shape {tuple(t.shape)}, expected {want}")
+    need = lib.lsnf_actnorm_init_workspace_bytes(nz, width, depth, coupling, B)
+    if workspace is None:
+        workspace = torch.empty((need + 15) // 16 * 4, dtype=torch.float32, device=z.device)
+    else:
+        if not workspace.is_cuda or workspace.device != z.device:
+            raise LsnfError(f"workspace must live on {z.device} (got {workspace.device})")
+        if not workspace.is_contiguous():
+            raise LsnfError("workspace must be contiguous")
+        if workspace.numel() * workspace.element_size() < need:
+            raise LsnfError(f"workspace has {workspace.numel() * workspace.element_size()} bytes, "
+                            f"lsnf_actnorm_init needs {need} (actnorm_init_workspace_bytes())")
+        if workspace.data_ptr() % 16:
+            raise LsnfError("workspace must be 16-byte aligned")
+    arr = (ctypes.c_void_p * len(params))(*[t.data_ptr() for t in params])
+    with torch.cuda.device(z.device):
+        rc = lib.lsnf_actnorm_init(arr, nz, width, depth, coupling, B, _ptr(z), _ptr(workspace), _stream_ptr(z.device))
+    _lib.check(rc, "lsnf_actnorm_init")
+
+
 def params_from_state_dict(sd, depth: int, device=None) -> List[torch.Tensor]:
     """Pick the 12 live tensors per block out of a reference-keyed state_dict."""
     out = []

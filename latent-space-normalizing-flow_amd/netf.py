@@ -246,9 +246,8 @@ class _netF(nn.Module):
 
     # ---- reference forward signature (model.py:473) ---------------------------------------------
     def forward(self, z, objective, init=False, reverse=False, eps=None, eps_std=None, z2_s=None, return_obj=False):
-        if init:
-            raise NotImplementedError("data-dependent actnorm init (init=True) is never used by the reference's "
-                                      "train.py (all call sites pass init=False) and is not implemented")
+        if init and not reverse and not (z.is_cuda and all(p.is_cuda for p in self._param_list())):
+            raise NotImplementedError("data-dependent init (init=True) has no CPU path: move the module and z to the GPU")
         if z.dim() != 2:
             raise ValueError(f"z must be (B, nz); got shape {tuple(z.shape)} (note: the reference's "
                              f"torch.squeeze(z) call site breaks for B == 1, train.py:316)")
@@ -256,6 +255,15 @@ class _netF(nn.Module):
         objective = objective.contiguous()
         if not reverse:
             params = self._param_list()
+            if init:      # model.py:238-241,253-262: fit the actnorms to this batch, then the plain forward with the new values
+                if z.shape[0] == 0:
+                    raise LsnfError("data-dependent init needs a non-empty batch")
+                flow.actnorm_init([p.detach() for p in params], z.detach(), self.nz, self.hps.f_width, self.hps.f_depth,
+                                  self.hps.f_flow_coupling)
+                # the kernels wrote through raw pointers: bump the version counters so that the cached plan is re-derived
+                # and a graph recorded before this call refuses to back-propagate (_current_key)
+                written = [p for i, p in enumerate(params) if i % flow.LSNF_PARAMS_PER_BLOCK in (0, 1, 4, 5, 7, 8)]
+                torch.autograd.graph.increment_version(written)
             if torch.is_grad_enabled() and (z.requires_grad or objective.requires_grad or
                                             any(p.requires_grad for p in params)):
                 holder = _Upstream()
