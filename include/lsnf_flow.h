@@ -98,8 +98,7 @@ int lsnf_set_small_batch_max(int rows);
  *                      computation's are.  In-place calls (z_out == z_in) and calls with in-kernel batch sums (`stats`)
  *                      run LSNF_MATH_BF16X3 directly.  Every other kernel (latency kernels, backward) as LSNF_MATH_BF16X3.
  * mode < 0 only queries.  Returns the previous mode (default LSNF_MATH_DEFAULT, or the LSNF_MATH environment
- * variable "fp32" / "bf16x3" / "bf16x3_phased" / "fp16x2").  (Values 2 and 4 -- the same scheme on v_mfma_f32_32x32x16_bf16, phase-separated /
- * software-pipelined, both measured slower -- exist only in research builds, -DLSNF_EXPERIMENTAL_KERNELS; refused otherwise.) */
+ * variable "fp32" / "bf16x3" / "bf16x3_phased" / "fp16x2").  Other values are refused. */
 #define LSNF_MATH_FP32 0
 #define LSNF_MATH_BF16X3 1
 #define LSNF_MATH_FP16X2 3

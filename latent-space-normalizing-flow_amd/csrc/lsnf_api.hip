@@ -15,80 +15,77 @@
 #include "../../include/lsnf_flow.h"
 #include "lsnf_layout.h"
 
-// Research builds (-DLSNF_EXPERIMENTAL_KERNELS) also carry the bf16x3 scheme on v_mfma_f32_32x32x16_bf16 -- phase-separated (2)
-// and software-pipelined (4) -- both measured slower than the 16x16x32 kernels (profiles/HISTORY.md); not part of the ABI.
-#define LSNF_MATH_X_BF16X3_32 2
-#define LSNF_MATH_X_BF16X3_PIPE 4
-#ifdef LSNF_EXPERIMENTAL_KERNELS
-#define LSNF_HAVE_X 1
-#else
-#define LSNF_HAVE_X 0
-#endif
-
-// kernel launchers (other translation units)
+// kernel launchers (other translation units) and the predicates of what each takes (pure host functions, no HIP calls)
 hipError_t lsnf_launch_prepare(const LsnfGeo& g, const float* const* params_host, float* plan, void* scratch, hipStream_t stream);
 size_t lsnf_prep_scratch_bytes(int nz, int depth);
 hipError_t lsnf_launch_forward(const LsnfGeo& g, const float* plan, int first_block, int n_blocks, int B,
                                const float* z_in, const float* objective, float* z_out, float* logdet_out,
                                float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4,
                                hipStream_t stream);
+bool lsnf_forward3_covers(const LsnfGeo& g, int n_blocks, bool stats, bool fixup);
 hipError_t lsnf_launch_forward3(const LsnfGeo& g, const float* plan, int first_block, int n_blocks, int B,
                                 const float* z_in, const float* objective, float* z_out, float* logdet_out,
                                 float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4,
-                                int shape16, int fixup, hipStream_t stream, float* hdump = nullptr, int hdump_tiled = 0);
+                                int fixup, hipStream_t stream, float* hdump = nullptr, int hdump_tiled = 0);
+bool lsnf_forward3q_covers(const LsnfGeo& g, int first_block, int n_blocks, int B, int vec4, const float* z_out,
+                           const float* z_saved, const float* act_saved, const float* hdump, int hdump_tiled);
 hipError_t lsnf_launch_forward3q(const LsnfGeo& g, const float* plan, int first_block, int n_blocks, int B,
                                  const float* z_in, const float* objective, float* z_out, float* logdet_out,
                                  float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4, hipStream_t stream,
                                  float* hdump = nullptr, int hdump_tiled = 0);
-hipError_t lsnf_launch_forward3p(const LsnfGeo& g, const float* plan, int first_block, int n_blocks, int B,
-                                 const float* z_in, const float* objective, float* z_out, float* logdet_out,
-                                 float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4, hipStream_t stream);
+bool lsnf_forward2h_covers(const LsnfGeo& g, int n_blocks, bool stats, bool fixup);
 hipError_t lsnf_launch_forward2h(const LsnfGeo& g, const float* plan, int first_block, int n_blocks, int B,
                                  const float* z_in, const float* objective, float* z_out, float* logdet_out,
                                  float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4,
-                                 int shape16, int fixup, hipStream_t stream, float* hdump = nullptr, int hdump_tiled = 0);
+                                 int fixup, hipStream_t stream, float* hdump = nullptr, int hdump_tiled = 0);
+int lsnf_small3_forward_st(const LsnfGeo& g, int n_blocks, int B, bool extras);
 hipError_t lsnf_launch_small3_forward(const LsnfGeo& g, const float* plan, int first_block, int n_blocks, int B,
                                       const float* z_in, const float* objective, float* z_out, float* logdet_out,
-                                      float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4,
-                                      hipStream_t stream, float* hdump = nullptr);
+                                      float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4, int st,
+                                      hipStream_t stream, float* hdump);
 hipError_t lsnf_launch_small3_restash(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
                                       float* act_saved, int vec4, hipStream_t stream);
+bool lsnf_small_forward_covers(const LsnfGeo& g, int n_blocks);
 hipError_t lsnf_launch_small_forward(const LsnfGeo& g, const float* plan, int first_block, int n_blocks, int B,
                                      const float* z_in, const float* objective, float* z_out, float* logdet_out,
                                      float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4,
                                      hipStream_t stream);
 hipError_t lsnf_launch_reverse(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
                                float* z_out, float* objective_out, int vec4, hipStream_t stream);
+int lsnf_small3_reverse_st(const LsnfGeo& g, int B);
+hipError_t lsnf_launch_small3_reverse(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
+                                      float* z_out, float* objective_out, int vec4, int st, hipStream_t stream);
+bool lsnf_reverse3_covers(const LsnfGeo& g);
+hipError_t lsnf_launch_reverse3(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
+                                float* z_out, float* objective_out, int vec4, int fixup, hipStream_t stream);
+bool lsnf_reverse2h_covers(const LsnfGeo& g);
+hipError_t lsnf_launch_reverse2h(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
+                                 float* z_out, float* objective_out, int vec4, int fixup, hipStream_t stream);
+bool lsnf_small_reverse_covers(const LsnfGeo& g);
+hipError_t lsnf_launch_small_reverse(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
+                                     float* z_out, float* objective_out, int vec4, hipStream_t stream);
 hipError_t lsnf_launch_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
                                   const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
                                   float* g_z_in, float* dump, float* gl_total, int vec4, hipStream_t stream,
-                                  const LsnfLangevinArgs* lv = nullptr, const float* act_saved = nullptr);
-hipError_t lsnf_launch_small3_reverse(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                                      float* z_out, float* objective_out, int vec4, hipStream_t stream);
-hipError_t lsnf_launch_reverse3(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                                float* z_out, float* objective_out, int vec4, int fixup, hipStream_t stream);
-hipError_t lsnf_launch_reverse2h(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                                 float* z_out, float* objective_out, int vec4, int fixup, hipStream_t stream);
-hipError_t lsnf_launch_small_reverse(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                                     float* z_out, float* objective_out, int vec4, hipStream_t stream);
+                                  const LsnfLangevinArgs* lv, const float* act_saved);
+bool lsnf_small_backward_covers(const LsnfGeo& g);
 hipError_t lsnf_launch_small_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
                                         const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale, float* g_z_in,
                                         int vec4, hipStream_t stream, const LsnfLangevinArgs* lv, const float* act_saved,
-                                        float* dump = nullptr, float* gl_total = nullptr);
+                                        float* dump, float* gl_total);
+int lsnf_small3_backward_st(const LsnfGeo& g, int B);
 hipError_t lsnf_launch_small3_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
                                          const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode,
-                                         float ll_scale, float* g_z_in, int vec4, hipStream_t stream, const LsnfLangevinArgs* lv,
-                                         float* dump = nullptr, float* gl_total = nullptr);
+                                         float ll_scale, float* g_z_in, int vec4, int st, hipStream_t stream,
+                                         const LsnfLangevinArgs* lv, float* dump, float* gl_total);
 hipError_t lsnf_launch_backward3_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
                                    const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
                                    float* g_z_in, int vec4, hipStream_t stream, const LsnfLangevinArgs* lv,
-                                   float* dump = nullptr, float* gl_total = nullptr, int dump_tiled = 0);
+                                   float* dump, float* gl_total, int dump_tiled);
 bool lsnf_contract_x3_covers(int B, int nz, int half, int width, const float* z_in, const float* z_out, const float* z_saved);
-hipError_t lsnf_launch_backward_params(const LsnfGeo& g, const float* plan, const float* const* params_host,
+hipError_t lsnf_launch_params_contract(const LsnfGeo& g, const float* plan, const float* const* params_host,
                                        float* const* grads_host, int B, const float* z_in, const float* z_out,
-                                       const float* z_saved, const float* g_z1, const float* g_logdet, int ll_mode,
-                                       float ll_scale, float* g_z_in, float* workspace, int vec4, int small_batch,
-                                       hipStream_t stream, const float* act_saved);
+                                       const float* z_saved, float* workspace, int contraction, int g_tiled, hipStream_t stream);
 size_t lsnf_init_workspace_bytes(const LsnfGeo& g, int B);
 hipError_t lsnf_launch_actnorm_init(const LsnfGeo& g, float* const* params_host, int B, const float* z_in, void* workspace,
                                     hipStream_t stream);
@@ -127,9 +124,7 @@ int math_mode() {
     if (m < 0) {
         const char* e = getenv("LSNF_MATH");
         m = (e && !strcmp(e, "bf16x3")) ? LSNF_MATH_BF16X3 : (e && !strcmp(e, "bf16x3_phased")) ? LSNF_MATH_BF16X3_PHASED
-          : (e && !strcmp(e, "fp16x2")) ? LSNF_MATH_FP16X2 : (e && !strcmp(e, "fp32")) ? LSNF_MATH_FP32
-          : (LSNF_HAVE_X && e && !strcmp(e, "bf16x3_32")) ? LSNF_MATH_X_BF16X3_32
-          : (LSNF_HAVE_X && e && !strcmp(e, "bf16x3_pipe")) ? LSNF_MATH_X_BF16X3_PIPE : LSNF_MATH_DEFAULT;
+          : (e && !strcmp(e, "fp16x2")) ? LSNF_MATH_FP16X2 : (e && !strcmp(e, "fp32")) ? LSNF_MATH_FP32 : LSNF_MATH_DEFAULT;
         int expected = -1;
         g_math.compare_exchange_strong(expected, m, std::memory_order_relaxed);
         m = g_math.load(std::memory_order_relaxed);
@@ -160,7 +155,7 @@ int small_batch_max() {
     return math_mode() == LSNF_MATH_FP16X2 ? 12288 : LSNF_SMALL_MAX_DEFAULT;
 }
 // modes whose latency / backward / reverse kernels are the bf16x3 "L16" ones
-bool l16_math() { const int m = math_mode(); return m == LSNF_MATH_BF16X3 || m == LSNF_MATH_FP16X2 || m == LSNF_MATH_X_BF16X3_PIPE || m == LSNF_MATH_BF16X3_PHASED; }
+bool l16_math() { const int m = math_mode(); return m == LSNF_MATH_BF16X3 || m == LSNF_MATH_FP16X2 || m == LSNF_MATH_BF16X3_PHASED; }
 
 int geo_or_fail(LsnfGeo* g, int nz, int width, int depth, int coupling) {
     if (lsnf_geo_init(g, nz, width, depth, coupling))
@@ -168,6 +163,128 @@ int geo_or_fail(LsnfGeo* g, int nz, int width, int depth, int coupling) {
                     "(need nz even in [2,128], width in [1,128], depth in [1,%d], coupling 0 or 1)",
                     nz, width, depth, coupling, LSNF_MAX_DEPTH);
     return 0;
+}
+
+// ---- kernel selection: each operation decides on the host, from the kernels' coverage predicates, which kernel(s) a call
+// runs, BEFORE anything is launched; the entry point then launches exactly that.  A launcher reached outside what it covers
+// is a selection bug and fails the call (LSNF_E_HIP, the kernel named in lsnf_last_error()); nothing falls through to another
+// kernel.
+enum Kernel {
+    K_NONE, K_FWD, K_FWD3, K_FWD3Q, K_FWD2H_FIXUP, K_SMALL_FWD, K_SMALL3_FWD,
+    K_REV, K_REV3, K_REV2H_FIXUP, K_SMALL_REV, K_SMALL3_REV,
+    K_BWD, K_BWD3, K_SMALL_BWD, K_SMALL3_BWD,
+};
+const char* const kKernelName[] = {
+    "no kernel takes this call", "lsnf_fwd_kernel", "lsnf_fwd3b_kernel", "lsnf_fwd3q_kernel",
+    "lsnf_fwd2h_kernel + lsnf_fwd3b_kernel fix-up", "lsnf_small_fwd_kernel", "lsnf_small3_fwd_kernel",
+    "lsnf_rev_kernel", "lsnf_rev3_kernel", "lsnf_rev2h_kernel + lsnf_rev3_kernel fix-up", "lsnf_small_rev_kernel",
+    "lsnf_small3_rev_kernel",
+    "lsnf_bwd_z_kernel", "lsnf_bwd3_kernel", "lsnf_small_bwd_kernel", "lsnf_small3_bwd_kernel",
+};
+struct Pick { Kernel k; int st = 0; };     // st: rows per workgroup / 16 of the small3 kernels
+
+int launch_fail(hipError_t e, const char* entry, Kernel k) {
+    if (k == K_NONE) return fail(LSNF_E_HIP, "%s: %s", entry, kKernelName[k]);
+    return fail(LSNF_E_HIP, "%s: %s: %s", entry, kKernelName[k], hipGetErrorString(e));
+}
+
+// Forward.  Up to small_max rows the latency kernels (the bf16-pipe one for the bf16x3 family, 16 x ST rows per workgroup; the
+// fp32-MFMA one, 32 rows, otherwise), above it the throughput kernels (weights shared through LDS):
+//  - fp16x2 (opt-in): two fp16 terms per operand, three MFMAs per product (lsnf_fwd2h.hip), followed by the bf16x3 kernel as a
+//    fix-up pass that recomputes the workgroups in which a wave met an operand outside fp16's range (the flag travels in
+//    logdet_out) and exits at once elsewhere.  Not for in-place calls (the fix-up re-reads the inputs) and not with in-kernel
+//    batch sums (a partial recomputation cannot repair them): those run the bf16x3 kernel directly;
+//  - bf16x3: the vector work software-pipelined under 16x16x32 MFMAs (lsnf_fwd3p.hip) where it applies;
+//  - the bf16x3 family: the error-free split on the bf16 matrix pipe (lsnf_fwd3.hip);
+//  - the fp32-MFMA kernel -- not with the parameter-gradient dump, which only the bf16 kernels write.
+Pick select_forward(const LsnfGeo& g, int first_block, int n_blocks, int B, int small_max, int vec4, const float* z_in,
+                    const float* objective, const float* z_out, const float* logdet_out, const float* z_saved,
+                    const float* act_saved, bool stats, const float* hdump, int hdump_tiled) {
+    const int math = math_mode();
+    if (B <= small_max) {
+        if (l16_math())
+            if (int st = lsnf_small3_forward_st(g, n_blocks, B, z_saved || act_saved || hdump)) return {K_SMALL3_FWD, st};
+        return {!hdump && lsnf_small_forward_covers(g, n_blocks) ? K_SMALL_FWD : K_NONE};
+    }
+    if (math == LSNF_MATH_FP16X2 && !stats && z_in != z_out && (objective == nullptr || objective != logdet_out) &&
+        lsnf_forward2h_covers(g, n_blocks, false, false) && lsnf_forward3_covers(g, n_blocks, false, true))
+        return {K_FWD2H_FIXUP};
+    if (math == LSNF_MATH_BF16X3 && (!hdump || hdump_tiled) &&
+        lsnf_forward3q_covers(g, first_block, n_blocks, B, vec4, z_out, z_saved, act_saved, hdump, hdump_tiled))
+        return {K_FWD3Q};
+    if (l16_math() && lsnf_forward3_covers(g, n_blocks, stats, false)) return {K_FWD3};
+    return {hdump ? K_NONE : K_FWD};
+}
+
+// Reverse (sampling).  It neither writes nor reads a stash, so under the automatic threshold the bf16x3 family takes its own
+// crossover: the 64-row latency form is the faster one up to ~28 K rows (profiles/r03_latency_reverse.txt: 34.2 vs 57.9 us at
+// 16 384, 67.3 vs 60.6 at 32 768); above it the throughput kernel (lsnf_rev3.hip; fp16x2: lsnf_rev2h.hip + the bf16x3 fix-up
+// pass, as in the forward).  The latency form also stands in where the throughput form does not fit (it is faster than the
+// fp32 throughput reverse), and the throughput form where the latency form does not.  Otherwise the fp32-MFMA kernels of the
+// batch size's family.
+Pick select_reverse(const LsnfGeo& g, int B, const float* z_in, const float* objective, const float* z_out,
+                    const float* objective_out) {
+    const int small_max = small_batch_max();
+    if (l16_math()) {
+        const int math = math_mode();
+        int lat_max = small_max;
+        if (small_batch_setting() == LSNF_SMALL_BATCH_AUTO && math != LSNF_MATH_FP16X2 && lat_max < 24576) lat_max = 24576;
+        if (B > lat_max) {
+            if (math == LSNF_MATH_FP16X2 && z_in != z_out && (objective == nullptr || objective != objective_out) &&
+                lsnf_reverse2h_covers(g) && lsnf_reverse3_covers(g))
+                return {K_REV2H_FIXUP};
+            if (lsnf_reverse3_covers(g)) return {K_REV3};
+        }
+        if (lat_max > 0)
+            if (int st = lsnf_small3_reverse_st(g, B)) return {K_SMALL3_REV, st};
+        if (B > small_max && B <= lat_max && lsnf_reverse3_covers(g)) return {K_REV3};
+    }
+    if (B > small_max) return {K_REV};
+    return {lsnf_small_reverse_covers(g) ? K_SMALL_REV : K_NONE};
+}
+
+// Backward (lsnf_backward_z, lsnf_langevin_step, lsnf_backward_params): from the activation stash on the bf16 matrix pipe when
+// the call brings one under a bf16x3-family mode (lsnf_small3_bwd.hip / lsnf_bwd3.hip: both take every such call), otherwise
+// the recomputing fp32-MFMA kernels -- the latency or the throughput family by the common threshold, so that the family that
+// wrote a stash is the family that reads it.
+Pick select_backward(const LsnfGeo& g, int B, const float* act_saved) {
+    const bool small = B <= small_batch_max();
+    if (act_saved && l16_math()) return small ? Pick{K_SMALL3_BWD, lsnf_small3_backward_st(g, B)} : Pick{K_BWD3};
+    if (!small) return {K_BWD};
+    return {lsnf_small_backward_covers(g) ? K_SMALL_BWD : K_NONE};
+}
+hipError_t launch_backward(Pick p, const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
+                           const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
+                           float* g_z_in, int vec4, hipStream_t stream, const LsnfLangevinArgs* lv,
+                           float* dump = nullptr, float* gl_total = nullptr, int dump_tiled = 0) {
+    switch (p.k) {
+    case K_SMALL3_BWD:
+        return lsnf_launch_small3_backward_z(g, plan, B, z_out, z_saved, act_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in,
+                                             vec4, p.st, stream, lv, dump, gl_total);
+    case K_BWD3:
+        return lsnf_launch_backward3_z(g, plan, B, z_out, z_saved, act_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in, vec4,
+                                       stream, lv, dump, gl_total, dump_tiled);
+    case K_SMALL_BWD:
+        return lsnf_launch_small_backward_z(g, plan, B, z_out, z_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in, vec4,
+                                            stream, lv, act_saved, dump, gl_total);
+    default:
+        return lsnf_launch_backward_z(g, plan, B, z_out, z_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in, dump, gl_total,
+                                      vec4, stream, lv, act_saved);
+    }
+}
+
+// Batch contraction of the parameter gradients (LsnfContraction): on the bf16 matrix pipe where lsnf_params3.hip covers the
+// call (use_x3); from 4 096 rows the fp32-MFMA kernel through LDS, with the widest row loads the rows allow -- every row the
+// tasks read starts 16-byte aligned iff nz, width and half are multiples of 4 (z tensors: the caller's alignment is folded
+// into vec4; the dump rows start at 16-byte aligned offsets of the 16-byte aligned workspace); the plain kernel below that
+// (and with LSNF_TN_PLAIN set: experiment knob of tools/tn_probe.py).
+int select_contraction(const LsnfGeo& g, int B, bool use_x3, int vec4) {
+    static const bool knob_plain = getenv("LSNF_TN_PLAIN") != nullptr;
+    if (use_x3) return LSNF_CONTRACT_X3;
+    if (B < 4096 || knob_plain) return LSNF_CONTRACT_PLAIN;
+    if (vec4 == 4 && g.nz % 4 == 0 && g.width % 4 == 0 && g.half % 4 == 0) return LSNF_CONTRACT_LDS4;
+    if (vec4 >= 2 && g.nz % 2 == 0 && g.width % 2 == 0 && g.half % 2 == 0) return LSNF_CONTRACT_LDS2;
+    return LSNF_CONTRACT_LDS1;
 }
 }  // namespace
 
@@ -183,8 +300,7 @@ int lsnf_set_small_batch_max(int rows) {
 }
 int lsnf_set_math_mode(int mode) {
     const int prev = math_mode();
-    if (mode == LSNF_MATH_FP32 || mode == LSNF_MATH_BF16X3 || mode == LSNF_MATH_FP16X2 || mode == LSNF_MATH_BF16X3_PHASED ||
-        (LSNF_HAVE_X && (mode == LSNF_MATH_X_BF16X3_32 || mode == LSNF_MATH_X_BF16X3_PIPE)))
+    if (mode == LSNF_MATH_FP32 || mode == LSNF_MATH_BF16X3 || mode == LSNF_MATH_FP16X2 || mode == LSNF_MATH_BF16X3_PHASED)
         g_math.store(mode, std::memory_order_relaxed);
     return prev;
 }
@@ -270,7 +386,6 @@ int lsnf_forward(const float* plan, int nz, int width, int depth, int coupling, 
     if (!aligned16(plan)) return fail(LSNF_E_ARG, "lsnf_forward: plan must be 16-byte aligned");
     if (!aligned4(z_in) || !aligned4(z_out) || !aligned4(logdet_out) || !aligned4(objective) || !aligned4(ll_out) || !aligned4(z_saved))
         return fail(LSNF_E_ARG, "lsnf_forward: tensors must be 4-byte aligned");
-    if (B == 0) return LSNF_OK;
     const int vec4 = row_vector_width(g, {z_in, z_out, z_saved});
     if (act_saved && !aligned16(act_saved)) return fail(LSNF_E_ARG, "lsnf_forward: act_saved must be 16-byte aligned");
     if (stats && (reinterpret_cast<uintptr_t>(stats) & 7u)) return fail(LSNF_E_ARG, "lsnf_forward: stats must be 8-byte aligned");
@@ -282,11 +397,7 @@ int lsnf_forward(const float* plan, int nz, int width, int depth, int coupling, 
         if (!aligned16(params_workspace)) return fail(LSNF_E_ARG, "lsnf_forward: params_workspace must be 16-byte aligned");
         hdump = params_workspace + 4 + (size_t)depth * lsnf_fold_layout(nz, width).per_block;
     }
-    // batch-size dispatch: latency kernel (32 rows per workgroup, stages split over the 4 waves) below the
-    // crossover, throughput kernel (128 rows per workgroup, weights shared through LDS) above it
-    hipError_t e;
     const int math = math_mode();
-    const bool split = math == LSNF_MATH_BF16X3 || math == LSNF_MATH_X_BF16X3_32 || math == LSNF_MATH_X_BF16X3_PIPE || math == LSNF_MATH_BF16X3_PHASED;
     // Calls without a stash that the software-pipelined forward covers cross over at 8 192 rows, not at the common threshold:
     // the latency kernel puts 16 / 32 rows on a workgroup up to 4 096 / 8 192 rows (one round of <= 256 workgroups that each
     // stream the weights once: 14.1 / 20.1 us), lsnf_fwd3q_kernel in its 16-rows-per-wave form takes 30.5 us up to 16 384 rows,
@@ -301,49 +412,48 @@ int lsnf_forward(const float* plan, int nz, int width, int depth, int coupling, 
     // tag word which form h1 / h2 have -- tiled (whole 1 KiB stores) when the bf16x3 throughput forward writes them, row-major otherwise
     int hdump_tiled = 0;
     if (hdump && B >= LSNF_X3_MIN_ROWS) {
-        hdump_tiled = (B > small_max && split && math != LSNF_MATH_X_BF16X3_32 && lsnf_dump_can_tile(nz, width) &&
+        hdump_tiled = (B > small_max && (math == LSNF_MATH_BF16X3 || math == LSNF_MATH_BF16X3_PHASED) && lsnf_dump_can_tile(nz, width) &&
                        lsnf_contract_x3_covers(B, nz, g.half, width, z_in, z_out, z_saved)) ? 1 : 0;
         if (hipMemsetD32Async((hipDeviceptr_t)(params_workspace + lsnf_params_workspace_tag(nz, width, depth, B)), hdump_tiled, 1,
                               (hipStream_t)stream) != hipSuccess)
             return fail(LSNF_E_HIP, "lsnf_forward: hipMemsetD32Async(workspace tag) failed");
     }
-    if (B <= small_max) {
-        e = hipErrorInvalidValue;
-        if (l16_math())                           // latency forward on the bf16 pipe: 16-sample workgroups (lsnf_small3_fwd.hip)
-            e = lsnf_launch_small3_forward(g, plan, first_block, n_blocks, B, z_in, objective, z_out, logdet_out, ll_out,
-                                           z_saved, act_saved, stats, vec4, (hipStream_t)stream, hdump);
-        if (e == hipErrorInvalidValue && !hdump)
-            e = lsnf_launch_small_forward(g, plan, first_block, n_blocks, B, z_in, objective, z_out, logdet_out, ll_out,
-                                          z_saved, act_saved, stats, vec4, (hipStream_t)stream);
-    } else {
-        e = hipErrorInvalidValue;
-        // fp16x2 (opt-in): two fp16 terms per operand, three MFMAs per product (lsnf_fwd2h.hip), followed by the bf16x3 kernel
-        // as a fix-up pass that recomputes the workgroups in which a wave met an operand outside fp16's range (the flag
-        // travels in logdet_out) and exits at once elsewhere.  Not for in-place calls (the fix-up re-reads the inputs) and
-        // not with in-kernel batch sums (a partial recomputation cannot repair them): those run bf16x3 directly.
-        const bool fp16_ok = math == LSNF_MATH_FP16X2 && stats == nullptr && z_in != z_out &&
-                             (objective == nullptr || objective != logdet_out);
-        if (fp16_ok) {
-            e = lsnf_launch_forward2h(g, plan, first_block, n_blocks, B, z_in, objective, z_out, logdet_out, ll_out,
-                                      z_saved, act_saved, nullptr, vec4, 1, 0, (hipStream_t)stream, hdump);
-            if (e == hipSuccess)
-                e = lsnf_launch_forward3(g, plan, first_block, n_blocks, B, z_in, objective, z_out, logdet_out, ll_out,
-                                         z_saved, act_saved, nullptr, vec4, 1, /*fixup=*/1, (hipStream_t)stream, hdump);
-        }
-        if (math == LSNF_MATH_BF16X3 && (!hdump || hdump_tiled))   // vector work software-pipelined under 16x16x32 MFMAs (lsnf_fwd3p.hip, lsnf_fwd3q_kernel)
-            e = lsnf_launch_forward3q(g, plan, first_block, n_blocks, B, z_in, objective, z_out, logdet_out, ll_out,
-                                      z_saved, act_saved, stats, vec4, (hipStream_t)stream, hdump, hdump_tiled);
-        if (math == LSNF_MATH_X_BF16X3_PIPE && !hdump) // (research builds) the 32x32x16 kernel with its vector work pipelined under the MFMAs
-            e = lsnf_launch_forward3p(g, plan, first_block, n_blocks, B, z_in, objective, z_out, logdet_out, ll_out,
-                                      z_saved, act_saved, stats, vec4, (hipStream_t)stream);
-        if (e == hipErrorInvalidValue && (split || math == LSNF_MATH_FP16X2))   // error-free split on the bf16 matrix pipe (lsnf_fwd3.hip)
-            e = lsnf_launch_forward3(g, plan, first_block, n_blocks, B, z_in, objective, z_out, logdet_out, ll_out,
-                                     z_saved, act_saved, stats, vec4, math != LSNF_MATH_X_BF16X3_32, /*fixup=*/0, (hipStream_t)stream, hdump, hdump_tiled);
-        if (e == hipErrorInvalidValue && !hdump)  // fp32 MFMA kernel (also: stacks too deep for fwd3's LDS budget)
-            e = lsnf_launch_forward(g, plan, first_block, n_blocks, B, z_in, objective, z_out, logdet_out, ll_out,
-                                    z_saved, act_saved, stats, vec4, (hipStream_t)stream);
+    const Pick p = select_forward(g, first_block, n_blocks, B, small_max, vec4, z_in, objective, z_out, logdet_out, z_saved,
+                                  act_saved, stats != nullptr, hdump, hdump_tiled);
+    const hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSuccess;
+    switch (p.k) {
+    case K_SMALL3_FWD:
+        e = lsnf_launch_small3_forward(g, plan, first_block, n_blocks, B, z_in, objective, z_out, logdet_out, ll_out, z_saved,
+                                       act_saved, stats, vec4, p.st, st, hdump);
+        break;
+    case K_SMALL_FWD:
+        e = lsnf_launch_small_forward(g, plan, first_block, n_blocks, B, z_in, objective, z_out, logdet_out, ll_out, z_saved,
+                                      act_saved, stats, vec4, st);
+        break;
+    case K_FWD2H_FIXUP:
+        e = lsnf_launch_forward2h(g, plan, first_block, n_blocks, B, z_in, objective, z_out, logdet_out, ll_out, z_saved,
+                                  act_saved, nullptr, vec4, /*fixup=*/0, st, hdump);
+        if (e == hipSuccess)
+            e = lsnf_launch_forward3(g, plan, first_block, n_blocks, B, z_in, objective, z_out, logdet_out, ll_out, z_saved,
+                                     act_saved, nullptr, vec4, /*fixup=*/1, st, hdump);
+        break;
+    case K_FWD3Q:
+        e = lsnf_launch_forward3q(g, plan, first_block, n_blocks, B, z_in, objective, z_out, logdet_out, ll_out, z_saved,
+                                  act_saved, stats, vec4, st, hdump, hdump_tiled);
+        break;
+    case K_FWD3:
+        e = lsnf_launch_forward3(g, plan, first_block, n_blocks, B, z_in, objective, z_out, logdet_out, ll_out, z_saved,
+                                 act_saved, stats, vec4, /*fixup=*/0, st, hdump, hdump_tiled);
+        break;
+    case K_FWD:
+        e = lsnf_launch_forward(g, plan, first_block, n_blocks, B, z_in, objective, z_out, logdet_out, ll_out, z_saved,
+                                act_saved, stats, vec4, st);
+        break;
+    default:
+        break;
     }
-    if (e != hipSuccess) return hip_fail(e, "lsnf_forward launch");
+    if (p.k == K_NONE || e != hipSuccess) return launch_fail(e, "lsnf_forward", p.k);
     return LSNF_OK;
 }
 
@@ -379,33 +489,22 @@ int lsnf_reverse(const float* plan, int nz, int width, int depth, int coupling, 
     if (!aligned16(plan)) return fail(LSNF_E_ARG, "lsnf_reverse: plan must be 16-byte aligned");
     if (!aligned4(z_in) || !aligned4(z_out) || !aligned4(objective) || !aligned4(objective_out))
         return fail(LSNF_E_ARG, "lsnf_reverse: tensors must be 4-byte aligned");
-    if (B == 0) return LSNF_OK;
     const int vec4 = row_vector_width(g, {z_in, z_out});
-    hipError_t e = hipErrorInvalidValue;
-    if (l16_math()) {        // on the bf16 pipe: lsnf_small3_rev.hip / lsnf_rev3.hip
-        // the reverse neither writes nor reads a stash, so under the automatic threshold it takes its own crossover: the 64-row latency
-        // form is the faster one up to ~28 K rows (profiles/r03_latency_reverse.txt: 34.2 vs 57.9 us at 16 384, 67.3 vs 60.6 at 32 768)
-        int small_max = small_batch_max();
-        if (small_batch_setting() == LSNF_SMALL_BATCH_AUTO && math_mode() != LSNF_MATH_FP16X2 && small_max < 24576) small_max = 24576;
-        // fp16 two-term split (lsnf_rev2h.hip) + the bf16x3 kernel behind it as the early-exit fix-up pass, as in lsnf_forward
-        if (B > small_max && math_mode() == LSNF_MATH_FP16X2 && z_in != z_out && (objective == nullptr || objective != objective_out)) {
-            e = lsnf_launch_reverse2h(g, plan, B, z_in, objective, z_out, objective_out, vec4, 0, (hipStream_t)stream);
-            if (e == hipSuccess)
-                e = lsnf_launch_reverse3(g, plan, B, z_in, objective, z_out, objective_out, vec4, /*fixup=*/1, (hipStream_t)stream);
-        }
-        if (B > small_max && e == hipErrorInvalidValue)
-            e = lsnf_launch_reverse3(g, plan, B, z_in, objective, z_out, objective_out, vec4, /*fixup=*/0, (hipStream_t)stream);
-        // (the latency form is also faster than the fp32 throughput reverse where the bf16 throughput form does not fit)
-        if (e == hipErrorInvalidValue && small_max > 0)
-            e = lsnf_launch_small3_reverse(g, plan, B, z_in, objective, z_out, objective_out, vec4, (hipStream_t)stream);
-        if (e == hipErrorInvalidValue && B > small_batch_max() && B <= small_max)       // the latency form does not cover this stack
-            e = lsnf_launch_reverse3(g, plan, B, z_in, objective, z_out, objective_out, vec4, /*fixup=*/0, (hipStream_t)stream);
+    const Pick p = select_reverse(g, B, z_in, objective, z_out, objective_out);
+    const hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSuccess;
+    switch (p.k) {
+    case K_REV2H_FIXUP:
+        e = lsnf_launch_reverse2h(g, plan, B, z_in, objective, z_out, objective_out, vec4, /*fixup=*/0, st);
+        if (e == hipSuccess) e = lsnf_launch_reverse3(g, plan, B, z_in, objective, z_out, objective_out, vec4, /*fixup=*/1, st);
+        break;
+    case K_REV3: e = lsnf_launch_reverse3(g, plan, B, z_in, objective, z_out, objective_out, vec4, /*fixup=*/0, st); break;
+    case K_SMALL3_REV: e = lsnf_launch_small3_reverse(g, plan, B, z_in, objective, z_out, objective_out, vec4, p.st, st); break;
+    case K_SMALL_REV: e = lsnf_launch_small_reverse(g, plan, B, z_in, objective, z_out, objective_out, vec4, st); break;
+    case K_REV: e = lsnf_launch_reverse(g, plan, B, z_in, objective, z_out, objective_out, vec4, st); break;
+    default: break;
     }
-    if (e == hipErrorInvalidValue)      // not taken or not covered: the fp32-MFMA kernels of the batch size's family
-        e = (B <= small_batch_max())
-            ? lsnf_launch_small_reverse(g, plan, B, z_in, objective, z_out, objective_out, vec4, (hipStream_t)stream)
-            : lsnf_launch_reverse(g, plan, B, z_in, objective, z_out, objective_out, vec4, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "lsnf_reverse launch");
+    if (p.k == K_NONE || e != hipSuccess) return launch_fail(e, "lsnf_reverse", p.k);
     return LSNF_OK;
 }
 
@@ -420,23 +519,13 @@ int lsnf_backward_z(const float* plan, int nz, int width, int depth, int couplin
     if (!aligned16(plan)) return fail(LSNF_E_ARG, "lsnf_backward_z: plan must be 16-byte aligned");
     if (!aligned4(z_out) || !aligned4(z_saved) || !aligned4(g_z1) || !aligned4(g_logdet) || !aligned4(g_z_in))
         return fail(LSNF_E_ARG, "lsnf_backward_z: tensors must be 4-byte aligned");
-    if (B == 0) return LSNF_OK;
     const int vec4 = row_vector_width(g, {z_out, g_z_in, z_saved, g_z1});
     if (act_saved && !aligned16(act_saved)) return fail(LSNF_E_ARG, "lsnf_backward_z: act_saved must be 16-byte aligned");
-    hipError_t e = hipErrorInvalidValue;
-    if (B <= small_batch_max() && act_saved && l16_math())     // from the stash, on the bf16 pipe (lsnf_small3_bwd.hip)
-        e = lsnf_launch_small3_backward_z(g, plan, B, z_out, z_saved, act_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in,
-                                          vec4, (hipStream_t)stream, nullptr);
-    else if (act_saved && l16_math() && B > small_batch_max())          // throughput form (lsnf_bwd3.hip)
-        e = lsnf_launch_backward3_z(g, plan, B, z_out, z_saved, act_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in, vec4,
-                                    (hipStream_t)stream, nullptr);
-    if (e == hipErrorInvalidValue)      // not taken or not covered: the fp32-MFMA kernels of the batch size's family
-        e = (B <= small_batch_max())
-            ? lsnf_launch_small_backward_z(g, plan, B, z_out, z_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in, vec4,
-                                             (hipStream_t)stream, nullptr, act_saved)
-            : lsnf_launch_backward_z(g, plan, B, z_out, z_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in, nullptr,
-                                       nullptr, vec4, (hipStream_t)stream, nullptr, act_saved);
-    if (e != hipSuccess) return hip_fail(e, "lsnf_backward_z launch");
+    const Pick p = select_backward(g, B, act_saved);
+    const hipError_t e = p.k == K_NONE ? hipSuccess
+        : launch_backward(p, g, plan, B, z_out, z_saved, act_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in, vec4,
+                          (hipStream_t)stream, nullptr);
+    if (p.k == K_NONE || e != hipSuccess) return launch_fail(e, "lsnf_backward_z", p.k);
     return LSNF_OK;
 }
 
@@ -461,20 +550,11 @@ int lsnf_langevin_step(const float* plan, int nz, int width, int depth, int coup
     LsnfLangevinArgs lv = {z_cur, grad_g, noise, z_new, gf_norm, gg_norm, step_size,
                            rng ? LsnfRngArgs{rng->seed, rng->offset, rng->offset_dev, rng->row0, 1}
                                : LsnfRngArgs{0ull, 0ull, nullptr, 0ll, 0}};
-    hipError_t e = hipErrorInvalidValue;
-    if (B <= small_batch_max() && act_saved && l16_math())
-        e = lsnf_launch_small3_backward_z(g, plan, B, z_out, z_saved, act_saved, nullptr, nullptr, /*ll_mode=*/1,
-                                          /*ll_scale=*/-1.0f, nullptr, vec4, (hipStream_t)stream, &lv);
-    else if (act_saved && l16_math() && B > small_batch_max())
-        e = lsnf_launch_backward3_z(g, plan, B, z_out, z_saved, act_saved, nullptr, nullptr, /*ll_mode=*/1, /*ll_scale=*/-1.0f,
-                                    nullptr, vec4, (hipStream_t)stream, &lv);
-    if (e == hipErrorInvalidValue)      // not taken or not covered: the fp32-MFMA kernels of the batch size's family
-        e = (B <= small_batch_max())
-            ? lsnf_launch_small_backward_z(g, plan, B, z_out, z_saved, nullptr, nullptr, /*ll_mode=*/1, /*ll_scale=*/-1.0f,
-                                             nullptr, vec4, (hipStream_t)stream, &lv, act_saved)
-            : lsnf_launch_backward_z(g, plan, B, z_out, z_saved, nullptr, nullptr, /*ll_mode=*/1, /*ll_scale=*/-1.0f,
-                                       nullptr, nullptr, nullptr, vec4, (hipStream_t)stream, &lv, act_saved);
-    if (e != hipSuccess) return hip_fail(e, "lsnf_langevin_step launch");
+    const Pick p = select_backward(g, B, act_saved);
+    const hipError_t e = p.k == K_NONE ? hipSuccess
+        : launch_backward(p, g, plan, B, z_out, z_saved, act_saved, nullptr, nullptr, /*ll_mode=*/1, /*ll_scale=*/-1.0f,
+                          nullptr, vec4, (hipStream_t)stream, &lv);
+    if (p.k == K_NONE || e != hipSuccess) return launch_fail(e, "lsnf_langevin_step", p.k);
     return LSNF_OK;
 }
 
@@ -503,10 +583,31 @@ int lsnf_backward_params(const float* plan, const float* const* params_host, flo
     // (z_in too: the batch contraction of block 0 reads its rows with the same vector width)
     const int vec4 = row_vector_width(g, {z_in, z_out, g_z_in, z_saved, g_z1});
     if (act_saved && !aligned16(act_saved)) return fail(LSNF_E_ARG, "lsnf_backward_params: act_saved must be 16-byte aligned");
-    hipError_t e = lsnf_launch_backward_params(g, plan, params_host, grads_host, B, z_in, z_out, z_saved, g_z1, g_logdet,
-                                               ll_mode, ll_scale, g_z_in, workspace, vec4, B <= small_batch_max(),
-                                               (hipStream_t)stream, l16_math() ? act_saved : nullptr);
-    if (e != hipSuccess) return hip_fail(e, "lsnf_backward_params launch");
+    // Fast path (act_saved given, bf16x3-family math): the forward of this evaluation kept the activation stash and wrote h1 / h2
+    // into this workspace's dump (lsnf_forward(params_workspace)); the backward FROM THE STASH, on the bf16 matrix pipe, adds
+    // g_v, g_a1, g_a2, g_t, g_p -- no recomputation of the coupling MLP (1.0x instead of 1.5x the forward's matrix work, at
+    // 2.6x the matrix rate).  Otherwise: the recomputing fp32-MFMA backward writes all seven tensors itself.
+    // Large batches on the fast path: the contraction runs on the bf16 matrix pipe, operands read once (lsnf_params3.hip;
+    // LSNF_TN_X3=0 keeps the fp32-MFMA kernels), and the throughput backward then writes its g arrays in the tiled form (whole
+    // 1 KiB stores instead of 16 rows x 64 bytes; g_v as its first half only: the second half is g_t)
+    if (!l16_math()) act_saved = nullptr;
+    const hipStream_t st = (hipStream_t)stream;
+    const Pick p = select_backward(g, B, act_saved);
+    const bool use_x3 = act_saved && lsnf_contract_x3_covers(B, nz, g.half, width, z_in, z_out, z_saved);
+    const int contraction = select_contraction(g, B, use_x3, vec4);
+    const int g_tiled = (use_x3 && p.k == K_BWD3 && lsnf_dump_can_tile(nz, width)) ? 1 : 0;
+    if (p.k == K_NONE) return launch_fail(hipSuccess, "lsnf_backward_params", p.k);
+    // workspace: G, the folded gradients (zeroed: both accumulate by atomics), then the dump the backward writes
+    const size_t folded = 4 + (size_t)depth * lsnf_fold_layout(nz, width).per_block;
+    hipError_t e = hipMemsetAsync(workspace, 0, sizeof(float) * folded, st);
+    if (e != hipSuccess) return hip_fail(e, "lsnf_backward_params: hipMemsetAsync(workspace)");
+    e = launch_backward(p, g, plan, B, z_out, z_saved, act_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in, vec4, st, nullptr,
+                        workspace + folded, workspace, g_tiled);
+    if (e != hipSuccess) return launch_fail(e, "lsnf_backward_params", p.k);
+    e = lsnf_launch_params_contract(g, plan, params_host, grads_host, B, z_in, z_out, z_saved, workspace, contraction, g_tiled, st);
+    if (e != hipSuccess)
+        return hip_fail(e, contraction == LSNF_CONTRACT_X3 ? "lsnf_backward_params: lsnf_contract_x3_kernel / lsnf_unfold_kernel"
+                                                           : "lsnf_backward_params: lsnf_tn_gemm kernel / lsnf_unfold_kernel");
     return LSNF_OK;
 }
 

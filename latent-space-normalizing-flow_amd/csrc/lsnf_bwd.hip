@@ -321,14 +321,7 @@ hipError_t lsnf_launch_backward_z(const LsnfGeo& g, const float* plan, int B, co
     a.fwd_consts = plan + g.off_fwd_const; a.fwd_panels = plan + g.off_fwd_panels; a.bwd_panels = plan + g.off_bwd_panels;
     a.z_out = z_out; a.z_saved = z_saved; a.g_z1 = g_z1; a.g_logdet = g_logdet; a.g_z_in = g_z_in;
     a.ll_scale = ll_scale; a.ll_mode = ll_mode; a.B = B; a.nz = g.nz; a.half = g.half; a.depth = g.depth; a.vec4 = vec4;
-    if (dump) {
-        if (g.HT == 1 && g.WT == 1) return launch_bwd<BwdCfg<1, 1>, true>(a, stream);
-        if (g.HT == 2 && g.WT == 2) return launch_bwd<BwdCfg<2, 2>, true>(a, stream);
-        if (g.HT == 2 && g.WT == 4) return launch_bwd<BwdCfg<2, 4>, true>(a, stream);
-    } else {
-        if (g.HT == 1 && g.WT == 1) return launch_bwd<BwdCfg<1, 1>, false>(a, stream);
-        if (g.HT == 2 && g.WT == 2) return launch_bwd<BwdCfg<2, 2>, false>(a, stream);
-        if (g.HT == 2 && g.WT == 4) return launch_bwd<BwdCfg<2, 4>, false>(a, stream);
-    }
-    return hipErrorInvalidValue;
+    return lsnf_with_cfg<BwdCfg>(g, [&](auto c) {
+        return dump ? launch_bwd<decltype(c), true>(a, stream) : launch_bwd<decltype(c), false>(a, stream);
+    });
 }

@@ -27,6 +27,26 @@ static inline hipError_t lsnf_allow_big_lds(const void* kernel, unsigned long lo
     return hipSuccess;
 }
 
+// Host side: f(Cfg<HT, WT>{}) for the kernel instantiation of the geometry (lsnf_pick_tiles: (1,1), (2,2) or (2,4)).
+template <template <int, int> class Cfg, class F>
+static inline auto lsnf_with_cfg(const LsnfGeo& g, F&& f) {
+    if (g.HT == 1) return f(Cfg<1, 1>{});
+    if (g.WT == 2) return f(Cfg<2, 2>{});
+    return f(Cfg<2, 4>{});
+}
+
+// Host side: the clock-stamp buffer of the -DLSNF_STAMPS diagnostic build (leaked; address through lsnf_debug_stamps(),
+// tools/stamps.py); NULL in every other build.
+static inline unsigned long long* lsnf_stamps_buffer() {
+#ifdef LSNF_STAMPS
+    extern unsigned long long* g_lsnf_stamps;
+    if (!g_lsnf_stamps && hipMalloc(&g_lsnf_stamps, sizeof(unsigned long long) * 64 * 4 * 4096) != hipSuccess) g_lsnf_stamps = nullptr;
+    return g_lsnf_stamps;
+#else
+    return nullptr;
+#endif
+}
+
 // Compile-time geometry of one coupling block for a kernel instantiation (HT = tiles of nz/2, WT = tiles of f_width):
 // panel counts / k-tiles of the forward stages S1..S4 and of the backward stages B4..B1, and the float offsets of
 // their packed panels inside a block's forward / backward stream (layout produced by lsnf_prep.hip).

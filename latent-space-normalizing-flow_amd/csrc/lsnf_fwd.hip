@@ -238,7 +238,7 @@ hipError_t launch_fwd(const FwdArgs& a, hipStream_t stream) {
 unsigned long long* g_lsnf_stamps = nullptr;
 extern "C" unsigned long long* lsnf_debug_stamps(void) { return g_lsnf_stamps; }
 #endif
-// host-side dispatcher (called from lsnf_api.hip)
+// host-side dispatcher (called from lsnf_api.hip): takes every call
 hipError_t lsnf_launch_forward(const LsnfGeo& g, const float* plan, int first_block, int n_blocks, int B,
                                const float* z_in, const float* objective, float* z_out, float* logdet_out,
                                float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4,
@@ -250,17 +250,6 @@ hipError_t lsnf_launch_forward(const LsnfGeo& g, const float* plan, int first_bl
     a.panels = plan + g.off_fwd_panels + (size_t)first_block * g.fwd_block_floats;
     a.z_in = z_in; a.objective = objective; a.z_out = z_out; a.logdet_out = logdet_out; a.ll_out = ll_out;
     a.z_saved = z_saved; a.B = B; a.nz = g.nz; a.half = g.half; a.n_blocks = n_blocks; a.vec4 = vec4;
-    a.stamps = nullptr;
-#ifdef LSNF_STAMPS
-    {   // diagnostic build: a leaked device buffer, address published through LSNF_STAMPS_PTR (see tools/stamps.py)
-        static unsigned long long* buf = nullptr;
-        if (!buf) { if (hipMalloc(&buf, sizeof(unsigned long long) * 64 * 4 * 4096) != hipSuccess) buf = nullptr; }
-        a.stamps = (B <= 128 * 4096) ? buf : nullptr;
-        extern unsigned long long* g_lsnf_stamps; g_lsnf_stamps = buf;
-    }
-#endif
-    if (g.HT == 1 && g.WT == 1) return launch_fwd<FwdCfg<1, 1>>(a, stream);
-    if (g.HT == 2 && g.WT == 2) return launch_fwd<FwdCfg<2, 2>>(a, stream);
-    if (g.HT == 2 && g.WT == 4) return launch_fwd<FwdCfg<2, 4>>(a, stream);
-    return hipErrorInvalidValue;
+    a.stamps = B <= 128 * 4096 ? lsnf_stamps_buffer() : nullptr;
+    return lsnf_with_cfg<FwdCfg>(g, [&](auto c) { return launch_fwd<decltype(c)>(a, stream); });
 }

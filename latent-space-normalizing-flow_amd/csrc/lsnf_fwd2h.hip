@@ -9,5 +9,6 @@
 // The kernel source is lsnf_fwd3.hip, compiled here with the other split (lsnf_l16.h, LSNF_L16_PARTS).
 #define LSNF_L16_PARTS 2
 #define LSNF_FWD3_ENTRY lsnf_launch_forward2h
+#define LSNF_FWD3_COVERS lsnf_forward2h_covers
 #define lsnf_fwd3b_kernel lsnf_fwd2h_kernel
 #include "lsnf_fwd3.hip"

@@ -6,11 +6,10 @@
 // 4.7 % of MFMA-busy cycles there (PMC).  Two hardware facts decide what can be done about it (tools/micro/shadow.hip,
 // tools/micro/stagger.hip): (1) an MFMA of either shape holds the SIMD's VALU issue for ~12 cycles -- the
 // 32-cycle 32x32x16 then leaves five 4-cycle slots, the 16-cycle 16x16x32 one; (2) packed fp32 math (v_pk_add_f32 ...) waits
-// for the matrix pipe, so this file is compiled without it (Makefile: -fno-slp-vectorize).  The first kernel below is the
-// 32x32x16 kernel with every piece of vector work placed, by hand, between the MFMAs of a stage that does not depend on it
-// (it needs the fewest cycles, but the chip sustains a ~12 % lower clock under that MFMA shape on real data: opt-in
-// LSNF_MATH_BF16X3_PIPE, the reference point); the second, lsnf_fwd3q_kernel, is the same pipeline on 16x16x32 and the
-// library's default throughput forward:
+// for the matrix pipe, so this file is compiled without it (Makefile: -fno-slp-vectorize).  lsnf_fwd3q_kernel, the library's
+// default throughput forward, places every piece of vector work, by hand, between the MFMAs of a stage that does not depend on
+// it.  (The same pipeline on 32x32x16 needed fewer cycles, but the chip sustains a ~12 % lower clock under that MFMA shape on
+// real data; it was measured slower and removed -- profiles/HISTORY.md.)  The pipeline, in 32x32x16 terms:
 //
 //   phase (one LDS weight buffer)   MFMAs   vector work carried between them
 //   S1a  v[0,1]  += Wa^T x           96     block 0: split x[1..3] one k-tile ahead; later blocks (k order 2,0,1,3):
@@ -25,7 +24,7 @@
 // that the split of input k-tile 1 has four MFMA groups to hide under.  The interleave is pinned with
 // sched_group_barrier (1 MFMA, V VALU); V <= 6 keeps the issue cost inside the MFMA's 32 cycles.
 //
-// Same math, same prepared weights (plan region off_f3_panels) and the same I/O contract as lsnf_fwd3_kernel; replaces
+// Same math, same prepared weights (plan region off_f3b_panels) and the same I/O contract as lsnf_fwd3b_kernel; replaces
 // reference model.py:473-483 + train.py:317-319.  Covers HT = 2 (nz in 66..128).  The STASH instantiation of lsnf_fwd3q_kernel also
 // writes the backward's stash (block outputs, sigma tiles, ReLU mask words: bit for bit what lsnf_fwd3.hip writes) from inside the
 // phases -- buffer stores late in each phase, left in flight across the phase barrier by a counted s_waitcnt (stash helpers below);
@@ -87,327 +86,9 @@ __device__ __forceinline__ void keep(float a, float b, float c, float d, float e
 struct StepDesc { int acc, tile, s, frag; };     // accumulator index, input tile, k-step, fragment offset (bf16x8 units / 64)
 template <int KT> constexpr StepDesc mkstep(int acc, int tl, int in_tile, int kt, int s) { return StepDesc{acc, in_tile, s, ((tl * KT + kt) * 2 + s) * 3}; }
 
-#ifdef LSNF_EXPERIMENTAL_KERNELS   // the 32x32x16 form of the pipeline (research builds: LSNF_MATH value 4), measured slower than the 16x16x32 form
-// the three bf16 terms of one activation tile, B-operand order: w[s][part] = k-step s (registers 8s..8s+7)
-struct SplitTile { unsigned d[2][3][4]; };    // scalars, assembled into the 128-bit operand at the MFMA: a partial write
-                                               // of a register TUPLE keeps the whole old tuple alive (measured: +170 VGPRs)
-
-// registers 4q..4q+3 of `x` (optionally through ReLU) -> dwords 2(q&1), 2(q&1)+1 of k-step q>>1: 18 (22) VALU
-template <bool RELU>
-__device__ __forceinline__ void split_quad(const f32x16& x, int q, SplitTile& out) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        float a = x[4 * q + 2 * j], b = x[4 * q + 2 * j + 1];
-        if (RELU) { a = fmaxf(a, 0.0f); b = fmaxf(b, 0.0f); }
-        const unsigned p1 = pk_bf16(a, b);
-        a -= __builtin_bit_cast(float, p1 << 16); b -= __builtin_bit_cast(float, p1 & 0xffff0000u);
-        const unsigned p2 = pk_bf16(a, b);
-        a -= __builtin_bit_cast(float, p2 << 16); b -= __builtin_bit_cast(float, p2 & 0xffff0000u);
-        const int d = 2 * (q & 1) + j;
-        out.d[q >> 1][0][d] = p1; out.d[q >> 1][1][d] = p2; out.d[q >> 1][2][d] = pk_bf16(a, b);
-        keep(out.d[q >> 1][0][d], out.d[q >> 1][1][d], out.d[q >> 1][2][d]);
-    }
-}
-template <bool RELU>
-__device__ __forceinline__ void split_tile(const f32x16& x, SplitTile& out) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) split_quad<RELU>(x, q, out);
-}
-
-// sigmoid / log2 of registers 4q..4q+3: p <- sigmoid(p), lsum += log2(1 + exp(-p))   (model.py:413,418)
-__device__ __forceinline__ void sigmoid_quad(f32x16& p, int q, float& lsum) {
-#pragma unroll
-    for (int r = 4 * q; r < 4 * q + 4; ++r) {
-        float sig, l2;
-        lsnf_sigmoid_log2(p[r], sig, l2);
-        p[r] = sig; lsum += l2;
-    }
-    keep(p[4 * q], p[4 * q + 1], p[4 * q + 2], p[4 * q + 3], lsum);
-}
-// coupling on registers 4q..4q+3: v <- (v + t) * sig   (model.py:414-415)
-__device__ __forceinline__ void couple_quad(f32x16& v, const f32x16& t, const f32x16& sig, int q) {
-#pragma unroll
-    for (int r = 4 * q; r < 4 * q + 4; ++r) v[r] = (v[r] + t[r]) * sig[r];
-}
-
-template <int V>
-__device__ __forceinline__ void pin6() {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        if constexpr (V > 0) __builtin_amdgcn_sched_group_barrier(0x402, V, 0);   // VALU | transcendental
-    }
-}
-
-// PH: struct with  static constexpr int N, MID;  static constexpr StepDesc at(int i);  static constexpr int valu(int i);
-// fill(ic): vector work of step ic (generic lambda on std::integral_constant); mid(): called between steps MID-1 and MID
-template <class PH, class Fill, class Mid>
-__device__ __forceinline__ void run_phase(f32x16* acc, const SplitTile* in, const float* lbuf, int lane, Fill&& fill, Mid&& mid) {
-    const bf16x8* wp = reinterpret_cast<const bf16x8*>(lbuf) + lane;
-    __builtin_amdgcn_sched_barrier(0);
-    bf16x8 a[3];
-#pragma unroll
-    for (int p = 0; p < 3; ++p) a[p] = wp[(PH::at(0).frag + p) * 64];
-    __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
-    lsnf_static_for<PH::N>([&](auto ic) {
-        constexpr int i = decltype(ic)::value;
-        constexpr StepDesc d = PH::at(i);
-        if constexpr (i == PH::MID) { mid(); __builtin_amdgcn_sched_barrier(0); }
-        bf16x8 na[3];
-#pragma unroll
-        for (int p = 0; p < 3; ++p) na[p] = a[p];
-        if constexpr (i + 1 < PH::N) {
-#pragma unroll
-            for (int p = 0; p < 3; ++p) na[p] = wp[(PH::at(i + 1).frag + p) * 64];
-        }
-#ifndef LSNF_ABL_NOFILL     // timing diagnostics only (wrong numbers): tools/ablate_fwd3p.sh
-        fill(ic);
-#endif
-        const SplitTile& x = in[d.tile];
-#define LSNF_P_MMA(WI, XI) \
-        acc[d.acc] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[WI], __builtin_bit_cast(bf16x8, u32x4{x.d[d.s][XI][0], x.d[d.s][XI][1], x.d[d.s][XI][2], x.d[d.s][XI][3]}), acc[d.acc], 0, 0, 0);
-#ifdef LSNF_ABL_NOMFMA
-        LSNF_P_MMA(0, 0)
-#else
-        LSNF_F3_TERMS(LSNF_P_MMA)
-#endif
-#undef LSNF_P_MMA
-        if constexpr (i + 1 < PH::N) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
-        pin6<PH::valu(i)>();
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int p = 0; p < 3; ++p) a[p] = na[p];
-    });
-}
-
-// ---- phase tables: every phase is 16 MFMA groups (96 MFMAs) out of one 48 KiB LDS buffer --------------------------
-// S1a: v[0], v[1] (accumulators 0,1 = buffer tiles 0,1), k order 2,3,0,1: x[2]'s split is ready; x[3] is split under
-// k-tile 2, x[0] under 3, x[1] under 0
-struct PhS1a {
-    static constexpr int N = 16, MID = 8;
-    static constexpr int korder(int j) { return j == 0 ? 2 : (j == 1 ? 3 : (j == 2 ? 0 : 1)); }
-    static constexpr StepDesc at(int i) { return mkstep<4>((i >> 1) & 1, (i >> 1) & 1, korder(i >> 2), korder(i >> 2), i & 1); }
-    static constexpr int valu(int i) { return i < 12 ? 3 : 0; }
-};
-// S1b: v[2], v[3] (array offset by the caller), all inputs ready; v[0], v[1] are split under the first eight groups
-struct PhS1b {
-    static constexpr int N = 16, MID = 8;
-    static constexpr StepDesc at(int i) { return mkstep<4>((i >> 1) & 1, (i >> 1) & 1, i >> 2, i >> 2, i & 1); }
-    static constexpr int valu(int i) { return i < 8 ? 3 : 0; }
-};
-// S2 + S3 out of one buffer [h1_0][h1_1][h2_0][h2_1] (two k-tiles each).  Accumulators 0,1 = h1, 2,3 = h2; inputs 0,1 =
-// split v[0..1], 2,3 = split h1[0..1].  Both k-major: groups 0-7 S2 (h1[0] complete after group 5), 8-15 S3.
-struct PhS23 {
-    static constexpr int N = 16, MID = 8;
-    static constexpr StepDesc at(int i) {
-        const int st = i >> 3, j = i & 7, tl = (j >> 1) & 1, kt = j >> 2;
-        return mkstep<2>(2 * st + tl, 2 * st + tl, 2 * st + kt, kt, j & 1);
-    }
-    //                                  S2: relu+split h1[0] under 6,7 | S3: h1[1] under 8-11, h2[0] under 14,15
-    static constexpr int valu(int i) { return (i == 6 || i == 7 || i == 14 || i == 15) ? 8 : ((i >= 8 && i < 12) ? 4 : 0); }
-};
-// S4 out of one buffer [t0][t1][p0][p1] (fc_zeros panels, two k-tiles each): n-major p0, t0, p1, t1 = accumulators 0..3
-struct PhS4 {
-    static constexpr int N = 16, MID = 8;
-    static constexpr StepDesc at(int i) {
-        const int q = i >> 2, tl = (q == 0) ? 2 : (q == 1 ? 0 : (q == 2 ? 3 : 1)), kt = (i >> 1) & 1;
-        return mkstep<2>(q, tl, kt, kt, i & 1);
-    }
-    //          relu+split h2[1] under 0,1 | sigmoid(p0) under 4-7 | x[2] coupling + split under 8-11 | sigmoid(p1) under 12-15
-    static constexpr int valu(int i) { return i < 2 ? 8 : (i < 4 ? 0 : (i < 8 ? 6 : (i < 12 ? 5 : 6))); }
-};
-
-template <int WT, int NWAVES>
-__global__ __launch_bounds__(64 * NWAVES, 1) void lsnf_fwd3p_kernel(const Fwd3pArgs a) {
-    using C = Fwd3pCfg<WT>;
-    static_assert(WT == 2, "lsnf_fwd3p_kernel: f_width <= 64 instantiation");
-    constexpr int THREADS = 64 * NWAVES;
-    constexpr int HT = 2, NZT = 4, F = C::F;
-    constexpr int SLOT = C::SLOT3;                             // 48 KiB
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* cst = smem;                                         // n_blocks * CONST_FLOATS
-    float* const buf0 = smem + a.n_blocks * C::CONST_FLOATS;   // 3 x SLOT
-    const int tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lane = tid & 63;
-    const int m = lane & 31, h = lane >> 5;
-    // Two waves share a SIMD (wave w and w + 4).  The second half of the workgroup runs HALF A PHASE behind the first:
-    // it meets the workgroup barrier of phase k in the middle of its phase k-1.  What one wave spends outside its MFMA
-    // stream at a phase boundary (barrier skew, LDS-DMA issue, first fragment reads, the few exposed VALU: ~1 800 cycles,
-    // tools/stamps_fwd3p.py) then falls beside its partner's MFMAs instead of beside its partner's identical pause.
-    // Needs a third weight buffer: at barrier k the late half still reads buffer k-1 while buffer k+1 is being filled.
-#ifdef LSNF_ABL_NOSTAGGER
-    const bool late = false;
-#else
-    const bool late = NWAVES == 8 && wave >= 4;                // wave-uniform
-#endif
-
-    P_STAMP(0, "s_memtime");
-    P_STAMP(50, "s_memrealtime");
-    const int n_phases = 4 * a.n_blocks;
-    // phase k of the launch: block k >> 2; (k & 3) = 0 S1a, 1 S1b, 2 S2+S3, 3 S4 -- each ONE contiguous 48 KiB of the stream
-    auto phase_src = [&](int k) -> const float* {
-        const float* gb = a.panels3 + (size_t)(k >> 2) * C::BLOCK3;
-        const int j = k & 3;
-        return gb + (j == 0 ? 0 : (j == 1 ? 2 * 4 * F : (j == 2 ? C::OFF3_S2 : C::OFF3_S4)));
-    };
-    // barrier k: my LDS-DMA has landed (vmcnt), everybody's has (barrier), buffer (k+1) % 3 is free -> start phase k+1's panels
-    auto sync_issue = [&](int k) {
-#ifndef LSNF_ABL_NOSYNC
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();                       // (reached by the two halves at different points of their instruction streams,
-                                               //  the same number of times: wave-uniform control flow around a convergent call)
-#endif
-#ifndef LSNF_ABL_NODMA
-        if (k + 1 < n_phases) issue_kib<48, NWAVES>(phase_src(k + 1), buf0 + ((k + 1) % 3) * SLOT, wave, lane);
-#endif
-    };
-    issue_kib<48, NWAVES>(phase_src(0), buf0, wave, lane);
-    for (int i = tid; i < a.n_blocks * C::CONST_FLOATS; i += THREADS) cst[i] = a.consts[i];
-
-    const long sample = ((long)blockIdx.x * NWAVES + wave) * 32 + m;
-    const bool live = sample < a.B;
-    const long row = live ? sample : (long)a.B - 1;
-
-    // Loop-carried state: xin[0..1] = first half of the block input (fp32; = v1 of the previous block), v[3] = last tile of
-    // the second half (coupled, fp32), xs[2] = split of the third tile, ell.  Every iteration runs the same code:
-    // S1a (which finishes the split of its own input under its first MFMAs) .. S4; no branch leaves the loop body.
-    f32x16 xin[2];
-    f32x16 v[NZT];                // S1 accumulators; v[2..3] become x[2..3] through the coupling
-    SplitTile xs[NZT];            // split of the block input
-    {
-        f32x16 x[NZT];
-        lsnf_load_rows<HT>(x, a.z_in, row, a.nz, a.half, h, a.vec4);
-        xin[0] = x[0]; xin[1] = x[1]; v[2] = x[2]; v[3] = x[3];
-    }
-    float ell = a.objective ? a.objective[row] : 0.0f;
-    split_tile<false>(v[2], xs[2]);                 // the only split that is not hidden (once per launch)
-    float ss01 = 0.0f;                              // sum of squares of the (final) first half, taken when it is stored
-    sync_issue(0);                                  // barrier 0: both halves, before their first phase
-    P_STAMP(1, "s_memtime");
-
-    for (int blk = 0; blk < a.n_blocks; ++blk) {
-        const float* cb = cst + blk * C::CONST_FLOATS;
-        const bool more = blk + 1 < a.n_blocks;
-        const int k0 = 4 * blk;
-        SplitTile vh[4];                            // S2+S3 inputs: split v[0], v[1], h1[0], h1[1]
-        SplitTile h2s[WT];
-        f32x16 hh[4], tp[4];                        // hh: h1[0], h1[1], h2[0], h2[1];  tp: p0, t0, p1, t1
-        float lsum = 0.0f;
-        auto mid_sync = [&](int k) { if (late && k + 1 < n_phases) sync_issue(k + 1); };
-
-        if (blk == 1) P_STAMP(10, "s_memtime");
-        // ---- S1a: v[0,1] (k order 2,3,0,1): split x[3] | x[0] | x[1] under k-tiles 2 | 3 | 0  (model.py:187; actnorm :244,268 folded) ----
-        {
-            v[0] = lsnf_bias_init(cb + 0, h); v[1] = lsnf_bias_init(cb + 32, h);
-            if (!late && k0 > 0) sync_issue(k0);
-            run_phase<PhS1a>(v, xs, buf0 + (k0 % 3) * SLOT, lane, [&](auto ic) {
-                constexpr int i = decltype(ic)::value;
-                if constexpr (i < 4) split_quad<false>(v[3], i, xs[3]);
-                else if constexpr (i < 12) split_quad<false>(xin[(i - 4) >> 2], i & 3, xs[(i - 4) >> 2]);
-            }, [&] { mid_sync(k0); });
-        }
-        if (blk == 1) P_STAMP(11, "s_memtime");
-        // ---- S1b: v[2,3]; split v[0], v[1] for S2 under the first groups ----
-        {
-            v[2] = lsnf_bias_init(cb + 64, h); v[3] = lsnf_bias_init(cb + 96, h);
-            if (!late) sync_issue(k0 + 1);
-            run_phase<PhS1b>(v + 2, xs, buf0 + ((k0 + 1) % 3) * SLOT, lane, [&](auto ic) {
-                constexpr int i = decltype(ic)::value;
-                if constexpr (i < 8) split_quad<false>(v[i >> 2], i & 3, vh[i >> 2]);
-            }, [&] { mid_sync(k0 + 1); });
-        }
-        if (blk == 1) P_STAMP(12, "s_memtime");
-        if (!more) {             // last block: the v1 half is final (model.py:422) -- its stores drain under S2..S4
-            if (live) {
-                float* zo = a.z_out + sample * (long)a.nz;
-#pragma unroll
-                for (int t = 0; t < HT; ++t) lsnf_store_tile<HT>(t, v[t], zo, a.half, h, a.vec4);
-            }
-#pragma unroll
-            for (int t = 0; t < HT; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) ss01 += v[t][r] * v[t][r];
-        }
-        ell = ell + cb[32 * C::NP + 0];          // sum(3*logs)  (model.py:273-276)
-        ell = ell + cb[32 * C::NP + 1];          // log|det W|   (model.py:182,189)
-        // ---- S2 + S3: h1 = relu(actnorm(v1 @ W1)), h2 = relu(actnorm(h1 @ W2))  (model.py:326-328,307-308) ----
-        {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) hh[t] = lsnf_bias_init(cb + 32 * (C::P1 + t), h);
-            if (!late) sync_issue(k0 + 2);
-            run_phase<PhS23>(hh, vh, buf0 + ((k0 + 2) % 3) * SLOT, lane, [&](auto ic) {
-                constexpr int i = decltype(ic)::value;
-                if constexpr (i == 6 || i == 7) { split_quad<true>(hh[0], 2 * (i - 6), vh[2]); split_quad<true>(hh[0], 2 * (i - 6) + 1, vh[2]); }
-                if constexpr (i >= 8 && i < 12) split_quad<true>(hh[1], i - 8, vh[3]);
-                if constexpr (i >= 14) { split_quad<true>(hh[2], 2 * (i - 14), h2s[0]); split_quad<true>(hh[2], 2 * (i - 14) + 1, h2s[0]); }
-            }, [&] { mid_sync(k0 + 2); });
-        }
-        if (blk == 1) P_STAMP(13, "s_memtime");
-        xin[0] = v[0]; xin[1] = v[1];            // v1 is the next block's first half (model.py:422)
-        // ---- S4: p0, t0, p1, t1 = fc_zeros(h2), de-interleaved (model.py:347-349,411-413) + coupling (:414-418) ----
-        {
-            constexpr int B4 = C::P1 + C::P2 + C::P3;
-            tp[0] = lsnf_bias_init(cb + 32 * (B4 + HT), h); tp[1] = lsnf_bias_init(cb + 32 * (B4 + 0), h);
-            tp[2] = lsnf_bias_init(cb + 32 * (B4 + HT + 1), h); tp[3] = lsnf_bias_init(cb + 32 * (B4 + 1), h);
-            if (!late) sync_issue(k0 + 3);
-            run_phase<PhS4>(tp, h2s, buf0 + ((k0 + 3) % 3) * SLOT, lane, [&](auto ic) {
-                constexpr int i = decltype(ic)::value;
-                if constexpr (i < 2) { split_quad<true>(hh[3], 2 * i, h2s[1]); split_quad<true>(hh[3], 2 * i + 1, h2s[1]); }
-                if constexpr (i >= 4 && i < 8) sigmoid_quad(tp[0], i - 4, lsum);
-                if constexpr (i >= 8 && i < 12) { couple_quad(v[2], tp[1], tp[0], i - 8); split_quad<false>(v[2], i - 8, xs[2]); }   // (split unused after the last block)
-                if constexpr (i >= 12) sigmoid_quad(tp[2], i - 12, lsum);
-            }, [&] { mid_sync(k0 + 3); });
-#pragma unroll
-            for (int q = 0; q < 4; ++q) couple_quad(v[3], tp[3], tp[2], q);   // x[3] (32 VALU, not hidden)
-        }
-        ell = ell + -0.6931471805599453f * lsnf_pair_sum(lsum);
-        if (blk == 1) P_STAMP(14, "s_memtime");
-    }
-    P_STAMP(40, "s_memtime");
-
-    // ---- epilogue: z_out, logdet, ll = -0.5*sum z^2 + log(2pi) + logdet (train.py:317-319) ----
-    float ss = ss01;
-#pragma unroll
-    for (int t = HT; t < NZT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ss += v[t][r] * v[t][r];
-    ss = lsnf_pair_sum(ss);
-    if (live) {
-        float* zo = a.z_out + sample * (long)a.nz;
-#pragma unroll
-        for (int t = HT; t < NZT; ++t) lsnf_store_tile<HT>(t, v[t], zo, a.half, h, a.vec4);
-        if (h == 0) {
-            a.logdet_out[sample] = ell;
-            if (a.ll_out) a.ll_out[sample] = (-0.5f * ss + 1.8378770664093453f) + ell;
-        }
-    }
-    if (a.stats) {   // kernel-uniform: batch sums of ll and logdet, one pair of fp64 atomics per workgroup
-        float sl = (live && h == 0) ? ((-0.5f * ss + 1.8378770664093453f) + ell) : 0.0f;
-        float sd = (live && h == 0) ? ell : 0.0f;
-        double dl = (double)sl, dd = (double)sd;
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) { dl += __shfl_xor(dl, o, 64); dd += __shfl_xor(dd, o, 64); }
-        __syncthreads();
-        double* red = reinterpret_cast<double*>(buf0);
-        if (lane == 0) { red[2 * wave] = dl; red[2 * wave + 1] = dd; }
-        __syncthreads();
-        if (wave == 0) {         // (all 64 lanes: lsnf_publish_stats is a wave-level protocol)
-            double tl = 0.0, td = 0.0;
-            for (int w = 0; w < NWAVES; ++w) { tl += red[2 * w]; td += red[2 * w + 1]; }
-            lsnf_publish_stats(a.stats, tl, td, a.B, lane);
-        }
-    }
-    P_STAMP(41, "s_memtime");
-    P_STAMP(51, "s_memrealtime");
-}
-
-#endif  // LSNF_EXPERIMENTAL_KERNELS
-
 // =====================================================================================================================
-// The same pipeline on v_mfma_f32_16x16x32_bf16 (the "L16" lane layout of lsnf_l16.h, the weights of plan region
-// off_f3b_panels).  Why a second form: the 32x32x16 kernel above needs fewer cycles than lsnf_fwd3b_kernel but the chip
-// sustains a ~12 % lower clock under that MFMA shape.  tools/micro/shadow.hip: an MFMA of either shape holds the SIMD's
+// The pipeline on v_mfma_f32_16x16x32_bf16 (the "L16" lane layout of lsnf_l16.h, the weights of plan region
+// off_f3b_panels).  tools/micro/shadow.hip: an MFMA of either shape holds the SIMD's
 // VALU issue for ~12 cycles; the 16-cycle 16x16x32 then leaves ONE 4-cycle slot, and one independent VALU per MFMA in that
 // slot is free (7.41 vs 7.20 ns per MFMA with two waves per SIMD), two cost +15 %.  So here a step = 12 MFMAs (one
 // 16-feature half of an output tile x one 32-feature k-tile x two sample tiles x six terms) carries 12..24 VALU.
@@ -1048,11 +729,14 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void lsnf_fwd3q_kernel(const Fwd3pA
     P_STAMP(51, "s_memrealtime");
 }
 
+size_t fwd3q_lds(int n_blocks) {
+    using C = Fwd3pCfg<2>;
+    return ((size_t)n_blocks * C::CONST_FLOATS + 2 * (size_t)C::SLOT3) * sizeof(float);
+}
+
 template <int WT, int NWAVES, int ST, int STASH = 0>
 hipError_t launch_fwd3q_w(const Fwd3pArgs& a, hipStream_t stream) {
-    using C = Fwd3pCfg<WT>;
-    const size_t lds = ((size_t)a.n_blocks * C::CONST_FLOATS + 2 * (size_t)C::SLOT3) * sizeof(float);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const size_t lds = fwd3q_lds(a.n_blocks);
     auto kern = lsnf_fwd3q_kernel<WT, NWAVES, ST, STASH>;
     static unsigned long long lds_ok = 0;
     if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
@@ -1060,63 +744,31 @@ hipError_t launch_fwd3q_w(const Fwd3pArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NWAVES), lds, stream, a);
     return hipGetLastError();
 }
-
-#ifdef LSNF_EXPERIMENTAL_KERNELS
-template <int WT, int NWAVES>
-hipError_t launch_fwd3p_w(const Fwd3pArgs& a, hipStream_t stream) {
-    using C = Fwd3pCfg<WT>;
-    const size_t lds = ((size_t)a.n_blocks * C::CONST_FLOATS + 3 * (size_t)C::SLOT3) * sizeof(float);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    auto kern = lsnf_fwd3p_kernel<WT, NWAVES>;
-    static unsigned long long lds_ok = 0;
-    if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
-    const unsigned grid = (unsigned)((a.B + 32 * NWAVES - 1) / (32 * NWAVES));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NWAVES), lds, stream, a);
-    return hipGetLastError();
-}
-#endif
 }  // namespace
 
-// host-side dispatcher (called from lsnf_api.hip); hipErrorInvalidValue = this call is not covered (geometry, or the
-// backward's stash / block outputs are wanted): the caller falls back to lsnf_fwd3.hip
-hipError_t lsnf_launch_forward3p(const LsnfGeo& g, const float* plan, int first_block, int n_blocks, int B,
-                                 const float* z_in, const float* objective, float* z_out, float* logdet_out,
-                                 float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4, hipStream_t stream) {
-#ifndef LSNF_EXPERIMENTAL_KERNELS
-    return hipErrorInvalidValue;         // (not in this build)
-#else
-    if (g.HT != 2 || g.WT != 2 || z_saved != nullptr || act_saved != nullptr) return hipErrorInvalidValue;
-    Fwd3pArgs a;
-    a.consts = plan + g.off_fwd_const + (size_t)first_block * g.fwd_const_floats;
-    a.panels3 = plan + g.off_f3_panels + (size_t)first_block * g.f3_block_floats;
-    a.z_in = z_in; a.objective = objective; a.z_out = z_out; a.logdet_out = logdet_out; a.ll_out = ll_out;
-    a.B = B; a.nz = g.nz; a.half = g.half; a.n_blocks = n_blocks; a.vec4 = vec4; a.stats = stats;
-    a.stamps = nullptr;
-#ifdef LSNF_STAMPS
-    { extern unsigned long long* g_lsnf_stamps;
-      if (!g_lsnf_stamps) { if (hipMalloc(&g_lsnf_stamps, sizeof(unsigned long long) * 64 * 4 * 4096) != hipSuccess) g_lsnf_stamps = nullptr; }
-      a.stamps = g_lsnf_stamps; }
-#endif
-    return B > 128 * 256 ? launch_fwd3p_w<2, 8>(a, stream) : launch_fwd3p_w<2, 4>(a, stream);
-#endif
+// Does lsnf_fwd3q_kernel take this call (host only, no HIP calls; lsnf_api.hip selects by it)?  nz in 66..128 and f_width <= 64
+// (HT = WT = 2); the constants of n_blocks blocks and a panel pair in 160 KiB of LDS.  The h dump of the parameter gradients:
+// in its tiled form only, with both parts of the stash, for the whole stack.  With the stash, or a part of it (STASH
+// instantiation: buffer stores of whole 16-byte groups through 32-bit offsets): rows that take 16-byte accesses, and a block of
+// rows / of stash tiles below 2 GiB.
+bool lsnf_forward3q_covers(const LsnfGeo& g, int first_block, int n_blocks, int B, int vec4, const float* z_out,
+                           const float* z_saved, const float* act_saved, const float* hdump, int hdump_tiled) {
+    if (g.HT != 2 || g.WT != 2 || fwd3q_lds(n_blocks) > 160 * 1024) return false;
+    if (hdump && (!hdump_tiled || !act_saved || (n_blocks > 1 && !z_saved) || first_block != 0 || (g.width & 15) ||
+                  ((size_t)B + 32) * g.width * 4 >= (1ull << 31))) return false;
+    const bool stash = act_saved != nullptr || z_saved != nullptr;
+    return !(stash && (vec4 != 4 || (size_t)B * g.nz * 4 >= (1ull << 31) || lsnf_act_layout(B, g.HT, g.WT).per_block * 4 >= (1ull << 31) ||
+                       (((size_t)act_saved | (size_t)z_saved | (size_t)z_out) & 15)));
 }
 
-// the 16x16x32 form (lsnf_fwd3q_kernel): the default throughput forward of LSNF_MATH_BF16X3 for calls it covers (nz in 66..128,
-// f_width <= 64, no stash / parameter-gradient dump); hipErrorInvalidValue = not covered, the caller falls back to lsnf_fwd3.hip
+// the default throughput forward of LSNF_MATH_BF16X3 for the calls lsnf_forward3q_covers admits
 hipError_t lsnf_launch_forward3q(const LsnfGeo& g, const float* plan, int first_block, int n_blocks, int B,
                                  const float* z_in, const float* objective, float* z_out, float* logdet_out,
                                  float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4, hipStream_t stream,
                                  float* hdump, int hdump_tiled) {
-    if (g.HT != 2 || g.WT != 2) return hipErrorInvalidValue;
-    // the h dump of the parameter gradients: in its tiled form only, with both parts of the stash, for the whole stack
-    if (hdump && (!hdump_tiled || !act_saved || (n_blocks > 1 && !z_saved) || first_block != 0 || (g.width & 15) ||
-                  ((size_t)B + 32) * g.width * 4 >= (1ull << 31))) return hipErrorInvalidValue;
-    // with the stash, or a part of it (STASH instantiation: buffer stores of whole 16-byte groups through 32-bit offsets): rows that take
-    // 16-byte accesses, and a block of rows / of stash tiles below 2 GiB
+    if (!lsnf_forward3q_covers(g, first_block, n_blocks, B, vec4, z_out, z_saved, act_saved, hdump, hdump_tiled))
+        return hipErrorInvalidValue;                                       // (a selection bug)
     const bool stash = act_saved != nullptr || z_saved != nullptr;
-    if (stash && (vec4 != 4 || (size_t)B * g.nz * 4 >= (1ull << 31) || lsnf_act_layout(B, g.HT, g.WT).per_block * 4 >= (1ull << 31) ||
-                  (((size_t)act_saved | (size_t)z_saved | (size_t)z_out) & 15)))
-        return hipErrorInvalidValue;
     Fwd3pArgs a;
     a.consts = plan + g.off_fwd_const + (size_t)first_block * g.fwd_const_floats;
     a.panels3 = plan + g.off_f3b_panels + (size_t)first_block * g.f3_block_floats;
@@ -1124,12 +776,7 @@ hipError_t lsnf_launch_forward3q(const LsnfGeo& g, const float* plan, int first_
     a.B = B; a.nz = g.nz; a.half = g.half; a.n_blocks = n_blocks; a.vec4 = vec4; a.stats = stats;
     a.z_saved = z_saved; a.act_saved = act_saved ? act_saved + (size_t)first_block * lsnf_act_layout(B, g.HT, g.WT).per_block : nullptr;
     a.hdump = hdump; a.width = g.width;
-    a.stamps = nullptr;
-#ifdef LSNF_STAMPS
-    { extern unsigned long long* g_lsnf_stamps;
-      if (!g_lsnf_stamps) { if (hipMalloc(&g_lsnf_stamps, sizeof(unsigned long long) * 64 * 4 * 4096) != hipSuccess) g_lsnf_stamps = nullptr; }
-      a.stamps = g_lsnf_stamps; }
-#endif
+    a.stamps = lsnf_stamps_buffer();
     // workgroup shape by batch size (one workgroup per CU; 256 CUs): 256 rows (8 waves x 32) above 32 768 rows; below, 16 rows
     // per wave so that the grid still covers the chip -- 8 waves x 16 rows down to 16 384 rows, 4 waves x 16 rows below
     static const char* shape = getenv("LSNF_FWD3Q_SHAPE");     // experiment knob (tools/shard_times.py): "82", "42", "81", "41"

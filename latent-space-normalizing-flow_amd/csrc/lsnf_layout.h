@@ -21,13 +21,9 @@
 #define LSNF_MAX_DEPTH 16
 #define LSNF_TILE 32
 #define LSNF_FRAG_FLOATS 1024 /* one (nt,kt) 32x32 fragment block */
-// Split-bf16 forward stream (lsnf_fwd3.hip): the same (nt,kt) block as THREE bf16 matrices w = w1 + w2 + w3 (each the
-// round-to-nearest bf16 of what the previous ones left), in the A-operand order of v_mfma_f32_32x32x16_bf16:
-//   dword[((s*3 + part)*64 + lane)*4 + jw] = pack(bf16 part of M[k(2jw)][n], M[k(2jw+1)][n]),  n = 32*nt + (lane&31),
-//   k(j) = 32*kt + 16*s + (j&3) + 8*(j>>2) + 4*(lane>>5)      (s = k-step 0/1, j = 0..7)
-// i.e. k-slot j of lane-half h in k-step s is accumulator register 8*s + j of that lane-half -- an output tile
-// converted to bf16 pairs in register order is directly the next GEMM's B operand.
-#define LSNF_FRAG3_FLOATS 1536 /* 2 k-steps x 3 parts x 1 KiB, in 4-byte units */
+// Split-bf16 streams (lsnf_fwd3.hip, lsnf_fwd3p.hip, ...): the same (nt,kt) block as THREE bf16 matrices w = w1 + w2 + w3
+// (each the round-to-nearest bf16 of what the previous ones left), in the A-operand order of v_mfma_f32_16x16x32_bf16 (below).
+#define LSNF_FRAG3_FLOATS 1536 /* 2 feature halves x 3 parts x 1 KiB, in 4-byte units */
 #define LSNF_GUARD_WORDS 256 /* word 0: folded weights outside fp16's range (written by lsnf_prepare only); rest reserved */
 // fp16 range guard (lsnf_fwd2h.hip / lsnf_rev2h.hip): a wave whose GEMMs met an operand outside fp16's range writes this
 // quiet-NaN bit pattern into the FIRST output element it owns (forward: logdet_out[first row of the wave]; reverse:
@@ -37,8 +33,7 @@
 #define LSNF_F16_SENTINEL_BITS 0x7FD0F16Au
 #define LSNF_F16_GUARD_MAX 65504.0f /* |x| >= this does not survive the round-to-nearest fp16 conversion */
 #define LSNF_FRAG2H_FLOATS 1024 /* fp16 two-term split: 2 feature halves x 2 parts x 1 KiB */
-// The same three bf16 matrices once more in the A-operand order of v_mfma_f32_16x16x32_bf16 (lsnf_fwd3.hip, 16x16 variant;
-// that shape sustains a higher clock on real data).  Lane layout of that variant: a wave's 32 samples are two sample
+// The A-operand order of v_mfma_f32_16x16x32_bf16 (that shape sustains a higher clock on real data than 32x32x16).  Lane layout: a wave's 32 samples are two sample
 // tiles st of 16, lane = (n = lane & 15 -> sample 16*st + n, g = lane >> 4); a 32-feature activation tile is 16 registers
 // per lane, register (2*ft + st)*4 + r holding feature 16*ft + 4*g + r of sample 16*st + n.  Per (nt,kt) block:
 //   dword[((ft*3 + part)*64 + lane)*4 + jw] = pack(bf16 part of M[k(2jw)][n], M[k(2jw+1)][n]),  n = 32*nt + 16*ft + (lane&15),
@@ -62,8 +57,7 @@ struct LsnfGeo {
     size_t off_bwd_const, off_bwd_panels;
     size_t off_winv;            // depth * nz*nz fp32 W^-1 (natural layout; used by d log|det W|/dW)
     int f3_block_floats;        // split-bf16 forward panels per block (same tile order as the forward stream)
-    size_t off_f3_panels;
-    size_t off_f3b_panels;      // the same in the 16x16x32 operand order (same size)
+    size_t off_f3b_panels;      // in the 16x16x32 operand order
     int b3_block_floats;        // backward-z panels (B4, B3, B2, B1) as three bf16 matrices, 16x16x32 operand order
     size_t off_b3b_panels;
     int i3_block_floats;        // inverse panel I1 likewise
@@ -146,8 +140,6 @@ static inline int lsnf_geo_init(LsnfGeo* g, int nz, int width, int depth, int co
     g->off_winv = o;       o += (size_t)depth * nz * nz;
     o = (o + 255) & ~(size_t)255;
     g->f3_block_floats = LSNF_FRAG3_FLOATS * (NZT * NZT + WT * HT + WT * WT + 2 * HT * WT);
-    g->off_f3_panels = o;  o += (size_t)depth * g->f3_block_floats;
-    o = (o + 255) & ~(size_t)255;
     g->off_f3b_panels = o; o += (size_t)depth * g->f3_block_floats;
     o = (o + 255) & ~(size_t)255;
     g->b3_block_floats = LSNF_FRAG3_FLOATS * (WT * 2 * HT + WT * WT + HT * WT + NZT * NZT);
@@ -214,6 +206,9 @@ static inline size_t lsnf_params_workspace_floats(int nz, int width, int depth, 
 // the tiled form of the dump needs whole feature groups of 16 and the natural tile order of the latent rows
 static inline int lsnf_dump_can_tile(int nz, int width) { return nz % 64 == 0 && width % 16 == 0; }
 #define LSNF_X3_MIN_ROWS 12288      /* lsnf_params3.hip takes the batch contraction from this many rows (fp32-MFMA kernel below) */
+// the batch contraction of lsnf_backward_params: lsnf_params3.hip's kernel on the bf16 matrix pipe, or lsnf_params.hip's fp32-MFMA
+// kernels -- through LDS with rows of 4 / 2 / 1 floats per load, or the plain one (lsnf_api.hip select_contraction picks)
+enum LsnfContraction { LSNF_CONTRACT_X3, LSNF_CONTRACT_LDS4, LSNF_CONTRACT_LDS2, LSNF_CONTRACT_LDS1, LSNF_CONTRACT_PLAIN };
 
 // ---- optional activation stash of the forward (act_saved), read by the backward instead of recomputing the MLP ----
 // Opaque, register-order layout, per block and per 32-sample tile `wt` (nwt = ceil(B/32) tiles):

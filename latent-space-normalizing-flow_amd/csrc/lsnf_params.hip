@@ -1,8 +1,8 @@
 // lsnf_params.hip -- parameter gradients of the flow stack (replaces autograd of train.py:406-411,
 // `loss_f.backward()` into the 60 live tensors of _netF).
 //
-// Three steps on one stream:
-//  (1) lsnf_bwd_z_kernel<DUMP>  (lsnf_bwd.hip): the fused backward, which additionally writes, per block,
+// Three steps on one stream (lsnf_api.hip lsnf_backward_params launches (1), lsnf_launch_params_contract below (2) and (3)):
+//  (1) lsnf_bwd_z_kernel<DUMP>  (lsnf_bwd.hip; from the stash: lsnf_small3_bwd.hip / lsnf_bwd3.hip): the fused backward, which additionally writes, per block,
 //      the per-sample gradients at every GEMM output (g_v, g_a1, g_a2, g_t, g_p) and the recomputed
 //      hidden activations (h1, h2), and accumulates G = sum_b dL/dlogdet_b.
 //  (2) lsnf_tn_gemm_kernel: dM = A^T G contracted over the batch (fp32 MFMA, operands loaded straight
@@ -24,29 +24,10 @@ struct LsnfParamPtrs { const float* p[LSNF_MAX_DEPTH * 12]; };
 struct LsnfGradPtrs { float* p[LSNF_MAX_DEPTH * 12]; };
 enum { P_AB = 0, P_ALOGS, P_W, P_W1, P_B1, P_LOGS1, P_W2, P_B2, P_LOGS2, P_W3, P_B3, P_LOGS3 };
 
-hipError_t lsnf_launch_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
-                                  const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
-                                  float* g_z_in, float* dump, float* gl_total, int vec4, hipStream_t stream,
-                                  const LsnfLangevinArgs* lv = nullptr, const float* act_saved = nullptr);
-hipError_t lsnf_launch_small_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
-                                        const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale, float* g_z_in,
-                                        int vec4, hipStream_t stream, const LsnfLangevinArgs* lv, const float* act_saved,
-                                        float* dump, float* gl_total);
-
-hipError_t lsnf_launch_small3_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
-                                         const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode,
-                                         float ll_scale, float* g_z_in, int vec4, hipStream_t stream, const LsnfLangevinArgs* lv,
-                                         float* dump, float* gl_total);
-hipError_t lsnf_launch_backward3_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
-                                   const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
-                                   float* g_z_in, int vec4, hipStream_t stream, const LsnfLangevinArgs* lv,
-                                   float* dump, float* gl_total, int dump_tiled);
-
-// lsnf_params3.hip: the same contraction on the bf16 matrix pipe (large batches); hipErrorInvalidValue = not covered
+// lsnf_params3.hip: the same contraction on the bf16 matrix pipe (large batches)
 hipError_t lsnf_launch_contract_x3(const float* z_in, const float* z_out, const float* z_saved, const float* dump, float* fold,
                                    int B, int nz, int half, int width, int depth, int chunk_override, int g_tiled, const int* h_tag,
                                    hipStream_t stream);
-bool lsnf_contract_x3_covers(int B, int nz, int half, int width, const float* z_in, const float* z_out, const float* z_saved);
 
 namespace {
 
@@ -408,68 +389,37 @@ __global__ __launch_bounds__(256) void lsnf_unfold_kernel(LsnfParamPtrs pp, Lsnf
 }
 }  // namespace
 
-hipError_t lsnf_launch_backward_params(const LsnfGeo& g, const float* plan, const float* const* params_host,
+// Steps (2) and (3): the batch contraction `contraction` (LsnfContraction) of the dump that the backward of step (1) wrote
+// into the zeroed workspace, then the chain rule into the parameter gradients.  g_tiled: the backward wrote its g arrays tiled.
+hipError_t lsnf_launch_params_contract(const LsnfGeo& g, const float* plan, const float* const* params_host,
                                        float* const* grads_host, int B, const float* z_in, const float* z_out,
-                                       const float* z_saved, const float* g_z1, const float* g_logdet, int ll_mode,
-                                       float ll_scale, float* g_z_in, float* workspace, int vec4, int small_batch,
-                                       hipStream_t stream, const float* act_saved) {
+                                       const float* z_saved, float* workspace, int contraction, int g_tiled, hipStream_t stream) {
     const LsnfFoldLayout fl = lsnf_fold_layout(g.nz, g.width);
-    float* gl_total = workspace;
+    const float* gl_total = workspace;
     float* fold = workspace + 4;
     float* dump = fold + (size_t)g.depth * fl.per_block;
-    hipError_t e = hipMemsetAsync(workspace, 0, sizeof(float) * (4 + (size_t)g.depth * fl.per_block), stream);
-    if (e != hipSuccess) return e;
-    // Fast path (act_saved given, bf16x3-family math): the forward of this evaluation kept the activation stash and wrote h1 / h2
-    // into this workspace's dump (lsnf_forward(params_workspace)); the backward FROM THE STASH, on the bf16 matrix pipe, adds
-    // g_v, g_a1, g_a2, g_t, g_p -- no recomputation of the coupling MLP (1.0x instead of 1.5x the forward's matrix work, at
-    // 2.6x the matrix rate).  Otherwise: the recomputing fp32-MFMA backward writes all seven tensors itself.
-    // Large batches on the fast path (bf16x3-family math: act_saved given): the contraction runs on the bf16 matrix pipe, operands read
-    // once (lsnf_params3.hip; LSNF_TN_X3=0 keeps the fp32-MFMA kernels), and the throughput backward then writes its g arrays in the
-    // tiled form (whole 1 KiB stores instead of 16 rows x 64 bytes; g_v as its first half only: the second half is g_t)
-    static const bool knob_plain = getenv("LSNF_TN_PLAIN") != nullptr;
-    const bool use_x3 = act_saved && lsnf_contract_x3_covers(B, g.nz, g.half, g.width, z_in, z_out, z_saved);
-    const int g_tiled = (use_x3 && !small_batch && lsnf_dump_can_tile(g.nz, g.width)) ? 1 : 0;
-    if (act_saved) {
-        e = small_batch
-            ? lsnf_launch_small3_backward_z(g, plan, B, z_out, z_saved, act_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in, vec4, stream,
-                                            nullptr, dump, gl_total)
-            : lsnf_launch_backward3_z(g, plan, B, z_out, z_saved, act_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in, vec4, stream,
-                                      nullptr, dump, gl_total, g_tiled);
-    } else
-    e = small_batch
-        ? lsnf_launch_small_backward_z(g, plan, B, z_out, z_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in, vec4, stream,
-                                       nullptr, nullptr, dump, gl_total)
-        : lsnf_launch_backward_z(g, plan, B, z_out, z_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in, dump, gl_total, vec4, stream);
-    if (e != hipSuccess) return e;
     TnArgs t;
     t.z_in = z_in; t.z_out = z_out; t.z_saved = z_saved; t.dump = dump; t.fold = fold;
     t.B = B; t.nz = g.nz; t.half = g.half; t.width = g.width; t.depth = g.depth;
     t.chunk = B >= 16384 ? 512 : 128;                // samples per workgroup (multiple of 16; 512: 3 200 workgroups at B = 65 536 -- measured 620 us for the whole call against 672 at 1 024 and 760 at 2 048)
-    // experiment knobs of tools/tn_probe.py (read once per process): ablation switches, samples per workgroup, plain kernel
+    // experiment knobs of tools/tn_probe.py (read once per process): ablation switches, samples per workgroup
     static const int knob_abl = [] { const char* e = getenv("LSNF_TN_ABL"); return e ? atoi(e) : 0; }();
     static const int knob_chunk = [] { const char* e = getenv("LSNF_TN_CHUNK"); return e ? atoi(e) : 0; }();
     t.abl = knob_abl;
     if (knob_chunk > 0) t.chunk = knob_chunk;
-    const unsigned chunks = (unsigned)((B + t.chunk - 1) / t.chunk);
-    e = hipErrorInvalidValue;
-    if (use_x3)
+    const dim3 grid(g.depth * 5, (unsigned)((B + t.chunk - 1) / t.chunk));
+    hipError_t e = hipSuccess;
+    switch (contraction) {
+    case LSNF_CONTRACT_X3:
         e = lsnf_launch_contract_x3(z_in, z_out, z_saved, dump, fold, B, g.nz, g.half, g.width, g.depth, knob_chunk, g_tiled,
                                     reinterpret_cast<const int*>(workspace + lsnf_params_workspace_tag(g.nz, g.width, g.depth, B)), stream);
-    if (e == hipErrorInvalidValue && g_tiled) return hipErrorUnknown;        // (cannot happen: lsnf_contract_x3_covers said yes)
-    if (e == hipSuccess) {
-    } else if (e != hipErrorInvalidValue) {
-        return e;
-    } else if (B >= 4096 && !knob_plain) {
-        // every row the tasks read starts 16-byte aligned iff nz, width and half are multiples of 4 (z tensors: the caller's
-        // alignment is folded into vec4; the dump rows start at 16-byte aligned offsets of the 16-byte aligned workspace)
-        const bool a4 = vec4 == 4 && g.nz % 4 == 0 && g.width % 4 == 0 && g.half % 4 == 0;
-        const bool a2 = vec4 >= 2 && g.nz % 2 == 0 && g.width % 2 == 0 && g.half % 2 == 0;
-        if (a4) hipLaunchKernelGGL(lsnf_tn_gemm_lds_kernel<4>, dim3(g.depth * 5, chunks), dim3(256), 0, stream, t);
-        else if (a2) hipLaunchKernelGGL(lsnf_tn_gemm_lds_kernel<2>, dim3(g.depth * 5, chunks), dim3(256), 0, stream, t);
-        else hipLaunchKernelGGL(lsnf_tn_gemm_lds_kernel<1>, dim3(g.depth * 5, chunks), dim3(256), 0, stream, t);
-    } else
-    hipLaunchKernelGGL(lsnf_tn_gemm_kernel, dim3(g.depth * 5, chunks), dim3(256), 0, stream, t);
-    e = hipGetLastError();
+        break;
+    case LSNF_CONTRACT_LDS4: hipLaunchKernelGGL(lsnf_tn_gemm_lds_kernel<4>, grid, dim3(256), 0, stream, t); break;
+    case LSNF_CONTRACT_LDS2: hipLaunchKernelGGL(lsnf_tn_gemm_lds_kernel<2>, grid, dim3(256), 0, stream, t); break;
+    case LSNF_CONTRACT_LDS1: hipLaunchKernelGGL(lsnf_tn_gemm_lds_kernel<1>, grid, dim3(256), 0, stream, t); break;
+    default: hipLaunchKernelGGL(lsnf_tn_gemm_kernel, grid, dim3(256), 0, stream, t); break;
+    }
+    if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) return e;
     LsnfParamPtrs pp; LsnfGradPtrs gp;
     for (int i = 0; i < LSNF_MAX_DEPTH * 12; ++i) {
@@ -477,6 +427,6 @@ hipError_t lsnf_launch_backward_params(const LsnfGeo& g, const float* plan, cons
         gp.p[i] = i < g.depth * 12 ? grads_host[i] : nullptr;
     }
     hipLaunchKernelGGL(lsnf_unfold_kernel, dim3(g.depth, LSNF_UNFOLD_SECTIONS), dim3(256), 0, stream, pp, gp, (const float*)fold,
-                       (const float*)gl_total, plan + g.off_winv, g.nz, g.width, g.coupling);
+                       gl_total, plan + g.off_winv, g.nz, g.width, g.coupling);
     return hipGetLastError();
 }

@@ -17,7 +17,7 @@
 // folded buffer with float atomics (LsnfFoldLayout), exactly as in lsnf_params.hip.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
-#include "lsnf_layout.h"
+#include "lsnf_device.h"
 
 #ifndef X3_ABL
 #define X3_ABL 0          // timing experiments (wrong results): 1 no atomics, 2 no MFMA, 4 no global loads after the first two stages, 8 no split
@@ -250,17 +250,9 @@ __global__ __launch_bounds__(512, 1) void lsnf_contract_x3_kernel(const X3Args a
     x3_run(t, m_begin, m_end, a.B, x3_lds);
 }
 
-hipError_t x3_allow_lds(const void* kern) {
-    static bool done = false;
-    if (done) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS);
-    if (e == hipSuccess) done = true;
-    return e;
-}
+static_assert(X3_LDS <= 160 * 1024, "lsnf_allow_big_lds admits 160 KiB");
 }  // namespace
 
-// hipErrorInvalidValue = not covered (the caller runs the fp32-MFMA contraction of lsnf_params.hip): rows that do not take 16-byte
-// loads, operands wider than 128 features.  (all rows 16-byte aligned: the caller checked the tensors and nz, width, half % 4 == 0)
 // Does this kernel take the contraction of such a call?  ONE rule for lsnf_forward (which then may write h1 / h2 tiled) and for
 // lsnf_backward_params: batch size, geometry (operands of <= 128 features in whole 16-byte groups, 32-bit byte offsets), the three
 // latent tensors 16-byte aligned, and the process-wide knobs LSNF_TN_X3=0 / LSNF_TN_PLAIN (fp32-MFMA kernels of lsnf_params.hip).
@@ -273,7 +265,7 @@ bool lsnf_contract_x3_covers(int B, int nz, int half, int width, const float* z_
 hipError_t lsnf_launch_contract_x3(const float* z_in, const float* z_out, const float* z_saved, const float* dump, float* fold,
                                    int B, int nz, int half, int width, int depth, int chunk_override, int g_tiled, const int* h_tag,
                                    hipStream_t stream) {
-    if (!lsnf_contract_x3_covers(B, nz, half, width, z_in, z_out, z_saved)) return hipErrorInvalidValue;
+    if (!lsnf_contract_x3_covers(B, nz, half, width, z_in, z_out, z_saved)) return hipErrorInvalidValue;    // (a selection bug)
     X3Args a;
     a.g_tiled = g_tiled; a.h_tag = h_tag;
     a.z_in = z_in; a.z_out = z_out; a.z_saved = z_saved; a.dump = dump; a.fold = fold;
@@ -286,7 +278,8 @@ hipError_t lsnf_launch_contract_x3(const float* z_in, const float* z_out, const 
     if (chunk_override > 0) chunk = (chunk_override + X3_S - 1) / X3_S * X3_S;
     a.chunk = chunk;
     chunks = (B + chunk - 1) / chunk;
-    if (hipError_t e = x3_allow_lds((const void*)lsnf_contract_x3_kernel); e != hipSuccess) return e;
+    static unsigned long long lds_ok = 0;
+    if (hipError_t e = lsnf_allow_big_lds((const void*)lsnf_contract_x3_kernel, &lds_ok); e != hipSuccess) return e;
     hipLaunchKernelGGL(lsnf_contract_x3_kernel, dim3(chunks, depth), dim3(512), X3_LDS, stream, a);
     return hipGetLastError();
 }

@@ -247,20 +247,8 @@ __device__ static inline void frag_decode(int q, int KT, int* k, int* n) {
     *n = 32 * nt + (lane & 31);
 }
 
-// split-bf16 stream: dword index inside a stage's panels -> the two (k, n) it packs and which part (0..2)
-__device__ static inline void frag3_decode(int q, int KT, int* k0, int* k1, int* n, int* part) {
-    const int per_panel = KT * LSNF_FRAG3_FLOATS;
-    const int nt = q / per_panel; int r = q % per_panel;
-    const int kt = r / LSNF_FRAG3_FLOATS; r %= LSNF_FRAG3_FLOATS;
-    const int sp = r / 256; r %= 256;                 // s*3 + part
-    const int s = sp / 3, lane = r / 4, jw = r % 4;
-    *part = sp % 3;
-    const int j0 = 2 * jw, j1 = 2 * jw + 1, h = lane >> 5;
-    *k0 = 32 * kt + 16 * s + (j0 & 3) + 8 * (j0 >> 2) + 4 * h;
-    *k1 = 32 * kt + 16 * s + (j1 & 3) + 8 * (j1 >> 2) + 4 * h;
-    *n = 32 * nt + (lane & 31);
-}
-// the same for the 16x16x32 operand order (lsnf_layout.h)
+// split-bf16 stream (16x16x32 operand order, lsnf_layout.h): dword index inside a stage's panels -> the two (k, n) it packs
+// and which part (0..2)
 __device__ static inline void frag3b_decode(int q, int KT, int* k0, int* k1, int* n, int* part) {
     const int per_panel = KT * LSNF_FRAG3_FLOATS;
     const int nt = q / per_panel; int r = q % per_panel;
@@ -323,7 +311,7 @@ __global__ __launch_bounds__(256) void lsnf_pack_kernel(LsnfParamPtrs pp, LsnfGe
     const int n_ic = g.inv_const_floats, n_ip = g.inv_block_floats;
     const int n_bp = g.bwd_block_floats, n_wi = nz * nz, n_f3 = g.f3_block_floats;
     const int n_b3 = g.b3_block_floats, n_i3 = g.i3_block_floats;
-    const int total = n_fc + n_fp + n_ic + n_ip + n_bp + n_wi + 2 * n_f3 + n_b3 + n_i3;
+    const int total = n_fc + n_fp + n_ic + n_ip + n_bp + n_wi + n_f3 + n_b3 + n_i3;
     for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
         int q = idx;
         if (q < n_fc) {                     // ---- forward constants
@@ -389,8 +377,8 @@ __global__ __launch_bounds__(256) void lsnf_pack_kernel(LsnfParamPtrs pp, LsnfGe
         q -= n_bp;
         if (q < n_wi) { plan[g.off_winv + (size_t)blk * n_wi + q] = (float)sb[q]; continue; }   // W^-1, natural layout
         q -= n_wi;
-        if (q >= 2 * n_f3 + n_b3) {         // ---- split-bf16 inverse panel I1: Winv' = Winv diag(exp(-3 logs_a)), 16x16x32 order
-            q -= 2 * n_f3 + n_b3;
+        if (q >= n_f3 + n_b3) {             // ---- split-bf16 inverse panel I1: Winv' = Winv diag(exp(-3 logs_a)), 16x16x32 order
+            q -= n_f3 + n_b3;
             unsigned* dst = reinterpret_cast<unsigned*>(plan + g.off_i3b_panels + (size_t)blk * n_i3);
             int k0, k1, n, part;
             frag3b_decode(q, NZT, &k0, &k1, &n, &part);
@@ -404,8 +392,8 @@ __global__ __launch_bounds__(256) void lsnf_pack_kernel(LsnfParamPtrs pp, LsnfGe
             dst[q] = bf16_part_bits(v[0], part) | (bf16_part_bits(v[1], part) << 16);
             continue;
         }
-        if (q >= 2 * n_f3) {                // ---- split-bf16 backward panels (transposes, as the fp32 backward stream), 16x16x32 order
-            q -= 2 * n_f3;
+        if (q >= n_f3) {                    // ---- split-bf16 backward panels (transposes, as the fp32 backward stream), 16x16x32 order
+            q -= n_f3;
             unsigned* dst = reinterpret_cast<unsigned*>(plan + g.off_b3b_panels + (size_t)blk * n_b3);
             int r = q, k0, k1, n, part;
             const int b4 = LSNF_FRAG3_FLOATS * WT * 2 * HT, b3 = LSNF_FRAG3_FLOATS * WT * WT, b2 = LSNF_FRAG3_FLOATS * HT * WT;
@@ -418,17 +406,15 @@ __global__ __launch_bounds__(256) void lsnf_pack_kernel(LsnfParamPtrs pp, LsnfGe
             dst[q] = bf16_part_bits(fwd_mat(g, P, stage, n, k0), part) | (bf16_part_bits(fwd_mat(g, P, stage, n, k1), part) << 16);
             continue;
         }
-        {                                   // ---- split-bf16 forward panels (same matrices as the forward stream), both operand orders
-            const bool shape16 = q >= n_f3;
-            if (shape16) q -= n_f3;
-            unsigned* dst = reinterpret_cast<unsigned*>(plan + (shape16 ? g.off_f3b_panels : g.off_f3_panels) + (size_t)blk * n_f3);
+        {                                   // ---- split-bf16 forward panels (same matrices as the forward stream), 16x16x32 order
+            unsigned* dst = reinterpret_cast<unsigned*>(plan + g.off_f3b_panels + (size_t)blk * n_f3);
             int r = q, k0, k1, n, part, stage, KT;
             const int s1 = LSNF_FRAG3_FLOATS * NZT * NZT, s2 = LSNF_FRAG3_FLOATS * WT * HT, s3 = LSNF_FRAG3_FLOATS * WT * WT;
             if (r < s1) { stage = 1; KT = NZT; }
             else if ((r -= s1) < s2) { stage = 2; KT = HT; }
             else if ((r -= s2) < s3) { stage = 3; KT = WT; }
             else { r -= s3; stage = 4; KT = WT; }
-            if (shape16) frag3b_decode(r, KT, &k0, &k1, &n, &part); else frag3_decode(r, KT, &k0, &k1, &n, &part);
+            frag3b_decode(r, KT, &k0, &k1, &n, &part);
             dst[q] = bf16_part_bits(fwd_mat(g, P, stage, k0, n), part) | (bf16_part_bits(fwd_mat(g, P, stage, k1, n), part) << 16);
         }
     }
@@ -476,7 +462,7 @@ hipError_t lsnf_launch_prepare(const LsnfGeo& g, const float* const* params_host
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const int per_block = g.fwd_const_floats + g.fwd_block_floats + g.inv_const_floats + g.inv_block_floats +
-                          g.bwd_block_floats + g.nz * g.nz + 2 * g.f3_block_floats + g.b3_block_floats + g.i3_block_floats;
+                          g.bwd_block_floats + g.nz * g.nz + g.f3_block_floats + g.b3_block_floats + g.i3_block_floats;
     if (hipError_t em = hipMemsetAsync(plan + g.off_guard, 0, sizeof(unsigned) * LSNF_GUARD_WORDS, stream); em != hipSuccess) return em;
     int gx = (per_block + 255) / 256;
     if (gx > 512) gx = 512;

@@ -134,8 +134,5 @@ hipError_t lsnf_launch_reverse(const LsnfGeo& g, const float* plan, int B, const
     a.inv_consts = plan + g.off_inv_const; a.inv_panels = plan + g.off_inv_panels;
     a.z_in = z_in; a.objective = objective; a.z_out = z_out; a.objective_out = objective_out;
     a.B = B; a.nz = g.nz; a.half = g.half; a.depth = g.depth; a.vec4 = vec4;
-    if (g.HT == 1 && g.WT == 1) return launch_rev<RevCfg<1, 1>>(a, stream);
-    if (g.HT == 2 && g.WT == 2) return launch_rev<RevCfg<2, 2>>(a, stream);
-    if (g.HT == 2 && g.WT == 4) return launch_rev<RevCfg<2, 4>>(a, stream);
-    return hipErrorInvalidValue;
+    return lsnf_with_cfg<RevCfg>(g, [&](auto c) { return launch_rev<decltype(c)>(a, stream); });
 }

@@ -4,5 +4,6 @@
 // guard words).  The kernel source is lsnf_rev3.hip, compiled here with the other split (lsnf_l16.h, LSNF_L16_PARTS).
 #define LSNF_L16_PARTS 2
 #define LSNF_REV3_ENTRY lsnf_launch_reverse2h
+#define LSNF_REV3_COVERS lsnf_reverse2h_covers
 #define lsnf_rev3_kernel lsnf_rev2h_kernel
 #include "lsnf_rev3.hip"

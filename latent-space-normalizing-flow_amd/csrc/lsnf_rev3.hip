@@ -167,10 +167,12 @@ __global__ __launch_bounds__(64 * NW, 1) void lsnf_rev3_kernel(const Rev3Args a)
     }
 }
 
+template <class C>
+size_t rev3_lds(int depth) { return ((size_t)depth * C::CONST_PER_BLOCK + 2 * (size_t)C::SLOT3) * sizeof(float); }
+
 template <class C, int NW>
 hipError_t launch_rev3_w(const Rev3Args& a, hipStream_t stream) {
-    const size_t lds = ((size_t)a.depth * C::CONST_PER_BLOCK + 2 * (size_t)C::SLOT3) * sizeof(float);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const size_t lds = rev3_lds<C>(a.depth);
     auto kern = lsnf_rev3_kernel<C, NW>;
     static unsigned long long lds_ok = 0;
     if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
@@ -186,12 +188,19 @@ hipError_t launch_rev3(const Rev3Args& a, hipStream_t stream) {
 }
 }  // namespace
 
-// host-side dispatcher (called from lsnf_api.hip); hipErrorInvalidValue = not covered (e.g. very deep stacks: LDS)
 #ifndef LSNF_REV3_ENTRY
 #define LSNF_REV3_ENTRY lsnf_launch_reverse3
+#define LSNF_REV3_COVERS lsnf_reverse3_covers
 #endif
+// Does LSNF_REV3_ENTRY take this geometry (host only, no HIP calls; lsnf_api.hip selects by it)?  The constants of the whole
+// stack and a panel pair fit in 160 KiB of LDS.
+bool LSNF_REV3_COVERS(const LsnfGeo& g) {
+    return lsnf_with_cfg<Rev3Cfg>(g, [&](auto c) { return rev3_lds<decltype(c)>(g.depth) <= 160 * 1024; });
+}
+
 hipError_t LSNF_REV3_ENTRY(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
                            float* z_out, float* objective_out, int vec4, int fixup, hipStream_t stream) {
+    if (!LSNF_REV3_COVERS(g)) return hipErrorInvalidValue;      // (a selection bug)
     Rev3Args a;
     a.guard = reinterpret_cast<const unsigned*>(plan + g.off_guard); a.fixup = fixup;
     a.fwd_consts = plan + g.off_fwd_const; a.inv_consts = plan + g.off_inv_const;
@@ -202,8 +211,5 @@ hipError_t LSNF_REV3_ENTRY(const LsnfGeo& g, const float* plan, int B, const flo
 #endif
     a.z_in = z_in; a.objective = objective; a.z_out = z_out; a.objective_out = objective_out;
     a.B = B; a.nz = g.nz; a.half = g.half; a.depth = g.depth; a.vec4 = vec4;
-    if (g.HT == 1 && g.WT == 1) return launch_rev3<Rev3Cfg<1, 1>>(a, stream);
-    if (g.HT == 2 && g.WT == 2) return launch_rev3<Rev3Cfg<2, 2>>(a, stream);
-    if (g.HT == 2 && g.WT == 4) return launch_rev3<Rev3Cfg<2, 4>>(a, stream);
-    return hipErrorInvalidValue;
+    return lsnf_with_cfg<Rev3Cfg>(g, [&](auto c) { return launch_rev3<decltype(c)>(a, stream); });
 }

@@ -363,10 +363,15 @@ __global__ __launch_bounds__(256, 1) void lsnf_small3_bwd_kernel(const Small3Bwd
     }
 }
 
+// (shapes that do not fit are not instantiated; the LDS footprint does not depend on the depth, and ST = 1 always fits)
+template <class C, int ST>
+constexpr bool small3_bwd_built = (size_t)Small3BwdLds<C, ST>::L_END * sizeof(float) <= 160 * 1024;
+static_assert(small3_bwd_built<Small3BwdCfg<1, 1>, 1> && small3_bwd_built<Small3BwdCfg<2, 2>, 1> && small3_bwd_built<Small3BwdCfg<2, 4>, 1>);
+
 template <class C, int ST>
 hipError_t launch_small3_bwd_st(const Small3BwdArgs& a, hipStream_t stream) {
-    if constexpr ((size_t)Small3BwdLds<C, ST>::L_END * sizeof(float) > 160 * 1024) {
-        return hipErrorInvalidValue;                 // (this shape does not fit: not instantiated)
+    if constexpr (!small3_bwd_built<C, ST>) {
+        return hipErrorInvalidValue;                 // (a selection bug)
     } else {
         const size_t lds = (size_t)Small3BwdLds<C, ST>::L_END * sizeof(float);
         auto kern = a.dump ? lsnf_small3_bwd_kernel<C, ST, true> : lsnf_small3_bwd_kernel<C, ST, false>;
@@ -377,25 +382,26 @@ hipError_t launch_small3_bwd_st(const Small3BwdArgs& a, hipStream_t stream) {
         return hipGetLastError();
     }
 }
-// rows per workgroup by batch size, as the forward (lsnf_small3_fwd.hip launch_small3_fwd); LSNF_SMALL3_ST forces a shape
-template <class C>
-hipError_t launch_small3_bwd(const Small3BwdArgs& a, hipStream_t stream) {
-    static const char* env = getenv("LSNF_SMALL3_ST");
-    const int st = env ? atoi(env) : (a.B <= 256 * 16 ? 1 : (a.B <= 256 * 32 ? 2 : 4));
-    hipError_t e = hipErrorInvalidValue;
-    if (st >= 4) e = launch_small3_bwd_st<C, 4>(a, stream);
-    if (e == hipErrorInvalidValue && st >= 2) e = launch_small3_bwd_st<C, 2>(a, stream);
-    if (e == hipErrorInvalidValue) e = launch_small3_bwd_st<C, 1>(a, stream);
-    return e;
-}
 }  // namespace
 
-// host-side dispatcher (called from lsnf_api.hip); needs the activation stash; hipErrorInvalidValue = not covered
+// Rows per workgroup (16 x ST) for this call (host only, no HIP calls; lsnf_api.hip selects by it): by batch size as the forward
+// (lsnf_small3_forward_st), LSNF_SMALL3_ST forces a shape; a shape that is not instantiated gives way to the next smaller one.
+// Never 0: the kernel takes every call that brings the activation stash.
+int lsnf_small3_backward_st(const LsnfGeo& g, int B) {
+    static const char* env = getenv("LSNF_SMALL3_ST");
+    return lsnf_with_cfg<Small3BwdCfg>(g, [&](auto c) {
+        using C = decltype(c);
+        const int st = env ? atoi(env) : (B <= 256 * 16 ? 1 : (B <= 256 * 32 ? 2 : 4));
+        return (st >= 4 && small3_bwd_built<C, 4>) ? 4 : (st >= 2 && small3_bwd_built<C, 2>) ? 2 : 1;
+    });
+}
+
+// the backward from the activation stash; st: lsnf_small3_backward_st of the call
 hipError_t lsnf_launch_small3_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
                                          const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode,
-                                         float ll_scale, float* g_z_in, int vec4, hipStream_t stream, const LsnfLangevinArgs* lv,
-                                         float* dump, float* gl_total) {
-    if (!act_saved) return hipErrorInvalidValue;
+                                         float ll_scale, float* g_z_in, int vec4, int st, hipStream_t stream,
+                                         const LsnfLangevinArgs* lv, float* dump, float* gl_total) {
+    if (!act_saved) return hipErrorInvalidValue;     // (a selection bug)
     Small3BwdArgs a;
     a.dump = dump; a.gl_total = gl_total; a.width = g.width;
     a.panels = plan + g.off_b3b_panels;
@@ -405,8 +411,9 @@ hipError_t lsnf_launch_small3_backward_z(const LsnfGeo& g, const float* plan, in
     if (lv) { a.z_cur = lv->z_cur; a.grad_g = lv->grad_g; a.noise = lv->noise; a.z_new = lv->z_new; a.gf_norm = lv->gf_norm;
               a.gg_norm = lv->gg_norm; a.step = lv->step; a.rng = lv->rng; }
     a.ll_scale = ll_scale; a.ll_mode = ll_mode; a.B = B; a.nz = g.nz; a.half = g.half; a.depth = g.depth; a.vec4 = vec4;
-    if (g.HT == 1 && g.WT == 1) return launch_small3_bwd<Small3BwdCfg<1, 1>>(a, stream);
-    if (g.HT == 2 && g.WT == 2) return launch_small3_bwd<Small3BwdCfg<2, 2>>(a, stream);
-    if (g.HT == 2 && g.WT == 4) return launch_small3_bwd<Small3BwdCfg<2, 4>>(a, stream);
-    return hipErrorInvalidValue;
+    return lsnf_with_cfg<Small3BwdCfg>(g, [&](auto c) {
+        using C = decltype(c);
+        return st == 4 ? launch_small3_bwd_st<C, 4>(a, stream) : st == 2 ? launch_small3_bwd_st<C, 2>(a, stream)
+                                                                         : launch_small3_bwd_st<C, 1>(a, stream);
+    });
 }

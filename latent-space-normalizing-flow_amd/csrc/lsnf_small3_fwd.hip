@@ -540,12 +540,17 @@ __global__ __launch_bounds__(256, 1) void lsnf_small3_restash_kernel(const Resta
 }
 
 template <class C, int ST>
+size_t small3_fwd_lds(int n_blocks) { return ((size_t)Small3Lds<C, ST>::L_CONST + (size_t)n_blocks * C::CONST_FLOATS) * sizeof(float); }
+// (shapes that cannot fit for any depth are not instantiated)
+template <class C, int ST>
+constexpr bool small3_fwd_built = (size_t)(Small3Lds<C, ST>::L_CONST + C::CONST_FLOATS) * sizeof(float) <= 160 * 1024 && !(ST == 4 && C::WT > 2);
+
+template <class C, int ST>
 hipError_t launch_small3_fwd_st(const Small3Args& a, hipStream_t stream) {
-    if constexpr ((size_t)(Small3Lds<C, ST>::L_CONST + C::CONST_FLOATS) * sizeof(float) > 160 * 1024 || (ST == 4 && C::WT > 2)) {
-        return hipErrorInvalidValue;                 // (this shape cannot fit for any depth: not instantiated)
+    if constexpr (!small3_fwd_built<C, ST>) {
+        return hipErrorInvalidValue;                 // (a selection bug)
     } else {
-        const size_t lds = ((size_t)Small3Lds<C, ST>::L_CONST + (size_t)a.n_blocks * C::CONST_FLOATS) * sizeof(float);
-        if (lds > 160 * 1024) return hipErrorInvalidValue;
+        const size_t lds = small3_fwd_lds<C, ST>(a.n_blocks);
         const bool extras = a.z_saved != nullptr || a.act_saved != nullptr || a.hdump != nullptr;
         auto kern = extras ? lsnf_small3_fwd_kernel<C, ST, true> : lsnf_small3_fwd_kernel<C, ST, false>;
         static unsigned long long lds_ok[2] = {0, 0};
@@ -555,27 +560,30 @@ hipError_t launch_small3_fwd_st(const Small3Args& a, hipStream_t stream) {
         return hipGetLastError();
     }
 }
-// Rows per workgroup by batch size: 16 while one round of workgroups covers the batch (<= 256 CUs x 16 rows), then 32, then 64
-// -- the weight stream per workgroup is the same, so a second round (or a second workgroup per CU) costs a whole stream
-// while a second sample tile costs its MFMAs only.  LSNF_SMALL3_ST (1 / 2 / 4) forces a shape (experiments, tests).
-template <class C>
-hipError_t launch_small3_fwd(const Small3Args& a, hipStream_t stream) {
-    static const char* env = getenv("LSNF_SMALL3_ST");
-    const bool extras = a.z_saved != nullptr || a.act_saved != nullptr || a.hdump != nullptr;
-    // (the plain 32-row form runs two workgroups per CU: 512 of them cover 16 384 rows in one round)
-    int st = env ? atoi(env) : (a.B <= 256 * 16 ? 1 : ((a.B <= 256 * 32 || (LSNF_SMALL3_WAVES2 && !extras && C::WT <= 2 && a.B <= 512 * 32)) ? 2 : 4));
-    hipError_t e = hipErrorInvalidValue;
-    if (st >= 4) e = launch_small3_fwd_st<C, 4>(a, stream);
-    if (e == hipErrorInvalidValue && st >= 2) e = launch_small3_fwd_st<C, 2>(a, stream);     // (the larger shape did not fit into LDS)
-    if (e == hipErrorInvalidValue) e = launch_small3_fwd_st<C, 1>(a, stream);
-    return e;
-}
 }  // namespace
 
-// host-side dispatcher (called from lsnf_api.hip); hipErrorInvalidValue = this geometry is not covered
+// Rows per workgroup (16 x ST) for this call, 0 if the kernel does not take it (host only, no HIP calls; lsnf_api.hip selects by
+// it).  By batch size: 16 while one round of workgroups covers the batch (<= 256 CUs x 16 rows), then 32, then 64 -- the weight
+// stream per workgroup is the same, so a second round (or a second workgroup per CU) costs a whole stream while a second sample
+// tile costs its MFMAs only.  LSNF_SMALL3_ST (1 / 2 / 4) forces a shape (experiments, tests).  A shape whose constants of
+// n_blocks blocks do not fit in 160 KiB of LDS gives way to the next smaller one.
+int lsnf_small3_forward_st(const LsnfGeo& g, int n_blocks, int B, bool extras) {
+    static const char* env = getenv("LSNF_SMALL3_ST");
+    return lsnf_with_cfg<Small3Cfg>(g, [&](auto c) {
+        using C = decltype(c);
+        // (the plain 32-row form runs two workgroups per CU: 512 of them cover 16 384 rows in one round)
+        const int st = env ? atoi(env) : (B <= 256 * 16 ? 1 : ((B <= 256 * 32 || (LSNF_SMALL3_WAVES2 && !extras && C::WT <= 2 && B <= 512 * 32)) ? 2 : 4));
+        if (st >= 4 && small3_fwd_built<C, 4> && small3_fwd_lds<C, 4>(n_blocks) <= 160 * 1024) return 4;
+        if (st >= 2 && small3_fwd_built<C, 2> && small3_fwd_lds<C, 2>(n_blocks) <= 160 * 1024) return 2;
+        if (small3_fwd_built<C, 1> && small3_fwd_lds<C, 1>(n_blocks) <= 160 * 1024) return 1;
+        return 0;
+    });
+}
+
+// st: lsnf_small3_forward_st of the call
 hipError_t lsnf_launch_small3_forward(const LsnfGeo& g, const float* plan, int first_block, int n_blocks, int B,
                                       const float* z_in, const float* objective, float* z_out, float* logdet_out,
-                                      float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4,
+                                      float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4, int st,
                                       hipStream_t stream, float* hdump) {
     Small3Args a;
     a.hdump = hdump ? hdump + (size_t)first_block * lsnf_dump_layout(B, g.nz, g.width).per_block : nullptr;
@@ -585,19 +593,15 @@ hipError_t lsnf_launch_small3_forward(const LsnfGeo& g, const float* plan, int f
     a.act_saved = act_saved ? act_saved + (size_t)first_block * lsnf_act_layout(B, g.HT, g.WT).per_block : nullptr;
     a.z_in = z_in; a.objective = objective; a.z_out = z_out; a.logdet_out = logdet_out; a.ll_out = ll_out;
     a.z_saved = z_saved; a.stats = stats; a.B = B; a.nz = g.nz; a.half = g.half; a.n_blocks = n_blocks; a.vec4 = vec4;
-    a.stamps = nullptr;
-#ifdef LSNF_STAMPS
-    { extern unsigned long long* g_lsnf_stamps;
-      if (!g_lsnf_stamps) { if (hipMalloc(&g_lsnf_stamps, sizeof(unsigned long long) * 64 * 4 * 4096) != hipSuccess) g_lsnf_stamps = nullptr; }
-      a.stamps = g_lsnf_stamps; }
-#endif
-    if (g.HT == 1 && g.WT == 1) return launch_small3_fwd<Small3Cfg<1, 1>>(a, stream);
-    if (g.HT == 2 && g.WT == 2) return launch_small3_fwd<Small3Cfg<2, 2>>(a, stream);
-    if (g.HT == 2 && g.WT == 4) return launch_small3_fwd<Small3Cfg<2, 4>>(a, stream);
-    return hipErrorInvalidValue;
+    a.stamps = lsnf_stamps_buffer();
+    return lsnf_with_cfg<Small3Cfg>(g, [&](auto c) {
+        using C = decltype(c);
+        return st == 4 ? launch_small3_fwd_st<C, 4>(a, stream) : st == 2 ? launch_small3_fwd_st<C, 2>(a, stream)
+                                                                         : launch_small3_fwd_st<C, 1>(a, stream);
+    });
 }
 
-// the stash of a forward that kept none, from its block outputs (lsnf_api.hip lsnf_restash); hipErrorInvalidValue = not covered
+// the stash of a forward that kept none, from its block outputs (lsnf_api.hip lsnf_restash)
 hipError_t lsnf_launch_small3_restash(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
                                       float* act_saved, int vec4, hipStream_t stream) {
     RestashArgs a;
@@ -613,8 +617,5 @@ hipError_t lsnf_launch_small3_restash(const LsnfGeo& g, const float* plan, int B
         hipLaunchKernelGGL(kern, dim3((unsigned)((B + S3_SAMPLES - 1) / S3_SAMPLES), (unsigned)g.depth), dim3(256), lds, stream, a);
         return hipGetLastError();
     };
-    if (g.HT == 1 && g.WT == 1) return go(Small3Cfg<1, 1>{});
-    if (g.HT == 2 && g.WT == 2) return go(Small3Cfg<2, 2>{});
-    if (g.HT == 2 && g.WT == 4) return go(Small3Cfg<2, 4>{});
-    return hipErrorInvalidValue;
+    return lsnf_with_cfg<Small3Cfg>(g, go);
 }

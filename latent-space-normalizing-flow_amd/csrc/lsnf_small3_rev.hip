@@ -226,12 +226,17 @@ __global__ __launch_bounds__(256, 1) void lsnf_small3_rev_kernel(const Small3Rev
 }
 
 template <class C, int ST>
+size_t small3_rev_lds(int depth) { return ((size_t)Small3RevLds<C, ST>::L_CONST + (size_t)depth * C::CONST_PER_BLOCK) * sizeof(float); }
+// (shapes that cannot fit for any depth are not instantiated)
+template <class C, int ST>
+constexpr bool small3_rev_built = (size_t)(Small3RevLds<C, ST>::L_CONST + C::CONST_PER_BLOCK) * sizeof(float) <= 160 * 1024 && !(ST == 4 && C::WT > 2);
+
+template <class C, int ST>
 hipError_t launch_small3_rev_st(const Small3RevArgs& a, hipStream_t stream) {
-    if constexpr ((size_t)(Small3RevLds<C, ST>::L_CONST + C::CONST_PER_BLOCK) * sizeof(float) > 160 * 1024 || (ST == 4 && C::WT > 2)) {
-        return hipErrorInvalidValue;
+    if constexpr (!small3_rev_built<C, ST>) {
+        return hipErrorInvalidValue;                 // (a selection bug)
     } else {
-        const size_t lds = ((size_t)Small3RevLds<C, ST>::L_CONST + (size_t)a.depth * C::CONST_PER_BLOCK) * sizeof(float);
-        if (lds > 160 * 1024) return hipErrorInvalidValue;
+        const size_t lds = small3_rev_lds<C, ST>(a.depth);
         auto kern = lsnf_small3_rev_kernel<C, ST>;
         static unsigned long long lds_ok = 0;
         if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
@@ -240,28 +245,34 @@ hipError_t launch_small3_rev_st(const Small3RevArgs& a, hipStream_t stream) {
         return hipGetLastError();
     }
 }
-// rows per workgroup by batch size, as the forward (lsnf_small3_fwd.hip launch_small3_fwd); LSNF_SMALL3_ST forces a shape
-template <class C>
-hipError_t launch_small3_rev(const Small3RevArgs& a, hipStream_t stream) {
-    static const char* env = getenv("LSNF_SMALL3_ST");
-    const int st = env ? atoi(env) : (a.B <= 256 * 16 ? 1 : (a.B <= 256 * 32 ? 2 : 4));
-    hipError_t e = hipErrorInvalidValue;
-    if (st >= 4) e = launch_small3_rev_st<C, 4>(a, stream);
-    if (e == hipErrorInvalidValue && st >= 2) e = launch_small3_rev_st<C, 2>(a, stream);
-    if (e == hipErrorInvalidValue) e = launch_small3_rev_st<C, 1>(a, stream);
-    return e;
-}
 }  // namespace
 
+// Rows per workgroup (16 x ST) for this call, 0 if the kernel does not take it (host only, no HIP calls; lsnf_api.hip selects by
+// it): by batch size as the forward (lsnf_small3_forward_st), LSNF_SMALL3_ST forces a shape; a shape whose constants of the whole
+// stack do not fit in 160 KiB of LDS gives way to the next smaller one.
+int lsnf_small3_reverse_st(const LsnfGeo& g, int B) {
+    static const char* env = getenv("LSNF_SMALL3_ST");
+    return lsnf_with_cfg<Small3RevCfg>(g, [&](auto c) {
+        using C = decltype(c);
+        const int st = env ? atoi(env) : (B <= 256 * 16 ? 1 : (B <= 256 * 32 ? 2 : 4));
+        if (st >= 4 && small3_rev_built<C, 4> && small3_rev_lds<C, 4>(g.depth) <= 160 * 1024) return 4;
+        if (st >= 2 && small3_rev_built<C, 2> && small3_rev_lds<C, 2>(g.depth) <= 160 * 1024) return 2;
+        if (small3_rev_built<C, 1> && small3_rev_lds<C, 1>(g.depth) <= 160 * 1024) return 1;
+        return 0;
+    });
+}
+
+// st: lsnf_small3_reverse_st of the call
 hipError_t lsnf_launch_small3_reverse(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                                      float* z_out, float* objective_out, int vec4, hipStream_t stream) {
+                                      float* z_out, float* objective_out, int vec4, int st, hipStream_t stream) {
     Small3RevArgs a;
     a.fwd_consts = plan + g.off_fwd_const; a.inv_consts = plan + g.off_inv_const;
     a.panels3b = plan + g.off_f3b_panels; a.ipanels3b = plan + g.off_i3b_panels;
     a.z_in = z_in; a.objective = objective; a.z_out = z_out; a.objective_out = objective_out;
     a.B = B; a.nz = g.nz; a.half = g.half; a.depth = g.depth; a.vec4 = vec4;
-    if (g.HT == 1 && g.WT == 1) return launch_small3_rev<Small3RevCfg<1, 1>>(a, stream);
-    if (g.HT == 2 && g.WT == 2) return launch_small3_rev<Small3RevCfg<2, 2>>(a, stream);
-    if (g.HT == 2 && g.WT == 4) return launch_small3_rev<Small3RevCfg<2, 4>>(a, stream);
-    return hipErrorInvalidValue;
+    return lsnf_with_cfg<Small3RevCfg>(g, [&](auto c) {
+        using C = decltype(c);
+        return st == 4 ? launch_small3_rev_st<C, 4>(a, stream) : st == 2 ? launch_small3_rev_st<C, 2>(a, stream)
+                                                                         : launch_small3_rev_st<C, 1>(a, stream);
+    });
 }

@@ -340,10 +340,12 @@ __global__ __launch_bounds__(LSNF_WG_THREADS, 1) void lsnf_small_bwd_kernel(cons
     }
 }
 
+template <class C>
+size_t small_bwd_lds(int depth) { return ((size_t)C::T_END * LSNF_TILE_FLOATS + C::AUX_FLOATS + (size_t)depth * C::CONST_USED) * sizeof(float); }
+
 template <class C, bool SAVED, bool DUMP>
 hipError_t launch_small_bwd_v(const SmallBwdArgs& a, hipStream_t stream) {
-    const size_t lds = ((size_t)C::T_END * LSNF_TILE_FLOATS + C::AUX_FLOATS + (size_t)a.depth * C::CONST_USED) * sizeof(float);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const size_t lds = small_bwd_lds<C>(a.depth);
     auto kern = lsnf_small_bwd_kernel<C, SAVED, DUMP>;
     static unsigned long long lds_ok = 0;
     if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
@@ -358,7 +360,12 @@ hipError_t launch_small_bwd(const SmallBwdArgs& a, hipStream_t stream) {
 }
 }  // namespace
 
-// returns hipErrorInvalidValue when the geometry's LDS footprint does not fit (caller falls back to lsnf_bwd.hip)
+// Does the kernel take this geometry (host only, no HIP calls; lsnf_api.hip selects by it)?  The constants of the whole stack
+// fit in 160 KiB of LDS.
+bool lsnf_small_backward_covers(const LsnfGeo& g) {
+    return lsnf_with_cfg<SmallBwdCfg>(g, [&](auto c) { return small_bwd_lds<decltype(c)>(g.depth) <= 160 * 1024; });
+}
+
 hipError_t lsnf_launch_small_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
                                         const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale, float* g_z_in,
                                         int vec4, hipStream_t stream, const LsnfLangevinArgs* lv, const float* act_saved,
@@ -373,8 +380,6 @@ hipError_t lsnf_launch_small_backward_z(const LsnfGeo& g, const float* plan, int
     if (lv) { a.z_cur = lv->z_cur; a.grad_g = lv->grad_g; a.noise = lv->noise; a.z_new = lv->z_new; a.gf_norm = lv->gf_norm;
               a.gg_norm = lv->gg_norm; a.step = lv->step; a.rng = lv->rng; }
     a.ll_scale = ll_scale; a.ll_mode = ll_mode; a.B = B; a.nz = g.nz; a.half = g.half; a.depth = g.depth; a.vec4 = vec4;
-    if (g.HT == 1 && g.WT == 1) return launch_small_bwd<SmallBwdCfg<1, 1>>(a, stream);
-    if (g.HT == 2 && g.WT == 2) return launch_small_bwd<SmallBwdCfg<2, 2>>(a, stream);
-    if (g.HT == 2 && g.WT == 4) return launch_small_bwd<SmallBwdCfg<2, 4>>(a, stream);
-    return hipErrorInvalidValue;
+    if (!lsnf_small_backward_covers(g)) return hipErrorInvalidValue;      // (a selection bug)
+    return lsnf_with_cfg<SmallBwdCfg>(g, [&](auto c) { return launch_small_bwd<decltype(c)>(a, stream); });
 }

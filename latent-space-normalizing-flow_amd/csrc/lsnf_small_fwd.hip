@@ -205,9 +205,11 @@ __global__ __launch_bounds__(LSNF_WG_THREADS, 1) void lsnf_small_fwd_kernel(cons
 }
 
 template <class C>
+size_t small_fwd_lds(int n_blocks) { return ((size_t)C::T_END * LSNF_TILE_FLOATS + C::AUX_FLOATS + (size_t)n_blocks * C::CONST_FLOATS) * sizeof(float); }
+
+template <class C>
 hipError_t launch_small_fwd(const SmallFwdArgs& a, hipStream_t stream) {
-    const size_t lds = ((size_t)C::T_END * LSNF_TILE_FLOATS + C::AUX_FLOATS + (size_t)a.n_blocks * C::CONST_FLOATS) * sizeof(float);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const size_t lds = small_fwd_lds<C>(a.n_blocks);
     auto kern = lsnf_small_fwd_kernel<C>;
     static unsigned long long lds_ok = 0;
     if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
@@ -216,6 +218,12 @@ hipError_t launch_small_fwd(const SmallFwdArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 }  // namespace
+
+// Does the kernel take this call (host only, no HIP calls; lsnf_api.hip selects by it)?  The constants of n_blocks blocks fit
+// in 160 KiB of LDS.
+bool lsnf_small_forward_covers(const LsnfGeo& g, int n_blocks) {
+    return lsnf_with_cfg<SmallFwdCfg>(g, [&](auto c) { return small_fwd_lds<decltype(c)>(n_blocks) <= 160 * 1024; });
+}
 
 hipError_t lsnf_launch_small_forward(const LsnfGeo& g, const float* plan, int first_block, int n_blocks, int B,
                                      const float* z_in, const float* objective, float* z_out, float* logdet_out,
@@ -226,15 +234,8 @@ hipError_t lsnf_launch_small_forward(const LsnfGeo& g, const float* plan, int fi
     a.panels = plan + g.off_fwd_panels + (size_t)first_block * g.fwd_block_floats;
     a.z_in = z_in; a.objective = objective; a.z_out = z_out; a.logdet_out = logdet_out; a.ll_out = ll_out;
     a.act_saved = act_saved ? act_saved + (size_t)first_block * lsnf_act_layout(B, g.HT, g.WT).per_block : nullptr;
-    a.stamps = nullptr;
-#ifdef LSNF_STAMPS
-    { extern unsigned long long* g_lsnf_stamps;
-      if (!g_lsnf_stamps) { if (hipMalloc(&g_lsnf_stamps, sizeof(unsigned long long) * 64 * 4 * 4096) != hipSuccess) g_lsnf_stamps = nullptr; }
-      a.stamps = g_lsnf_stamps; }
-#endif
+    a.stamps = lsnf_stamps_buffer();
     a.z_saved = z_saved; a.stats = stats; a.B = B; a.nz = g.nz; a.half = g.half; a.n_blocks = n_blocks; a.vec4 = vec4;
-    if (g.HT == 1 && g.WT == 1) return launch_small_fwd<SmallFwdCfg<1, 1>>(a, stream);
-    if (g.HT == 2 && g.WT == 2) return launch_small_fwd<SmallFwdCfg<2, 2>>(a, stream);
-    if (g.HT == 2 && g.WT == 4) return launch_small_fwd<SmallFwdCfg<2, 4>>(a, stream);
-    return hipErrorInvalidValue;
+    if (!lsnf_small_forward_covers(g, n_blocks)) return hipErrorInvalidValue;      // (a selection bug)
+    return lsnf_with_cfg<SmallFwdCfg>(g, [&](auto c) { return launch_small_fwd<decltype(c)>(a, stream); });
 }

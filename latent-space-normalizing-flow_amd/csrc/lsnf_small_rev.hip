@@ -131,9 +131,11 @@ __global__ __launch_bounds__(LSNF_WG_THREADS, 1) void lsnf_small_rev_kernel(cons
 }
 
 template <class C>
+size_t small_rev_lds(int depth) { return ((size_t)C::T_END * LSNF_TILE_FLOATS + C::AUX_FLOATS + (size_t)depth * C::CONST_PER_BLOCK) * sizeof(float); }
+
+template <class C>
 hipError_t launch_small_rev(const SmallRevArgs& a, hipStream_t stream) {
-    const size_t lds = ((size_t)C::T_END * LSNF_TILE_FLOATS + C::AUX_FLOATS + (size_t)a.depth * C::CONST_PER_BLOCK) * sizeof(float);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const size_t lds = small_rev_lds<C>(a.depth);
     auto kern = lsnf_small_rev_kernel<C>;
     static unsigned long long lds_ok = 0;
     if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
@@ -143,6 +145,12 @@ hipError_t launch_small_rev(const SmallRevArgs& a, hipStream_t stream) {
 }
 }  // namespace
 
+// Does the kernel take this geometry (host only, no HIP calls; lsnf_api.hip selects by it)?  The constants of the whole stack
+// fit in 160 KiB of LDS.
+bool lsnf_small_reverse_covers(const LsnfGeo& g) {
+    return lsnf_with_cfg<SmallRevCfg>(g, [&](auto c) { return small_rev_lds<decltype(c)>(g.depth) <= 160 * 1024; });
+}
+
 hipError_t lsnf_launch_small_reverse(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
                                      float* z_out, float* objective_out, int vec4, hipStream_t stream) {
     SmallRevArgs a;
@@ -150,8 +158,6 @@ hipError_t lsnf_launch_small_reverse(const LsnfGeo& g, const float* plan, int B,
     a.inv_consts = plan + g.off_inv_const; a.inv_panels = plan + g.off_inv_panels;
     a.z_in = z_in; a.objective = objective; a.z_out = z_out; a.objective_out = objective_out;
     a.B = B; a.nz = g.nz; a.half = g.half; a.depth = g.depth; a.vec4 = vec4;
-    if (g.HT == 1 && g.WT == 1) return launch_small_rev<SmallRevCfg<1, 1>>(a, stream);
-    if (g.HT == 2 && g.WT == 2) return launch_small_rev<SmallRevCfg<2, 2>>(a, stream);
-    if (g.HT == 2 && g.WT == 4) return launch_small_rev<SmallRevCfg<2, 4>>(a, stream);
-    return hipErrorInvalidValue;
+    if (!lsnf_small_reverse_covers(g)) return hipErrorInvalidValue;      // (a selection bug)
+    return lsnf_with_cfg<SmallRevCfg>(g, [&](auto c) { return launch_small_rev<decltype(c)>(a, stream); });
 }

@@ -291,9 +291,6 @@ def set_small_batch_max(rows: int) -> int:
 
 
 MATH_FP32, MATH_BF16X3, MATH_FP16X2, MATH_BF16X3_PHASED = 0, 1, 3, 5
-# research builds of the library only (make EXTRA=-DLSNF_EXPERIMENTAL_KERNELS; refused by the shipped one): the bf16x3 scheme on
-# v_mfma_f32_32x32x16_bf16, phase-separated / software-pipelined -- both measured slower (profiles/HISTORY.md); used by tools/
-_MATH_X_BF16X3_32, _MATH_X_BF16X3_PIPE = 2, 4
 
 
 def set_math_mode(mode: int) -> int:
