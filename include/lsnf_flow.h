@@ -162,7 +162,10 @@ int lsnf_actnorm_init(float* const* params_host, int nz, int width, int depth, i
  *             (lsnf_backward_params_workspace_floats(), 16-byte aligned): the forward then also writes the hidden
  *             activations h1, h2 of every block into it, which lets lsnf_backward_params run FROM THE STASH instead of
  *             recomputing the coupling MLP.  Whole stack only, with act_saved and z_saved; needs a bf16x3-family math
- *             mode (lsnf_params_fast_path() == 1, LSNF_E_ARG otherwise).
+ *             mode (lsnf_params_fast_path() == 1, LSNF_E_ARG otherwise).  Where the large-batch kernels may write the
+ *             dump tiled (math mode LSNF_MATH_BF16X3 or LSNF_MATH_BF16X3_PHASED, B > the small-batch threshold,
+ *             B >= 12 288, nz a multiple of 64, width of 16, both <= 128) z_in, z_out and z_saved must be 16-byte
+ *             aligned (LSNF_E_ARG otherwise; lsnf_backward_params applies the same rule).
  *   stats     NULL, or LSNF_STATS_DOUBLES doubles (device, 8-byte aligned) that the caller zero-initialises ONCE:
  *             after the launch stats[4] = sum_b ll_b (train.py:320), stats[5] = sum_b logdet_b,
  *             stats[6] = B.  Summed inside the kernel (fp64 atomics, one pair per workgroup, into 64
@@ -251,6 +254,8 @@ int lsnf_langevin_step(const float* plan, int nz, int width, int depth, int coup
  *   workspace   : lsnf_backward_params_workspace_floats() floats, 16-byte aligned.  Opaque between the two calls of the fast path
  *                 (the forward records there in which form it left h1 / h2: from 12 288 rows the batch contraction runs on the bf16
  *                 matrix pipe and the large-batch kernels write their arrays tiled); pass the forward's own z_in / z_out / z_saved.
+ *                 Where the dump may be tiled (see params_workspace under lsnf_forward) the fast path refuses z tensors that are
+ *                 not 16-byte aligned with LSNF_E_ARG, as that forward does: the two calls then always agree on the dump's form.
  * Sums over the batch use fp32 atomics when B > 1024 (order, hence last bits, may vary run to run:
  * tests/test_gpu_module.py bounds the spread at B = 65 536 to 2e-6 of each tensor's norm). */
 size_t lsnf_backward_params_workspace_floats(int nz, int width, int depth, int B);

@@ -66,22 +66,22 @@ hipError_t lsnf_launch_small_reverse(const LsnfGeo& g, const float* plan, int B,
                                      float* z_out, float* objective_out, int vec4, hipStream_t stream);
 hipError_t lsnf_launch_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
                                   const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
-                                  float* g_z_in, float* dump, float* gl_total, int vec4, hipStream_t stream,
+                                  float* g_z_in, float* dump, double* gl_total, int vec4, hipStream_t stream,
                                   const LsnfLangevinArgs* lv, const float* act_saved);
 bool lsnf_small_backward_covers(const LsnfGeo& g);
 hipError_t lsnf_launch_small_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
                                         const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale, float* g_z_in,
                                         int vec4, hipStream_t stream, const LsnfLangevinArgs* lv, const float* act_saved,
-                                        float* dump, float* gl_total);
+                                        float* dump, double* gl_total);
 int lsnf_small3_backward_st(const LsnfGeo& g, int B);
 hipError_t lsnf_launch_small3_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
                                          const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode,
                                          float ll_scale, float* g_z_in, int vec4, int st, hipStream_t stream,
-                                         const LsnfLangevinArgs* lv, float* dump, float* gl_total);
+                                         const LsnfLangevinArgs* lv, float* dump, double* gl_total);
 hipError_t lsnf_launch_backward3_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
                                    const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
                                    float* g_z_in, int vec4, hipStream_t stream, const LsnfLangevinArgs* lv,
-                                   float* dump, float* gl_total, int dump_tiled);
+                                   float* dump, double* gl_total, int dump_tiled);
 bool lsnf_contract_x3_covers(int B, int nz, int half, int width, const float* z_in, const float* z_out, const float* z_saved);
 hipError_t lsnf_launch_params_contract(const LsnfGeo& g, const float* plan, const float* const* params_host,
                                        float* const* grads_host, int B, const float* z_in, const float* z_out,
@@ -256,7 +256,7 @@ Pick select_backward(const LsnfGeo& g, int B, const float* act_saved) {
 hipError_t launch_backward(Pick p, const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
                            const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
                            float* g_z_in, int vec4, hipStream_t stream, const LsnfLangevinArgs* lv,
-                           float* dump = nullptr, float* gl_total = nullptr, int dump_tiled = 0) {
+                           float* dump = nullptr, double* gl_total = nullptr, int dump_tiled = 0) {
     switch (p.k) {
     case K_SMALL3_BWD:
         return lsnf_launch_small3_backward_z(g, plan, B, z_out, z_saved, act_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in,
@@ -285,6 +285,17 @@ int select_contraction(const LsnfGeo& g, int B, bool use_x3, int vec4) {
     if (vec4 == 4 && g.nz % 4 == 0 && g.width % 4 == 0 && g.half % 4 == 0) return LSNF_CONTRACT_LDS4;
     if (vec4 >= 2 && g.nz % 2 == 0 && g.width % 2 == 0 && g.half % 2 == 0) return LSNF_CONTRACT_LDS2;
     return LSNF_CONTRACT_LDS1;
+}
+
+// The fast path's h dump is tiled iff the bf16x3 / bf16x3_phased throughput forward writes it and the contraction of
+// lsnf_params3.hip covers the call; that contraction is the one reader that asks the workspace's tag, and it needs 16-byte
+// aligned z tensors.  Where this returns true, lsnf_forward(params_workspace) and lsnf_backward_params(act_saved) therefore
+// both refuse z tensors that are not 16-byte aligned: a backward that re-decided on pointers of another alignment than the
+// forward's would hand a tiled dump to the fp32 contraction, which reads it row-major.
+bool dump_may_tile(const LsnfGeo& g, int B, int small_max) {
+    const int math = math_mode();
+    return B > small_max && (math == LSNF_MATH_BF16X3 || math == LSNF_MATH_BF16X3_PHASED) && lsnf_dump_can_tile(g.nz, g.width) &&
+           lsnf_contract_x3_covers(B, g.nz, g.half, g.width, nullptr, nullptr, nullptr);
 }
 }  // namespace
 
@@ -412,8 +423,9 @@ int lsnf_forward(const float* plan, int nz, int width, int depth, int coupling, 
     // tag word which form h1 / h2 have -- tiled (whole 1 KiB stores) when the bf16x3 throughput forward writes them, row-major otherwise
     int hdump_tiled = 0;
     if (hdump && B >= LSNF_X3_MIN_ROWS) {
-        hdump_tiled = (B > small_max && (math == LSNF_MATH_BF16X3 || math == LSNF_MATH_BF16X3_PHASED) && lsnf_dump_can_tile(nz, width) &&
-                       lsnf_contract_x3_covers(B, nz, g.half, width, z_in, z_out, z_saved)) ? 1 : 0;
+        hdump_tiled = dump_may_tile(g, B, small_max) ? 1 : 0;
+        if (hdump_tiled && !(aligned16(z_in) && aligned16(z_out) && aligned16(z_saved)))
+            return fail(LSNF_E_ARG, "lsnf_forward: with params_workspace at B=%d, z_in / z_out / z_saved must be 16-byte aligned", B);
         if (hipMemsetD32Async((hipDeviceptr_t)(params_workspace + lsnf_params_workspace_tag(nz, width, depth, B)), hdump_tiled, 1,
                               (hipStream_t)stream) != hipSuccess)
             return fail(LSNF_E_HIP, "lsnf_forward: hipMemsetD32Async(workspace tag) failed");
@@ -591,18 +603,22 @@ int lsnf_backward_params(const float* plan, const float* const* params_host, flo
     // LSNF_TN_X3=0 keeps the fp32-MFMA kernels), and the throughput backward then writes its g arrays in the tiled form (whole
     // 1 KiB stores instead of 16 rows x 64 bytes; g_v as its first half only: the second half is g_t)
     if (!l16_math()) act_saved = nullptr;
+    if (act_saved && dump_may_tile(g, B, small_batch_max()) && !(aligned16(z_in) && aligned16(z_out) && aligned16(z_saved)))
+        return fail(LSNF_E_ARG, "lsnf_backward_params: with act_saved at B=%d, z_in / z_out / z_saved must be 16-byte aligned", B);
     const hipStream_t st = (hipStream_t)stream;
     const Pick p = select_backward(g, B, act_saved);
     const bool use_x3 = act_saved && lsnf_contract_x3_covers(B, nz, g.half, width, z_in, z_out, z_saved);
     const int contraction = select_contraction(g, B, use_x3, vec4);
     const int g_tiled = (use_x3 && p.k == K_BWD3 && lsnf_dump_can_tile(nz, width)) ? 1 : 0;
     if (p.k == K_NONE) return launch_fail(hipSuccess, "lsnf_backward_params", p.k);
-    // workspace: G, the folded gradients (zeroed: both accumulate by atomics), then the dump the backward writes
+    // workspace: G = sum_b dL/dlogdet_b (one double in floats 0-1: in float32 the per-wave atomics lost up to ~1e-5 of it, and
+    // G * 3 / G * W^-T cancel against the data terms of the actnorm.logs / 1x1-conv gradients), the folded gradients (zeroed:
+    // both accumulate by atomics), then the dump the backward writes
     const size_t folded = 4 + (size_t)depth * lsnf_fold_layout(nz, width).per_block;
     hipError_t e = hipMemsetAsync(workspace, 0, sizeof(float) * folded, st);
     if (e != hipSuccess) return hip_fail(e, "lsnf_backward_params: hipMemsetAsync(workspace)");
     e = launch_backward(p, g, plan, B, z_out, z_saved, act_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in, vec4, st, nullptr,
-                        workspace + folded, workspace, g_tiled);
+                        workspace + folded, reinterpret_cast<double*>(workspace), g_tiled);
     if (e != hipSuccess) return launch_fail(e, "lsnf_backward_params", p.k);
     e = lsnf_launch_params_contract(g, plan, params_host, grads_host, B, z_in, z_out, z_saved, workspace, contraction, g_tiled, st);
     if (e != hipSuccess)

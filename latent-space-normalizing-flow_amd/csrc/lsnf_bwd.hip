@@ -24,7 +24,7 @@ struct BwdArgs {
     const float* z_out; const float* z_saved; const float* g_z1; const float* g_logdet;
     float* g_z_in;          // may be NULL when only parameter gradients are wanted
     float* dump;            // DUMP variant: per-block intermediates for the parameter gradients (lsnf_layout.h)
-    float* gl_total;        // DUMP variant: += sum_b dL/dlogdet_b
+    double* gl_total;       // DUMP variant: += sum_b dL/dlogdet_b
     const float* act_saved; // SAVED variant: activation stash of the forward (sigma, relu masks): no MLP recompute
     // fused Langevin update (train.py:324-329): z_new = z_cur - 0.5 s^2 (grad_g + g_z_in) + s * noise
     const float* z_cur; const float* grad_g; const float* noise; float* z_new; float* gf_norm; float* gg_norm;
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(64 * NW, ((C::WT >= 4 && !SAVED) ? 1 : 2)) void lsn
         float t = (live && h == 0) ? gl : 0.0f;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-        if (lane == 0) atomicAdd(a.gl_total, t);
+        if (lane == 0) atomicAdd(a.gl_total, (double)t);
     }
     const LsnfDumpLayout dl = lsnf_dump_layout(a.B, a.nz, a.width);
     const LsnfActLayout al = lsnf_act_layout(a.B, HT, WT);
@@ -309,7 +309,7 @@ hipError_t launch_bwd(const BwdArgs& a, hipStream_t stream) {
 // (and accumulates sum dL/dlogdet into gl_total) that lsnf_params.hip turns into parameter gradients.
 hipError_t lsnf_launch_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
                                   const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
-                                  float* g_z_in, float* dump, float* gl_total, int vec4, hipStream_t stream,
+                                  float* g_z_in, float* dump, double* gl_total, int vec4, hipStream_t stream,
                                   const LsnfLangevinArgs* lv, const float* act_saved) {
     BwdArgs a;
     a.act_saved = dump ? nullptr : act_saved;

@@ -32,7 +32,7 @@ struct Bwd3Args {
     float step, ll_scale;
     LsnfRngArgs rng;
     int ll_mode, B, nz, half, depth, vec4;
-    float* dump; float* gl_total; int width; int dump_tiled;     // dump_tiled: the g arrays in the tiled form (lsnf_l16.h l16_store_tiled), g_v as its first half only
+    float* dump; double* gl_total; int width; int dump_tiled;     // dump_tiled: the g arrays in the tiled form (lsnf_l16.h l16_store_tiled), g_v as its first half only
          // DUMP variant (parameter gradients, lsnf_params.hip): per block g_v, g_a1, g_a2,
                                                   // g_t, g_p written for the batch contraction; G = sum_b dL/dlogdet_b
 };
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(64 * NW, 1) void lsnf_bwd3_kernel(const Bwd3Args a)
         for (int st = 0; st < 2; ++st) t += (live[st] && g == 0) ? gl[st] : 0.0f;
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-        if (lane == 0) atomicAdd(a.gl_total, t);
+        if (lane == 0) atomicAdd(a.gl_total, (double)t);
     }
 
     for (int blk = last; blk >= 0; --blk) {
@@ -315,12 +315,12 @@ hipError_t launch_bwd3(const Bwd3Args& a, hipStream_t stream) {
 hipError_t lsnf_launch_backward3_z_wide(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
                                         const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
                                         float* g_z_in, int vec4, hipStream_t stream, const LsnfLangevinArgs* lv,
-                                        float* dump, float* gl_total, int dump_tiled);
+                                        float* dump, double* gl_total, int dump_tiled);
 #endif
 hipError_t LSNF_BWD3_ENTRY(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
                            const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
                            float* g_z_in, int vec4, hipStream_t stream, const LsnfLangevinArgs* lv,
-                           float* dump, float* gl_total, int dump_tiled) {
+                           float* dump, double* gl_total, int dump_tiled) {
     if (!act_saved) return hipErrorInvalidValue;     // (a selection bug)
     Bwd3Args a;
     a.dump = dump; a.gl_total = gl_total; a.width = g.width; a.dump_tiled = dump_tiled;

@@ -286,7 +286,7 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 __global__ __launch_bounds__(256) void lsnf_unfold_kernel(LsnfParamPtrs pp, LsnfGradPtrs gp, const float* fold_all,
-                                                          const float* gl_total, const float* winv_all, int nz, int width,
+                                                          const double* gl_total, const float* winv_all, int nz, int width,
                                                           int coupling) {
     const int blk = blockIdx.x, sec = blockIdx.y, tid = threadIdx.x;
     const int gtid = sec * 256 + tid, gstride = LSNF_UNFOLD_SECTIONS * 256;
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(256) void lsnf_unfold_kernel(LsnfParamPtrs pp, Lsnf
     const float* const* P = &pp.p[blk * 12];
     float* const* Gp = &gp.p[blk * 12];
     const float* winv = winv_all + (size_t)blk * nz * nz;
-    const double Gtot = (double)gl_total[0];
+    const double Gtot = gl_total[0];
     // exp(3*logs) of the four log-scale vectors, once (float64)
     __shared__ double ea[128], e1v[128], e2v[128], e3v[128];
     const int n3 = coupling ? nz : half;           // fc_zeros outputs: interleaved shift/scale columns, or shift only
@@ -395,7 +395,7 @@ hipError_t lsnf_launch_params_contract(const LsnfGeo& g, const float* plan, cons
                                        float* const* grads_host, int B, const float* z_in, const float* z_out,
                                        const float* z_saved, float* workspace, int contraction, int g_tiled, hipStream_t stream) {
     const LsnfFoldLayout fl = lsnf_fold_layout(g.nz, g.width);
-    const float* gl_total = workspace;
+    const double* gl_total = reinterpret_cast<const double*>(workspace);   // floats 0-1 of the 16-byte aligned workspace
     float* fold = workspace + 4;
     float* dump = fold + (size_t)g.depth * fl.per_block;
     TnArgs t;

@@ -49,7 +49,7 @@ struct Small3BwdArgs {
     float step, ll_scale;
     LsnfRngArgs rng;
     int ll_mode, B, nz, half, depth, vec4;
-    float* dump; float* gl_total; int width;      // DUMP variant (parameter gradients, lsnf_params.hip): per block g_v, g_a1, g_a2,
+    float* dump; double* gl_total; int width;      // DUMP variant (parameter gradients, lsnf_params.hip): per block g_v, g_a1, g_a2,
                                                   // g_t, g_p written for the batch contraction; G = sum_b dL/dlogdet_b
 };
 
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256, 1) void lsnf_small3_bwd_kernel(const Small3Bwd
             for (int st = 0; st < ST; ++st) t += (live[st] && g == 0) ? gl[st] : 0.0f;
 #pragma unroll
             for (int o = 8; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-            if (lane == 0) atomicAdd(a.gl_total, t);
+            if (lane == 0) atomicAdd(a.gl_total, (double)t);
         }
     }
     // CB of block `blk` for sample tile st: from this wave's g_x2 (the gradient on the block's output, second half), the block's
@@ -400,7 +400,7 @@ int lsnf_small3_backward_st(const LsnfGeo& g, int B) {
 hipError_t lsnf_launch_small3_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
                                          const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode,
                                          float ll_scale, float* g_z_in, int vec4, int st, hipStream_t stream,
-                                         const LsnfLangevinArgs* lv, float* dump, float* gl_total) {
+                                         const LsnfLangevinArgs* lv, float* dump, double* gl_total) {
     if (!act_saved) return hipErrorInvalidValue;     // (a selection bug)
     Small3BwdArgs a;
     a.dump = dump; a.gl_total = gl_total; a.width = g.width;

@@ -49,7 +49,7 @@ struct SmallBwdArgs {
     const float* fwd_consts; const float* fwd_panels; const float* bwd_panels;
     const float* z_out; const float* z_saved; const float* act_saved; const float* g_z1; const float* g_logdet;
     float* g_z_in;
-    float* dump; float* gl_total;      // DUMP variant only
+    float* dump; double* gl_total;     // DUMP variant only
     const float* z_cur; const float* grad_g; const float* noise; float* z_new; float* gf_norm; float* gg_norm;
     float step, ll_scale;
     LsnfRngArgs rng;                   // Langevin update: in-kernel noise when `noise` is NULL and rng.enabled
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(LSNF_WG_THREADS, 1) void lsnf_small_bwd_kernel(cons
             float t = (live && h == 0) ? gl : 0.0f;
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-            if (lane == 0) atomicAdd(a.gl_total, t);
+            if (lane == 0) atomicAdd(a.gl_total, (double)t);
         }
     }
     if (wave < NZT) {
@@ -369,7 +369,7 @@ bool lsnf_small_backward_covers(const LsnfGeo& g) {
 hipError_t lsnf_launch_small_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
                                         const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale, float* g_z_in,
                                         int vec4, hipStream_t stream, const LsnfLangevinArgs* lv, const float* act_saved,
-                                        float* dump, float* gl_total) {
+                                        float* dump, double* gl_total) {
     SmallBwdArgs a;
     a.act_saved = dump ? nullptr : act_saved;
     a.dump = dump; a.gl_total = gl_total; a.width = g.width;

@@ -150,6 +150,8 @@ class _FlowStackFn(torch.autograd.Function):
         for_params = bool(B) and not ctx.needs_input_grad[2] and ctx.needs_input_grad[4] and flow.params_fast_path()
         act = flow.new_act_saved(plan, B, z.device) if (B and (ctx.needs_input_grad[2] or for_params)) else None
         ws = flow.new_params_workspace(plan, B, z.device) if for_params else None
+        if ws is not None and z.data_ptr() % 16:
+            z = z.clone()        # the fast path wants 16-byte aligned rows at large B (lsnf_forward, params_workspace)
         z1, logdet, _, saved = flow.forward(plan, z, objective, want_ll=False, save_for_backward=True, act_saved=act, params_ws=ws)
         ctx.module, ctx.holder = module, holder
         ctx.plan_key = module._plan_key
@@ -329,6 +331,8 @@ class _netF(nn.Module):
             if reuse_buffers:
                 plan.__dict__["_mle_buffers"] = bufs
         act, ws = (bufs[1], bufs[2]) if fast else (None, None)
+        if fast and z.data_ptr() % 16:
+            z = z.clone()        # the fast path wants 16-byte aligned rows at large B (lsnf_forward, params_workspace)
         z1, _, _, saved = flow.forward(plan, z, None, want_ll=False, save_for_backward=True, stats=stats, act_saved=act, params_ws=ws)
         params = self._param_list()
         grads, flat = flow.backward_params(plan, params, z, z1, saved, ll_scale=-1.0 / B, want_flat=True,

@@ -230,6 +230,23 @@ def relu_margin(p: Params, z: Tensor) -> Tensor:
     return margin
 
 
+def smooth_batch(p: Params, B: int, nz: int, seed: int, margin: float = 2e-5, max_rounds: int = 100):
+    """(z, n_replaced): B seeded N(0,1) rows (float32) of which none has a relu_margin <= `margin`.  Rows of the first draw
+    that sit near a kink are replaced by further draws of the same generator (again and again until every row clears the
+    margin), so the batch keeps exactly B rows -- the size, and so the kernels a dispatcher picks, of the raw batch -- and
+    fp32 gradients of every row are well defined.  n_replaced counts the rows of the first draw that were replaced."""
+    g = torch.Generator().manual_seed(seed)
+    z = torch.randn(B, nz, generator=g)
+    bad = torch.nonzero(relu_margin(p, z) <= margin).flatten()
+    n_replaced = int(bad.numel())
+    for _ in range(max_rounds):
+        if bad.numel() == 0:
+            return z, n_replaced
+        z[bad] = torch.randn(int(bad.numel()), nz, generator=g)
+        bad = bad[relu_margin(p, z[bad]) <= margin]
+    raise RuntimeError(f"smooth_batch: {bad.numel()} rows still within {margin} of a ReLU kink after {max_rounds} redraws")
+
+
 def is_live_param(key: str) -> bool:
     """Parameters that get a gradient in the reference: everything except
     fc_1.b / fc_2.b (unused, model.py:319,327-330) and the '.bias' alias (model.py:231)."""

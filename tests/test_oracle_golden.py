@@ -1,6 +1,9 @@
 """CPU: pins oracle/flow_oracle.py against the golden vectors the reference's own
 model.py produced (tests/golden/make_golden.py).  fp32 results must agree with the
 reference's fp32 results to rounding noise; the fp64 oracle must agree with the fp64 run."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
@@ -110,6 +113,35 @@ def test_init_params_shapes_and_roundtrip():
     J = J.reshape(10, 10)
     _, ld64 = O.flow_forward(p64, z0, torch.zeros(1, dtype=torch.float64))
     assert abs(torch.log(torch.abs(torch.det(J))).item() - ld64.item()) < 1e-10
+
+
+@pytest.mark.parametrize("nz,width,depth,B,margin,coupling", [(128, 64, 5, 2000, 2e-5, 1), (16, 8, 3, 777, 1e-3, 1),
+                                                               (16, 8, 2, 500, 1e-3, 0)])
+def test_smooth_batch_is_kink_free_and_exact_size(nz, width, depth, B, margin, coupling):
+    """oracle.smooth_batch: exactly B rows, every ReLU margin above `margin`, the rows it kept are those of the raw seeded
+    draw, and the same seed gives the same batch (the GPU parameter-gradient tests hold whole batches to 2e-5 with it)."""
+    p = O.init_params(nz, width, depth, seed=3)
+    if coupling == 0:                                   # additive: fc_zeros has nz/2 outputs (model.py:385)
+        for i in range(depth):
+            for k in ("f.fc_zeros.w", "f.fc_zeros.b", "f.fc_zeros.logs"):
+                p[O.block_prefix(i) + k] = p[O.block_prefix(i) + k][:, : nz // 2].contiguous()
+        assert O.coupling_of(p) == 0
+    z, n_rep = O.smooth_batch(p, B, nz, seed=B, margin=margin)
+    assert z.shape == (B, nz) and z.dtype == torch.float32
+    raw = torch.randn(B, nz, generator=torch.Generator().manual_seed(B))
+    raw_bad = O.relu_margin(p, raw) <= margin
+    assert n_rep == int(raw_bad.sum()) > 0
+    assert torch.equal(z[~raw_bad], raw[~raw_bad])
+    assert not torch.equal(z[raw_bad], raw[raw_bad])
+    assert bool((O.relu_margin(p, z) > margin).all())
+    z2, n2 = O.smooth_batch(p, B, nz, seed=B, margin=margin)
+    assert torch.equal(z, z2) and n2 == n_rep
+    z3, _ = O.smooth_batch(p, B, nz, seed=B + 1, margin=margin)
+    assert not torch.equal(z, z3)
+    # tools/fuzz_parity.py restates it on relu_margin alone (it also runs beside older oracles): the same batch
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import fuzz_parity
+    assert torch.equal(fuzz_parity.kink_free_batch(p, B, nz, seed=B, margin=margin), z)
 
 
 def test_philox_oracle_known_answers_and_moments():

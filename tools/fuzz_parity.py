@@ -1,6 +1,8 @@
 """Randomised parity sweep (GPU box): random geometries x batch sizes at the kernel-family / tile boundaries x every
-entry point x every arithmetic mode, each checked against the float64 oracle.  Prints one line per failing case and a
-summary; exit code 1 if anything failed.  `python tools/fuzz_parity.py [n_cases] [seed]`.
+entry point x every arithmetic mode, each checked against the float64 oracle.  Batches are kink-free (no row within 2e-5
+of a ReLU kink, kink_free_batch), so every row's gradients and the parameter gradients of every case -- recomputing path, and fast
+path in the bf16x3-family modes -- are held to the oracle.  Prints one line per failing case and a summary; exit code 1 if
+anything failed.  `python tools/fuzz_parity.py [n_cases] [seed]`.
 The oracle is the checker only (tests/ infrastructure); the product path is the C ABI."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -27,6 +29,19 @@ def check(tag, name, got, ref, tol):
         print("FAIL", tag, name, "err %.3g > %.3g" % (e, tol), flush=True)
 
 
+def kink_free_batch(p, B, nz, seed, margin=2e-5):
+    """B seeded N(0,1) rows with every row whose ReLU margin is <= `margin` redrawn from the same generator: what
+    oracle.smooth_batch returns, restated here on oracle.relu_margin alone because tests/test_gpu_fuzz.py runs this tool
+    beside whichever oracle/ the test tree brings, and earlier ones have no smooth_batch."""
+    g = torch.Generator().manual_seed(seed)
+    z = torch.randn(B, nz, generator=g)
+    bad = torch.nonzero(O.relu_margin(p, z) <= margin).flatten()
+    while bad.numel():
+        z[bad] = torch.randn(int(bad.numel()), nz, generator=g)
+        bad = bad[O.relu_margin(p, z[bad]) <= margin]
+    return z
+
+
 def run(n_cases, seed, batches=BATCHES):
     """Returns (number of checks, list of failures (tag, quantity, error, tolerance))."""
     global checks
@@ -44,13 +59,11 @@ def run(n_cases, seed, batches=BATCHES):
             small_max = int(rs.choice([0, 16384]))          # 0: throughput family for every B; default: latency family here
             p32 = O.init_params(nz, width, depth, seed=1000 + case, fcz_std=0.05, all_std=float(rs.choice([0.0, 0.02])))
             p64 = O.to_dtype(p32, torch.float64)
-            z = torch.randn(B, nz, generator=torch.Generator().manual_seed(case)).float()
+            z = kink_free_batch(p32, B, nz, seed=case)         # every row away from a ReLU kink (gradients are discontinuous there)
             obj0 = torch.randn(B, generator=torch.Generator().manual_seed(case + 7)).float()
             gg = torch.randn(B, nz, generator=torch.Generator().manual_seed(case + 11)).float()
             noise_t = torch.randn(B, nz, generator=torch.Generator().manual_seed(case + 13)).float()
             step = float(rs.choice([0.1, 0.3]))
-            margin = O.relu_margin(p32, z)
-            smooth = margin > 2e-5                              # rows away from a ReLU kink (gradients are discontinuous there)
             z1_ref, ld_ref, ll_ref = O.flow_log_prob(p64, z.double())
             gz_ref = O.grad_neg_sum_ll_wrt_z(p64, z.double())
             x_ref, xobj_ref = O.flow_reverse(p64, z.double(), obj0.double())
@@ -74,13 +87,9 @@ def run(n_cases, seed, batches=BATCHES):
                     check(t, "logdet", ld, ld_ref if ld_ref.abs().max() > 1e-3 else ld_ref + 1.0 - 1.0, 1e-5 if ld_ref.abs().max() > 1 else 1e-3)
                     check(t, "ll", ll, ll_ref, 1e-5)
                     gz = flow.backward_z(plan, z1, saved, ll_scale=-1.0, act_saved=act)
-                    if bool(smooth.any()):
-                        check(t, "grad_z", gz[smooth.to(dev)], gz_ref[smooth], 2e-4)
+                    check(t, "grad_z", gz, gz_ref, 2e-4)
                 # Langevin step (train.py:316-329) with explicit noise and with in-kernel Philox noise (oracle/philox_oracle.py)
                 for kind in ("tensor", "philox"):
-                    rows_ok = smooth
-                    if not bool(rows_ok.any()):
-                        break
                     if kind == "tensor":
                         nref = noise_t
                         zn, ll2, gfn, ggn = flow.langevin_step(plan, zd, gg.to(dev), noise_t.to(dev), step)
@@ -89,7 +98,7 @@ def run(n_cases, seed, batches=BATCHES):
                         nref = torch.from_numpy(PO.langevin_noise(B, nz, 1234 + case, 5 + case, 0)).float()
                         zn, ll2, gfn, ggn = flow.langevin_step(plan, zd, gg.to(dev), ph, step)
                     zn_ref = z.double() - 0.5 * step * step * (gg.double() + gz_ref) + step * nref.double()
-                    check(tag, "langevin_z_" + kind, zn[rows_ok.to(dev)], zn_ref[rows_ok], 2e-5)
+                    check(tag, "langevin_z_" + kind, zn, zn_ref, 2e-5)
                     check(tag, "langevin_ll_" + kind, ll2, ll_ref, 1e-5)
                 x, xo = flow.reverse(plan, zd, od)
                 check(tag, "reverse_x", x, x_ref, 5e-5)
@@ -99,15 +108,19 @@ def run(n_cases, seed, batches=BATCHES):
                 zb, ob = flow.reverse(plan, z1, ld)
                 check(tag, "roundtrip_z", zb, z.double(), 5e-5)
                 check(tag, "roundtrip_obj", ob, obj0.double() if B > 1 or abs(float(obj0[0])) > 1e-2 else ob.double().cpu(), 5e-4)
-                if bool(smooth.all()):
-                    z1, _, _, saved = flow.forward(plan, zd, None, want_ll=False, save_for_backward=True)
-                    grads = flow.backward_params(plan, params, zd, z1, saved, ll_scale=-1.0 / B)
-                    keys = [O.block_prefix(i) + k for i in range(depth) for k in flow.BLOCK_PARAM_KEYS]
+                # parameter gradients: the recomputing path, and in the bf16x3-family modes also the fast path (the forward keeps
+                # the stash and writes h1 / h2 into the workspace, the backward runs from them)
+                keys = [O.block_prefix(i) + k for i in range(depth) for k in flow.BLOCK_PARAM_KEYS]
+                for fast in ((False, True) if flow.params_fast_path() else (False,)):
+                    act = flow.new_act_saved(plan, B, dev) if fast else None
+                    ws = flow.new_params_workspace(plan, B, dev) if fast else None
+                    z1, _, _, saved = flow.forward(plan, zd, None, want_ll=False, save_for_backward=True, act_saved=act, params_ws=ws)
+                    grads = flow.backward_params(plan, params, zd, z1, saved, ll_scale=-1.0 / B, act_saved=act, workspace=ws)
                     for k, g in zip(keys, grads):
                         ref = gp_ref[k].reshape(g.shape)
                         if float(ref.abs().max()) < 1e-6:
                             continue
-                        check(tag, "dparam " + k, g, ref, 5e-4)
+                        check(tag + (" fast" if fast else ""), "dparam " + k, g, ref, 1e-4)
             print(f"case {case} done: nz={nz} w={width} d={depth} B={B} small_max={small_max}  ({checks} checks, {len(fails)} failures, "
                   f"{time.time() - t00:.0f} s)", flush=True)
 
