@@ -95,8 +95,10 @@ int lsnf_set_small_batch_max(int rows);
  *                      guarded: a wave that meets an operand (or folded weight) at or beyond 65504 flags its first output
  *                      element, and the LSNF_MATH_BF16X3 kernel queued behind the launch recomputes the flagged
  *                      workgroups (an early-exit launch otherwise), so results are finite wherever the fp32
- *                      computation's are.  In-place calls (z_out == z_in) and calls with in-kernel batch sums (`stats`)
- *                      run LSNF_MATH_BF16X3 directly.  Every other kernel (latency kernels, backward) as LSNF_MATH_BF16X3.
+ *                      computation's are.  In-place calls (an output aliases an input: z_out == z_in, or logdet_out /
+ *                      objective_out == objective -- the fix-up pass re-reads both inputs) and calls with in-kernel batch
+ *                      sums (`stats`) run LSNF_MATH_BF16X3 directly (the phase-separated lsnf_fwd3b_kernel / lsnf_rev3_kernel).
+ *                      Every other kernel (latency kernels, backward) as LSNF_MATH_BF16X3.
  * mode < 0 only queries.  Returns the previous mode (default LSNF_MATH_DEFAULT, or the LSNF_MATH environment
  * variable "fp32" / "bf16x3" / "bf16x3_phased" / "fp16x2").  Other values are refused. */
 #define LSNF_MATH_FP32 0
@@ -149,8 +151,8 @@ int lsnf_actnorm_init(float* const* params_host, int nz, int width, int depth, i
  * revnet2d_step.forward model.py:391-422) on B rows in ONE launch.
  *   z_in      (B, nz)   input latents
  *   objective (B) or NULL (= zeros)      running log-det in
- *   z_out     (B, nz)   output of the last block run
- *   logdet_out(B)       objective + sum of the blocks' log|det J|
+ *   z_out     (B, nz)   output of the last block run; may be z_in itself (in-place call)
+ *   logdet_out(B)       objective + sum of the blocks' log|det J|; may be objective itself
  *   ll_out    (B) or NULL: -0.5*sum_j z_out^2 + log(2*pi) + logdet_out  (train.py:317-319)
  *   z_saved   NULL, or ((n_blocks-1), B, nz): outputs of all but the last block, kept for
  *             lsnf_backward_z / lsnf_backward_params.
@@ -184,7 +186,9 @@ size_t lsnf_act_saved_floats(int nz, int width, int depth, int B);
 
 /* ---- reverse: replaces `_netF.forward(z, objective, reverse=True)` (model.py:484-498,
  * block inverse model.py:424-456).  Functional: inputs are not modified (the reference
- * mutates them in place, model.py:436-438).  objective_out = objective - sum log|det J|
+ * mutates them in place, model.py:436-438) unless the caller aliases them: z_out may be z_in and
+ * objective_out may be objective (in-place call).  objective (B) or NULL (= zeros);
+ * objective_out = objective - sum log|det J|
  * (the reference returns its negation when return_obj=True, model.py:498). */
 int lsnf_reverse(const float* plan, int nz, int width, int depth, int coupling, int B,
                  const float* z_in, const float* objective,

@@ -327,8 +327,10 @@ def new_stats(device) -> torch.Tensor:
     return torch.zeros(STATS_DOUBLES, dtype=torch.float64, device=device)
 
 
-def reverse(plan: FlowPlan, z: torch.Tensor, objective: Optional[torch.Tensor] = None):
-    """model.py:484-498: returns (z_out, objective_out) with objective_out = objective - sum log|det J|."""
+def reverse(plan: FlowPlan, z: torch.Tensor, objective: Optional[torch.Tensor] = None, *,
+            out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """model.py:484-498: returns (z_out, objective_out) with objective_out = objective - sum log|det J|.
+    out: optional caller-owned (z_out, objective_out); either may be the input itself (in-place call)."""
     lib = _lib.load()
     _need_cuda(z, "z")
     if z.dim() != 2 or z.shape[1] != plan.nz:
@@ -336,8 +338,15 @@ def reverse(plan: FlowPlan, z: torch.Tensor, objective: Optional[torch.Tensor] =
     B = z.shape[0]
     if objective is not None:
         _need_cuda(objective, "objective")
-    z_out = torch.empty_like(z)
-    obj_out = torch.empty(B, dtype=torch.float32, device=z.device)
+        if objective.numel() != B:
+            raise LsnfError("objective must have B elements")
+    if out is not None:
+        z_out, obj_out = out
+        _check_out(z_out, "out[0] (z_out)", B * plan.nz, z.device)
+        _check_out(obj_out, "out[1] (objective_out)", B, z.device)
+    else:
+        z_out = torch.empty_like(z)
+        obj_out = torch.empty(B, dtype=torch.float32, device=z.device)
     with torch.cuda.device(z.device):
         rc = lib.lsnf_reverse(_ptr(plan.buf), plan.nz, plan.width, plan.depth, plan.coupling, B,
                               _ptr(z), _ptr(objective), _ptr(z_out), _ptr(obj_out), _stream_ptr(z.device))

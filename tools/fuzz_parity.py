@@ -1,5 +1,8 @@
 """Randomised parity sweep (GPU box): random geometries x batch sizes at the kernel-family / tile boundaries x every
-entry point x every arithmetic mode, each checked against the float64 oracle.  Batches are kink-free (no row within 2e-5
+entry point x every arithmetic mode x affine / additive coupling, each checked against the float64 oracle; every case also
+draws one documented call form of the ABI (forward and reverse in place, the stack in two pieces sharing one activation stash,
+one row tensor of the forward at a 4- or 8-byte offset) from a second generator, so that the geometries of a seed do not depend
+on the forms.  Batches are kink-free (no row within 2e-5
 of a ReLU kink, kink_free_batch), so every row's gradients and the parameter gradients of every case -- recomputing path, and fast
 path in the bf16x3-family modes -- are held to the oracle.  Prints one line per failing case and a summary; exit code 1 if
 anything failed.  `python tools/fuzz_parity.py [n_cases] [seed]`.
@@ -42,12 +45,70 @@ def kink_free_batch(p, B, nz, seed, margin=2e-5):
     return z
 
 
+def offset_view(shape, off, src=None):
+    """A contiguous tensor `off` floats past a 16-byte boundary (a view into a larger allocation), optionally a copy of src."""
+    n = int(np.prod(shape))
+    t = torch.empty(n + 4, dtype=torch.float32, device=dev)[off: off + n].view(shape)
+    assert t.data_ptr() % 16 == 4 * off
+    return t if src is None else t.copy_(src)
+
+
+def nan_stash(plan, B, n_saved):
+    act = flow.new_act_saved(plan, B, dev)
+    act.fill_(float("nan"))
+    saved = torch.full((n_saved, B, plan.nz), float("nan"), device=dev) if n_saved > 0 else None
+    return act, saved
+
+
+def call_form(tag, form, plan, zd, od, cut, mis_tensor, mis_off, ref):
+    """One documented call form of the ABI (include/lsnf_flow.h) per case, in the math mode / threshold in force, against
+    the same oracle and tolerances as the plain calls."""
+    B, depth = zd.shape[0], plan.depth
+    ld_ref, ll_ref = ref["ld"] + ref["obj"], ref["ll"] + ref["obj"]
+    ld_tol = 1e-5 if ld_ref.abs().max() > 1 else 1e-3
+    if form == "inplace":                      # z_out == z_in, logdet_out == objective; reverse: the same two aliases
+        zc, oc = zd.clone(), od.clone()
+        ll = torch.empty(B, device=dev)
+        flow.forward(plan, zc, oc, out=(zc, oc, ll))
+        check(tag, "z1", zc, ref["z1"], 2e-5)
+        check(tag, "logdet", oc, ld_ref, ld_tol)
+        check(tag, "ll", ll, ll_ref, 1e-5)
+        zc, oc = zd.clone(), od.clone()
+        flow.reverse(plan, zc, oc, out=(zc, oc))
+        check(tag, "reverse_x", zc, ref["x"], 5e-5)
+        check(tag, "reverse_obj", oc, ref["xobj"], 2e-5)
+        return
+    if form == "split":                        # [0, cut) + [cut, depth): one stash (indexed by absolute block), z_saved per piece
+        cut = min(cut, depth)
+        act, _ = nan_stash(plan, B, 0)
+        z, ld, ll, outs = zd, od, None, []
+        for a, b in ((0, cut), (cut, depth)):
+            if b > a:
+                _, sv = nan_stash(plan, B, b - a - 1)
+                z, ld, ll, _ = flow.forward(plan, z, ld, first_block=a, n_blocks=b - a, act_saved=act, z_saved_out=sv)
+                outs += ([] if sv is None else list(sv)) + [z]
+        z1, saved = z, (torch.stack(outs[:-1]) if depth > 1 else None)
+    else:                                      # one row tensor of the forward 4 or 8 bytes off a 16-byte boundary
+        act, saved = nan_stash(plan, B, depth - 1)
+        z_in = offset_view(zd.shape, mis_off if mis_tensor == "z_in" else 0, zd)
+        z1 = offset_view(zd.shape, mis_off if mis_tensor == "z_out" else 0)
+        if saved is not None:
+            saved = offset_view(saved.shape, mis_off if mis_tensor == "z_saved" else 0, saved)
+        ld, ll = torch.empty(B, device=dev), torch.empty(B, device=dev)
+        flow.forward(plan, z_in, od, out=(z1, ld, ll), act_saved=act, z_saved_out=saved)
+    check(tag, "z1", z1, ref["z1"], 2e-5)
+    check(tag, "logdet", ld, ld_ref, ld_tol)
+    check(tag, "ll", ll, ll_ref, 1e-5)
+    check(tag, "grad_z", flow.backward_z(plan, z1, saved, ll_scale=-1.0, act_saved=act), ref["gz"], 2e-4)
+
+
 def run(n_cases, seed, batches=BATCHES):
     """Returns (number of checks, list of failures (tag, quantity, error, tolerance))."""
     global checks
     del fails[:]
     checks = 0
     rs = np.random.RandomState(seed)
+    rs2 = np.random.RandomState(seed + 7919)      # coupling type and call form: a stream of its own, so that `rs` draws what it always drew
     t00 = time.time()
     prev_small, prev_mode = flow.set_small_batch_max(flow.SMALL_BATCH_AUTO), flow.set_math_mode(-1)   # (restored below)
     try:
@@ -58,19 +119,27 @@ def run(n_cases, seed, batches=BATCHES):
             B = int(rs.choice(batches))
             small_max = int(rs.choice([0, 16384]))          # 0: throughput family for every B; default: latency family here
             p32 = O.init_params(nz, width, depth, seed=1000 + case, fcz_std=0.05, all_std=float(rs.choice([0.0, 0.02])))
+            coupling = int(rs2.randint(0, 2))
+            form = str(rs2.choice(["inplace", "split", "misaligned"]))
+            cut = int(rs2.randint(1, max(depth, 2)))                       # split: blocks [0, cut) + [cut, depth)
+            mis_tensor, mis_off = str(rs2.choice(["z_in", "z_out", "z_saved"])), int(rs2.choice([1, 2]))
+            if coupling == 0:                    # additive: fc_zeros maps to the nz/2 shifts only (model.py:385)
+                for i in range(depth):
+                    for k in ("f.fc_zeros.w", "f.fc_zeros.b", "f.fc_zeros.logs"):
+                        p32[O.block_prefix(i) + k] = p32[O.block_prefix(i) + k][:, : nz // 2].contiguous()
             p64 = O.to_dtype(p32, torch.float64)
             z = kink_free_batch(p32, B, nz, seed=case)         # every row away from a ReLU kink (gradients are discontinuous there)
             obj0 = torch.randn(B, generator=torch.Generator().manual_seed(case + 7)).float()
             gg = torch.randn(B, nz, generator=torch.Generator().manual_seed(case + 11)).float()
             noise_t = torch.randn(B, nz, generator=torch.Generator().manual_seed(case + 13)).float()
             step = float(rs.choice([0.1, 0.3]))
-            z1_ref, ld_ref, ll_ref = O.flow_log_prob(p64, z.double())
-            gz_ref = O.grad_neg_sum_ll_wrt_z(p64, z.double())
-            x_ref, xobj_ref = O.flow_reverse(p64, z.double(), obj0.double())
-            gp_ref = O.grad_neg_mean_ll_wrt_params(p64, z.double())
+            z1_ref, ld_ref, ll_ref = O.flow_log_prob(p64, z.double(), coupling)
+            gz_ref = O.grad_neg_sum_ll_wrt_z(p64, z.double(), coupling)
+            x_ref, xobj_ref = O.flow_reverse(p64, z.double(), obj0.double(), coupling)
+            gp_ref = O.grad_neg_mean_ll_wrt_params(p64, z.double(), coupling)
             params = flow.params_from_state_dict(p32, depth, dev)
             try:
-                plan = flow.prepare(params, nz, width, depth)
+                plan = flow.prepare(params, nz, width, depth, coupling)
             except lsnf_amd.LsnfError as e:
                 print("unsupported geometry", nz, width, depth, e)
                 continue
@@ -78,7 +147,7 @@ def run(n_cases, seed, batches=BATCHES):
             flow.set_small_batch_max(small_max)
             for mode in (flow.MATH_FP32, flow.MATH_BF16X3, flow.MATH_BF16X3_PHASED, flow.MATH_FP16X2):
                 flow.set_math_mode(mode)
-                tag = f"case{case} nz={nz} w={width} d={depth} B={B} small_max={small_max} mode={mode}"
+                tag = f"case{case} nz={nz} w={width} d={depth} c={coupling} B={B} small_max={small_max} mode={mode}"
                 for stash in (False, True):
                     act = flow.new_act_saved(plan, B, dev) if stash else None
                     z1, ld, ll, saved = flow.forward(plan, zd, None, want_ll=True, save_for_backward=True, act_saved=act)
@@ -108,6 +177,8 @@ def run(n_cases, seed, batches=BATCHES):
                 zb, ob = flow.reverse(plan, z1, ld)
                 check(tag, "roundtrip_z", zb, z.double(), 5e-5)
                 check(tag, "roundtrip_obj", ob, obj0.double() if B > 1 or abs(float(obj0[0])) > 1e-2 else ob.double().cpu(), 5e-4)
+                call_form(tag + " " + form, form, plan, zd, od, cut, mis_tensor, mis_off,
+                          dict(z1=z1_ref, ld=ld_ref, ll=ll_ref, gz=gz_ref, x=x_ref, xobj=-xobj_ref, obj=obj0.double()))
                 # parameter gradients: the recomputing path, and in the bf16x3-family modes also the fast path (the forward keeps
                 # the stash and writes h1 / h2 into the workspace, the backward runs from them)
                 keys = [O.block_prefix(i) + k for i in range(depth) for k in flow.BLOCK_PARAM_KEYS]
@@ -121,7 +192,7 @@ def run(n_cases, seed, batches=BATCHES):
                         if float(ref.abs().max()) < 1e-6:
                             continue
                         check(tag + (" fast" if fast else ""), "dparam " + k, g, ref, 1e-4)
-            print(f"case {case} done: nz={nz} w={width} d={depth} B={B} small_max={small_max}  ({checks} checks, {len(fails)} failures, "
+            print(f"case {case} done: nz={nz} w={width} d={depth} c={coupling} {form} B={B} small_max={small_max}  ({checks} checks, {len(fails)} failures, "
                   f"{time.time() - t00:.0f} s)", flush=True)
 
     finally:
