@@ -207,6 +207,20 @@ int lsnf_backward_z(const float* plan, int nz, int width, int depth, int couplin
                     const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
                     float* g_z_in, void* stream);
 
+/* ---- backward of lsnf_reverse w.r.t. its inputs (autograd through the sampling direction, model.py:484-498) ----
+ * With f the forward stack, x = f^-1(y) = the z_out of lsnf_reverse and objective_out = objective - logdet_f(x):
+ *     g_z_in = J_f(x)^-T (g_x - g_objective * grad_x logdet_f(x)),      dL/d objective = g_objective itself.
+ * z_out / z_saved / act_saved: what lsnf_forward (whole stack, with the stash) wrote when run on x; act_saved is required
+ * (lsnf_restash can rebuild it) and may come from any kernel family / math mode.
+ * g_x = dL/dx (B,nz) or NULL (= 0); g_objective = dL/d objective_out (B) or NULL (= 0); g_z_in (B,nz) may be g_x itself.
+ * The parameter gradients of the reverse need no entry point of their own: they are lsnf_backward_params of the FORWARD
+ * evaluated at x with upstream gradients g_z1 = -g_z_in, g_logdet = -g_objective (implicit-function theorem).
+ * One kernel and one arithmetic (bf16x3, not narrower than fp32) under every lsnf_set_math_mode and for every B;
+ * lsnf_set_small_batch_max does not affect it. */
+int lsnf_reverse_backward_z(const float* plan, int nz, int width, int depth, int coupling, int B,
+                            const float* z_out, const float* z_saved, const float* act_saved,
+                            const float* g_x, const float* g_objective, float* g_z_in, void* stream);
+
 /* The activation stash of a forward that was run WITHOUT one (act_saved = NULL), rebuilt from its block outputs: the
  * coupling MLP's input is the first half of the block's output (model.py:422), so sigmoid(p) and the two ReLU masks follow
  * from z_out / z_saved alone (S2, S3 and the pre-sigmoid half of S4 per block; blocks in parallel).  lsnf_restash + the

@@ -41,6 +41,8 @@ _SIGNATURES = {
                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lsnf_backward_z": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p]),
+    "lsnf_reverse_backward_z": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lsnf_langevin_step": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(LsnfRng), c_float,
                                    c_void_p, c_void_p, c_void_p, c_void_p]),

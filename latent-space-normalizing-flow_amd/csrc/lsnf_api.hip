@@ -78,6 +78,10 @@ hipError_t lsnf_launch_small3_backward_z(const LsnfGeo& g, const float* plan, in
                                          const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode,
                                          float ll_scale, float* g_z_in, int vec4, int st, hipStream_t stream,
                                          const LsnfLangevinArgs* lv, float* dump, double* gl_total);
+int lsnf_small3_reverse_backward_st(const LsnfGeo& g, int B);
+hipError_t lsnf_launch_small3_reverse_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
+                                                 const float* act_saved, const float* g_x, const float* g_obj, float* g_z_in,
+                                                 int vec4, int st, hipStream_t stream);
 hipError_t lsnf_launch_backward3_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
                                    const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
                                    float* g_z_in, int vec4, hipStream_t stream, const LsnfLangevinArgs* lv,
@@ -173,6 +177,7 @@ enum Kernel {
     K_NONE, K_FWD, K_FWD3, K_FWD3Q, K_FWD2H_FIXUP, K_SMALL_FWD, K_SMALL3_FWD,
     K_REV, K_REV3, K_REV2H_FIXUP, K_SMALL_REV, K_SMALL3_REV,
     K_BWD, K_BWD3, K_SMALL_BWD, K_SMALL3_BWD,
+    K_SMALL3_RBWD,
 };
 const char* const kKernelName[] = {
     "no kernel takes this call", "lsnf_fwd_kernel", "lsnf_fwd3b_kernel", "lsnf_fwd3q_kernel",
@@ -180,6 +185,7 @@ const char* const kKernelName[] = {
     "lsnf_rev_kernel", "lsnf_rev3_kernel", "lsnf_rev2h_kernel + lsnf_rev3_kernel fix-up", "lsnf_small_rev_kernel",
     "lsnf_small3_rev_kernel",
     "lsnf_bwd_z_kernel", "lsnf_bwd3_kernel", "lsnf_small_bwd_kernel", "lsnf_small3_bwd_kernel",
+    "lsnf_small3_rbwd_kernel",
 };
 struct Pick { Kernel k; int st = 0; };     // st: rows per workgroup / 16 of the small3 kernels
 
@@ -272,6 +278,11 @@ hipError_t launch_backward(Pick p, const LsnfGeo& g, const float* plan, int B, c
                                       vec4, stream, lv, act_saved);
     }
 }
+
+// Backward of the reverse pass (lsnf_reverse_backward_z): one kernel (lsnf_small3_rbwd.hip) whose bf16x3 arithmetic is not narrower
+// than fp32, so it serves every math mode; its workgroup shape follows the batch size alone (more rounds of workgroups above
+// 16 384 rows), not the small-batch threshold -- it reads the stash of whichever forward family the threshold selected.
+Pick select_reverse_backward(const LsnfGeo& g, int B) { return {K_SMALL3_RBWD, lsnf_small3_reverse_backward_st(g, B)}; }
 
 // Batch contraction of the parameter gradients (LsnfContraction): on the bf16 matrix pipe where lsnf_params3.hip covers the
 // call (use_x3); from 4 096 rows the fp32-MFMA kernel through LDS, with the widest row loads the rows allow -- every row the
@@ -538,6 +549,27 @@ int lsnf_backward_z(const float* plan, int nz, int width, int depth, int couplin
         : launch_backward(p, g, plan, B, z_out, z_saved, act_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in, vec4,
                           (hipStream_t)stream, nullptr);
     if (p.k == K_NONE || e != hipSuccess) return launch_fail(e, "lsnf_backward_z", p.k);
+    return LSNF_OK;
+}
+
+int lsnf_reverse_backward_z(const float* plan, int nz, int width, int depth, int coupling, int B, const float* z_out,
+                            const float* z_saved, const float* act_saved, const float* g_x, const float* g_objective,
+                            float* g_z_in, void* stream) {
+    LsnfGeo g;
+    if (int rc = geo_or_fail(&g, nz, width, depth, coupling)) return rc;
+    if (B < 0 || B > (1 << 28)) return fail(LSNF_E_ARG, "lsnf_reverse_backward_z: B=%d out of range", B);
+    if (B == 0) return LSNF_OK;
+    if (!plan || !z_out || !g_z_in || (depth > 1 && !z_saved)) return fail(LSNF_E_ARG, "lsnf_reverse_backward_z: NULL argument");
+    if (!act_saved) return fail(LSNF_E_ARG, "lsnf_reverse_backward_z: act_saved is required (lsnf_forward's stash, or lsnf_restash)");
+    if (!aligned16(plan)) return fail(LSNF_E_ARG, "lsnf_reverse_backward_z: plan must be 16-byte aligned");
+    if (!aligned16(act_saved)) return fail(LSNF_E_ARG, "lsnf_reverse_backward_z: act_saved must be 16-byte aligned");
+    if (!aligned4(z_out) || !aligned4(z_saved) || !aligned4(g_x) || !aligned4(g_objective) || !aligned4(g_z_in))
+        return fail(LSNF_E_ARG, "lsnf_reverse_backward_z: tensors must be 4-byte aligned");
+    const int vec4 = row_vector_width(g, {z_out, g_z_in, z_saved, g_x});
+    const Pick p = select_reverse_backward(g, B);
+    const hipError_t e = lsnf_launch_small3_reverse_backward_z(g, plan, B, z_out, z_saved, act_saved, g_x, g_objective, g_z_in, vec4,
+                                                               p.st, (hipStream_t)stream);
+    if (e != hipSuccess) return launch_fail(e, "lsnf_reverse_backward_z", p.k);
     return LSNF_OK;
 }
 

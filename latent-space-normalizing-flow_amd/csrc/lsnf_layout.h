@@ -68,6 +68,8 @@ struct LsnfGeo {
     size_t off_i2h_panels;
     size_t off_guard;           // LSNF_GUARD_WORDS 32-bit words; [0] = 1 if a folded weight is outside fp16's range (set by
                                 // lsnf_prepare, read-only afterwards): the fp16 kernels then leave every row to the fix-up pass
+    int t3_block_floats;        // transposed inverse panel T1 = Winv'^T (lsnf_small3_rbwd.hip: the backward of the REVERSE pass) as three
+    size_t off_t3b_panels;      // bf16 matrices, 16x16x32 operand order; behind the guard words: every older region keeps its offset
     size_t total_floats;
 };
 
@@ -112,6 +114,8 @@ static inline int lsnf_pick_tiles(int half, int width, int* HT, int* WT) {
 //   B3  g_h1 = W2' g_a2             K = WT,   N = WT
 //   B2  g_v1 += W1' g_a1            K = WT,   N = HT
 //   B1  g_x  = Wa [g_v1; g_v2]      K = NZT,  N = NZT
+// Backward of the REVERSE pass per block (lsnf_small3_rbwd.hip; blocks first to last, given g on the block's input x):
+//   T1  g_v  = Winv' g              K = NZT,  N = NZT   (the transpose of I1), then B4, B3, B2 with the coupling's inverse Jacobian
 static inline int lsnf_geo_init(LsnfGeo* g, int nz, int width, int depth, int coupling) {
     if (nz < 2 || (nz & 1) || nz > 128 || width < 1 || width > 128 || depth < 1 || depth > LSNF_MAX_DEPTH) return -1;
     if (coupling != 0 && coupling != 1) return -1;
@@ -155,6 +159,8 @@ static inline int lsnf_geo_init(LsnfGeo* g, int nz, int width, int depth, int co
     g->off_i2h_panels = o; o += (size_t)depth * g->i2h_block_floats;
     o = (o + 255) & ~(size_t)255;
     g->off_guard = o; o += 256;
+    g->t3_block_floats = LSNF_FRAG3_FLOATS * (NZT * NZT);
+    g->off_t3b_panels = o; o += (size_t)depth * g->t3_block_floats;
     g->total_floats = o;
     return 0;
 }

@@ -449,6 +449,21 @@ __global__ __launch_bounds__(256) void lsnf_pack_kernel(LsnfParamPtrs pp, LsnfGe
             reinterpret_cast<unsigned*>(plan + g.off_guard)[0] = 1u;
         dst[q] = f16_part_bits(v[0], part) | (f16_part_bits(v[1], part) << 16);
     }
+    // ---- split-bf16 transposed inverse panel T1 (lsnf_small3_rbwd.hip): g_v[n] = sum_k Winv'[n][k] g[k], i.e. the matrix of I1
+    //      with k and n exchanged (as B1 is S1's), from the same float64 inverse, rounded once; 16x16x32 operand order
+    for (int q = blockIdx.x * 256 + threadIdx.x; q < g.t3_block_floats; q += gridDim.x * 256) {
+        unsigned* dst = reinterpret_cast<unsigned*>(plan + g.off_t3b_panels + (size_t)blk * g.t3_block_floats);
+        int k0, k1, n, part;
+        frag3b_decode(q, NZT, &k0, &k1, &n, &part);
+        const SplitIdx sn = split_nat(n, HT, g.half);
+        double v[2] = {0.0, 0.0};
+        const int ks[2] = {k0, k1};
+        for (int i = 0; i < 2; ++i) {
+            const SplitIdx sk = split_nat(ks[i], HT, g.half);
+            if (sk.ok && sn.ok) v[i] = sb[(size_t)sn.nat * nz + sk.nat] * exp(-(double)(P[P_ALOGS][sk.nat] * 3.0f));
+        }
+        dst[q] = bf16_part_bits(v[0], part) | (bf16_part_bits(v[1], part) << 16);
+    }
 }
 
 size_t lsnf_prep_scratch_bytes(int nz, int depth) { return sizeof(double) * scratch_block_doubles(nz) * (size_t)depth; }

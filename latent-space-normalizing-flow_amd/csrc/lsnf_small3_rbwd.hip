@@ -1,0 +1,313 @@
+// lsnf_small3_rbwd.hip -- backward of the REVERSE (sampling) pass w.r.t. its input, on the bf16 matrix pipe: the sibling of
+// lsnf_small3_bwd.hip (workgroups of ST sample tiles of 16 rows, L16 layout, producer-side bf16x3 split, weights re-loaded in
+// place one block ahead: lsnf_small3.h units_mma_st).  With f the forward stack, x = f^-1(y) the reverse and
+// o_out = o_in - logdet_f(x):   g_y = J_f(x)^-T (g_x - g_o grad_x logdet_f(x)).
+// The MLP input of a block is the first half of its forward OUTPUT in both directions (model.py:404,422,426), so sigma and the
+// two ReLU masks are the activation stash of lsnf_forward run on x (or lsnf_restash of its block outputs), whichever kernel
+// family wrote it.
+//
+// Per block, FIRST to LAST; wave w owns the half-units g1[w], g2[w] of the running gradient (registers); [y1 | y2] = the block's
+// forward output, Winv' = W^-1 diag(exp(-3 logs)) the matrix of the inverse stage I1:
+//   T1 : g_v  = Winv' g                              (off_t3b_panels: the transpose of I1)            G   -> registers
+//   CB': s = sigma (stash); g_y2 = g_v2 / s ; g_t = -g_v2 ; g_p = -(1 - s)(g_y2 * y2 + g_o): this wave's own T1 output and
+//        stash slice, so it runs as T1's epilogue (under the next sample tile's MFMAs)               -> GTP, G[second half, other buffer]
+//   B4 : g_a2 = (W3s g_t + W3p g_p) * [h2 > 0]       (off_b3b_panels, masks: stash)                   GTP -> GA2
+//   B3 : g_a1 = (W2' g_a2) * [h1 > 0]                                                                 GA2 -> GA1
+//   B2 : g_y1 = g_v1 + W1' g_a1                                                                       GA1 -> G[first half]
+// Four barriers per block.  Additive coupling: the stash holds sigma = 1 exactly, so g_y2 = g_v2 and g_p = 0.
+//
+// ONE arithmetic for every lsnf_set_math_mode: bf16x3 is not narrower than fp32, so this kernel also serves LSNF_MATH_FP32 and
+// LSNF_MATH_FP16X2.  ONE form for every batch size: above 16 384 rows the grid simply runs more rounds of workgroups;
+// lsnf_set_small_batch_max does not affect it.  A row's result does not depend on the batch size or on ST (MFMA columns are
+// independent, the split and the coupling arithmetic are compiled without fp contraction).
+#include <stdlib.h>
+#include "lsnf_small3.h"
+
+namespace {
+
+template <int HT_, int WT_>
+struct Small3RbwdCfg : LsnfStackCfg<HT_, WT_> {
+    using S = LsnfStackCfg<HT_, WT_>;
+    static constexpr int F = LSNF_FRAG3_FLOATS;
+    static constexpr int OFFB4 = 0;                                       // inside a block of off_b3b_panels (B4, B3, B2, B1)
+    static constexpr int OFFB3 = OFFB4 + F * WT_ * 2 * HT_;
+    static constexpr int OFFB2 = OFFB3 + F * WT_ * WT_;
+    static constexpr int BLOCKB = OFFB2 + F * HT_ * WT_ + F * S::NZT * S::NZT;
+    static constexpr int BLOCKT = F * S::NZT * S::NZT;                    // a block of off_t3b_panels
+    static constexpr int NU2 = (2 * WT_ + 3) / 4;
+};
+// LDS map (floats) for ST sample tiles: GTP (g_t | g_p: 2HT B-tiles per sample tile; g_a1 reuses its front once B4 has read it),
+// GA2 (WT), G first half (HT), G second half (HT, double-buffered: the coupling of T1's epilogue writes the next block's input
+// while other waves still read this block's)
+template <class C, int ST>
+struct Small3RbwdLds {
+    static constexpr int TP = 2 * C::HT * S3_BTILE_FLOATS, HL = C::WT * S3_BTILE_FLOATS, GH = C::HT * S3_BTILE_FLOATS;
+    static_assert(C::WT <= 2 * C::HT, "g_a1 is kept in the front of the g_t | g_p tiles");
+    static constexpr int L_GTP = 0;
+    static constexpr int L_GA2 = L_GTP + ST * TP;
+    static constexpr int L_GVA = L_GA2 + ST * HL;
+    static constexpr int L_GVB = L_GVA + ST * GH;
+    static constexpr int L_END = L_GVB + 2 * ST * GH;
+};
+
+struct Small3RbwdArgs {
+    const float* panels;                 // b3b region, block 0
+    const float* tpanels;                // t3b region, block 0
+    const float* z_out; const float* z_saved; const float* act_saved; const float* g_x; const float* g_obj;
+    float* g_z_in;
+    int B, nz, half, depth, vec4;
+};
+
+__device__ __forceinline__ f32x4 rb_mask4(f32x4 a, unsigned nib) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) a[r] = ((nib >> r) & 1u) ? a[r] : 0.0f;
+    return a;
+}
+__device__ __forceinline__ f32x4 rb_zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
+
+template <class C, int ST>
+__global__ __launch_bounds__(256, 1) void lsnf_small3_rbwd_kernel(const Small3RbwdArgs a) {
+    constexpr int HT = C::HT, WT = C::WT, NZT = C::NZT, NU2 = C::NU2, LASTU = NU2 - 1;
+    using L = Small3RbwdLds<C, ST>;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* GTP = smem + L::L_GTP;
+    float* GA2 = smem + L::L_GA2;
+    float* GA1 = GTP;                                                     // (see Small3RbwdLds)
+    float* GVA = smem + L::L_GVA;
+    float* GVB = smem + L::L_GVB;
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = tid & 63, n = lane & 15, g = lane >> 4;
+    const int vec4 = a.vec4;
+
+    // a wave without a unit of its own (HT = 1: waves 2, 3) computes unit 0 again and stores the same values to the same LDS
+    // words: no branch in the stages (global stores stay under has1)
+    const bool has1 = wave < 2 * HT;
+    const int hu1 = has1 ? wave : 0, nt1 = hu1 >> 1, ft1 = hu1 & 1;
+    int hw[NU2];
+#pragma unroll
+    for (int i = 0; i < NU2; ++i) hw[i] = (wave + 4 * i < 2 * WT) ? wave + 4 * i : 0;
+
+    const int last = a.depth - 1;
+    long sample[ST]; bool live[ST]; long row[ST];
+    size_t wtile[ST]; int lane32[ST];
+#pragma unroll
+    for (int st = 0; st < ST; ++st) {
+        const size_t q = (size_t)blockIdx.x * ST + st;                    // 16-row tile q = half (q & 1) of the 32-sample stash tile q >> 1
+        sample[st] = (long)q * S3_SAMPLES + n;
+        live[st] = sample[st] < a.B;
+        row[st] = live[st] ? sample[st] : (long)a.B - 1;
+        wtile[st] = ((long)q * S3_SAMPLES < (long)a.B) ? (q >> 1) : 0;    // (a tile past the batch reads stash tile 0: never stored)
+        lane32[st] = 16 * (int)(q & 1) + n + 32 * (g & 1);
+    }
+    const LsnfActLayout al = lsnf_act_layout(a.B, HT, WT);
+    const int nibsh_base = 4 * (g >> 1);                                   // + 8*ft: bit offset of this lane's nibble in a mask word
+
+    // a block's stash slice and block output (this wave's second-half unit), fetched one block ahead of their use
+    f32x4 y2[ST], sg[ST]; unsigned m1[NU2][ST], m2[NU2][ST];
+    auto fetch_block_state = [&](int blk) {
+#pragma unroll
+        for (int st = 0; st < ST; ++st) {
+            const float* act = a.act_saved + (size_t)blk * al.per_block + wtile[st] * al.per_tile;
+            const float* ysrc = (blk == a.depth - 1) ? a.z_out + row[st] * (long)a.nz : a.z_saved + ((size_t)blk * a.B + row[st]) * a.nz;
+            y2[st] = load_row_half<HT>(HT + nt1, ft1, ysrc, a.half, g, vec4);
+            sg[st] = reinterpret_cast<const f32x4*>(act + (size_t)nt1 * 1024)[(2 * ft1 + (g >> 1)) * 64 + lane32[st]];
+            const unsigned* words = reinterpret_cast<const unsigned*>(act + al.mask_off);
+#pragma unroll
+            for (int i = 0; i < NU2; ++i) {
+                const int nt = hw[i] >> 1, ft = hw[i] & 1;
+                m1[i][st] = (words[nt * 64 + lane32[st]] >> (nibsh_base + 8 * ft)) & 0xFu;
+                m2[i][st] = (words[(WT + nt) * 64 + lane32[st]] >> (nibsh_base + 8 * ft)) & 0xFu;
+            }
+        }
+    };
+    // what the gradient needs first goes out first (vmcnt completes in order): the upstream gradient, the first block's stash
+    // slice, then the weights in order of use
+    float go[ST];
+    f32x4 g1[ST], g2[ST];
+#pragma unroll
+    for (int st = 0; st < ST; ++st) {
+        go[st] = a.g_obj ? a.g_obj[row[st]] : 0.0f;
+        if (a.g_x) {
+            g1[st] = load_row_half<HT>(nt1, ft1, a.g_x + row[st] * (long)a.nz, a.half, g, vec4);
+            g2[st] = load_row_half<HT>(HT + nt1, ft1, a.g_x + row[st] * (long)a.nz, a.half, g, vec4);
+        } else { g1[st] = rb_zero4(); g2[st] = rb_zero4(); }
+    }
+    fetch_block_state(0);
+    __builtin_amdgcn_sched_barrier(0);
+    UFrags<NZT> wt1a = fetch_unit<NZT>(a.tpanels, nt1, ft1, lane);
+    UFrags<NZT> wt1b = fetch_unit<NZT>(a.tpanels, HT + nt1, ft1, lane);
+    UFrags<2 * HT> wb4[NU2];
+    UFrags<WT> wb3[NU2];
+#pragma unroll
+    for (int i = 0; i < NU2; ++i) wb4[i] = fetch_unit<2 * HT>(a.panels + C::OFFB4, hw[i] >> 1, hw[i] & 1, lane);
+#pragma unroll
+    for (int i = 0; i < NU2; ++i) wb3[i] = fetch_unit<WT>(a.panels + C::OFFB3, hw[i] >> 1, hw[i] & 1, lane);
+    UFrags<WT> wb2 = fetch_unit<WT>(a.panels + C::OFFB2, nt1, ft1, lane);
+    __builtin_amdgcn_sched_barrier(0);
+
+    // the upstream gradient as the first block's T1 operand (buffer 0 of the second half)
+#pragma unroll
+    for (int st = 0; st < ST; ++st) {
+        store_half(GVA + st * L::GH + nt1 * S3_BTILE_FLOATS, ft1, g1[st], lane);
+        store_half(GVB + st * L::GH + nt1 * S3_BTILE_FLOATS, ft1, g2[st], lane);
+    }
+    __syncthreads();
+
+    f32x4 gv1[ST], gv2[ST];
+    for (int blk = 0; blk <= last; ++blk) {
+        const int nb = blk < last ? blk + 1 : last;                         // the last block re-fetches its own panels: no loads under a branch
+        const float* gb = a.panels + (size_t)blk * C::BLOCKB;
+        const float* gbn = a.panels + (size_t)nb * C::BLOCKB;
+        const float* tbn = a.tpanels + (size_t)nb * C::BLOCKT;
+        float* gvb_cur = GVB + (blk & 1) * ST * L::GH;
+        float* gvb_nxt = GVB + ((blk + 1) & 1) * ST * L::GH;
+
+        // ---- T1: g_v = Winv' g; under its last steps: the inverse coupling's Jacobian (CB') ----
+        {
+#pragma unroll
+            for (int st = 0; st < ST; ++st) { gv1[st] = rb_zero4(); gv2[st] = rb_zero4(); }
+            auto coupling = [&](int st) {
+#pragma clang fp contract(off)
+                f32x4 gt, gp, gy;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    gy[r] = gv2[st][r] / sg[st][r];
+                    gt[r] = -gv2[st][r];
+                    gp[r] = -((1.0f - sg[st][r]) * (gy[r] * y2[st][r] + go[st]));
+                }
+                g2[st] = gy;
+                store_half(GTP + st * L::TP + nt1 * S3_BTILE_FLOATS, ft1, gt, lane);
+                store_half(GTP + st * L::TP + (HT + nt1) * S3_BTILE_FLOATS, ft1, gp, lane);
+                store_half(gvb_nxt + st * L::GH + nt1 * S3_BTILE_FLOATS, ft1, gy, lane);         // the next block's T1 operand
+            };
+            // carry: the last k-tile of B2's unit, THIS block's fragments (B2 runs last in a block)
+            const bf16x8* cp = unit_ptr<WT>(gb + C::OFFB2, nt1, ft1, lane);
+            units_mma_st<NZT, 0, NZT, ST, 2, 48, 3, 0, HT>(gv1, gv2, wt1a, wt1b, unit_ptr<NZT>(tbn, nt1, ft1, lane),
+                unit_ptr<NZT>(tbn, HT + nt1, ft1, lane), GVA, L::GH, lane,
+                [&](int st) { coupling(st); },
+                [&](int q) { refill_last<WT>(wb2, cp, q); }, [](int) {}, gvb_cur);
+        }
+        __syncthreads();
+        // ---- B4: g_a2 = ([W3s W3p][g_t; g_p]) gated by h2 > 0 ----
+#pragma unroll
+        for (int i = 0; i < NU2; ++i) {
+            const int nt = hw[i] >> 1, ft = hw[i] & 1;
+            f32x4 ga[ST];
+#pragma unroll
+            for (int st = 0; st < ST; ++st) ga[st] = rb_zero4();
+            auto epi = [&](int st) {
+                ga[st] = rb_mask4(ga[st], m2[i][st]);
+                store_half(GA2 + st * L::HL + nt * S3_BTILE_FLOATS, ft, ga[st], lane);
+            };
+            const bf16x8* rf = unit_ptr<2 * HT>(gbn + C::OFFB4, nt, ft, lane);
+            if (i == 0) {        // carry: the last k-tile of T1's two units (next block's fragments)
+                const bf16x8* c1a = unit_ptr<NZT>(tbn, nt1, ft1, lane);
+                const bf16x8* c1b = unit_ptr<NZT>(tbn, HT + nt1, ft1, lane);
+                units_mma_st<2 * HT, 0, 2 * HT, ST, 1, 26, 6, 0>(ga, ga, wb4[i], wb4[i], rf, nullptr, GTP, L::TP, lane, epi,
+                    [&](int q) { if (q < 3) refill_last<NZT>(wt1a, c1a, q); else refill_last<NZT>(wt1b, c1b, q - 3); }, [](int) {});
+            } else {
+                const bf16x8* cp = unit_ptr<2 * HT>(gbn + C::OFFB4, hw[i > 0 ? i - 1 : 0] >> 1, hw[i > 0 ? i - 1 : 0] & 1, lane);
+                units_mma_st<2 * HT, 0, 2 * HT, ST, 1, 26, 3, 0>(ga, ga, wb4[i], wb4[i], rf, nullptr, GTP, L::TP, lane, epi,
+                    [&](int q) { refill_last<2 * HT>(wb4[i > 0 ? i - 1 : 0], cp, q); }, [](int) {});
+            }
+        }
+        __syncthreads();
+        // ---- B3: g_a1 = (W2' g_a2) gated by h1 > 0 ----
+#pragma unroll
+        for (int i = 0; i < NU2; ++i) {
+            const int nt = hw[i] >> 1, ft = hw[i] & 1;
+            f32x4 ga[ST];
+#pragma unroll
+            for (int st = 0; st < ST; ++st) ga[st] = rb_zero4();
+            auto epi = [&](int st) {
+                ga[st] = rb_mask4(ga[st], m1[i][st]);
+                store_half(GA1 + st * L::TP + nt * S3_BTILE_FLOATS, ft, ga[st], lane);
+            };
+            const bf16x8* rf = unit_ptr<WT>(gbn + C::OFFB3, nt, ft, lane);
+            if (i == 0) {        // carry: the last k-tile of B4's last unit (next block's fragments)
+                const bf16x8* cp = unit_ptr<2 * HT>(gbn + C::OFFB4, hw[LASTU] >> 1, hw[LASTU] & 1, lane);
+                units_mma_st<WT, 0, WT, ST, 1, 26, 3, 0>(ga, ga, wb3[i], wb3[i], rf, nullptr, GA2, L::HL, lane, epi,
+                    [&](int q) { refill_last<2 * HT>(wb4[LASTU], cp, q); }, [](int) {});
+            } else {
+                const bf16x8* cp = unit_ptr<WT>(gbn + C::OFFB3, hw[i > 0 ? i - 1 : 0] >> 1, hw[i > 0 ? i - 1 : 0] & 1, lane);
+                units_mma_st<WT, 0, WT, ST, 1, 26, 3, 0>(ga, ga, wb3[i], wb3[i], rf, nullptr, GA2, L::HL, lane, epi,
+                    [&](int q) { refill_last<WT>(wb3[i > 0 ? i - 1 : 0], cp, q); }, [](int) {});
+            }
+        }
+        __syncthreads();
+        // ---- B2: g_y1 = g_v1 (direct) + W1' g_a1.  The next block's stash slice / output rows are requested here ----
+        fetch_block_state(nb);                                             // (this block's are consumed: CB' ran in T1, the masks in B4 / B3)
+        {
+#pragma unroll
+            for (int st = 0; st < ST; ++st) g1[st] = gv1[st];
+            const bf16x8* cp = unit_ptr<WT>(gbn + C::OFFB3, hw[LASTU] >> 1, hw[LASTU] & 1, lane);
+            units_mma_st<WT, 0, WT, ST, 1, 24, 3, 0>(g1, g1, wb2, wb2, unit_ptr<WT>(gbn + C::OFFB2, nt1, ft1, lane), nullptr, GA1, L::TP, lane,
+                [&](int st) { store_half(GVA + st * L::GH + nt1 * S3_BTILE_FLOATS, ft1, g1[st], lane); },   // (after the last block: nobody reads it)
+                [&](int q) { refill_last<WT>(wb3[LASTU], cp, q); }, [](int) {});
+        }
+        __syncthreads();
+    }
+
+    // ---- output: g on the reverse's input ----
+    if (has1) {
+#pragma unroll
+        for (int st = 0; st < ST; ++st) {
+            if (live[st]) {
+                float* gr = a.g_z_in + sample[st] * (long)a.nz;
+                store_row_half<HT>(nt1, ft1, g1[st], gr, a.half, g, vec4);
+                store_row_half<HT>(HT + nt1, ft1, g2[st], gr, a.half, g, vec4);
+            }
+        }
+    }
+}
+
+// (shapes that do not fit are not instantiated; the LDS footprint does not depend on the depth, and ST = 1 always fits)
+template <class C, int ST>
+constexpr bool small3_rbwd_built = (size_t)Small3RbwdLds<C, ST>::L_END * sizeof(float) <= 160 * 1024;
+static_assert(small3_rbwd_built<Small3RbwdCfg<1, 1>, 1> && small3_rbwd_built<Small3RbwdCfg<2, 2>, 1> && small3_rbwd_built<Small3RbwdCfg<2, 4>, 1>);
+
+template <class C, int ST>
+hipError_t launch_small3_rbwd_st(const Small3RbwdArgs& a, hipStream_t stream) {
+    if constexpr (!small3_rbwd_built<C, ST>) {
+        return hipErrorInvalidValue;                 // (a selection bug)
+    } else {
+        const size_t lds = (size_t)Small3RbwdLds<C, ST>::L_END * sizeof(float);
+        auto kern = lsnf_small3_rbwd_kernel<C, ST>;
+        static unsigned long long lds_ok = 0;
+        if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
+        const unsigned grid = (unsigned)((a.B + ST * S3_SAMPLES - 1) / (ST * S3_SAMPLES));
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, a);
+        return hipGetLastError();
+    }
+}
+}  // namespace
+
+// Rows per workgroup (16 x ST) for this call (host only, no HIP calls; lsnf_api.hip selects by it): by batch size as the backward
+// from the stash (lsnf_small3_backward_st), LSNF_SMALL3_ST forces a shape; a shape that is not instantiated gives way to the next
+// smaller one.  Never 0: the kernel takes every call.
+int lsnf_small3_reverse_backward_st(const LsnfGeo& g, int B) {
+    static const char* env = getenv("LSNF_SMALL3_ST");
+    return lsnf_with_cfg<Small3RbwdCfg>(g, [&](auto c) {
+        using C = decltype(c);
+        const int st = env ? atoi(env) : (B <= 256 * 16 ? 1 : (B <= 256 * 32 ? 2 : 4));
+        return (st >= 4 && small3_rbwd_built<C, 4>) ? 4 : (st >= 2 && small3_rbwd_built<C, 2>) ? 2 : 1;
+    });
+}
+
+// st: lsnf_small3_reverse_backward_st of the call
+hipError_t lsnf_launch_small3_reverse_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
+                                                 const float* act_saved, const float* g_x, const float* g_obj, float* g_z_in,
+                                                 int vec4, int st, hipStream_t stream) {
+    if (!act_saved || !g_z_in || B < 1) return hipErrorInvalidValue;     // (a selection bug)
+    Small3RbwdArgs a;
+    a.panels = plan + g.off_b3b_panels;
+    a.tpanels = plan + g.off_t3b_panels;
+    a.z_out = z_out; a.z_saved = z_saved; a.act_saved = act_saved; a.g_x = g_x; a.g_obj = g_obj; a.g_z_in = g_z_in;
+    a.B = B; a.nz = g.nz; a.half = g.half; a.depth = g.depth; a.vec4 = vec4;
+    return lsnf_with_cfg<Small3RbwdCfg>(g, [&](auto c) {
+        using C = decltype(c);
+        return st == 4 ? launch_small3_rbwd_st<C, 4>(a, stream) : st == 2 ? launch_small3_rbwd_st<C, 2>(a, stream)
+                                                                         : launch_small3_rbwd_st<C, 1>(a, stream);
+    });
+}

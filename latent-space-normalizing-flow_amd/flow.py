@@ -391,6 +391,48 @@ def backward_z(plan: FlowPlan, z_out: torch.Tensor, z_saved: Optional[torch.Tens
     return g_in
 
 
+def reverse_backward_z(plan: FlowPlan, z_out: torch.Tensor, z_saved: Optional[torch.Tensor], act_saved: torch.Tensor,
+                       g_x: Optional[torch.Tensor] = None, g_obj: Optional[torch.Tensor] = None, *,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Backward of `reverse` w.r.t. its input: with x = reverse(eps)[0], returns dL/d eps for upstream gradients g_x = dL/dx
+    (or None = 0) and g_obj = dL/d objective_out (or None = 0); dL/d objective is g_obj itself.
+    z_out / z_saved / act_saved: what `forward(plan, x, save_for_backward=True, act_saved=new_act_saved(...))` returned and
+    filled (the forward evaluated AT x; the stash is required, from any math mode / kernel family).  out: optional (B, nz)
+    buffer for the result, may be g_x itself.  One launch, asynchronous on the current stream.
+    The parameter gradients of the reverse are `backward_params` of that forward with g_z1 = -result, g_logdet = -g_obj."""
+    lib = _lib.load()
+    _need_cuda(z_out, "z_out")
+    if z_out.dim() != 2 or z_out.shape[1] != plan.nz:
+        raise LsnfError(f"z_out must be (B, {plan.nz}), got {tuple(z_out.shape)}")
+    B = z_out.shape[0]
+    if act_saved is None:
+        raise LsnfError("act_saved is required: the stash of forward(plan, x, ..., act_saved=new_act_saved(plan, B, device))")
+    for name, t in (("z_saved", z_saved), ("g_x", g_x), ("g_obj", g_obj), ("act_saved", act_saved)):
+        if t is not None:
+            _need_cuda(t, name)
+            if t.device != z_out.device:
+                raise LsnfError(f"{name} lives on {t.device}, z_out on {z_out.device}")
+    if plan.depth > 1 and B > 0 and z_saved is None:
+        raise LsnfError("z_saved (the block outputs of the forward at x) is required for depth > 1")
+    if z_saved is not None and z_saved.numel() < (plan.depth - 1) * B * plan.nz:
+        raise LsnfError(f"z_saved has {z_saved.numel()} elements, expected {(plan.depth - 1) * B * plan.nz}")
+    if g_x is not None and g_x.shape != z_out.shape:
+        raise LsnfError("g_x must have the shape of z_out")
+    if g_obj is not None and g_obj.numel() != B:
+        raise LsnfError("g_obj must have B elements")
+    need = lib.lsnf_act_saved_floats(plan.nz, plan.width, plan.depth, B)
+    if act_saved.numel() < need:
+        raise LsnfError(f"act_saved has {act_saved.numel()} elements, the stash of {B} rows has {need} (new_act_saved())")
+    g_in = torch.empty_like(z_out) if out is None else out
+    _check_out(g_in, "out (g_z_in)", B * plan.nz, z_out.device)
+    with torch.cuda.device(z_out.device):
+        rc = lib.lsnf_reverse_backward_z(_ptr(plan.buf), plan.nz, plan.width, plan.depth, plan.coupling, B,
+                                         _ptr(z_out), _ptr(z_saved), _ptr(act_saved), _ptr(g_x), _ptr(g_obj), _ptr(g_in),
+                                         _stream_ptr(z_out.device))
+    _lib.check(rc, "lsnf_reverse_backward_z")
+    return g_in
+
+
 class PhiloxNoise:
     """In-kernel N(0,1) noise for `langevin_step` (include/lsnf_flow.h `LsnfRng`): a pure function of
     (seed, offset, row0 + row, column).  `offset` must differ from step to step (`.step()` returns the next one);

@@ -106,10 +106,11 @@ class revnet2d(nn.Module):
 # ---------------------------------------------------------------------------------------------
 class _Upstream:
     """Hand-over between the two autograd nodes below (filled by _FlowStackFn.backward)."""
-    __slots__ = ("g_z1", "g_logdet", "z", "z1", "saved", "plan_key", "act", "ws")
+    __slots__ = ("g_z1", "g_logdet", "z", "z1", "saved", "plan_key", "act", "ws", "empty")
 
     def __init__(self):
         self.g_z1 = self.g_logdet = self.z = self.z1 = self.saved = self.plan_key = self.act = self.ws = None
+        self.empty = False       # set by _FlowReverseFn.backward on an empty batch: the parameters get no gradient
 
 
 class _ParamGate(torch.autograd.Function):
@@ -125,6 +126,8 @@ class _ParamGate(torch.autograd.Function):
     @staticmethod
     def backward(ctx, _g_token):
         h, module = ctx.holder, ctx.module
+        if h.empty:
+            return (None, None) + (None,) * ctx.n
         if h.z1 is None:
             raise LsnfError("parameter gradients requested before the flow's backward ran")
         if module._current_key() != h.plan_key:     # the LIVE parameters, not the key cached at the last _plan() call
@@ -178,6 +181,51 @@ class _FlowStackFn(torch.autograd.Function):
             h.act, h.ws = ctx.act, ctx.ws
             g_tok = z1.new_zeros(())
         return None, None, g_z, g_obj, g_tok
+
+
+class _FlowReverseFn(torch.autograd.Function):
+    """(eps, objective, token) -> (x, objective_out) of the sampling direction.  Forward: the lsnf_reverse launch of the
+    no_grad call (same bits).  Backward: lsnf_forward on the saved x (block outputs + stash), then lsnf_reverse_backward_z for
+    eps; the parameters follow from the implicit-function theorem -- dL/dtheta of the reverse is lsnf_backward_params of the
+    FORWARD at x with upstream gradients (-g_eps, -g_obj) -- so they are handed to _ParamGate like the forward direction's."""
+
+    @staticmethod
+    def forward(ctx, module, holder, z, objective, token):
+        x, obj = flow.reverse(module._plan(), z, objective)
+        ctx.module, ctx.holder = module, holder
+        ctx.plan_key = module._plan_key
+        ctx.obj_shape = objective.shape
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x)
+        return x, obj
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_x, g_obj):
+        module, h = ctx.module, ctx.holder
+        x, = ctx.saved_tensors
+        if module._current_key() != ctx.plan_key:   # (see _FlowStackFn.backward)
+            raise LsnfError("flow parameters were modified between forward and backward")
+        plan = module._plan()
+        B = x.shape[0]
+        g_x = None if g_x is None else g_x.contiguous()
+        g_obj = None if g_obj is None else g_obj.contiguous()
+        h.empty = B == 0                                    # (an empty batch leaves the parameters without a gradient)
+        need_tok = ctx.needs_input_grad[4] and B > 0
+        for_params = need_tok and flow.params_fast_path()
+        act = flow.new_act_saved(plan, B, x.device)
+        ws = flow.new_params_workspace(plan, B, x.device) if for_params else None
+        if ws is not None and x.data_ptr() % 16:
+            x = x.clone()        # the fast path wants 16-byte aligned rows at large B (lsnf_forward, params_workspace)
+        z1, _, _, saved = flow.forward(plan, x, None, want_ll=False, save_for_backward=True, act_saved=act, params_ws=ws)
+        g_eps = flow.reverse_backward_z(plan, z1, saved, act, g_x, g_obj)
+        g_tok = None
+        if need_tok:
+            h.g_z1, h.g_logdet = g_eps.neg(), (None if g_obj is None else g_obj.neg())
+            h.z, h.z1, h.saved, h.plan_key = x, z1, saved, ctx.plan_key
+            h.act, h.ws = act, ws
+            g_tok = z1.new_zeros(())
+        return (None, None, g_eps if ctx.needs_input_grad[2] else None, g_obj.reshape(ctx.obj_shape) if (ctx.needs_input_grad[3] and g_obj is not None) else None, g_tok)
 
 
 class _netF(nn.Module):
@@ -274,10 +322,14 @@ class _netF(nn.Module):
             else:
                 z1, logdet, _, _ = flow.forward(self._plan(), z.detach(), objective.detach(), want_ll=False)
             return z1, logdet, []
-        if torch.is_grad_enabled() and z.requires_grad:
-            raise NotImplementedError("reverse pass is inference-only (the reference calls it under no_grad, "
-                                      "train.py:433-434,473-475,569-571)")
-        x, obj = flow.reverse(self._plan(), z.detach(), objective.detach())
+        if torch.is_grad_enabled() and (z.requires_grad or objective.requires_grad or
+                                        any(p.requires_grad for p in self._param_list())):
+            # differentiable sampling (the reference's reverse is plain eager PyTorch, model.py:424-456,484-498)
+            holder = _Upstream()
+            token = _ParamGate.apply(self, holder, *self._param_list())
+            x, obj = _FlowReverseFn.apply(self, holder, z, objective, token)
+        else:
+            x, obj = flow.reverse(self._plan(), z.detach(), objective.detach())
         if not return_obj:
             return x
         return x, -obj
