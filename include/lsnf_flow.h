@@ -256,6 +256,29 @@ int lsnf_langevin_step(const float* plan, int nz, int width, int depth, int coup
                        const float* grad_g, const float* noise, const LsnfRng* rng, float step_size,
                        float* z_new, float* gf_norm, float* gg_norm, void* stream);
 
+/* ---- fused prior sampling: replaces `sample_x`'s `torch.randn` + `_netF.forward(z, zeros, reverse=True)` ----
+ * (train.py:428-434, 472-478, 567-574).  ONE launch of the lsnf_reverse kernel the batch size selects, in a form that DRAWS its
+ * input rows where lsnf_reverse loads them:
+ *     eps[b][c] = temperature * xi(seed, offset (+ *offset_dev), row0 + b, c)
+ * with xi exactly the N(0,1) draw of lsnf_langevin_step (LsnfRng above; oracle/philox_oracle.py) and the product one fp32
+ * multiply.  A pure function of (seed, offset, global row, column): the same rows whatever B, the kernel family, the math mode
+ * or the sharding -- a rank that samples rows [r0, r1) of a global batch passes row0 = r0, B = r1 - r0 and gets the bits the
+ * one-GPU call has there (in z_out / objective_out / ll_out too, when both calls select the same kernel).
+ *   rng          required; row0 >= 0; offset_dev NULL or an 8-byte aligned device counter (captured graphs).  Not modified:
+ *                use a new offset for every call.
+ *   temperature  finite and >= 0 (the `temp` of train.py:429); 0 gives the flow's image of the origin in every row
+ *   z_out        (B, nz)  x = f^-1(eps): what lsnf_reverse(z_in = eps, objective = NULL) writes, bit for bit
+ *   objective_out(B) or NULL: -logdet_f(x), lsnf_reverse's bits
+ *   eps_out      (B, nz) or NULL: the drawn rows; must not be z_out
+ *   ll_out       (B) or NULL: -0.5*sum_c eps^2 + log(2*pi) - objective_out = log p(x) under the flow prior: lsnf_forward's ll_out
+ *                at x with z1 = eps and logdet = logdet_f(x), without the second pass
+ * Selection, math modes and the fp16x2 fix-up pass as lsnf_reverse (the fix-up pass redraws the rows of the workgroups it
+ * recomputes).  B = 0 succeeds without a launch.  Anything else outside these rules: LSNF_E_ARG.
+ * Added without an ABI bump (a new symbol; nothing existing changed). */
+int lsnf_sample(const float* plan, int nz, int width, int depth, int coupling, int B,
+                const LsnfRng* rng, float temperature,
+                float* z_out, float* objective_out, float* eps_out, float* ll_out, void* stream);
+
 /* ---- backward w.r.t. the parameters: replaces `loss_f.backward()` (train.py:406-411) --------
  * Gradients of L w.r.t. the 12 live tensors of every block (same order as lsnf_prepare), for the
  * upstream gradients described under lsnf_backward_z (train.py:410: L = -mean ll -> ll_mode=1,

@@ -16,7 +16,7 @@ LSNF_PARAMS_PER_BLOCK = 12
 ABI_VERSION = 5
 
 class LsnfRng(ctypes.Structure):
-    """include/lsnf_flow.h `LsnfRng`: in-kernel Philox noise of lsnf_langevin_step."""
+    """include/lsnf_flow.h `LsnfRng`: in-kernel Philox noise of lsnf_langevin_step and lsnf_sample."""
     _fields_ = [("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64), ("offset_dev", c_void_p), ("row0", ctypes.c_int64)]
 
 
@@ -46,6 +46,8 @@ _SIGNATURES = {
     "lsnf_langevin_step": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(LsnfRng), c_float,
                                    c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lsnf_sample": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(LsnfRng), c_float,
+                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lsnf_backward_params_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
     "lsnf_backward_params": (c_int, [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
                                      c_int, c_int, c_int, c_int, c_int,

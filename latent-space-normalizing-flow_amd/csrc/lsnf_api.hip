@@ -3,6 +3,7 @@
 // and alignments are checked against what the kernels and their grids assume.
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include <cmath>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -50,20 +51,25 @@ hipError_t lsnf_launch_small_forward(const LsnfGeo& g, const float* plan, int fi
                                      const float* z_in, const float* objective, float* z_out, float* logdet_out,
                                      float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4,
                                      hipStream_t stream);
+// (the reverse launchers: smp != NULL runs the kernel's sampling form -- lsnf_sample -- which draws its rows; z_in / objective NULL)
 hipError_t lsnf_launch_reverse(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                               float* z_out, float* objective_out, int vec4, hipStream_t stream);
+                               float* z_out, float* objective_out, int vec4, hipStream_t stream, const LsnfSampleArgs* smp = nullptr);
 int lsnf_small3_reverse_st(const LsnfGeo& g, int B);
 hipError_t lsnf_launch_small3_reverse(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                                      float* z_out, float* objective_out, int vec4, int st, hipStream_t stream);
+                                      float* z_out, float* objective_out, int vec4, int st, hipStream_t stream,
+                                      const LsnfSampleArgs* smp = nullptr);
 bool lsnf_reverse3_covers(const LsnfGeo& g);
 hipError_t lsnf_launch_reverse3(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                                float* z_out, float* objective_out, int vec4, int fixup, hipStream_t stream);
+                                float* z_out, float* objective_out, int vec4, int fixup, hipStream_t stream,
+                                const LsnfSampleArgs* smp = nullptr);
 bool lsnf_reverse2h_covers(const LsnfGeo& g);
 hipError_t lsnf_launch_reverse2h(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                                 float* z_out, float* objective_out, int vec4, int fixup, hipStream_t stream);
+                                 float* z_out, float* objective_out, int vec4, int fixup, hipStream_t stream,
+                                 const LsnfSampleArgs* smp = nullptr);
 bool lsnf_small_reverse_covers(const LsnfGeo& g);
 hipError_t lsnf_launch_small_reverse(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                                     float* z_out, float* objective_out, int vec4, hipStream_t stream);
+                                     float* z_out, float* objective_out, int vec4, hipStream_t stream,
+                                     const LsnfSampleArgs* smp = nullptr);
 hipError_t lsnf_launch_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
                                   const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
                                   float* g_z_in, float* dump, double* gl_total, int vec4, hipStream_t stream,
@@ -247,6 +253,30 @@ Pick select_reverse(const LsnfGeo& g, int B, const float* z_in, const float* obj
     }
     if (B > small_max) return {K_REV};
     return {lsnf_small_reverse_covers(g) ? K_SMALL_REV : K_NONE};
+}
+
+// Sampling (lsnf_sample): the reverse's kernels in their sampling form, so the reverse's selection -- same families, same
+// crossovers -- for a call whose inputs alias nothing (there are none: under fp16x2 the fix-up pass redraws the rows of the
+// workgroups it recomputes).
+Pick select_sample(const LsnfGeo& g, int B, const float* z_out, const float* objective_out) {
+    return select_reverse(g, B, /*z_in=*/nullptr, /*objective=*/nullptr, z_out, objective_out);
+}
+// the launch(es) of a reverse / sampling pick
+hipError_t launch_reverse(Pick p, const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
+                          float* z_out, float* objective_out, int vec4, hipStream_t st, const LsnfSampleArgs* smp) {
+    hipError_t e = hipSuccess;
+    switch (p.k) {
+    case K_REV2H_FIXUP:
+        e = lsnf_launch_reverse2h(g, plan, B, z_in, objective, z_out, objective_out, vec4, /*fixup=*/0, st, smp);
+        if (e == hipSuccess) e = lsnf_launch_reverse3(g, plan, B, z_in, objective, z_out, objective_out, vec4, /*fixup=*/1, st, smp);
+        break;
+    case K_REV3: e = lsnf_launch_reverse3(g, plan, B, z_in, objective, z_out, objective_out, vec4, /*fixup=*/0, st, smp); break;
+    case K_SMALL3_REV: e = lsnf_launch_small3_reverse(g, plan, B, z_in, objective, z_out, objective_out, vec4, p.st, st, smp); break;
+    case K_SMALL_REV: e = lsnf_launch_small_reverse(g, plan, B, z_in, objective, z_out, objective_out, vec4, st, smp); break;
+    case K_REV: e = lsnf_launch_reverse(g, plan, B, z_in, objective, z_out, objective_out, vec4, st, smp); break;
+    default: break;
+    }
+    return e;
 }
 
 // Backward (lsnf_backward_z, lsnf_langevin_step, lsnf_backward_params): from the activation stash on the bf16 matrix pipe when
@@ -514,20 +544,33 @@ int lsnf_reverse(const float* plan, int nz, int width, int depth, int coupling, 
         return fail(LSNF_E_ARG, "lsnf_reverse: tensors must be 4-byte aligned");
     const int vec4 = row_vector_width(g, {z_in, z_out});
     const Pick p = select_reverse(g, B, z_in, objective, z_out, objective_out);
-    const hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSuccess;
-    switch (p.k) {
-    case K_REV2H_FIXUP:
-        e = lsnf_launch_reverse2h(g, plan, B, z_in, objective, z_out, objective_out, vec4, /*fixup=*/0, st);
-        if (e == hipSuccess) e = lsnf_launch_reverse3(g, plan, B, z_in, objective, z_out, objective_out, vec4, /*fixup=*/1, st);
-        break;
-    case K_REV3: e = lsnf_launch_reverse3(g, plan, B, z_in, objective, z_out, objective_out, vec4, /*fixup=*/0, st); break;
-    case K_SMALL3_REV: e = lsnf_launch_small3_reverse(g, plan, B, z_in, objective, z_out, objective_out, vec4, p.st, st); break;
-    case K_SMALL_REV: e = lsnf_launch_small_reverse(g, plan, B, z_in, objective, z_out, objective_out, vec4, st); break;
-    case K_REV: e = lsnf_launch_reverse(g, plan, B, z_in, objective, z_out, objective_out, vec4, st); break;
-    default: break;
-    }
+    const hipError_t e = launch_reverse(p, g, plan, B, z_in, objective, z_out, objective_out, vec4, (hipStream_t)stream, nullptr);
     if (p.k == K_NONE || e != hipSuccess) return launch_fail(e, "lsnf_reverse", p.k);
+    return LSNF_OK;
+}
+
+int lsnf_sample(const float* plan, int nz, int width, int depth, int coupling, int B, const LsnfRng* rng, float temperature,
+                float* z_out, float* objective_out, float* eps_out, float* ll_out, void* stream) {
+    LsnfGeo g;
+    if (int rc = geo_or_fail(&g, nz, width, depth, coupling)) return rc;
+    if (B < 0 || B > (1 << 28)) return fail(LSNF_E_ARG, "lsnf_sample: B=%d out of range", B);
+    if (!rng) return fail(LSNF_E_ARG, "lsnf_sample: rng is required");
+    if (rng->row0 < 0) return fail(LSNF_E_ARG, "lsnf_sample: rng->row0 must be >= 0");
+    if (rng->offset_dev && (reinterpret_cast<uintptr_t>(rng->offset_dev) & 7u))
+        return fail(LSNF_E_ARG, "lsnf_sample: rng->offset_dev must be 8-byte aligned");
+    if (!std::isfinite(temperature) || temperature < 0.0f)
+        return fail(LSNF_E_ARG, "lsnf_sample: temperature must be finite and >= 0 (got %g)", (double)temperature);
+    if (B == 0) return LSNF_OK;
+    if (!plan || !z_out) return fail(LSNF_E_ARG, "lsnf_sample: NULL argument");
+    if (!aligned16(plan)) return fail(LSNF_E_ARG, "lsnf_sample: plan must be 16-byte aligned");
+    if (!aligned4(z_out) || !aligned4(objective_out) || !aligned4(eps_out) || !aligned4(ll_out))
+        return fail(LSNF_E_ARG, "lsnf_sample: tensors must be 4-byte aligned");
+    if (eps_out == z_out) return fail(LSNF_E_ARG, "lsnf_sample: eps_out must not alias z_out");
+    const int vec4 = row_vector_width(g, {z_out, eps_out});
+    const LsnfSampleArgs smp = {LsnfRngArgs{rng->seed, rng->offset, rng->offset_dev, rng->row0, 1}, temperature, eps_out, ll_out};
+    const Pick p = select_sample(g, B, z_out, objective_out);
+    const hipError_t e = launch_reverse(p, g, plan, B, nullptr, nullptr, z_out, objective_out, vec4, (hipStream_t)stream, &smp);
+    if (p.k == K_NONE || e != hipSuccess) return launch_fail(e, "lsnf_sample", p.k);
     return LSNF_OK;
 }
 

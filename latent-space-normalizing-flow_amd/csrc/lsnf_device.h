@@ -495,6 +495,44 @@ __device__ __forceinline__ f32x16 lsnf_noise_tile(int t, unsigned long long grow
     return x;
 }
 
+// ---- the latent rows of lsnf_sample, drawn where the reverse kernels would load them ----
+// eps(row, col) = T * noise(row, col): the draw above, one fp32 multiply.  One Philox call gives the four consecutive features
+// f0 .. f0+3 of half hh that a lane holds in every row layout (f0 is a multiple of 4); padded features (>= half) are drawn
+// and dropped (zero, as a row load leaves them); ss += the squares of what is kept.
+__device__ __forceinline__ LsnfRngState lsnf_rng_state(const LsnfRngArgs& r) {
+    const unsigned long long off = r.offset + (r.offset_dev ? *r.offset_dev : 0ull);
+    return {(unsigned)r.seed, (unsigned)(r.seed >> 32), (unsigned)off, (unsigned)(off >> 32), 1};
+}
+__device__ __forceinline__ f32x4 lsnf_sample4(int hh, int f0, int half, unsigned long long grow, const LsnfRngState& st, float T,
+                                              float& ss) {
+    unsigned c0 = ((unsigned)hh << 16) | (unsigned)(f0 >> 2), c1 = (unsigned)grow, c2 = st.c2, c3 = st.c3hi ^ (unsigned)(grow >> 32);
+    lsnf_philox4x32_10(c0, c1, c2, c3, st.k0, st.k1);
+    float n0, n1, n2, n3;
+    lsnf_box_muller(c0, c1, n0, n1);
+    lsnf_box_muller(c2, c3, n2, n3);
+    f32x4 v = {n0, n1, n2, n3};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        v[j] = (f0 + j < half) ? T * v[j] : 0.0f;
+        ss += v[j] * v[j];
+    }
+    return v;
+}
+// tile t of the split-pad row in the 32x32 layout (lsnf_load_tile's registers)
+template <int HT>
+__device__ __forceinline__ f32x16 lsnf_sample_tile(int t, unsigned long long grow, int half, int h, const LsnfRngState& st, float T,
+                                                   float& ss) {
+    f32x16 x;
+    const int hh = t / HT, tt = t % HT;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const f32x4 v = lsnf_sample4(hh, 32 * tt + 8 * g + 4 * h, half, grow, st, T, ss);
+        x[4 * g + 0] = v[0]; x[4 * g + 1] = v[1]; x[4 * g + 2] = v[2]; x[4 * g + 3] = v[3];
+    }
+    return x;
+}
+#define LSNF_LOG_2PI 1.8378770664093453f
+
 // bit r of the result = (a[r] > 0): relu mask of one tile, for the backward pass
 __device__ __forceinline__ unsigned lsnf_posmask16(const f32x16& a) {
     unsigned m = 0;

@@ -131,6 +131,23 @@ __device__ __forceinline__ f32x16 l16_load_tile(int t, const float* __restrict__
         }
     return x;
 }
+// the same registers drawn instead of loaded (lsnf_sample; lsnf_device.h lsnf_sample4): grow[st] = global row of sample tile st,
+// ss[st] += the squares of its row
+template <int HT>
+__device__ __forceinline__ f32x16 l16_sample_tile(int t, const unsigned long long* grow, int half, int g, const LsnfRngState& rs,
+                                                  float T, float* ss) {
+    f32x16 x;
+    const int hh = t / HT, tt = t % HT;
+#pragma unroll
+    for (int ft = 0; ft < 2; ++ft)
+#pragma unroll
+        for (int st = 0; st < 2; ++st) {
+            const int b = (2 * ft + st) * 4;
+            const f32x4 v = lsnf_sample4(hh, 32 * tt + l16_feat0(ft, g), half, grow[st], rs, T, ss[st]);
+            x[b] = v[0]; x[b + 1] = v[1]; x[b + 2] = v[2]; x[b + 3] = v[3];
+        }
+    return x;
+}
 template <int HT, class R>
 __device__ __forceinline__ void l16_store_tile(int t, const f32x16& x, float* __restrict__ z, const R* rows, const bool* live,
                                                int nz, int half, int g, int vw) {

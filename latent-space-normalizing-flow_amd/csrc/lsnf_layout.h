@@ -88,6 +88,14 @@ struct LsnfLangevinArgs {
     LsnfRngArgs rng;
 };
 
+// sampling form of the reverse kernels (lsnf_sample): the input rows are drawn in the kernel, eps = temperature * noise(row, col)
+// with the generator above (rng.enabled is ignored: the draw is always on); eps_out (B, nz) / ll_out (B) may be NULL
+struct LsnfSampleArgs {
+    LsnfRngArgs rng;
+    float temperature;
+    float* eps_out; float* ll_out;
+};
+
 static inline int lsnf_ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 // Chooses the kernel instantiation (HT, WT) in {(1,1),(2,2),(2,4)} that covers (half, width).

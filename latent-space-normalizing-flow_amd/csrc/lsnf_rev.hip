@@ -21,9 +21,12 @@ struct RevArgs {
     int B, nz, half, depth, vec4;
 };
 
+struct RevSampleArgs : RevArgs { LsnfSampleArgs s; };      // lsnf_sample: z_in / objective are unused (NULL)
+
 // NW waves per workgroup (4: two workgroups per CU, 8: one; see lsnf_fwd.hip)
-template <class C, int NW>
-__global__ __launch_bounds__(64 * NW, 2) void lsnf_rev_kernel(const RevArgs a) {
+// SAMPLE: the rows are drawn where they would be loaded (lsnf_sample); every other instruction is lsnf_reverse's.
+template <class C, int NW, bool SAMPLE>
+__global__ __launch_bounds__(64 * NW, 2) void lsnf_rev_kernel(const std::conditional_t<SAMPLE, RevSampleArgs, RevArgs> a) {
     constexpr int HT = C::HT, WT = C::WT, NZT = C::NZT;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* cst = smem;                                   // depth * (FWD_CONST + INV_CONST)
@@ -44,7 +47,18 @@ __global__ __launch_bounds__(64 * NW, 2) void lsnf_rev_kernel(const RevArgs a) {
     const bool live = sample < a.B;
     const long row = live ? sample : (long)a.B - 1;
     f32x16 x[NZT];
-    lsnf_load_rows<HT>(x, a.z_in, row, a.nz, a.half, h, a.vec4);
+    float llp = 0.0f;                                    // SAMPLE: -0.5 * sum eps^2 + log(2 pi) of the row
+    if constexpr (SAMPLE) {
+        const LsnfRngState rs = lsnf_rng_state(a.s.rng);
+        float ss = 0.0f;
+#pragma unroll
+        for (int t = 0; t < NZT; ++t)
+            x[t] = lsnf_sample_tile<HT>(t, (unsigned long long)(a.s.rng.row0 + sample), a.half, h, rs, a.s.temperature, ss);
+        if (a.s.eps_out && live) lsnf_store_rows<HT>(x, a.s.eps_out, sample, a.nz, a.half, h, a.vec4);
+        llp = -0.5f * lsnf_pair_sum(ss) + LSNF_LOG_2PI;
+    } else {
+        lsnf_load_rows<HT>(x, a.z_in, row, a.nz, a.half, h, a.vec4);
+    }
     float obj = a.objective ? a.objective[row] : 0.0f;
 
     for (int blk = a.depth - 1; blk >= 0; --blk) {
@@ -108,31 +122,38 @@ __global__ __launch_bounds__(64 * NW, 2) void lsnf_rev_kernel(const RevArgs a) {
     if (live) {
         lsnf_store_rows<HT>(x, a.z_out, sample, a.nz, a.half, h, a.vec4);
         if (h == 0 && a.objective_out) a.objective_out[sample] = obj;
+        if constexpr (SAMPLE) {
+            if (h == 0 && a.s.ll_out) a.s.ll_out[sample] = llp - obj;
+        }
     }
 }
 
-template <class C, int NW>
-hipError_t launch_rev_w(const RevArgs& a, hipStream_t stream) {
+template <class C, int NW, bool SAMPLE, class Args>
+hipError_t launch_rev_w(const Args& a, hipStream_t stream) {
     const size_t lds = ((size_t)a.depth * C::CONST_PER_BLOCK + 2 * (size_t)C::SLOT) * sizeof(float);
-    auto kern = lsnf_rev_kernel<C, NW>;
+    auto kern = lsnf_rev_kernel<C, NW, SAMPLE>;
     static unsigned long long lds_ok = 0;
     if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
     const unsigned grid = (unsigned)((a.B + 32 * NW - 1) / (32 * NW));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds, stream, a);
     return hipGetLastError();
 }
-template <class C>
-hipError_t launch_rev(const RevArgs& a, hipStream_t stream) {
-    return a.B > 256 * 128 ? launch_rev_w<C, 8>(a, stream) : launch_rev_w<C, 4>(a, stream);
+template <class C, bool SAMPLE, class Args>
+hipError_t launch_rev(const Args& a, hipStream_t stream) {
+    return a.B > 256 * 128 ? launch_rev_w<C, 8, SAMPLE>(a, stream) : launch_rev_w<C, 4, SAMPLE>(a, stream);
 }
 }  // namespace
 
 hipError_t lsnf_launch_reverse(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                               float* z_out, float* objective_out, int vec4, hipStream_t stream) {
-    RevArgs a;
+                               float* z_out, float* objective_out, int vec4, hipStream_t stream, const LsnfSampleArgs* smp) {
+    RevSampleArgs a;
     a.fwd_consts = plan + g.off_fwd_const; a.fwd_panels = plan + g.off_fwd_panels;
     a.inv_consts = plan + g.off_inv_const; a.inv_panels = plan + g.off_inv_panels;
     a.z_in = z_in; a.objective = objective; a.z_out = z_out; a.objective_out = objective_out;
     a.B = B; a.nz = g.nz; a.half = g.half; a.depth = g.depth; a.vec4 = vec4;
-    return lsnf_with_cfg<RevCfg>(g, [&](auto c) { return launch_rev<decltype(c)>(a, stream); });
+    if (smp) {
+        a.s = *smp;
+        return lsnf_with_cfg<RevCfg>(g, [&](auto c) { return launch_rev<decltype(c), true>(a, stream); });
+    }
+    return lsnf_with_cfg<RevCfg>(g, [&](auto c) { return launch_rev<decltype(c), false>(static_cast<const RevArgs&>(a), stream); });
 }

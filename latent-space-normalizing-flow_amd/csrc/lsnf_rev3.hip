@@ -28,9 +28,12 @@ struct Rev3Args {
     int B, nz, half, depth, vec4;
     const unsigned* guard; int fixup;        // fp16 range guard, as in lsnf_fwd3.hip (Fwd3Args); the flag travels in z_out[first row of the wave][0]
 };
+struct Rev3SampleArgs : Rev3Args { LsnfSampleArgs s; };      // lsnf_sample: z_in / objective are unused (NULL)
 
-template <class C, int NW>
-__global__ __launch_bounds__(64 * NW, 1) void lsnf_rev3_kernel(const Rev3Args a) {
+// SAMPLE: the rows are drawn where they would be loaded (lsnf_sample); every other instruction is lsnf_reverse's.  As the
+// fix-up pass of the fp16 reverse it redraws the rows of the workgroups it recomputes: the draw is a pure function.
+template <class C, int NW, bool SAMPLE>
+__global__ __launch_bounds__(64 * NW, 1) void lsnf_rev3_kernel(const std::conditional_t<SAMPLE, Rev3SampleArgs, Rev3Args> a) {
     constexpr int HT = C::HT, WT = C::WT, NZT = C::NZT;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* cst = smem;                                         // depth * CONST_PER_BLOCK
@@ -72,14 +75,31 @@ __global__ __launch_bounds__(64 * NW, 1) void lsnf_rev3_kernel(const Rev3Args a)
     for (int st = 0; st < 2; ++st) { sample[st] = base + 16 * st + n; live[st] = sample[st] < a.B; rows[st] = live[st] ? sample[st] : (long)a.B - 1; }
 
     f32x16 x[NZT];
+    float llp[2] = {0.0f, 0.0f};                                      // SAMPLE: -0.5 * sum eps^2 + log(2 pi) of the two rows
+    if constexpr (SAMPLE) {
+        const LsnfRngState rs = lsnf_rng_state(a.s.rng);
+        const unsigned long long grow[2] = {(unsigned long long)(a.s.rng.row0 + sample[0]), (unsigned long long)(a.s.rng.row0 + sample[1])};
+        float ss[2] = {0.0f, 0.0f};
 #pragma unroll
-    for (int t = 0; t < NZT; ++t) x[t] = l16_load_tile<HT>(t, a.z_in, rows, a.nz, a.half, g, vec4);
+        for (int t = 0; t < NZT; ++t) x[t] = l16_sample_tile<HT>(t, grow, a.half, g, rs, a.s.temperature, ss);
+#pragma unroll
+        for (int st = 0; st < 2; ++st) llp[st] = -0.5f * l16_group_sum(ss[st]) + LSNF_LOG_2PI;
+    } else {
+#pragma unroll
+        for (int t = 0; t < NZT; ++t) x[t] = l16_load_tile<HT>(t, a.z_in, rows, a.nz, a.half, g, vec4);
+    }
     __builtin_amdgcn_sched_barrier(0);
     // (the constant blocks are copied AFTER the row loads have gone out: the copy waits for its loads in order, one memory
     //  round trip that the rows would otherwise start behind)
     for (int i = tid; i < a.depth * C::CONST_PER_BLOCK; i += 64 * NW) {
         const int blk = i / C::CONST_PER_BLOCK, r = i % C::CONST_PER_BLOCK;
         cst[i] = r < C::FWD_CONST ? a.fwd_consts[blk * C::FWD_CONST + r] : a.inv_consts[blk * C::INV_CONST + (r - C::FWD_CONST)];
+    }
+    if constexpr (SAMPLE) {              // (behind the constants: their copy waits for every access before it)
+        if (a.s.eps_out) {
+#pragma unroll
+            for (int t = 0; t < NZT; ++t) l16_store_tile<HT>(t, x[t], a.s.eps_out, sample, live, a.nz, a.half, g, vec4);
+        }
     }
     float obj[2];
 #pragma unroll
@@ -165,26 +185,39 @@ __global__ __launch_bounds__(64 * NW, 1) void lsnf_rev3_kernel(const Rev3Args a)
         for (int st = 0; st < 2; ++st)
             if (live[st] && g == 0) a.objective_out[sample[st]] = obj[st];
     }
+    if constexpr (SAMPLE) {
+        if (a.s.ll_out) {
+#pragma unroll
+            for (int st = 0; st < 2; ++st)
+                if (live[st] && g == 0) a.s.ll_out[sample[st]] = llp[st] - obj[st];
+        }
+    }
 }
 
 template <class C>
 size_t rev3_lds(int depth) { return ((size_t)depth * C::CONST_PER_BLOCK + 2 * (size_t)C::SLOT3) * sizeof(float); }
 
-template <class C, int NW>
-hipError_t launch_rev3_w(const Rev3Args& a, hipStream_t stream) {
+template <class C, int NW, bool SAMPLE, class Args>
+hipError_t launch_rev3_w(const Args& a, hipStream_t stream) {
     const size_t lds = rev3_lds<C>(a.depth);
-    auto kern = lsnf_rev3_kernel<C, NW>;
+    auto kern = lsnf_rev3_kernel<C, NW, SAMPLE>;
     static unsigned long long lds_ok = 0;
     if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
     const unsigned grid = (unsigned)((a.B + 32 * NW - 1) / (32 * NW));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds, stream, a);
     return hipGetLastError();
 }
-template <class C>
-hipError_t launch_rev3(const Rev3Args& a, hipStream_t stream) {
-    static const char* fw = getenv("LSNF_FORCE_WAVES");   // experiment knob (tools/): 4 or 8
-    const bool eight = fw ? atoi(fw) == 8 : a.B > 128 * 256;
-    return eight ? launch_rev3_w<C, 8>(a, stream) : launch_rev3_w<C, 4>(a, stream);
+template <class C, bool SAMPLE, class Args>
+hipError_t launch_rev3(const Args& a, hipStream_t stream) {
+    // (the sampling form of the f_width > 64 geometry stays on 4 waves: at 8 waves -- 256 registers per lane -- the words it carries
+    //  for ll_out would go to scratch; what a wave computes does not depend on NW)
+    if constexpr (SAMPLE && C::WT == 4) {
+        return launch_rev3_w<C, 4, SAMPLE>(a, stream);
+    } else {
+        static const char* fw = getenv("LSNF_FORCE_WAVES");   // experiment knob (tools/): 4 or 8
+        const bool eight = fw ? atoi(fw) == 8 : a.B > 128 * 256;
+        return eight ? launch_rev3_w<C, 8, SAMPLE>(a, stream) : launch_rev3_w<C, 4, SAMPLE>(a, stream);
+    }
 }
 }  // namespace
 
@@ -199,9 +232,10 @@ bool LSNF_REV3_COVERS(const LsnfGeo& g) {
 }
 
 hipError_t LSNF_REV3_ENTRY(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                           float* z_out, float* objective_out, int vec4, int fixup, hipStream_t stream) {
+                           float* z_out, float* objective_out, int vec4, int fixup, hipStream_t stream,
+                           const LsnfSampleArgs* smp) {
     if (!LSNF_REV3_COVERS(g)) return hipErrorInvalidValue;      // (a selection bug)
-    Rev3Args a;
+    Rev3SampleArgs a;
     a.guard = reinterpret_cast<const unsigned*>(plan + g.off_guard); a.fixup = fixup;
     a.fwd_consts = plan + g.off_fwd_const; a.inv_consts = plan + g.off_inv_const;
 #if LSNF_L16_PARTS == 3
@@ -211,5 +245,9 @@ hipError_t LSNF_REV3_ENTRY(const LsnfGeo& g, const float* plan, int B, const flo
 #endif
     a.z_in = z_in; a.objective = objective; a.z_out = z_out; a.objective_out = objective_out;
     a.B = B; a.nz = g.nz; a.half = g.half; a.depth = g.depth; a.vec4 = vec4;
-    return lsnf_with_cfg<Rev3Cfg>(g, [&](auto c) { return launch_rev3<decltype(c)>(a, stream); });
+    if (smp) {
+        a.s = *smp;
+        return lsnf_with_cfg<Rev3Cfg>(g, [&](auto c) { return launch_rev3<decltype(c), true>(a, stream); });
+    }
+    return lsnf_with_cfg<Rev3Cfg>(g, [&](auto c) { return launch_rev3<decltype(c), false>(static_cast<const Rev3Args&>(a), stream); });
 }

@@ -42,8 +42,13 @@ struct Small3RevArgs {
     int B, nz, half, depth, vec4;
 };
 
-template <class C, int ST>
-__global__ __launch_bounds__(256, 1) void lsnf_small3_rev_kernel(const Small3RevArgs a) {
+struct Small3RevSampleArgs : Small3RevArgs { LsnfSampleArgs s; };      // lsnf_sample: z_in / objective are unused (NULL)
+
+// SAMPLE: the rows are drawn where they would be loaded (lsnf_sample): each wave draws the two half-units it owns, behind its
+// weight fetches; every other instruction is lsnf_reverse's.  -0.5 * sum eps^2 takes the objective's way through RED, in the
+// prologue (RED is free until the final reduction), into a second accumulator that wave 0 carries.
+template <class C, int ST, bool SAMPLE>
+__global__ __launch_bounds__(256, 1) void lsnf_small3_rev_kernel(const std::conditional_t<SAMPLE, Small3RevSampleArgs, Small3RevArgs> a) {
     constexpr int HT = C::HT, WT = C::WT, NZT = C::NZT, NU2 = C::NU2, LASTU = NU2 - 1;
     using L = Small3RevLds<C, ST>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -75,9 +80,11 @@ __global__ __launch_bounds__(256, 1) void lsnf_small3_rev_kernel(const Small3Rev
         sample[st] = ((long)blockIdx.x * ST + st) * S3_SAMPLES + n;
         live[st] = sample[st] < a.B;
         row[st] = live[st] ? sample[st] : (long)a.B - 1;
-        // this wave's half-units of the input (requested before the weights and the constants: vmcnt completes in order)
-        z1[st] = load_row_half<HT>(nt1, ft1, a.z_in + row[st] * (long)a.nz, a.half, g, vec4);
-        z2[st] = load_row_half<HT>(HT + nt1, ft1, a.z_in + row[st] * (long)a.nz, a.half, g, vec4);
+        if constexpr (!SAMPLE) {
+            // this wave's half-units of the input (requested before the weights and the constants: vmcnt completes in order)
+            z1[st] = load_row_half<HT>(nt1, ft1, a.z_in + row[st] * (long)a.nz, a.half, g, vec4);
+            z2[st] = load_row_half<HT>(HT + nt1, ft1, a.z_in + row[st] * (long)a.nz, a.half, g, vec4);
+        }
     }
     float obj[ST];                                                        // per-wave partial of the running objective
 #pragma unroll
@@ -98,12 +105,42 @@ __global__ __launch_bounds__(256, 1) void lsnf_small3_rev_kernel(const Small3Rev
         const int blk = i / C::CONST_PER_BLOCK, r = i % C::CONST_PER_BLOCK;
         cst[i] = r < C::FWD_CONST ? a.fwd_consts[blk * C::FWD_CONST + r] : a.inv_consts[blk * C::INV_CONST + (r - C::FWD_CONST)];
     }
+    if constexpr (SAMPLE) {
+        const LsnfRngState rs = lsnf_rng_state(a.s.rng);
+        const int f0 = 32 * nt1 + 16 * ft1 + 4 * g;
+#pragma unroll
+        for (int st = 0; st < ST; ++st) {
+            const unsigned long long grow = (unsigned long long)(a.s.rng.row0 + sample[st]);
+            float ss = 0.0f;
+            z1[st] = lsnf_sample4(0, f0, a.half, grow, rs, a.s.temperature, ss);
+            z2[st] = lsnf_sample4(1, f0, a.half, grow, rs, a.s.temperature, ss);
+            if (a.s.eps_out && has1 && live[st]) {
+                float* er = a.s.eps_out + sample[st] * (long)a.nz;
+                store_row_half<HT>(nt1, ft1, z1[st], er, a.half, g, vec4);
+                store_row_half<HT>(HT + nt1, ft1, z2[st], er, a.half, g, vec4);
+            }
+            if (a.s.ll_out) {                  // kernel-uniform
+                ss = has1 ? group_sum(ss) : 0.0f;
+                if (g == 0) RED[(st * 4 + wave) * 16 + n] = ss;
+            }
+        }
+    }
 #pragma unroll
     for (int st = 0; st < ST; ++st) store_half(Z1 + st * L::GH + nt1 * S3_BTILE_FLOATS, ft1, z1[st], lane);   // buffer 0
     float lsum[ST];                                                       // running sum of log sigmoid(p) over all blocks
 #pragma unroll
     for (int st = 0; st < ST; ++st) lsum[st] = 0.0f;
     __syncthreads();
+    float llp[ST];                                                        // SAMPLE: -0.5 * sum eps^2 + log(2 pi), carried by wave 0
+#pragma unroll
+    for (int st = 0; st < ST; ++st) llp[st] = 0.0f;
+    if constexpr (SAMPLE) {
+        if (a.s.ll_out && wave == 0) {
+#pragma unroll
+            for (int st = 0; st < ST; ++st)
+                llp[st] = -0.5f * (RED[(st * 4 + 0) * 16 + n] + RED[(st * 4 + 1) * 16 + n] + RED[(st * 4 + 2) * 16 + n] + RED[(st * 4 + 3) * 16 + n]) + LSNF_LOG_2PI;
+        }
+    }
 
     for (int blk = last; blk >= 0; --blk) {
         const float* cb = cst + blk * C::CONST_PER_BLOCK;
@@ -210,7 +247,9 @@ __global__ __launch_bounds__(256, 1) void lsnf_small3_rev_kernel(const Small3Rev
             store_row_half<HT>(HT + nt1, ft1, z2[st], zr, a.half, g, vec4);
         }
     }
-    if (a.objective_out) {                     // kernel-uniform
+    bool want_obj = a.objective_out != nullptr;       // kernel-uniform
+    if constexpr (SAMPLE) want_obj = want_obj || a.s.ll_out != nullptr;
+    if (want_obj) {
 #pragma unroll
         for (int st = 0; st < ST; ++st) {
             const float o = obj[st] - (has1 ? group_sum(lsum[st]) : 0.0f);
@@ -220,7 +259,13 @@ __global__ __launch_bounds__(256, 1) void lsnf_small3_rev_kernel(const Small3Rev
         if (wave == 0 && g == 0) {
 #pragma unroll
             for (int st = 0; st < ST; ++st)
-                if (live[st]) a.objective_out[sample[st]] = RED[(st * 4 + 0) * 16 + n] + RED[(st * 4 + 1) * 16 + n] + RED[(st * 4 + 2) * 16 + n] + RED[(st * 4 + 3) * 16 + n];
+                if (live[st]) {
+                    const float o = RED[(st * 4 + 0) * 16 + n] + RED[(st * 4 + 1) * 16 + n] + RED[(st * 4 + 2) * 16 + n] + RED[(st * 4 + 3) * 16 + n];
+                    if (a.objective_out) a.objective_out[sample[st]] = o;
+                    if constexpr (SAMPLE) {
+                        if (a.s.ll_out) a.s.ll_out[sample[st]] = llp[st] - o;
+                    }
+                }
         }
     }
 }
@@ -231,13 +276,13 @@ size_t small3_rev_lds(int depth) { return ((size_t)Small3RevLds<C, ST>::L_CONST 
 template <class C, int ST>
 constexpr bool small3_rev_built = (size_t)(Small3RevLds<C, ST>::L_CONST + C::CONST_PER_BLOCK) * sizeof(float) <= 160 * 1024 && !(ST == 4 && C::WT > 2);
 
-template <class C, int ST>
-hipError_t launch_small3_rev_st(const Small3RevArgs& a, hipStream_t stream) {
+template <class C, int ST, bool SAMPLE, class Args>
+hipError_t launch_small3_rev_st(const Args& a, hipStream_t stream) {
     if constexpr (!small3_rev_built<C, ST>) {
         return hipErrorInvalidValue;                 // (a selection bug)
     } else {
         const size_t lds = small3_rev_lds<C, ST>(a.depth);
-        auto kern = lsnf_small3_rev_kernel<C, ST>;
+        auto kern = lsnf_small3_rev_kernel<C, ST, SAMPLE>;
         static unsigned long long lds_ok = 0;
         if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
         const unsigned grid = (unsigned)((a.B + ST * S3_SAMPLES - 1) / (ST * S3_SAMPLES));
@@ -264,15 +309,25 @@ int lsnf_small3_reverse_st(const LsnfGeo& g, int B) {
 
 // st: lsnf_small3_reverse_st of the call
 hipError_t lsnf_launch_small3_reverse(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                                      float* z_out, float* objective_out, int vec4, int st, hipStream_t stream) {
-    Small3RevArgs a;
+                                      float* z_out, float* objective_out, int vec4, int st, hipStream_t stream,
+                                      const LsnfSampleArgs* smp) {
+    Small3RevSampleArgs a;
     a.fwd_consts = plan + g.off_fwd_const; a.inv_consts = plan + g.off_inv_const;
     a.panels3b = plan + g.off_f3b_panels; a.ipanels3b = plan + g.off_i3b_panels;
     a.z_in = z_in; a.objective = objective; a.z_out = z_out; a.objective_out = objective_out;
     a.B = B; a.nz = g.nz; a.half = g.half; a.depth = g.depth; a.vec4 = vec4;
+    if (smp) {
+        a.s = *smp;
+        return lsnf_with_cfg<Small3RevCfg>(g, [&](auto c) {
+            using C = decltype(c);
+            return st == 4 ? launch_small3_rev_st<C, 4, true>(a, stream) : st == 2 ? launch_small3_rev_st<C, 2, true>(a, stream)
+                                                                                   : launch_small3_rev_st<C, 1, true>(a, stream);
+        });
+    }
+    const Small3RevArgs& r = a;
     return lsnf_with_cfg<Small3RevCfg>(g, [&](auto c) {
         using C = decltype(c);
-        return st == 4 ? launch_small3_rev_st<C, 4>(a, stream) : st == 2 ? launch_small3_rev_st<C, 2>(a, stream)
-                                                                         : launch_small3_rev_st<C, 1>(a, stream);
+        return st == 4 ? launch_small3_rev_st<C, 4, false>(r, stream) : st == 2 ? launch_small3_rev_st<C, 2, false>(r, stream)
+                                                                                : launch_small3_rev_st<C, 1, false>(r, stream);
     });
 }

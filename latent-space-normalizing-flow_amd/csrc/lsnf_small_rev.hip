@@ -33,8 +33,11 @@ struct SmallRevArgs {
     int B, nz, half, depth, vec4;
 };
 
-template <class C>
-__global__ __launch_bounds__(LSNF_WG_THREADS, 1) void lsnf_small_rev_kernel(const SmallRevArgs a) {
+struct SmallRevSampleArgs : SmallRevArgs { LsnfSampleArgs s; };      // lsnf_sample: z_in / objective are unused (NULL)
+
+// SAMPLE: the rows are drawn where they would be loaded (lsnf_sample); every other instruction is lsnf_reverse's.
+template <class C, bool SAMPLE>
+__global__ __launch_bounds__(LSNF_WG_THREADS, 1) void lsnf_small_rev_kernel(const std::conditional_t<SAMPLE, SmallRevSampleArgs, SmallRevArgs> a) {
     constexpr int HT = C::HT, NZT = C::NZT;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* tiles = smem;
@@ -57,11 +60,32 @@ __global__ __launch_bounds__(LSNF_WG_THREADS, 1) void lsnf_small_rev_kernel(cons
     const long sample = (long)blockIdx.x * LSNF_SMALL_SAMPLES + m;
     const bool live = sample < a.B;
     const long row = live ? sample : (long)a.B - 1;
-    if (wave < NZT) small_store_tile(T(C::T_X + (last & 1) * NZT + wave),
-                                     lsnf_load_tile<HT>(wave, a.z_in + row * (long)a.nz, a.half, h, vec4), lane);
+    if constexpr (SAMPLE) {
+        if (wave < NZT) {                                            // wave w draws tile w of the row, as it would load it
+            const LsnfRngState rs = lsnf_rng_state(a.s.rng);
+            float ss = 0.0f;
+            const f32x16 e = lsnf_sample_tile<HT>(wave, (unsigned long long)(a.s.rng.row0 + sample), a.half, h, rs, a.s.temperature, ss);
+            small_store_tile(T(C::T_X + (last & 1) * NZT + wave), e, lane);
+            if (a.s.eps_out && live) lsnf_store_tile<HT>(wave, e, a.s.eps_out + sample * (long)a.nz, a.half, h, vec4);
+            ss = lsnf_pair_sum(ss);
+            if (h == 0) aux[32 * wave + m] = ss;                     // (aux is free until the first inverse coupling: 3 barriers on)
+        }
+    } else {
+        if (wave < NZT) small_store_tile(T(C::T_X + (last & 1) * NZT + wave),
+                                         lsnf_load_tile<HT>(wave, a.z_in + row * (long)a.nz, a.half, h, vec4), lane);
+    }
     float obj = 0.0f;                                                // carried by wave 0
     if (wave == 0) obj = a.objective ? a.objective[row] : 0.0f;
     __syncthreads();
+    float llp = 0.0f;                                                // SAMPLE: -0.5 * sum eps^2 + log(2 pi), carried by wave 0
+    if constexpr (SAMPLE) {
+        if (wave == 0) {
+            float ss = 0.0f;
+#pragma unroll
+            for (int w = 0; w < NZT; ++w) ss += aux[32 * w + m];
+            llp = -0.5f * ss + LSNF_LOG_2PI;
+        }
+    }
 
     for (int blk = last; blk >= 0; --blk) {
         const float* cb = cst + blk * C::CONST_PER_BLOCK;
@@ -128,15 +152,18 @@ __global__ __launch_bounds__(LSNF_WG_THREADS, 1) void lsnf_small_rev_kernel(cons
         lsnf_store_tile<HT>(wave, small_load_tile(Xf + (size_t)wave * LSNF_TILE_FLOATS, lane), a.z_out + sample * (long)a.nz,
                             a.half, h, vec4);
     if (wave == 0 && live && h == 0 && a.objective_out) a.objective_out[sample] = obj;
+    if constexpr (SAMPLE) {
+        if (wave == 0 && live && h == 0 && a.s.ll_out) a.s.ll_out[sample] = llp - obj;
+    }
 }
 
 template <class C>
 size_t small_rev_lds(int depth) { return ((size_t)C::T_END * LSNF_TILE_FLOATS + C::AUX_FLOATS + (size_t)depth * C::CONST_PER_BLOCK) * sizeof(float); }
 
-template <class C>
-hipError_t launch_small_rev(const SmallRevArgs& a, hipStream_t stream) {
+template <class C, bool SAMPLE, class Args>
+hipError_t launch_small_rev(const Args& a, hipStream_t stream) {
     const size_t lds = small_rev_lds<C>(a.depth);
-    auto kern = lsnf_small_rev_kernel<C>;
+    auto kern = lsnf_small_rev_kernel<C, SAMPLE>;
     static unsigned long long lds_ok = 0;
     if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
     const unsigned grid = (unsigned)((a.B + LSNF_SMALL_SAMPLES - 1) / LSNF_SMALL_SAMPLES);
@@ -152,12 +179,16 @@ bool lsnf_small_reverse_covers(const LsnfGeo& g) {
 }
 
 hipError_t lsnf_launch_small_reverse(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                                     float* z_out, float* objective_out, int vec4, hipStream_t stream) {
-    SmallRevArgs a;
+                                     float* z_out, float* objective_out, int vec4, hipStream_t stream, const LsnfSampleArgs* smp) {
+    SmallRevSampleArgs a;
     a.fwd_consts = plan + g.off_fwd_const; a.fwd_panels = plan + g.off_fwd_panels;
     a.inv_consts = plan + g.off_inv_const; a.inv_panels = plan + g.off_inv_panels;
     a.z_in = z_in; a.objective = objective; a.z_out = z_out; a.objective_out = objective_out;
     a.B = B; a.nz = g.nz; a.half = g.half; a.depth = g.depth; a.vec4 = vec4;
     if (!lsnf_small_reverse_covers(g)) return hipErrorInvalidValue;      // (a selection bug)
-    return lsnf_with_cfg<SmallRevCfg>(g, [&](auto c) { return launch_small_rev<decltype(c)>(a, stream); });
+    if (smp) {
+        a.s = *smp;
+        return lsnf_with_cfg<SmallRevCfg>(g, [&](auto c) { return launch_small_rev<decltype(c), true>(a, stream); });
+    }
+    return lsnf_with_cfg<SmallRevCfg>(g, [&](auto c) { return launch_small_rev<decltype(c), false>(static_cast<const SmallRevArgs&>(a), stream); });
 }

@@ -459,6 +459,54 @@ class PhiloxNoise:
         return _lib.LsnfRng(self.seed & mask, self.offset & mask, dev, self.row0)
 
 
+def sample(plan: FlowPlan, B: int, rng: PhiloxNoise, *, temperature: float = 1.0, want_eps: bool = False,
+           want_ll: bool = False, out: Optional[Tuple[Optional[torch.Tensor], ...]] = None):
+    """Fused prior sampling (`lsnf_sample`; train.py:472-475 without the `randn` launch and its (B, nz) tensor): ONE launch draws
+    eps = temperature * N(0,1) inside the reverse kernel -- a pure function of (rng.seed, rng.offset, rng.row0 + row, column),
+    so row-sharded calls with matching `row0` draw what one call would -- and returns (x, objective_out, eps or None, ll or None):
+    x, objective_out = what `reverse(plan, eps)` returns, bit for bit; ll = -0.5*sum eps^2 + log(2 pi) - objective_out, the
+    log-density of x under the flow prior.  `rng` is not advanced: pass `rng.step()` (or advance it) for the next call.
+    out: optional caller-owned (x, objective_out, eps, ll) on the plan's device; each of the last three may be None (not
+    written; want_eps / want_ll then do not apply).  Every buffer is checked before anything is launched."""
+    lib = _lib.load()
+    B = int(B)
+    dev = plan.device
+    if not isinstance(rng, PhiloxNoise):
+        raise LsnfError("rng must be a flow.PhiloxNoise (the draw is made inside the kernel; there is no tensor form)")
+    if B < 0:
+        raise LsnfError(f"B must be >= 0 (got {B})")
+    if rng.offset_dev is not None:
+        od = rng.offset_dev
+        if not od.is_cuda or od.device != dev or od.dtype not in (torch.int64, torch.uint64) or od.numel() != 1:
+            raise LsnfError(f"offset_dev must be one 64-bit integer on {dev}")
+    if out is not None:
+        if len(out) != 4:
+            raise LsnfError("out must be (x, objective_out, eps, ll); the last three may be None")
+        x, obj, eps, ll = out
+        if x is None:
+            raise LsnfError("out[0] (x) is required")
+    else:
+        f32 = dict(dtype=torch.float32, device=dev)
+        x, obj = torch.empty((B, plan.nz), **f32), torch.empty(B, **f32)
+        eps = torch.empty((B, plan.nz), **f32) if want_eps else None
+        ll = torch.empty(B, **f32) if want_ll else None
+    _check_out(x, "out[0] (x)", B * plan.nz, dev)
+    if obj is not None:
+        _check_out(obj, "out[1] (objective_out)", B, dev)
+    if eps is not None:
+        _check_out(eps, "out[2] (eps)", B * plan.nz, dev)
+        if B and eps.data_ptr() == x.data_ptr():
+            raise LsnfError("out[2] (eps) must not alias out[0] (x)")
+    if ll is not None:
+        _check_out(ll, "out[3] (ll)", B, dev)
+    c = rng._c()
+    with torch.cuda.device(dev):
+        rc = lib.lsnf_sample(_ptr(plan.buf), plan.nz, plan.width, plan.depth, plan.coupling, B, ctypes.byref(c),
+                             float(temperature), _ptr(x), _ptr(obj), _ptr(eps), _ptr(ll), _stream_ptr(dev))
+    _lib.check(rc, "lsnf_sample")
+    return x, obj, eps, ll
+
+
 def langevin_step(plan: FlowPlan, z: torch.Tensor, grad_g: Optional[torch.Tensor], noise,
                   step_size: float, *, inplace: bool = False, want_norms: bool = True, reuse_buffers: bool = False):
     """One flow-prior Langevin update (train.py:316-329) in two launches: forward (keeps block outputs) and the

@@ -3,6 +3,7 @@ restated (they are closures inside train.py and cannot be imported) on top of th
 
   sample_langevin_post_z_with_flow  <- train.py:307-335 (training) / :602-634 (testing: 20x steps, no noise)
   flow_mle_step                     <- train.py:404-415
+  sample_x                          <- train.py:472-478 (prior samples for the FID evaluation)
 
 The generator `netG` is any `nn.Module` mapping (B, nz, 1, 1) -> images (the reference's `_netG`, stock PyTorch /
 MIOpen, is out of scope of this build and used as is); its z-gradient comes from torch autograd exactly as in the
@@ -71,6 +72,20 @@ def flow_mle_step(netF, optF, z_g_k, f_max_norm: Optional[float] = None, fused: 
         torch.nn.utils.clip_grad_norm_(netF.parameters(), f_max_norm)                        # train.py:413-414
     optF.step()
     return loss_f.detach()
+
+
+def sample_x(netG: nn.Module, netF, n: int, philox, temperature: float = 1.0):
+    """train.py:472-478 (`sample_x` of the FID evaluation; also :428-437): n images from the prior.  The latent draw and the
+    flow's reverse pass are one launch (`netF.sample`: no `torch.randn`, no zeros tensor); the generator runs on the result as
+    in the reference.  `philox` is a `flow.PhiloxNoise` (its `row0` = the shard's first global row when the n_fid_samples are
+    split over GPUs: the union of the shards is then the one-GPU draw); it is ADVANCED by one on return, as the K-step sampler
+    above advances it by K.  Returns netG's output, detached (range mapping and the copy to the host stay with the caller)."""
+    with torch.no_grad():
+        z_f_k = netF.sample(n, philox, temperature=temperature)                              # train.py:473-475
+        x_samples = netG(torch.reshape(z_f_k, (z_f_k.shape[0], z_f_k.shape[1], 1, 1)))       # train.py:476
+    if hasattr(philox, "advance"):        # (an int seed has no state to advance)
+        philox.advance(1)
+    return x_samples.detach()
 
 
 class GraphedLangevinSampler:

@@ -200,8 +200,8 @@ class _FlowReverseFn(torch.autograd.Function):
         return x, obj
 
     @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g_x, g_obj):
+    def _backward(ctx, g_x, g_obj, want_tok):
+        """(g_eps, g_obj made contiguous, g_tok) from the saved x: shared with _FlowSampleFn, which saves the same."""
         module, h = ctx.module, ctx.holder
         x, = ctx.saved_tensors
         if module._current_key() != ctx.plan_key:   # (see _FlowStackFn.backward)
@@ -211,7 +211,7 @@ class _FlowReverseFn(torch.autograd.Function):
         g_x = None if g_x is None else g_x.contiguous()
         g_obj = None if g_obj is None else g_obj.contiguous()
         h.empty = B == 0                                    # (an empty batch leaves the parameters without a gradient)
-        need_tok = ctx.needs_input_grad[4] and B > 0
+        need_tok = want_tok and B > 0
         for_params = need_tok and flow.params_fast_path()
         act = flow.new_act_saved(plan, B, x.device)
         ws = flow.new_params_workspace(plan, B, x.device) if for_params else None
@@ -225,7 +225,37 @@ class _FlowReverseFn(torch.autograd.Function):
             h.z, h.z1, h.saved, h.plan_key = x, z1, saved, ctx.plan_key
             h.act, h.ws = act, ws
             g_tok = z1.new_zeros(())
+        return g_eps, g_obj, g_tok
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_x, g_obj):
+        g_eps, g_obj, g_tok = _FlowReverseFn._backward(ctx, g_x, g_obj, ctx.needs_input_grad[4])
         return (None, None, g_eps if ctx.needs_input_grad[2] else None, g_obj.reshape(ctx.obj_shape) if (ctx.needs_input_grad[3] and g_obj is not None) else None, g_tok)
+
+
+class _FlowSampleFn(torch.autograd.Function):
+    """(token) -> (x, objective_out, eps, ll) of `_netF.sample`: _FlowReverseFn with the sampling launch (lsnf_sample) in place of
+    lsnf_reverse.  eps is drawn, not an input: the only leaves are the parameters.  The node saves x alone, as the reverse does, so
+    the backward is the reverse's; an upstream gradient on ll joins the objective's (ll = const(eps) - objective_out)."""
+
+    @staticmethod
+    def forward(ctx, module, holder, token, n, rng, temperature):
+        x, obj, eps, ll = flow.sample(module._plan(), n, rng, temperature=temperature, want_eps=True, want_ll=True)
+        ctx.module, ctx.holder = module, holder
+        ctx.plan_key = module._plan_key
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(eps)
+        ctx.save_for_backward(x)
+        return x, obj, eps, ll
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_x, g_obj, _g_eps, g_ll):
+        if g_ll is not None:
+            g_obj = g_ll.neg() if g_obj is None else g_obj - g_ll
+        _, _, g_tok = _FlowReverseFn._backward(ctx, g_x, g_obj, ctx.needs_input_grad[2])
+        return None, None, g_tok, None, None, None
 
 
 class _netF(nn.Module):
@@ -333,6 +363,29 @@ class _netF(nn.Module):
         if not return_obj:
             return x
         return x, -obj
+
+    # ---- fused prior sampling (train.py:472-475: `torch.randn` + `netF(z, zeros, reverse=True)`) ----------
+    def sample(self, n, philox, temperature=1.0, return_eps=False, return_log_prob=False):
+        """n samples x = f^-1(temperature * eps) of the flow prior in ONE launch: eps ~ N(0, 1) is drawn inside the reverse
+        kernel (`flow.sample`), so there is no `randn` launch and no (n, nz) latent tensor, and the draw is a pure function of
+        (seed, offset, row0 + row, column) -- the same rows however they are sharded over GPUs.
+        philox: a `flow.PhiloxNoise` (not advanced: pass `philox.step()` next time) or an int seed.
+        Returns x, or (x, eps if return_eps, log_prob if return_log_prob) with log_prob = log p(x) under the prior
+        (= `log_prob(x)[2]`, without the second pass).  With grad enabled and parameters that require grad, x and log_prob are
+        differentiable w.r.t. the parameters through the reverse bridge (eps is a constant); otherwise nothing is recorded."""
+        params = self._param_list()
+        self._require_gpu(params)
+        rng = philox if isinstance(philox, flow.PhiloxNoise) else flow.PhiloxNoise(int(philox))
+        n, temperature = int(n), float(temperature)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            holder = _Upstream()
+            token = _ParamGate.apply(self, holder, *params)
+            x, _, eps, ll = _FlowSampleFn.apply(self, holder, token, n, rng, temperature)
+        else:
+            x, _, eps, ll = flow.sample(self._plan(), n, rng, temperature=temperature, want_eps=return_eps, want_ll=return_log_prob)
+        if not (return_eps or return_log_prob):
+            return x
+        return (x,) + ((eps,) if return_eps else ()) + ((ll,) if return_log_prob else ())
 
     # ---- fused extras (not in the reference; train.py:316-323 collapsed into two launches) ---------
     def log_prob(self, z, stats=None):

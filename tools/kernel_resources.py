@@ -1,0 +1,116 @@
+"""Resource notes of the kernels in built objects, from the code objects' own metadata (no GPU needed).
+
+    python tools/kernel_resources.py BUILD_DIR [--match rev] [--against OTHER_BUILD_DIR]
+
+For every *.o in BUILD_DIR: the gfx950 code object is taken out of the .hip_fatbin section and its AMDGPU metadata note
+is read (llvm-readelf --notes): VGPRs, AGPRs, SGPRs, static LDS and Scratch_Size (.private_segment_fixed_size) per kernel.
+Kernel names are shortened to `kernel<HT, WT, ...>` (the template arguments in order).  --against compares with a second build (e.g. the
+parent commit's): a kernel is matched by its name with any trailing `false` template argument removed, so that an
+instantiation that gained a compile-time flag is compared with what it was; kernels only in BUILD_DIR are listed as new.
+Exit status 1 if a matched kernel differs in VGPRs, AGPRs, LDS or scratch."""
+import argparse
+import glob
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+LLVM = os.environ.get("LLVM_BIN", "/opt/rocm/llvm/bin")
+FIELDS = (("vgpr", ".vgpr_count"), ("agpr", ".agpr_count"), ("sgpr", ".sgpr_count"), ("lds", ".group_segment_fixed_size"),
+          ("scratch", ".private_segment_fixed_size"))
+
+
+def _run(*cmd):
+    return subprocess.run(cmd, check=True, capture_output=True, text=True).stdout
+
+
+def _short(mangled):
+    """`_ZN12_GLOBAL__N_115lsnf_rev_kernelINS_6RevCfgILi1ELi1EEELi8ELb1EEEv...` -> `lsnf_rev_kernel<1, 1, 8, true>`: the kernel's
+    name and the integer / boolean template arguments in order (the Cfg<HT, WT> class contributes its two)."""
+    m = re.search(r"(\d\d)(lsnf_\w+)", mangled)          # (kernel names have 10..99 characters)
+    if not m:
+        return mangled
+    name = m.group(2)[: int(m.group(1))]
+    rest = mangled[m.start(2) + int(m.group(1)):]
+    targs = rest.split("EEv", 1)[0] if rest.startswith("I") else ""
+    vals = [v if k == "i" else ("true" if v == "1" else "false") for k, v in re.findall(r"L([ib])(\d+)E", targs)]
+    return f"{name}<{', '.join(vals)}>" if vals else name
+
+
+def kernels_of(obj):
+    """{short name: {vgpr, agpr, sgpr, lds, scratch}} of one object file."""
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        fat, co = os.path.join(tmp, "fatbin"), os.path.join(tmp, "co")
+        try:
+            _run(os.path.join(LLVM, "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", obj)
+        except subprocess.CalledProcessError:                # (an object without device code)
+            return out
+        if not os.path.exists(fat) or os.path.getsize(fat) == 0:
+            return out
+        _run(os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+             f"--input={fat}", f"--output={co}")
+        notes = _run(os.path.join(LLVM, "llvm-readelf"), "--notes", co)
+    cur = None
+    for line in notes.splitlines():
+        s = line.strip()
+        if s.startswith("- "):                               # a new entry of a YAML list (kernels, or their args)
+            if cur and ".name" in cur and ".vgpr_count" in cur:
+                out[_short(cur[".name"])] = {k: int(cur.get(f, 0)) for k, f in FIELDS}
+            cur, s = {}, s[2:].strip()
+        if cur is not None and ":" in s:
+            k, v = s.split(":", 1)
+            if k in (".name",) or k in [f for _, f in FIELDS]:
+                if k != ".name" or v.strip().startswith("_Z"):
+                    cur[k] = v.strip()
+    if cur and ".name" in cur and ".vgpr_count" in cur:
+        out[_short(cur[".name"])] = {k: int(cur.get(f, 0)) for k, f in FIELDS}
+    return out
+
+
+def collect(build_dir, match):
+    res = {}
+    for obj in sorted(glob.glob(os.path.join(build_dir, "*.o"))):
+        if match and match not in os.path.basename(obj):
+            continue
+        res.update(kernels_of(obj))
+    return res
+
+
+def _base(name):
+    return re.sub(r", false>$", ">", name)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("build_dir")
+    ap.add_argument("--match", default="", help="only objects whose file name contains this")
+    ap.add_argument("--against", default=None, help="a second build directory to compare with")
+    a = ap.parse_args()
+    mine = collect(a.build_dir, a.match)
+    if a.against is None:
+        print(f"{'kernel':<70} {'VGPR':>5} {'AGPR':>5} {'SGPR':>5} {'LDS':>6} {'scratch':>7}")
+        for n, r in sorted(mine.items()):
+            print(f"{n:<70} {r['vgpr']:>5} {r['agpr']:>5} {r['sgpr']:>5} {r['lds']:>6} {r['scratch']:>7}")
+        return 0
+    theirs = collect(a.against, a.match)
+    bad = 0
+    print(f"{'kernel':<70} {'VGPR':>9} {'AGPR':>9} {'LDS':>9} {'scratch':>9}")
+    for n, r in sorted(mine.items()):
+        o = theirs.get(n) or theirs.get(_base(n))
+        if o is None:
+            print(f"{n:<70} {r['vgpr']:>9} {r['agpr']:>9} {r['lds']:>9} {r['scratch']:>9}   new")
+            continue
+        same = all(r[k] == o[k] for k in ("vgpr", "agpr", "lds", "scratch"))
+        bad += not same
+        cell = lambda k: f"{o[k]}->{r[k]}" if o[k] != r[k] else f"{r[k]}"
+        print(f"{n:<70} {cell('vgpr'):>9} {cell('agpr'):>9} {cell('lds'):>9} {cell('scratch'):>9}   {'same' if same else 'CHANGED'}")
+    gone = [n for n in theirs if n not in mine and not any(_base(m) == n for m in mine)]
+    for n in sorted(gone):
+        print(f"{n:<70} only in {a.against}")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
