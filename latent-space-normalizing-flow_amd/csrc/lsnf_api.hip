@@ -14,91 +14,7 @@
 #endif
 
 #include "../../include/lsnf_flow.h"
-#include "lsnf_layout.h"
-
-// kernel launchers (other translation units) and the predicates of what each takes (pure host functions, no HIP calls)
-hipError_t lsnf_launch_prepare(const LsnfGeo& g, const float* const* params_host, float* plan, void* scratch, hipStream_t stream);
-size_t lsnf_prep_scratch_bytes(int nz, int depth);
-hipError_t lsnf_launch_forward(const LsnfGeo& g, const float* plan, int first_block, int n_blocks, int B,
-                               const float* z_in, const float* objective, float* z_out, float* logdet_out,
-                               float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4,
-                               hipStream_t stream);
-bool lsnf_forward3_covers(const LsnfGeo& g, int n_blocks, bool stats, bool fixup);
-hipError_t lsnf_launch_forward3(const LsnfGeo& g, const float* plan, int first_block, int n_blocks, int B,
-                                const float* z_in, const float* objective, float* z_out, float* logdet_out,
-                                float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4,
-                                int fixup, hipStream_t stream, float* hdump = nullptr, int hdump_tiled = 0);
-bool lsnf_forward3q_covers(const LsnfGeo& g, int first_block, int n_blocks, int B, int vec4, const float* z_out,
-                           const float* z_saved, const float* act_saved, const float* hdump, int hdump_tiled);
-hipError_t lsnf_launch_forward3q(const LsnfGeo& g, const float* plan, int first_block, int n_blocks, int B,
-                                 const float* z_in, const float* objective, float* z_out, float* logdet_out,
-                                 float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4, hipStream_t stream,
-                                 float* hdump = nullptr, int hdump_tiled = 0);
-bool lsnf_forward2h_covers(const LsnfGeo& g, int n_blocks, bool stats, bool fixup);
-hipError_t lsnf_launch_forward2h(const LsnfGeo& g, const float* plan, int first_block, int n_blocks, int B,
-                                 const float* z_in, const float* objective, float* z_out, float* logdet_out,
-                                 float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4,
-                                 int fixup, hipStream_t stream, float* hdump = nullptr, int hdump_tiled = 0);
-int lsnf_small3_forward_st(const LsnfGeo& g, int n_blocks, int B, bool extras);
-hipError_t lsnf_launch_small3_forward(const LsnfGeo& g, const float* plan, int first_block, int n_blocks, int B,
-                                      const float* z_in, const float* objective, float* z_out, float* logdet_out,
-                                      float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4, int st,
-                                      hipStream_t stream, float* hdump);
-hipError_t lsnf_launch_small3_restash(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
-                                      float* act_saved, int vec4, hipStream_t stream);
-bool lsnf_small_forward_covers(const LsnfGeo& g, int n_blocks);
-hipError_t lsnf_launch_small_forward(const LsnfGeo& g, const float* plan, int first_block, int n_blocks, int B,
-                                     const float* z_in, const float* objective, float* z_out, float* logdet_out,
-                                     float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4,
-                                     hipStream_t stream);
-// (the reverse launchers: smp != NULL runs the kernel's sampling form -- lsnf_sample -- which draws its rows; z_in / objective NULL)
-hipError_t lsnf_launch_reverse(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                               float* z_out, float* objective_out, int vec4, hipStream_t stream, const LsnfSampleArgs* smp = nullptr);
-int lsnf_small3_reverse_st(const LsnfGeo& g, int B);
-hipError_t lsnf_launch_small3_reverse(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                                      float* z_out, float* objective_out, int vec4, int st, hipStream_t stream,
-                                      const LsnfSampleArgs* smp = nullptr);
-bool lsnf_reverse3_covers(const LsnfGeo& g);
-hipError_t lsnf_launch_reverse3(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                                float* z_out, float* objective_out, int vec4, int fixup, hipStream_t stream,
-                                const LsnfSampleArgs* smp = nullptr);
-bool lsnf_reverse2h_covers(const LsnfGeo& g);
-hipError_t lsnf_launch_reverse2h(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                                 float* z_out, float* objective_out, int vec4, int fixup, hipStream_t stream,
-                                 const LsnfSampleArgs* smp = nullptr);
-bool lsnf_small_reverse_covers(const LsnfGeo& g);
-hipError_t lsnf_launch_small_reverse(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                                     float* z_out, float* objective_out, int vec4, hipStream_t stream,
-                                     const LsnfSampleArgs* smp = nullptr);
-hipError_t lsnf_launch_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
-                                  const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
-                                  float* g_z_in, float* dump, double* gl_total, int vec4, hipStream_t stream,
-                                  const LsnfLangevinArgs* lv, const float* act_saved);
-bool lsnf_small_backward_covers(const LsnfGeo& g);
-hipError_t lsnf_launch_small_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
-                                        const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale, float* g_z_in,
-                                        int vec4, hipStream_t stream, const LsnfLangevinArgs* lv, const float* act_saved,
-                                        float* dump, double* gl_total);
-int lsnf_small3_backward_st(const LsnfGeo& g, int B);
-hipError_t lsnf_launch_small3_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
-                                         const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode,
-                                         float ll_scale, float* g_z_in, int vec4, int st, hipStream_t stream,
-                                         const LsnfLangevinArgs* lv, float* dump, double* gl_total);
-int lsnf_small3_reverse_backward_st(const LsnfGeo& g, int B);
-hipError_t lsnf_launch_small3_reverse_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
-                                                 const float* act_saved, const float* g_x, const float* g_obj, float* g_z_in,
-                                                 int vec4, int st, hipStream_t stream);
-hipError_t lsnf_launch_backward3_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
-                                   const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
-                                   float* g_z_in, int vec4, hipStream_t stream, const LsnfLangevinArgs* lv,
-                                   float* dump, double* gl_total, int dump_tiled);
-bool lsnf_contract_x3_covers(int B, int nz, int half, int width, const float* z_in, const float* z_out, const float* z_saved);
-hipError_t lsnf_launch_params_contract(const LsnfGeo& g, const float* plan, const float* const* params_host,
-                                       float* const* grads_host, int B, const float* z_in, const float* z_out,
-                                       const float* z_saved, float* workspace, int contraction, int g_tiled, hipStream_t stream);
-size_t lsnf_init_workspace_bytes(const LsnfGeo& g, int B);
-hipError_t lsnf_launch_actnorm_init(const LsnfGeo& g, float* const* params_host, int B, const float* z_in, void* workspace,
-                                    hipStream_t stream);
+#include "lsnf_launch.h"      // the call descriptors, the launchers and their coverage predicates
 
 namespace {
 thread_local char g_err[512] = "";
@@ -209,23 +125,36 @@ int launch_fail(hipError_t e, const char* entry, Kernel k) {
 //  - bf16x3: the vector work software-pipelined under 16x16x32 MFMAs (lsnf_fwd3p.hip) where it applies;
 //  - the bf16x3 family: the error-free split on the bf16 matrix pipe (lsnf_fwd3.hip);
 //  - the fp32-MFMA kernel -- not with the parameter-gradient dump, which only the bf16 kernels write.
-Pick select_forward(const LsnfGeo& g, int first_block, int n_blocks, int B, int small_max, int vec4, const float* z_in,
-                    const float* objective, const float* z_out, const float* logdet_out, const float* z_saved,
-                    const float* act_saved, bool stats, const float* hdump, int hdump_tiled) {
+Pick select_forward(const LsnfForwardCall& c, int small_max) {
     const int math = math_mode();
-    if (B <= small_max) {
+    if (c.B <= small_max) {
         if (l16_math())
-            if (int st = lsnf_small3_forward_st(g, n_blocks, B, z_saved || act_saved || hdump)) return {K_SMALL3_FWD, st};
-        return {!hdump && lsnf_small_forward_covers(g, n_blocks) ? K_SMALL_FWD : K_NONE};
+            if (int st = lsnf_small3_forward_st(c)) return {K_SMALL3_FWD, st};
+        return {!c.hdump && lsnf_small_forward_covers(c) ? K_SMALL_FWD : K_NONE};
     }
-    if (math == LSNF_MATH_FP16X2 && !stats && z_in != z_out && (objective == nullptr || objective != logdet_out) &&
-        lsnf_forward2h_covers(g, n_blocks, false, false) && lsnf_forward3_covers(g, n_blocks, false, true))
+    if (math == LSNF_MATH_FP16X2 && !c.stats && c.z_in != c.z_out && (c.objective == nullptr || c.objective != c.logdet_out) &&
+        lsnf_forward2h_covers(c, /*fixup=*/0) && lsnf_forward3_covers(c, /*fixup=*/1))
         return {K_FWD2H_FIXUP};
-    if (math == LSNF_MATH_BF16X3 && (!hdump || hdump_tiled) &&
-        lsnf_forward3q_covers(g, first_block, n_blocks, B, vec4, z_out, z_saved, act_saved, hdump, hdump_tiled))
-        return {K_FWD3Q};
-    if (l16_math() && lsnf_forward3_covers(g, n_blocks, stats, false)) return {K_FWD3};
-    return {hdump ? K_NONE : K_FWD};
+    if (math == LSNF_MATH_BF16X3 && (!c.hdump || c.hdump_tiled) && lsnf_forward3q_covers(c)) return {K_FWD3Q};
+    if (l16_math() && lsnf_forward3_covers(c, /*fixup=*/0)) return {K_FWD3};
+    return {c.hdump ? K_NONE : K_FWD};
+}
+// the launch(es) of a forward pick
+hipError_t launch_forward(Pick p, const LsnfForwardCall& c) {
+    switch (p.k) {
+    case K_SMALL3_FWD: return lsnf_launch_small3_forward(c, p.st);
+    case K_SMALL_FWD: return lsnf_launch_small_forward(c);
+    case K_FWD2H_FIXUP: {
+        LsnfForwardCall pair = c;
+        pair.stats = nullptr; pair.hdump_tiled = 0;      // (both launches of the fp16x2 pair: no in-kernel batch sums, the dump row-major)
+        const hipError_t e = lsnf_launch_forward2h(pair, /*fixup=*/0);
+        return e != hipSuccess ? e : lsnf_launch_forward3(pair, /*fixup=*/1);
+    }
+    case K_FWD3Q: return lsnf_launch_forward3q(c);
+    case K_FWD3: return lsnf_launch_forward3(c, /*fixup=*/0);
+    case K_FWD: return lsnf_launch_forward(c);
+    default: return hipSuccess;
+    }
 }
 
 // Reverse (sampling).  It neither writes nor reads a stash, so under the automatic threshold the bf16x3 family takes its own
@@ -234,85 +163,67 @@ Pick select_forward(const LsnfGeo& g, int first_block, int n_blocks, int B, int 
 // pass, as in the forward).  The latency form also stands in where the throughput form does not fit (it is faster than the
 // fp32 throughput reverse), and the throughput form where the latency form does not.  Otherwise the fp32-MFMA kernels of the
 // batch size's family.
-Pick select_reverse(const LsnfGeo& g, int B, const float* z_in, const float* objective, const float* z_out,
-                    const float* objective_out) {
+Pick select_reverse(const LsnfReverseCall& c) {
     const int small_max = small_batch_max();
     if (l16_math()) {
         const int math = math_mode();
         int lat_max = small_max;
         if (small_batch_setting() == LSNF_SMALL_BATCH_AUTO && math != LSNF_MATH_FP16X2 && lat_max < 24576) lat_max = 24576;
-        if (B > lat_max) {
-            if (math == LSNF_MATH_FP16X2 && z_in != z_out && (objective == nullptr || objective != objective_out) &&
-                lsnf_reverse2h_covers(g) && lsnf_reverse3_covers(g))
+        if (c.B > lat_max) {
+            if (math == LSNF_MATH_FP16X2 && c.z_in != c.z_out && (c.objective == nullptr || c.objective != c.objective_out) &&
+                lsnf_reverse2h_covers(c) && lsnf_reverse3_covers(c))
                 return {K_REV2H_FIXUP};
-            if (lsnf_reverse3_covers(g)) return {K_REV3};
+            if (lsnf_reverse3_covers(c)) return {K_REV3};
         }
         if (lat_max > 0)
-            if (int st = lsnf_small3_reverse_st(g, B)) return {K_SMALL3_REV, st};
-        if (B > small_max && B <= lat_max && lsnf_reverse3_covers(g)) return {K_REV3};
+            if (int st = lsnf_small3_reverse_st(c)) return {K_SMALL3_REV, st};
+        if (c.B > small_max && c.B <= lat_max && lsnf_reverse3_covers(c)) return {K_REV3};
     }
-    if (B > small_max) return {K_REV};
-    return {lsnf_small_reverse_covers(g) ? K_SMALL_REV : K_NONE};
+    if (c.B > small_max) return {K_REV};
+    return {lsnf_small_reverse_covers(c) ? K_SMALL_REV : K_NONE};
 }
-
-// Sampling (lsnf_sample): the reverse's kernels in their sampling form, so the reverse's selection -- same families, same
-// crossovers -- for a call whose inputs alias nothing (there are none: under fp16x2 the fix-up pass redraws the rows of the
-// workgroups it recomputes).
-Pick select_sample(const LsnfGeo& g, int B, const float* z_out, const float* objective_out) {
-    return select_reverse(g, B, /*z_in=*/nullptr, /*objective=*/nullptr, z_out, objective_out);
-}
+// Sampling (lsnf_sample) is the reverse's kernels in their sampling form (c.smp), so the reverse's selection -- same families,
+// same crossovers -- for a call whose inputs alias nothing: lsnf_sample leaves z_in / objective NULL (under fp16x2 the fix-up
+// pass redraws the rows of the workgroups it recomputes).
 // the launch(es) of a reverse / sampling pick
-hipError_t launch_reverse(Pick p, const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                          float* z_out, float* objective_out, int vec4, hipStream_t st, const LsnfSampleArgs* smp) {
-    hipError_t e = hipSuccess;
+hipError_t launch_reverse(Pick p, const LsnfReverseCall& c) {
     switch (p.k) {
-    case K_REV2H_FIXUP:
-        e = lsnf_launch_reverse2h(g, plan, B, z_in, objective, z_out, objective_out, vec4, /*fixup=*/0, st, smp);
-        if (e == hipSuccess) e = lsnf_launch_reverse3(g, plan, B, z_in, objective, z_out, objective_out, vec4, /*fixup=*/1, st, smp);
-        break;
-    case K_REV3: e = lsnf_launch_reverse3(g, plan, B, z_in, objective, z_out, objective_out, vec4, /*fixup=*/0, st, smp); break;
-    case K_SMALL3_REV: e = lsnf_launch_small3_reverse(g, plan, B, z_in, objective, z_out, objective_out, vec4, p.st, st, smp); break;
-    case K_SMALL_REV: e = lsnf_launch_small_reverse(g, plan, B, z_in, objective, z_out, objective_out, vec4, st, smp); break;
-    case K_REV: e = lsnf_launch_reverse(g, plan, B, z_in, objective, z_out, objective_out, vec4, st, smp); break;
-    default: break;
+    case K_REV2H_FIXUP: {
+        const hipError_t e = lsnf_launch_reverse2h(c, /*fixup=*/0);
+        return e != hipSuccess ? e : lsnf_launch_reverse3(c, /*fixup=*/1);
     }
-    return e;
+    case K_REV3: return lsnf_launch_reverse3(c, /*fixup=*/0);
+    case K_SMALL3_REV: return lsnf_launch_small3_reverse(c, p.st);
+    case K_SMALL_REV: return lsnf_launch_small_reverse(c);
+    case K_REV: return lsnf_launch_reverse(c);
+    default: return hipSuccess;
+    }
 }
 
 // Backward (lsnf_backward_z, lsnf_langevin_step, lsnf_backward_params): from the activation stash on the bf16 matrix pipe when
 // the call brings one under a bf16x3-family mode (lsnf_small3_bwd.hip / lsnf_bwd3.hip: both take every such call), otherwise
 // the recomputing fp32-MFMA kernels -- the latency or the throughput family by the common threshold, so that the family that
 // wrote a stash is the family that reads it.
-Pick select_backward(const LsnfGeo& g, int B, const float* act_saved) {
-    const bool small = B <= small_batch_max();
-    if (act_saved && l16_math()) return small ? Pick{K_SMALL3_BWD, lsnf_small3_backward_st(g, B)} : Pick{K_BWD3};
+Pick select_backward(const LsnfBackwardCall& c) {
+    const bool small = c.B <= small_batch_max();
+    if (c.act_saved && l16_math()) return small ? Pick{K_SMALL3_BWD, lsnf_small3_backward_st(c)} : Pick{K_BWD3};
     if (!small) return {K_BWD};
-    return {lsnf_small_backward_covers(g) ? K_SMALL_BWD : K_NONE};
+    return {lsnf_small_backward_covers(c) ? K_SMALL_BWD : K_NONE};
 }
-hipError_t launch_backward(Pick p, const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
-                           const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
-                           float* g_z_in, int vec4, hipStream_t stream, const LsnfLangevinArgs* lv,
-                           float* dump = nullptr, double* gl_total = nullptr, int dump_tiled = 0) {
+hipError_t launch_backward(Pick p, const LsnfBackwardCall& c) {
     switch (p.k) {
-    case K_SMALL3_BWD:
-        return lsnf_launch_small3_backward_z(g, plan, B, z_out, z_saved, act_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in,
-                                             vec4, p.st, stream, lv, dump, gl_total);
-    case K_BWD3:
-        return lsnf_launch_backward3_z(g, plan, B, z_out, z_saved, act_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in, vec4,
-                                       stream, lv, dump, gl_total, dump_tiled);
-    case K_SMALL_BWD:
-        return lsnf_launch_small_backward_z(g, plan, B, z_out, z_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in, vec4,
-                                            stream, lv, act_saved, dump, gl_total);
-    default:
-        return lsnf_launch_backward_z(g, plan, B, z_out, z_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in, dump, gl_total,
-                                      vec4, stream, lv, act_saved);
+    case K_SMALL3_BWD: return lsnf_launch_small3_backward_z(c, p.st);
+    case K_BWD3: return lsnf_launch_backward3_z(c);
+    case K_SMALL_BWD: return lsnf_launch_small_backward_z(c);
+    case K_BWD: return lsnf_launch_backward_z(c);
+    default: return hipSuccess;
     }
 }
 
 // Backward of the reverse pass (lsnf_reverse_backward_z): one kernel (lsnf_small3_rbwd.hip) whose bf16x3 arithmetic is not narrower
 // than fp32, so it serves every math mode; its workgroup shape follows the batch size alone (more rounds of workgroups above
 // 16 384 rows), not the small-batch threshold -- it reads the stash of whichever forward family the threshold selected.
-Pick select_reverse_backward(const LsnfGeo& g, int B) { return {K_SMALL3_RBWD, lsnf_small3_reverse_backward_st(g, B)}; }
+Pick select_reverse_backward(const LsnfReverseBackwardCall& c) { return {K_SMALL3_RBWD, lsnf_small3_reverse_backward_st(c)}; }
 
 // Batch contraction of the parameter gradients (LsnfContraction): on the bf16 matrix pipe where lsnf_params3.hip covers the
 // call (use_x3); from 4 096 rows the fp32-MFMA kernel through LDS, with the widest row loads the rows allow -- every row the
@@ -335,8 +246,10 @@ int select_contraction(const LsnfGeo& g, int B, bool use_x3, int vec4) {
 // forward's would hand a tiled dump to the fp32 contraction, which reads it row-major.
 bool dump_may_tile(const LsnfGeo& g, int B, int small_max) {
     const int math = math_mode();
+    LsnfContractCall any;                // (the contraction's rule for the call's shape: no tensors, NULL is 16-byte aligned)
+    any.g = g; any.B = B;
     return B > small_max && (math == LSNF_MATH_BF16X3 || math == LSNF_MATH_BF16X3_PHASED) && lsnf_dump_can_tile(g.nz, g.width) &&
-           lsnf_contract_x3_covers(B, g.nz, g.half, g.width, nullptr, nullptr, nullptr);
+           lsnf_contract_x3_covers(any);
 }
 }  // namespace
 
@@ -391,7 +304,9 @@ int lsnf_prepare(const float* const* params_host, int nz, int width, int depth, 
         if (!params_host[i] || !aligned4(params_host[i]))
             return fail(LSNF_E_ARG, "lsnf_prepare: parameter pointer %d (block %d, slot %d) is NULL or misaligned", i,
                         i / LSNF_PARAMS_PER_BLOCK, i % LSNF_PARAMS_PER_BLOCK);
-    hipError_t e = lsnf_launch_prepare(g, params_host, plan, scratch, (hipStream_t)stream);
+    LsnfPrepareCall c;
+    c.g = g; c.params_host = params_host; c.plan = plan; c.scratch = scratch; c.stream = (hipStream_t)stream;
+    hipError_t e = lsnf_launch_prepare(c);
     if (e != hipSuccess) return hip_fail(e, "lsnf_prepare launch");
     return LSNF_OK;
 }
@@ -414,7 +329,9 @@ int lsnf_actnorm_init(float* const* params_host, int nz, int width, int depth, i
         if (!params_host[i] || !aligned4(params_host[i]))
             return fail(LSNF_E_ARG, "lsnf_actnorm_init: parameter pointer %d (block %d, slot %d) is NULL or misaligned", i,
                         i / LSNF_PARAMS_PER_BLOCK, i % LSNF_PARAMS_PER_BLOCK);
-    hipError_t e = lsnf_launch_actnorm_init(g, params_host, B, z_in, workspace, (hipStream_t)stream);
+    LsnfInitCall c;
+    c.g = g; c.params_host = params_host; c.B = B; c.z_in = z_in; c.workspace = workspace; c.stream = (hipStream_t)stream;
+    hipError_t e = lsnf_launch_actnorm_init(c);
     if (e != hipSuccess) return hip_fail(e, "lsnf_actnorm_init launch");
     return LSNF_OK;
 }
@@ -471,41 +388,13 @@ int lsnf_forward(const float* plan, int nz, int width, int depth, int coupling, 
                               (hipStream_t)stream) != hipSuccess)
             return fail(LSNF_E_HIP, "lsnf_forward: hipMemsetD32Async(workspace tag) failed");
     }
-    const Pick p = select_forward(g, first_block, n_blocks, B, small_max, vec4, z_in, objective, z_out, logdet_out, z_saved,
-                                  act_saved, stats != nullptr, hdump, hdump_tiled);
-    const hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSuccess;
-    switch (p.k) {
-    case K_SMALL3_FWD:
-        e = lsnf_launch_small3_forward(g, plan, first_block, n_blocks, B, z_in, objective, z_out, logdet_out, ll_out, z_saved,
-                                       act_saved, stats, vec4, p.st, st, hdump);
-        break;
-    case K_SMALL_FWD:
-        e = lsnf_launch_small_forward(g, plan, first_block, n_blocks, B, z_in, objective, z_out, logdet_out, ll_out, z_saved,
-                                      act_saved, stats, vec4, st);
-        break;
-    case K_FWD2H_FIXUP:
-        e = lsnf_launch_forward2h(g, plan, first_block, n_blocks, B, z_in, objective, z_out, logdet_out, ll_out, z_saved,
-                                  act_saved, nullptr, vec4, /*fixup=*/0, st, hdump);
-        if (e == hipSuccess)
-            e = lsnf_launch_forward3(g, plan, first_block, n_blocks, B, z_in, objective, z_out, logdet_out, ll_out, z_saved,
-                                     act_saved, nullptr, vec4, /*fixup=*/1, st, hdump);
-        break;
-    case K_FWD3Q:
-        e = lsnf_launch_forward3q(g, plan, first_block, n_blocks, B, z_in, objective, z_out, logdet_out, ll_out, z_saved,
-                                  act_saved, stats, vec4, st, hdump, hdump_tiled);
-        break;
-    case K_FWD3:
-        e = lsnf_launch_forward3(g, plan, first_block, n_blocks, B, z_in, objective, z_out, logdet_out, ll_out, z_saved,
-                                 act_saved, stats, vec4, /*fixup=*/0, st, hdump, hdump_tiled);
-        break;
-    case K_FWD:
-        e = lsnf_launch_forward(g, plan, first_block, n_blocks, B, z_in, objective, z_out, logdet_out, ll_out, z_saved,
-                                act_saved, stats, vec4, st);
-        break;
-    default:
-        break;
-    }
+    LsnfForwardCall c;
+    c.g = g; c.plan = plan; c.B = B; c.vec4 = vec4; c.stream = (hipStream_t)stream;
+    c.first_block = first_block; c.n_blocks = n_blocks;
+    c.z_in = z_in; c.objective = objective; c.z_out = z_out; c.logdet_out = logdet_out; c.ll_out = ll_out;
+    c.z_saved = z_saved; c.act_saved = act_saved; c.stats = stats; c.hdump = hdump; c.hdump_tiled = hdump_tiled;
+    const Pick p = select_forward(c, small_max);
+    const hipError_t e = launch_forward(p, c);
     if (p.k == K_NONE || e != hipSuccess) return launch_fail(e, "lsnf_forward", p.k);
     return LSNF_OK;
 }
@@ -526,8 +415,10 @@ int lsnf_restash(const float* plan, int nz, int width, int depth, int coupling, 
     if (!aligned16(plan) || !aligned16(act_saved)) return fail(LSNF_E_ARG, "lsnf_restash: plan / act_saved must be 16-byte aligned");
     if (!aligned4(z_out) || !aligned4(z_saved)) return fail(LSNF_E_ARG, "lsnf_restash: tensors must be 4-byte aligned");
     if (!l16_math()) return fail(LSNF_E_ARG, "lsnf_restash: needs a bf16x3-family math mode (lsnf_params_fast_path() == 1)");
-    const hipError_t e = lsnf_launch_small3_restash(g, plan, B, z_out, z_saved, act_saved, row_vector_width(g, {z_out, z_saved}),
-                                                    (hipStream_t)stream);
+    LsnfRestashCall c;
+    c.g = g; c.plan = plan; c.B = B; c.vec4 = row_vector_width(g, {z_out, z_saved}); c.stream = (hipStream_t)stream;
+    c.z_out = z_out; c.z_saved = z_saved; c.act_saved = act_saved;
+    const hipError_t e = lsnf_launch_small3_restash(c);
     if (e != hipSuccess) return hip_fail(e, "lsnf_restash launch");
     return LSNF_OK;
 }
@@ -542,9 +433,11 @@ int lsnf_reverse(const float* plan, int nz, int width, int depth, int coupling, 
     if (!aligned16(plan)) return fail(LSNF_E_ARG, "lsnf_reverse: plan must be 16-byte aligned");
     if (!aligned4(z_in) || !aligned4(z_out) || !aligned4(objective) || !aligned4(objective_out))
         return fail(LSNF_E_ARG, "lsnf_reverse: tensors must be 4-byte aligned");
-    const int vec4 = row_vector_width(g, {z_in, z_out});
-    const Pick p = select_reverse(g, B, z_in, objective, z_out, objective_out);
-    const hipError_t e = launch_reverse(p, g, plan, B, z_in, objective, z_out, objective_out, vec4, (hipStream_t)stream, nullptr);
+    LsnfReverseCall c;
+    c.g = g; c.plan = plan; c.B = B; c.vec4 = row_vector_width(g, {z_in, z_out}); c.stream = (hipStream_t)stream;
+    c.z_in = z_in; c.objective = objective; c.z_out = z_out; c.objective_out = objective_out;
+    const Pick p = select_reverse(c);
+    const hipError_t e = launch_reverse(p, c);
     if (p.k == K_NONE || e != hipSuccess) return launch_fail(e, "lsnf_reverse", p.k);
     return LSNF_OK;
 }
@@ -566,10 +459,12 @@ int lsnf_sample(const float* plan, int nz, int width, int depth, int coupling, i
     if (!aligned4(z_out) || !aligned4(objective_out) || !aligned4(eps_out) || !aligned4(ll_out))
         return fail(LSNF_E_ARG, "lsnf_sample: tensors must be 4-byte aligned");
     if (eps_out == z_out) return fail(LSNF_E_ARG, "lsnf_sample: eps_out must not alias z_out");
-    const int vec4 = row_vector_width(g, {z_out, eps_out});
     const LsnfSampleArgs smp = {LsnfRngArgs{rng->seed, rng->offset, rng->offset_dev, rng->row0, 1}, temperature, eps_out, ll_out};
-    const Pick p = select_sample(g, B, z_out, objective_out);
-    const hipError_t e = launch_reverse(p, g, plan, B, nullptr, nullptr, z_out, objective_out, vec4, (hipStream_t)stream, &smp);
+    LsnfReverseCall c;                   // (z_in / objective stay NULL: the kernels draw the rows)
+    c.g = g; c.plan = plan; c.B = B; c.vec4 = row_vector_width(g, {z_out, eps_out}); c.stream = (hipStream_t)stream;
+    c.z_out = z_out; c.objective_out = objective_out; c.smp = &smp;
+    const Pick p = select_reverse(c);
+    const hipError_t e = launch_reverse(p, c);
     if (p.k == K_NONE || e != hipSuccess) return launch_fail(e, "lsnf_sample", p.k);
     return LSNF_OK;
 }
@@ -587,10 +482,12 @@ int lsnf_backward_z(const float* plan, int nz, int width, int depth, int couplin
         return fail(LSNF_E_ARG, "lsnf_backward_z: tensors must be 4-byte aligned");
     const int vec4 = row_vector_width(g, {z_out, g_z_in, z_saved, g_z1});
     if (act_saved && !aligned16(act_saved)) return fail(LSNF_E_ARG, "lsnf_backward_z: act_saved must be 16-byte aligned");
-    const Pick p = select_backward(g, B, act_saved);
-    const hipError_t e = p.k == K_NONE ? hipSuccess
-        : launch_backward(p, g, plan, B, z_out, z_saved, act_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in, vec4,
-                          (hipStream_t)stream, nullptr);
+    LsnfBackwardCall c;
+    c.g = g; c.plan = plan; c.B = B; c.vec4 = vec4; c.stream = (hipStream_t)stream;
+    c.z_out = z_out; c.z_saved = z_saved; c.act_saved = act_saved; c.g_z1 = g_z1; c.g_logdet = g_logdet;
+    c.ll_mode = ll_mode; c.ll_scale = ll_scale; c.g_z_in = g_z_in;
+    const Pick p = select_backward(c);
+    const hipError_t e = launch_backward(p, c);
     if (p.k == K_NONE || e != hipSuccess) return launch_fail(e, "lsnf_backward_z", p.k);
     return LSNF_OK;
 }
@@ -608,10 +505,11 @@ int lsnf_reverse_backward_z(const float* plan, int nz, int width, int depth, int
     if (!aligned16(act_saved)) return fail(LSNF_E_ARG, "lsnf_reverse_backward_z: act_saved must be 16-byte aligned");
     if (!aligned4(z_out) || !aligned4(z_saved) || !aligned4(g_x) || !aligned4(g_objective) || !aligned4(g_z_in))
         return fail(LSNF_E_ARG, "lsnf_reverse_backward_z: tensors must be 4-byte aligned");
-    const int vec4 = row_vector_width(g, {z_out, g_z_in, z_saved, g_x});
-    const Pick p = select_reverse_backward(g, B);
-    const hipError_t e = lsnf_launch_small3_reverse_backward_z(g, plan, B, z_out, z_saved, act_saved, g_x, g_objective, g_z_in, vec4,
-                                                               p.st, (hipStream_t)stream);
+    LsnfReverseBackwardCall c;
+    c.g = g; c.plan = plan; c.B = B; c.vec4 = row_vector_width(g, {z_out, g_z_in, z_saved, g_x}); c.stream = (hipStream_t)stream;
+    c.z_out = z_out; c.z_saved = z_saved; c.act_saved = act_saved; c.g_x = g_x; c.g_objective = g_objective; c.g_z_in = g_z_in;
+    const Pick p = select_reverse_backward(c);
+    const hipError_t e = lsnf_launch_small3_reverse_backward_z(c, p.st);
     if (e != hipSuccess) return launch_fail(e, "lsnf_reverse_backward_z", p.k);
     return LSNF_OK;
 }
@@ -637,10 +535,11 @@ int lsnf_langevin_step(const float* plan, int nz, int width, int depth, int coup
     LsnfLangevinArgs lv = {z_cur, grad_g, noise, z_new, gf_norm, gg_norm, step_size,
                            rng ? LsnfRngArgs{rng->seed, rng->offset, rng->offset_dev, rng->row0, 1}
                                : LsnfRngArgs{0ull, 0ull, nullptr, 0ll, 0}};
-    const Pick p = select_backward(g, B, act_saved);
-    const hipError_t e = p.k == K_NONE ? hipSuccess
-        : launch_backward(p, g, plan, B, z_out, z_saved, act_saved, nullptr, nullptr, /*ll_mode=*/1, /*ll_scale=*/-1.0f,
-                          nullptr, vec4, (hipStream_t)stream, &lv);
+    LsnfBackwardCall c;                  // (no g_z1 / g_logdet / g_z_in: the gradient of -log p, consumed by the update)
+    c.g = g; c.plan = plan; c.B = B; c.vec4 = vec4; c.stream = (hipStream_t)stream;
+    c.z_out = z_out; c.z_saved = z_saved; c.act_saved = act_saved; c.ll_mode = 1; c.ll_scale = -1.0f; c.lv = &lv;
+    const Pick p = select_backward(c);
+    const hipError_t e = launch_backward(p, c);
     if (p.k == K_NONE || e != hipSuccess) return launch_fail(e, "lsnf_langevin_step", p.k);
     return LSNF_OK;
 }
@@ -681,21 +580,28 @@ int lsnf_backward_params(const float* plan, const float* const* params_host, flo
     if (act_saved && dump_may_tile(g, B, small_batch_max()) && !(aligned16(z_in) && aligned16(z_out) && aligned16(z_saved)))
         return fail(LSNF_E_ARG, "lsnf_backward_params: with act_saved at B=%d, z_in / z_out / z_saved must be 16-byte aligned", B);
     const hipStream_t st = (hipStream_t)stream;
-    const Pick p = select_backward(g, B, act_saved);
-    const bool use_x3 = act_saved && lsnf_contract_x3_covers(B, nz, g.half, width, z_in, z_out, z_saved);
-    const int contraction = select_contraction(g, B, use_x3, vec4);
-    const int g_tiled = (use_x3 && p.k == K_BWD3 && lsnf_dump_can_tile(nz, width)) ? 1 : 0;
-    if (p.k == K_NONE) return launch_fail(hipSuccess, "lsnf_backward_params", p.k);
     // workspace: G = sum_b dL/dlogdet_b (one double in floats 0-1: in float32 the per-wave atomics lost up to ~1e-5 of it, and
     // G * 3 / G * W^-T cancel against the data terms of the actnorm.logs / 1x1-conv gradients), the folded gradients (zeroed:
     // both accumulate by atomics), then the dump the backward writes
     const size_t folded = 4 + (size_t)depth * lsnf_fold_layout(nz, width).per_block;
+    LsnfBackwardCall b;
+    b.g = g; b.plan = plan; b.B = B; b.vec4 = vec4; b.stream = st;
+    b.z_out = z_out; b.z_saved = z_saved; b.act_saved = act_saved; b.g_z1 = g_z1; b.g_logdet = g_logdet;
+    b.ll_mode = ll_mode; b.ll_scale = ll_scale; b.g_z_in = g_z_in;
+    b.dump = workspace + folded; b.gl_total = reinterpret_cast<double*>(workspace);
+    LsnfContractCall c;
+    c.g = g; c.plan = plan; c.B = B; c.vec4 = vec4; c.stream = st;
+    c.params_host = params_host; c.grads_host = grads_host; c.z_in = z_in; c.z_out = z_out; c.z_saved = z_saved; c.workspace = workspace;
+    const Pick p = select_backward(b);
+    const bool use_x3 = act_saved && lsnf_contract_x3_covers(c);
+    const int contraction = select_contraction(g, B, use_x3, vec4);
+    b.dump_tiled = c.g_tiled = (use_x3 && p.k == K_BWD3 && lsnf_dump_can_tile(nz, width)) ? 1 : 0;
+    if (p.k == K_NONE) return launch_fail(hipSuccess, "lsnf_backward_params", p.k);
     hipError_t e = hipMemsetAsync(workspace, 0, sizeof(float) * folded, st);
     if (e != hipSuccess) return hip_fail(e, "lsnf_backward_params: hipMemsetAsync(workspace)");
-    e = launch_backward(p, g, plan, B, z_out, z_saved, act_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in, vec4, st, nullptr,
-                        workspace + folded, reinterpret_cast<double*>(workspace), g_tiled);
+    e = launch_backward(p, b);
     if (e != hipSuccess) return launch_fail(e, "lsnf_backward_params", p.k);
-    e = lsnf_launch_params_contract(g, plan, params_host, grads_host, B, z_in, z_out, z_saved, workspace, contraction, g_tiled, st);
+    e = lsnf_launch_params_contract(c, contraction);
     if (e != hipSuccess)
         return hip_fail(e, contraction == LSNF_CONTRACT_X3 ? "lsnf_backward_params: lsnf_contract_x3_kernel / lsnf_unfold_kernel"
                                                            : "lsnf_backward_params: lsnf_tn_gemm kernel / lsnf_unfold_kernel");

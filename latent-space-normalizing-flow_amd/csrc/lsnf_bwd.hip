@@ -9,6 +9,7 @@
 // dL/dlogdet (g_l) is constant through the stack because logdet_out = logdet_in + (...).
 // Activation memory: only the block outputs (z_saved from lsnf_forward) -- the MLP is recomputed.
 #include "lsnf_device.h"
+#include "lsnf_launch.h"
 
 namespace {
 
@@ -290,12 +291,7 @@ __global__ __launch_bounds__(64 * NW, ((C::WT >= 4 && !SAVED) ? 1 : 2)) void lsn
 template <class C, bool DUMP, int NW, bool SAVED>
 hipError_t launch_bwd_w(const BwdArgs& a, hipStream_t stream) {
     const size_t lds = ((size_t)a.depth * C::CONST_USED + 2 * (size_t)C::SLOT) * sizeof(float);
-    auto kern = lsnf_bwd_z_kernel<C, DUMP, NW, SAVED>;
-    static unsigned long long lds_ok = 0;
-    if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
-    const unsigned grid = (unsigned)((a.B + 32 * NW - 1) / (32 * NW));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds, stream, a);
-    return hipGetLastError();
+    return lsnf_launch_kernel<lsnf_bwd_z_kernel<C, DUMP, NW, SAVED>>(lsnf_grid(a.B, 32 * NW), 64 * NW, lds, stream, a);
 }
 template <class C, bool DUMP>
 hipError_t launch_bwd(const BwdArgs& a, hipStream_t stream) {
@@ -307,21 +303,12 @@ hipError_t launch_bwd(const BwdArgs& a, hipStream_t stream) {
 
 // dump == nullptr: plain backward w.r.t. z.  dump != nullptr: also writes the per-block intermediates
 // (and accumulates sum dL/dlogdet into gl_total) that lsnf_params.hip turns into parameter gradients.
-hipError_t lsnf_launch_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
-                                  const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
-                                  float* g_z_in, float* dump, double* gl_total, int vec4, hipStream_t stream,
-                                  const LsnfLangevinArgs* lv, const float* act_saved) {
+hipError_t lsnf_launch_backward_z(const LsnfBackwardCall& c) {
     BwdArgs a;
-    a.act_saved = dump ? nullptr : act_saved;
-    a.rng = LsnfRngArgs{0ull, 0ull, nullptr, 0ll, 0};
-    a.dump = dump; a.gl_total = gl_total; a.width = g.width;
-    a.z_cur = nullptr; a.grad_g = nullptr; a.noise = nullptr; a.z_new = nullptr; a.gf_norm = nullptr; a.gg_norm = nullptr; a.step = 0.f;
-    if (lv) { a.z_cur = lv->z_cur; a.grad_g = lv->grad_g; a.noise = lv->noise; a.z_new = lv->z_new; a.gf_norm = lv->gf_norm;
-              a.gg_norm = lv->gg_norm; a.step = lv->step; a.rng = lv->rng; }
-    a.fwd_consts = plan + g.off_fwd_const; a.fwd_panels = plan + g.off_fwd_panels; a.bwd_panels = plan + g.off_bwd_panels;
-    a.z_out = z_out; a.z_saved = z_saved; a.g_z1 = g_z1; a.g_logdet = g_logdet; a.g_z_in = g_z_in;
-    a.ll_scale = ll_scale; a.ll_mode = ll_mode; a.B = B; a.nz = g.nz; a.half = g.half; a.depth = g.depth; a.vec4 = vec4;
-    return lsnf_with_cfg<BwdCfg>(g, [&](auto c) {
-        return dump ? launch_bwd<decltype(c), true>(a, stream) : launch_bwd<decltype(c), false>(a, stream);
+    lsnf_fill_backward(a, c);
+    a.act_saved = c.dump ? nullptr : c.act_saved;       // (the DUMP variant recomputes: it has no SAVED form)
+    a.fwd_consts = c.plan + c.g.off_fwd_const; a.fwd_panels = c.plan + c.g.off_fwd_panels; a.bwd_panels = c.plan + c.g.off_bwd_panels;
+    return lsnf_with_cfg<BwdCfg>(c.g, [&](auto cfg) {
+        return c.dump ? launch_bwd<decltype(cfg), true>(a, c.stream) : launch_bwd<decltype(cfg), false>(a, c.stream);
     });
 }

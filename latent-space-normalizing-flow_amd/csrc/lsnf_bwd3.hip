@@ -8,6 +8,7 @@
 // panel pairs as in the forward.
 #include <stdlib.h>
 #include "lsnf_l16.h"
+#include "lsnf_launch.h"
 
 namespace {
 
@@ -287,18 +288,14 @@ __global__ __launch_bounds__(64 * NW, 1) void lsnf_bwd3_kernel(const Bwd3Args a)
 template <class C, int NW>
 hipError_t launch_bwd3_w(const Bwd3Args& a, hipStream_t stream) {
     const size_t lds = 2 * (size_t)C::SLOT3 * sizeof(float);
-    auto kern = a.dump ? (a.dump_tiled ? lsnf_bwd3_kernel<C, NW, 2> : lsnf_bwd3_kernel<C, NW, 1>) : lsnf_bwd3_kernel<C, NW, 0>;
-    static unsigned long long lds_ok[3] = {0, 0, 0};
-    if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok[a.dump ? (a.dump_tiled ? 2 : 1) : 0]); e != hipSuccess) return e;
-    const unsigned grid = (unsigned)((a.B + 32 * NW - 1) / (32 * NW));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds, stream, a);
-    return hipGetLastError();
+    const unsigned grid = lsnf_grid(a.B, 32 * NW);
+    return a.dump ? (a.dump_tiled ? lsnf_launch_kernel<lsnf_bwd3_kernel<C, NW, 2>>(grid, 64 * NW, lds, stream, a)
+                                  : lsnf_launch_kernel<lsnf_bwd3_kernel<C, NW, 1>>(grid, 64 * NW, lds, stream, a))
+                  : lsnf_launch_kernel<lsnf_bwd3_kernel<C, NW, 0>>(grid, 64 * NW, lds, stream, a);
 }
 template <class C>
 hipError_t launch_bwd3(const Bwd3Args& a, hipStream_t stream) {
-    static const char* fw = getenv("LSNF_FORCE_WAVES");   // experiment knob (tools/): 4 or 8
-    const bool eight = fw ? atoi(fw) == 8 : a.B > 128 * 256;
-    return eight ? launch_bwd3_w<C, 8>(a, stream) : launch_bwd3_w<C, 4>(a, stream);
+    return lsnf_eight_waves(a.B) ? launch_bwd3_w<C, 8>(a, stream) : launch_bwd3_w<C, 4>(a, stream);
 }
 }  // namespace
 
@@ -312,30 +309,19 @@ hipError_t launch_bwd3(const Bwd3Args& a, hipStream_t stream) {
 #define LSNF_BWD3_ENTRY lsnf_launch_backward3_z_wide
 #else
 #define LSNF_BWD3_ENTRY lsnf_launch_backward3_z
-hipError_t lsnf_launch_backward3_z_wide(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
-                                        const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
-                                        float* g_z_in, int vec4, hipStream_t stream, const LsnfLangevinArgs* lv,
-                                        float* dump, double* gl_total, int dump_tiled);
 #endif
-hipError_t LSNF_BWD3_ENTRY(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
-                           const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
-                           float* g_z_in, int vec4, hipStream_t stream, const LsnfLangevinArgs* lv,
-                           float* dump, double* gl_total, int dump_tiled) {
-    if (!act_saved) return hipErrorInvalidValue;     // (a selection bug)
+hipError_t LSNF_BWD3_ENTRY(const LsnfBackwardCall& c) {
+    if (!c.act_saved) return hipErrorInvalidValue;     // (a selection bug)
+#ifndef LSNF_BWD3_WIDE_TU
+    if (c.g.WT == 4) return lsnf_launch_backward3_z_wide(c);
+#endif
     Bwd3Args a;
-    a.dump = dump; a.gl_total = gl_total; a.width = g.width; a.dump_tiled = dump_tiled;
-    a.panels = plan + g.off_b3b_panels;
-    a.z_out = z_out; a.z_saved = z_saved; a.act_saved = act_saved; a.g_z1 = g_z1; a.g_logdet = g_logdet; a.g_z_in = g_z_in;
-    a.z_cur = nullptr; a.grad_g = nullptr; a.noise = nullptr; a.z_new = nullptr; a.gf_norm = nullptr; a.gg_norm = nullptr; a.step = 0.f;
-    a.rng = LsnfRngArgs{0ull, 0ull, nullptr, 0ll, 0};
-    if (lv) { a.z_cur = lv->z_cur; a.grad_g = lv->grad_g; a.noise = lv->noise; a.z_new = lv->z_new; a.gf_norm = lv->gf_norm;
-              a.gg_norm = lv->gg_norm; a.step = lv->step; a.rng = lv->rng; }
-    a.ll_scale = ll_scale; a.ll_mode = ll_mode; a.B = B; a.nz = g.nz; a.half = g.half; a.depth = g.depth; a.vec4 = vec4;
+    lsnf_fill_backward(a, c);
+    a.dump_tiled = c.dump_tiled;
+    a.panels = c.plan + c.g.off_b3b_panels;
 #ifdef LSNF_BWD3_WIDE_TU
-    return launch_bwd3<Bwd3Cfg<2, 4>>(a, stream);
+    return launch_bwd3<Bwd3Cfg<2, 4>>(a, c.stream);
 #else
-    if (g.HT == 1) return launch_bwd3<Bwd3Cfg<1, 1>>(a, stream);
-    if (g.WT == 2) return launch_bwd3<Bwd3Cfg<2, 2>>(a, stream);
-    return lsnf_launch_backward3_z_wide(g, plan, B, z_out, z_saved, act_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in, vec4, stream, lv, dump, gl_total, dump_tiled);
+    return c.g.HT == 1 ? launch_bwd3<Bwd3Cfg<1, 1>>(a, c.stream) : launch_bwd3<Bwd3Cfg<2, 2>>(a, c.stream);
 #endif
 }

@@ -15,26 +15,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define LSNF_AS1 __attribute__((address_space(1)))
 #define LSNF_AS3 __attribute__((address_space(3)))
 
-// Host side: kernels that use more than 64 KiB of dynamic LDS need the attribute set once PER DEVICE of the process.
-static inline hipError_t lsnf_allow_big_lds(const void* kernel, unsigned long long* done_mask) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64 && ((*done_mask >> dev) & 1ull)) return hipSuccess;
-    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) *done_mask |= 1ull << dev;      // benign race: the call is idempotent
-    return hipSuccess;
-}
-
-// Host side: f(Cfg<HT, WT>{}) for the kernel instantiation of the geometry (lsnf_pick_tiles: (1,1), (2,2) or (2,4)).
-template <template <int, int> class Cfg, class F>
-static inline auto lsnf_with_cfg(const LsnfGeo& g, F&& f) {
-    if (g.HT == 1) return f(Cfg<1, 1>{});
-    if (g.WT == 2) return f(Cfg<2, 2>{});
-    return f(Cfg<2, 4>{});
-}
-
 // Host side: the clock-stamp buffer of the -DLSNF_STAMPS diagnostic build (leaked; address through lsnf_debug_stamps(),
 // tools/stamps.py); NULL in every other build.
 static inline unsigned long long* lsnf_stamps_buffer() {

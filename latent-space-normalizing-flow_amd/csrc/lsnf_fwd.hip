@@ -14,6 +14,7 @@
 // one barrier per pair.
 #include <stdlib.h>
 #include "lsnf_device.h"
+#include "lsnf_launch.h"
 
 namespace {
 
@@ -216,12 +217,7 @@ __global__ __launch_bounds__(64 * FWD_WAVES, 2) void lsnf_fwd_kernel(const FwdAr
 template <class C, int FWD_WAVES>
 hipError_t launch_fwd_w(const FwdArgs& a, hipStream_t stream) {
     const size_t lds = ((size_t)a.n_blocks * C::CONST_FLOATS + 2 * (size_t)C::SLOT) * sizeof(float);
-    auto kern = lsnf_fwd_kernel<C, FWD_WAVES>;
-    static unsigned long long lds_ok = 0;
-    if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
-    const unsigned grid = (unsigned)((a.B + 32 * FWD_WAVES - 1) / (32 * FWD_WAVES));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * FWD_WAVES), lds, stream, a);
-    return hipGetLastError();
+    return lsnf_launch_kernel<lsnf_fwd_kernel<C, FWD_WAVES>>(lsnf_grid(a.B, 32 * FWD_WAVES), 64 * FWD_WAVES, lds, stream, a);
 }
 
 template <class C>
@@ -239,17 +235,10 @@ unsigned long long* g_lsnf_stamps = nullptr;
 extern "C" unsigned long long* lsnf_debug_stamps(void) { return g_lsnf_stamps; }
 #endif
 // host-side dispatcher (called from lsnf_api.hip): takes every call
-hipError_t lsnf_launch_forward(const LsnfGeo& g, const float* plan, int first_block, int n_blocks, int B,
-                               const float* z_in, const float* objective, float* z_out, float* logdet_out,
-                               float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4,
-                               hipStream_t stream) {
+hipError_t lsnf_launch_forward(const LsnfForwardCall& c) {
     FwdArgs a;
-    a.stats = stats;
-    a.act_saved = act_saved ? act_saved + (size_t)first_block * lsnf_act_layout(B, g.HT, g.WT).per_block : nullptr;
-    a.consts = plan + g.off_fwd_const + (size_t)first_block * g.fwd_const_floats;
-    a.panels = plan + g.off_fwd_panels + (size_t)first_block * g.fwd_block_floats;
-    a.z_in = z_in; a.objective = objective; a.z_out = z_out; a.logdet_out = logdet_out; a.ll_out = ll_out;
-    a.z_saved = z_saved; a.B = B; a.nz = g.nz; a.half = g.half; a.n_blocks = n_blocks; a.vec4 = vec4;
-    a.stamps = B <= 128 * 4096 ? lsnf_stamps_buffer() : nullptr;
-    return lsnf_with_cfg<FwdCfg>(g, [&](auto c) { return launch_fwd<decltype(c)>(a, stream); });
+    lsnf_fill_forward(a, c);
+    a.panels = lsnf_fwd_panels_at(c);
+    a.stamps = c.B <= 128 * 4096 ? lsnf_stamps_buffer() : nullptr;
+    return lsnf_with_cfg<FwdCfg>(c.g, [&](auto cfg) { return launch_fwd<decltype(cfg)>(a, c.stream); });
 }

@@ -20,6 +20,7 @@
 // register order is directly the next GEMM's B operand.
 #include <stdlib.h>
 #include "lsnf_l16.h"
+#include "lsnf_launch.h"
 
 namespace {
 
@@ -305,20 +306,11 @@ size_t fwd3_lds(int n_blocks) { return ((size_t)n_blocks * C::CONST_FLOATS + 2 *
 
 template <class C, int F3_WAVES>
 hipError_t launch_fwd3_w(const Fwd3Args& a, hipStream_t stream) {
-    const size_t lds = fwd3_lds<C>(a.n_blocks);
-    auto kern = lsnf_fwd3b_kernel<C, F3_WAVES>;
-    static unsigned long long lds_ok = 0;
-    if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
-    const unsigned grid = (unsigned)((a.B + 32 * F3_WAVES - 1) / (32 * F3_WAVES));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * F3_WAVES), lds, stream, a);
-    return hipGetLastError();
+    return lsnf_launch_kernel<lsnf_fwd3b_kernel<C, F3_WAVES>>(lsnf_grid(a.B, 32 * F3_WAVES), 64 * F3_WAVES, fwd3_lds<C>(a.n_blocks), stream, a);
 }
 template <class C>
 hipError_t launch_fwd3(const Fwd3Args& a, hipStream_t stream) {
-    // 256-row workgroups need B > 32768 to put one on (almost) every CU; below that 128-row workgroups use twice the CUs
-    static const char* fw = getenv("LSNF_FORCE_WAVES");   // experiment knob (tools/): 4 or 8
-    const bool eight = fw ? atoi(fw) == 8 : a.B > 128 * 256;
-    return eight ? launch_fwd3_w<C, 8>(a, stream) : launch_fwd3_w<C, 4>(a, stream);
+    return lsnf_eight_waves(a.B) ? launch_fwd3_w<C, 8>(a, stream) : launch_fwd3_w<C, 4>(a, stream);
 }
 }  // namespace
 
@@ -329,36 +321,26 @@ hipError_t launch_fwd3(const Fwd3Args& a, hipStream_t stream) {
 // Does LSNF_FWD3_ENTRY take this call (host only, no HIP calls; lsnf_api.hip selects by it)?  The constants of n_blocks blocks
 // and a panel pair fit in 160 KiB of LDS; no in-kernel batch sums in the fix-up pass (a partial recomputation cannot repair
 // them), nor ever in the fp16x2 kernel.
-bool LSNF_FWD3_COVERS(const LsnfGeo& g, int n_blocks, bool stats, bool fixup) {
+bool LSNF_FWD3_COVERS(const LsnfForwardCall& c, int fixup) {
 #if LSNF_L16_PARTS == 3
-    if (fixup && stats) return false;
+    if (fixup && c.stats) return false;
 #else
-    if (stats) return false;
+    if (c.stats) return false;
 #endif
-    return lsnf_with_cfg<Fwd3Cfg>(g, [&](auto c) { return fwd3_lds<decltype(c)>(n_blocks) <= 160 * 1024; });
+    return lsnf_with_cfg<Fwd3Cfg>(c.g, [&](auto cfg) { return fwd3_lds<decltype(cfg)>(c.n_blocks) <= 160 * 1024; });
 }
 
-hipError_t LSNF_FWD3_ENTRY(const LsnfGeo& g, const float* plan, int first_block, int n_blocks, int B,
-                           const float* z_in, const float* objective, float* z_out, float* logdet_out,
-                           float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4,
-                           int fixup, hipStream_t stream, float* hdump, int hdump_tiled) {
-    if (!LSNF_FWD3_COVERS(g, n_blocks, stats != nullptr, fixup)) return hipErrorInvalidValue;    // (a selection bug)
+hipError_t LSNF_FWD3_ENTRY(const LsnfForwardCall& c, int fixup) {
+    if (!LSNF_FWD3_COVERS(c, fixup)) return hipErrorInvalidValue;    // (a selection bug)
     Fwd3Args a;
-    a.hdump_tiled = hdump_tiled;
-    a.hdump = hdump ? hdump + (size_t)first_block * lsnf_dump_layout(B, g.nz, g.width).per_block : nullptr;
-    a.width = g.width;
-    a.fixup = fixup;
-    a.guard = reinterpret_cast<const unsigned*>(plan + g.off_guard);
-    a.stats = stats;
-    a.act_saved = act_saved ? act_saved + (size_t)first_block * lsnf_act_layout(B, g.HT, g.WT).per_block : nullptr;
-    a.consts = plan + g.off_fwd_const + (size_t)first_block * g.fwd_const_floats;
+    lsnf_fill_forward(a, c);
+    a.hdump_tiled = c.hdump_tiled; a.hdump = lsnf_hdump_at(c); a.width = c.g.width;
+    a.fixup = fixup; a.guard = lsnf_guard_words(c);
 #if LSNF_L16_PARTS == 3
-    a.panels3 = plan + g.off_f3b_panels + (size_t)first_block * g.f3_block_floats;
+    a.panels3 = lsnf_f3b_panels_at(c);
 #else
-    a.panels3 = plan + g.off_f2h_panels + (size_t)first_block * g.f2h_block_floats;
+    a.panels3 = lsnf_f2h_panels_at(c);
 #endif
-    a.z_in = z_in; a.objective = objective; a.z_out = z_out; a.logdet_out = logdet_out; a.ll_out = ll_out;
-    a.z_saved = z_saved; a.B = B; a.nz = g.nz; a.half = g.half; a.n_blocks = n_blocks; a.vec4 = vec4;
     a.stamps = lsnf_stamps_buffer();
-    return lsnf_with_cfg<Fwd3Cfg>(g, [&](auto c) { return launch_fwd3<decltype(c)>(a, stream); });
+    return lsnf_with_cfg<Fwd3Cfg>(c.g, [&](auto cfg) { return launch_fwd3<decltype(cfg)>(a, c.stream); });
 }

@@ -32,6 +32,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "lsnf_l16.h"
+#include "lsnf_launch.h"
 
 #if LSNF_L16_PARTS != 3
 #error "lsnf_fwd3p.hip is the three-term bf16 kernel"
@@ -736,13 +737,7 @@ size_t fwd3q_lds(int n_blocks) {
 
 template <int WT, int NWAVES, int ST, int STASH = 0>
 hipError_t launch_fwd3q_w(const Fwd3pArgs& a, hipStream_t stream) {
-    const size_t lds = fwd3q_lds(a.n_blocks);
-    auto kern = lsnf_fwd3q_kernel<WT, NWAVES, ST, STASH>;
-    static unsigned long long lds_ok = 0;
-    if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
-    const unsigned grid = (unsigned)((a.B + 16 * ST * NWAVES - 1) / (16 * ST * NWAVES));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NWAVES), lds, stream, a);
-    return hipGetLastError();
+    return lsnf_launch_kernel<lsnf_fwd3q_kernel<WT, NWAVES, ST, STASH>>(lsnf_grid(a.B, 16 * ST * NWAVES), 64 * NWAVES, fwd3q_lds(a.n_blocks), stream, a);
 }
 }  // namespace
 
@@ -751,37 +746,31 @@ hipError_t launch_fwd3q_w(const Fwd3pArgs& a, hipStream_t stream) {
 // in its tiled form only, with both parts of the stash, for the whole stack.  With the stash, or a part of it (STASH
 // instantiation: buffer stores of whole 16-byte groups through 32-bit offsets): rows that take 16-byte accesses, and a block of
 // rows / of stash tiles below 2 GiB.
-bool lsnf_forward3q_covers(const LsnfGeo& g, int first_block, int n_blocks, int B, int vec4, const float* z_out,
-                           const float* z_saved, const float* act_saved, const float* hdump, int hdump_tiled) {
-    if (g.HT != 2 || g.WT != 2 || fwd3q_lds(n_blocks) > 160 * 1024) return false;
-    if (hdump && (!hdump_tiled || !act_saved || (n_blocks > 1 && !z_saved) || first_block != 0 || (g.width & 15) ||
-                  ((size_t)B + 32) * g.width * 4 >= (1ull << 31))) return false;
-    const bool stash = act_saved != nullptr || z_saved != nullptr;
-    return !(stash && (vec4 != 4 || (size_t)B * g.nz * 4 >= (1ull << 31) || lsnf_act_layout(B, g.HT, g.WT).per_block * 4 >= (1ull << 31) ||
-                       (((size_t)act_saved | (size_t)z_saved | (size_t)z_out) & 15)));
+bool lsnf_forward3q_covers(const LsnfForwardCall& c) {
+    const LsnfGeo& g = c.g;
+    if (g.HT != 2 || g.WT != 2 || fwd3q_lds(c.n_blocks) > 160 * 1024) return false;
+    if (c.hdump && (!c.hdump_tiled || !c.act_saved || (c.n_blocks > 1 && !c.z_saved) || c.first_block != 0 || (g.width & 15) ||
+                    ((size_t)c.B + 32) * g.width * 4 >= (1ull << 31))) return false;
+    const bool stash = c.act_saved != nullptr || c.z_saved != nullptr;
+    return !(stash && (c.vec4 != 4 || (size_t)c.B * g.nz * 4 >= (1ull << 31) || lsnf_act_layout(c.B, g.HT, g.WT).per_block * 4 >= (1ull << 31) ||
+                       (((size_t)c.act_saved | (size_t)c.z_saved | (size_t)c.z_out) & 15)));
 }
 
 // the default throughput forward of LSNF_MATH_BF16X3 for the calls lsnf_forward3q_covers admits
-hipError_t lsnf_launch_forward3q(const LsnfGeo& g, const float* plan, int first_block, int n_blocks, int B,
-                                 const float* z_in, const float* objective, float* z_out, float* logdet_out,
-                                 float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4, hipStream_t stream,
-                                 float* hdump, int hdump_tiled) {
-    if (!lsnf_forward3q_covers(g, first_block, n_blocks, B, vec4, z_out, z_saved, act_saved, hdump, hdump_tiled))
-        return hipErrorInvalidValue;                                       // (a selection bug)
-    const bool stash = act_saved != nullptr || z_saved != nullptr;
+hipError_t lsnf_launch_forward3q(const LsnfForwardCall& c) {
+    if (!lsnf_forward3q_covers(c)) return hipErrorInvalidValue;            // (a selection bug)
+    const bool stash = c.act_saved != nullptr || c.z_saved != nullptr;
+    const hipStream_t stream = c.stream;
     Fwd3pArgs a;
-    a.consts = plan + g.off_fwd_const + (size_t)first_block * g.fwd_const_floats;
-    a.panels3 = plan + g.off_f3b_panels + (size_t)first_block * g.f3_block_floats;
-    a.z_in = z_in; a.objective = objective; a.z_out = z_out; a.logdet_out = logdet_out; a.ll_out = ll_out;
-    a.B = B; a.nz = g.nz; a.half = g.half; a.n_blocks = n_blocks; a.vec4 = vec4; a.stats = stats;
-    a.z_saved = z_saved; a.act_saved = act_saved ? act_saved + (size_t)first_block * lsnf_act_layout(B, g.HT, g.WT).per_block : nullptr;
-    a.hdump = hdump; a.width = g.width;
+    lsnf_fill_forward(a, c);
+    a.panels3 = lsnf_f3b_panels_at(c);
+    a.hdump = c.hdump; a.width = c.g.width;          // (the dump un-offset: lsnf_forward3q_covers demands first_block == 0 with it)
     a.stamps = lsnf_stamps_buffer();
     // workgroup shape by batch size (one workgroup per CU; 256 CUs): 256 rows (8 waves x 32) above 32 768 rows; below, 16 rows
     // per wave so that the grid still covers the chip -- 8 waves x 16 rows down to 16 384 rows, 4 waves x 16 rows below
     static const char* shape = getenv("LSNF_FWD3Q_SHAPE");     // experiment knob (tools/shard_times.py): "82", "42", "81", "41"
-    const int sh = shape ? atoi(shape) : (B > 128 * 256 ? 82 : (B > 64 * 256 ? 81 : 41));
-    if (hdump) return (sh == 82) ? launch_fwd3q_w<2, 8, 2, 2>(a, stream) : launch_fwd3q_w<2, 4, 2, 2>(a, stream);
+    const int sh = shape ? atoi(shape) : (c.B > 128 * 256 ? 82 : (c.B > 64 * 256 ? 81 : 41));
+    if (c.hdump) return (sh == 82) ? launch_fwd3q_w<2, 8, 2, 2>(a, stream) : launch_fwd3q_w<2, 4, 2, 2>(a, stream);
     if (stash) return (sh == 82) ? launch_fwd3q_w<2, 8, 2, 1>(a, stream) : launch_fwd3q_w<2, 4, 2, 1>(a, stream);
     if (sh == 82) return launch_fwd3q_w<2, 8, 2>(a, stream);
     if (sh == 42) return launch_fwd3q_w<2, 4, 2>(a, stream);

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/lsnf_flow.h"
 #include "lsnf_layout.h"
+#include "lsnf_launch.h"
 
 namespace {
 
@@ -192,8 +193,13 @@ size_t lsnf_init_workspace_bytes(const LsnfGeo& g, int B) {
     return slab_bytes(B) + sizeof(float) * ((size_t)B * (2 * (size_t)g.nz + 2 * (size_t)g.width));
 }
 
-hipError_t lsnf_launch_actnorm_init(const LsnfGeo& g, float* const* params_host, int B, const float* z_in,
-                                    void* workspace, hipStream_t stream) {
+hipError_t lsnf_launch_actnorm_init(const LsnfInitCall& c) {
+    const LsnfGeo& g = c.g;
+    float* const* params_host = c.params_host;
+    const int B = c.B;
+    const float* z_in = c.z_in;
+    void* workspace = c.workspace;
+    const hipStream_t stream = c.stream;
     const int nz = g.nz, half = g.half, width = g.width;
     const int n_out = g.coupling == 1 ? nz : half;
     double* slab = (double*)workspace;

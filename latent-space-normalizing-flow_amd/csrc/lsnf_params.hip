@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include "lsnf_layout.h"
+#include "lsnf_launch.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4v __attribute__((ext_vector_type(4)));
@@ -23,11 +24,6 @@ typedef float f32x2v __attribute__((ext_vector_type(2)));
 struct LsnfParamPtrs { const float* p[LSNF_MAX_DEPTH * 12]; };
 struct LsnfGradPtrs { float* p[LSNF_MAX_DEPTH * 12]; };
 enum { P_AB = 0, P_ALOGS, P_W, P_W1, P_B1, P_LOGS1, P_W2, P_B2, P_LOGS2, P_W3, P_B3, P_LOGS3 };
-
-// lsnf_params3.hip: the same contraction on the bf16 matrix pipe (large batches)
-hipError_t lsnf_launch_contract_x3(const float* z_in, const float* z_out, const float* z_saved, const float* dump, float* fold,
-                                   int B, int nz, int half, int width, int depth, int chunk_override, int g_tiled, const int* h_tag,
-                                   hipStream_t stream);
 
 namespace {
 
@@ -391,29 +387,25 @@ __global__ __launch_bounds__(256) void lsnf_unfold_kernel(LsnfParamPtrs pp, Lsnf
 
 // Steps (2) and (3): the batch contraction `contraction` (LsnfContraction) of the dump that the backward of step (1) wrote
 // into the zeroed workspace, then the chain rule into the parameter gradients.  g_tiled: the backward wrote its g arrays tiled.
-hipError_t lsnf_launch_params_contract(const LsnfGeo& g, const float* plan, const float* const* params_host,
-                                       float* const* grads_host, int B, const float* z_in, const float* z_out,
-                                       const float* z_saved, float* workspace, int contraction, int g_tiled, hipStream_t stream) {
-    const LsnfFoldLayout fl = lsnf_fold_layout(g.nz, g.width);
-    const double* gl_total = reinterpret_cast<const double*>(workspace);   // floats 0-1 of the 16-byte aligned workspace
-    float* fold = workspace + 4;
-    float* dump = fold + (size_t)g.depth * fl.per_block;
+hipError_t lsnf_launch_params_contract(const LsnfContractCall& c, int contraction) {
+    const LsnfGeo& g = c.g;
+    const hipStream_t stream = c.stream;
+    const double* gl_total = reinterpret_cast<const double*>(c.workspace);   // floats 0-1 of the 16-byte aligned workspace
+    float* fold = c.workspace + 4;
     TnArgs t;
-    t.z_in = z_in; t.z_out = z_out; t.z_saved = z_saved; t.dump = dump; t.fold = fold;
-    t.B = B; t.nz = g.nz; t.half = g.half; t.width = g.width; t.depth = g.depth;
-    t.chunk = B >= 16384 ? 512 : 128;                // samples per workgroup (multiple of 16; 512: 3 200 workgroups at B = 65 536 -- measured 620 us for the whole call against 672 at 1 024 and 760 at 2 048)
+    t.z_in = c.z_in; t.z_out = c.z_out; t.z_saved = c.z_saved; t.fold = fold;
+    t.dump = fold + (size_t)g.depth * lsnf_fold_layout(g.nz, g.width).per_block;
+    t.B = c.B; t.nz = g.nz; t.half = g.half; t.width = g.width; t.depth = g.depth;
+    t.chunk = c.B >= 16384 ? 512 : 128;              // samples per workgroup (multiple of 16; 512: 3 200 workgroups at B = 65 536 -- measured 620 us for the whole call against 672 at 1 024 and 760 at 2 048)
     // experiment knobs of tools/tn_probe.py (read once per process): ablation switches, samples per workgroup
     static const int knob_abl = [] { const char* e = getenv("LSNF_TN_ABL"); return e ? atoi(e) : 0; }();
     static const int knob_chunk = [] { const char* e = getenv("LSNF_TN_CHUNK"); return e ? atoi(e) : 0; }();
     t.abl = knob_abl;
     if (knob_chunk > 0) t.chunk = knob_chunk;
-    const dim3 grid(g.depth * 5, (unsigned)((B + t.chunk - 1) / t.chunk));
+    const dim3 grid(g.depth * 5, (unsigned)((c.B + t.chunk - 1) / t.chunk));
     hipError_t e = hipSuccess;
     switch (contraction) {
-    case LSNF_CONTRACT_X3:
-        e = lsnf_launch_contract_x3(z_in, z_out, z_saved, dump, fold, B, g.nz, g.half, g.width, g.depth, knob_chunk, g_tiled,
-                                    reinterpret_cast<const int*>(workspace + lsnf_params_workspace_tag(g.nz, g.width, g.depth, B)), stream);
-        break;
+    case LSNF_CONTRACT_X3: e = lsnf_launch_contract_x3(c, knob_chunk); break;
     case LSNF_CONTRACT_LDS4: hipLaunchKernelGGL(lsnf_tn_gemm_lds_kernel<4>, grid, dim3(256), 0, stream, t); break;
     case LSNF_CONTRACT_LDS2: hipLaunchKernelGGL(lsnf_tn_gemm_lds_kernel<2>, grid, dim3(256), 0, stream, t); break;
     case LSNF_CONTRACT_LDS1: hipLaunchKernelGGL(lsnf_tn_gemm_lds_kernel<1>, grid, dim3(256), 0, stream, t); break;
@@ -423,10 +415,10 @@ hipError_t lsnf_launch_params_contract(const LsnfGeo& g, const float* plan, cons
     if (e != hipSuccess) return e;
     LsnfParamPtrs pp; LsnfGradPtrs gp;
     for (int i = 0; i < LSNF_MAX_DEPTH * 12; ++i) {
-        pp.p[i] = i < g.depth * 12 ? params_host[i] : nullptr;
-        gp.p[i] = i < g.depth * 12 ? grads_host[i] : nullptr;
+        pp.p[i] = i < g.depth * 12 ? c.params_host[i] : nullptr;
+        gp.p[i] = i < g.depth * 12 ? c.grads_host[i] : nullptr;
     }
     hipLaunchKernelGGL(lsnf_unfold_kernel, dim3(g.depth, LSNF_UNFOLD_SECTIONS), dim3(256), 0, stream, pp, gp, (const float*)fold,
-                       gl_total, plan + g.off_winv, g.nz, g.width, g.coupling);
+                       gl_total, c.plan + g.off_winv, g.nz, g.width, g.coupling);
     return hipGetLastError();
 }

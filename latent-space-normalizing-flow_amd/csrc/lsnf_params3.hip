@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include "lsnf_device.h"
+#include "lsnf_launch.h"
 
 #ifndef X3_ABL
 #define X3_ABL 0          // timing experiments (wrong results): 1 no atomics, 2 no MFMA, 4 no global loads after the first two stages, 8 no split
@@ -256,20 +257,24 @@ static_assert(X3_LDS <= 160 * 1024, "lsnf_allow_big_lds admits 160 KiB");
 // Does this kernel take the contraction of such a call?  ONE rule for lsnf_forward (which then may write h1 / h2 tiled) and for
 // lsnf_backward_params: batch size, geometry (operands of <= 128 features in whole 16-byte groups, 32-bit byte offsets), the three
 // latent tensors 16-byte aligned, and the process-wide knobs LSNF_TN_X3=0 / LSNF_TN_PLAIN (fp32-MFMA kernels of lsnf_params.hip).
-bool lsnf_contract_x3_covers(int B, int nz, int half, int width, const float* z_in, const float* z_out, const float* z_saved) {
+bool lsnf_contract_x3_covers(const LsnfContractCall& c) {
     static const bool knob = [] { const char* e = getenv("LSNF_TN_X3"); return (e ? atoi(e) != 0 : true) && getenv("LSNF_TN_PLAIN") == nullptr; }();
+    const int B = c.B, nz = c.g.nz, half = c.g.half, width = c.g.width;
     if (!knob || B < LSNF_X3_MIN_ROWS) return false;
     if (nz > 128 || width > 128 || 2 * half > 128 || (nz & 3) || (width & 3) || (half & 3) || ((size_t)B + 32) * 128 * 4 >= (1ull << 31)) return false;
-    return (((size_t)z_in | (size_t)z_out | (size_t)z_saved) & 15) == 0;
+    return (((size_t)c.z_in | (size_t)c.z_out | (size_t)c.z_saved) & 15) == 0;
 }
-hipError_t lsnf_launch_contract_x3(const float* z_in, const float* z_out, const float* z_saved, const float* dump, float* fold,
-                                   int B, int nz, int half, int width, int depth, int chunk_override, int g_tiled, const int* h_tag,
-                                   hipStream_t stream) {
-    if (!lsnf_contract_x3_covers(B, nz, half, width, z_in, z_out, z_saved)) return hipErrorInvalidValue;    // (a selection bug)
+// chunk_override > 0: samples per workgroup (LSNF_TN_CHUNK, lsnf_params.hip)
+hipError_t lsnf_launch_contract_x3(const LsnfContractCall& c, int chunk_override) {
+    if (!lsnf_contract_x3_covers(c)) return hipErrorInvalidValue;    // (a selection bug)
+    const int B = c.B, depth = c.g.depth;
     X3Args a;
-    a.g_tiled = g_tiled; a.h_tag = h_tag;
-    a.z_in = z_in; a.z_out = z_out; a.z_saved = z_saved; a.dump = dump; a.fold = fold;
-    a.B = B; a.nz = nz; a.half = half; a.width = width; a.depth = depth;
+    a.g_tiled = c.g_tiled;
+    a.h_tag = reinterpret_cast<const int*>(c.workspace + lsnf_params_workspace_tag(c.g.nz, c.g.width, depth, B));
+    a.fold = c.workspace + 4;
+    a.dump = a.fold + (size_t)depth * lsnf_fold_layout(c.g.nz, c.g.width).per_block;
+    a.z_in = c.z_in; a.z_out = c.z_out; a.z_saved = c.z_saved;
+    a.B = B; a.nz = c.g.nz; a.half = c.g.half; a.width = c.g.width; a.depth = depth;
     // one round of workgroups: ~256 / depth chunks of the batch, in whole stages
     int chunks = 256 / depth;
     if (chunks < 1) chunks = 1;
@@ -278,8 +283,5 @@ hipError_t lsnf_launch_contract_x3(const float* z_in, const float* z_out, const 
     if (chunk_override > 0) chunk = (chunk_override + X3_S - 1) / X3_S * X3_S;
     a.chunk = chunk;
     chunks = (B + chunk - 1) / chunk;
-    static unsigned long long lds_ok = 0;
-    if (hipError_t e = lsnf_allow_big_lds((const void*)lsnf_contract_x3_kernel, &lds_ok); e != hipSuccess) return e;
-    hipLaunchKernelGGL(lsnf_contract_x3_kernel, dim3(chunks, depth), dim3(512), X3_LDS, stream, a);
-    return hipGetLastError();
+    return lsnf_launch_kernel<lsnf_contract_x3_kernel>(dim3(chunks, depth), 512, X3_LDS, c.stream, a);
 }

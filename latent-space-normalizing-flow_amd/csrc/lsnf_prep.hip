@@ -10,6 +10,7 @@
 // All folding arithmetic is float64, rounded to float32 once.
 #include <hip/hip_runtime.h>
 #include "lsnf_layout.h"
+#include "lsnf_launch.h"
 
 struct LsnfParamPtrs {
     const float* p[LSNF_MAX_DEPTH * 12];
@@ -468,8 +469,11 @@ __global__ __launch_bounds__(256) void lsnf_pack_kernel(LsnfParamPtrs pp, LsnfGe
 
 size_t lsnf_prep_scratch_bytes(int nz, int depth) { return sizeof(double) * scratch_block_doubles(nz) * (size_t)depth; }
 
-hipError_t lsnf_launch_prepare(const LsnfGeo& g, const float* const* params_host, float* plan, void* scratch,
-                               hipStream_t stream) {
+hipError_t lsnf_launch_prepare(const LsnfPrepareCall& c) {
+    const LsnfGeo& g = c.g;
+    const float* const* params_host = c.params_host;
+    float* plan = c.plan; void* scratch = c.scratch;
+    const hipStream_t stream = c.stream;
     LsnfParamPtrs pp;
     for (int i = 0; i < g.depth * 12; ++i) pp.p[i] = params_host[i];
     for (int i = g.depth * 12; i < LSNF_MAX_DEPTH * 12; ++i) pp.p[i] = nullptr;

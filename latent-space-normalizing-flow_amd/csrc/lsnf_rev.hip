@@ -5,6 +5,7 @@
 // Same sample-on-lane MFMA scheme as lsnf_fwd.hip; the MLP panels are the forward stream's,
 // the W^-1 panels (with exp(-3 logs) and -b folded) come from the inverse stream.
 #include "lsnf_device.h"
+#include "lsnf_launch.h"
 
 namespace {
 
@@ -131,12 +132,7 @@ __global__ __launch_bounds__(64 * NW, 2) void lsnf_rev_kernel(const std::conditi
 template <class C, int NW, bool SAMPLE, class Args>
 hipError_t launch_rev_w(const Args& a, hipStream_t stream) {
     const size_t lds = ((size_t)a.depth * C::CONST_PER_BLOCK + 2 * (size_t)C::SLOT) * sizeof(float);
-    auto kern = lsnf_rev_kernel<C, NW, SAMPLE>;
-    static unsigned long long lds_ok = 0;
-    if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
-    const unsigned grid = (unsigned)((a.B + 32 * NW - 1) / (32 * NW));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds, stream, a);
-    return hipGetLastError();
+    return lsnf_launch_kernel<lsnf_rev_kernel<C, NW, SAMPLE>>(lsnf_grid(a.B, 32 * NW), 64 * NW, lds, stream, a);
 }
 template <class C, bool SAMPLE, class Args>
 hipError_t launch_rev(const Args& a, hipStream_t stream) {
@@ -144,16 +140,11 @@ hipError_t launch_rev(const Args& a, hipStream_t stream) {
 }
 }  // namespace
 
-hipError_t lsnf_launch_reverse(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                               float* z_out, float* objective_out, int vec4, hipStream_t stream, const LsnfSampleArgs* smp) {
+hipError_t lsnf_launch_reverse(const LsnfReverseCall& c) {
     RevSampleArgs a;
-    a.fwd_consts = plan + g.off_fwd_const; a.fwd_panels = plan + g.off_fwd_panels;
-    a.inv_consts = plan + g.off_inv_const; a.inv_panels = plan + g.off_inv_panels;
-    a.z_in = z_in; a.objective = objective; a.z_out = z_out; a.objective_out = objective_out;
-    a.B = B; a.nz = g.nz; a.half = g.half; a.depth = g.depth; a.vec4 = vec4;
-    if (smp) {
-        a.s = *smp;
-        return lsnf_with_cfg<RevCfg>(g, [&](auto c) { return launch_rev<decltype(c), true>(a, stream); });
-    }
-    return lsnf_with_cfg<RevCfg>(g, [&](auto c) { return launch_rev<decltype(c), false>(static_cast<const RevArgs&>(a), stream); });
+    lsnf_fill_reverse(a, c);
+    a.fwd_panels = c.plan + c.g.off_fwd_panels; a.inv_panels = c.plan + c.g.off_inv_panels;
+    return lsnf_with_sample<RevArgs>(a, c.smp, [&](auto sample, const auto& args) {
+        return lsnf_with_cfg<RevCfg>(c.g, [&](auto cfg) { return launch_rev<decltype(cfg), decltype(sample)::value>(args, c.stream); });
+    });
 }

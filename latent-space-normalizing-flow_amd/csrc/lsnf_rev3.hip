@@ -6,6 +6,7 @@
 //   I1       : z = ([z1,z2] @ W^-1) * exp(-3 logs) - b ; objective -= log|det W| + sum 3 logs  (:193-196, 270, 246)
 #include <stdlib.h>
 #include "lsnf_l16.h"
+#include "lsnf_launch.h"
 
 namespace {
 
@@ -199,13 +200,7 @@ size_t rev3_lds(int depth) { return ((size_t)depth * C::CONST_PER_BLOCK + 2 * (s
 
 template <class C, int NW, bool SAMPLE, class Args>
 hipError_t launch_rev3_w(const Args& a, hipStream_t stream) {
-    const size_t lds = rev3_lds<C>(a.depth);
-    auto kern = lsnf_rev3_kernel<C, NW, SAMPLE>;
-    static unsigned long long lds_ok = 0;
-    if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
-    const unsigned grid = (unsigned)((a.B + 32 * NW - 1) / (32 * NW));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds, stream, a);
-    return hipGetLastError();
+    return lsnf_launch_kernel<lsnf_rev3_kernel<C, NW, SAMPLE>>(lsnf_grid(a.B, 32 * NW), 64 * NW, rev3_lds<C>(a.depth), stream, a);
 }
 template <class C, bool SAMPLE, class Args>
 hipError_t launch_rev3(const Args& a, hipStream_t stream) {
@@ -214,9 +209,7 @@ hipError_t launch_rev3(const Args& a, hipStream_t stream) {
     if constexpr (SAMPLE && C::WT == 4) {
         return launch_rev3_w<C, 4, SAMPLE>(a, stream);
     } else {
-        static const char* fw = getenv("LSNF_FORCE_WAVES");   // experiment knob (tools/): 4 or 8
-        const bool eight = fw ? atoi(fw) == 8 : a.B > 128 * 256;
-        return eight ? launch_rev3_w<C, 8, SAMPLE>(a, stream) : launch_rev3_w<C, 4, SAMPLE>(a, stream);
+        return lsnf_eight_waves(a.B) ? launch_rev3_w<C, 8, SAMPLE>(a, stream) : launch_rev3_w<C, 4, SAMPLE>(a, stream);
     }
 }
 }  // namespace
@@ -227,27 +220,21 @@ hipError_t launch_rev3(const Args& a, hipStream_t stream) {
 #endif
 // Does LSNF_REV3_ENTRY take this geometry (host only, no HIP calls; lsnf_api.hip selects by it)?  The constants of the whole
 // stack and a panel pair fit in 160 KiB of LDS.
-bool LSNF_REV3_COVERS(const LsnfGeo& g) {
-    return lsnf_with_cfg<Rev3Cfg>(g, [&](auto c) { return rev3_lds<decltype(c)>(g.depth) <= 160 * 1024; });
+bool LSNF_REV3_COVERS(const LsnfReverseCall& c) {
+    return lsnf_with_cfg<Rev3Cfg>(c.g, [&](auto cfg) { return rev3_lds<decltype(cfg)>(c.g.depth) <= 160 * 1024; });
 }
 
-hipError_t LSNF_REV3_ENTRY(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                           float* z_out, float* objective_out, int vec4, int fixup, hipStream_t stream,
-                           const LsnfSampleArgs* smp) {
-    if (!LSNF_REV3_COVERS(g)) return hipErrorInvalidValue;      // (a selection bug)
+hipError_t LSNF_REV3_ENTRY(const LsnfReverseCall& c, int fixup) {
+    if (!LSNF_REV3_COVERS(c)) return hipErrorInvalidValue;      // (a selection bug)
     Rev3SampleArgs a;
-    a.guard = reinterpret_cast<const unsigned*>(plan + g.off_guard); a.fixup = fixup;
-    a.fwd_consts = plan + g.off_fwd_const; a.inv_consts = plan + g.off_inv_const;
+    lsnf_fill_reverse(a, c);
+    a.guard = lsnf_guard_words(c); a.fixup = fixup;
 #if LSNF_L16_PARTS == 3
-    a.panels3b = plan + g.off_f3b_panels; a.ipanels3b = plan + g.off_i3b_panels;
+    a.panels3b = c.plan + c.g.off_f3b_panels; a.ipanels3b = c.plan + c.g.off_i3b_panels;
 #else
-    a.panels3b = plan + g.off_f2h_panels; a.ipanels3b = plan + g.off_i2h_panels;
+    a.panels3b = c.plan + c.g.off_f2h_panels; a.ipanels3b = c.plan + c.g.off_i2h_panels;
 #endif
-    a.z_in = z_in; a.objective = objective; a.z_out = z_out; a.objective_out = objective_out;
-    a.B = B; a.nz = g.nz; a.half = g.half; a.depth = g.depth; a.vec4 = vec4;
-    if (smp) {
-        a.s = *smp;
-        return lsnf_with_cfg<Rev3Cfg>(g, [&](auto c) { return launch_rev3<decltype(c), true>(a, stream); });
-    }
-    return lsnf_with_cfg<Rev3Cfg>(g, [&](auto c) { return launch_rev3<decltype(c), false>(static_cast<const Rev3Args&>(a), stream); });
+    return lsnf_with_sample<Rev3Args>(a, c.smp, [&](auto sample, const auto& args) {
+        return lsnf_with_cfg<Rev3Cfg>(c.g, [&](auto cfg) { return launch_rev3<decltype(cfg), decltype(sample)::value>(args, c.stream); });
+    });
 }

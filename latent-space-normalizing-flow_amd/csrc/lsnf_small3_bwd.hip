@@ -13,6 +13,7 @@
 // Four barriers per block.  The transposed matrices come as bf16x3 panels in the 16x16x32 operand order (off_b3b_panels).
 #include <stdlib.h>
 #include "lsnf_small3.h"
+#include "lsnf_launch.h"
 
 namespace {
 
@@ -374,46 +375,30 @@ hipError_t launch_small3_bwd_st(const Small3BwdArgs& a, hipStream_t stream) {
         return hipErrorInvalidValue;                 // (a selection bug)
     } else {
         const size_t lds = (size_t)Small3BwdLds<C, ST>::L_END * sizeof(float);
-        auto kern = a.dump ? lsnf_small3_bwd_kernel<C, ST, true> : lsnf_small3_bwd_kernel<C, ST, false>;
-        static unsigned long long lds_ok[2] = {0, 0};
-        if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok[a.dump ? 1 : 0]); e != hipSuccess) return e;
-        const unsigned grid = (unsigned)((a.B + ST * S3_SAMPLES - 1) / (ST * S3_SAMPLES));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, a);
-        return hipGetLastError();
+        const unsigned grid = lsnf_grid(a.B, ST * S3_SAMPLES);
+        return a.dump ? lsnf_launch_kernel<lsnf_small3_bwd_kernel<C, ST, true>>(grid, 256, lds, stream, a)
+                      : lsnf_launch_kernel<lsnf_small3_bwd_kernel<C, ST, false>>(grid, 256, lds, stream, a);
     }
 }
 }  // namespace
 
-// Rows per workgroup (16 x ST) for this call (host only, no HIP calls; lsnf_api.hip selects by it): by batch size as the forward
-// (lsnf_small3_forward_st), LSNF_SMALL3_ST forces a shape; a shape that is not instantiated gives way to the next smaller one.
-// Never 0: the kernel takes every call that brings the activation stash.
-int lsnf_small3_backward_st(const LsnfGeo& g, int B) {
-    static const char* env = getenv("LSNF_SMALL3_ST");
-    return lsnf_with_cfg<Small3BwdCfg>(g, [&](auto c) {
-        using C = decltype(c);
-        const int st = env ? atoi(env) : (B <= 256 * 16 ? 1 : (B <= 256 * 32 ? 2 : 4));
+// Rows per workgroup (16 x ST) for this call (lsnf_api.hip selects by it): what lsnf_small3_st_wanted asks for; a shape that is
+// not instantiated gives way to the next smaller one.  Never 0: the kernel takes every call that brings the activation stash.
+int lsnf_small3_backward_st(const LsnfBackwardCall& c) {
+    return lsnf_with_cfg<Small3BwdCfg>(c.g, [&](auto cfg) {
+        using C = decltype(cfg);
+        const int st = lsnf_small3_st_wanted(c.B, false);
         return (st >= 4 && small3_bwd_built<C, 4>) ? 4 : (st >= 2 && small3_bwd_built<C, 2>) ? 2 : 1;
     });
 }
 
 // the backward from the activation stash; st: lsnf_small3_backward_st of the call
-hipError_t lsnf_launch_small3_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
-                                         const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode,
-                                         float ll_scale, float* g_z_in, int vec4, int st, hipStream_t stream,
-                                         const LsnfLangevinArgs* lv, float* dump, double* gl_total) {
-    if (!act_saved) return hipErrorInvalidValue;     // (a selection bug)
+hipError_t lsnf_launch_small3_backward_z(const LsnfBackwardCall& c, int st) {
+    if (!c.act_saved) return hipErrorInvalidValue;     // (a selection bug)
     Small3BwdArgs a;
-    a.dump = dump; a.gl_total = gl_total; a.width = g.width;
-    a.panels = plan + g.off_b3b_panels;
-    a.z_out = z_out; a.z_saved = z_saved; a.act_saved = act_saved; a.g_z1 = g_z1; a.g_logdet = g_logdet; a.g_z_in = g_z_in;
-    a.z_cur = nullptr; a.grad_g = nullptr; a.noise = nullptr; a.z_new = nullptr; a.gf_norm = nullptr; a.gg_norm = nullptr; a.step = 0.f;
-    a.rng = LsnfRngArgs{0ull, 0ull, nullptr, 0ll, 0};
-    if (lv) { a.z_cur = lv->z_cur; a.grad_g = lv->grad_g; a.noise = lv->noise; a.z_new = lv->z_new; a.gf_norm = lv->gf_norm;
-              a.gg_norm = lv->gg_norm; a.step = lv->step; a.rng = lv->rng; }
-    a.ll_scale = ll_scale; a.ll_mode = ll_mode; a.B = B; a.nz = g.nz; a.half = g.half; a.depth = g.depth; a.vec4 = vec4;
-    return lsnf_with_cfg<Small3BwdCfg>(g, [&](auto c) {
-        using C = decltype(c);
-        return st == 4 ? launch_small3_bwd_st<C, 4>(a, stream) : st == 2 ? launch_small3_bwd_st<C, 2>(a, stream)
-                                                                         : launch_small3_bwd_st<C, 1>(a, stream);
+    lsnf_fill_backward(a, c);
+    a.panels = c.plan + c.g.off_b3b_panels;
+    return lsnf_with_cfg<Small3BwdCfg>(c.g, [&](auto cfg) {
+        return lsnf_with_st(st, [&](auto s) { return launch_small3_bwd_st<decltype(cfg), decltype(s)::value>(a, c.stream); });
     });
 }

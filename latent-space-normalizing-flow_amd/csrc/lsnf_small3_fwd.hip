@@ -16,6 +16,7 @@
 // samples) is 4 registers per lane: feature 16*ft + 4*g + r.
 #include <stdlib.h>
 #include "lsnf_small3.h"
+#include "lsnf_launch.h"
 
 namespace {
 
@@ -551,71 +552,53 @@ hipError_t launch_small3_fwd_st(const Small3Args& a, hipStream_t stream) {
         return hipErrorInvalidValue;                 // (a selection bug)
     } else {
         const size_t lds = small3_fwd_lds<C, ST>(a.n_blocks);
+        const unsigned grid = lsnf_grid(a.B, ST * S3_SAMPLES);
         const bool extras = a.z_saved != nullptr || a.act_saved != nullptr || a.hdump != nullptr;
-        auto kern = extras ? lsnf_small3_fwd_kernel<C, ST, true> : lsnf_small3_fwd_kernel<C, ST, false>;
-        static unsigned long long lds_ok[2] = {0, 0};
-        if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok[extras]); e != hipSuccess) return e;
-        const unsigned grid = (unsigned)((a.B + ST * S3_SAMPLES - 1) / (ST * S3_SAMPLES));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, a);
-        return hipGetLastError();
+        return extras ? lsnf_launch_kernel<lsnf_small3_fwd_kernel<C, ST, true>>(grid, 256, lds, stream, a)
+                      : lsnf_launch_kernel<lsnf_small3_fwd_kernel<C, ST, false>>(grid, 256, lds, stream, a);
     }
 }
 }  // namespace
 
-// Rows per workgroup (16 x ST) for this call, 0 if the kernel does not take it (host only, no HIP calls; lsnf_api.hip selects by
-// it).  By batch size: 16 while one round of workgroups covers the batch (<= 256 CUs x 16 rows), then 32, then 64 -- the weight
-// stream per workgroup is the same, so a second round (or a second workgroup per CU) costs a whole stream while a second sample
-// tile costs its MFMAs only.  LSNF_SMALL3_ST (1 / 2 / 4) forces a shape (experiments, tests).  A shape whose constants of
-// n_blocks blocks do not fit in 160 KiB of LDS gives way to the next smaller one.
-int lsnf_small3_forward_st(const LsnfGeo& g, int n_blocks, int B, bool extras) {
-    static const char* env = getenv("LSNF_SMALL3_ST");
-    return lsnf_with_cfg<Small3Cfg>(g, [&](auto c) {
-        using C = decltype(c);
+// Rows per workgroup (16 x ST) for this call, 0 if the kernel does not take it (lsnf_api.hip selects by it): what
+// lsnf_small3_st_wanted asks for; a shape whose constants of n_blocks blocks do not fit in 160 KiB of LDS gives way to the next
+// smaller one.
+int lsnf_small3_forward_st(const LsnfForwardCall& c) {
+    const bool extras = c.z_saved || c.act_saved || c.hdump;
+    return lsnf_with_cfg<Small3Cfg>(c.g, [&](auto cfg) {
+        using C = decltype(cfg);
         // (the plain 32-row form runs two workgroups per CU: 512 of them cover 16 384 rows in one round)
-        const int st = env ? atoi(env) : (B <= 256 * 16 ? 1 : ((B <= 256 * 32 || (LSNF_SMALL3_WAVES2 && !extras && C::WT <= 2 && B <= 512 * 32)) ? 2 : 4));
-        if (st >= 4 && small3_fwd_built<C, 4> && small3_fwd_lds<C, 4>(n_blocks) <= 160 * 1024) return 4;
-        if (st >= 2 && small3_fwd_built<C, 2> && small3_fwd_lds<C, 2>(n_blocks) <= 160 * 1024) return 2;
-        if (small3_fwd_built<C, 1> && small3_fwd_lds<C, 1>(n_blocks) <= 160 * 1024) return 1;
+        const int st = lsnf_small3_st_wanted(c.B, LSNF_SMALL3_WAVES2 && !extras && C::WT <= 2 && c.B <= 512 * 32);
+        if (st >= 4 && small3_fwd_built<C, 4> && small3_fwd_lds<C, 4>(c.n_blocks) <= 160 * 1024) return 4;
+        if (st >= 2 && small3_fwd_built<C, 2> && small3_fwd_lds<C, 2>(c.n_blocks) <= 160 * 1024) return 2;
+        if (small3_fwd_built<C, 1> && small3_fwd_lds<C, 1>(c.n_blocks) <= 160 * 1024) return 1;
         return 0;
     });
 }
 
 // st: lsnf_small3_forward_st of the call
-hipError_t lsnf_launch_small3_forward(const LsnfGeo& g, const float* plan, int first_block, int n_blocks, int B,
-                                      const float* z_in, const float* objective, float* z_out, float* logdet_out,
-                                      float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4, int st,
-                                      hipStream_t stream, float* hdump) {
+hipError_t lsnf_launch_small3_forward(const LsnfForwardCall& c, int st) {
     Small3Args a;
-    a.hdump = hdump ? hdump + (size_t)first_block * lsnf_dump_layout(B, g.nz, g.width).per_block : nullptr;
-    a.width = g.width;
-    a.consts = plan + g.off_fwd_const + (size_t)first_block * g.fwd_const_floats;
-    a.panels3b = plan + g.off_f3b_panels + (size_t)first_block * g.f3_block_floats;
-    a.act_saved = act_saved ? act_saved + (size_t)first_block * lsnf_act_layout(B, g.HT, g.WT).per_block : nullptr;
-    a.z_in = z_in; a.objective = objective; a.z_out = z_out; a.logdet_out = logdet_out; a.ll_out = ll_out;
-    a.z_saved = z_saved; a.stats = stats; a.B = B; a.nz = g.nz; a.half = g.half; a.n_blocks = n_blocks; a.vec4 = vec4;
+    lsnf_fill_forward(a, c);
+    a.panels3b = lsnf_f3b_panels_at(c);
+    a.hdump = lsnf_hdump_at(c); a.width = c.g.width;
     a.stamps = lsnf_stamps_buffer();
-    return lsnf_with_cfg<Small3Cfg>(g, [&](auto c) {
-        using C = decltype(c);
-        return st == 4 ? launch_small3_fwd_st<C, 4>(a, stream) : st == 2 ? launch_small3_fwd_st<C, 2>(a, stream)
-                                                                         : launch_small3_fwd_st<C, 1>(a, stream);
+    return lsnf_with_cfg<Small3Cfg>(c.g, [&](auto cfg) {
+        return lsnf_with_st(st, [&](auto s) { return launch_small3_fwd_st<decltype(cfg), decltype(s)::value>(a, c.stream); });
     });
 }
 
 // the stash of a forward that kept none, from its block outputs (lsnf_api.hip lsnf_restash)
-hipError_t lsnf_launch_small3_restash(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
-                                      float* act_saved, int vec4, hipStream_t stream) {
+hipError_t lsnf_launch_small3_restash(const LsnfRestashCall& c) {
+    const LsnfGeo& g = c.g;
     RestashArgs a;
-    a.consts = plan + g.off_fwd_const; a.panels3b = plan + g.off_f3b_panels;
-    a.z_out = z_out; a.z_saved = z_saved; a.act_saved = act_saved;
-    a.B = B; a.nz = g.nz; a.half = g.half; a.depth = g.depth; a.vec4 = vec4;
-    auto go = [&](auto cfg) -> hipError_t {
+    a.consts = c.plan + g.off_fwd_const; a.panels3b = c.plan + g.off_f3b_panels;
+    a.z_out = c.z_out; a.z_saved = c.z_saved; a.act_saved = c.act_saved;
+    a.B = c.B; a.nz = g.nz; a.half = g.half; a.depth = g.depth; a.vec4 = c.vec4;
+    // (the declared return type defers the lambda's instantiation, which keeps the kernels' order in the code object)
+    return lsnf_with_cfg<Small3Cfg>(g, [&](auto cfg) -> hipError_t {
         using C = decltype(cfg);
         const size_t lds = ((size_t)(C::HT + 2 * C::WT) * S3_BTILE_FLOATS + 2 * C::WT * 32 + C::CONST_FLOATS) * sizeof(float);
-        auto kern = lsnf_small3_restash_kernel<C>;
-        static unsigned long long lds_ok = 0;
-        if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3((unsigned)((B + S3_SAMPLES - 1) / S3_SAMPLES), (unsigned)g.depth), dim3(256), lds, stream, a);
-        return hipGetLastError();
-    };
-    return lsnf_with_cfg<Small3Cfg>(g, go);
+        return lsnf_launch_kernel<lsnf_small3_restash_kernel<C>>(dim3(lsnf_grid(c.B, S3_SAMPLES), (unsigned)g.depth), 256, lds, c.stream, a);
+    });
 }

@@ -22,6 +22,7 @@
 // independent, the split and the coupling arithmetic are compiled without fp contraction).
 #include <stdlib.h>
 #include "lsnf_small3.h"
+#include "lsnf_launch.h"
 
 namespace {
 
@@ -273,41 +274,30 @@ hipError_t launch_small3_rbwd_st(const Small3RbwdArgs& a, hipStream_t stream) {
         return hipErrorInvalidValue;                 // (a selection bug)
     } else {
         const size_t lds = (size_t)Small3RbwdLds<C, ST>::L_END * sizeof(float);
-        auto kern = lsnf_small3_rbwd_kernel<C, ST>;
-        static unsigned long long lds_ok = 0;
-        if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
-        const unsigned grid = (unsigned)((a.B + ST * S3_SAMPLES - 1) / (ST * S3_SAMPLES));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, a);
-        return hipGetLastError();
+        return lsnf_launch_kernel<lsnf_small3_rbwd_kernel<C, ST>>(lsnf_grid(a.B, ST * S3_SAMPLES), 256, lds, stream, a);
     }
 }
 }  // namespace
 
-// Rows per workgroup (16 x ST) for this call (host only, no HIP calls; lsnf_api.hip selects by it): by batch size as the backward
-// from the stash (lsnf_small3_backward_st), LSNF_SMALL3_ST forces a shape; a shape that is not instantiated gives way to the next
-// smaller one.  Never 0: the kernel takes every call.
-int lsnf_small3_reverse_backward_st(const LsnfGeo& g, int B) {
-    static const char* env = getenv("LSNF_SMALL3_ST");
-    return lsnf_with_cfg<Small3RbwdCfg>(g, [&](auto c) {
-        using C = decltype(c);
-        const int st = env ? atoi(env) : (B <= 256 * 16 ? 1 : (B <= 256 * 32 ? 2 : 4));
+// Rows per workgroup (16 x ST) for this call (lsnf_api.hip selects by it): what lsnf_small3_st_wanted asks for; a shape that is
+// not instantiated gives way to the next smaller one.  Never 0: the kernel takes every call.
+int lsnf_small3_reverse_backward_st(const LsnfReverseBackwardCall& c) {
+    return lsnf_with_cfg<Small3RbwdCfg>(c.g, [&](auto cfg) {
+        using C = decltype(cfg);
+        const int st = lsnf_small3_st_wanted(c.B, false);
         return (st >= 4 && small3_rbwd_built<C, 4>) ? 4 : (st >= 2 && small3_rbwd_built<C, 2>) ? 2 : 1;
     });
 }
 
 // st: lsnf_small3_reverse_backward_st of the call
-hipError_t lsnf_launch_small3_reverse_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
-                                                 const float* act_saved, const float* g_x, const float* g_obj, float* g_z_in,
-                                                 int vec4, int st, hipStream_t stream) {
-    if (!act_saved || !g_z_in || B < 1) return hipErrorInvalidValue;     // (a selection bug)
+hipError_t lsnf_launch_small3_reverse_backward_z(const LsnfReverseBackwardCall& c, int st) {
+    if (!c.act_saved || !c.g_z_in || c.B < 1) return hipErrorInvalidValue;     // (a selection bug)
     Small3RbwdArgs a;
-    a.panels = plan + g.off_b3b_panels;
-    a.tpanels = plan + g.off_t3b_panels;
-    a.z_out = z_out; a.z_saved = z_saved; a.act_saved = act_saved; a.g_x = g_x; a.g_obj = g_obj; a.g_z_in = g_z_in;
-    a.B = B; a.nz = g.nz; a.half = g.half; a.depth = g.depth; a.vec4 = vec4;
-    return lsnf_with_cfg<Small3RbwdCfg>(g, [&](auto c) {
-        using C = decltype(c);
-        return st == 4 ? launch_small3_rbwd_st<C, 4>(a, stream) : st == 2 ? launch_small3_rbwd_st<C, 2>(a, stream)
-                                                                         : launch_small3_rbwd_st<C, 1>(a, stream);
+    a.panels = c.plan + c.g.off_b3b_panels;
+    a.tpanels = c.plan + c.g.off_t3b_panels;
+    a.z_out = c.z_out; a.z_saved = c.z_saved; a.act_saved = c.act_saved; a.g_x = c.g_x; a.g_obj = c.g_objective; a.g_z_in = c.g_z_in;
+    a.B = c.B; a.nz = c.g.nz; a.half = c.g.half; a.depth = c.g.depth; a.vec4 = c.vec4;
+    return lsnf_with_cfg<Small3RbwdCfg>(c.g, [&](auto cfg) {
+        return lsnf_with_st(st, [&](auto s) { return launch_small3_rbwd_st<decltype(cfg), decltype(s)::value>(a, c.stream); });
     });
 }

@@ -8,6 +8,7 @@
 //              its epilogue publishes the new z1 (the next block's R2 operand) into the OTHER z1 buffer: four barriers per block
 #include <stdlib.h>
 #include "lsnf_small3.h"
+#include "lsnf_launch.h"
 
 namespace {
 
@@ -281,53 +282,33 @@ hipError_t launch_small3_rev_st(const Args& a, hipStream_t stream) {
     if constexpr (!small3_rev_built<C, ST>) {
         return hipErrorInvalidValue;                 // (a selection bug)
     } else {
-        const size_t lds = small3_rev_lds<C, ST>(a.depth);
-        auto kern = lsnf_small3_rev_kernel<C, ST, SAMPLE>;
-        static unsigned long long lds_ok = 0;
-        if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
-        const unsigned grid = (unsigned)((a.B + ST * S3_SAMPLES - 1) / (ST * S3_SAMPLES));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, a);
-        return hipGetLastError();
+        return lsnf_launch_kernel<lsnf_small3_rev_kernel<C, ST, SAMPLE>>(lsnf_grid(a.B, ST * S3_SAMPLES), 256, small3_rev_lds<C, ST>(a.depth), stream, a);
     }
 }
 }  // namespace
 
-// Rows per workgroup (16 x ST) for this call, 0 if the kernel does not take it (host only, no HIP calls; lsnf_api.hip selects by
-// it): by batch size as the forward (lsnf_small3_forward_st), LSNF_SMALL3_ST forces a shape; a shape whose constants of the whole
-// stack do not fit in 160 KiB of LDS gives way to the next smaller one.
-int lsnf_small3_reverse_st(const LsnfGeo& g, int B) {
-    static const char* env = getenv("LSNF_SMALL3_ST");
-    return lsnf_with_cfg<Small3RevCfg>(g, [&](auto c) {
-        using C = decltype(c);
-        const int st = env ? atoi(env) : (B <= 256 * 16 ? 1 : (B <= 256 * 32 ? 2 : 4));
-        if (st >= 4 && small3_rev_built<C, 4> && small3_rev_lds<C, 4>(g.depth) <= 160 * 1024) return 4;
-        if (st >= 2 && small3_rev_built<C, 2> && small3_rev_lds<C, 2>(g.depth) <= 160 * 1024) return 2;
-        if (small3_rev_built<C, 1> && small3_rev_lds<C, 1>(g.depth) <= 160 * 1024) return 1;
+// Rows per workgroup (16 x ST) for this call, 0 if the kernel does not take it (lsnf_api.hip selects by it): what
+// lsnf_small3_st_wanted asks for; a shape whose constants of the whole stack do not fit in 160 KiB of LDS gives way to the next
+// smaller one.
+int lsnf_small3_reverse_st(const LsnfReverseCall& c) {
+    return lsnf_with_cfg<Small3RevCfg>(c.g, [&](auto cfg) {
+        using C = decltype(cfg);
+        const int st = lsnf_small3_st_wanted(c.B, false), depth = c.g.depth;
+        if (st >= 4 && small3_rev_built<C, 4> && small3_rev_lds<C, 4>(depth) <= 160 * 1024) return 4;
+        if (st >= 2 && small3_rev_built<C, 2> && small3_rev_lds<C, 2>(depth) <= 160 * 1024) return 2;
+        if (small3_rev_built<C, 1> && small3_rev_lds<C, 1>(depth) <= 160 * 1024) return 1;
         return 0;
     });
 }
 
 // st: lsnf_small3_reverse_st of the call
-hipError_t lsnf_launch_small3_reverse(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                                      float* z_out, float* objective_out, int vec4, int st, hipStream_t stream,
-                                      const LsnfSampleArgs* smp) {
+hipError_t lsnf_launch_small3_reverse(const LsnfReverseCall& c, int st) {
     Small3RevSampleArgs a;
-    a.fwd_consts = plan + g.off_fwd_const; a.inv_consts = plan + g.off_inv_const;
-    a.panels3b = plan + g.off_f3b_panels; a.ipanels3b = plan + g.off_i3b_panels;
-    a.z_in = z_in; a.objective = objective; a.z_out = z_out; a.objective_out = objective_out;
-    a.B = B; a.nz = g.nz; a.half = g.half; a.depth = g.depth; a.vec4 = vec4;
-    if (smp) {
-        a.s = *smp;
-        return lsnf_with_cfg<Small3RevCfg>(g, [&](auto c) {
-            using C = decltype(c);
-            return st == 4 ? launch_small3_rev_st<C, 4, true>(a, stream) : st == 2 ? launch_small3_rev_st<C, 2, true>(a, stream)
-                                                                                   : launch_small3_rev_st<C, 1, true>(a, stream);
+    lsnf_fill_reverse(a, c);
+    a.panels3b = c.plan + c.g.off_f3b_panels; a.ipanels3b = c.plan + c.g.off_i3b_panels;
+    return lsnf_with_sample<Small3RevArgs>(a, c.smp, [&](auto sample, const auto& args) {
+        return lsnf_with_cfg<Small3RevCfg>(c.g, [&](auto cfg) {
+            return lsnf_with_st(st, [&](auto s) { return launch_small3_rev_st<decltype(cfg), decltype(s)::value, decltype(sample)::value>(args, c.stream); });
         });
-    }
-    const Small3RevArgs& r = a;
-    return lsnf_with_cfg<Small3RevCfg>(g, [&](auto c) {
-        using C = decltype(c);
-        return st == 4 ? launch_small3_rev_st<C, 4, false>(r, stream) : st == 2 ? launch_small3_rev_st<C, 2, false>(r, stream)
-                                                                                : launch_small3_rev_st<C, 1, false>(r, stream);
     });
 }

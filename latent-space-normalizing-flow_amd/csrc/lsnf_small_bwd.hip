@@ -14,6 +14,7 @@
 // per-sample tensors of LsnfDumpLayout (h1, h2, g_a1, g_a2, g_t, g_p, g_v) -- each tile by the one wave that
 // owns output tile 0 of the stage consuming it -- and accumulates sum_b dL/dlogdet_b.
 #include "lsnf_small.h"
+#include "lsnf_launch.h"
 
 namespace {
 
@@ -345,13 +346,7 @@ size_t small_bwd_lds(int depth) { return ((size_t)C::T_END * LSNF_TILE_FLOATS + 
 
 template <class C, bool SAVED, bool DUMP>
 hipError_t launch_small_bwd_v(const SmallBwdArgs& a, hipStream_t stream) {
-    const size_t lds = small_bwd_lds<C>(a.depth);
-    auto kern = lsnf_small_bwd_kernel<C, SAVED, DUMP>;
-    static unsigned long long lds_ok = 0;
-    if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
-    const unsigned grid = (unsigned)((a.B + LSNF_SMALL_SAMPLES - 1) / LSNF_SMALL_SAMPLES);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(LSNF_WG_THREADS), lds, stream, a);
-    return hipGetLastError();
+    return lsnf_launch_kernel<lsnf_small_bwd_kernel<C, SAVED, DUMP>>(lsnf_grid(a.B, LSNF_SMALL_SAMPLES), LSNF_WG_THREADS, small_bwd_lds<C>(a.depth), stream, a);
 }
 template <class C>
 hipError_t launch_small_bwd(const SmallBwdArgs& a, hipStream_t stream) {
@@ -362,24 +357,15 @@ hipError_t launch_small_bwd(const SmallBwdArgs& a, hipStream_t stream) {
 
 // Does the kernel take this geometry (host only, no HIP calls; lsnf_api.hip selects by it)?  The constants of the whole stack
 // fit in 160 KiB of LDS.
-bool lsnf_small_backward_covers(const LsnfGeo& g) {
-    return lsnf_with_cfg<SmallBwdCfg>(g, [&](auto c) { return small_bwd_lds<decltype(c)>(g.depth) <= 160 * 1024; });
+bool lsnf_small_backward_covers(const LsnfBackwardCall& c) {
+    return lsnf_with_cfg<SmallBwdCfg>(c.g, [&](auto cfg) { return small_bwd_lds<decltype(cfg)>(c.g.depth) <= 160 * 1024; });
 }
 
-hipError_t lsnf_launch_small_backward_z(const LsnfGeo& g, const float* plan, int B, const float* z_out, const float* z_saved,
-                                        const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale, float* g_z_in,
-                                        int vec4, hipStream_t stream, const LsnfLangevinArgs* lv, const float* act_saved,
-                                        float* dump, double* gl_total) {
+hipError_t lsnf_launch_small_backward_z(const LsnfBackwardCall& c) {
+    if (!lsnf_small_backward_covers(c)) return hipErrorInvalidValue;      // (a selection bug)
     SmallBwdArgs a;
-    a.act_saved = dump ? nullptr : act_saved;
-    a.dump = dump; a.gl_total = gl_total; a.width = g.width;
-    a.fwd_consts = plan + g.off_fwd_const; a.fwd_panels = plan + g.off_fwd_panels; a.bwd_panels = plan + g.off_bwd_panels;
-    a.z_out = z_out; a.z_saved = z_saved; a.g_z1 = g_z1; a.g_logdet = g_logdet; a.g_z_in = g_z_in;
-    a.rng = LsnfRngArgs{0ull, 0ull, nullptr, 0ll, 0};
-    a.z_cur = nullptr; a.grad_g = nullptr; a.noise = nullptr; a.z_new = nullptr; a.gf_norm = nullptr; a.gg_norm = nullptr; a.step = 0.f;
-    if (lv) { a.z_cur = lv->z_cur; a.grad_g = lv->grad_g; a.noise = lv->noise; a.z_new = lv->z_new; a.gf_norm = lv->gf_norm;
-              a.gg_norm = lv->gg_norm; a.step = lv->step; a.rng = lv->rng; }
-    a.ll_scale = ll_scale; a.ll_mode = ll_mode; a.B = B; a.nz = g.nz; a.half = g.half; a.depth = g.depth; a.vec4 = vec4;
-    if (!lsnf_small_backward_covers(g)) return hipErrorInvalidValue;      // (a selection bug)
-    return lsnf_with_cfg<SmallBwdCfg>(g, [&](auto c) { return launch_small_bwd<decltype(c)>(a, stream); });
+    lsnf_fill_backward(a, c);
+    a.act_saved = c.dump ? nullptr : c.act_saved;       // (the DUMP variant recomputes: it has no SAVED form)
+    a.fwd_consts = c.plan + c.g.off_fwd_const; a.fwd_panels = c.plan + c.g.off_fwd_panels; a.bwd_panels = c.plan + c.g.off_bwd_panels;
+    return lsnf_with_cfg<SmallBwdCfg>(c.g, [&](auto cfg) { return launch_small_bwd<decltype(cfg)>(a, c.stream); });
 }

@@ -3,6 +3,7 @@
 // replaces reference model.py:473-483 + train.py:317-319; see lsnf_small.h for the work decomposition:
 // one workgroup = 32 samples, its 4 waves split every GEMM stage, activations exchanged through LDS.
 #include "lsnf_small.h"
+#include "lsnf_launch.h"
 
 namespace {
 
@@ -209,33 +210,21 @@ size_t small_fwd_lds(int n_blocks) { return ((size_t)C::T_END * LSNF_TILE_FLOATS
 
 template <class C>
 hipError_t launch_small_fwd(const SmallFwdArgs& a, hipStream_t stream) {
-    const size_t lds = small_fwd_lds<C>(a.n_blocks);
-    auto kern = lsnf_small_fwd_kernel<C>;
-    static unsigned long long lds_ok = 0;
-    if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
-    const unsigned grid = (unsigned)((a.B + LSNF_SMALL_SAMPLES - 1) / LSNF_SMALL_SAMPLES);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(LSNF_WG_THREADS), lds, stream, a);
-    return hipGetLastError();
+    return lsnf_launch_kernel<lsnf_small_fwd_kernel<C>>(lsnf_grid(a.B, LSNF_SMALL_SAMPLES), LSNF_WG_THREADS, small_fwd_lds<C>(a.n_blocks), stream, a);
 }
 }  // namespace
 
 // Does the kernel take this call (host only, no HIP calls; lsnf_api.hip selects by it)?  The constants of n_blocks blocks fit
 // in 160 KiB of LDS.
-bool lsnf_small_forward_covers(const LsnfGeo& g, int n_blocks) {
-    return lsnf_with_cfg<SmallFwdCfg>(g, [&](auto c) { return small_fwd_lds<decltype(c)>(n_blocks) <= 160 * 1024; });
+bool lsnf_small_forward_covers(const LsnfForwardCall& c) {
+    return lsnf_with_cfg<SmallFwdCfg>(c.g, [&](auto cfg) { return small_fwd_lds<decltype(cfg)>(c.n_blocks) <= 160 * 1024; });
 }
 
-hipError_t lsnf_launch_small_forward(const LsnfGeo& g, const float* plan, int first_block, int n_blocks, int B,
-                                     const float* z_in, const float* objective, float* z_out, float* logdet_out,
-                                     float* ll_out, float* z_saved, float* act_saved, double* stats, int vec4,
-                                     hipStream_t stream) {
+hipError_t lsnf_launch_small_forward(const LsnfForwardCall& c) {
+    if (!lsnf_small_forward_covers(c)) return hipErrorInvalidValue;      // (a selection bug)
     SmallFwdArgs a;
-    a.consts = plan + g.off_fwd_const + (size_t)first_block * g.fwd_const_floats;
-    a.panels = plan + g.off_fwd_panels + (size_t)first_block * g.fwd_block_floats;
-    a.z_in = z_in; a.objective = objective; a.z_out = z_out; a.logdet_out = logdet_out; a.ll_out = ll_out;
-    a.act_saved = act_saved ? act_saved + (size_t)first_block * lsnf_act_layout(B, g.HT, g.WT).per_block : nullptr;
+    lsnf_fill_forward(a, c);
+    a.panels = lsnf_fwd_panels_at(c);
     a.stamps = lsnf_stamps_buffer();
-    a.z_saved = z_saved; a.stats = stats; a.B = B; a.nz = g.nz; a.half = g.half; a.n_blocks = n_blocks; a.vec4 = vec4;
-    if (!lsnf_small_forward_covers(g, n_blocks)) return hipErrorInvalidValue;      // (a selection bug)
-    return lsnf_with_cfg<SmallFwdCfg>(g, [&](auto c) { return launch_small_fwd<decltype(c)>(a, stream); });
+    return lsnf_with_cfg<SmallFwdCfg>(c.g, [&](auto cfg) { return launch_small_fwd<decltype(cfg)>(a, c.stream); });
 }

@@ -6,6 +6,7 @@
 //   CI       : z2 = z2 / sigmoid(p) - t ; objective -= sum log sigmoid(p)     (model.py:436-438)
 //   I1       : z = ([z1,z2] @ W^-1) * exp(-3 logs) - b ; objective -= log|det W| + sum 3 logs  (:193-196, 270, 246)
 #include "lsnf_small.h"
+#include "lsnf_launch.h"
 
 namespace {
 
@@ -162,33 +163,22 @@ size_t small_rev_lds(int depth) { return ((size_t)C::T_END * LSNF_TILE_FLOATS + 
 
 template <class C, bool SAMPLE, class Args>
 hipError_t launch_small_rev(const Args& a, hipStream_t stream) {
-    const size_t lds = small_rev_lds<C>(a.depth);
-    auto kern = lsnf_small_rev_kernel<C, SAMPLE>;
-    static unsigned long long lds_ok = 0;
-    if (hipError_t e = lsnf_allow_big_lds((const void*)kern, &lds_ok); e != hipSuccess) return e;
-    const unsigned grid = (unsigned)((a.B + LSNF_SMALL_SAMPLES - 1) / LSNF_SMALL_SAMPLES);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(LSNF_WG_THREADS), lds, stream, a);
-    return hipGetLastError();
+    return lsnf_launch_kernel<lsnf_small_rev_kernel<C, SAMPLE>>(lsnf_grid(a.B, LSNF_SMALL_SAMPLES), LSNF_WG_THREADS, small_rev_lds<C>(a.depth), stream, a);
 }
 }  // namespace
 
 // Does the kernel take this geometry (host only, no HIP calls; lsnf_api.hip selects by it)?  The constants of the whole stack
 // fit in 160 KiB of LDS.
-bool lsnf_small_reverse_covers(const LsnfGeo& g) {
-    return lsnf_with_cfg<SmallRevCfg>(g, [&](auto c) { return small_rev_lds<decltype(c)>(g.depth) <= 160 * 1024; });
+bool lsnf_small_reverse_covers(const LsnfReverseCall& c) {
+    return lsnf_with_cfg<SmallRevCfg>(c.g, [&](auto cfg) { return small_rev_lds<decltype(cfg)>(c.g.depth) <= 160 * 1024; });
 }
 
-hipError_t lsnf_launch_small_reverse(const LsnfGeo& g, const float* plan, int B, const float* z_in, const float* objective,
-                                     float* z_out, float* objective_out, int vec4, hipStream_t stream, const LsnfSampleArgs* smp) {
+hipError_t lsnf_launch_small_reverse(const LsnfReverseCall& c) {
+    if (!lsnf_small_reverse_covers(c)) return hipErrorInvalidValue;      // (a selection bug)
     SmallRevSampleArgs a;
-    a.fwd_consts = plan + g.off_fwd_const; a.fwd_panels = plan + g.off_fwd_panels;
-    a.inv_consts = plan + g.off_inv_const; a.inv_panels = plan + g.off_inv_panels;
-    a.z_in = z_in; a.objective = objective; a.z_out = z_out; a.objective_out = objective_out;
-    a.B = B; a.nz = g.nz; a.half = g.half; a.depth = g.depth; a.vec4 = vec4;
-    if (!lsnf_small_reverse_covers(g)) return hipErrorInvalidValue;      // (a selection bug)
-    if (smp) {
-        a.s = *smp;
-        return lsnf_with_cfg<SmallRevCfg>(g, [&](auto c) { return launch_small_rev<decltype(c), true>(a, stream); });
-    }
-    return lsnf_with_cfg<SmallRevCfg>(g, [&](auto c) { return launch_small_rev<decltype(c), false>(static_cast<const SmallRevArgs&>(a), stream); });
+    lsnf_fill_reverse(a, c);
+    a.fwd_panels = c.plan + c.g.off_fwd_panels; a.inv_panels = c.plan + c.g.off_inv_panels;
+    return lsnf_with_sample<SmallRevArgs>(a, c.smp, [&](auto sample, const auto& args) {
+        return lsnf_with_cfg<SmallRevCfg>(c.g, [&](auto cfg) { return launch_small_rev<decltype(cfg), decltype(sample)::value>(args, c.stream); });
+    });
 }

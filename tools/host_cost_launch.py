@@ -1,0 +1,105 @@
+#!/usr/bin/env python3
+"""GPU: host cost of a call through the library's launch layer, two builds of liblsnf_flow.so against each other in one job.
+
+    python tools/host_cost_launch.py parent.so new.so [rounds=6]
+
+The builds alternate in fresh child processes (LSNF_LIB_PATH), the order within a pair swapped from round to round (use an
+even number of rounds: a build against a copy of itself shows the second child of a pair ~0.1-0.5 us slower).  A child times the ENQUEUE of five calls -- no synchronisation
+inside a timed region, as tools/host_rate.py -- in REGIONS regions of CALLS calls each (queue drained between regions):
+  forward(B=64), forward(B=64, stash), langevin_step(B=100), sample(B=100), BoundForward(B=8192).
+Per build and call: median and p10 / p90 over every region of every round, and the medians of the rounds.  The first build is
+the reference: the second one's median may exceed its median by at most the reference's own p10-p90 width; exit status 1 if
+a call does."""
+import os
+import statistics
+import subprocess
+import sys
+
+REGIONS, CALLS = 15, 300
+NAMES = ("forward B=64", "forward B=64 +stash", "langevin_step B=100", "sample B=100", "BoundForward B=8192")
+
+CHILD = r'''
+import os, sys, time, torch
+sys.path.insert(0, os.getcwd())
+import bench, lsnf_amd
+F = lsnf_amd.flow
+REGIONS, CALLS = int(sys.argv[1]), int(sys.argv[2])
+dev = torch.device("cuda:0")
+plan = lsnf_amd.prepare([t.to(dev) for t in bench.synth_weights(1)], bench.NZ, bench.WIDTH, bench.DEPTH)
+gen = torch.Generator().manual_seed(1234)
+f32 = dict(dtype=torch.float32, device=dev)
+def outs(B): return (torch.empty(B, bench.NZ, **f32), torch.empty(B, **f32), torch.empty(B, **f32))
+z64, z100, z8k = (torch.randn(B, bench.NZ, generator=gen).to(dev) for B in (64, 100, 8192))
+o64, o8k = outs(64), outs(8192)
+act64 = F.new_act_saved(plan, 64, dev)
+sav64 = torch.empty((bench.DEPTH - 1, 64, bench.NZ), **f32)
+rng = F.PhiloxNoise(7)
+smp_out = (torch.empty(100, bench.NZ, **f32), torch.empty(100, **f32), None, None)
+bound = F.BoundForward(plan, z8k, o8k)
+calls = (
+    lambda: F.forward(plan, z64, out=o64),
+    lambda: F.forward(plan, z64, out=o64, act_saved=act64, z_saved_out=sav64),
+    lambda: F.langevin_step(plan, z100, None, rng, 0.1, inplace=True, reuse_buffers=True),
+    lambda: F.sample(plan, 100, rng, out=smp_out),
+    lambda: bound(None),
+)
+for i, fn in enumerate(calls):
+    for _ in range(CALLS): fn()
+    torch.cuda.synchronize()
+    us = []
+    for _ in range(REGIONS):
+        t0 = time.perf_counter()
+        for _ in range(CALLS): fn()
+        t1 = time.perf_counter()
+        torch.cuda.synchronize()
+        us.append(1e6 * (t1 - t0) / CALLS)
+    print("REGION", i, " ".join("%.3f" % u for u in us), flush=True)
+'''
+
+
+def pct(xs, q):
+    xs = sorted(xs)
+    k = q * (len(xs) - 1)
+    lo = int(k)
+    return xs[lo] + (xs[min(lo + 1, len(xs) - 1)] - xs[lo]) * (k - lo)
+
+
+def main():
+    libs = [os.path.abspath(p) for p in sys.argv[1:3]]
+    rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 6
+    regions = {lib: [[] for _ in NAMES] for lib in libs}          # every region of every round
+    round_medians = {lib: [[] for _ in NAMES] for lib in libs}
+    for r in range(rounds):
+        for lib in (libs if r % 2 == 0 else libs[::-1]):      # (whichever child runs second in a pair measures ~0.3 us more)
+            out = subprocess.run([sys.executable, "-c", CHILD, str(REGIONS), str(CALLS)], env=dict(os.environ, LSNF_LIB_PATH=lib),
+                                 capture_output=True, text=True, timeout=280)
+            rows = [l.split()[1:] for l in out.stdout.splitlines() if l.startswith("REGION")]
+            if out.returncode or len(rows) != len(NAMES):
+                print(f"round {r} {lib}: child failed ({out.returncode}): {out.stderr[-600:]}", flush=True)
+                return 2
+            for row in rows:
+                us = [float(x) for x in row[1:]]
+                regions[lib][int(row[0])] += us
+                round_medians[lib][int(row[0])].append(statistics.median(us))
+            print(f"round {r} {os.path.basename(os.path.dirname(lib)) or lib}: done", flush=True)
+    print(f"\nenqueue-only host time, us per call ({rounds} rounds per build, alternating; {REGIONS} regions x {CALLS} calls per round)")
+    print(f"reference: {libs[0]}\nnew:       {libs[1]}")
+    print(f"{'call':<22} {'build':<10} {'median':>8} {'p10':>8} {'p90':>8}   medians of the rounds")
+    bad = 0
+    for i, name in enumerate(NAMES):
+        stat = {}
+        for tag, lib in zip(("reference", "new"), libs):
+            xs = regions[lib][i]
+            stat[tag] = (statistics.median(xs), pct(xs, 0.1), pct(xs, 0.9))
+            print(f"{name:<22} {tag:<10} {stat[tag][0]:8.2f} {stat[tag][1]:8.2f} {stat[tag][2]:8.2f}   "
+                  + " ".join("%.2f" % m for m in round_medians[lib][i]))
+        width = stat["reference"][2] - stat["reference"][1]
+        delta = stat["new"][0] - stat["reference"][0]
+        ok = delta <= width
+        bad += not ok
+        print(f"{'':<22} new - reference median {delta:+.2f} us; allowed +{width:.2f} (the reference's p10-p90 width): {'ok' if ok else 'SLOWER'}")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

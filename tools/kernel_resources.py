@@ -1,15 +1,18 @@
 """Resource notes of the kernels in built objects, from the code objects' own metadata (no GPU needed).
 
-    python tools/kernel_resources.py BUILD_DIR [--match rev] [--against OTHER_BUILD_DIR]
+    python tools/kernel_resources.py BUILD_DIR [--match rev] [--against OTHER_BUILD_DIR] [--sha256]
 
 For every *.o in BUILD_DIR: the gfx950 code object is taken out of the .hip_fatbin section and its AMDGPU metadata note
 is read (llvm-readelf --notes): VGPRs, AGPRs, SGPRs, static LDS and Scratch_Size (.private_segment_fixed_size) per kernel.
 Kernel names are shortened to `kernel<HT, WT, ...>` (the template arguments in order).  --against compares with a second build (e.g. the
 parent commit's): a kernel is matched by its name with any trailing `false` template argument removed, so that an
 instantiation that gained a compile-time flag is compared with what it was; kernels only in BUILD_DIR are listed as new.
-Exit status 1 if a matched kernel differs in VGPRs, AGPRs, LDS or scratch."""
+Exit status 1 if a matched kernel differs in VGPRs, AGPRs, LDS or scratch.
+--sha256 adds, below the table, the SHA-256 of every object's gfx950 code object: with --against, exit status 1 as well if any
+object's device code differs by a single byte (or exists on one side only) -- the check of a host-only change."""
 import argparse
 import glob
+import hashlib
 import os
 import re
 import subprocess
@@ -38,19 +41,57 @@ def _short(mangled):
     return f"{name}<{', '.join(vals)}>" if vals else name
 
 
+def _code_object(obj, tmp):
+    """Path of the gfx950 code object of one object file, unbundled into tmp; None for an object without device code."""
+    fat, co = os.path.join(tmp, "fatbin"), os.path.join(tmp, "co")
+    try:
+        _run(os.path.join(LLVM, "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", obj)
+    except subprocess.CalledProcessError:
+        return None
+    if not os.path.exists(fat) or os.path.getsize(fat) == 0:
+        return None
+    _run(os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+         f"--input={fat}", f"--output={co}")
+    return co
+
+
+def device_hashes(build_dir, match):
+    """{object file name: (sha256 of its gfx950 code object, its size)}."""
+    res = {}
+    for obj in sorted(glob.glob(os.path.join(build_dir, "*.o"))):
+        if match and match not in os.path.basename(obj):
+            continue
+        with tempfile.TemporaryDirectory() as tmp:
+            co = _code_object(obj, tmp)
+            data = open(co, "rb").read() if co else b""
+            res[os.path.basename(obj)] = (hashlib.sha256(data).hexdigest() if co else "(host code only)", len(data))
+    return res
+
+
+def print_hashes(mine, theirs):
+    """The hash table; the number of objects whose device code differs from `theirs` (None: nothing to compare with)."""
+    bad = 0
+    print(f"\n{'object':<24} {'bytes':>9}  sha256 of the gfx950 code object")
+    for n in sorted(set(mine) | set(theirs or {})):
+        h, size = mine.get(n, ("-" * 64, 0))
+        verdict = ""
+        if theirs is not None:
+            same = n in mine and n in theirs and theirs[n][0] == h
+            bad += not same
+            verdict = "   identical" if same else "   DIFFERENT"
+        print(f"{n:<24} {size:>9}  {h}{verdict}")
+    if theirs is not None:
+        print(f"{len(mine)} objects, {bad} with different device code")
+    return bad
+
+
 def kernels_of(obj):
     """{short name: {vgpr, agpr, sgpr, lds, scratch}} of one object file."""
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
-        fat, co = os.path.join(tmp, "fatbin"), os.path.join(tmp, "co")
-        try:
-            _run(os.path.join(LLVM, "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", obj)
-        except subprocess.CalledProcessError:                # (an object without device code)
+        co = _code_object(obj, tmp)
+        if co is None:
             return out
-        if not os.path.exists(fat) or os.path.getsize(fat) == 0:
-            return out
-        _run(os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-             f"--input={fat}", f"--output={co}")
         notes = _run(os.path.join(LLVM, "llvm-readelf"), "--notes", co)
     cur = None
     for line in notes.splitlines():
@@ -87,12 +128,15 @@ def main():
     ap.add_argument("build_dir")
     ap.add_argument("--match", default="", help="only objects whose file name contains this")
     ap.add_argument("--against", default=None, help="a second build directory to compare with")
+    ap.add_argument("--sha256", action="store_true", help="also hash every object's gfx950 code object (byte identity)")
     a = ap.parse_args()
     mine = collect(a.build_dir, a.match)
     if a.against is None:
         print(f"{'kernel':<70} {'VGPR':>5} {'AGPR':>5} {'SGPR':>5} {'LDS':>6} {'scratch':>7}")
         for n, r in sorted(mine.items()):
             print(f"{n:<70} {r['vgpr']:>5} {r['agpr']:>5} {r['sgpr']:>5} {r['lds']:>6} {r['scratch']:>7}")
+        if a.sha256:
+            print_hashes(device_hashes(a.build_dir, a.match), None)
         return 0
     theirs = collect(a.against, a.match)
     bad = 0
@@ -109,6 +153,8 @@ def main():
     gone = [n for n in theirs if n not in mine and not any(_base(m) == n for m in mine)]
     for n in sorted(gone):
         print(f"{n:<70} only in {a.against}")
+    if a.sha256:
+        bad += print_hashes(device_hashes(a.build_dir, a.match), device_hashes(a.against, a.match))
     return 1 if bad else 0
 
 
