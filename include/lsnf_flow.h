@@ -279,6 +279,35 @@ int lsnf_sample(const float* plan, int nz, int width, int depth, int coupling, i
                 const LsnfRng* rng, float temperature,
                 float* z_out, float* objective_out, float* eps_out, float* ll_out, void* stream);
 
+/* ---- stash-keeping reverse / sampling: the sampling direction leaves what its own backward needs ----
+ * lsnf_reverse_keep / lsnf_sample_keep are lsnf_reverse / lsnf_sample -- same kernel, same bits in z_out, objective_out (eps_out,
+ * ll_out) -- that ALSO write, each only if its pointer is not NULL, what lsnf_forward(z_in = x, whole stack) would keep for a
+ * backward pass at x = z_out: the coupling MLP's input is the first half of a block's OUTPUT (model.py:422), so the reverse holds the
+ * forward's block outputs, sigmoid and ReLU masks in registers when it produces x.
+ *   z_saved          ((depth-1), B, nz): outputs of forward blocks 0 .. depth-2 at x (the last block's output is the call's own
+ *                    input, z_in / eps_out, and is not written again); must not alias another tensor of the call
+ *   act_saved        lsnf_act_saved_floats() floats, 16-byte aligned: the stash, in lsnf_forward's layout
+ *   params_workspace the workspace of the lsnf_backward_params call that will follow (16-byte aligned): h1 / h2 of every block, as
+ *                    lsnf_forward(params_workspace) leaves them; needs act_saved, z_saved (depth > 1) and
+ *                    lsnf_params_fast_path() == 1
+ * lsnf_reverse_backward_z(z_out = z_in / eps_out, z_saved, act_saved, ...), lsnf_backward_z and lsnf_backward_params(z_in = x,
+ * z_out = z_in / eps_out, z_saved, act_saved, workspace) take them as they take lsnf_forward's: the second pass over x is not needed.
+ * lsnf_sample_keep with act_saved or z_saved requires eps_out.  lsnf_reverse_keep with act_saved or z_saved refuses the in-place call
+ * z_out == z_in: it would overwrite the last block's output, which every backward must be given.  Other rules (NULL, alignment,
+ * aliasing) as lsnf_reverse / lsnf_sample.
+ * Covered: the latency bf16x3 reverse only -- a bf16x3-family math mode (lsnf_params_fast_path() == 1), B <= the small-batch
+ * threshold in force (lsnf_set_small_batch_max(-1)) and a geometry / depth that kernel takes; lsnf_reverse_keep_covers() answers
+ * 1 / 0 for a call (0 on a bad geometry), and outside it both entry points return LSNF_E_ARG (not covered: the throughput reverse
+ * kernels, LSNF_MATH_FP32).  B = 0 succeeds without a launch.  Added without an ABI bump (new symbols; nothing existing changed). */
+int lsnf_reverse_keep_covers(int nz, int width, int depth, int coupling, int B);
+int lsnf_reverse_keep(const float* plan, int nz, int width, int depth, int coupling, int B,
+                      const float* z_in, const float* objective, float* z_out, float* objective_out,
+                      float* z_saved, float* act_saved, float* params_workspace, void* stream);
+int lsnf_sample_keep(const float* plan, int nz, int width, int depth, int coupling, int B,
+                     const LsnfRng* rng, float temperature,
+                     float* z_out, float* objective_out, float* eps_out, float* ll_out,
+                     float* z_saved, float* act_saved, float* params_workspace, void* stream);
+
 /* ---- backward w.r.t. the parameters: replaces `loss_f.backward()` (train.py:406-411) --------
  * Gradients of L w.r.t. the 12 live tensors of every block (same order as lsnf_prepare), for the
  * upstream gradients described under lsnf_backward_z (train.py:410: L = -mean ll -> ll_mode=1,

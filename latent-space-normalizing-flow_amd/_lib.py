@@ -48,6 +48,11 @@ _SIGNATURES = {
                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     "lsnf_sample": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(LsnfRng), c_float,
                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lsnf_reverse_keep_covers": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "lsnf_reverse_keep": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lsnf_sample_keep": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(LsnfRng), c_float,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lsnf_backward_params_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
     "lsnf_backward_params": (c_int, [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
                                      c_int, c_int, c_int, c_int, c_int,

@@ -200,6 +200,89 @@ hipError_t launch_reverse(Pick p, const LsnfReverseCall& c) {
     }
 }
 
+// The stash-keeping forms (lsnf_reverse_keep, lsnf_sample_keep) exist for the latency bf16x3 kernel alone.  ONE rule, for the query
+// and both entry points: a bf16x3-family mode, B within the common threshold (the family that writes a stash is the family the
+// forward would have picked: the parameter-gradient dump is then row-major) and a workgroup shape of that kernel for the call.  Under it
+// select_reverse picks the same kernel for the plain call, so the outputs of the two are the same bits.
+bool reverse_keep_covers(const LsnfReverseCall& c) {
+    return l16_math() && c.B <= small_batch_max() && lsnf_small3_reverse_st(c) != 0;
+}
+// Argument rules of lsnf_reverse / lsnf_reverse_keep and of lsnf_sample / lsnf_sample_keep, ONE copy each (`entry` names the caller in
+// the message).  Return: a negative LSNF_E_* code; 0 = checked, go on; 1 = empty batch, nothing to launch (the caller returns LSNF_OK).
+int check_reverse_args(const char* entry, LsnfGeo* g, int nz, int width, int depth, int coupling, int B, const float* plan,
+                       const float* z_in, const float* objective, const float* z_out, const float* objective_out) {
+    if (int rc = geo_or_fail(g, nz, width, depth, coupling)) return rc;
+    if (B < 0 || B > (1 << 28)) return fail(LSNF_E_ARG, "%s: B=%d out of range", entry, B);
+    if (B == 0) return 1;
+    if (!plan || !z_in || !z_out) return fail(LSNF_E_ARG, "%s: NULL argument", entry);
+    if (!aligned16(plan)) return fail(LSNF_E_ARG, "%s: plan must be 16-byte aligned", entry);
+    if (!aligned4(z_in) || !aligned4(z_out) || !aligned4(objective) || !aligned4(objective_out))
+        return fail(LSNF_E_ARG, "%s: tensors must be 4-byte aligned", entry);
+    return 0;
+}
+int check_sample_args(const char* entry, LsnfGeo* g, int nz, int width, int depth, int coupling, int B, const LsnfRng* rng,
+                      float temperature, const float* plan, const float* z_out, const float* objective_out, const float* eps_out,
+                      const float* ll_out) {
+    if (int rc = geo_or_fail(g, nz, width, depth, coupling)) return rc;
+    if (B < 0 || B > (1 << 28)) return fail(LSNF_E_ARG, "%s: B=%d out of range", entry, B);
+    if (!rng) return fail(LSNF_E_ARG, "%s: rng is required", entry);
+    if (rng->row0 < 0) return fail(LSNF_E_ARG, "%s: rng->row0 must be >= 0", entry);
+    if (rng->offset_dev && (reinterpret_cast<uintptr_t>(rng->offset_dev) & 7u))
+        return fail(LSNF_E_ARG, "%s: rng->offset_dev must be 8-byte aligned", entry);
+    if (!std::isfinite(temperature) || temperature < 0.0f)
+        return fail(LSNF_E_ARG, "%s: temperature must be finite and >= 0 (got %g)", entry, (double)temperature);
+    if (B == 0) return 1;
+    if (!plan || !z_out) return fail(LSNF_E_ARG, "%s: NULL argument", entry);
+    if (!aligned16(plan)) return fail(LSNF_E_ARG, "%s: plan must be 16-byte aligned", entry);
+    if (!aligned4(z_out) || !aligned4(objective_out) || !aligned4(eps_out) || !aligned4(ll_out))
+        return fail(LSNF_E_ARG, "%s: tensors must be 4-byte aligned", entry);
+    if (eps_out == z_out) return fail(LSNF_E_ARG, "%s: eps_out must not alias z_out", entry);
+    return 0;
+}
+// the plain selection and launch of a checked reverse / sampling call
+int reverse_select_launch(const char* entry, const LsnfReverseCall& c) {
+    const Pick p = select_reverse(c);
+    const hipError_t e = launch_reverse(p, c);
+    if (p.k == K_NONE || e != hipSuccess) return launch_fail(e, entry, p.k);
+    return LSNF_OK;
+}
+// What the two keep entry points share once the plain call's arguments are checked: the rules of the three optional tensors (as
+// lsnf_forward's), the coverage rule, the workspace tag, the launch.  The descriptor comes filled but for vec4 and the three tensors.
+int reverse_keep_launch(const char* entry, LsnfReverseCall& c, float* z_saved, float* act_saved, float* params_workspace) {
+    const LsnfGeo& g = c.g;
+    const float* eps_out = c.smp ? c.smp->eps_out : nullptr;
+    if (!aligned4(z_saved)) return fail(LSNF_E_ARG, "%s: tensors must be 4-byte aligned", entry);
+    if (act_saved && !aligned16(act_saved)) return fail(LSNF_E_ARG, "%s: act_saved must be 16-byte aligned", entry);
+    if (z_saved && (z_saved == c.z_in || z_saved == c.z_out || z_saved == eps_out))
+        return fail(LSNF_E_ARG, "%s: z_saved must not alias another tensor of the call", entry);
+    // (an in-place call would overwrite the last block's output, which every backward must be given as z_out: the stash would be useless)
+    if ((z_saved || act_saved) && c.z_in && c.z_in == c.z_out)
+        return fail(LSNF_E_ARG, "%s: z_out must not alias z_in when z_saved / act_saved are kept (the backward reads z_in)", entry);
+    if (params_workspace) {
+        if (!l16_math()) return fail(LSNF_E_ARG, "%s: params_workspace needs a bf16x3-family math mode (lsnf_params_fast_path() == 1)", entry);
+        if (!act_saved || (g.depth > 1 && !z_saved)) return fail(LSNF_E_ARG, "%s: params_workspace goes with act_saved and z_saved", entry);
+        if (!aligned16(params_workspace)) return fail(LSNF_E_ARG, "%s: params_workspace must be 16-byte aligned", entry);
+    }
+    if (c.smp && (act_saved || z_saved) && !eps_out)
+        return fail(LSNF_E_ARG, "%s: act_saved / z_saved need eps_out (the last block's output, which the backward reads)", entry);
+    if (!reverse_keep_covers(c))
+        return fail(LSNF_E_ARG, "%s: only the latency bf16x3 reverse keeps a stash: needs a bf16x3-family math mode and B=%d <= the "
+                    "small-batch threshold %d (lsnf_reverse_keep_covers)", entry, c.B, small_batch_max());
+    c.vec4 = row_vector_width(g, {c.z_in, c.z_out, eps_out, z_saved});
+    c.z_saved = z_saved; c.act_saved = act_saved;
+    if (params_workspace) {
+        c.hdump = params_workspace + 4 + (size_t)g.depth * lsnf_fold_layout(g.nz, g.width).per_block;
+        // (the tag word the batch contraction of lsnf_params3.hip asks, as lsnf_forward writes it: this kernel's h1 / h2 are row-major)
+        if (c.B >= LSNF_X3_MIN_ROWS &&
+            hipMemsetD32Async((hipDeviceptr_t)(params_workspace + lsnf_params_workspace_tag(g.nz, g.width, g.depth, c.B)), 0, 1, c.stream) != hipSuccess)
+            return fail(LSNF_E_HIP, "%s: hipMemsetD32Async(workspace tag) failed", entry);
+    }
+    const Pick p = {K_SMALL3_REV, lsnf_small3_reverse_st(c)};
+    const hipError_t e = launch_reverse(p, c);
+    if (e != hipSuccess) return launch_fail(e, entry, p.k);
+    return LSNF_OK;
+}
+
 // Backward (lsnf_backward_z, lsnf_langevin_step, lsnf_backward_params): from the activation stash on the bf16 matrix pipe when
 // the call brings one under a bf16x3-family mode (lsnf_small3_bwd.hip / lsnf_bwd3.hip: both take every such call), otherwise
 // the recomputing fp32-MFMA kernels -- the latency or the throughput family by the common threshold, so that the family that
@@ -425,48 +508,53 @@ int lsnf_restash(const float* plan, int nz, int width, int depth, int coupling, 
 
 int lsnf_reverse(const float* plan, int nz, int width, int depth, int coupling, int B, const float* z_in,
                  const float* objective, float* z_out, float* objective_out, void* stream) {
-    LsnfGeo g;
-    if (int rc = geo_or_fail(&g, nz, width, depth, coupling)) return rc;
-    if (B < 0 || B > (1 << 28)) return fail(LSNF_E_ARG, "lsnf_reverse: B=%d out of range", B);
-    if (B == 0) return LSNF_OK;
-    if (!plan || !z_in || !z_out) return fail(LSNF_E_ARG, "lsnf_reverse: NULL argument");
-    if (!aligned16(plan)) return fail(LSNF_E_ARG, "lsnf_reverse: plan must be 16-byte aligned");
-    if (!aligned4(z_in) || !aligned4(z_out) || !aligned4(objective) || !aligned4(objective_out))
-        return fail(LSNF_E_ARG, "lsnf_reverse: tensors must be 4-byte aligned");
     LsnfReverseCall c;
-    c.g = g; c.plan = plan; c.B = B; c.vec4 = row_vector_width(g, {z_in, z_out}); c.stream = (hipStream_t)stream;
+    if (int rc = check_reverse_args("lsnf_reverse", &c.g, nz, width, depth, coupling, B, plan, z_in, objective, z_out, objective_out))
+        return rc < 0 ? rc : LSNF_OK;
+    c.plan = plan; c.B = B; c.vec4 = row_vector_width(c.g, {z_in, z_out}); c.stream = (hipStream_t)stream;
     c.z_in = z_in; c.objective = objective; c.z_out = z_out; c.objective_out = objective_out;
-    const Pick p = select_reverse(c);
-    const hipError_t e = launch_reverse(p, c);
-    if (p.k == K_NONE || e != hipSuccess) return launch_fail(e, "lsnf_reverse", p.k);
-    return LSNF_OK;
+    return reverse_select_launch("lsnf_reverse", c);
 }
 
 int lsnf_sample(const float* plan, int nz, int width, int depth, int coupling, int B, const LsnfRng* rng, float temperature,
                 float* z_out, float* objective_out, float* eps_out, float* ll_out, void* stream) {
-    LsnfGeo g;
-    if (int rc = geo_or_fail(&g, nz, width, depth, coupling)) return rc;
-    if (B < 0 || B > (1 << 28)) return fail(LSNF_E_ARG, "lsnf_sample: B=%d out of range", B);
-    if (!rng) return fail(LSNF_E_ARG, "lsnf_sample: rng is required");
-    if (rng->row0 < 0) return fail(LSNF_E_ARG, "lsnf_sample: rng->row0 must be >= 0");
-    if (rng->offset_dev && (reinterpret_cast<uintptr_t>(rng->offset_dev) & 7u))
-        return fail(LSNF_E_ARG, "lsnf_sample: rng->offset_dev must be 8-byte aligned");
-    if (!std::isfinite(temperature) || temperature < 0.0f)
-        return fail(LSNF_E_ARG, "lsnf_sample: temperature must be finite and >= 0 (got %g)", (double)temperature);
-    if (B == 0) return LSNF_OK;
-    if (!plan || !z_out) return fail(LSNF_E_ARG, "lsnf_sample: NULL argument");
-    if (!aligned16(plan)) return fail(LSNF_E_ARG, "lsnf_sample: plan must be 16-byte aligned");
-    if (!aligned4(z_out) || !aligned4(objective_out) || !aligned4(eps_out) || !aligned4(ll_out))
-        return fail(LSNF_E_ARG, "lsnf_sample: tensors must be 4-byte aligned");
-    if (eps_out == z_out) return fail(LSNF_E_ARG, "lsnf_sample: eps_out must not alias z_out");
-    const LsnfSampleArgs smp = {LsnfRngArgs{rng->seed, rng->offset, rng->offset_dev, rng->row0, 1}, temperature, eps_out, ll_out};
     LsnfReverseCall c;                   // (z_in / objective stay NULL: the kernels draw the rows)
-    c.g = g; c.plan = plan; c.B = B; c.vec4 = row_vector_width(g, {z_out, eps_out}); c.stream = (hipStream_t)stream;
+    if (int rc = check_sample_args("lsnf_sample", &c.g, nz, width, depth, coupling, B, rng, temperature, plan, z_out, objective_out, eps_out, ll_out))
+        return rc < 0 ? rc : LSNF_OK;
+    const LsnfSampleArgs smp = {LsnfRngArgs{rng->seed, rng->offset, rng->offset_dev, rng->row0, 1}, temperature, eps_out, ll_out};
+    c.plan = plan; c.B = B; c.vec4 = row_vector_width(c.g, {z_out, eps_out}); c.stream = (hipStream_t)stream;
     c.z_out = z_out; c.objective_out = objective_out; c.smp = &smp;
-    const Pick p = select_reverse(c);
-    const hipError_t e = launch_reverse(p, c);
-    if (p.k == K_NONE || e != hipSuccess) return launch_fail(e, "lsnf_sample", p.k);
-    return LSNF_OK;
+    return reverse_select_launch("lsnf_sample", c);
+}
+
+int lsnf_reverse_keep_covers(int nz, int width, int depth, int coupling, int B) {
+    LsnfReverseCall c;
+    if (lsnf_geo_init(&c.g, nz, width, depth, coupling) || B < 0 || B > (1 << 28)) return 0;
+    c.B = B;
+    return reverse_keep_covers(c) ? 1 : 0;
+}
+
+int lsnf_reverse_keep(const float* plan, int nz, int width, int depth, int coupling, int B, const float* z_in,
+                      const float* objective, float* z_out, float* objective_out, float* z_saved, float* act_saved,
+                      float* params_workspace, void* stream) {
+    LsnfReverseCall c;
+    if (int rc = check_reverse_args("lsnf_reverse_keep", &c.g, nz, width, depth, coupling, B, plan, z_in, objective, z_out, objective_out))
+        return rc < 0 ? rc : LSNF_OK;
+    c.plan = plan; c.B = B; c.stream = (hipStream_t)stream;
+    c.z_in = z_in; c.objective = objective; c.z_out = z_out; c.objective_out = objective_out;
+    return reverse_keep_launch("lsnf_reverse_keep", c, z_saved, act_saved, params_workspace);
+}
+
+int lsnf_sample_keep(const float* plan, int nz, int width, int depth, int coupling, int B, const LsnfRng* rng, float temperature,
+                     float* z_out, float* objective_out, float* eps_out, float* ll_out, float* z_saved, float* act_saved,
+                     float* params_workspace, void* stream) {
+    LsnfReverseCall c;                   // (z_in / objective stay NULL: the kernel draws the rows)
+    if (int rc = check_sample_args("lsnf_sample_keep", &c.g, nz, width, depth, coupling, B, rng, temperature, plan, z_out, objective_out, eps_out, ll_out))
+        return rc < 0 ? rc : LSNF_OK;
+    const LsnfSampleArgs smp = {LsnfRngArgs{rng->seed, rng->offset, rng->offset_dev, rng->row0, 1}, temperature, eps_out, ll_out};
+    c.plan = plan; c.B = B; c.stream = (hipStream_t)stream;
+    c.z_out = z_out; c.objective_out = objective_out; c.smp = &smp;
+    return reverse_keep_launch("lsnf_sample_keep", c, z_saved, act_saved, params_workspace);
 }
 
 int lsnf_backward_z(const float* plan, int nz, int width, int depth, int coupling, int B, const float* z_out,

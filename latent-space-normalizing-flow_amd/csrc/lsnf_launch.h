@@ -34,6 +34,9 @@ struct LsnfReverseCall : LsnfCall {      // lsnf_reverse; lsnf_sample: smp != NU
     const float* z_in = nullptr; const float* objective = nullptr;      // rows -- z_in / objective are then NULL
     float* z_out = nullptr; float* objective_out = nullptr;
     const LsnfSampleArgs* smp = nullptr;
+    // lsnf_reverse_keep / lsnf_sample_keep (NULL elsewhere; only the latency bf16x3 kernel writes them): the block outputs, the stash
+    // and the parameter-gradient dump (LsnfDumpLayout of block 0, h1 / h2 row-major) of the FORWARD at z_out
+    float* z_saved = nullptr; float* act_saved = nullptr; float* hdump = nullptr;
 };
 struct LsnfBackwardCall : LsnfCall {     // lsnf_backward_z, lsnf_langevin_step (lv != NULL), step (1) of lsnf_backward_params (dump)
     const float* z_out = nullptr; const float* z_saved = nullptr; const float* act_saved = nullptr;

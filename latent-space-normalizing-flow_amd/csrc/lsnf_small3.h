@@ -214,4 +214,34 @@ __device__ __forceinline__ unsigned pair_or32(unsigned u) { return lsnf_pair_or3
 // sum over the 4 lane groups of a per-sample value (lanes n, n + 16, n + 32, n + 48)
 __device__ __forceinline__ float group_sum(float v) { return lsnf_pair_add32(lsnf_pair_add16(v)); }
 
+// ---- the activation stash (lsnf_layout.h LsnfActLayout) as the 16-row latency kernels write it: the forward and the stash-keeping reverse ----
+// stash addressing of a workgroup's ST sample tiles: 16-row tile q = blockIdx.x * ST + st is half (q & 1) of the 32-sample stash tile q >> 1
+struct StashTile { size_t wtile; int lane32; bool ok; };     // ok: a 16-row tile past the batch has no stash tile, nothing of it is stored
+__device__ __forceinline__ StashTile stash_tile(size_t q, int B, int n, int g) {
+    StashTile t;
+    t.wtile = q >> 1;
+    t.ok = (long)q * S3_SAMPLES < (long)B;
+    t.lane32 = 16 * (int)(q & 1) + n + 32 * (g & 1);                      // stash lane of (sample, feature-group parity)
+    return t;
+}
+// sigma of the latent half-unit (nt, ft) of one sample tile: feature tile nt, accumulator layout [g(4)][lane(64)][4]
+__device__ __forceinline__ void stash_sigma(float* act_tile, int nt, int ft, int g, int lane32, const f32x4& sig) {
+    reinterpret_cast<f32x4*>(act_tile + (size_t)nt * 1024)[(2 * ft + (g >> 1)) * 64 + lane32] = sig;
+}
+// ReLU mask of one half-unit (nt, ft) of a hidden layer into the stash (per 32-sample tile and hidden tile one 32-bit word per
+// stash lane, bit 4*(2*ft + (g >> 1)) + r = h[r] > 0): the two lane groups g >> 1 meet in one v_permlane32_swap, and what a wave
+// then holds is exactly BYTE ft of the word -- stored as a byte by lanes 0..31; no LDS staging, no atomics (the ft = 1 wave also
+// clears the unused upper half).
+__device__ __forceinline__ void stash_relu_mask(float* act_tile, size_t mask_off, int t, int lane32, int ft, const f32x4& h, int lane) {
+    unsigned c = 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) c |= (h[r] > 0.0f ? 1u : 0u) << (4 * (lane >> 5) + r);
+    c = pair_or32(c);
+    if (lane < 32) {
+        unsigned char* w = reinterpret_cast<unsigned char*>(reinterpret_cast<unsigned*>(act_tile + mask_off) + t * 64 + lane32);
+        w[ft] = (unsigned char)c;
+        if (ft) *reinterpret_cast<unsigned short*>(w + 2) = (unsigned short)0;
+    }
+}
+
 }  // namespace

@@ -65,22 +65,6 @@ struct Small3Args {
 #define S3_STAMP(i, INSN) do {} while (0)
 #endif
 
-// ReLU mask of one half-unit (nt, ft) of a hidden layer into the stash (lsnf_layout.h LsnfActLayout: per 32-sample tile and hidden
-// tile one 32-bit word per stash lane, bit 4*(2*ft + (g >> 1)) + r = h[r] > 0): the two lane groups g >> 1 meet in one
-// v_permlane32_swap, and what a wave then holds is exactly BYTE ft of the word -- stored as a byte by lanes 0..31; no LDS staging, no atomics
-// (the ft = 1 wave also clears the unused upper half).
-__device__ __forceinline__ void stash_relu_mask(float* act_tile, size_t mask_off, int t, int lane32, int ft, const f32x4& h, int lane) {
-    unsigned c = 0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) c |= (h[r] > 0.0f ? 1u : 0u) << (4 * (lane >> 5) + r);
-    c = pair_or32(c);
-    if (lane < 32) {
-        unsigned char* w = reinterpret_cast<unsigned char*>(reinterpret_cast<unsigned*>(act_tile + mask_off) + t * 64 + lane32);
-        w[ft] = (unsigned char)c;
-        if (ft) *reinterpret_cast<unsigned short*>(w + 2) = (unsigned short)0;
-    }
-}
-
 // ST = sample tiles (of 16 rows) per workgroup.  ST = 1 is the latency form (B = 100: 7 workgroups).  ST = 2 / 4 are the
 // SHARD-SIZE forms (strong scaling of the 65 536-row evaluation over 8 / 4 GPUs leaves 8 192 / 16 384 rows per GPU): a
 // workgroup of 32 / 64 rows streams the same 192 KiB of weights per block as a 16-row one -- every fetched fragment triple
@@ -200,14 +184,12 @@ __global__ __launch_bounds__(256, (LSNF_SMALL3_WAVES2 && ST <= 2 && C::WT <= 2 &
     const LsnfActLayout al = lsnf_act_layout(a.B, HT, WT);
     const LsnfDumpLayout dl = lsnf_dump_layout(a.B, a.nz, a.width);
     const bool w4 = (a.width & 3) == 0;
-    // stash addressing: 16-row tile q = blockIdx.x * ST + st is half (q & 1) of the 32-sample stash tile q >> 1
+    // stash addressing (lsnf_small3.h): 16-row tile q = blockIdx.x * ST + st is half (q & 1) of the 32-sample stash tile q >> 1
     size_t wtile[ST]; int lane32[ST]; bool tile_ok[ST];
 #pragma unroll
     for (int st = 0; st < ST; ++st) {
-        const size_t q = (size_t)blockIdx.x * ST + st;
-        wtile[st] = q >> 1;
-        tile_ok[st] = (long)q * S3_SAMPLES < (long)a.B;                   // (a 16-row tile past the batch has no stash tile: nothing of it is stored)
-        lane32[st] = 16 * (int)(q & 1) + n + 32 * (g & 1);                // stash lane of (sample, feature-group parity)
+        const StashTile t = stash_tile((size_t)blockIdx.x * ST + st, a.B, n, g);
+        wtile[st] = t.wtile; tile_ok[st] = t.ok; lane32[st] = t.lane32;
     }
     // (the row loads above are older than every weight load: the split above waited for them and, in order, for the constants' DMA)
     S3_STAMP(5, "s_memtime");

@@ -6,6 +6,9 @@
 //   CI       : z2 = z2 / sigmoid(p) - t ; objective -= sum log sigmoid(p)     (model.py:436-438), in registers: R4's epilogue
 //   I1       : z = ([z1,z2] @ W^-1) * exp(-3 logs) - b ; objective -= log|det W| + sum 3 logs  (:193-196, 270, 246);
 //              its epilogue publishes the new z1 (the next block's R2 operand) into the OTHER z1 buffer: four barriers per block
+// KEEP (lsnf_reverse_keep / lsnf_sample_keep): the pass also leaves what the backward of the reverse (lsnf_small3_rbwd.hip) and the
+// parameter gradients read of the FORWARD at x -- the coupling MLP's input is the first half of the block's OUTPUT (model.py:422), so
+// the [z1; z2] at the top of reverse block b is forward block b's output, R2 / R3's h are h1 / h2 and R4's sigmoid is the stash's.
 #include <stdlib.h>
 #include "lsnf_small3.h"
 #include "lsnf_launch.h"
@@ -44,12 +47,22 @@ struct Small3RevArgs {
 };
 
 struct Small3RevSampleArgs : Small3RevArgs { LsnfSampleArgs s; };      // lsnf_sample: z_in / objective are unused (NULL)
+// KEEP: each pointer NULL or the tensor lsnf_forward documents (z_saved; act_saved: LsnfActLayout, absolute block; hdump: LsnfDumpLayout
+// of block 0, h1 / h2 row-major)
+struct Small3RevKeep { float* z_saved; float* act_saved; float* hdump; int width; };
+struct Small3RevKeepArgs : Small3RevArgs { Small3RevKeep k; };
+struct Small3RevSampleKeepArgs : Small3RevSampleArgs { Small3RevKeep k; };
+template <bool SAMPLE, bool KEEP>
+using small3_rev_args_t = std::conditional_t<KEEP, std::conditional_t<SAMPLE, Small3RevSampleKeepArgs, Small3RevKeepArgs>,
+                                             std::conditional_t<SAMPLE, Small3RevSampleArgs, Small3RevArgs>>;
 
 // SAMPLE: the rows are drawn where they would be loaded (lsnf_sample): each wave draws the two half-units it owns, behind its
 // weight fetches; every other instruction is lsnf_reverse's.  -0.5 * sum eps^2 takes the objective's way through RED, in the
 // prologue (RED is free until the final reduction), into a second accumulator that wave 0 carries.
-template <class C, int ST, bool SAMPLE>
-__global__ __launch_bounds__(256, 1) void lsnf_small3_rev_kernel(const std::conditional_t<SAMPLE, Small3RevSampleArgs, Small3RevArgs> a) {
+// KEEP: stores only, each under its own pointer, in the stage epilogues (under the next sample tile's MFMAs): the ReLU masks and h1 /
+// h2 rows from R2 / R3, sigma from R4, the block outputs from I1 -- what lsnf_small3_fwd.hip's EXTRAS form keeps, same layouts.
+template <class C, int ST, bool SAMPLE, bool KEEP = false>
+__global__ __launch_bounds__(256, 1) void lsnf_small3_rev_kernel(const small3_rev_args_t<SAMPLE, KEEP> a) {
     constexpr int HT = C::HT, WT = C::WT, NZT = C::NZT, NU2 = C::NU2, LASTU = NU2 - 1;
     using L = Small3RevLds<C, ST>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -132,6 +145,19 @@ __global__ __launch_bounds__(256, 1) void lsnf_small3_rev_kernel(const std::cond
 #pragma unroll
     for (int st = 0; st < ST; ++st) lsum[st] = 0.0f;
     __syncthreads();
+    // KEEP: stash addressing (lsnf_small3.h) and the layouts of the stash and of the parameter-gradient dump
+    size_t wtile[ST]; int lane32[ST]; bool tile_ok[ST];
+    LsnfActLayout al = {}; LsnfDumpLayout dl = {}; bool w4 = false;
+    if constexpr (KEEP) {
+#pragma unroll
+        for (int st = 0; st < ST; ++st) {
+            const StashTile t = stash_tile((size_t)blockIdx.x * ST + st, a.B, n, g);
+            wtile[st] = t.wtile; tile_ok[st] = t.ok; lane32[st] = t.lane32;
+        }
+        al = lsnf_act_layout(a.B, HT, WT);
+        dl = lsnf_dump_layout(a.B, a.nz, a.k.width);
+        w4 = (a.k.width & 3) == 0;
+    }
     float llp[ST];                                                        // SAMPLE: -0.5 * sum eps^2 + log(2 pi), carried by wave 0
 #pragma unroll
     for (int st = 0; st < ST; ++st) llp[st] = 0.0f;
@@ -152,6 +178,14 @@ __global__ __launch_bounds__(256, 1) void lsnf_small3_rev_kernel(const std::cond
         const float* gin = a.ipanels3b + (size_t)nb * C::BLOCKI;
         float* z1_cur = Z1 + ((last - blk) & 1) * ST * L::GH;
         float* z1_nxt = Z1 + ((last - blk + 1) & 1) * ST * L::GH;
+        float* act[ST]; float* hd[ST];                                     // KEEP: this block's stash tile / h1, h2 row of each sample tile
+        if constexpr (KEEP) {
+#pragma unroll
+            for (int st = 0; st < ST; ++st) {
+                act[st] = (a.k.act_saved && tile_ok[st]) ? a.k.act_saved + (size_t)blk * al.per_block + wtile[st] * al.per_tile : nullptr;
+                hd[st] = (a.k.hdump && live[st]) ? a.k.hdump + (size_t)blk * dl.per_block + sample[st] * (long)a.k.width : nullptr;
+            }
+        }
 
         // ---- R2: h1 = relu(W1'^T z1 + c1) ----
 #pragma unroll
@@ -161,7 +195,16 @@ __global__ __launch_bounds__(256, 1) void lsnf_small3_rev_kernel(const std::cond
             const f32x4 bh = unit_bias(cb + 32 * (C::P1 + nt), ft, g);
 #pragma unroll
             for (int st = 0; st < ST; ++st) h[st] = bh;
-            auto epi = [&](int st) { h[st] = relu4(h[st]); store_half(H1B + st * L::HL + nt * S3_BTILE_FLOATS, ft, h[st], lane); };
+            auto epi = [&](int st) {
+                h[st] = relu4(h[st]);
+                store_half(H1B + st * L::HL + nt * S3_BTILE_FLOATS, ft, h[st], lane);
+                if constexpr (KEEP) {
+                    if (hasw[i]) {
+                        if (hd[st]) store_plain_half(h[st], hd[st] + dl.off_h1, a.k.width, nt, ft, g, w4);
+                        if (act[st]) stash_relu_mask(act[st], al.mask_off, nt, lane32[st], ft, h[st], lane);
+                    }
+                }
+            };
             const bf16x8* rf = unit_ptr<HT>(gfn + C::OFF3_S2, nt, ft, lane);
             if (i == 0) {        // carry: the last k-tile of I1's two units, THIS block's fragments (I1 runs last in the block)
                 const bf16x8* ca = unit_ptr<NZT>(gi, nt1, ft1, lane);
@@ -183,7 +226,16 @@ __global__ __launch_bounds__(256, 1) void lsnf_small3_rev_kernel(const std::cond
             const f32x4 bh = unit_bias(cb + 32 * (C::P1 + C::P2 + nt), ft, g);
 #pragma unroll
             for (int st = 0; st < ST; ++st) h[st] = bh;
-            auto epi = [&](int st) { h[st] = relu4(h[st]); store_half(H2B + st * L::HL + nt * S3_BTILE_FLOATS, ft, h[st], lane); };
+            auto epi = [&](int st) {
+                h[st] = relu4(h[st]);
+                store_half(H2B + st * L::HL + nt * S3_BTILE_FLOATS, ft, h[st], lane);
+                if constexpr (KEEP) {
+                    if (hasw[i]) {
+                        if (hd[st]) store_plain_half(h[st], hd[st] + dl.off_h2, a.k.width, nt, ft, g, w4);
+                        if (act[st]) stash_relu_mask(act[st], al.mask_off, WT + nt, lane32[st], ft, h[st], lane);
+                    }
+                }
+            };
             const bf16x8* rf = unit_ptr<WT>(gfn + C::OFF3_S3, nt, ft, lane);
             if (i == 0) {
                 const bf16x8* cp = unit_ptr<HT>(gfn + C::OFF3_S2, hw[LASTU] >> 1, hw[LASTU] & 1, lane);
@@ -213,8 +265,12 @@ __global__ __launch_bounds__(256, 1) void lsnf_small3_rev_kernel(const std::cond
                         lsnf_sigmoid_logsig(pp[st][r], sig, lsig);
                         z2[st][r] = z2[st][r] / sig - tt_[st][r];
                         lsum[st] += lsig;
+                        if constexpr (KEEP) pp[st][r] = sig;              // (kept for the stash)
                     }
                     store_half(Z2 + st * L::GH + nt1 * S3_BTILE_FLOATS, ft1, z2[st], lane);
+                    if constexpr (KEEP) {
+                        if (has1 && act[st]) stash_sigma(act[st], nt1, ft1, g, lane32[st], pp[st]);
+                    }
                 },
                 [&](int q) { refill_last<WT>(w3[LASTU], c3, q); }, [](int) {});
         }
@@ -235,7 +291,16 @@ __global__ __launch_bounds__(256, 1) void lsnf_small3_rev_kernel(const std::cond
             const bf16x8* c4p = unit_ptr<WT>(gfn + C::OFF3_S4, HT + nt1, ft1, lane);
             units_mma_st<NZT, 0, NZT, ST, 2, 24, 6, 0, HT>(z1, z2, wia, wib, unit_ptr<NZT>(gin, nt1, ft1, lane), unit_ptr<NZT>(gin, HT + nt1, ft1, lane),
                 z1_cur, L::GH, lane,
-                [&](int st) { store_half(z1_nxt + st * L::GH + nt1 * S3_BTILE_FLOATS, ft1, z1[st], lane); },   // (after block 0: nobody reads it)
+                [&](int st) {
+                    store_half(z1_nxt + st * L::GH + nt1 * S3_BTILE_FLOATS, ft1, z1[st], lane);   // (after block 0: nobody reads it)
+                    if constexpr (KEEP) {            // [z1; z2] is forward block blk-1's output: slice blk-1 of z_saved
+                        if (a.k.z_saved && blk > 0 && has1 && live[st]) {
+                            float* zr = a.k.z_saved + ((size_t)(blk - 1) * a.B + sample[st]) * a.nz;
+                            store_row_half<HT>(nt1, ft1, z1[st], zr, a.half, g, vec4);
+                            store_row_half<HT>(HT + nt1, ft1, z2[st], zr, a.half, g, vec4);
+                        }
+                    }
+                },
                 [&](int q) { if (q < 3) refill_last<WT>(w4t, c4t, q); else refill_last<WT>(w4p, c4p, q - 3); }, [](int) {}, Z2);
         }
         __syncthreads();
@@ -277,13 +342,20 @@ size_t small3_rev_lds(int depth) { return ((size_t)Small3RevLds<C, ST>::L_CONST 
 template <class C, int ST>
 constexpr bool small3_rev_built = (size_t)(Small3RevLds<C, ST>::L_CONST + C::CONST_PER_BLOCK) * sizeof(float) <= 160 * 1024 && !(ST == 4 && C::WT > 2);
 
-template <class C, int ST, bool SAMPLE, class Args>
+template <class C, int ST, bool SAMPLE, bool KEEP, class Args>
 hipError_t launch_small3_rev_st(const Args& a, hipStream_t stream) {
     if constexpr (!small3_rev_built<C, ST>) {
         return hipErrorInvalidValue;                 // (a selection bug)
     } else {
-        return lsnf_launch_kernel<lsnf_small3_rev_kernel<C, ST, SAMPLE>>(lsnf_grid(a.B, ST * S3_SAMPLES), 256, small3_rev_lds<C, ST>(a.depth), stream, a);
+        return lsnf_launch_kernel<lsnf_small3_rev_kernel<C, ST, SAMPLE, KEEP>>(lsnf_grid(a.B, ST * S3_SAMPLES), 256, small3_rev_lds<C, ST>(a.depth), stream, a);
     }
+}
+// the instantiation of (geometry, st) in the form `args` is the argument type of
+template <bool SAMPLE, bool KEEP, class Args>
+hipError_t launch_small3_rev(const LsnfReverseCall& c, int st, const Args& args) {
+    return lsnf_with_cfg<Small3RevCfg>(c.g, [&](auto cfg) {
+        return lsnf_with_st(st, [&](auto s) { return launch_small3_rev_st<decltype(cfg), decltype(s)::value, SAMPLE, KEEP>(args, c.stream); });
+    });
 }
 }  // namespace
 
@@ -301,14 +373,23 @@ int lsnf_small3_reverse_st(const LsnfReverseCall& c) {
     });
 }
 
-// st: lsnf_small3_reverse_st of the call
+// st: lsnf_small3_reverse_st of the call.  A call that keeps something (z_saved / act_saved / hdump) runs the KEEP form.
 hipError_t lsnf_launch_small3_reverse(const LsnfReverseCall& c, int st) {
     Small3RevSampleArgs a;
     lsnf_fill_reverse(a, c);
     a.panels3b = c.plan + c.g.off_f3b_panels; a.ipanels3b = c.plan + c.g.off_i3b_panels;
+    if (c.z_saved || c.act_saved || c.hdump) {
+        const Small3RevKeep k = {c.z_saved, c.act_saved, c.hdump, c.g.width};
+        if (c.smp) {
+            Small3RevSampleKeepArgs ak;
+            static_cast<Small3RevArgs&>(ak) = a; ak.s = *c.smp; ak.k = k;
+            return launch_small3_rev<true, true>(c, st, ak);
+        }
+        Small3RevKeepArgs ak;
+        static_cast<Small3RevArgs&>(ak) = a; ak.k = k;
+        return launch_small3_rev<false, true>(c, st, ak);
+    }
     return lsnf_with_sample<Small3RevArgs>(a, c.smp, [&](auto sample, const auto& args) {
-        return lsnf_with_cfg<Small3RevCfg>(c.g, [&](auto cfg) {
-            return lsnf_with_st(st, [&](auto s) { return launch_small3_rev_st<decltype(cfg), decltype(s)::value, decltype(sample)::value>(args, c.stream); });
-        });
+        return launch_small3_rev<decltype(sample)::value, false>(c, st, args);
     });
 }

@@ -327,10 +327,37 @@ def new_stats(device) -> torch.Tensor:
     return torch.zeros(STATS_DOUBLES, dtype=torch.float64, device=device)
 
 
+def reverse_keep_supported(plan: FlowPlan, B: int) -> bool:
+    """True if `reverse` / `sample` can keep the backward's stash for a batch of B rows (`lsnf_reverse_keep_covers`): the
+    latency bf16x3 reverse, i.e. a bf16x3-family math mode and B up to the small-batch threshold in force."""
+    return bool(_lib.load().lsnf_reverse_keep_covers(plan.nz, plan.width, plan.depth, plan.coupling, int(B)))
+
+
+def _keep_buffers(plan: FlowPlan, B: int, device, save_for_backward: bool, act_saved, params_ws):
+    """The block-output buffer of a stash-keeping reverse / sample (or None), after the size checks of all three buffers."""
+    lib = _lib.load()
+    saved = None
+    if save_for_backward and plan.depth > 1:
+        saved = torch.empty((plan.depth - 1, B, plan.nz), dtype=torch.float32, device=device)
+    if act_saved is not None:
+        _check_out(act_saved, "act_saved", lib.lsnf_act_saved_floats(plan.nz, plan.width, plan.depth, B), device,
+                   hint="from new_act_saved()")
+    if params_ws is not None:
+        _check_out(params_ws, "params_ws", lib.lsnf_backward_params_workspace_floats(plan.nz, plan.width, plan.depth, B), device,
+                   hint="from new_params_workspace()")
+    return saved
+
+
 def reverse(plan: FlowPlan, z: torch.Tensor, objective: Optional[torch.Tensor] = None, *,
-            out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+            out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, save_for_backward: bool = False,
+            act_saved: Optional[torch.Tensor] = None, params_ws: Optional[torch.Tensor] = None):
     """model.py:484-498: returns (z_out, objective_out) with objective_out = objective - sum log|det J|.
-    out: optional caller-owned (z_out, objective_out); either may be the input itself (in-place call)."""
+    out: optional caller-owned (z_out, objective_out); either may be the input itself (in-place call).
+    save_for_backward / act_saved / params_ws (as `forward`'s): the same launch, same bits, also keeps what the FORWARD at
+    x = z_out would -- the block outputs, the activation stash, h1 / h2 for the parameter gradients -- so that
+    `reverse_backward_z(plan, z, saved, act_saved, ...)` and `backward_params(plan, params, x, z, saved, ..., act_saved=,
+    workspace=)` need no second pass over x.  The return is then (z_out, objective_out, saved).  Only where
+    `reverse_keep_supported(plan, B)`; elsewhere the call raises."""
     lib = _lib.load()
     _need_cuda(z, "z")
     if z.dim() != 2 or z.shape[1] != plan.nz:
@@ -347,6 +374,14 @@ def reverse(plan: FlowPlan, z: torch.Tensor, objective: Optional[torch.Tensor] =
     else:
         z_out = torch.empty_like(z)
         obj_out = torch.empty(B, dtype=torch.float32, device=z.device)
+    if save_for_backward or act_saved is not None or params_ws is not None:
+        saved = _keep_buffers(plan, B, z.device, save_for_backward, act_saved, params_ws)
+        with torch.cuda.device(z.device):
+            rc = lib.lsnf_reverse_keep(_ptr(plan.buf), plan.nz, plan.width, plan.depth, plan.coupling, B,
+                                       _ptr(z), _ptr(objective), _ptr(z_out), _ptr(obj_out), _ptr(saved), _ptr(act_saved),
+                                       _ptr(params_ws), _stream_ptr(z.device))
+        _lib.check(rc, "lsnf_reverse_keep")
+        return z_out, obj_out, saved
     with torch.cuda.device(z.device):
         rc = lib.lsnf_reverse(_ptr(plan.buf), plan.nz, plan.width, plan.depth, plan.coupling, B,
                               _ptr(z), _ptr(objective), _ptr(z_out), _ptr(obj_out), _stream_ptr(z.device))
@@ -460,17 +495,22 @@ class PhiloxNoise:
 
 
 def sample(plan: FlowPlan, B: int, rng: PhiloxNoise, *, temperature: float = 1.0, want_eps: bool = False,
-           want_ll: bool = False, out: Optional[Tuple[Optional[torch.Tensor], ...]] = None):
+           want_ll: bool = False, out: Optional[Tuple[Optional[torch.Tensor], ...]] = None, save_for_backward: bool = False,
+           act_saved: Optional[torch.Tensor] = None, params_ws: Optional[torch.Tensor] = None):
     """Fused prior sampling (`lsnf_sample`; train.py:472-475 without the `randn` launch and its (B, nz) tensor): ONE launch draws
     eps = temperature * N(0,1) inside the reverse kernel -- a pure function of (rng.seed, rng.offset, rng.row0 + row, column),
     so row-sharded calls with matching `row0` draw what one call would -- and returns (x, objective_out, eps or None, ll or None):
     x, objective_out = what `reverse(plan, eps)` returns, bit for bit; ll = -0.5*sum eps^2 + log(2 pi) - objective_out, the
     log-density of x under the flow prior.  `rng` is not advanced: pass `rng.step()` (or advance it) for the next call.
     out: optional caller-owned (x, objective_out, eps, ll) on the plan's device; each of the last three may be None (not
-    written; want_eps / want_ll then do not apply).  Every buffer is checked before anything is launched."""
+    written; want_eps / want_ll then do not apply).  Every buffer is checked before anything is launched.
+    save_for_backward / act_saved / params_ws: as `reverse`'s (`lsnf_sample_keep`); the return is then (x, objective_out, eps, ll,
+    saved), and eps -- the last block's output, which the backward reads -- is always returned (with `out`, out[2] is required)."""
     lib = _lib.load()
     B = int(B)
     dev = plan.device
+    keep = save_for_backward or act_saved is not None or params_ws is not None
+    want_eps = want_eps or keep
     if not isinstance(rng, PhiloxNoise):
         raise LsnfError("rng must be a flow.PhiloxNoise (the draw is made inside the kernel; there is no tensor form)")
     if B < 0:
@@ -500,6 +540,16 @@ def sample(plan: FlowPlan, B: int, rng: PhiloxNoise, *, temperature: float = 1.0
     if ll is not None:
         _check_out(ll, "out[3] (ll)", B, dev)
     c = rng._c()
+    if keep:
+        if eps is None:
+            raise LsnfError("out[2] (eps) is required with save_for_backward / act_saved / params_ws")
+        saved = _keep_buffers(plan, B, dev, save_for_backward, act_saved, params_ws)
+        with torch.cuda.device(dev):
+            rc = lib.lsnf_sample_keep(_ptr(plan.buf), plan.nz, plan.width, plan.depth, plan.coupling, B, ctypes.byref(c),
+                                      float(temperature), _ptr(x), _ptr(obj), _ptr(eps), _ptr(ll), _ptr(saved), _ptr(act_saved),
+                                      _ptr(params_ws), _stream_ptr(dev))
+        _lib.check(rc, "lsnf_sample_keep")
+        return x, obj, eps, ll, saved
     with torch.cuda.device(dev):
         rc = lib.lsnf_sample(_ptr(plan.buf), plan.nz, plan.width, plan.depth, plan.coupling, B, ctypes.byref(c),
                              float(temperature), _ptr(x), _ptr(obj), _ptr(eps), _ptr(ll), _stream_ptr(dev))

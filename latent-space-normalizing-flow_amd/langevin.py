@@ -2,6 +2,7 @@
 restated (they are closures inside train.py and cannot be imported) on top of the fused kernels.
 
   sample_langevin_post_z_with_flow  <- train.py:307-335 (training) / :602-634 (testing: 20x steps, no noise)
+  sample_langevin_post_eps_with_flow   the same sampler in the flow's base space (eps, with z = f^-1(eps)); not in the reference
   flow_mle_step                     <- train.py:404-415
   sample_x                          <- train.py:472-478 (prior samples for the FID evaluation)
 
@@ -47,6 +48,61 @@ def sample_langevin_post_z_with_flow(z, x, netG: nn.Module, netF, *, g_l_steps: 
     if philox is not None and g_l_with_noise:
         philox.advance(g_l_steps)
     return z.detach(), gg_norm, gf_norm, f_log_lkhd
+
+
+def sample_langevin_post_eps_with_flow(eps, x, netG: nn.Module, netF, *, g_l_steps: int, g_l_step_size: float,
+                                       g_llhd_sigma: float, noise: bool = True, philox=None):
+    """The sampler above in the flow's BASE space: Langevin on eps with z = f^-1(eps), target
+    p(eps | x) ~ N(eps; 0, I) * p(x | g(f^-1(eps))) -- the flow's Jacobian cancels against the prior's density, so the prior's
+    gradient is eps itself and the flow enters only through the pull-back of the generator's gradient.  Per step:
+        z      = f^-1(eps)                                  the reverse launch, which keeps its backward's stash
+        grad_g = d/dz 1/(2 sigma^2) |g(z) - x|^2            torch autograd through netG, as train.py:312-314
+        g_eps  = J_{f^-1}(eps)^T grad_g                     `flow.reverse_backward_z`
+        eps   <- eps - 0.5 s^2 (eps + g_eps) [+ s * noise]  torch ops
+    -- two flow launches per step where `flow.reverse_keep_supported` (the latency bf16x3 reverse, up to the small-batch
+    threshold); elsewhere three (reverse, forward at z, backward).  noise: `torch.randn` draws, or, with `philox` =
+    `flow.PhiloxNoise`, the in-kernel stream of the other samplers for step k at offset + k (drawn by a sampling launch of its own
+    whose x is discarded; `philox` is ADVANCED by g_l_steps on return).  There is no fused update kernel.
+    eps: (B, nz) or (B, nz, 1, 1).  Returns (eps_k (B, nz), z_k = f^-1(eps_k) (B, nz, 1, 1), mean |g_eps|, mean |eps|): the last two
+    are the per-row norms of the likelihood's and the prior's gradient at the last step's input, as the z-space sampler's (None
+    if no step ran: g_l_steps = 0, or an empty batch, which comes back as it is without a launch)."""
+    from . import flow
+    B, nz = eps.shape[0], eps.shape[1]
+    eps = eps.detach().reshape(B, nz).contiguous().clone()
+    if B == 0:
+        return eps, eps.view(0, nz, 1, 1), None, None
+    plan = netF._plan()
+    keeps = flow.reverse_keep_supported(plan, B)
+    act = flow.new_act_saved(plan, B, eps.device)
+    mse = nn.MSELoss(reduction="sum")
+    gg_norm = gf_norm = None
+    s = float(g_l_step_size)
+    with torch.no_grad():
+        for k in range(g_l_steps):
+            if keeps:
+                z, _, saved = flow.reverse(plan, eps, None, save_for_backward=True, act_saved=act)
+                z_last = eps
+            else:
+                z, _ = flow.reverse(plan, eps, None)
+                z_last, _, _, saved = flow.forward(plan, z, None, want_ll=False, save_for_backward=True, act_saved=act)
+            with torch.enable_grad():
+                zr = z.view(B, nz, 1, 1).requires_grad_(True)
+                g_log_lkhd = 1.0 / (2.0 * g_llhd_sigma * g_llhd_sigma) * mse(netG(zr), x)        # train.py:312-313
+                grad_g = torch.autograd.grad(g_log_lkhd, zr)[0].reshape(B, nz).contiguous()     # train.py:314
+            g_eps = flow.reverse_backward_z(plan, z_last, saved, act, grad_g, None)
+            gg_norm, gf_norm = g_eps.norm(dim=1).mean(), eps.norm(dim=1).mean()
+            new = eps - 0.5 * s * s * (eps + g_eps)
+            if noise:
+                if philox is not None:
+                    draw = flow.sample(plan, B, philox.step(k), want_eps=True)[2]
+                else:
+                    draw = torch.randn_like(eps)
+                new = new + s * draw
+            eps = new
+        z = flow.reverse(plan, eps, None)[0]
+    if philox is not None and noise:
+        philox.advance(g_l_steps)
+    return eps, z.view(B, nz, 1, 1), gg_norm, gf_norm
 
 
 def flow_mle_step(netF, optF, z_g_k, f_max_norm: Optional[float] = None, fused: bool = False):

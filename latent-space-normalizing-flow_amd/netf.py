@@ -187,23 +187,43 @@ class _FlowReverseFn(torch.autograd.Function):
     """(eps, objective, token) -> (x, objective_out) of the sampling direction.  Forward: the lsnf_reverse launch of the
     no_grad call (same bits).  Backward: lsnf_forward on the saved x (block outputs + stash), then lsnf_reverse_backward_z for
     eps; the parameters follow from the implicit-function theorem -- dL/dtheta of the reverse is lsnf_backward_params of the
-    FORWARD at x with upstream gradients (-g_eps, -g_obj) -- so they are handed to _ParamGate like the forward direction's."""
+    FORWARD at x with upstream gradients (-g_eps, -g_obj) -- so they are handed to _ParamGate like the forward direction's.
+    With `module.reverse_keeps_stash` (where flow.reverse_keep_supported): the reverse launch itself keeps the block outputs and the
+    stash (lsnf_reverse_keep), and the backward goes straight to lsnf_reverse_backward_z."""
+
+    @staticmethod
+    def _keeps(module, plan, B):
+        return bool(module.reverse_keeps_stash) and B > 0 and flow.reverse_keep_supported(plan, B)
+
+    @staticmethod
+    def _keep_buffers(ctx, plan, B, want_tok):
+        """(act, ws) of a stash-keeping forward: the workspace only if a parameter requires grad and the fast path is on."""
+        ctx.act = flow.new_act_saved(plan, B, plan.device)
+        ctx.ws = flow.new_params_workspace(plan, B, plan.device) if (want_tok and flow.params_fast_path()) else None
+        return ctx.act, ctx.ws
 
     @staticmethod
     def forward(ctx, module, holder, z, objective, token):
-        x, obj = flow.reverse(module._plan(), z, objective)
+        plan = module._plan()
         ctx.module, ctx.holder = module, holder
         ctx.plan_key = module._plan_key
         ctx.obj_shape = objective.shape
         ctx.set_materialize_grads(False)
-        ctx.save_for_backward(x)
+        ctx.keeps = _FlowReverseFn._keeps(module, plan, z.shape[0])
+        if ctx.keeps:
+            act, ws = _FlowReverseFn._keep_buffers(ctx, plan, z.shape[0], ctx.needs_input_grad[4])
+            x, obj, saved = flow.reverse(plan, z, objective, save_for_backward=True, act_saved=act, params_ws=ws)
+            ctx.save_for_backward(x, z, saved if saved is not None else x.new_empty(0))
+        else:
+            x, obj = flow.reverse(plan, z, objective)
+            ctx.save_for_backward(x)
         return x, obj
 
     @staticmethod
     def _backward(ctx, g_x, g_obj, want_tok):
         """(g_eps, g_obj made contiguous, g_tok) from the saved x: shared with _FlowSampleFn, which saves the same."""
         module, h = ctx.module, ctx.holder
-        x, = ctx.saved_tensors
+        x = ctx.saved_tensors[0]
         if module._current_key() != ctx.plan_key:   # (see _FlowStackFn.backward)
             raise LsnfError("flow parameters were modified between forward and backward")
         plan = module._plan()
@@ -212,12 +232,17 @@ class _FlowReverseFn(torch.autograd.Function):
         g_obj = None if g_obj is None else g_obj.contiguous()
         h.empty = B == 0                                    # (an empty batch leaves the parameters without a gradient)
         need_tok = want_tok and B > 0
-        for_params = need_tok and flow.params_fast_path()
-        act = flow.new_act_saved(plan, B, x.device)
-        ws = flow.new_params_workspace(plan, B, x.device) if for_params else None
-        if ws is not None and x.data_ptr() % 16:
-            x = x.clone()        # the fast path wants 16-byte aligned rows at large B (lsnf_forward, params_workspace)
-        z1, _, _, saved = flow.forward(plan, x, None, want_ll=False, save_for_backward=True, act_saved=act, params_ws=ws)
+        if ctx.keeps:            # the reverse launch kept everything: z1 is its own input, the last block's output
+            _, z1, saved = ctx.saved_tensors
+            saved = saved if saved.numel() else None
+            act, ws = ctx.act, ctx.ws
+        else:
+            for_params = need_tok and flow.params_fast_path()
+            act = flow.new_act_saved(plan, B, x.device)
+            ws = flow.new_params_workspace(plan, B, x.device) if for_params else None
+            if ws is not None and x.data_ptr() % 16:
+                x = x.clone()        # the fast path wants 16-byte aligned rows at large B (lsnf_forward, params_workspace)
+            z1, _, _, saved = flow.forward(plan, x, None, want_ll=False, save_for_backward=True, act_saved=act, params_ws=ws)
         g_eps = flow.reverse_backward_z(plan, z1, saved, act, g_x, g_obj)
         g_tok = None
         if need_tok:
@@ -241,12 +266,20 @@ class _FlowSampleFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, module, holder, token, n, rng, temperature):
-        x, obj, eps, ll = flow.sample(module._plan(), n, rng, temperature=temperature, want_eps=True, want_ll=True)
+        plan = module._plan()
         ctx.module, ctx.holder = module, holder
         ctx.plan_key = module._plan_key
         ctx.set_materialize_grads(False)
+        ctx.keeps = _FlowReverseFn._keeps(module, plan, n)
+        if ctx.keeps:
+            act, ws = _FlowReverseFn._keep_buffers(ctx, plan, n, ctx.needs_input_grad[2])
+            x, obj, eps, ll, saved = flow.sample(plan, n, rng, temperature=temperature, want_eps=True, want_ll=True,
+                                                 save_for_backward=True, act_saved=act, params_ws=ws)
+            ctx.save_for_backward(x, eps, saved if saved is not None else x.new_empty(0))
+        else:
+            x, obj, eps, ll = flow.sample(plan, n, rng, temperature=temperature, want_eps=True, want_ll=True)
+            ctx.save_for_backward(x)
         ctx.mark_non_differentiable(eps)
-        ctx.save_for_backward(x)
         return x, obj, eps, ll
 
     @staticmethod
@@ -274,6 +307,10 @@ class _netF(nn.Module):
         self.revnet2d_s = nn.ModuleList(revnet2d_s)
         self._cached_plan: Optional[flow.FlowPlan] = None
         self._plan_key = None
+        # True: the differentiable reverse / sample launches keep the backward's stash themselves (lsnf_reverse_keep /
+        # lsnf_sample_keep) where flow.reverse_keep_supported -- the backward then skips the forward pass at x; elsewhere (large
+        # batches, MATH_FP32) the default bridge runs.  Default False: the bridge that recomputes the forward at x.
+        self.reverse_keeps_stash = False
 
     # ---- prepared weights, re-derived only when a parameter changed -------------------------------
     def _param_list(self) -> List[nn.Parameter]:
