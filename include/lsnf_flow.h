@@ -308,6 +308,33 @@ int lsnf_sample_keep(const float* plan, int nz, int width, int depth, int coupli
                      float* z_out, float* objective_out, float* eps_out, float* ll_out,
                      float* z_saved, float* act_saved, float* params_workspace, void* stream);
 
+/* ---- fused Langevin update in the base space: eps-space Langevin with x = f^-1(eps) ----
+ * lsnf_reverse_backward_z with the update as its output section, one launch.  With g = J_{f^-1}(eps)^T grad_g (the bits of
+ * lsnf_reverse_backward_z(g_x = grad_g, g_objective = NULL)) it computes per element, in this order, every step one fp32 rounding:
+ *     coef = 0.5f * step_size * step_size
+ *     t    = eps + g                        (g = 0 where grad_g is NULL: the same bits as explicit zeros)
+ *     u    = fma(-coef, t, eps)             = eps - coef * t
+ *     new  = fma(step_size, xi, u)          = u + step_size * xi      (only when noise or rng is given; new = u otherwise)
+ * xi is the row of `noise`, or the N(0,1) draw of LsnfRng above -- lsnf_langevin_step's and lsnf_sample's draw (at temperature 1
+ * lsnf_sample's eps_out IS xi), through the same instructions as a loaded xi: the two agree bit for bit.
+ *   z_out        (B, nz) eps, the reverse's input = the last forward block's output; z_saved / act_saved as for
+ *                lsnf_reverse_backward_z: from lsnf_forward at x, lsnf_restash, or lsnf_reverse_keep / lsnf_sample_keep
+ *   grad_g       (B, nz) dL/dx, or NULL
+ *   noise / rng  both NULL: no noise; rng only when noise is NULL; rng->row0 >= 0, offset_dev NULL or 8-byte aligned
+ *   step_size    finite
+ *   eps_new      (B, nz), required; may be z_out itself (the in-place step: every read of a workgroup's rows precedes its stores,
+ *                rows are workgroup-private); must not be grad_g, noise, z_saved or g_eps_out
+ *   g_eps_out    (B, nz) or NULL: g; may be grad_g; must not be noise, z_out or z_saved
+ *   g_norm       (B) or NULL: ||g||_2 per row;   eps_norm (B) or NULL: ||eps||_2 per row (of the input); neither may be
+ *                another tensor of the call (nor each other).  Every forbidden alias is LSNF_E_ARG.
+ * Alignment as lsnf_reverse_backward_z (plan and act_saved 16 bytes, tensors 4; the vector width follows the pointers).  A row's
+ * result does not depend on B, on the workgroup shape or on row0 sharding.  One kernel under every lsnf_set_math_mode and for every
+ * B.  B = 0 succeeds without a launch.  Added without an ABI bump (a new symbol; nothing existing changed). */
+int lsnf_reverse_langevin_step(const float* plan, int nz, int width, int depth, int coupling, int B,
+                               const float* z_out, const float* z_saved, const float* act_saved,
+                               const float* grad_g, const float* noise, const LsnfRng* rng, float step_size,
+                               float* eps_new, float* g_eps_out, float* g_norm, float* eps_norm, void* stream);
+
 /* ---- backward w.r.t. the parameters: replaces `loss_f.backward()` (train.py:406-411) --------
  * Gradients of L w.r.t. the 12 live tensors of every block (same order as lsnf_prepare), for the
  * upstream gradients described under lsnf_backward_z (train.py:410: L = -mean ll -> ll_mode=1,

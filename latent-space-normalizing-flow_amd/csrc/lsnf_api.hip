@@ -99,7 +99,7 @@ enum Kernel {
     K_NONE, K_FWD, K_FWD3, K_FWD3Q, K_FWD2H_FIXUP, K_SMALL_FWD, K_SMALL3_FWD,
     K_REV, K_REV3, K_REV2H_FIXUP, K_SMALL_REV, K_SMALL3_REV,
     K_BWD, K_BWD3, K_SMALL_BWD, K_SMALL3_BWD,
-    K_SMALL3_RBWD,
+    K_SMALL3_RBWD, K_SMALL3_RLV,
 };
 const char* const kKernelName[] = {
     "no kernel takes this call", "lsnf_fwd_kernel", "lsnf_fwd3b_kernel", "lsnf_fwd3q_kernel",
@@ -107,7 +107,7 @@ const char* const kKernelName[] = {
     "lsnf_rev_kernel", "lsnf_rev3_kernel", "lsnf_rev2h_kernel + lsnf_rev3_kernel fix-up", "lsnf_small_rev_kernel",
     "lsnf_small3_rev_kernel",
     "lsnf_bwd_z_kernel", "lsnf_bwd3_kernel", "lsnf_small_bwd_kernel", "lsnf_small3_bwd_kernel",
-    "lsnf_small3_rbwd_kernel",
+    "lsnf_small3_rbwd_kernel", "lsnf_small3_rbwd_kernel (update form)",
 };
 struct Pick { Kernel k; int st = 0; };     // st: rows per workgroup / 16 of the small3 kernels
 
@@ -307,6 +307,9 @@ hipError_t launch_backward(Pick p, const LsnfBackwardCall& c) {
 // than fp32, so it serves every math mode; its workgroup shape follows the batch size alone (more rounds of workgroups above
 // 16 384 rows), not the small-batch threshold -- it reads the stash of whichever forward family the threshold selected.
 Pick select_reverse_backward(const LsnfReverseBackwardCall& c) { return {K_SMALL3_RBWD, lsnf_small3_reverse_backward_st(c)}; }
+// The base-space Langevin step (lsnf_reverse_langevin_step) is that kernel with the update as its output section: the same one
+// kernel under every math mode and batch size, the same workgroup shape as the plain backward of the call.
+Pick select_reverse_langevin(const LsnfReverseLangevinCall& c) { return {K_SMALL3_RLV, lsnf_small3_reverse_backward_st(c)}; }
 
 // Batch contraction of the parameter gradients (LsnfContraction): on the bf16 matrix pipe where lsnf_params3.hip covers the
 // call (use_x3); from 4 096 rows the fp32-MFMA kernel through LDS, with the widest row loads the rows allow -- every row the
@@ -599,6 +602,48 @@ int lsnf_reverse_backward_z(const float* plan, int nz, int width, int depth, int
     const Pick p = select_reverse_backward(c);
     const hipError_t e = lsnf_launch_small3_reverse_backward_z(c, p.st);
     if (e != hipSuccess) return launch_fail(e, "lsnf_reverse_backward_z", p.k);
+    return LSNF_OK;
+}
+
+int lsnf_reverse_langevin_step(const float* plan, int nz, int width, int depth, int coupling, int B, const float* z_out,
+                               const float* z_saved, const float* act_saved, const float* grad_g, const float* noise,
+                               const LsnfRng* rng, float step_size, float* eps_new, float* g_eps_out, float* g_norm, float* eps_norm,
+                               void* stream) {
+    LsnfGeo g;
+    if (int rc = geo_or_fail(&g, nz, width, depth, coupling)) return rc;
+    if (B < 0 || B > (1 << 28)) return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: B=%d out of range", B);
+    if (noise && rng) return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: pass either a noise tensor or an rng, not both");
+    if (rng && rng->offset_dev && (reinterpret_cast<uintptr_t>(rng->offset_dev) & 7u))
+        return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: rng->offset_dev must be 8-byte aligned");
+    if (rng && rng->row0 < 0) return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: rng->row0 must be >= 0");
+    if (!std::isfinite(step_size)) return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: step_size must be finite (got %g)", (double)step_size);
+    // eps_new may be z_out (every read of a workgroup's rows precedes its stores), g_eps_out may be grad_g (read first, as g_z_in / g_x
+    // of lsnf_reverse_backward_z); nothing else the kernel reads may be what it writes, and no two outputs may be one tensor
+    if (eps_new && (eps_new == grad_g || eps_new == noise || eps_new == z_saved || eps_new == g_eps_out))
+        return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: eps_new must not alias grad_g, noise, z_saved or g_eps_out");
+    if (g_eps_out && (g_eps_out == noise || g_eps_out == z_out || g_eps_out == z_saved))
+        return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: g_eps_out must not alias noise, z_out or z_saved");
+    for (const float* nrm : {(const float*)g_norm, (const float*)eps_norm})
+        if (nrm && (nrm == z_out || nrm == z_saved || nrm == grad_g || nrm == noise || nrm == eps_new || nrm == g_eps_out ||
+                    (g_norm == eps_norm)))
+            return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: g_norm / eps_norm must not alias another tensor of the call");
+    if (B == 0) return LSNF_OK;
+    if (!plan || !z_out || !eps_new || (depth > 1 && !z_saved)) return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: NULL argument");
+    if (!act_saved)
+        return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: act_saved is required (the stash of lsnf_forward, lsnf_restash or lsnf_reverse_keep)");
+    if (!aligned16(plan)) return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: plan must be 16-byte aligned");
+    if (!aligned16(act_saved)) return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: act_saved must be 16-byte aligned");
+    if (!aligned4(z_out) || !aligned4(z_saved) || !aligned4(grad_g) || !aligned4(noise) || !aligned4(eps_new) || !aligned4(g_eps_out) ||
+        !aligned4(g_norm) || !aligned4(eps_norm))
+        return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: tensors must be 4-byte aligned");
+    LsnfReverseLangevinCall c;           // (no g_x / g_objective: the upstream gradient is grad_g)
+    c.g = g; c.plan = plan; c.B = B; c.vec4 = row_vector_width(g, {z_out, z_saved, grad_g, noise, eps_new, g_eps_out}); c.stream = (hipStream_t)stream;
+    c.z_out = z_out; c.z_saved = z_saved; c.act_saved = act_saved; c.g_z_in = g_eps_out;
+    c.grad_g = grad_g; c.noise = noise; c.step = step_size; c.eps_new = eps_new; c.g_norm = g_norm; c.eps_norm = eps_norm;
+    if (rng) c.rng = LsnfRngArgs{rng->seed, rng->offset, rng->offset_dev, rng->row0, 1};
+    const Pick p = select_reverse_langevin(c);
+    const hipError_t e = lsnf_launch_small3_reverse_langevin(c, p.st);
+    if (e != hipSuccess) return launch_fail(e, "lsnf_reverse_langevin_step", p.k);
     return LSNF_OK;
 }
 

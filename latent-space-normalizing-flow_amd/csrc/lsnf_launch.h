@@ -51,6 +51,12 @@ struct LsnfReverseBackwardCall : LsnfCall {      // lsnf_reverse_backward_z
     const float* g_x = nullptr; const float* g_objective = nullptr;
     float* g_z_in = nullptr;
 };
+struct LsnfReverseLangevinCall : LsnfReverseBackwardCall {      // lsnf_reverse_langevin_step: g_x / g_objective stay NULL (the
+    const float* grad_g = nullptr; const float* noise = nullptr;   // upstream gradient is grad_g), g_z_in is the optional g_eps_out
+    LsnfRngArgs rng = {0ull, 0ull, nullptr, 0ll, 0};
+    float step = 0.f;
+    float* eps_new = nullptr; float* g_norm = nullptr; float* eps_norm = nullptr;
+};
 struct LsnfContractCall : LsnfCall {     // steps (2), (3) of lsnf_backward_params: batch contraction of the dump, chain rule
     const float* const* params_host = nullptr; float* const* grads_host = nullptr;
     const float* z_in = nullptr; const float* z_out = nullptr; const float* z_saved = nullptr;
@@ -108,6 +114,7 @@ int lsnf_small3_backward_st(const LsnfBackwardCall& c);
 hipError_t lsnf_launch_small3_backward_z(const LsnfBackwardCall& c, int st);
 int lsnf_small3_reverse_backward_st(const LsnfReverseBackwardCall& c);
 hipError_t lsnf_launch_small3_reverse_backward_z(const LsnfReverseBackwardCall& c, int st);
+hipError_t lsnf_launch_small3_reverse_langevin(const LsnfReverseLangevinCall& c, int st);      // st: of the same predicate
 
 bool lsnf_contract_x3_covers(const LsnfContractCall& c);                   // (also asked with NULL tensors: lsnf_api.hip dump_may_tile)
 hipError_t lsnf_launch_contract_x3(const LsnfContractCall& c, int chunk_override);

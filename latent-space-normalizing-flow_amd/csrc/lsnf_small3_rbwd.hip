@@ -20,6 +20,10 @@
 // LSNF_MATH_FP16X2.  ONE form for every batch size: above 16 384 rows the grid simply runs more rounds of workgroups;
 // lsnf_set_small_batch_max does not affect it.  A row's result does not depend on the batch size or on ST (MFMA columns are
 // independent, the split and the coupling arithmetic are compiled without fp contraction).
+//
+// UPDATE form (lsnf_reverse_langevin_step): the reverse's input y IS the point eps of the base-space Langevin sampler and z_out holds it,
+// so the output section becomes  eps_new = eps - 0.5 s^2 (eps + g_y) [+ s xi]  on the registers that hold g_y -- xi from a tensor or
+// drawn here (lsnf_device.h lsnf_sample4) --, with optional per-row norms of g_y and eps.  The UPDATE = false code is what it was.
 #include <stdlib.h>
 #include "lsnf_small3.h"
 #include "lsnf_launch.h"
@@ -58,6 +62,12 @@ struct Small3RbwdArgs {
     float* g_z_in;
     int B, nz, half, depth, vec4;
 };
+// UPDATE form (lsnf_reverse_langevin_step): the base-space Langevin update on the kernel's own result.  g_z_in is then optional.
+struct Small3RlvArgs : Small3RbwdArgs {
+    const float* noise; float* eps_new; float* g_norm; float* eps_norm;
+    float step;
+    LsnfRngArgs rng;
+};
 
 __device__ __forceinline__ f32x4 rb_mask4(f32x4 a, unsigned nib) {
 #pragma unroll
@@ -66,8 +76,12 @@ __device__ __forceinline__ f32x4 rb_mask4(f32x4 a, unsigned nib) {
 }
 __device__ __forceinline__ f32x4 rb_zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
 
-template <class C, int ST>
-__global__ __launch_bounds__(256, 1) void lsnf_small3_rbwd_kernel(const Small3RbwdArgs a) {
+// UPDATE = false: g on the reverse's input.  UPDATE = true: the output section is the Langevin update of the reverse's input eps
+// (= z_out) with that g -- per element, in this order, each step one fp32 rounding (explicit intrinsics: nothing is re-contracted,
+// and a loaded xi and a drawn xi go through the same instructions):
+//     t = eps + g ;  u = fma(-coef, t, eps), coef = 0.5f * step * step ;  new = fma(step, xi, u)  (only with noise / rng)
+template <class C, int ST, bool UPDATE>
+__global__ __launch_bounds__(256, 1) void lsnf_small3_rbwd_kernel(const std::conditional_t<UPDATE, Small3RlvArgs, Small3RbwdArgs> a) {
     constexpr int HT = C::HT, WT = C::WT, NZT = C::NZT, NU2 = C::NU2, LASTU = NU2 - 1;
     using L = Small3RbwdLds<C, ST>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -156,6 +170,7 @@ __global__ __launch_bounds__(256, 1) void lsnf_small3_rbwd_kernel(const Small3Rb
     __syncthreads();
 
     f32x4 gv1[ST], gv2[ST];
+    f32x4 e1[UPDATE ? ST : 1];                                            // UPDATE: the first half of this wave's unit of eps (the second is y2)
     for (int blk = 0; blk <= last; ++blk) {
         const int nb = blk < last ? blk + 1 : last;                         // the last block re-fetches its own panels: no loads under a branch
         const float* gb = a.panels + (size_t)blk * C::BLOCKB;
@@ -239,6 +254,12 @@ __global__ __launch_bounds__(256, 1) void lsnf_small3_rbwd_kernel(const Small3Rb
         __syncthreads();
         // ---- B2: g_y1 = g_v1 (direct) + W1' g_a1.  The next block's stash slice / output rows are requested here ----
         fetch_block_state(nb);                                             // (this block's are consumed: CB' ran in T1, the masks in B4 / B3)
+        if constexpr (UPDATE) {
+            if (blk == last) {                                             // (kernel-uniform) with the last block's re-fetch of y2 = eps, second half
+#pragma unroll
+                for (int st = 0; st < ST; ++st) e1[st] = load_row_half<HT>(nt1, ft1, a.z_out + row[st] * (long)a.nz, a.half, g, vec4);
+            }
+        }
         {
 #pragma unroll
             for (int st = 0; st < ST; ++st) g1[st] = gv1[st];
@@ -251,13 +272,74 @@ __global__ __launch_bounds__(256, 1) void lsnf_small3_rbwd_kernel(const Small3Rb
     }
 
     // ---- output: g on the reverse's input ----
-    if (has1) {
+    if constexpr (!UPDATE) {
+        if (has1) {
+#pragma unroll
+            for (int st = 0; st < ST; ++st) {
+                if (live[st]) {
+                    float* gr = a.g_z_in + sample[st] * (long)a.nz;
+                    store_row_half<HT>(nt1, ft1, g1[st], gr, a.half, g, vec4);
+                    store_row_half<HT>(HT + nt1, ft1, g2[st], gr, a.half, g, vec4);
+                }
+            }
+        }
+    } else {
+        // ---- output: the Langevin update of eps (every read of the workgroup's rows of z_out was issued before the last barrier and
+        // is of the columns this lane stores: eps_new may be z_out) ----
+        const bool norms = a.g_norm || a.eps_norm;                         // kernel-uniform
+        const bool noisy = a.noise || a.rng.enabled;
+        const LsnfRngState rs = (!a.noise && a.rng.enabled) ? lsnf_rng_state(a.rng) : LsnfRngState{0u, 0u, 0u, 0u, 0};
+        const float coef = __fmul_rn(__fmul_rn(0.5f, a.step), a.step);
+        float* RED = GTP;                                                  // (dead since the last barrier; ST * 4 * 16 * 2 floats of ST * TP)
 #pragma unroll
         for (int st = 0; st < ST; ++st) {
-            if (live[st]) {
-                float* gr = a.g_z_in + sample[st] * (long)a.nz;
-                store_row_half<HT>(nt1, ft1, g1[st], gr, a.half, g, vec4);
-                store_row_half<HT>(HT + nt1, ft1, g2[st], gr, a.half, g, vec4);
+            float gn2 = 0.0f, en2 = 0.0f;
+            if (has1) {
+                if (live[st] && a.g_z_in) {
+                    float* gr = a.g_z_in + sample[st] * (long)a.nz;
+                    store_row_half<HT>(nt1, ft1, g1[st], gr, a.half, g, vec4);
+                    store_row_half<HT>(HT + nt1, ft1, g2[st], gr, a.half, g, vec4);
+                }
+#pragma unroll
+                for (int hs = 0; hs < 2; ++hs) {                           // this wave's first-half and second-half unit
+                    const int t = hs * HT + nt1;
+                    const f32x4 gq = hs ? g2[st] : g1[st];
+                    const f32x4 ec = hs ? y2[st] : e1[st];
+                    f32x4 xi = rb_zero4();
+                    if (a.noise) {
+                        xi = load_row_half<HT>(t, ft1, a.noise + row[st] * (long)a.nz, a.half, g, vec4);
+                    } else if (rs.on) {     // the same draws as every other kernel (lsnf_device.h): lsnf_sample's eps at temperature 1
+                        float unused = 0.0f;
+                        xi = lsnf_sample4(hs, 32 * nt1 + 16 * ft1 + 4 * g, a.half, (unsigned long long)(a.rng.row0 + sample[st]), rs, 1.0f, unused);
+                    }
+                    f32x4 en;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        gn2 = __fmaf_rn(gq[r], gq[r], gn2); en2 = __fmaf_rn(ec[r], ec[r], en2);
+                        const float u = __fmaf_rn(-coef, __fadd_rn(ec[r], gq[r]), ec[r]);
+                        en[r] = noisy ? __fmaf_rn(a.step, xi[r], u) : u;
+                    }
+                    if (live[st]) store_row_half<HT>(t, ft1, en, a.eps_new + sample[st] * (long)a.nz, a.half, g, vec4);
+                }
+            }
+            if (norms) {                                                   // per-row norms: over the 4 lane groups, then over the waves
+                gn2 = group_sum(gn2); en2 = group_sum(en2);
+                if (g == 0) { RED[((st * 4 + wave) * 16 + n) * 2] = gn2; RED[((st * 4 + wave) * 16 + n) * 2 + 1] = en2; }
+            }
+        }
+        if (norms) {
+            __syncthreads();
+            if (wave == 0 && g == 0) {
+#pragma unroll
+                for (int st = 0; st < ST; ++st) {
+                    float s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) { s1 += RED[((st * 4 + w) * 16 + n) * 2]; s2 += RED[((st * 4 + w) * 16 + n) * 2 + 1]; }
+                    if (live[st]) {
+                        if (a.g_norm) a.g_norm[sample[st]] = sqrtf(s1);
+                        if (a.eps_norm) a.eps_norm[sample[st]] = sqrtf(s2);
+                    }
+                }
             }
         }
     }
@@ -268,13 +350,13 @@ template <class C, int ST>
 constexpr bool small3_rbwd_built = (size_t)Small3RbwdLds<C, ST>::L_END * sizeof(float) <= 160 * 1024;
 static_assert(small3_rbwd_built<Small3RbwdCfg<1, 1>, 1> && small3_rbwd_built<Small3RbwdCfg<2, 2>, 1> && small3_rbwd_built<Small3RbwdCfg<2, 4>, 1>);
 
-template <class C, int ST>
-hipError_t launch_small3_rbwd_st(const Small3RbwdArgs& a, hipStream_t stream) {
+template <class C, int ST, bool UPDATE, class Args>
+hipError_t launch_small3_rbwd_st(const Args& a, hipStream_t stream) {
     if constexpr (!small3_rbwd_built<C, ST>) {
         return hipErrorInvalidValue;                 // (a selection bug)
     } else {
         const size_t lds = (size_t)Small3RbwdLds<C, ST>::L_END * sizeof(float);
-        return lsnf_launch_kernel<lsnf_small3_rbwd_kernel<C, ST>>(lsnf_grid(a.B, ST * S3_SAMPLES), 256, lds, stream, a);
+        return lsnf_launch_kernel<lsnf_small3_rbwd_kernel<C, ST, UPDATE>>(lsnf_grid(a.B, ST * S3_SAMPLES), 256, lds, stream, a);
     }
 }
 }  // namespace
@@ -298,6 +380,20 @@ hipError_t lsnf_launch_small3_reverse_backward_z(const LsnfReverseBackwardCall& 
     a.z_out = c.z_out; a.z_saved = c.z_saved; a.act_saved = c.act_saved; a.g_x = c.g_x; a.g_obj = c.g_objective; a.g_z_in = c.g_z_in;
     a.B = c.B; a.nz = c.g.nz; a.half = c.g.half; a.depth = c.g.depth; a.vec4 = c.vec4;
     return lsnf_with_cfg<Small3RbwdCfg>(c.g, [&](auto cfg) {
-        return lsnf_with_st(st, [&](auto s) { return launch_small3_rbwd_st<decltype(cfg), decltype(s)::value>(a, c.stream); });
+        return lsnf_with_st(st, [&](auto s) { return launch_small3_rbwd_st<decltype(cfg), decltype(s)::value, false>(a, c.stream); });
+    });
+}
+
+// the same backward with the Langevin update of eps = z_out as its output section; st: lsnf_small3_reverse_backward_st of the call
+hipError_t lsnf_launch_small3_reverse_langevin(const LsnfReverseLangevinCall& c, int st) {
+    if (!c.act_saved || !c.eps_new || c.B < 1 || (c.noise && c.rng.enabled)) return hipErrorInvalidValue;     // (a selection bug)
+    Small3RlvArgs a;
+    a.panels = c.plan + c.g.off_b3b_panels;
+    a.tpanels = c.plan + c.g.off_t3b_panels;
+    a.z_out = c.z_out; a.z_saved = c.z_saved; a.act_saved = c.act_saved; a.g_x = c.grad_g; a.g_obj = nullptr; a.g_z_in = c.g_z_in;
+    a.B = c.B; a.nz = c.g.nz; a.half = c.g.half; a.depth = c.g.depth; a.vec4 = c.vec4;
+    a.noise = c.noise; a.eps_new = c.eps_new; a.g_norm = c.g_norm; a.eps_norm = c.eps_norm; a.step = c.step; a.rng = c.rng;
+    return lsnf_with_cfg<Small3RbwdCfg>(c.g, [&](auto cfg) {
+        return lsnf_with_st(st, [&](auto s) { return launch_small3_rbwd_st<decltype(cfg), decltype(s)::value, true>(a, c.stream); });
     });
 }

@@ -350,14 +350,16 @@ def _keep_buffers(plan: FlowPlan, B: int, device, save_for_backward: bool, act_s
 
 def reverse(plan: FlowPlan, z: torch.Tensor, objective: Optional[torch.Tensor] = None, *,
             out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, save_for_backward: bool = False,
-            act_saved: Optional[torch.Tensor] = None, params_ws: Optional[torch.Tensor] = None):
+            act_saved: Optional[torch.Tensor] = None, params_ws: Optional[torch.Tensor] = None,
+            z_saved_out: Optional[torch.Tensor] = None):
     """model.py:484-498: returns (z_out, objective_out) with objective_out = objective - sum log|det J|.
     out: optional caller-owned (z_out, objective_out); either may be the input itself (in-place call).
     save_for_backward / act_saved / params_ws (as `forward`'s): the same launch, same bits, also keeps what the FORWARD at
     x = z_out would -- the block outputs, the activation stash, h1 / h2 for the parameter gradients -- so that
     `reverse_backward_z(plan, z, saved, act_saved, ...)` and `backward_params(plan, params, x, z, saved, ..., act_saved=,
     workspace=)` need no second pass over x.  The return is then (z_out, objective_out, saved).  Only where
-    `reverse_keep_supported(plan, B)`; elsewhere the call raises."""
+    `reverse_keep_supported(plan, B)`; elsewhere the call raises.  z_saved_out: optional caller-owned (depth-1, B, nz) buffer for
+    `saved` (implies save_for_backward)."""
     lib = _lib.load()
     _need_cuda(z, "z")
     if z.dim() != 2 or z.shape[1] != plan.nz:
@@ -374,8 +376,12 @@ def reverse(plan: FlowPlan, z: torch.Tensor, objective: Optional[torch.Tensor] =
     else:
         z_out = torch.empty_like(z)
         obj_out = torch.empty(B, dtype=torch.float32, device=z.device)
-    if save_for_backward or act_saved is not None or params_ws is not None:
-        saved = _keep_buffers(plan, B, z.device, save_for_backward, act_saved, params_ws)
+    if save_for_backward or act_saved is not None or params_ws is not None or z_saved_out is not None:
+        if z_saved_out is not None:
+            _check_out(z_saved_out, "z_saved_out", (plan.depth - 1) * B * plan.nz, z.device)
+        saved = _keep_buffers(plan, B, z.device, save_for_backward and z_saved_out is None, act_saved, params_ws)
+        if z_saved_out is not None and plan.depth > 1:
+            saved = z_saved_out
         with torch.cuda.device(z.device):
             rc = lib.lsnf_reverse_keep(_ptr(plan.buf), plan.nz, plan.width, plan.depth, plan.coupling, B,
                                        _ptr(z), _ptr(objective), _ptr(z_out), _ptr(obj_out), _ptr(saved), _ptr(act_saved),
@@ -605,6 +611,82 @@ def langevin_step(plan: FlowPlan, z: torch.Tensor, grad_g: Optional[torch.Tensor
                                     _ptr(z_new), _ptr(gf), _ptr(gg), _stream_ptr(z.device))
     _lib.check(rc, "lsnf_langevin_step")
     return z_new, ll, gf, gg
+
+
+def reverse_langevin_step(plan: FlowPlan, eps: torch.Tensor, z_saved: Optional[torch.Tensor], act_saved: torch.Tensor,
+                          grad_g: Optional[torch.Tensor], noise, step_size: float, *, inplace: bool = False,
+                          out: Optional[Tuple[Optional[torch.Tensor], ...]] = None, want_g: bool = False, want_norms: bool = True):
+    """One base-space Langevin update in ONE launch (`lsnf_reverse_langevin_step`): with x = reverse(eps)[0] and
+    g_eps = J_{f^-1}(eps)^T grad_g (`reverse_backward_z(plan, eps, z_saved, act_saved, grad_g)`'s bits),
+        eps_new = eps - 0.5 s^2 (eps + g_eps) + s * noise         (fp32: t = eps + g; u = fma(-0.5 s^2, t, eps); fma(s, noise, u)).
+    eps / z_saved / act_saved: the last block's output (= eps), the block outputs and the stash of the forward AT x -- from
+    `forward(plan, x, ...)`, or kept by `reverse(plan, eps, save_for_backward=True, act_saved=...)`.  grad_g: dL/dx or None (= 0).
+    `noise`: None, a (B, nz) tensor of N(0,1) draws, or a `PhiloxNoise` (drawn inside the kernel: the same draw as `sample`'s eps at
+    temperature 1, and the same result bits as passing that tensor).
+    Returns (eps_new, g_eps or None, g_norm or None, eps_norm or None): g_norm / eps_norm (B) = the per-row 2-norms of g_eps and of
+    the INPUT eps (want_norms), g_eps with want_g.  inplace: eps_new is eps itself.  out: optional caller-owned
+    (eps_new, g_eps, g_norm, eps_norm), each may be None (then allocated if wanted); out[1] may be grad_g.  Asynchronous on the
+    current stream; nothing but the launch, so it can be captured in a graph."""
+    lib = _lib.load()
+    _need_cuda(eps, "eps")
+    if eps.dim() != 2 or eps.shape[1] != plan.nz:
+        raise LsnfError(f"eps must be (B, {plan.nz}), got {tuple(eps.shape)}")
+    B = eps.shape[0]
+    if act_saved is None:
+        raise LsnfError("act_saved is required: the stash of the forward at x = reverse(eps) (forward(..., act_saved=) or reverse(..., act_saved=))")
+    rng = None
+    if isinstance(noise, PhiloxNoise):
+        if noise.offset_dev is not None:
+            od = noise.offset_dev
+            if not od.is_cuda or od.device != eps.device or od.dtype not in (torch.int64, torch.uint64) or od.numel() != 1:
+                raise LsnfError(f"offset_dev must be one 64-bit integer on {eps.device}")
+        rng, noise = ctypes.byref(noise._c()), None
+    for name, t in (("z_saved", z_saved), ("act_saved", act_saved), ("grad_g", grad_g), ("noise", noise)):
+        if t is not None:
+            _need_cuda(t, name)
+            if t.device != eps.device:
+                raise LsnfError(f"{name} lives on {t.device}, eps on {eps.device}")
+    for name, t in (("grad_g", grad_g), ("noise", noise)):
+        if t is not None and t.shape != eps.shape:
+            raise LsnfError(f"{name} must have the shape of eps")
+    if plan.depth > 1 and B > 0 and z_saved is None:
+        raise LsnfError("z_saved (the block outputs of the forward at x) is required for depth > 1")
+    if z_saved is not None and z_saved.numel() < (plan.depth - 1) * B * plan.nz:
+        raise LsnfError(f"z_saved has {z_saved.numel()} elements, expected {(plan.depth - 1) * B * plan.nz}")
+    need = lib.lsnf_act_saved_floats(plan.nz, plan.width, plan.depth, B)
+    if act_saved.numel() < need:
+        raise LsnfError(f"act_saved has {act_saved.numel()} elements, the stash of {B} rows has {need} (new_act_saved())")
+    eps_new = g_eps = g_norm = eps_norm = None
+    if out is not None:
+        if len(out) != 4:
+            raise LsnfError("out must be (eps_new, g_eps, g_norm, eps_norm); each may be None")
+        eps_new, g_eps, g_norm, eps_norm = out
+    if inplace:
+        if eps_new is not None and eps_new.data_ptr() != eps.data_ptr():
+            raise LsnfError("inplace=True writes eps itself: out[0] must be None (or eps)")
+        eps_new = eps
+    f32 = dict(dtype=torch.float32, device=eps.device)
+    if eps_new is None:
+        eps_new = torch.empty_like(eps)
+    if g_eps is None and want_g:
+        g_eps = torch.empty_like(eps)
+    if g_norm is None and want_norms:
+        g_norm = torch.empty(B, **f32)
+    if eps_norm is None and want_norms:
+        eps_norm = torch.empty(B, **f32)
+    _check_out(eps_new, "out[0] (eps_new)", B * plan.nz, eps.device)
+    if g_eps is not None:
+        _check_out(g_eps, "out[1] (g_eps)", B * plan.nz, eps.device)
+    for name, t in (("out[2] (g_norm)", g_norm), ("out[3] (eps_norm)", eps_norm)):
+        if t is not None:
+            _check_out(t, name, B, eps.device)
+    with torch.cuda.device(eps.device):
+        rc = lib.lsnf_reverse_langevin_step(_ptr(plan.buf), plan.nz, plan.width, plan.depth, plan.coupling, B,
+                                            _ptr(eps), _ptr(z_saved), _ptr(act_saved), _ptr(grad_g), _ptr(noise), rng,
+                                            float(step_size), _ptr(eps_new), _ptr(g_eps), _ptr(g_norm), _ptr(eps_norm),
+                                            _stream_ptr(eps.device))
+    _lib.check(rc, "lsnf_reverse_langevin_step")
+    return eps_new, g_eps, g_norm, eps_norm
 
 
 def backward_params(plan: FlowPlan, params: Sequence[torch.Tensor], z_in: torch.Tensor, z_out: torch.Tensor,

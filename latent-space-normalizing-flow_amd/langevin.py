@@ -51,7 +51,7 @@ def sample_langevin_post_z_with_flow(z, x, netG: nn.Module, netF, *, g_l_steps: 
 
 
 def sample_langevin_post_eps_with_flow(eps, x, netG: nn.Module, netF, *, g_l_steps: int, g_l_step_size: float,
-                                       g_llhd_sigma: float, noise: bool = True, philox=None):
+                                       g_llhd_sigma: float, noise: bool = True, philox=None, fused: bool = False):
     """The sampler above in the flow's BASE space: Langevin on eps with z = f^-1(eps), target
     p(eps | x) ~ N(eps; 0, I) * p(x | g(f^-1(eps))) -- the flow's Jacobian cancels against the prior's density, so the prior's
     gradient is eps itself and the flow enters only through the pull-back of the generator's gradient.  Per step:
@@ -62,7 +62,11 @@ def sample_langevin_post_eps_with_flow(eps, x, netG: nn.Module, netF, *, g_l_ste
     -- two flow launches per step where `flow.reverse_keep_supported` (the latency bf16x3 reverse, up to the small-batch
     threshold); elsewhere three (reverse, forward at z, backward).  noise: `torch.randn` draws, or, with `philox` =
     `flow.PhiloxNoise`, the in-kernel stream of the other samplers for step k at offset + k (drawn by a sampling launch of its own
-    whose x is discarded; `philox` is ADVANCED by g_l_steps on return).  There is no fused update kernel.
+    whose x is discarded; `philox` is ADVANCED by g_l_steps on return).
+    fused=True: the last two lines are ONE launch, `flow.reverse_langevin_step` -- the backward with the update as its output
+    section (fp32 fused multiply-adds: the last bits differ from the torch ops'), the per-row norms from the same kernel, and with
+    `philox` the noise of step k drawn inside it at offset + k: the sampling launch disappears, the flow's part of a step is the
+    reverse and this launch.  `GraphedEpsLangevinSampler` replays that step from a captured graph.
     eps: (B, nz) or (B, nz, 1, 1).  Returns (eps_k (B, nz), z_k = f^-1(eps_k) (B, nz, 1, 1), mean |g_eps|, mean |eps|): the last two
     are the per-row norms of the likelihood's and the prior's gradient at the last step's input, as the z-space sampler's (None
     if no step ran: g_l_steps = 0, or an empty batch, which comes back as it is without a launch)."""
@@ -89,6 +93,13 @@ def sample_langevin_post_eps_with_flow(eps, x, netG: nn.Module, netF, *, g_l_ste
                 zr = z.view(B, nz, 1, 1).requires_grad_(True)
                 g_log_lkhd = 1.0 / (2.0 * g_llhd_sigma * g_llhd_sigma) * mse(netG(zr), x)        # train.py:312-313
                 grad_g = torch.autograd.grad(g_log_lkhd, zr)[0].reshape(B, nz).contiguous()     # train.py:314
+            if fused:
+                # (the kernel's z_out is the point it updates: eps itself, also where the forward at z wrote its own last output, which
+                #  is eps up to the round trip's rounding)
+                xi = None if not noise else philox.step(k) if philox is not None else torch.randn_like(eps)
+                eps, _, gn, en = flow.reverse_langevin_step(plan, eps, saved, act, grad_g, xi, s)
+                gg_norm, gf_norm = gn.mean(), en.mean()
+                continue
             g_eps = flow.reverse_backward_z(plan, z_last, saved, act, grad_g, None)
             gg_norm, gf_norm = g_eps.norm(dim=1).mean(), eps.norm(dim=1).mean()
             new = eps - 0.5 * s * s * (eps + g_eps)
@@ -198,3 +209,76 @@ class GraphedLangevinSampler:
         for _ in range(g_l_steps):
             self.graph.replay()
         return self.z.detach().clone(), self.gg_norm, self.gf_norm, self.f_log_lkhd
+
+
+class GraphedEpsLangevinSampler:
+    """`sample_langevin_post_eps_with_flow(..., fused=True)` with ONE step captured in a HIP graph and replayed K times: the
+    stash-keeping reverse, the generator's forward and input gradient, and `flow.reverse_langevin_step` in place on static buffers
+    (eps, z, the block outputs, the stash), the noise drawn inside the update kernel from a device-side counter that the graph
+    itself advances (`PhiloxNoise(offset_dev=)`).  The host then issues one call per step, as `GraphedLangevinSampler` does for the
+    z-space sampler; the results are the eager fused sampler's with `philox = PhiloxNoise(seed, offset, row0)`, bit for bit.
+    Only where `flow.reverse_keep_supported(plan, B)` (the reverse must keep the stash itself); `LsnfError` otherwise.
+
+        sampler = GraphedEpsLangevinSampler(netG, netF, B, nz, x_shape, g_l_step_size=0.1, g_llhd_sigma=0.3, seed=1)
+        eps_k, z_k, gg_norm, gf_norm = sampler.run(eps0, x, g_l_steps=20, offset=it * 20)
+    """
+
+    def __init__(self, netG: nn.Module, netF, B: int, nz: int, x_shape, *, g_l_step_size: float, g_llhd_sigma: float,
+                 noise: bool = True, seed: int = 0, row0: int = 0, device=None, warmup: int = 3):
+        from . import flow
+        dev = device or next(netF.parameters()).device
+        plan = netF._plan()                            # prepared weights exist before anything is captured
+        if B < 1 or not flow.reverse_keep_supported(plan, B):
+            raise flow.LsnfError(f"GraphedEpsLangevinSampler needs the stash-keeping reverse (flow.reverse_keep_supported) for B={B}: "
+                                 "a bf16x3-family math mode and B within the small-batch threshold")
+        self.netG, self.netF, self.B, self.nz = netG, netF, B, nz
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.eps = torch.zeros(B, nz, **f32)
+        self.z, self.obj = torch.zeros(B, nz, **f32), torch.zeros(B, **f32)
+        self.saved = torch.zeros(max(plan.depth - 1, 1), B, nz, **f32)
+        self.act = flow.new_act_saved(plan, B, dev)
+        self.g_norm, self.eps_norm = torch.zeros(B, **f32), torch.zeros(B, **f32)
+        self.x = torch.zeros(tuple(x_shape), device=dev)
+        self.ctr = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.noise = flow.PhiloxNoise(seed, 0, row0, offset_dev=self.ctr) if noise else None
+        self.s, self.sigma = float(g_l_step_size), float(g_llhd_sigma)
+        self.mse = nn.MSELoss(reduction="sum")
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):                  # warm-up off the capture stream (MIOpen finds its solvers here)
+            for _ in range(warmup):
+                self._step()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self.gg_norm, self.gf_norm = self._step()
+
+    def _step(self):
+        from . import flow
+        plan = self.netF._plan()
+        with torch.no_grad():
+            flow.reverse(plan, self.eps, None, out=(self.z, self.obj), act_saved=self.act, z_saved_out=self.saved)
+        zr = self.z.view(self.B, self.nz, 1, 1).detach().requires_grad_(True)
+        g_log_lkhd = 1.0 / (2.0 * self.sigma * self.sigma) * self.mse(self.netG(zr), self.x)         # train.py:312-313
+        grad_g = torch.autograd.grad(g_log_lkhd, zr)[0].reshape(self.B, self.nz).contiguous()        # train.py:314
+        with torch.no_grad():
+            flow.reverse_langevin_step(plan, self.eps, self.saved if plan.depth > 1 else None, self.act, grad_g, self.noise,
+                                       self.s, inplace=True, out=(None, None, self.g_norm, self.eps_norm))
+            self.ctr.add_(1)                                                                         # next step's noise
+            return self.g_norm.mean(), self.eps_norm.mean()
+
+    def run(self, eps0: torch.Tensor, x: torch.Tensor, g_l_steps: int, offset: int = 0):
+        """Returns (eps_k (B, nz), z_k = f^-1(eps_k) (B, nz, 1, 1), mean |g_eps|, mean |eps|) -- the norms of the last step's input,
+        None if g_l_steps = 0 -- as `sample_langevin_post_eps_with_flow(..., fused=True)`."""
+        from . import flow
+        self.eps.copy_(eps0.reshape(self.eps.shape))
+        self.x.copy_(x)
+        self.ctr.fill_(int(offset))
+        plan = self.netF._plan()                       # re-derives the prepared weights in place if a parameter changed
+        for _ in range(g_l_steps):
+            self.graph.replay()
+        eps = self.eps.detach().clone()
+        z = flow.reverse(plan, eps, None)[0]
+        if g_l_steps < 1:
+            return eps, z.view(self.B, self.nz, 1, 1), None, None
+        return eps, z.view(self.B, self.nz, 1, 1), self.gg_norm.clone(), self.gf_norm.clone()
