@@ -60,6 +60,8 @@ def main():
                     "the per-phase wall time of each (rank 0, stderr); the JSON line then carries their medians")
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL, one GPU per rank); gloo lets several "
                     "ranks SHARE one GPU -- a rehearsal of the data-parallel code path on a one-GPU box, not a measurement")
+    ap.add_argument("--flow-adam", choices=("torch", "fused"), default="torch", help="the flow's optimizer: torch.optim.Adam (+ the clip in "
+                    "torch), or lsnf_amd.FlowAdam -- clip and Adam on the device in two launches, one rank: netF.mle_step")
     args = ap.parse_args()
     size, nz, ngf, f_width, K = GEOMETRY[args.dataset]
     step_size, sigma, nc, B = 0.1, 0.3, 3, args.batch
@@ -78,10 +80,14 @@ def main():
     if world > 1:
         netG = nn.parallel.DistributedDataParallel(netG, device_ids=[dev.index])
     optG = torch.optim.Adam(netG.parameters(), lr=3e-4, betas=(0.5, 0.999))
-    try:                                                        # one fused Adam kernel over the flow's 60 tensors
-        optF = torch.optim.Adam(netF.parameters(), lr=1e-4, betas=(0.5, 0.999), fused=True)
-    except (RuntimeError, TypeError):
-        optF = torch.optim.Adam(netF.parameters(), lr=1e-4, betas=(0.5, 0.999))
+    flow_adam = args.flow_adam == "fused"
+    if flow_adam:                                               # clip (train.py:413-414) and Adam in the library's two launches
+        optF = lsnf_amd.FlowAdam(netF, lr=1e-4, betas=(0.5, 0.999), max_norm=100.0)
+    else:
+        try:                                                    # one fused Adam kernel over the flow's 60 tensors
+            optF = torch.optim.Adam(netF.parameters(), lr=1e-4, betas=(0.5, 0.999), fused=True)
+        except (RuntimeError, TypeError):
+            optF = torch.optim.Adam(netF.parameters(), lr=1e-4, betas=(0.5, 0.999))
     mse = nn.MSELoss(reduction="sum")
     gen = torch.Generator(device=dev).manual_seed(100 + rank)   # every rank owns different rows
     x = torch.tanh(torch.randn(B, nc, size, size, device=dev, generator=gen))
@@ -128,16 +134,20 @@ def main():
         mark("generator_backward_incl_ddp_allreduce")
         optG.step()
         mark("generator_adam")
-        optF.zero_grad(set_to_none=True)                        # train.py:404-415, fused: loss and the 60 gradients in 5 launches,
-        loss_f = netF.mle_grads(zk.view(B, nz), max_norm=100.0 if world == 1 else None,   # then the one-bucket all-reduce
-                                reuse_buffers=True)
-        mark("flow_mle_grads")
-        if world > 1:
-            parallel.allreduce_gradients(netF.parameters(), average=True)
-            mark("flow_grad_allreduce")
-            torch.nn.utils.clip_grad_norm_(netF.parameters(), 100.0)
-        optF.step()
-        mark("flow_clip_adam")
+        if flow_adam and world == 1 and not args.phases:        # gradients, clip, Adam and the plan refresh: no torch launch
+            loss_f = netF.mle_step(zk.view(B, nz), optF)
+        else:
+            optF.zero_grad(set_to_none=True)                    # train.py:404-415, fused: loss and the 60 gradients in 5 launches,
+            loss_f = netF.mle_grads(zk.view(B, nz), max_norm=100.0 if (world == 1 and not flow_adam) else None,
+                                    reuse_buffers=True)         # then the one-bucket all-reduce
+            mark("flow_mle_grads")
+            if world > 1:
+                parallel.allreduce_gradients(netF.parameters(), average=True)
+                mark("flow_grad_allreduce")
+                if not flow_adam:                               # (FlowAdam.step() clips the all-reduced gradients itself)
+                    torch.nn.utils.clip_grad_norm_(netF.parameters(), 100.0)
+            optF.step()
+            mark("flow_clip_adam")
         if args.phases:
             row = {b[0]: (b[1] - a[1]) * 1e3 for a, b in zip(marks, marks[1:])}
             phase_log.append(row)

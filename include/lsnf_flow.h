@@ -364,6 +364,62 @@ int lsnf_backward_params(const float* plan, const float* const* params_host, flo
                          const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
                          float* g_z_in, float* workspace, void* stream);
 
+/* ---- optimizer step of the flow: replaces `clip_grad_norm_` + `optF.step()` (train.py:413-415, optimizer train.py:295) ----
+ * Global-norm clip and torch.optim.Adam (non-amsgrad, maximize=False, L2 weight decay; definition: PyTorch's
+ * _single_tensor_adam) over the depth*12 live tensors, in at most two stream-ordered launches (csrc/lsnf_optim.hip):
+ *     norm = sqrt(sum g^2)  (float64, fixed order)        coef = min(1, max_norm / (norm + 1e-6))   (clip_grad_norm_'s formula)
+ *     g   = coef * grad                       (only when max_norm > 0; a coef of exactly 1 leaves the unclipped call's bits)
+ *     g   = g + weight_decay * p              (only when weight_decay != 0)
+ *     m   = m + (1 - beta1) * (g - m)
+ *     v   = beta2 * v + (1 - beta2) * g * g
+ *     bc1 = 1 - beta1^step;  bc2 = 1 - beta2^step          (float64, step = the device counter AFTER its increment)
+ *     p   = p - (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
+ * Scalars that depend on `step` or on the norm are derived in float64 once per workgroup.  The element math runs in float64
+ * on the stored fp32 values (p is updated from the unrounded m and v) and every stored p, m and v is rounded ONCE: the
+ * correctly rounded value of the formulas above, at most half an ulp per step from the float64 definition.  (In fp32
+ * arithmetic the two to four roundings per value and the fp32 images of 1 - beta put v up to 1.4 ulp off after one step.)
+ *  No atomics and no cross-workgroup barrier: the
+ * result is bit-for-bit reproducible and does not depend on the vector width the pointers allow.
+ *   params_host  HOST array of depth*12 DEVICE pointers (order above), updated in place; none may be NULL
+ *   grads_host   HOST array of depth*12 DEVICE pointers, read only; a NULL entry skips that tensor entirely (its parameter,
+ *                m and v keep their bits and it contributes 0 to the norm: torch's `grad is None`)
+ *   state        device, 16-byte aligned, lsnf_adam_state_bytes() bytes, owned by the caller; all-zero bytes are a fresh
+ *                optimizer.  Layout:
+ *                  [LSNF_ADAM_STEP_OFFSET, +8 * LSNF_ADAM_MAX_GROUPS)      int64 step counters, one per workgroup of the update
+ *                                                                           launch (a single launch cannot read AND advance a
+ *                                                                           shared counter without a grid-wide barrier, so each
+ *                                                                           workgroup advances its own; the grid follows from
+ *                                                                           the geometry alone, so they always agree; slots
+ *                                                                           beyond the grid are not touched).  The one at
+ *                                                                           byte 0 is THE step count.  To set the step, write
+ *                                                                           all LSNF_ADAM_MAX_GROUPS of them.
+ *                  [LSNF_ADAM_PARTIALS_OFFSET, +8 * LSNF_ADAM_MAX_GROUPS)  float64 partial sums of g^2 (internal)
+ *                  LSNF_ADAM_NORM_OFFSET                                   float: the last pre-clip norm that was computed
+ *                  LSNF_ADAM_HEADER_BYTES ...                              m, flat, in ABI tensor order (block by block, no
+ *                                                                           padding between tensors): N = depth * sum of the 12
+ *                                                                           sizes floats, rounded up to a multiple of 4; then v
+ *   lr, beta1, beta2, eps, weight_decay, max_norm
+ *                doubles, as torch.optim.Adam holds them (0.999 is not a float: 1 - beta2 would be off by 1.3e-5 of itself)
+ *   lr_dev       NULL, or one device float that replaces `lr` (learning-rate schedules under a captured graph; the idea of
+ *                LsnfRng.offset_dev)
+ *   max_norm     <= 0: no clipping
+ *   grad_norm_out NULL, or one device float that receives the pre-clip global norm (may be the state's own norm slot)
+ * With neither clipping nor a norm output the norm launch is skipped: one launch.  Asynchronous, allocates nothing, capturable.
+ * LSNF_E_ARG: NULL tables / state / parameter pointer, a pointer that is not 4-byte aligned, misaligned state, lr / eps /
+ * weight_decay negative or not finite, a beta outside [0, 1), max_norm NaN.  Non-finite gradients are NOT special-cased: as in
+ * torch a NaN norm makes coef NaN and poisons the step -- check grad_norm_out.  Plans prepared before the call are stale
+ * afterwards, as after lsnf_actnorm_init.  Added without an ABI bump (new symbols; nothing existing changed). */
+#define LSNF_ADAM_MAX_GROUPS 256
+#define LSNF_ADAM_STEP_OFFSET 0
+#define LSNF_ADAM_PARTIALS_OFFSET 2048
+#define LSNF_ADAM_NORM_OFFSET 4096
+#define LSNF_ADAM_HEADER_BYTES 4160
+size_t lsnf_adam_state_bytes(int nz, int width, int depth, int coupling);      /* 0 on bad geometry */
+int lsnf_adam_step(float* const* params_host, const float* const* grads_host,
+                   int nz, int width, int depth, int coupling, void* state,
+                   double lr, const float* lr_dev, double beta1, double beta2, double eps, double weight_decay,
+                   double max_norm, float* grad_norm_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_size_t, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LSNF_LIB_PATH: developer override to A/B alternative BUILDS of the same library (tools/); not a fallback.
@@ -61,6 +61,9 @@ _SIGNATURES = {
                                      c_int, c_int, c_int, c_int, c_int,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
                                      c_void_p, c_void_p, c_void_p]),
+    "lsnf_adam_state_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "lsnf_adam_step": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_void_p,
+                               c_double, c_void_p, c_double, c_double, c_double, c_double, c_double, c_void_p, c_void_p]),
 }
 
 _lib = None

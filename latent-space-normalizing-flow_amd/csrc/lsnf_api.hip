@@ -422,6 +422,42 @@ int lsnf_actnorm_init(float* const* params_host, int nz, int width, int depth, i
     return LSNF_OK;
 }
 
+size_t lsnf_adam_state_bytes(int nz, int width, int depth, int coupling) {
+    LsnfGeo g;
+    if (lsnf_geo_init(&g, nz, width, depth, coupling)) return 0;
+    return lsnf_adam_bytes(g);
+}
+
+int lsnf_adam_step(float* const* params_host, const float* const* grads_host, int nz, int width, int depth, int coupling,
+                   void* state, double lr, const float* lr_dev, double beta1, double beta2, double eps, double weight_decay,
+                   double max_norm, float* grad_norm_out, void* stream) {
+    LsnfGeo g;
+    if (int rc = geo_or_fail(&g, nz, width, depth, coupling)) return rc;
+    if (!params_host || !grads_host || !state) return fail(LSNF_E_ARG, "lsnf_adam_step: NULL argument");
+    if (!aligned16(state)) return fail(LSNF_E_ARG, "lsnf_adam_step: state must be 16-byte aligned");
+    if (!aligned4(lr_dev) || !aligned4(grad_norm_out)) return fail(LSNF_E_ARG, "lsnf_adam_step: lr_dev / grad_norm_out must be 4-byte aligned");
+    if (!std::isfinite(lr) || lr < 0.0) return fail(LSNF_E_ARG, "lsnf_adam_step: lr must be finite and >= 0");
+    if (!std::isfinite(eps) || eps < 0.0) return fail(LSNF_E_ARG, "lsnf_adam_step: eps must be finite and >= 0");
+    if (!std::isfinite(weight_decay) || weight_decay < 0.0) return fail(LSNF_E_ARG, "lsnf_adam_step: weight_decay must be finite and >= 0");
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(LSNF_E_ARG, "lsnf_adam_step: betas must lie in [0, 1)");
+    if (std::isnan(max_norm)) return fail(LSNF_E_ARG, "lsnf_adam_step: max_norm is NaN");
+    for (int i = 0; i < depth * LSNF_PARAMS_PER_BLOCK; ++i) {
+        if (!params_host[i] || !aligned4(params_host[i]))
+            return fail(LSNF_E_ARG, "lsnf_adam_step: parameter pointer %d (block %d, slot %d) is NULL or misaligned", i,
+                        i / LSNF_PARAMS_PER_BLOCK, i % LSNF_PARAMS_PER_BLOCK);
+        if (!aligned4(grads_host[i]))
+            return fail(LSNF_E_ARG, "lsnf_adam_step: gradient pointer %d (block %d, slot %d) is misaligned", i,
+                        i / LSNF_PARAMS_PER_BLOCK, i % LSNF_PARAMS_PER_BLOCK);
+    }
+    LsnfAdamCall c;
+    c.g = g; c.params_host = params_host; c.grads_host = grads_host; c.state = state;
+    c.lr = lr; c.beta1 = beta1; c.beta2 = beta2; c.eps = eps; c.weight_decay = weight_decay; c.max_norm = max_norm;
+    c.lr_dev = lr_dev; c.grad_norm_out = grad_norm_out; c.stream = (hipStream_t)stream;
+    hipError_t e = lsnf_launch_adam(c);
+    if (e != hipSuccess) return hip_fail(e, "lsnf_adam_step launch");
+    return LSNF_OK;
+}
+
 int lsnf_params_fast_path(void) { return l16_math() ? 1 : 0; }
 
 int lsnf_forward(const float* plan, int nz, int width, int depth, int coupling, int first_block, int n_blocks, int B,

@@ -73,6 +73,13 @@ struct LsnfInitCall {                    // lsnf_actnorm_init
     float* const* params_host = nullptr; int B = 0; const float* z_in = nullptr; void* workspace = nullptr;
     hipStream_t stream = nullptr;
 };
+struct LsnfAdamCall {                    // lsnf_adam_step
+    LsnfGeo g;
+    float* const* params_host = nullptr; const float* const* grads_host = nullptr; void* state = nullptr;
+    double lr = 0.0, beta1 = 0.0, beta2 = 0.0, eps = 0.0, weight_decay = 0.0, max_norm = 0.0;
+    const float* lr_dev = nullptr; float* grad_norm_out = nullptr;
+    hipStream_t stream = nullptr;
+};
 
 // ---- launchers and the predicates of what each takes (pure host functions, no HIP calls) ---------------------------------
 // *_covers: does the kernel take this call?  *_st: rows per workgroup / 16 of a latency kernel for this call (forward, reverse:
@@ -81,6 +88,8 @@ size_t lsnf_prep_scratch_bytes(int nz, int depth);
 hipError_t lsnf_launch_prepare(const LsnfPrepareCall& c);
 size_t lsnf_init_workspace_bytes(const LsnfGeo& g, int B);
 hipError_t lsnf_launch_actnorm_init(const LsnfInitCall& c);
+size_t lsnf_adam_bytes(const LsnfGeo& g);
+hipError_t lsnf_launch_adam(const LsnfAdamCall& c);
 
 hipError_t lsnf_launch_forward(const LsnfForwardCall& c);
 bool lsnf_forward3_covers(const LsnfForwardCall& c, int fixup);

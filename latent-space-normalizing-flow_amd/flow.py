@@ -748,3 +748,99 @@ def backward_params(plan: FlowPlan, params: Sequence[torch.Tensor], z_in: torch.
     _lib.check(rc, "lsnf_backward_params")
     out = (grads,) + ((g_in,) if want_grad_z else ()) + ((flat,) if want_flat else ())
     return out if len(out) > 1 else grads
+
+
+# ---- optimizer step of the flow (include/lsnf_flow.h lsnf_adam_step) ---------------------------------------------------
+ADAM_MAX_GROUPS, ADAM_STEP_OFFSET, ADAM_PARTIALS_OFFSET, ADAM_NORM_OFFSET, ADAM_HEADER_BYTES = 256, 0, 2048, 4096, 4160
+_adam_tables: dict = {}       # state address -> (key, params table, grads table): the ctypes arrays of the last call on that state
+
+
+def adam_state_bytes(nz: int, width: int, depth: int, coupling: int = 1) -> int:
+    """Bytes of the optimizer state of `adam_step` (0 on an unsupported geometry)."""
+    return int(_lib.load().lsnf_adam_state_bytes(int(nz), int(width), int(depth), int(coupling)))
+
+
+def new_adam_state(nz: int, width: int, depth: int, coupling: int, device) -> torch.Tensor:
+    """A fresh (all-zero) optimizer state for `adam_step`: one float32 buffer holding the header (step counters, norm
+    partials, the last norm) followed by m and v, flat in ABI tensor order (`adam_state_views`)."""
+    need = adam_state_bytes(nz, width, depth, coupling)
+    if need == 0:
+        raise LsnfError(f"unsupported geometry nz={nz} width={width} depth={depth} coupling={coupling}")
+    return torch.zeros(need // 4, dtype=torch.float32, device=device)
+
+
+def adam_state_views(state: torch.Tensor, nz: int, width: int, depth: int, coupling: int = 1):
+    """(steps, norm, m, v) as views of `state`: steps = the int64 step counters (one per workgroup of the update launch, those in
+    use all equal; steps[0] is the step count, and setting the step means filling all of them), norm = the last pre-clip norm (0-dim), m / v = lists of depth*12 tensors
+    shaped like the parameters."""
+    shapes = _param_shapes(nz, width, coupling) * depth
+    sizes = [a * b for a, b in shapes]
+    n4 = (sum(sizes) + 3) // 4 * 4
+    h = ADAM_HEADER_BYTES // 4
+    steps = state[ADAM_STEP_OFFSET // 4: ADAM_STEP_OFFSET // 4 + 2 * ADAM_MAX_GROUPS].view(torch.int64)
+    norm = state[ADAM_NORM_OFFSET // 4]
+    m = [t.view(sh) for t, sh in zip(state[h: h + sum(sizes)].split(sizes), shapes)]
+    v = [t.view(sh) for t, sh in zip(state[h + n4: h + n4 + sum(sizes)].split(sizes), shapes)]
+    return steps, norm, m, v
+
+
+def adam_step(params: Sequence[torch.Tensor], grads: Sequence[Optional[torch.Tensor]], state: torch.Tensor,
+              nz: int, width: int, depth: int, coupling: int = 1, *, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999),
+              eps: float = 1e-8, weight_decay: float = 0.0, max_norm: Optional[float] = None,
+              lr_dev: Optional[torch.Tensor] = None, want_norm: bool = False) -> Optional[torch.Tensor]:
+    """Global-norm clip + Adam on the device (`lsnf_adam_step`; train.py:413-415): updates the depth*12 tensors `params` in
+    place from `grads` (a None entry skips that tensor: parameter, m and v keep their bits, as torch treats `grad is None`)
+    and the moments in `state` (`new_adam_state`).  torch.optim.Adam's arithmetic (no amsgrad, L2 weight decay);
+    max_norm: clip the global gradient norm first (`clip_grad_norm_`'s formula), None = no clipping.  lr_dev: one float32 on
+    the device that replaces `lr` (schedules under a captured graph).  Returns the pre-clip global norm as a 0-dim view of the
+    state's norm slot when max_norm is given or want_norm is set (the norm launch runs only then), else None.
+    One or two launches on the current stream, no synchronisation, no allocation.  Plans prepared from `params` are stale
+    afterwards.  Every argument is checked before anything is launched; a bad one raises LsnfError."""
+    lib = _lib.load()
+    geo = (int(nz), int(width), int(depth), int(coupling))
+    nz, width, depth, coupling = geo
+    n = depth * LSNF_PARAMS_PER_BLOCK
+    if len(params) != n or len(grads) != n:
+        raise LsnfError(f"expected {n} parameter tensors and {n} gradients (None allowed), got {len(params)} and {len(grads)}")
+    if state is None:
+        raise LsnfError("state is required (new_adam_state())")
+    # the checks and the pointer tables are kept per state buffer, keyed by the tensors' addresses (as backward_params does):
+    # a training loop hands over the same storages every step
+    key = (geo, state.numel(), tuple(t.data_ptr() for t in params), tuple(0 if g is None else g.data_ptr() for g in grads))
+    tab = _adam_tables.get(state.data_ptr())
+    if tab is None or tab[0] != key:
+        need = lib.lsnf_adam_state_bytes(*geo)
+        if need == 0:
+            raise LsnfError(f"unsupported geometry nz={nz} width={width} depth={depth} coupling={coupling}")
+        dev = state.device
+        _check_out(state, "state", need // 4, dev, hint="from new_adam_state()")
+        if state.data_ptr() % 16:
+            raise LsnfError("state must be 16-byte aligned")
+        shapes = _param_shapes(nz, width, coupling)
+        for i, (t, g) in enumerate(zip(params, grads)):
+            name = f"param[{i}] ({BLOCK_PARAM_KEYS[i % LSNF_PARAMS_PER_BLOCK]})"
+            want = shapes[i % LSNF_PARAMS_PER_BLOCK]
+            _need_cuda(t, name)
+            if t.device != dev:
+                raise LsnfError(f"{name} lives on {t.device}, state on {dev}")
+            if t.numel() != want[0] * want[1]:
+                raise LsnfError(f"{name} has {t.numel()} elements, expected {want[0] * want[1]}")
+            if g is not None:
+                _need_cuda(g, "grad of " + name)
+                if g.device != dev:
+                    raise LsnfError(f"grad of {name} lives on {g.device}, state on {dev}")
+                if g.numel() != t.numel():
+                    raise LsnfError(f"grad of {name} has {g.numel()} elements, the parameter {t.numel()}")
+        if len(_adam_tables) >= 16:
+            _adam_tables.clear()
+        tab = _adam_tables[state.data_ptr()] = (key, (ctypes.c_void_p * n)(*key[2]), (ctypes.c_void_p * n)(*[p or None for p in key[3]]))
+    dev = state.device
+    if lr_dev is not None:
+        _check_out(lr_dev, "lr_dev", 1, dev)
+    norm = state[ADAM_NORM_OFFSET // 4] if (max_norm is not None or want_norm) else None
+    with torch.cuda.device(dev):
+        rc = lib.lsnf_adam_step(tab[1], tab[2], nz, width, depth, coupling, _ptr(state), float(lr), _ptr(lr_dev),
+                                float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+                                0.0 if max_norm is None else float(max_norm), _ptr(norm), _stream_ptr(dev))
+    _lib.check(rc, "lsnf_adam_step")
+    return norm

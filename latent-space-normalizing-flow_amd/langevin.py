@@ -119,8 +119,15 @@ def sample_langevin_post_eps_with_flow(eps, x, netG: nn.Module, netF, *, g_l_ste
 def flow_mle_step(netF, optF, z_g_k, f_max_norm: Optional[float] = None, fused: bool = False):
     """train.py:404-415: one Adam step of the flow on the Langevin-inferred z.  Returns loss_f (detached).
     fused=False restates the reference line by line (autograd through `netF(...)`); fused=True computes the same
-    loss and gradients with `netF.mle_grads` (no autograd graph, no element-wise torch launches)."""
+    loss and gradients with `netF.mle_grads` (no autograd graph, no element-wise torch launches); with a `FlowAdam` as optF it
+    runs `netF.mle_step`: the clip and the update on the device too."""
     import numpy as np
+    from .optim import FlowAdam
+    if fused and isinstance(optF, FlowAdam):       # clip + Adam on the device, the plan left current (netF.mle_step)
+        if f_max_norm is not None and optF.param_groups[0]["max_norm"] != f_max_norm:
+            raise flow.LsnfError(f"flow_mle_step: the FlowAdam owns the clip (max_norm={optF.param_groups[0]['max_norm']}); "
+                            f"f_max_norm={f_max_norm} disagrees with it")
+        return netF.mle_step(z_g_k.reshape(z_g_k.shape[0], -1), optF)
     if fused:
         optF.zero_grad(set_to_none=True)
         loss_f = netF.mle_grads(z_g_k.reshape(z_g_k.shape[0], -1), max_norm=f_max_norm,    # clip: train.py:413-414

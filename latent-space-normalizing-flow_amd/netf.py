@@ -488,3 +488,17 @@ class _netF(nn.Module):
                 continue
             p.grad = g if (p.grad is None or not accumulate) else p.grad + g
         return (stats[4] * (-1.0 / B)).to(torch.float32)
+
+    def mle_step(self, z, optimizer, reuse_buffers: bool = True):
+        """One whole flow-MLE update (train.py:404-415) without stock-PyTorch launches: `mle_grads` (no clip of its own),
+        `optimizer.step()` -- a `FlowAdam`, which owns the clip (its max_norm) -- and the prepared weights re-derived from the
+        written values into the cached plan buffer, so the next call on the module finds its plan current.  Returns loss_f
+        (of the parameters BEFORE the update) as a 0-dim device tensor; nothing synchronises."""
+        from .optim import FlowAdam
+        if not isinstance(optimizer, FlowAdam) or optimizer._netF is not self:
+            raise LsnfError("mle_step needs this module's lsnf_amd.FlowAdam; with any other optimizer use "
+                            "langevin.flow_mle_step (mle_grads + optimizer.step())")
+        loss_f = self.mle_grads(z, reuse_buffers=reuse_buffers)
+        optimizer.step()
+        self._plan()          # lsnf_prepare into the cached plan buffer; the plan key becomes the new versions
+        return loss_f
