@@ -31,6 +31,12 @@ def _stream_ptr(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else t.data_ptr()
+
+
+# ---- argument checks: the C ABI takes bare pointers, so this file is the only place that can know how large a caller's tensor
+# is.  Every tensor of every call goes through one of the rules below before anything is launched; each rule is written once.
 def _need_cuda(t: torch.Tensor, name: str):
     if not t.is_cuda:
         raise LsnfError(f"{name} must live on the GPU (got {t.device}); this library has no CPU path")
@@ -38,6 +44,38 @@ def _need_cuda(t: torch.Tensor, name: str):
         raise LsnfError(f"{name} must be float32 (got {t.dtype})")
     if not t.is_contiguous():
         raise LsnfError(f"{name} must be contiguous")
+
+
+def _anchor(t: torch.Tensor, name: str, plan: Optional["FlowPlan"], nz: Optional[int] = None) -> int:
+    """The (B, nz) tensor that defines B and the call's device, which must be the plan's (nz: for a call without a plan).
+    Returns B."""
+    _need_cuda(t, name)
+    nz = plan.nz if nz is None else nz
+    if t.dim() != 2 or t.shape[1] != nz:
+        raise LsnfError(f"{name} must be (B, {nz}), got {tuple(t.shape)}")
+    if plan is not None and plan.buf.device != t.device:
+        raise LsnfError(f"the plan lives on {plan.buf.device}, {name} on {t.device}")
+    return t.shape[0]
+
+
+def _check_in(t: Optional[torch.Tensor], name: str, n: int, device, at_least: bool = False, hint: str = ""):
+    """A tensor a kernel reads (None = an optional one left out): on the call's device, float32, contiguous, with the n elements
+    the kernel reads (at_least: a stash-like buffer, which may be larger)."""
+    if t is None:
+        return
+    if t.device != device or t.dtype != torch.float32 or not t.is_contiguous():
+        _need_cuda(t, name)
+        raise LsnfError(f"{name} lives on {t.device}, the call's tensors on {device}")
+    k = t.numel()
+    if k < n or (k > n and not at_least):
+        raise LsnfError(f"{name} has {k} elements, the kernel reads {n}" + (f" ({hint})" if hint else ""))
+
+
+def _check_like(t: Optional[torch.Tensor], name: str, anchor: torch.Tensor, anchor_name: str):
+    """A row tensor a kernel reads that must have the anchor's very shape."""
+    _check_in(t, name, anchor.numel(), anchor.device)
+    if t is not None and t.shape != anchor.shape:
+        raise LsnfError(f"{name} must have the shape of {anchor_name}")
 
 
 def _check_out(t: torch.Tensor, name: str, need: int, device, dtype=torch.float32, hint: str = ""):
@@ -52,8 +90,94 @@ def _check_out(t: torch.Tensor, name: str, need: int, device, dtype=torch.float3
         raise LsnfError(f"{name} has {t.numel()} elements, the kernel writes {need}" + (f" (allocate it {hint})" if hint else ""))
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
+_stash_sizes: dict = {}       # (nz, width, depth, B) -> (floats of act_saved, floats of the parameter-gradient workspace)
+
+
+def _stash_floats(plan: "FlowPlan", B: int) -> Tuple[int, int]:
+    """`lsnf_act_saved_floats` and `lsnf_backward_params_workspace_floats` of B rows: functions of the geometry alone, so they are
+    asked once per (geometry, B) instead of crossing ctypes in every call."""
+    key = (plan.nz, plan.width, plan.depth, B)
+    n = _stash_sizes.get(key)
+    if n is None:
+        lib = _lib.load()
+        if len(_stash_sizes) >= 1024:
+            _stash_sizes.clear()
+        n = _stash_sizes[key] = (lib.lsnf_act_saved_floats(*key), lib.lsnf_backward_params_workspace_floats(*key))
+    return n
+
+
+def _check_stash_out(plan: "FlowPlan", B: int, device, act_saved, params_ws):
+    """The two stash buffers a forward / stash-keeping reverse fills (either may be None)."""
+    if act_saved is not None:
+        _check_out(act_saved, "act_saved", _stash_floats(plan, B)[0], device, hint="from new_act_saved()")
+    if params_ws is not None:
+        _check_out(params_ws, "params_ws", _stash_floats(plan, B)[1], device, hint="from new_params_workspace()")
+
+
+def _check_stash(plan: "FlowPlan", B: int, device, z_saved, act_saved, need_act: bool):
+    """What a backward reads of the forward it belongs to: the block outputs (depth > 1) and the activation stash."""
+    if act_saved is None and need_act:
+        raise LsnfError("act_saved is required: the stash of the forward at these rows, forward(plan, x, ..., act_saved=new_act_saved(plan, B, "
+                        "device)) or reverse(..., act_saved=)")
+    if z_saved is None and plan.depth > 1 and B > 0:
+        raise LsnfError("z_saved (the block outputs of the forward) is required for depth > 1")
+    _check_in(z_saved, "z_saved", (plan.depth - 1) * B * plan.nz, device, at_least=True)
+    if act_saved is not None:
+        _check_in(act_saved, "act_saved", _stash_floats(plan, B)[0], device, at_least=True, hint="the stash of B rows, new_act_saved()")
+
+
+def _check_params(params: Sequence[torch.Tensor], nz: int, width: int, depth: int, coupling: int, device=None, on: str = "",
+                  exact_shape: bool = False):
+    """The depth*12 parameter tensors: their count, float32 / contiguous, one device (`device`, the one of `on`; None: the first
+    tensor's), and the geometry's size for each (exact_shape: the registered shape, else its element count).  Returns the device."""
+    if len(params) != depth * LSNF_PARAMS_PER_BLOCK:
+        raise LsnfError(f"expected {depth * LSNF_PARAMS_PER_BLOCK} parameter tensors, got {len(params)}")
+    shapes = _param_shapes(nz, width, coupling)
+    for i, t in enumerate(params):
+        name = f"param[{i}] ({BLOCK_PARAM_KEYS[i % LSNF_PARAMS_PER_BLOCK]})"
+        want = shapes[i % LSNF_PARAMS_PER_BLOCK]
+        _need_cuda(t, name)
+        if device is None:
+            device, on = t.device, "param[0]"
+        if t.device != device:
+            raise LsnfError(f"{name} lives on {t.device}, {on} on {device}")
+        if exact_shape and tuple(t.shape) != want:
+            raise LsnfError(f"{name} has shape {tuple(t.shape)}, expected {want}")
+        if t.numel() != want[0] * want[1]:
+            raise LsnfError(f"{name} has {t.numel()} elements, expected {want[0] * want[1]}")
+    return device
+
+
+def _param_table(params: Sequence[torch.Tensor]):
+    return (ctypes.c_void_p * len(params))(*[t.data_ptr() for t in params])
+
+
+def _plan_head(plan: "FlowPlan"):
+    """The five leading arguments every entry point that runs the stack takes."""
+    return plan.buf.data_ptr(), plan.nz, plan.width, plan.depth, plan.coupling
+
+
+def _call(name: str, device, *args, may_refuse: bool = False) -> int:
+    """The one way into a launching entry point: `name(*args, stream)` on the current stream of `device`, with that device current;
+    a refusal raises LsnfError (may_refuse: it is returned instead -- the caller has another way)."""
+    with torch.cuda.device(device):
+        rc = getattr(_lib.load(), name)(*args, torch.cuda.current_stream(device).cuda_stream)
+    if rc and not may_refuse:
+        _lib.check(rc, name)
+    return rc
+
+
+def _stream_buffers(plan: "FlowPlan", attr: str, B: int, device, make):
+    """Buffers kept on the plan between calls, one set per (batch size, device, stream): two streams sharing one plan must not
+    share them, and a stream keeps one batch size at a time."""
+    cache = plan.__dict__.setdefault(attr, {})
+    key = (B, device, torch.cuda.current_stream(device).cuda_stream)
+    bufs = cache.get(key)
+    if bufs is None:
+        for k in [k for k in cache if k[2] == key[2]]:
+            del cache[k]
+        bufs = cache[key] = make()
+    return bufs
 
 
 @dataclass
@@ -99,23 +223,17 @@ def prepare(params: Sequence[torch.Tensor], nz: int, width: int, depth: int, cou
     """params: depth*12 device tensors in BLOCK_PARAM_KEYS order per block.
     Replaces the batch-independent work the reference redoes on every call (model.py:182,193,264,349)."""
     lib = _lib.load()
-    if len(params) != depth * LSNF_PARAMS_PER_BLOCK:
-        raise LsnfError(f"expected {depth * LSNF_PARAMS_PER_BLOCK} parameter tensors, got {len(params)}")
-    half = nz // 2
-    n_out = nz if coupling == 1 else half
-    shapes = [nz, nz, nz * nz, half * width, width, width, width * width, width, width, width * n_out, n_out, n_out]
-    for i, t in enumerate(params):
-        _need_cuda(t, f"param[{i}]")
-        if t.numel() != shapes[i % LSNF_PARAMS_PER_BLOCK]:
-            raise LsnfError(f"param[{i}] ({BLOCK_PARAM_KEYS[i % 12]}) has {t.numel()} elements, "
-                            f"expected {shapes[i % 12]}")
-    dev = params[0].device
+    dev = _check_params(params, nz, width, depth, coupling)
     if plan is None:
         plan = alloc_plan(nz, width, depth, coupling, dev)
-    arr = (ctypes.c_void_p * len(params))(*[t.data_ptr() for t in params])
-    with torch.cuda.device(dev):
-        rc = lib.lsnf_prepare(arr, nz, width, depth, coupling, _ptr(plan.buf), _ptr(plan.scratch), _stream_ptr(dev))
-    _lib.check(rc, "lsnf_prepare")
+    else:       # lsnf_prepare writes what the ARGUMENTS' geometry says into the plan's buffers
+        if _plan_head(plan)[1:] != (nz, width, depth, coupling):
+            raise LsnfError(f"plan= is one of (nz, width, depth, coupling) = {_plan_head(plan)[1:]}, the call's arguments say "
+                            f"{(nz, width, depth, coupling)}")
+        _check_out(plan.buf, "plan.buf", lib.lsnf_plan_floats(nz, width, depth, coupling), dev, hint="with alloc_plan()")
+        _check_out(plan.scratch, "plan.scratch", lib.lsnf_prepare_scratch_bytes(nz, width, depth) // 8, dev, torch.float64,
+                   "with alloc_plan()")
+    _call("lsnf_prepare", dev, _param_table(params), nz, width, depth, coupling, _ptr(plan.buf), _ptr(plan.scratch))
     return plan
 
 
@@ -145,23 +263,10 @@ def actnorm_init(params: Sequence[torch.Tensor], z: torch.Tensor, nz: int, width
     need = lib.lsnf_actnorm_init_workspace_bytes(nz, width, depth, coupling, 1)
     if need == 0:
         raise LsnfError(f"unsupported geometry nz={nz} width={width} depth={depth} coupling={coupling}")
-    _need_cuda(z, "z")
-    if z.dim() != 2 or z.shape[1] != nz:
-        raise LsnfError(f"z must be (B, {nz}), got {tuple(z.shape)}")
-    B = z.shape[0]
+    B = _anchor(z, "z", None, nz)
     if B < 1:
         raise LsnfError("actnorm_init needs a non-empty batch")
-    if len(params) != depth * LSNF_PARAMS_PER_BLOCK:
-        raise LsnfError(f"expected {depth * LSNF_PARAMS_PER_BLOCK} parameter tensors, got {len(params)}")
-    shapes = _param_shapes(nz, width, coupling)
-    for i, t in enumerate(params):
-        name = f"param[{i}] ({BLOCK_PARAM_KEYS[i % LSNF_PARAMS_PER_BLOCK]})"
-        _need_cuda(t, name)
-        if t.device != z.device:
-            raise LsnfError(f"{name} lives on {t.device}, z on {z.device}")
-        want = shapes[i % LSNF_PARAMS_PER_BLOCK]
-        if tuple(t.shape) != want:
-            raise LsnfError(f"{name} has shape {tuple(t.shape)}, expected {want}")
+    _check_params(params, nz, width, depth, coupling, z.device, "z", exact_shape=True)
     need = lib.lsnf_actnorm_init_workspace_bytes(nz, width, depth, coupling, B)
     if workspace is None:
         workspace = torch.empty((need + 15) // 16 * 4, dtype=torch.float32, device=z.device)
@@ -175,10 +280,7 @@ def actnorm_init(params: Sequence[torch.Tensor], z: torch.Tensor, nz: int, width
                             f"lsnf_actnorm_init needs {need} (actnorm_init_workspace_bytes())")
         if workspace.data_ptr() % 16:
             raise LsnfError("workspace must be 16-byte aligned")
-    arr = (ctypes.c_void_p * len(params))(*[t.data_ptr() for t in params])
-    with torch.cuda.device(z.device):
-        rc = lib.lsnf_actnorm_init(arr, nz, width, depth, coupling, B, _ptr(z), _ptr(workspace), _stream_ptr(z.device))
-    _lib.check(rc, "lsnf_actnorm_init")
+    _call("lsnf_actnorm_init", z.device, _param_table(params), nz, width, depth, coupling, B, _ptr(z), _ptr(workspace))
 
 
 def params_from_state_dict(sd, depth: int, device=None) -> List[torch.Tensor]:
@@ -207,46 +309,36 @@ def forward(plan: FlowPlan, z: torch.Tensor, objective: Optional[torch.Tensor] =
     (summed inside the kernel -- no separate reduction launch).
     params_ws: optional workspace from `new_params_workspace()` (with act_saved and the block outputs): the forward also
     writes the hidden activations there, so that `backward_params(..., act_saved=, workspace=)` runs from the stash."""
-    lib = _lib.load()
-    _need_cuda(z, "z")
-    if z.dim() != 2 or z.shape[1] != plan.nz:
-        raise LsnfError(f"z must be (B, {plan.nz}), got {tuple(z.shape)}")
-    B = z.shape[0]
+    B, dev = _anchor(z, "z", plan), z.device
     n_blocks = plan.depth - first_block if n_blocks is None else n_blocks
-    if objective is not None:
-        _need_cuda(objective, "objective")
-        if objective.numel() != B:
-            raise LsnfError("objective must have B elements")
+    _check_in(objective, "objective", B, dev)
     if out is not None:
         z_out, logdet, ll = out
     else:
         z_out = torch.empty_like(z)
-        logdet = torch.empty(B, dtype=torch.float32, device=z.device)
-        ll = torch.empty(B, dtype=torch.float32, device=z.device) if want_ll else None
+        logdet = torch.empty(B, dtype=torch.float32, device=dev)
+        ll = torch.empty(B, dtype=torch.float32, device=dev) if want_ll else None
     saved = z_saved_out                     # caller-owned (n_blocks-1, B, nz) buffer for the block outputs, or
     if saved is None and save_for_backward and n_blocks > 1:
-        saved = torch.empty((n_blocks - 1, B, plan.nz), dtype=torch.float32, device=z.device)
-    # The kernels WRITE these caller-owned buffers without knowing their size (the ABI passes pointers): check them here.
-    _check_out(z_out, "out[0] (z_out)", B * plan.nz, z.device)
-    _check_out(logdet, "out[1] (logdet)", B, z.device)
+        saved = torch.empty((n_blocks - 1, B, plan.nz), dtype=torch.float32, device=dev)
+    _check_out(z_out, "out[0] (z_out)", B * plan.nz, dev)
+    _check_out(logdet, "out[1] (logdet)", B, dev)
     if ll is not None:
-        _check_out(ll, "out[2] (ll)", B, z.device)
+        _check_out(ll, "out[2] (ll)", B, dev)
     if saved is not None:
-        _check_out(saved, "z_saved", max(n_blocks - 1, 0) * B * plan.nz, z.device)
+        _check_out(saved, "z_saved", max(n_blocks - 1, 0) * B * plan.nz, dev)
     if stats is not None:               # ABI v5: 264 doubles (8 + 64 sub-accumulators of 4); the kernel writes all of them
-        _check_out(stats, "stats", STATS_DOUBLES, z.device, torch.float64, "from new_stats()")
-    if act_saved is not None:
-        _check_out(act_saved, "act_saved", lib.lsnf_act_saved_floats(plan.nz, plan.width, plan.depth, B), z.device,
-                   hint="from new_act_saved()")
-    if params_ws is not None:
-        _check_out(params_ws, "params_ws", lib.lsnf_backward_params_workspace_floats(plan.nz, plan.width, plan.depth, B), z.device,
-                   hint="from new_params_workspace()")
-    with torch.cuda.device(z.device):
-        rc = lib.lsnf_forward(_ptr(plan.buf), plan.nz, plan.width, plan.depth, plan.coupling, first_block, n_blocks, B,
-                              _ptr(z), _ptr(objective), _ptr(z_out), _ptr(logdet), _ptr(ll), _ptr(saved),
-                              _ptr(act_saved), _ptr(params_ws), _ptr(stats), _stream_ptr(z.device))
-    _lib.check(rc, "lsnf_forward")
+        _check_out(stats, "stats", STATS_DOUBLES, dev, torch.float64, "from new_stats()")
+    _check_stash_out(plan, B, dev, act_saved, params_ws)
+    args = _forward_args(plan, first_block, n_blocks, z, objective, z_out, logdet, ll, saved, act_saved, params_ws)
+    _call("lsnf_forward", dev, *args, _ptr(stats))
     return z_out, logdet, ll, saved
+
+
+def _forward_args(plan: FlowPlan, first_block: int, n_blocks: int, z, objective, z_out, logdet, ll, saved, act_saved, params_ws):
+    """The arguments of `lsnf_forward` in ABI order, up to `stats` and the stream (which vary from call to call)."""
+    return _plan_head(plan) + (first_block, n_blocks, z.shape[0], _ptr(z), _ptr(objective), _ptr(z_out), _ptr(logdet), _ptr(ll),
+                               _ptr(saved), _ptr(act_saved), _ptr(params_ws))
 
 
 class BoundForward:
@@ -265,9 +357,7 @@ class BoundForward:
         self._keep = (plan, z, out, objective, act_saved, z_saved_out)
         self._lib = _lib.load()
         self._dev = z.device
-        B = z.shape[0]
-        self._head = (_ptr(plan.buf), plan.nz, plan.width, plan.depth, plan.coupling, 0, plan.depth, B,
-                      _ptr(z), _ptr(objective), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(z_saved_out), _ptr(act_saved), None)
+        self._head = _forward_args(plan, 0, plan.depth, z, objective, out[0], out[1], out[2], z_saved_out, act_saved, None)
 
     def __call__(self, stats: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None) -> None:
         """stream: the stream to launch on (default: the current one) -- passing it saves the `with torch.cuda.stream(...)` around the call."""
@@ -304,8 +394,7 @@ def set_math_mode(mode: int) -> int:
 
 def new_act_saved(plan: "FlowPlan", B: int, device) -> torch.Tensor:
     """Uninitialised activation stash for `forward(..., act_saved=)` on a batch of B rows."""
-    n = _lib.load().lsnf_act_saved_floats(plan.nz, plan.width, plan.depth, int(B))
-    return torch.empty(max(n, 1), dtype=torch.float32, device=device)
+    return torch.empty(max(_stash_floats(plan, int(B))[0], 1), dtype=torch.float32, device=device)
 
 
 def params_fast_path() -> bool:
@@ -315,8 +404,7 @@ def params_fast_path() -> bool:
 
 def new_params_workspace(plan: "FlowPlan", B: int, device) -> torch.Tensor:
     """Uninitialised workspace of `backward_params` for a batch of B rows (also the `params_ws` of `forward`)."""
-    n = _lib.load().lsnf_backward_params_workspace_floats(plan.nz, plan.width, plan.depth, int(B))
-    return torch.empty(max(n, 4), dtype=torch.float32, device=device)
+    return torch.empty(max(_stash_floats(plan, int(B))[1], 4), dtype=torch.float32, device=device)
 
 
 STATS_DOUBLES = 264          # include/lsnf_flow.h LSNF_STATS_DOUBLES
@@ -330,21 +418,15 @@ def new_stats(device) -> torch.Tensor:
 def reverse_keep_supported(plan: FlowPlan, B: int) -> bool:
     """True if `reverse` / `sample` can keep the backward's stash for a batch of B rows (`lsnf_reverse_keep_covers`): the
     latency bf16x3 reverse, i.e. a bf16x3-family math mode and B up to the small-batch threshold in force."""
-    return bool(_lib.load().lsnf_reverse_keep_covers(plan.nz, plan.width, plan.depth, plan.coupling, int(B)))
+    return bool(_lib.load().lsnf_reverse_keep_covers(*_plan_head(plan)[1:], int(B)))
 
 
 def _keep_buffers(plan: FlowPlan, B: int, device, save_for_backward: bool, act_saved, params_ws):
     """The block-output buffer of a stash-keeping reverse / sample (or None), after the size checks of all three buffers."""
-    lib = _lib.load()
     saved = None
     if save_for_backward and plan.depth > 1:
         saved = torch.empty((plan.depth - 1, B, plan.nz), dtype=torch.float32, device=device)
-    if act_saved is not None:
-        _check_out(act_saved, "act_saved", lib.lsnf_act_saved_floats(plan.nz, plan.width, plan.depth, B), device,
-                   hint="from new_act_saved()")
-    if params_ws is not None:
-        _check_out(params_ws, "params_ws", lib.lsnf_backward_params_workspace_floats(plan.nz, plan.width, plan.depth, B), device,
-                   hint="from new_params_workspace()")
+    _check_stash_out(plan, B, device, act_saved, params_ws)
     return saved
 
 
@@ -360,38 +442,25 @@ def reverse(plan: FlowPlan, z: torch.Tensor, objective: Optional[torch.Tensor] =
     workspace=)` need no second pass over x.  The return is then (z_out, objective_out, saved).  Only where
     `reverse_keep_supported(plan, B)`; elsewhere the call raises.  z_saved_out: optional caller-owned (depth-1, B, nz) buffer for
     `saved` (implies save_for_backward)."""
-    lib = _lib.load()
-    _need_cuda(z, "z")
-    if z.dim() != 2 or z.shape[1] != plan.nz:
-        raise LsnfError(f"z must be (B, {plan.nz}), got {tuple(z.shape)}")
-    B = z.shape[0]
-    if objective is not None:
-        _need_cuda(objective, "objective")
-        if objective.numel() != B:
-            raise LsnfError("objective must have B elements")
+    B, dev = _anchor(z, "z", plan), z.device
+    _check_in(objective, "objective", B, dev)
     if out is not None:
         z_out, obj_out = out
-        _check_out(z_out, "out[0] (z_out)", B * plan.nz, z.device)
-        _check_out(obj_out, "out[1] (objective_out)", B, z.device)
+        _check_out(z_out, "out[0] (z_out)", B * plan.nz, dev)
+        _check_out(obj_out, "out[1] (objective_out)", B, dev)
     else:
         z_out = torch.empty_like(z)
-        obj_out = torch.empty(B, dtype=torch.float32, device=z.device)
+        obj_out = torch.empty(B, dtype=torch.float32, device=dev)
+    args = _plan_head(plan) + (B, _ptr(z), _ptr(objective), _ptr(z_out), _ptr(obj_out))
     if save_for_backward or act_saved is not None or params_ws is not None or z_saved_out is not None:
         if z_saved_out is not None:
-            _check_out(z_saved_out, "z_saved_out", (plan.depth - 1) * B * plan.nz, z.device)
-        saved = _keep_buffers(plan, B, z.device, save_for_backward and z_saved_out is None, act_saved, params_ws)
+            _check_out(z_saved_out, "z_saved_out", (plan.depth - 1) * B * plan.nz, dev)
+        saved = _keep_buffers(plan, B, dev, save_for_backward and z_saved_out is None, act_saved, params_ws)
         if z_saved_out is not None and plan.depth > 1:
             saved = z_saved_out
-        with torch.cuda.device(z.device):
-            rc = lib.lsnf_reverse_keep(_ptr(plan.buf), plan.nz, plan.width, plan.depth, plan.coupling, B,
-                                       _ptr(z), _ptr(objective), _ptr(z_out), _ptr(obj_out), _ptr(saved), _ptr(act_saved),
-                                       _ptr(params_ws), _stream_ptr(z.device))
-        _lib.check(rc, "lsnf_reverse_keep")
+        _call("lsnf_reverse_keep", dev, *args, _ptr(saved), _ptr(act_saved), _ptr(params_ws))
         return z_out, obj_out, saved
-    with torch.cuda.device(z.device):
-        rc = lib.lsnf_reverse(_ptr(plan.buf), plan.nz, plan.width, plan.depth, plan.coupling, B,
-                              _ptr(z), _ptr(objective), _ptr(z_out), _ptr(obj_out), _stream_ptr(z.device))
-    _lib.check(rc, "lsnf_reverse")
+    _call("lsnf_reverse", dev, *args)
     return z_out, obj_out
 
 
@@ -402,33 +471,19 @@ def backward_z(plan: FlowPlan, z_out: torch.Tensor, z_saved: Optional[torch.Tens
     ll_scale for L = ll_scale * sum_b ll_b (train.py:320: ll_scale = -1).  act_saved: the stash the forward
     filled (same batch), or None: the stash is then rebuilt from the block outputs (`lsnf_restash`, bf16 matrix pipe;
     in MATH_FP32 the fp32 backward recomputes the coupling MLP itself)."""
-    lib = _lib.load()
-    _need_cuda(z_out, "z_out")
-    B = z_out.shape[0]
+    B, dev = _anchor(z_out, "z_out", plan), z_out.device
+    _check_stash(plan, B, dev, z_saved, act_saved, False)
+    _check_in(g_z1, "g_z1", B * plan.nz, dev)
+    _check_in(g_logdet, "g_logdet", B, dev)
     if act_saved is None and B > 0 and params_fast_path():
-        # the rebuilt stash lives on the plan, one per (batch size, device, stream) -- ~1.4 KB per row, not re-allocated per call
-        # (and not inside a graph capture); if the rebuild is refused, lsnf_backward_z recomputes the MLP itself (act_saved NULL)
-        cache = plan.__dict__.setdefault("_restash_buffers", {})
-        key = (B, z_out.device, torch.cuda.current_stream(z_out.device).cuda_stream)
-        buf = cache.get(key)
-        if buf is None:
-            for k in [k for k in cache if k[2] == key[2]]:
-                del cache[k]                 # one batch size at a time per stream
-            buf = cache[key] = new_act_saved(plan, B, z_out.device)
-        with torch.cuda.device(z_out.device):
-            rc = lib.lsnf_restash(_ptr(plan.buf), plan.nz, plan.width, plan.depth, plan.coupling, B, _ptr(z_out), _ptr(z_saved),
-                                  _ptr(buf), _stream_ptr(z_out.device))
-        act_saved = buf if rc == 0 else None
-    for name, t in (("z_saved", z_saved), ("g_z1", g_z1), ("g_logdet", g_logdet), ("act_saved", act_saved)):
-        if t is not None:
-            _need_cuda(t, name)
+        # the rebuilt stash lives on the plan -- ~1.4 KB per row, not re-allocated per call (and not inside a graph capture); if the
+        # rebuild is refused, lsnf_backward_z recomputes the MLP itself (act_saved NULL)
+        buf = _stream_buffers(plan, "_restash_buffers", B, dev, lambda: new_act_saved(plan, B, dev))
+        if _call("lsnf_restash", dev, *_plan_head(plan), B, _ptr(z_out), _ptr(z_saved), _ptr(buf), may_refuse=True) == 0:
+            act_saved = buf
     g_in = torch.empty_like(z_out)
-    with torch.cuda.device(z_out.device):
-        rc = lib.lsnf_backward_z(_ptr(plan.buf), plan.nz, plan.width, plan.depth, plan.coupling, B,
-                                 _ptr(z_out), _ptr(z_saved), _ptr(act_saved), _ptr(g_z1), _ptr(g_logdet),
-                                 0 if ll_scale is None else 1, float(ll_scale or 0.0), _ptr(g_in),
-                                 _stream_ptr(z_out.device))
-    _lib.check(rc, "lsnf_backward_z")
+    _call("lsnf_backward_z", dev, *_plan_head(plan), B, _ptr(z_out), _ptr(z_saved), _ptr(act_saved), _ptr(g_z1), _ptr(g_logdet),
+          0 if ll_scale is None else 1, float(ll_scale or 0.0), _ptr(g_in))
     return g_in
 
 
@@ -441,36 +496,14 @@ def reverse_backward_z(plan: FlowPlan, z_out: torch.Tensor, z_saved: Optional[to
     filled (the forward evaluated AT x; the stash is required, from any math mode / kernel family).  out: optional (B, nz)
     buffer for the result, may be g_x itself.  One launch, asynchronous on the current stream.
     The parameter gradients of the reverse are `backward_params` of that forward with g_z1 = -result, g_logdet = -g_obj."""
-    lib = _lib.load()
-    _need_cuda(z_out, "z_out")
-    if z_out.dim() != 2 or z_out.shape[1] != plan.nz:
-        raise LsnfError(f"z_out must be (B, {plan.nz}), got {tuple(z_out.shape)}")
-    B = z_out.shape[0]
-    if act_saved is None:
-        raise LsnfError("act_saved is required: the stash of forward(plan, x, ..., act_saved=new_act_saved(plan, B, device))")
-    for name, t in (("z_saved", z_saved), ("g_x", g_x), ("g_obj", g_obj), ("act_saved", act_saved)):
-        if t is not None:
-            _need_cuda(t, name)
-            if t.device != z_out.device:
-                raise LsnfError(f"{name} lives on {t.device}, z_out on {z_out.device}")
-    if plan.depth > 1 and B > 0 and z_saved is None:
-        raise LsnfError("z_saved (the block outputs of the forward at x) is required for depth > 1")
-    if z_saved is not None and z_saved.numel() < (plan.depth - 1) * B * plan.nz:
-        raise LsnfError(f"z_saved has {z_saved.numel()} elements, expected {(plan.depth - 1) * B * plan.nz}")
-    if g_x is not None and g_x.shape != z_out.shape:
-        raise LsnfError("g_x must have the shape of z_out")
-    if g_obj is not None and g_obj.numel() != B:
-        raise LsnfError("g_obj must have B elements")
-    need = lib.lsnf_act_saved_floats(plan.nz, plan.width, plan.depth, B)
-    if act_saved.numel() < need:
-        raise LsnfError(f"act_saved has {act_saved.numel()} elements, the stash of {B} rows has {need} (new_act_saved())")
+    B, dev = _anchor(z_out, "z_out", plan), z_out.device
+    _check_stash(plan, B, dev, z_saved, act_saved, True)
+    _check_like(g_x, "g_x", z_out, "z_out")
+    _check_in(g_obj, "g_obj", B, dev)
     g_in = torch.empty_like(z_out) if out is None else out
-    _check_out(g_in, "out (g_z_in)", B * plan.nz, z_out.device)
-    with torch.cuda.device(z_out.device):
-        rc = lib.lsnf_reverse_backward_z(_ptr(plan.buf), plan.nz, plan.width, plan.depth, plan.coupling, B,
-                                         _ptr(z_out), _ptr(z_saved), _ptr(act_saved), _ptr(g_x), _ptr(g_obj), _ptr(g_in),
-                                         _stream_ptr(z_out.device))
-    _lib.check(rc, "lsnf_reverse_backward_z")
+    _check_out(g_in, "out (g_z_in)", B * plan.nz, dev)
+    _call("lsnf_reverse_backward_z", dev, *_plan_head(plan), B, _ptr(z_out), _ptr(z_saved), _ptr(act_saved), _ptr(g_x), _ptr(g_obj),
+          _ptr(g_in))
     return g_in
 
 
@@ -500,6 +533,18 @@ class PhiloxNoise:
         return _lib.LsnfRng(self.seed & mask, self.offset & mask, dev, self.row0)
 
 
+def _noise_args(noise, anchor: Optional[torch.Tensor], anchor_name: str, device):
+    """The noise argument of a call -- None, a tensor shaped like the anchor, or a `PhiloxNoise` -- as the ABI's pair
+    (noise tensor or None, LsnfRng by reference or None)."""
+    if not isinstance(noise, PhiloxNoise):
+        _check_like(noise, "noise", anchor, anchor_name)
+        return noise, None
+    od = noise.offset_dev
+    if od is not None and (od.device != device or od.dtype not in (torch.int64, torch.uint64) or od.numel() != 1):
+        raise LsnfError(f"offset_dev must be one 64-bit integer on {device}")
+    return None, ctypes.byref(noise._c())
+
+
 def sample(plan: FlowPlan, B: int, rng: PhiloxNoise, *, temperature: float = 1.0, want_eps: bool = False,
            want_ll: bool = False, out: Optional[Tuple[Optional[torch.Tensor], ...]] = None, save_for_backward: bool = False,
            act_saved: Optional[torch.Tensor] = None, params_ws: Optional[torch.Tensor] = None):
@@ -512,7 +557,6 @@ def sample(plan: FlowPlan, B: int, rng: PhiloxNoise, *, temperature: float = 1.0
     written; want_eps / want_ll then do not apply).  Every buffer is checked before anything is launched.
     save_for_backward / act_saved / params_ws: as `reverse`'s (`lsnf_sample_keep`); the return is then (x, objective_out, eps, ll,
     saved), and eps -- the last block's output, which the backward reads -- is always returned (with `out`, out[2] is required)."""
-    lib = _lib.load()
     B = int(B)
     dev = plan.device
     keep = save_for_backward or act_saved is not None or params_ws is not None
@@ -521,10 +565,8 @@ def sample(plan: FlowPlan, B: int, rng: PhiloxNoise, *, temperature: float = 1.0
         raise LsnfError("rng must be a flow.PhiloxNoise (the draw is made inside the kernel; there is no tensor form)")
     if B < 0:
         raise LsnfError(f"B must be >= 0 (got {B})")
-    if rng.offset_dev is not None:
-        od = rng.offset_dev
-        if not od.is_cuda or od.device != dev or od.dtype not in (torch.int64, torch.uint64) or od.numel() != 1:
-            raise LsnfError(f"offset_dev must be one 64-bit integer on {dev}")
+    _need_cuda(plan.buf, "plan.buf")         # there is no anchor tensor: the call's device is the plan's
+    c = _noise_args(rng, None, "", dev)[1]
     if out is not None:
         if len(out) != 4:
             raise LsnfError("out must be (x, objective_out, eps, ll); the last three may be None")
@@ -545,21 +587,14 @@ def sample(plan: FlowPlan, B: int, rng: PhiloxNoise, *, temperature: float = 1.0
             raise LsnfError("out[2] (eps) must not alias out[0] (x)")
     if ll is not None:
         _check_out(ll, "out[3] (ll)", B, dev)
-    c = rng._c()
+    args = _plan_head(plan) + (B, c, float(temperature), _ptr(x), _ptr(obj), _ptr(eps), _ptr(ll))
     if keep:
         if eps is None:
             raise LsnfError("out[2] (eps) is required with save_for_backward / act_saved / params_ws")
         saved = _keep_buffers(plan, B, dev, save_for_backward, act_saved, params_ws)
-        with torch.cuda.device(dev):
-            rc = lib.lsnf_sample_keep(_ptr(plan.buf), plan.nz, plan.width, plan.depth, plan.coupling, B, ctypes.byref(c),
-                                      float(temperature), _ptr(x), _ptr(obj), _ptr(eps), _ptr(ll), _ptr(saved), _ptr(act_saved),
-                                      _ptr(params_ws), _stream_ptr(dev))
-        _lib.check(rc, "lsnf_sample_keep")
+        _call("lsnf_sample_keep", dev, *args, _ptr(saved), _ptr(act_saved), _ptr(params_ws))
         return x, obj, eps, ll, saved
-    with torch.cuda.device(dev):
-        rc = lib.lsnf_sample(_ptr(plan.buf), plan.nz, plan.width, plan.depth, plan.coupling, B, ctypes.byref(c),
-                             float(temperature), _ptr(x), _ptr(obj), _ptr(eps), _ptr(ll), _stream_ptr(dev))
-    _lib.check(rc, "lsnf_sample")
+    _call("lsnf_sample", dev, *args)
     return x, obj, eps, ll
 
 
@@ -572,44 +607,24 @@ def langevin_step(plan: FlowPlan, z: torch.Tensor, grad_g: Optional[torch.Tensor
     z1, logdet, ll, norms: ~4 KB per row) on the plan between calls of the same batch size instead of asking the
     allocator for them every step -- the returned ll / norms are then overwritten by the next call (the K-step sampler
     consumes them at once)."""
-    lib = _lib.load()
-    _need_cuda(z, "z")
-    B = z.shape[0]
-    rng = None
-    if isinstance(noise, PhiloxNoise):
-        if noise.offset_dev is not None:
-            od = noise.offset_dev
-            if not od.is_cuda or od.dtype not in (torch.int64, torch.uint64) or od.numel() != 1:
-                raise LsnfError("offset_dev must be one 64-bit integer on the GPU")
-        rng, noise = ctypes.byref(noise._c()), None
-    for name, t in (("grad_g", grad_g), ("noise", noise)):
-        if t is not None:
-            _need_cuda(t, name)
-            if t.shape != z.shape:
-                raise LsnfError(f"{name} must have the shape of z")
-    cache = plan.__dict__.setdefault("_langevin_buffers", {}) if reuse_buffers else None
-    key = (B, z.device, torch.cuda.current_stream(z.device).cuda_stream)     # (two streams sharing one plan must not share buffers)
-    bufs = cache.get(key) if cache is not None else None
-    if bufs is None:
-        f32 = dict(dtype=torch.float32, device=z.device)
-        bufs = {"act": new_act_saved(plan, B, z.device), "out": (torch.empty_like(z), torch.empty(B, **f32), torch.empty(B, **f32)),
+    B, dev = _anchor(z, "z", plan), z.device
+    _check_like(grad_g, "grad_g", z, "z")
+    noise, rng = _noise_args(noise, z, "z", dev)
+
+    def make():
+        f32 = dict(dtype=torch.float32, device=dev)
+        return {"act": new_act_saved(plan, B, dev), "out": (torch.empty_like(z), torch.empty(B, **f32), torch.empty(B, **f32)),
                 "saved": torch.empty((plan.depth - 1, B, plan.nz), **f32) if plan.depth > 1 else None,
                 "gf": torch.empty(B, **f32), "gg": torch.empty(B, **f32)}
-        if cache is not None:
-            for k in [k for k in cache if k[2] == key[2]]:
-                del cache[k]                 # one batch size at a time per stream
-            cache[key] = bufs
+    bufs = _stream_buffers(plan, "_langevin_buffers", B, dev, make) if reuse_buffers else make()
     act, saved = bufs["act"], bufs["saved"]
+    _check_stash(plan, B, dev, saved, act, True)
     z1, logdet, ll, _ = forward(plan, z, None, want_ll=True, out=bufs["out"], act_saved=act, z_saved_out=saved)
     z_new = z if inplace else torch.empty_like(z)
     gf = bufs["gf"] if want_norms else None
     gg = bufs["gg"] if (want_norms and grad_g is not None) else None
-    with torch.cuda.device(z.device):
-        rc = lib.lsnf_langevin_step(_ptr(plan.buf), plan.nz, plan.width, plan.depth, plan.coupling, B,
-                                    _ptr(z), _ptr(z1), _ptr(saved), _ptr(act), _ptr(grad_g), _ptr(noise), rng,
-                                    float(step_size),
-                                    _ptr(z_new), _ptr(gf), _ptr(gg), _stream_ptr(z.device))
-    _lib.check(rc, "lsnf_langevin_step")
+    _call("lsnf_langevin_step", dev, *_plan_head(plan), B, _ptr(z), _ptr(z1), _ptr(saved), _ptr(act), _ptr(grad_g), _ptr(noise), rng,
+          float(step_size), _ptr(z_new), _ptr(gf), _ptr(gg))
     return z_new, ll, gf, gg
 
 
@@ -627,35 +642,10 @@ def reverse_langevin_step(plan: FlowPlan, eps: torch.Tensor, z_saved: Optional[t
     the INPUT eps (want_norms), g_eps with want_g.  inplace: eps_new is eps itself.  out: optional caller-owned
     (eps_new, g_eps, g_norm, eps_norm), each may be None (then allocated if wanted); out[1] may be grad_g.  Asynchronous on the
     current stream; nothing but the launch, so it can be captured in a graph."""
-    lib = _lib.load()
-    _need_cuda(eps, "eps")
-    if eps.dim() != 2 or eps.shape[1] != plan.nz:
-        raise LsnfError(f"eps must be (B, {plan.nz}), got {tuple(eps.shape)}")
-    B = eps.shape[0]
-    if act_saved is None:
-        raise LsnfError("act_saved is required: the stash of the forward at x = reverse(eps) (forward(..., act_saved=) or reverse(..., act_saved=))")
-    rng = None
-    if isinstance(noise, PhiloxNoise):
-        if noise.offset_dev is not None:
-            od = noise.offset_dev
-            if not od.is_cuda or od.device != eps.device or od.dtype not in (torch.int64, torch.uint64) or od.numel() != 1:
-                raise LsnfError(f"offset_dev must be one 64-bit integer on {eps.device}")
-        rng, noise = ctypes.byref(noise._c()), None
-    for name, t in (("z_saved", z_saved), ("act_saved", act_saved), ("grad_g", grad_g), ("noise", noise)):
-        if t is not None:
-            _need_cuda(t, name)
-            if t.device != eps.device:
-                raise LsnfError(f"{name} lives on {t.device}, eps on {eps.device}")
-    for name, t in (("grad_g", grad_g), ("noise", noise)):
-        if t is not None and t.shape != eps.shape:
-            raise LsnfError(f"{name} must have the shape of eps")
-    if plan.depth > 1 and B > 0 and z_saved is None:
-        raise LsnfError("z_saved (the block outputs of the forward at x) is required for depth > 1")
-    if z_saved is not None and z_saved.numel() < (plan.depth - 1) * B * plan.nz:
-        raise LsnfError(f"z_saved has {z_saved.numel()} elements, expected {(plan.depth - 1) * B * plan.nz}")
-    need = lib.lsnf_act_saved_floats(plan.nz, plan.width, plan.depth, B)
-    if act_saved.numel() < need:
-        raise LsnfError(f"act_saved has {act_saved.numel()} elements, the stash of {B} rows has {need} (new_act_saved())")
+    B, dev = _anchor(eps, "eps", plan), eps.device
+    _check_stash(plan, B, dev, z_saved, act_saved, True)
+    _check_like(grad_g, "grad_g", eps, "eps")
+    noise, rng = _noise_args(noise, eps, "eps", dev)
     eps_new = g_eps = g_norm = eps_norm = None
     if out is not None:
         if len(out) != 4:
@@ -665,7 +655,7 @@ def reverse_langevin_step(plan: FlowPlan, eps: torch.Tensor, z_saved: Optional[t
         if eps_new is not None and eps_new.data_ptr() != eps.data_ptr():
             raise LsnfError("inplace=True writes eps itself: out[0] must be None (or eps)")
         eps_new = eps
-    f32 = dict(dtype=torch.float32, device=eps.device)
+    f32 = dict(dtype=torch.float32, device=dev)
     if eps_new is None:
         eps_new = torch.empty_like(eps)
     if g_eps is None and want_g:
@@ -674,18 +664,14 @@ def reverse_langevin_step(plan: FlowPlan, eps: torch.Tensor, z_saved: Optional[t
         g_norm = torch.empty(B, **f32)
     if eps_norm is None and want_norms:
         eps_norm = torch.empty(B, **f32)
-    _check_out(eps_new, "out[0] (eps_new)", B * plan.nz, eps.device)
+    _check_out(eps_new, "out[0] (eps_new)", B * plan.nz, dev)
     if g_eps is not None:
-        _check_out(g_eps, "out[1] (g_eps)", B * plan.nz, eps.device)
+        _check_out(g_eps, "out[1] (g_eps)", B * plan.nz, dev)
     for name, t in (("out[2] (g_norm)", g_norm), ("out[3] (eps_norm)", eps_norm)):
         if t is not None:
-            _check_out(t, name, B, eps.device)
-    with torch.cuda.device(eps.device):
-        rc = lib.lsnf_reverse_langevin_step(_ptr(plan.buf), plan.nz, plan.width, plan.depth, plan.coupling, B,
-                                            _ptr(eps), _ptr(z_saved), _ptr(act_saved), _ptr(grad_g), _ptr(noise), rng,
-                                            float(step_size), _ptr(eps_new), _ptr(g_eps), _ptr(g_norm), _ptr(eps_norm),
-                                            _stream_ptr(eps.device))
-    _lib.check(rc, "lsnf_reverse_langevin_step")
+            _check_out(t, name, B, dev)
+    _call("lsnf_reverse_langevin_step", dev, *_plan_head(plan), B, _ptr(eps), _ptr(z_saved), _ptr(act_saved), _ptr(grad_g), _ptr(noise),
+          rng, float(step_size), _ptr(eps_new), _ptr(g_eps), _ptr(g_norm), _ptr(eps_norm))
     return eps_new, g_eps, g_norm, eps_norm
 
 
@@ -702,50 +688,41 @@ def backward_params(plan: FlowPlan, params: Sequence[torch.Tensor], z_in: torch.
     overwritten in place (an optimizer that consumes .grad before the next call does not notice; ~0.2 ms of host time).
     act_saved + workspace: the stash and the `params_ws` the forward of THIS evaluation was given -- the backward then runs
     from the stash on the bf16 matrix pipe instead of recomputing the coupling MLP in fp32 (`params_fast_path()`)."""
-    lib = _lib.load()
-    _need_cuda(z_in, "z_in")
-    _need_cuda(z_out, "z_out")
-    B = z_out.shape[0]
-    if len(params) != plan.depth * LSNF_PARAMS_PER_BLOCK:
-        raise LsnfError(f"expected {plan.depth * LSNF_PARAMS_PER_BLOCK} parameter tensors, got {len(params)}")
-    for name, t in (("z_saved", z_saved), ("g_z1", g_z1), ("g_logdet", g_logdet), ("act_saved", act_saved), ("workspace", workspace)):
-        if t is not None:
-            _need_cuda(t, name)
+    B, dev, head = _anchor(z_out, "z_out", plan), z_out.device, _plan_head(plan)
+    _check_in(z_in, "z_in", B * plan.nz, dev)
     if (act_saved is None) != (workspace is None):
         raise LsnfError("act_saved and workspace go together: both from the forward of this evaluation")
-    key = (tuple(p.data_ptr() for p in params), B, z_out.device, want_grad_z, torch.cuda.current_stream(z_out.device).cuda_stream)
+    _check_stash(plan, B, dev, z_saved, act_saved, False)
+    _check_in(g_z1, "g_z1", B * plan.nz, dev)
+    _check_in(g_logdet, "g_logdet", B, dev)
+    _check_in(workspace, "workspace", _stash_floats(plan, B)[1], dev, at_least=True, hint="new_params_workspace()")
+    key = (tuple(p.data_ptr() for p in params), B, dev, want_grad_z, torch.cuda.current_stream(dev).cuda_stream)
     st = plan.__dict__.get("_bp_state") if reuse_buffers else None     # (keyed by stream too: a second stream re-allocates)
     if st is None or st["key"] != key:
+        # the gradient views below are shaped like the tensors handed over and the kernels write what the geometry says: check them
+        _check_params(params, *head[1:], dev, "z_out")
         # one flat gradient buffer, handed out as views (60 separate allocations cost ~200 us of host time)
         raw = [p.detach() for p in params]
-        for i, t in enumerate(raw):
-            _need_cuda(t, f"param[{i}]")
         sizes = [t.numel() for t in raw]
-        flat = torch.empty(sum(sizes), dtype=torch.float32, device=z_out.device)
+        flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
         grads = [g.view(t.shape) for g, t in zip(flat.split(sizes), raw)]
-        nws = lib.lsnf_backward_params_workspace_floats(plan.nz, plan.width, plan.depth, B) if workspace is None else 0
+        nws = _stash_floats(plan, B)[1] if workspace is None else 0
         base, o, offs = flat.data_ptr(), 0, []
         for n in sizes:
             offs.append(base + o * 4)
             o += n
         st = {"key": key, "flat": flat, "grads": grads,
               "g_in": torch.empty_like(z_out) if want_grad_z else None,
-              "ws": torch.empty(nws, dtype=torch.float32, device=z_out.device),
-              "parr": (ctypes.c_void_p * len(raw))(*key[0]), "garr": (ctypes.c_void_p * len(raw))(*offs)}
+              "ws": torch.empty(nws, dtype=torch.float32, device=dev),
+              "parr": _param_table(raw), "garr": (ctypes.c_void_p * len(raw))(*offs)}
         if reuse_buffers:
             plan.__dict__["_bp_state"] = st
     flat, grads, g_in, ws, parr, garr = st["flat"], st["grads"], st["g_in"], st["ws"], st["parr"], st["garr"]
     if workspace is not None:
-        need = lib.lsnf_backward_params_workspace_floats(plan.nz, plan.width, plan.depth, B)
-        if workspace.numel() < need:
-            raise LsnfError(f"workspace has {workspace.numel()} floats, lsnf_backward_params needs {need}")
         ws = workspace
-    with torch.cuda.device(z_out.device):
-        rc = lib.lsnf_backward_params(_ptr(plan.buf), parr, garr, plan.nz, plan.width, plan.depth, plan.coupling, B,
-                                      _ptr(z_in), _ptr(z_out), _ptr(z_saved), _ptr(act_saved), _ptr(g_z1), _ptr(g_logdet),
-                                      0 if ll_scale is None else 1, float(ll_scale or 0.0), _ptr(g_in), _ptr(ws),
-                                      _stream_ptr(z_out.device))
-    _lib.check(rc, "lsnf_backward_params")
+    _call("lsnf_backward_params", dev, head[0], parr, garr, *head[1:], B,
+          _ptr(z_in), _ptr(z_out), _ptr(z_saved), _ptr(act_saved), _ptr(g_z1), _ptr(g_logdet),
+          0 if ll_scale is None else 1, float(ll_scale or 0.0), _ptr(g_in), _ptr(ws))
     out = (grads,) + ((g_in,) if want_grad_z else ()) + ((flat,) if want_flat else ())
     return out if len(out) > 1 else grads
 
@@ -816,21 +793,9 @@ def adam_step(params: Sequence[torch.Tensor], grads: Sequence[Optional[torch.Ten
         _check_out(state, "state", need // 4, dev, hint="from new_adam_state()")
         if state.data_ptr() % 16:
             raise LsnfError("state must be 16-byte aligned")
-        shapes = _param_shapes(nz, width, coupling)
+        _check_params(params, nz, width, depth, coupling, dev, "state")
         for i, (t, g) in enumerate(zip(params, grads)):
-            name = f"param[{i}] ({BLOCK_PARAM_KEYS[i % LSNF_PARAMS_PER_BLOCK]})"
-            want = shapes[i % LSNF_PARAMS_PER_BLOCK]
-            _need_cuda(t, name)
-            if t.device != dev:
-                raise LsnfError(f"{name} lives on {t.device}, state on {dev}")
-            if t.numel() != want[0] * want[1]:
-                raise LsnfError(f"{name} has {t.numel()} elements, expected {want[0] * want[1]}")
-            if g is not None:
-                _need_cuda(g, "grad of " + name)
-                if g.device != dev:
-                    raise LsnfError(f"grad of {name} lives on {g.device}, state on {dev}")
-                if g.numel() != t.numel():
-                    raise LsnfError(f"grad of {name} has {g.numel()} elements, the parameter {t.numel()}")
+            _check_in(g, f"grad of param[{i}] ({BLOCK_PARAM_KEYS[i % LSNF_PARAMS_PER_BLOCK]})", t.numel(), dev)
         if len(_adam_tables) >= 16:
             _adam_tables.clear()
         tab = _adam_tables[state.data_ptr()] = (key, (ctypes.c_void_p * n)(*key[2]), (ctypes.c_void_p * n)(*[p or None for p in key[3]]))
@@ -838,9 +803,6 @@ def adam_step(params: Sequence[torch.Tensor], grads: Sequence[Optional[torch.Ten
     if lr_dev is not None:
         _check_out(lr_dev, "lr_dev", 1, dev)
     norm = state[ADAM_NORM_OFFSET // 4] if (max_norm is not None or want_norm) else None
-    with torch.cuda.device(dev):
-        rc = lib.lsnf_adam_step(tab[1], tab[2], nz, width, depth, coupling, _ptr(state), float(lr), _ptr(lr_dev),
-                                float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
-                                0.0 if max_norm is None else float(max_norm), _ptr(norm), _stream_ptr(dev))
-    _lib.check(rc, "lsnf_adam_step")
+    _call("lsnf_adam_step", dev, tab[1], tab[2], nz, width, depth, coupling, _ptr(state), float(lr), _ptr(lr_dev),
+          float(betas[0]), float(betas[1]), float(eps), float(weight_decay), 0.0 if max_norm is None else float(max_norm), _ptr(norm))
     return norm

@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
-"""GPU: host cost of a call through the library's launch layer, two builds of liblsnf_flow.so against each other in one job.
+"""GPU: host cost of a call through the library's launch layer, two builds against each other in one job.
 
     python tools/host_cost_launch.py parent.so new.so [rounds=6]
+    python tools/host_cost_launch.py PARENT_CHECKOUT NEW_CHECKOUT [rounds=6]
 
-The builds alternate in fresh child processes (LSNF_LIB_PATH), the order within a pair swapped from round to round (use an
-even number of rounds: a build against a copy of itself shows the second child of a pair ~0.1-0.5 us slower).  A child times the ENQUEUE of five calls -- no synchronisation
+An argument is a build of liblsnf_flow.so (run under this checkout's Python, LSNF_LIB_PATH) or a checkout directory: the child
+then runs with that directory as its working directory -- that tree's Python layer and that tree's built library.
+The builds alternate in fresh child processes, the order within a pair swapped from round to round (use an
+even number of rounds: a build against a copy of itself shows the second child of a pair ~0.1-0.5 us slower).  A child times the ENQUEUE of eight calls -- no synchronisation
 inside a timed region, as tools/host_rate.py -- in REGIONS regions of CALLS calls each (queue drained between regions):
-  forward(B=64), forward(B=64, stash), langevin_step(B=100), sample(B=100), BoundForward(B=8192).
+  forward(B=64), forward(B=64, stash), langevin_step(B=100), sample(B=100), BoundForward(B=8192),
+  backward_z(B=100), reverse_backward_z(B=100), backward_params(B=100, reuse_buffers) -- the last three from the forward's stash.
 Per build and call: median and p10 / p90 over every region of every round, and the medians of the rounds.  The first build is
 the reference: the second one's median may exceed its median by at most the reference's own p10-p90 width; exit status 1 if
 a call does."""
@@ -16,7 +20,8 @@ import subprocess
 import sys
 
 REGIONS, CALLS = 15, 300
-NAMES = ("forward B=64", "forward B=64 +stash", "langevin_step B=100", "sample B=100", "BoundForward B=8192")
+NAMES = ("forward B=64", "forward B=64 +stash", "langevin_step B=100", "sample B=100", "BoundForward B=8192",
+         "backward_z B=100", "reverse_backward_z B=100", "backward_params B=100")
 
 CHILD = r'''
 import os, sys, time, torch
@@ -25,7 +30,8 @@ import bench, lsnf_amd
 F = lsnf_amd.flow
 REGIONS, CALLS = int(sys.argv[1]), int(sys.argv[2])
 dev = torch.device("cuda:0")
-plan = lsnf_amd.prepare([t.to(dev) for t in bench.synth_weights(1)], bench.NZ, bench.WIDTH, bench.DEPTH)
+params = [t.to(dev) for t in bench.synth_weights(1)]
+plan = lsnf_amd.prepare(params, bench.NZ, bench.WIDTH, bench.DEPTH)
 gen = torch.Generator().manual_seed(1234)
 f32 = dict(dtype=torch.float32, device=dev)
 def outs(B): return (torch.empty(B, bench.NZ, **f32), torch.empty(B, **f32), torch.empty(B, **f32))
@@ -36,12 +42,18 @@ sav64 = torch.empty((bench.DEPTH - 1, 64, bench.NZ), **f32)
 rng = F.PhiloxNoise(7)
 smp_out = (torch.empty(100, bench.NZ, **f32), torch.empty(100, **f32), None, None)
 bound = F.BoundForward(plan, z8k, o8k)
+act100, ws100 = F.new_act_saved(plan, 100, dev), F.new_params_workspace(plan, 100, dev)
+z1, _, _, sav100 = F.forward(plan, z100, save_for_backward=True, act_saved=act100, params_ws=ws100)
+gz, gld = torch.randn(100, bench.NZ, generator=gen).to(dev), torch.randn(100, generator=gen).to(dev)
 calls = (
     lambda: F.forward(plan, z64, out=o64),
     lambda: F.forward(plan, z64, out=o64, act_saved=act64, z_saved_out=sav64),
     lambda: F.langevin_step(plan, z100, None, rng, 0.1, inplace=True, reuse_buffers=True),
     lambda: F.sample(plan, 100, rng, out=smp_out),
     lambda: bound(None),
+    lambda: F.backward_z(plan, z1, sav100, gz, gld, act_saved=act100),
+    lambda: F.reverse_backward_z(plan, z1, sav100, act100, gz, gld),
+    lambda: F.backward_params(plan, params, z100, z1, sav100, gz, gld, reuse_buffers=True, act_saved=act100, workspace=ws100),
 )
 for i, fn in enumerate(calls):
     for _ in range(CALLS): fn()
@@ -64,6 +76,13 @@ def pct(xs, q):
     return xs[lo] + (xs[min(lo + 1, len(xs) - 1)] - xs[lo]) * (k - lo)
 
 
+def child_env(build):
+    """(cwd, environment) of the child that measures `build`: a checkout directory runs itself, a library runs under this checkout."""
+    if os.path.isdir(build):
+        return build, dict(os.environ, LSNF_LIB_PATH=os.path.join(build, "latent-space-normalizing-flow_amd", "liblsnf_flow.so"))
+    return None, dict(os.environ, LSNF_LIB_PATH=build)
+
+
 def main():
     libs = [os.path.abspath(p) for p in sys.argv[1:3]]
     rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 6
@@ -71,7 +90,8 @@ def main():
     round_medians = {lib: [[] for _ in NAMES] for lib in libs}
     for r in range(rounds):
         for lib in (libs if r % 2 == 0 else libs[::-1]):      # (whichever child runs second in a pair measures ~0.3 us more)
-            out = subprocess.run([sys.executable, "-c", CHILD, str(REGIONS), str(CALLS)], env=dict(os.environ, LSNF_LIB_PATH=lib),
+            cwd, env = child_env(lib)
+            out = subprocess.run([sys.executable, "-c", CHILD, str(REGIONS), str(CALLS)], cwd=cwd, env=env,
                                  capture_output=True, text=True, timeout=280)
             rows = [l.split()[1:] for l in out.stdout.splitlines() if l.startswith("REGION")]
             if out.returncode or len(rows) != len(NAMES):
@@ -81,23 +101,23 @@ def main():
                 us = [float(x) for x in row[1:]]
                 regions[lib][int(row[0])] += us
                 round_medians[lib][int(row[0])].append(statistics.median(us))
-            print(f"round {r} {os.path.basename(os.path.dirname(lib)) or lib}: done", flush=True)
+            print(f"round {r} {lib}: done", flush=True)
     print(f"\nenqueue-only host time, us per call ({rounds} rounds per build, alternating; {REGIONS} regions x {CALLS} calls per round)")
     print(f"reference: {libs[0]}\nnew:       {libs[1]}")
-    print(f"{'call':<22} {'build':<10} {'median':>8} {'p10':>8} {'p90':>8}   medians of the rounds")
+    print(f"{'call':<26} {'build':<10} {'median':>8} {'p10':>8} {'p90':>8}   medians of the rounds")
     bad = 0
     for i, name in enumerate(NAMES):
         stat = {}
         for tag, lib in zip(("reference", "new"), libs):
             xs = regions[lib][i]
             stat[tag] = (statistics.median(xs), pct(xs, 0.1), pct(xs, 0.9))
-            print(f"{name:<22} {tag:<10} {stat[tag][0]:8.2f} {stat[tag][1]:8.2f} {stat[tag][2]:8.2f}   "
+            print(f"{name:<26} {tag:<10} {stat[tag][0]:8.2f} {stat[tag][1]:8.2f} {stat[tag][2]:8.2f}   "
                   + " ".join("%.2f" % m for m in round_medians[lib][i]))
         width = stat["reference"][2] - stat["reference"][1]
         delta = stat["new"][0] - stat["reference"][0]
         ok = delta <= width
         bad += not ok
-        print(f"{'':<22} new - reference median {delta:+.2f} us; allowed +{width:.2f} (the reference's p10-p90 width): {'ok' if ok else 'SLOWER'}")
+        print(f"{'':<26} new - reference median {delta:+.2f} us; allowed +{width:.2f} (the reference's p10-p90 width): {'ok' if ok else 'SLOWER'}")
     return 1 if bad else 0
 
 
