@@ -42,6 +42,13 @@
 #define LSNF_FILLMASK 0x7f   // diagnostic builds: which phases carry their vector work (register-pressure bisection)
 #endif
 
+#ifndef LSNF_PAIR_DMA_PER_STEP
+#define LSNF_PAIR_DMA_PER_STEP 6   // CU-sharing form: LDS-DMA pieces at the head of each step of a half-phase until the wave's six are out (1, 2, 3, 6)
+#endif
+#ifndef LSNF_FWD3Q_LARGE
+#define LSNF_FWD3Q_LARGE 242   // shape code of the plain forward above 32 768 rows (lsnf_launch_forward3q): 242 or 82
+#endif
+
 namespace {
 
 struct Fwd3pArgs {
@@ -159,11 +166,15 @@ __device__ __forceinline__ f32x4v bias_quad(const float* lane_ptr, int float_off
     for (int j = 0; j < 4; ++j) r[j] = v[j];
     return r;
 }
-template <class PH> constexpr bool first_touch(int i) {       // is step i the first one on its (accumulator, ft)?
-    for (int j = 0; j < i; ++j)
-        if (PH::at(j).acc == PH::at(i).acc && PH::at(j).s == PH::at(i).s) return false;
-    return true;
-}
+template <class PH> struct FirstTouch {                       // is step i the first one on its (accumulator, ft)?
+    static constexpr bool at(int i) {
+        for (int j = 0; j < i; ++j)
+            if (PH::at(j).acc == PH::at(i).acc && PH::at(j).s == PH::at(i).s) return false;
+        return true;
+    }
+};
+template <class PH> constexpr bool first_touch(int i) { return FirstTouch<PH>::at(i); }
+template <class T> struct TypeTag { using type = T; };
 // One unit of vector work, indexed q = 0..3 in the phase tables.  ST = 2: quad q = 2*ft + st of a tile (4 values per lane).
 // ST = 1: the tile has the quads 2*ft only, and unit q = 2*ft + j is the element PAIR j of quad 2*ft -- half the work per
 // unit, under half the MFMAs per step, with the same readiness (a unit depends on the 16-feature half ft = q >> 1 only).
@@ -418,9 +429,81 @@ template <class PH> constexpr int stores_after(int last_dma_step) {
     return n;
 }
 
-template <int WT, int NWAVES, int ST, int STASH = 0>      // STASH: 0 plain, 1 block outputs + activation stash, 2 also the tiled h dump
-__global__ __launch_bounds__(64 * NWAVES, 1) void lsnf_fwd3q_kernel(const Fwd3pArgs a) {
+// ---- the CU-sharing form (PAIR): two independent 4-wave workgroups per CU, each with HALF the weight ring -------------------------
+// One workgroup per CU leaves every matrix pipe of the CU idle while its rows arrive, its stores drain and wave 0 walks the sums
+// chain; a second resident workgroup (of the same or of the next launch) computes meanwhile.  Two fit only with <= 256 VGPRs per
+// wave and <= 80 KiB of LDS per workgroup, so the ring is two 24 KiB buffers and a 16-step phase runs as two 8-step HALF-PHASES with
+// a barrier between them; buffer h holds the four 6 KiB fragments ("chunks": one n-tile x one k-tile) that half h of the phase reads.
+// Those are not contiguous in the phase's 48 KiB panel (S1a / S1b: k-tiles 0, 1 then 2, 3 of both n-tiles; S4: k-tile 0 of all four
+// tiles, then k-tile 1), and the plan is not repacked: the table below names, per half, the panel chunk behind each compact chunk.
+// The DMA of a half-phase moves compact chunk w with wave w (six 1 KiB pieces); StepDesc::frag is remapped to the compact buffer.
+struct PairMap {
+    // [0: S1a, S1b | 1: S2+S3 | 2: S4][half][compact chunk] -> chunk of the phase's panel
+    static constexpr int src(int kind, int h, int c) {
+        constexpr int T[3][2][4] = {{{0, 1, 4, 5}, {2, 3, 6, 7}}, {{0, 1, 2, 3}, {4, 5, 6, 7}}, {{0, 2, 4, 6}, {1, 3, 5, 7}}};
+        return T[kind][h][c];
+    }
+    static constexpr int kind(int j) { return j < 2 ? 0 : j - 1; }                 // phase j of a block (S1a, S1b, S2+S3, S4)
+    static constexpr unsigned packed(int kind, int h) {                            // the row as four nibbles: chunk of wave w = (packed >> 4w) & 7
+        unsigned v = 0;
+        for (int c = 0; c < 4; ++c) v |= (unsigned)src(kind, h, c) << (4 * c);
+        return v;
+    }
+    static constexpr int compact(int kind, int h, int chunk) {                     // -1: half h does not hold the chunk
+        for (int c = 0; c < 4; ++c)
+            if (src(kind, h, c) == chunk) return c;
+        return -1;
+    }
+    static constexpr bool once(int kind) {                                         // every chunk of the panel in exactly one (half, compact chunk)
+        for (int chunk = 0; chunk < 8; ++chunk) {
+            int n = 0;
+            for (int h = 0; h < 2; ++h)
+                for (int c = 0; c < 4; ++c) n += src(kind, h, c) == chunk;
+            if (n != 1) return false;
+        }
+        return true;
+    }
+};
+static_assert(PairMap::once(0) && PairMap::once(1) && PairMap::once(2), "the piece tables cover every fragment of a panel exactly once");
+// half H (steps 8H .. 8H + 7) of a phase table, reading the compact buffer
+template <class PH, int KIND, int H>
+struct HalfPh {
+    static constexpr int N = 8;
+    static constexpr int btile(int acc) { return PH::btile(acc); }
+    static constexpr StepDesc at(int i) {
+        StepDesc d = PH::at(8 * H + i);
+        d.frag = (PairMap::compact(KIND, H, d.frag / 6) * 2 + d.s) * 3;            // (frag = (chunk * 2 + s) * 3)
+        return d;
+    }
+    static constexpr int valu(int i) { return PH::valu(8 * H + i); }
+    static constexpr int stores(int i) { return PH::stores(8 * H + i); }
+    static constexpr bool resident() {                                             // every step reads a chunk its half holds
+        for (int i = 0; i < N; ++i)
+            if (PairMap::compact(KIND, H, PH::at(8 * H + i).frag / 6) < 0) return false;
+        return true;
+    }
+};
+template <class PH, int KIND, int H> struct FirstTouch<HalfPh<PH, KIND, H>> {     // (a chain begun in the first half goes on in the second)
+    static constexpr bool at(int i) { return FirstTouch<PH>::at(8 * H + i); }
+};
+static_assert(HalfPh<QhS1a, 0, 0>::resident() && HalfPh<QhS1a, 0, 1>::resident() && HalfPh<QhS1b, 0, 0>::resident() && HalfPh<QhS1b, 0, 1>::resident() &&
+              HalfPh<QhS23, 1, 0>::resident() && HalfPh<QhS23, 1, 1>::resident() && HalfPh<QhS4, 2, 0>::resident() && HalfPh<QhS4, 2, 1>::resident(),
+              "the step order of a half-phase stays inside its four fragments");
+// one 1 KiB LDS-DMA piece at a byte offset the caller formed (issue_piece of lsnf_l16.h without its wave-interleaved segment rule)
+__device__ __forceinline__ void issue_piece_at(const float* __restrict__ gsrc, float* lbuf, int kib, int lane) {
+    const char* sb = reinterpret_cast<const char*>(gsrc) + (size_t)kib * 1024u;
+    const unsigned m0v = (unsigned)(size_t)((LSNF_AS3 char*)lbuf) + (unsigned)kib * 1024u;
+    const unsigned lane_off = (unsigned)lane * 16u;
+    unsigned keep_m0;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep_m0) : "v"(lane_off), "s"(sb), "s"(m0v) : "memory");
+}
+
+// STASH: 0 plain, 1 block outputs + activation stash, 2 also the tiled h dump.  PAIR: the CU-sharing form above (plain, 4 waves x 32 rows)
+template <int WT, int NWAVES, int ST, int STASH = 0, int PAIR = 0>
+__global__ __launch_bounds__(64 * NWAVES, PAIR ? 2 : 1) void lsnf_fwd3q_kernel(const Fwd3pArgs a) {
     static_assert(!STASH || ST == 2, "the stash tile is a wave's 32 rows");
+    static_assert(!PAIR || (STASH == 0 && NWAVES == 4 && ST == 2), "the CU-sharing form: plain forward, one wave per SIMD and workgroup, 32 rows per wave");
     using TS1a = std::conditional_t<STASH != 0, QsS1a, QhS1a>;
     using TS1b = std::conditional_t<STASH != 0, QsS1b, QhS1b>;
     using TS23 = std::conditional_t<STASH == 2, QxS23, std::conditional_t<STASH != 0, QsS23, QhS23>>;
@@ -430,9 +513,12 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void lsnf_fwd3q_kernel(const Fwd3pA
     constexpr int THREADS = 64 * NWAVES;
     constexpr int HT = 2, NZT = 4, F = C::F;
     constexpr int SLOT = C::SLOT3;                             // 48 KiB
+    constexpr int HSLOT = SLOT / 2;                            // PAIR: the 24 KiB buffer of a half-phase (four fragments)
+    static_assert(HSLOT == 4 * F && (2 * HSLOT + 5 * C::CONST_FLOATS) * sizeof(float) <= 80 * 1024,
+                  "PAIR: two half-phase buffers and the constants of the five-block stack in half a CU's LDS");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* cst = smem;
-    float* const buf0 = smem + a.n_blocks * C::CONST_FLOATS;   // 2 x SLOT
+    float* const buf0 = smem + a.n_blocks * C::CONST_FLOATS;   // 2 x SLOT (PAIR: 2 x HSLOT)
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
@@ -459,6 +545,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void lsnf_fwd3q_kernel(const Fwd3pA
         asm volatile("s_waitcnt vmcnt(%0)" :: "n"(decltype(left)::value) : "memory");
         __syncthreads();
 #ifdef LSNF_FWD3Q_BURST_DMA
+        static_assert(!PAIR, "the burst-DMA timing build fills whole 48 KiB buffers: the CU-sharing form has none");
         if (k + 1 < n_phases) issue_kib<48, NWAVES>(phase_src(k + 1), buf0 + ((k + 1) & 1) * SLOT, wave, lane);
 #endif
     };
@@ -477,8 +564,48 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void lsnf_fwd3q_kernel(const Fwd3pA
     auto dma_step = [&](auto ic) {
 #ifndef LSNF_FWD3Q_BURST_DMA
         constexpr int i = decltype(ic)::value;
-        if constexpr (i % EVERY == 0 && i / EVERY < PER_WAVE) issue_piece<NWAVES>(dma_src, dma_dst, i / EVERY, wave, lane);
+        if constexpr (PAIR) {
+            // this wave's chunk: six pieces, PS at the head of a step.  A half-phase is 8 steps, half the time the 8-wave form has for
+            // a piece to land before the next barrier's vmcnt(0): measured at 65 536 rows, three streams, with the pieces over steps
+            // 0-5 / 0-2 / 0-1 / all at step 0: 84.6 / 84.7 / 84.5 / 84.3 us per step (8-wave form 87.2; profiles/fwd3q_pair_ab.txt)
+            constexpr int PS = LSNF_PAIR_DMA_PER_STEP;
+            if constexpr (i * PS < 6) {
+#pragma unroll
+                for (int s = i * PS; s < i * PS + PS && s < 6; ++s) issue_piece_at(dma_src, dma_dst, s, lane);
+            }
+        } else if constexpr (i % EVERY == 0 && i / EVERY < PER_WAVE) issue_piece<NWAVES>(dma_src, dma_dst, i / EVERY, wave, lane);
 #endif
+    };
+    // PAIR.  Half-phase (k, h) reads buffer h.  Barrier in front of it: my pieces of it have landed, everybody's have, and buffer h ^ 1
+    // is free; its steps then carry the next half-phase's pieces -- (k, 1) behind (k, 0), (k + 1, 0) behind (k, 1).  The last half-phase
+    // of the call re-fetches its own chunks into the free buffer (no DMA under a branch; the epilogue waits for it).
+    auto pair_chunk = [&](unsigned packed) { return (int)((packed >> (4 * wave)) & 7u); };       // (scalar unit: wave is uniform)
+    auto pair_arm = [&](auto jc, auto hc, int k) {                       // jc: phase of the block (0..3), hc: half about to run
+        constexpr int J = decltype(jc)::value, H = decltype(hc)::value;
+        if constexpr (H == 0) {
+            dma_src = phase_src(k) + pair_chunk(PairMap::packed(PairMap::kind(J), 1)) * F;
+            dma_dst = buf0 + HSLOT + wave * F;
+        } else {
+            const bool last = k + 1 >= n_phases;
+            dma_src = phase_src(last ? k : k + 1) + pair_chunk(last ? PairMap::packed(PairMap::kind(J), 1) : PairMap::packed(PairMap::kind((J + 1) & 3), 0)) * F;
+            dma_dst = buf0 + wave * F;
+        }
+    };
+    // one phase of the block: phase table PH, phase jc of the block, global phase index k.  Its opening barrier is the caller's.
+    auto run_phase = [&](auto ph, auto jc, int k, Tile16* acc, const float* bv, const SplitTile16* in, auto&& fill) {
+        using PH = typename decltype(ph)::type;
+        if constexpr (!PAIR) {
+            dma_arm(k);
+            run_phase16<PH, ST>(acc, bv, in, buf0 + (k & 1) * SLOT, lane, fill, dma_step);
+        } else {
+            constexpr int KIND = PairMap::kind(decltype(jc)::value);
+            pair_arm(jc, std::integral_constant<int, 0>{}, k);
+            run_phase16<HalfPh<PH, KIND, 0>, ST>(acc, bv, in, buf0, lane, fill, dma_step);
+            sync_issue(k, Left0{});
+            pair_arm(jc, std::integral_constant<int, 1>{}, k);
+            run_phase16<HalfPh<PH, KIND, 1>, ST>(acc, bv, in, buf0 + HSLOT, lane,
+                                                 [&](auto ic) { fill(std::integral_constant<int, decltype(ic)::value + 8>{}); }, dma_step);
+        }
     };
 
     const int wbase = (blockIdx.x * NWAVES + wave) * (16 * ST);
@@ -503,7 +630,11 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void lsnf_fwd3q_kernel(const Fwd3pA
         v[2] = load_tile16<HT, ST>(2, a.z_in, rows, a.nz, a.half, g, a.vec4);
         v[3] = load_tile16<HT, ST>(3, a.z_in, rows, a.nz, a.half, g, a.vec4);
         __builtin_amdgcn_sched_barrier(0);
-        issue_kib<48, NWAVES>(phase_src(0), buf0, wave, lane);
+        if constexpr (PAIR) {                       // the first half of S1a: this wave's chunk
+            const float* src0 = phase_src(0) + pair_chunk(PairMap::packed(0, 0)) * F;
+#pragma unroll
+            for (int s = 0; s < 6; ++s) issue_piece_at(src0, buf0 + wave * F, s, lane);
+        } else issue_kib<48, NWAVES>(phase_src(0), buf0, wave, lane);
         for (int i = tid; i < a.n_blocks * C::CONST_FLOATS; i += THREADS) cst[i] = a.consts[i];
 #pragma unroll
         for (int q = 0; q < 4; ++q) { split_q16<false, ST>(x0, q, xs[0]); split_q16<false, ST>(x1, q, xs[1]); }     // (not hidden: once per launch)
@@ -569,8 +700,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void lsnf_fwd3q_kernel(const Fwd3pA
         {
             const float* bv = bias_lane_ptr(cb, g);
             if (k0 > 0) sync_issue(k0, LeftS4{});
-            dma_arm(k0);
-            run_phase16<TS1a, ST>(v, bv, xs, buf0 + (k0 & 1) * SLOT, lane, [&](auto ic) {
+            run_phase(TypeTag<TS1a>{}, std::integral_constant<int, 0>{}, k0, v, bv, xs, [&](auto ic) {
                 constexpr int i = decltype(ic)::value;
                 if constexpr (STASH && i >= 8 && i < 12) stash_row_quad<HT>(rs_zp, sl, 2, i - 8, v[2], a.nz, a.half, g);   // x[2] of the previous block
                 if constexpr (i < 2) split_q16<false, ST>(v[2], 2 + i, xs[2]);                 // x[2]: k-tile 2 starts at step 8
@@ -581,19 +711,18 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void lsnf_fwd3q_kernel(const Fwd3pA
                     couple_q16<ST>(v[3], t1, p1, 2 * (i - 6)); couple_q16<ST>(v[3], t1, p1, 2 * (i - 6) + 1);
                     if constexpr (STASH) { stash_row_quad<HT>(rs_zp, sl, 3, 2 * (i - 6), v[3], a.nz, a.half, g); stash_row_quad<HT>(rs_zp, sl, 3, 2 * (i - 6) + 1, v[3], a.nz, a.half, g); }
                 } else if constexpr (i < 12) split_q16<false, ST>(v[3], i - 8, xs[3]);         // x[3]: k-tile 3 starts at step 12
-            }, dma_step);
+            });
         }
         if (blk == 1) P_STAMP(11, "s_memtime");
         // ---- S1b: v[2,3]; split v[0], v[1]: S2's input AND the next block's x[0], x[1] ----
         {
             const float* bv = bias_lane_ptr(cb, g);
             sync_issue(k0 + 1, LeftS1a{});
-            dma_arm(k0 + 1);
-            run_phase16<TS1b, ST>(v + 2, bv, xs, buf0 + ((k0 + 1) & 1) * SLOT, lane, [&](auto ic) {
+            run_phase(TypeTag<TS1b>{}, std::integral_constant<int, 1>{}, k0 + 1, v + 2, bv, xs, [&](auto ic) {
                 constexpr int i = decltype(ic)::value;
                 if constexpr (STASH && i >= 6 && i < 14) stash_row_quad<HT>(rs_zc, sl, (i - 6) >> 2, (i - 6) & 3, v[(i - 6) >> 2], a.nz, a.half, g);   // the v1 half of this block's output
                 if constexpr (i >= 8) split_q16<false, ST>(v[(i - 8) >> 2], i & 3, vh[(i - 8) >> 2]);    // (xs[0], xs[1] are dead by now: k order)
-            }, dma_step);
+            });
         }
         if (blk == 1) P_STAMP(12, "s_memtime");
         if (!more) {             // last block: the v1 half is final (model.py:422) -- its stores drain under S2..S4
@@ -619,8 +748,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void lsnf_fwd3q_kernel(const Fwd3pA
             static_assert(C::P1 == 4 && C::P2 == 2 && C::P3 == 2, "bias tile indices of the phase tables");
             const float* bv = bias_lane_ptr(cb, g);
             sync_issue(k0 + 2, LeftS1b{});
-            dma_arm(k0 + 2);
-            run_phase16<TS23, ST>(hh, bv, vh, buf0 + ((k0 + 2) & 1) * SLOT, lane, [&](auto ic) {
+            run_phase(TypeTag<TS23>{}, std::integral_constant<int, 2>{}, k0 + 2, hh, bv, vh, [&](auto ic) {
                 constexpr int i = decltype(ic)::value;
                 if constexpr (i >= 4 && i < 8) split_q16<true, ST>(hh[0], i - 4, vh[2]);      // h1[0] under h1[1]'s steps
                 if constexpr (i >= 8 && i < 12) split_q16<true, ST>(hh[1], i - 8, vh[3]);     // h1[1] under S3's k-tile 0
@@ -636,7 +764,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void lsnf_fwd3q_kernel(const Fwd3pA
                     if constexpr (i >= 8 && i < 12) stash_h_quad(rs_h1, sl, 1, i - 8, hh[1], a.width);
                     if constexpr (i >= 13) stash_h_quad(rs_h2, sl, 0, i - 13, hh[2], a.width);
                 }
-            }, dma_step);
+            });
         }
         if (blk == 1) P_STAMP(13, "s_memtime");
         xs[0] = vh[0]; xs[1] = vh[1];            // v1 is the next block's first half (model.py:422): its split is kept
@@ -649,8 +777,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void lsnf_fwd3q_kernel(const Fwd3pA
             if constexpr (STASH) mask_q16(hh[2], 3, mk2);
             if constexpr (STASH == 2) stash_h_quad(rs_h2, sl, 0, 3, hh[2], a.width);
             sync_issue(k0 + 3, LeftS23{});
-            dma_arm(k0 + 3);
-            run_phase16<TS4, ST>(tp, bv, h2s, buf0 + ((k0 + 3) & 1) * SLOT, lane, [&](auto ic) {
+            run_phase(TypeTag<TS4>{}, std::integral_constant<int, 3>{}, k0 + 3, tp, bv, h2s, [&](auto ic) {
                 constexpr int i = decltype(ic)::value;
                 if constexpr (i < 4) split_q16<true, ST>(hh[3], i, h2s[1]);                    // h2[1] under k-tile 0
                 if constexpr (STASH) {
@@ -665,7 +792,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void lsnf_fwd3q_kernel(const Fwd3pA
                 if constexpr (i == 12) couple_q16<ST>(v[2], tp[1], tp[0], 0);
                 if constexpr (i == 13) { couple_q16<ST>(v[2], tp[1], tp[0], 1); couple_q16<ST>(v[2], tp[1], tp[0], 2); couple_q16<ST>(v[2], tp[1], tp[0], 3); }
                 if constexpr (i >= 14) split_q16<false, ST>(v[2], i - 14, xs[2]);
-            }, dma_step);
+            });
             p1 = tp[2]; t1 = tp[3];              // (the rest of the coupling rides under the next block's S1a)
         }
         if (blk == 1) P_STAMP(14, "s_memtime");
@@ -730,14 +857,14 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void lsnf_fwd3q_kernel(const Fwd3pA
     P_STAMP(51, "s_memrealtime");
 }
 
-size_t fwd3q_lds(int n_blocks) {
+size_t fwd3q_lds(int n_blocks, bool pair = false) {
     using C = Fwd3pCfg<2>;
-    return ((size_t)n_blocks * C::CONST_FLOATS + 2 * (size_t)C::SLOT3) * sizeof(float);
+    return ((size_t)n_blocks * C::CONST_FLOATS + (pair ? 1 : 2) * (size_t)C::SLOT3) * sizeof(float);
 }
 
-template <int WT, int NWAVES, int ST, int STASH = 0>
+template <int WT, int NWAVES, int ST, int STASH = 0, int PAIR = 0>
 hipError_t launch_fwd3q_w(const Fwd3pArgs& a, hipStream_t stream) {
-    return lsnf_launch_kernel<lsnf_fwd3q_kernel<WT, NWAVES, ST, STASH>>(lsnf_grid(a.B, 16 * ST * NWAVES), 64 * NWAVES, fwd3q_lds(a.n_blocks), stream, a);
+    return lsnf_launch_kernel<lsnf_fwd3q_kernel<WT, NWAVES, ST, STASH, PAIR>>(lsnf_grid(a.B, 16 * ST * NWAVES), 64 * NWAVES, fwd3q_lds(a.n_blocks, PAIR), stream, a);
 }
 }  // namespace
 
@@ -766,12 +893,17 @@ hipError_t lsnf_launch_forward3q(const LsnfForwardCall& c) {
     a.panels3 = lsnf_f3b_panels_at(c);
     a.hdump = c.hdump; a.width = c.g.width;          // (the dump un-offset: lsnf_forward3q_covers demands first_block == 0 with it)
     a.stamps = lsnf_stamps_buffer();
-    // workgroup shape by batch size (one workgroup per CU; 256 CUs): 256 rows (8 waves x 32) above 32 768 rows; below, 16 rows
-    // per wave so that the grid still covers the chip -- 8 waves x 16 rows down to 16 384 rows, 4 waves x 16 rows below
-    static const char* shape = getenv("LSNF_FWD3Q_SHAPE");     // experiment knob (tools/shard_times.py): "82", "42", "81", "41"
-    const int sh = shape ? atoi(shape) : (c.B > 128 * 256 ? 82 : (c.B > 64 * 256 ? 81 : 41));
+    // workgroup shape by batch size (256 CUs).  Above 32 768 rows the plain forward runs as TWO 128-row workgroups per CU (4 waves x
+    // 32 rows each, half the weight ring: code 242) -- the stash and dump forwards as one 256-row workgroup (8 waves x 32: code 82);
+    // below, 16 rows per wave so that the grid still covers the chip -- 8 waves x 16 rows down to 16 384 rows, 4 waves x 16 rows below
+    static const char* shape = getenv("LSNF_FWD3Q_SHAPE");     // experiment knob (tools/shard_times.py): "242", "82", "42", "81", "41"
+    // (242 needs the constants of the stack beside two 24 KiB buffers in half a CU's LDS; a deeper stack stays on 82)
+    const bool pair_ok = !c.hdump && !stash && fwd3q_lds(c.n_blocks, true) <= 80 * 1024;
+    int sh = shape ? atoi(shape) : (c.B > 128 * 256 ? LSNF_FWD3Q_LARGE : (c.B > 64 * 256 ? 81 : 41));
+    if (sh == 242 && !pair_ok) sh = 82;
     if (c.hdump) return (sh == 82) ? launch_fwd3q_w<2, 8, 2, 2>(a, stream) : launch_fwd3q_w<2, 4, 2, 2>(a, stream);
     if (stash) return (sh == 82) ? launch_fwd3q_w<2, 8, 2, 1>(a, stream) : launch_fwd3q_w<2, 4, 2, 1>(a, stream);
+    if (sh == 242) return launch_fwd3q_w<2, 4, 2, 0, 1>(a, stream);
     if (sh == 82) return launch_fwd3q_w<2, 8, 2>(a, stream);
     if (sh == 42) return launch_fwd3q_w<2, 4, 2>(a, stream);
     if (sh == 81) return launch_fwd3q_w<2, 8, 1>(a, stream);
