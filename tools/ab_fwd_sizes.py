@@ -1,9 +1,12 @@
 """GPU A/B of two builds of the library on the plain forward (+ in-kernel sums) at the strong-scaling shard sizes and the full size:
-python tools/ab_fwd_sizes.py LIB_A LIB_B  (each size timed alternately, three rounds; a child process per library and round)."""
-import json, os, subprocess, sys
+python tools/ab_fwd_sizes.py LIB_A LIB_B  (each size timed alternately, three rounds; a child process per library and round;
+"LIB round R: ok" after each child, then the table)."""
+import sys
+
+import ab_harness
+
 CHILD = r'''
 import os, sys, torch
-sys.path.insert(0, os.getcwd())
 import bench, lsnf_amd
 F = lsnf_amd.flow
 dev = torch.device("cuda:0")
@@ -15,24 +18,23 @@ for B in (65536, 32768, 16384, 8192):
     st = F.new_stats(dev)
     for _ in range(600): lsnf_amd.forward(plan, z, out=outs, stats=st)
     torch.cuda.synchronize()
-    ts = []
-    for _ in range(5):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(300): lsnf_amd.forward(plan, z, out=outs, stats=st)
-        e1.record(); torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1) / 300 * 1e3)
-    res[B] = sorted(ts)[2]
-import json; print("RES" + json.dumps(res))
+    res[B] = sorted(windows(lambda: lsnf_amd.forward(plan, z, out=outs, stats=st), 300, 5))[2]
+emit(res)
 '''
-libs = sys.argv[1:3]
-acc = {l: [] for l in libs}
-for rnd in range(3):
+
+
+def main(argv=None):
+    libs = (sys.argv[1:] if argv is None else argv)[:2]
+    acc = ab_harness.run(CHILD, [(l, l, {}) for l in libs], rounds=3, timeout=280)
+    if acc is None:
+        return 1
     for l in libs:
-        out = subprocess.run([sys.executable, "-c", CHILD], env=dict(os.environ, LSNF_LIB_PATH=os.path.abspath(l)), capture_output=True, text=True).stdout
-        acc[l].append(json.loads([x for x in out.splitlines() if x.startswith("RES")][0][3:]))
-for l in libs:
-    print(l)
-    for B in ("65536", "32768", "16384", "8192"):
-        v = sorted(r[B] for r in acc[l])
-        print(f"   B={B:>6}: median {v[1]:7.2f} us  (min {v[0]:.2f}, max {v[2]:.2f})")
+        print(l)
+        for B in ("65536", "32768", "16384", "8192"):
+            v = sorted(r[B] for r in acc[l])
+            print(f"   B={B:>6}: median {v[1]:7.2f} us  (min {v[0]:.2f}, max {v[2]:.2f})")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

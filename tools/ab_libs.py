@@ -2,12 +2,12 @@
 """GPU: A/B of two builds of liblsnf_flow.so in one job (alternating child processes, LSNF_LIB_PATH): kernel-only time of the
 headline forward (and optionally other entry points) per math mode.   usage: ab_libs.py libA.so libB.so [rounds]"""
 import os
-import subprocess
 import sys
+
+import ab_harness
 
 CHILD = r'''
 import os, sys, torch
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(sys.argv[0]))) if False else os.getcwd())
 import bench, lsnf_amd
 F = lsnf_amd.flow
 dev = torch.device("cuda:0")
@@ -18,30 +18,23 @@ outs = (torch.empty_like(z), torch.empty(z.shape[0], device=dev), torch.empty(z.
 def t_us(fn, n=400):
     for _ in range(600): fn()
     torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n): fn()
-    e1.record(); torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e3
+    return windows(fn, n, 1)[0]
 res = []
 for name, mode in (("fwd3b", getattr(F, "MATH_BF16X3_PHASED", F.MATH_BF16X3)), ("fwd3q", F.MATH_BF16X3)):
     F.set_math_mode(mode)
     res.append(f"{name} {t_us(lambda: lsnf_amd.forward(plan, z, out=outs)):.2f}")
 F.set_math_mode(F.MATH_BF16X3)
-z1, ld, ll, saved = lsnf_amd.forward(plan, z, save_for_backward=True)[:4] if False else (None, None, None, None)
-print("  ".join(res), flush=True)
+emit("  ".join(res))
 '''
 
 
-def main():
-    libs = sys.argv[1:3]
-    rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 2
-    for r in range(rounds):
-        for lib in libs:
-            env = dict(os.environ, LSNF_LIB_PATH=os.path.abspath(lib))
-            out = subprocess.run([sys.executable, "-c", CHILD], env=env, capture_output=True, text=True, timeout=280)
-            line = [l for l in out.stdout.splitlines() if l.startswith("fwd3b")]
-            print(f"{os.path.basename(lib):24s} {line[0] if line else 'FAILED: ' + out.stderr[-400:]}", flush=True)
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else argv
+    rounds = int(argv[2]) if len(argv) > 2 else 2
+    res = ab_harness.run(CHILD, [(lib, lib, {}) for lib in argv[:2]], rounds, timeout=280,
+                         ok=lambda lib, r, line: f"{os.path.basename(lib):24s} {line}")
+    return 1 if res is None else 0
 
 
-main()
+if __name__ == "__main__":
+    sys.exit(main())

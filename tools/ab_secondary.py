@@ -3,12 +3,12 @@
 the stash, reverse; C3 nz=128 w=64 and C5 nz=100 w=128), alternating child processes (LSNF_LIB_PATH), each timing = median of
 9 chunks of 40 calls after a 300-launch clock ramp, buffers preallocated.   usage: ab_secondary.py lib1.so lib2.so ... [rounds]"""
 import os
-import subprocess
 import sys
+
+import ab_harness
 
 CHILD = r'''
 import os, sys, types, torch, numpy as np
-sys.path.insert(0, os.getcwd())
 import lsnf_amd
 from lsnf_amd import flow
 dev = torch.device("cuda:0")
@@ -16,14 +16,7 @@ flow.set_small_batch_max(0)
 def med(fn, chunks=9, per=40):
     for _ in range(300): fn()
     torch.cuda.synchronize()
-    r = []
-    for _ in range(chunks):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(per): fn()
-        e1.record(); torch.cuda.synchronize()
-        r.append(e0.elapsed_time(e1) / per * 1e3)
-    return sorted(r)[len(r) // 2]
+    return sorted(windows(fn, per, chunks))[chunks // 2]
 out = []
 for tag, nz, w in (("C3", 128, 64), ("C5", 100, 128)):
     hps = types.SimpleNamespace(f_n_levels=1, f_depth=5, f_flow_permutation=2, f_width=w, f_flow_coupling=1)
@@ -45,21 +38,19 @@ for tag, nz, w in (("C3", 128, 64), ("C5", 100, 128)):
     t_r = med(lambda: flow.reverse(plan, z))
     t_p = med(lambda: flow.forward(plan, z, out=outs))
     out.append(f"{tag}: fwd+stash {t_f:6.1f}  bwd(stash) {t_b:6.1f}  reverse {t_r:6.1f}  fwd {t_p:6.1f}")
-print(" | ".join(out), flush=True)
+emit(" | ".join(out))
 '''
 
 
-def main():
-    args = sys.argv[1:]
+def main(argv=None):
+    args = list(sys.argv[1:] if argv is None else argv)
     rounds = 2
     if args and args[-1].isdigit():
         rounds = int(args.pop())
-    for r in range(rounds):
-        for lib in args:
-            env = dict(os.environ, LSNF_LIB_PATH=os.path.abspath(lib))
-            o = subprocess.run([sys.executable, "-c", CHILD], env=env, capture_output=True, text=True, timeout=400)
-            line = [l for l in o.stdout.splitlines() if l.startswith("C3")]
-            print(f"{os.path.basename(lib):20s} {line[0] if line else 'FAILED: ' + o.stderr[-600:]}", flush=True)
+    res = ab_harness.run(CHILD, [(lib, lib, {}) for lib in args], rounds, timeout=400,
+                         ok=lambda lib, r, line: f"{os.path.basename(lib):20s} {line}")
+    return 1 if res is None else 0
 
 
-main()
+if __name__ == "__main__":
+    sys.exit(main())

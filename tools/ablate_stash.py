@@ -1,6 +1,11 @@
-"""GPU: time of the forward with stash at B = 65 536 for the library named by LSNF_LIB_PATH (tools/ablate_stash.sh)."""
+"""GPU: time of the forward with stash at B = 65 536 for each library given (the variants tools/ablate_stash.sh builds), one child
+process per library:   python tools/ablate_stash.py _ablate/s_0.so _ablate/s_1.so ..."""
+import sys
+
+import ab_harness
+
+CHILD = r'''
 import os, sys, torch
-sys.path.insert(0, os.getcwd())
 import bench, lsnf_amd
 F = lsnf_amd.flow
 dev = torch.device("cuda:0")
@@ -15,16 +20,20 @@ saved = torch.empty(bench.DEPTH - 1, B, bench.NZ, device=dev)
 def t_us(fn, n=300):
     for _ in range(300): fn()
     torch.cuda.synchronize()
-    ts = []
-    for _ in range(7):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(n): fn()
-        e1.record(); torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1) / n * 1e3)
-    return sorted(ts)[3]
+    return sorted(windows(fn, n, 7))[3]
 a = t_us(lambda: lsnf_amd.forward(plan, zd, out=outs))
 b = t_us(lambda: lsnf_amd.forward(plan, zd, out=outs, act_saved=act, z_saved_out=saved))
 gg = torch.randn(B, bench.NZ, device=dev); nn_ = torch.randn(B, bench.NZ, device=dev)
 c = t_us(lambda: F.langevin_step(plan, zd, gg, nn_, 0.1, reuse_buffers=True))
-print(f"{os.environ.get('LSNF_LIB_PATH', 'default')}: B={B} forward {a:6.1f} us  forward+stash {b:6.1f} us  Langevin step {c:6.1f} us", flush=True)
+emit(f"B={B} forward {a:6.1f} us  forward+stash {b:6.1f} us  Langevin step {c:6.1f} us")
+'''
+
+
+def main(argv=None):
+    libs = sys.argv[1:] if argv is None else argv
+    res = ab_harness.run(CHILD, [(lib, lib, {}) for lib in libs], timeout=120, ok=lambda lib, r, line: f"{lib}: {line}")
+    return 1 if res is None else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Timing-only builds of the stash-writing pipelined forward (wrong stash): which part of the stash costs what.
 #   tools/ablate_stash.sh   (here: builds latent-space-normalizing-flow_amd/_ablate/s_<parts>.so; parts: 1 masks, 2 sigma tiles, 4 rows)
-#   on the GPU box: for p in 0 1 2 4 7; do LSNF_LIB_PATH=latent-space-normalizing-flow_amd/_ablate/s_$p.so python tools/ablate_stash.py; done
+#   on the GPU box: python tools/ablate_stash.py latent-space-normalizing-flow_amd/_ablate/s_{0,1,2,4,7}.so
 set -e
 cd "$(dirname "$0")/../latent-space-normalizing-flow_amd/csrc"
 make -j8 >/dev/null

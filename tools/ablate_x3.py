@@ -1,6 +1,11 @@
-"""GPU: time of lsnf_backward_params at B = 65 536 (fast path) for the library named by LSNF_LIB_PATH (tools/ablate_x3.sh)."""
+"""GPU: time of lsnf_backward_params at B = 65 536 (fast path) for each library given (the variants tools/ablate_x3.sh builds), one
+child process per library:   python tools/ablate_x3.py _ablate/x3_0.so _ablate/x3_1.so ..."""
+import sys
+
+import ab_harness
+
+CHILD = r'''
 import os, sys, types
-sys.path.insert(0, os.getcwd())
 import numpy as np, torch
 import lsnf_amd
 from lsnf_amd import flow
@@ -16,11 +21,16 @@ z1, _, _, saved = flow.forward(plan, z, want_ll=False, save_for_backward=True, a
 fn = lambda: flow.backward_params(plan, params, z, z1, saved, ll_scale=-1.0 / B, reuse_buffers=True, act_saved=act, workspace=ws)
 for _ in range(20): fn()
 torch.cuda.synchronize()
-ts = []
-for _ in range(7):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(20): fn()
-    e1.record(); torch.cuda.synchronize()
-    ts.append(e0.elapsed_time(e1) / 20 * 1e3)
-print(f"{os.environ.get('LSNF_LIB_PATH', 'default')} (LSNF_TN_X3={os.environ.get('LSNF_TN_X3')}): B={B} backward_params {sorted(ts)[3]:7.1f} us", flush=True)
+ts = windows(fn, 20, 7)
+emit(f"(LSNF_TN_X3={os.environ.get('LSNF_TN_X3')}): B={B} backward_params {sorted(ts)[3]:7.1f} us")
+'''
+
+
+def main(argv=None):
+    libs = sys.argv[1:] if argv is None else argv
+    res = ab_harness.run(CHILD, [(lib, lib, {}) for lib in libs], timeout=120, ok=lambda lib, r, line: f"{lib} {line}")
+    return 1 if res is None else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Timing-only builds of the bf16x3 batch contraction (lsnf_params3.hip; wrong gradients): X3_ABL bits 1 no atomics, 2 no MFMA,
-# 4 no global loads after the first two stages, 8 no split.  GPU box: for v in 0 1 2 4 8 ...; do LSNF_LIB_PATH=.../_ablate/x3_$v.so python tools/ablate_x3.py; done
+# 4 no global loads after the first two stages, 8 no split.  GPU box: python tools/ablate_x3.py .../_ablate/x3_{0,1,2,4,8,...}.so
 set -e
 cd "$(dirname "$0")/../latent-space-normalizing-flow_amd/csrc"
 make -j8 >/dev/null

@@ -16,8 +16,9 @@ the reference: the second one's median may exceed its median by at most the refe
 a call does."""
 import os
 import statistics
-import subprocess
 import sys
+
+import ab_harness
 
 REGIONS, CALLS = 15, 300
 NAMES = ("forward B=64", "forward B=64 +stash", "langevin_step B=100", "sample B=100", "BoundForward B=8192",
@@ -25,7 +26,6 @@ NAMES = ("forward B=64", "forward B=64 +stash", "langevin_step B=100", "sample B
 
 CHILD = r'''
 import os, sys, time, torch
-sys.path.insert(0, os.getcwd())
 import bench, lsnf_amd
 F = lsnf_amd.flow
 REGIONS, CALLS = int(sys.argv[1]), int(sys.argv[2])
@@ -55,7 +55,8 @@ calls = (
     lambda: F.reverse_backward_z(plan, z1, sav100, act100, gz, gld),
     lambda: F.backward_params(plan, params, z100, z1, sav100, gz, gld, reuse_buffers=True, act_saved=act100, workspace=ws100),
 )
-for i, fn in enumerate(calls):
+res = []
+for fn in calls:
     for _ in range(CALLS): fn()
     torch.cuda.synchronize()
     us = []
@@ -65,7 +66,8 @@ for i, fn in enumerate(calls):
         t1 = time.perf_counter()
         torch.cuda.synchronize()
         us.append(1e6 * (t1 - t0) / CALLS)
-    print("REGION", i, " ".join("%.3f" % u for u in us), flush=True)
+    res.append(us)
+emit(res)
 '''
 
 
@@ -76,32 +78,18 @@ def pct(xs, q):
     return xs[lo] + (xs[min(lo + 1, len(xs) - 1)] - xs[lo]) * (k - lo)
 
 
-def child_env(build):
-    """(cwd, environment) of the child that measures `build`: a checkout directory runs itself, a library runs under this checkout."""
-    if os.path.isdir(build):
-        return build, dict(os.environ, LSNF_LIB_PATH=os.path.join(build, "latent-space-normalizing-flow_amd", "liblsnf_flow.so"))
-    return None, dict(os.environ, LSNF_LIB_PATH=build)
-
-
-def main():
-    libs = [os.path.abspath(p) for p in sys.argv[1:3]]
-    rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 6
-    regions = {lib: [[] for _ in NAMES] for lib in libs}          # every region of every round
-    round_medians = {lib: [[] for _ in NAMES] for lib in libs}
-    for r in range(rounds):
-        for lib in (libs if r % 2 == 0 else libs[::-1]):      # (whichever child runs second in a pair measures ~0.3 us more)
-            cwd, env = child_env(lib)
-            out = subprocess.run([sys.executable, "-c", CHILD, str(REGIONS), str(CALLS)], cwd=cwd, env=env,
-                                 capture_output=True, text=True, timeout=280)
-            rows = [l.split()[1:] for l in out.stdout.splitlines() if l.startswith("REGION")]
-            if out.returncode or len(rows) != len(NAMES):
-                print(f"round {r} {lib}: child failed ({out.returncode}): {out.stderr[-600:]}", flush=True)
-                return 2
-            for row in rows:
-                us = [float(x) for x in row[1:]]
-                regions[lib][int(row[0])] += us
-                round_medians[lib][int(row[0])].append(statistics.median(us))
-            print(f"round {r} {lib}: done", flush=True)
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else argv
+    libs = [os.path.abspath(p) for p in argv[:2]]
+    rounds = int(argv[2]) if len(argv) > 2 else 6
+    # the order within a pair is swapped from round to round: whichever child runs second in a pair measures ~0.3 us more
+    res = ab_harness.run(CHILD, [(lib, lib, {}) for lib in libs], rounds, [str(REGIONS), str(CALLS)], timeout=280, swap=True,
+                         ok=lambda lib, r, _: f"round {r} {lib}: done")
+    if res is None:
+        return 2
+    # per build and call: every region of every round, and the medians of the rounds
+    regions = {lib: [sum((rnd[i] for rnd in res[lib]), []) for i in range(len(NAMES))] for lib in libs}
+    round_medians = {lib: [[statistics.median(rnd[i]) for rnd in res[lib]] for i in range(len(NAMES))] for lib in libs}
     print(f"\nenqueue-only host time, us per call ({rounds} rounds per build, alternating; {REGIONS} regions x {CALLS} calls per round)")
     print(f"reference: {libs[0]}\nnew:       {libs[1]}")
     print(f"{'call':<26} {'build':<10} {'median':>8} {'p10':>8} {'p90':>8}   medians of the rounds")

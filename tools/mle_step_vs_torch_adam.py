@@ -19,20 +19,18 @@ the time between two device events around the window (it includes the launch gap
 the wall time the host needs to issue the window (before the synchronise).  Every (library, round) takes WINDOWS windows after a
 warm-up of every variant; the table gives the median with p10 / p90 over all windows (30 per build at the default 2 rounds).
 No GPU: the driver fails (there is no CPU path)."""
-import argparse
 import json
-import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import ab_harness
+from ab_harness import pct
+
 SIZES = (100, 8192)
 WINDOWS = 15
 NAMES = ("mle_grads", "mle_step", "torch fused", "torch foreach", "step graphed")
 
 CHILD = r'''
-import json, os, sys, time, types
-sys.path.insert(0, os.getcwd())
+import json, os, sys, types
 import torch
 import bench, lsnf_amd
 parent = bool(os.environ.get("MSA_PARENT"))
@@ -51,7 +49,7 @@ def make_net():
             q.copy_(t.reshape(q.shape))
     return net
 
-sizes, windows = json.loads(sys.argv[1]), int(sys.argv[2])
+sizes, nwin = json.loads(sys.argv[1]), int(sys.argv[2])
 HYPER = dict(lr=1e-4, betas=(0.5, 0.999))
 res = {}
 for B in sizes:
@@ -84,67 +82,28 @@ for B in sizes:
         for _ in range(n): fn()
     torch.cuda.synchronize()
     for name, fn in fns.items():
-        dev_us, host_us = [], []
-        for _ in range(windows):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            e0.record()
-            for _ in range(n): fn()
-            e1.record()
-            t1 = time.perf_counter()
-            torch.cuda.synchronize()
-            dev_us.append(e0.elapsed_time(e1) / n * 1e3)
-            host_us.append((t1 - t0) / n * 1e6)
-        res[f"{B}/{name}/device"] = dev_us
-        res[f"{B}/{name}/host"] = host_us
-print("MSA " + json.dumps(res), flush=True)
+        res[f"{B}/{name}/device"], res[f"{B}/{name}/host"] = windows(fn, n, nwin, host=True)
+emit(res)
 '''
 
 
-def pct(v, q):
-    v = sorted(v)
-    return v[min(len(v) - 1, max(0, int(round(q * (len(v) - 1)))))]
-
-
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--parent-lib", default=None)
-    ap.add_argument("--rounds", type=int, default=2)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    libs = [("this", None)] + ([("parent", os.path.abspath(a.parent_lib))] if a.parent_lib else [])
-    acc = {}
-    for r in range(a.rounds):
-        for tag, path in libs:
-            env = dict(os.environ)
-            if path:
-                env.update(LSNF_LIB_PATH=path, MSA_PARENT="1")
-            out = subprocess.run([sys.executable, "-c", CHILD, json.dumps(SIZES), str(WINDOWS)], env=env, cwd=ROOT,
-                                 capture_output=True, text=True, timeout=400)
-            line = [l for l in out.stdout.splitlines() if l.startswith("MSA ")]
-            if out.returncode != 0 or not line:
-                print(f"{tag} round {r}: FAILED (exit {out.returncode})\n{out.stderr[-2000:]}", flush=True)
-                return 1                              # nothing more is started after a failure
-            for k, ts in json.loads(line[0][4:]).items():
-                acc.setdefault((tag, k), []).extend(ts)
-            print(f"{tag} round {r}: ok", flush=True)
+def main(argv=None):
+    a, libs = ab_harness.parent_lib_args(__doc__, 2, "MSA_PARENT", argv)
+    res = ab_harness.run(CHILD, libs, a.rounds, [json.dumps(SIZES), str(WINDOWS)], timeout=400)
+    if res is None:
+        return 1
+    acc = ab_harness.pooled(res)
     rows = [f"# tools/mle_step_vs_torch_adam.py: us per call, median [p10, p90] over {a.rounds} x {WINDOWS} windows per library; "
             f"nz=128 w=64 depth=5, default math mode and dispatch",
             f"{'B':>7} {'what':<16} {'build':<7} {'clock':<7} {'median':>9} {'p10':>9} {'p90':>9}"]
     for B in SIZES:
         for name in NAMES:
-            for tag, _ in libs:
+            for tag, _, _ in libs:
                 for clock in ("device", "host"):
                     ts = acc.get((tag, f"{B}/{name}/{clock}"))
                     if ts:
                         rows.append(f"{B:>7} {name:<16} {tag:<7} {clock:<7} {pct(ts, 0.5):>9.2f} {pct(ts, 0.1):>9.2f} {pct(ts, 0.9):>9.2f}")
-    text = "\n".join(rows) + "\n"
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text)
+    ab_harness.finish(rows, a.out)
     return 0
 
 

@@ -16,20 +16,18 @@ processes that alternate between the two libraries (LSNF_LIB_PATH), `rounds` tim
 of back-to-back calls between two device events (so it includes the launch gaps a caller sees, not only kernel time); every
 (library, round) takes WINDOWS windows after a warm-up of every shape; the table gives the median with p10 / p90 over all windows
 (30 per build at the default 2 rounds).  No GPU: the driver fails (there is no CPU path)."""
-import argparse
 import json
-import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import ab_harness
+from ab_harness import pct
+
 SIZES = (100, 8192, 16384)
 WINDOWS = 15
 NAMES = ("reverse", "reverse_keep", "reverse_keep+ws", "reverse+forward", "reverse+forward+ws", "d_eps bridge", "d_eps keeps_stash")
 
 CHILD = r'''
 import json, os, sys, types
-sys.path.insert(0, os.getcwd())
 import torch
 import bench, lsnf_amd
 parent = bool(os.environ.get("RKF_PARENT"))
@@ -48,7 +46,7 @@ with torch.no_grad():
         q.copy_(t.reshape(q.shape))
 for q in net.parameters():
     q.requires_grad_(False)                                    # d eps alone: no parameter-gradient workspace on either path
-sizes, windows = json.loads(sys.argv[1]), int(sys.argv[2])
+sizes, nwin = json.loads(sys.argv[1]), int(sys.argv[2])
 res = {}
 for B in sizes:
     f32 = dict(dtype=torch.float32, device=dev)
@@ -86,59 +84,26 @@ for B in sizes:
         for _ in range(n): fn()
     torch.cuda.synchronize()
     for name, fn in fns.items():
-        ts = []
-        for _ in range(windows):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(n): fn()
-            e1.record(); torch.cuda.synchronize()
-            ts.append(e0.elapsed_time(e1) / n * 1e3)
-        res[f"{B}/{name}"] = ts
-print("RKF " + json.dumps(res), flush=True)
+        res[f"{B}/{name}"] = windows(fn, n, nwin)
+emit(res)
 '''
 
 
-def pct(v, q):
-    v = sorted(v)
-    return v[min(len(v) - 1, max(0, int(round(q * (len(v) - 1)))))]
-
-
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--parent-lib", default=None)
-    ap.add_argument("--rounds", type=int, default=2)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    libs = [("this", None)] + ([("parent", os.path.abspath(a.parent_lib))] if a.parent_lib else [])
-    acc = {}
-    for r in range(a.rounds):
-        for tag, path in libs:
-            env = dict(os.environ)
-            if path:
-                env.update(LSNF_LIB_PATH=path, RKF_PARENT="1")
-            out = subprocess.run([sys.executable, "-c", CHILD, json.dumps(SIZES), str(WINDOWS)], env=env, cwd=ROOT,
-                                 capture_output=True, text=True, timeout=400)
-            line = [l for l in out.stdout.splitlines() if l.startswith("RKF ")]
-            if out.returncode != 0 or not line:
-                print(f"{tag} round {r}: FAILED (exit {out.returncode})\n{out.stderr[-2000:]}", flush=True)
-                return 1                              # nothing more is started after a failure
-            for k, ts in json.loads(line[0][4:]).items():
-                acc.setdefault((tag, k), []).extend(ts)
-            print(f"{tag} round {r}: ok", flush=True)
+def main(argv=None):
+    a, libs = ab_harness.parent_lib_args(__doc__, 2, "RKF_PARENT", argv)
+    res = ab_harness.run(CHILD, libs, a.rounds, [json.dumps(SIZES), str(WINDOWS)], timeout=400)
+    if res is None:
+        return 1
+    acc = ab_harness.pooled(res)
     rows = [f"# tools/reverse_keep_vs_forward.py: us per call, median [p10, p90] over {a.rounds} x {WINDOWS} windows per library; "
             f"nz=128 w=64 depth=5, default math mode and dispatch", f"{'B':>7} {'what':<20} {'build':<7} {'median':>9} {'p10':>9} {'p90':>9}"]
     for B in SIZES:
         for name in NAMES:
-            for tag, _ in libs:
+            for tag, _, _ in libs:
                 ts = acc.get((tag, f"{B}/{name}"))
                 if ts:
                     rows.append(f"{B:>7} {name:<20} {tag:<7} {pct(ts, 0.5):>9.2f} {pct(ts, 0.1):>9.2f} {pct(ts, 0.9):>9.2f}")
-    text = "\n".join(rows) + "\n"
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text)
+    ab_harness.finish(rows, a.out)
     return 0
 
 
