@@ -353,8 +353,9 @@ int lsnf_reverse_langevin_step(const float* plan, int nz, int width, int depth, 
  *                 matrix pipe and the large-batch kernels write their arrays tiled); pass the forward's own z_in / z_out / z_saved.
  *                 Where the dump may be tiled (see params_workspace under lsnf_forward) the fast path refuses z tensors that are
  *                 not 16-byte aligned with LSNF_E_ARG, as that forward does: the two calls then always agree on the dump's form.
- * Sums over the batch use fp32 atomics when B > 1024 (order, hence last bits, may vary run to run:
- * tests/test_gpu_module.py bounds the spread at B = 65 536 to 2e-6 of each tensor's norm). */
+ * Sums over the batch use fp32 atomics above 128 rows, and G = sum_b dL/dlogdet_b float64 atomics above one workgroup of rows
+ * (order, hence last bits, may vary run to run: tests/test_gpu_module.py bounds the spread at B = 65 536 to 2e-6 of each
+ * tensor's norm).  lsnf_backward_params_det below is the same call with every sum over the batch in a fixed order. */
 size_t lsnf_backward_params_workspace_floats(int nz, int width, int depth, int B);
 /* 1 if the math mode in force offers the from-the-stash fast path of lsnf_backward_params (every bf16x3-family mode) */
 int lsnf_params_fast_path(void);
@@ -363,6 +364,39 @@ int lsnf_backward_params(const float* plan, const float* const* params_host, flo
                          const float* z_in, const float* z_out, const float* z_saved, const float* act_saved,
                          const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
                          float* g_z_in, float* workspace, void* stream);
+
+/* ---- bit-reproducible parameter gradients: lsnf_backward_params with a fixed-order batch contraction ----
+ * Same arguments, same selection of the backward and contraction kernels, same fast path / recomputing path and the same
+ * alignment rules as lsnf_backward_params, no atomics in any result: every workgroup of the batch contraction stores its
+ * partial matrices and column sums into its own slot of a partials area, one further launch (lsnf_fold_reduce_kernel) adds
+ * the slots in chunk order in float64 and rounds once, and G is summed over the batch in float64 in a fixed tree.  The
+ * chunking follows from (B, depth, contraction kind) alone -- not from the device's CU count, the stream or the environment
+ * (LSNF_TN_CHUNK is ignored): at most 128 chunks for the fp32-MFMA contractions (128 rows per chunk below 16 384 rows, 512
+ * from there, more once that would exceed 128 chunks), 256 / depth chunks for the bf16 contraction (from 12 288 rows).
+ * Guarantee: the same build, inputs, math mode and small-batch threshold give the same bits in every gradient tensor and in
+ * g_z_in -- on any stream, inside or outside a captured graph, on any gfx950 device.  "Inputs" includes what selects the
+ * contraction kind, since the kind sets the chunking and the arithmetic: whether act_saved is given, the alignment of z_in /
+ * z_out / z_saved / g_z1 / g_z_in (16-byte aligned tensors take the bf16 contraction from 12 288 rows and the widest row loads
+ * below; others the narrower fp32 forms), and the process-wide experiment knobs LSNF_TN_X3 / LSNF_TN_PLAIN, which this entry
+ * point honours as lsnf_backward_params does (read once per process: leave them unset, or set them alike in every run).  The bits are NOT claimed equal to
+ * lsnf_backward_params' (another summation order; both are within the same distance of the float64 gradients), nor equal
+ * across batch shardings or math modes.
+ *   workspace : lsnf_backward_params_det_workspace_floats() floats, 16-byte aligned: lsnf_backward_params_workspace_floats()
+ *               rounded up to 16 bytes, plus the partials area behind it -- chunks(B, depth) * depth * F floats, F = the
+ *               folded gradients of one block (nz*nz + nz + (nz/2 + width + nz) * width + 2*width + nz, rounded up to 4).
+ *               nz 128 / width 64 / depth 5: 663 040 bytes per chunk -- 1 chunk at B = 100, 64 at 8 192, 128 (84.9 MB, on
+ *               top of the 671 MB of the dump) at 65 536.  The part before the partials is lsnf_backward_params' own layout:
+ *               lsnf_forward / lsnf_reverse_keep take the same pointer as `params_workspace`, and the buffer is also
+ *               valid for lsnf_backward_params.
+ * Stream-ordered (memset of the 16-byte header, backward, contraction, reduce, unfold: a straight line of launches),
+ * allocates nothing, capturable.  Errors as lsnf_backward_params.  Added without an ABI bump (new symbols; nothing existing
+ * changed). */
+size_t lsnf_backward_params_det_workspace_floats(int nz, int width, int depth, int B);
+int lsnf_backward_params_det(const float* plan, const float* const* params_host, float* const* grads_host,
+                             int nz, int width, int depth, int coupling, int B,
+                             const float* z_in, const float* z_out, const float* z_saved, const float* act_saved,
+                             const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
+                             float* g_z_in, float* workspace, void* stream);
 
 /* ---- optimizer step of the flow: replaces `clip_grad_norm_` + `optF.step()` (train.py:413-415, optimizer train.py:295) ----
  * Global-norm clip and torch.optim.Adam (non-amsgrad, maximize=False, L2 weight decay; definition: PyTorch's

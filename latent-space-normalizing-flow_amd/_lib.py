@@ -61,6 +61,11 @@ _SIGNATURES = {
                                      c_int, c_int, c_int, c_int, c_int,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
                                      c_void_p, c_void_p, c_void_p]),
+    "lsnf_backward_params_det_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "lsnf_backward_params_det": (c_int, [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
+                                         c_int, c_int, c_int, c_int, c_int,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
+                                         c_void_p, c_void_p, c_void_p]),
     "lsnf_adam_state_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "lsnf_adam_step": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_void_p,
                                c_double, c_void_p, c_double, c_double, c_double, c_double, c_double, c_void_p, c_void_p]),

@@ -337,6 +337,69 @@ bool dump_may_tile(const LsnfGeo& g, int B, int small_max) {
     return B > small_max && (math == LSNF_MATH_BF16X3 || math == LSNF_MATH_BF16X3_PHASED) && lsnf_dump_can_tile(g.nz, g.width) &&
            lsnf_contract_x3_covers(any);
 }
+// lsnf_backward_params (det = 0) and lsnf_backward_params_det (det = 1): one validation, one selection, one set of alignment rules
+int backward_params_entry(const char* entry, int det, const float* plan, const float* const* params_host, float* const* grads_host, int nz, int width,
+                          int depth, int coupling, int B, const float* z_in, const float* z_out, const float* z_saved,
+                          const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
+                          float* g_z_in, float* workspace, void* stream) {
+    LsnfGeo g;
+    if (int rc = geo_or_fail(&g, nz, width, depth, coupling)) return rc;
+    if (B < 1 || B > (1 << 28)) return fail(LSNF_E_ARG, "%s: B=%d out of range", entry, B);
+    if (!plan || !params_host || !grads_host || !z_in || !z_out || !workspace || (depth > 1 && !z_saved))
+        return fail(LSNF_E_ARG, "%s: NULL argument", entry);
+    if (!aligned16(plan) || !aligned16(workspace)) return fail(LSNF_E_ARG, "%s: plan/workspace must be 16-byte aligned", entry);
+    for (int i = 0; i < depth * LSNF_PARAMS_PER_BLOCK; ++i) {
+        if (!params_host[i] || !aligned4(params_host[i]) || !aligned4(grads_host[i]))
+            return fail(LSNF_E_ARG, "%s: parameter/gradient pointer %d is NULL or misaligned", entry, i);
+    }
+    if (!aligned4(z_in) || !aligned4(z_out) || !aligned4(z_saved) || !aligned4(g_z1) || !aligned4(g_logdet) || !aligned4(g_z_in))
+        return fail(LSNF_E_ARG, "%s: tensors must be 4-byte aligned", entry);
+    // (z_in too: the batch contraction of block 0 reads its rows with the same vector width)
+    const int vec4 = row_vector_width(g, {z_in, z_out, g_z_in, z_saved, g_z1});
+    if (act_saved && !aligned16(act_saved)) return fail(LSNF_E_ARG, "%s: act_saved must be 16-byte aligned", entry);
+    // Fast path (act_saved given, bf16x3-family math): the forward of this evaluation kept the activation stash and wrote h1 / h2
+    // into this workspace's dump (lsnf_forward(params_workspace)); the backward FROM THE STASH, on the bf16 matrix pipe, adds
+    // g_v, g_a1, g_a2, g_t, g_p -- no recomputation of the coupling MLP (1.0x instead of 1.5x the forward's matrix work, at
+    // 2.6x the matrix rate).  Otherwise: the recomputing fp32-MFMA backward writes all seven tensors itself.
+    // Large batches on the fast path: the contraction runs on the bf16 matrix pipe, operands read once (lsnf_params3.hip;
+    // LSNF_TN_X3=0 keeps the fp32-MFMA kernels), and the throughput backward then writes its g arrays in the tiled form (whole
+    // 1 KiB stores instead of 16 rows x 64 bytes; g_v as its first half only: the second half is g_t)
+    if (!l16_math()) act_saved = nullptr;
+    if (act_saved && dump_may_tile(g, B, small_batch_max()) && !(aligned16(z_in) && aligned16(z_out) && aligned16(z_saved)))
+        return fail(LSNF_E_ARG, "%s: with act_saved at B=%d, z_in / z_out / z_saved must be 16-byte aligned", entry, B);
+    const hipStream_t st = (hipStream_t)stream;
+    // workspace: G = sum_b dL/dlogdet_b (one double in floats 0-1: in float32 the per-wave atomics lost up to ~1e-5 of it, and
+    // G * 3 / G * W^-T cancel against the data terms of the actnorm.logs / 1x1-conv gradients), the folded gradients (zeroed:
+    // both accumulate by atomics), then the dump the backward writes
+    const size_t folded = 4 + (size_t)depth * lsnf_fold_layout(nz, width).per_block;
+    LsnfBackwardCall b;
+    b.g = g; b.plan = plan; b.B = B; b.vec4 = vec4; b.stream = st;
+    b.z_out = z_out; b.z_saved = z_saved; b.act_saved = act_saved; b.g_z1 = g_z1; b.g_logdet = g_logdet;
+    b.ll_mode = ll_mode; b.ll_scale = ll_scale; b.g_z_in = g_z_in;
+    // (det: G is summed in a fixed order by lsnf_fold_reduce_kernel; the kernels' atomic sum goes to the spare floats 2-3)
+    b.dump = workspace + folded; b.gl_total = reinterpret_cast<double*>(workspace + (det ? 2 : 0));
+    LsnfContractCall c;
+    c.g = g; c.plan = plan; c.B = B; c.vec4 = vec4; c.stream = st;
+    c.params_host = params_host; c.grads_host = grads_host; c.z_in = z_in; c.z_out = z_out; c.z_saved = z_saved; c.workspace = workspace;
+    c.det = det; c.g_logdet = g_logdet; c.ll_mode = ll_mode; c.ll_scale = ll_scale;
+    const Pick p = select_backward(b);
+    const bool use_x3 = act_saved && lsnf_contract_x3_covers(c);
+    const int contraction = select_contraction(g, B, use_x3, vec4);
+    b.dump_tiled = c.g_tiled = (use_x3 && p.k == K_BWD3 && lsnf_dump_can_tile(nz, width)) ? 1 : 0;
+    if (p.k == K_NONE) return launch_fail(hipSuccess, entry, p.k);
+    // (det: the reduce kernel writes every element of the fold; only the header is accumulated into)
+    hipError_t e = hipMemsetAsync(workspace, 0, sizeof(float) * (det ? 4 : folded), st);
+    if (e != hipSuccess) return hip_fail(e, det ? "lsnf_backward_params_det: hipMemsetAsync(workspace)" : "lsnf_backward_params: hipMemsetAsync(workspace)");
+    e = launch_backward(p, b);
+    if (e != hipSuccess) return launch_fail(e, entry, p.k);
+    e = lsnf_launch_params_contract(c, contraction);
+    if (e != hipSuccess)
+        return hip_fail(e, det ? "lsnf_backward_params_det: contraction / lsnf_fold_reduce_kernel / lsnf_unfold_kernel"
+                               : contraction == LSNF_CONTRACT_X3 ? "lsnf_backward_params: lsnf_contract_x3_kernel / lsnf_unfold_kernel"
+                                                                 : "lsnf_backward_params: lsnf_tn_gemm kernel / lsnf_unfold_kernel");
+    return LSNF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -723,58 +786,22 @@ int lsnf_backward_params(const float* plan, const float* const* params_host, flo
                          int depth, int coupling, int B, const float* z_in, const float* z_out, const float* z_saved,
                          const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
                          float* g_z_in, float* workspace, void* stream) {
+    return backward_params_entry("lsnf_backward_params", 0, plan, params_host, grads_host, nz, width, depth, coupling, B, z_in, z_out, z_saved,
+                                 act_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in, workspace, stream);
+}
+
+size_t lsnf_backward_params_det_workspace_floats(int nz, int width, int depth, int B) {
     LsnfGeo g;
-    if (int rc = geo_or_fail(&g, nz, width, depth, coupling)) return rc;
-    if (B < 1 || B > (1 << 28)) return fail(LSNF_E_ARG, "lsnf_backward_params: B=%d out of range", B);
-    if (!plan || !params_host || !grads_host || !z_in || !z_out || !workspace || (depth > 1 && !z_saved))
-        return fail(LSNF_E_ARG, "lsnf_backward_params: NULL argument");
-    if (!aligned16(plan) || !aligned16(workspace)) return fail(LSNF_E_ARG, "lsnf_backward_params: plan/workspace must be 16-byte aligned");
-    for (int i = 0; i < depth * LSNF_PARAMS_PER_BLOCK; ++i) {
-        if (!params_host[i] || !aligned4(params_host[i]) || !aligned4(grads_host[i]))
-            return fail(LSNF_E_ARG, "lsnf_backward_params: parameter/gradient pointer %d is NULL or misaligned", i);
-    }
-    if (!aligned4(z_in) || !aligned4(z_out) || !aligned4(z_saved) || !aligned4(g_z1) || !aligned4(g_logdet) || !aligned4(g_z_in))
-        return fail(LSNF_E_ARG, "lsnf_backward_params: tensors must be 4-byte aligned");
-    // (z_in too: the batch contraction of block 0 reads its rows with the same vector width)
-    const int vec4 = row_vector_width(g, {z_in, z_out, g_z_in, z_saved, g_z1});
-    if (act_saved && !aligned16(act_saved)) return fail(LSNF_E_ARG, "lsnf_backward_params: act_saved must be 16-byte aligned");
-    // Fast path (act_saved given, bf16x3-family math): the forward of this evaluation kept the activation stash and wrote h1 / h2
-    // into this workspace's dump (lsnf_forward(params_workspace)); the backward FROM THE STASH, on the bf16 matrix pipe, adds
-    // g_v, g_a1, g_a2, g_t, g_p -- no recomputation of the coupling MLP (1.0x instead of 1.5x the forward's matrix work, at
-    // 2.6x the matrix rate).  Otherwise: the recomputing fp32-MFMA backward writes all seven tensors itself.
-    // Large batches on the fast path: the contraction runs on the bf16 matrix pipe, operands read once (lsnf_params3.hip;
-    // LSNF_TN_X3=0 keeps the fp32-MFMA kernels), and the throughput backward then writes its g arrays in the tiled form (whole
-    // 1 KiB stores instead of 16 rows x 64 bytes; g_v as its first half only: the second half is g_t)
-    if (!l16_math()) act_saved = nullptr;
-    if (act_saved && dump_may_tile(g, B, small_batch_max()) && !(aligned16(z_in) && aligned16(z_out) && aligned16(z_saved)))
-        return fail(LSNF_E_ARG, "lsnf_backward_params: with act_saved at B=%d, z_in / z_out / z_saved must be 16-byte aligned", B);
-    const hipStream_t st = (hipStream_t)stream;
-    // workspace: G = sum_b dL/dlogdet_b (one double in floats 0-1: in float32 the per-wave atomics lost up to ~1e-5 of it, and
-    // G * 3 / G * W^-T cancel against the data terms of the actnorm.logs / 1x1-conv gradients), the folded gradients (zeroed:
-    // both accumulate by atomics), then the dump the backward writes
-    const size_t folded = 4 + (size_t)depth * lsnf_fold_layout(nz, width).per_block;
-    LsnfBackwardCall b;
-    b.g = g; b.plan = plan; b.B = B; b.vec4 = vec4; b.stream = st;
-    b.z_out = z_out; b.z_saved = z_saved; b.act_saved = act_saved; b.g_z1 = g_z1; b.g_logdet = g_logdet;
-    b.ll_mode = ll_mode; b.ll_scale = ll_scale; b.g_z_in = g_z_in;
-    b.dump = workspace + folded; b.gl_total = reinterpret_cast<double*>(workspace);
-    LsnfContractCall c;
-    c.g = g; c.plan = plan; c.B = B; c.vec4 = vec4; c.stream = st;
-    c.params_host = params_host; c.grads_host = grads_host; c.z_in = z_in; c.z_out = z_out; c.z_saved = z_saved; c.workspace = workspace;
-    const Pick p = select_backward(b);
-    const bool use_x3 = act_saved && lsnf_contract_x3_covers(c);
-    const int contraction = select_contraction(g, B, use_x3, vec4);
-    b.dump_tiled = c.g_tiled = (use_x3 && p.k == K_BWD3 && lsnf_dump_can_tile(nz, width)) ? 1 : 0;
-    if (p.k == K_NONE) return launch_fail(hipSuccess, "lsnf_backward_params", p.k);
-    hipError_t e = hipMemsetAsync(workspace, 0, sizeof(float) * folded, st);
-    if (e != hipSuccess) return hip_fail(e, "lsnf_backward_params: hipMemsetAsync(workspace)");
-    e = launch_backward(p, b);
-    if (e != hipSuccess) return launch_fail(e, "lsnf_backward_params", p.k);
-    e = lsnf_launch_params_contract(c, contraction);
-    if (e != hipSuccess)
-        return hip_fail(e, contraction == LSNF_CONTRACT_X3 ? "lsnf_backward_params: lsnf_contract_x3_kernel / lsnf_unfold_kernel"
-                                                           : "lsnf_backward_params: lsnf_tn_gemm kernel / lsnf_unfold_kernel");
-    return LSNF_OK;
+    if (lsnf_geo_init(&g, nz, width, depth, 1) || B < 0) return 0;   // independent of the coupling type
+    return lsnf_params_det_workspace_floats(nz, width, depth, B);
+}
+
+int lsnf_backward_params_det(const float* plan, const float* const* params_host, float* const* grads_host, int nz, int width,
+                             int depth, int coupling, int B, const float* z_in, const float* z_out, const float* z_saved,
+                             const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
+                             float* g_z_in, float* workspace, void* stream) {
+    return backward_params_entry("lsnf_backward_params_det", 1, plan, params_host, grads_host, nz, width, depth, coupling, B, z_in, z_out,
+                                 z_saved, act_saved, g_z1, g_logdet, ll_mode, ll_scale, g_z_in, workspace, stream);
 }
 
 }  // extern "C"

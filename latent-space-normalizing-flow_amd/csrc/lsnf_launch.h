@@ -62,6 +62,10 @@ struct LsnfContractCall : LsnfCall {     // steps (2), (3) of lsnf_backward_para
     const float* z_in = nullptr; const float* z_out = nullptr; const float* z_saved = nullptr;
     float* workspace = nullptr;          // [G | folded gradients | dump | tag] (lsnf_layout.h)
     int g_tiled = 0;                     // the backward wrote its g arrays tiled
+    // lsnf_backward_params_det: the contraction writes per-chunk partials behind the tag word (lsnf_layout.h), chunked by (B,
+    // depth, kind) alone, and lsnf_fold_reduce_kernel sums them -- and dL/dlogdet over the batch -- in a fixed order
+    int det = 0;
+    const float* g_logdet = nullptr; int ll_mode = 0; float ll_scale = 0.f;      // (det only: the upstream dL/dlogdet_b)
 };
 struct LsnfPrepareCall {                 // lsnf_prepare
     LsnfGeo g;

@@ -220,6 +220,44 @@ static inline size_t lsnf_params_workspace_floats(int nz, int width, int depth, 
 // the tiled form of the dump needs whole feature groups of 16 and the natural tile order of the latent rows
 static inline int lsnf_dump_can_tile(int nz, int width) { return nz % 64 == 0 && width % 16 == 0; }
 #define LSNF_X3_MIN_ROWS 12288      /* lsnf_params3.hip takes the batch contraction from this many rows (fp32-MFMA kernel below) */
+
+// ---- deterministic parameter gradients (lsnf_backward_params_det): fixed-order batch contraction ----
+// The chunking of the batch follows from (B, depth, contraction kind) ALONE -- not from the device, the environment or the stream:
+//   fp32-MFMA kernels (lsnf_params.hip): 128 rows per chunk below 16 384 rows, 512 from there (the default path's sizes), and
+//     beyond LSNF_DET_MAX_CHUNKS chunks the chunk grows (in whole 16-row stages) so that there are never more;
+//   bf16 kernel (lsnf_params3.hip): 256 / depth chunks in whole 32-row stages (the default path's one round of workgroups).
+// Every (chunk, block) has its own SLOT of LsnfFoldLayout.per_block floats in the partials area behind the tag word; chunk c's
+// slots are the floats [c * depth * per_block, (c + 1) * depth * per_block) of the area -- one whole image of the fold per chunk,
+// which lsnf_fold_reduce_kernel sums in chunk order.
+#define LSNF_DET_MAX_CHUNKS 128
+static inline int lsnf_det_chunk_rows(int B, int depth, int x3) {
+    if (x3) {
+        int chunks = 256 / depth;
+        if (chunks < 1) chunks = 1;
+        return ((B + chunks - 1) / chunks + 31) / 32 * 32;
+    }
+    int chunk = B >= 16384 ? 512 : 128;
+    if ((B + chunk - 1) / chunk > LSNF_DET_MAX_CHUNKS) chunk = ((B + LSNF_DET_MAX_CHUNKS - 1) / LSNF_DET_MAX_CHUNKS + 15) / 16 * 16;
+    return chunk;
+}
+static inline int lsnf_det_chunks(int B, int depth, int x3) {
+    const int chunk = lsnf_det_chunk_rows(B, depth, x3);
+    return B < 1 ? 0 : (B + chunk - 1) / chunk;
+}
+// chunks the workspace holds slots for: the kind is decided per call (alignment, the stash), so the larger of the two counts
+// where the bf16 kernel can run at all (<= 128 for depth >= 2, <= 256 for depth 1)
+static inline int lsnf_det_workspace_chunks(int B, int depth) {
+    const int a = lsnf_det_chunks(B, depth, 0), b = B >= LSNF_X3_MIN_ROWS ? lsnf_det_chunks(B, depth, 1) : 0;
+    return a > b ? a : b;
+}
+// first float of the partials area: behind the default workspace, rounded up to 16 bytes
+static inline size_t lsnf_params_det_partials(int nz, int width, int depth, int B) {
+    return LSNF_AL4(lsnf_params_workspace_floats(nz, width, depth, B));
+}
+static inline size_t lsnf_params_det_workspace_floats(int nz, int width, int depth, int B) {
+    return lsnf_params_det_partials(nz, width, depth, B) +
+           (size_t)lsnf_det_workspace_chunks(B, depth) * depth * lsnf_fold_layout(nz, width).per_block;
+}
 // the batch contraction of lsnf_backward_params: lsnf_params3.hip's kernel on the bf16 matrix pipe, or lsnf_params.hip's fp32-MFMA
 // kernels -- through LDS with rows of 4 / 2 / 1 floats per load, or the plain one (lsnf_api.hip select_contraction picks)
 enum LsnfContraction { LSNF_CONTRACT_X3, LSNF_CONTRACT_LDS4, LSNF_CONTRACT_LDS2, LSNF_CONTRACT_LDS1, LSNF_CONTRACT_PLAIN };

@@ -9,6 +9,9 @@
 //      from HBM in fragment layout -- rows are contiguous along the feature index, which is the lane
 //      index of both operands), plus the column sums of G (bias gradients); split over sample chunks,
 //      accumulated with float atomics into the zero-initialised "folded" gradient buffer.
+//      Deterministic form (lsnf_backward_params_det; DET instantiations below): a workgroup does not add into the shared fold but
+//      STORES its tiles and column sums into its own (chunk, block) slot of the partials area; lsnf_fold_reduce_kernel then sums
+//      the chunks' slots in chunk order in float64, rounds once and writes the fold -- and sums dL/dlogdet over the batch.
 //  (3) lsnf_unfold_kernel: chain rule from the folded matrices (Wa = diag(e^{3s}) W, W1' = W1 diag(e^{3s1}),
 //      ..., interleaved fc_zeros columns) back to the reference's raw parameters, incl.
 //      d log|det W| / dW = W^-T (model.py:182) and d sum(3 logs)/d logs = 3 (model.py:264,273).
@@ -29,7 +32,7 @@ namespace {
 
 struct TnArgs {
     const float* z_in; const float* z_out; const float* z_saved;
-    const float* dump; float* fold;
+    const float* dump; float* fold;    // DET: the partials area (slot (chunk, block) at ((chunk * depth) + block) * per_block)
     int B, nz, half, width, depth, chunk;
     int abl;                           // timing experiments only (tools/): 1 no atomics, 2 no MFMA, 4 no global loads after the first stage
 };
@@ -51,12 +54,16 @@ __device__ __forceinline__ void tn_wave_tiles(int wave, int KT, int NT, int& kt,
 
 // task = blk*5 + which: 0 dWa (A = block input x, G = g_v) ; 1 dW1' (A = v1, G = g_a1) ; 2 dW2' (A = h1, G = g_a2)
 //                       3 dW3s (A = h2, G = g_t) ; 4 dW3p (A = h2, G = g_p)
+// DET: every element (krow < K, ncol < N) of C belongs to exactly one (kt, n-tile) pair, tn_wave_tiles gives every pair of the task to
+// exactly one wave, and a wave's 16 registers x 2 lane halves cover the 32 rows of its tile once; cs[ncol] is written by the one
+// wave with kt == 0 that owns n-tile ncol / 32, from its lanes kk == 0.  So a slot has one writer per element: plain stores.
+template <bool DET>
 __global__ __launch_bounds__(256) void lsnf_tn_gemm_kernel(const TnArgs a) {
     const int task = blockIdx.x, blk = task / 5, which = task % 5;
     const LsnfDumpLayout dl = lsnf_dump_layout(a.B, a.nz, a.width);
     const LsnfFoldLayout fl = lsnf_fold_layout(a.nz, a.width);
     const float* dmp = a.dump + (size_t)blk * dl.per_block;
-    float* fold = a.fold + (size_t)blk * fl.per_block;
+    float* fold = a.fold + (DET ? (size_t)blockIdx.y * a.depth + blk : (size_t)blk) * fl.per_block;
     const float* yblk = (blk == a.depth - 1) ? a.z_out : a.z_saved + (size_t)blk * a.B * a.nz;       // block output
     const float* xblk = (blk == 0) ? a.z_in : a.z_saved + (size_t)(blk - 1) * a.B * a.nz;            // block input
     const float *A, *G; int lda, ldg, K, N; float *C, *cs;
@@ -131,12 +138,12 @@ __global__ __launch_bounds__(256) void lsnf_tn_gemm_kernel(const TnArgs a) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int krow = 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * kk;
-                    if (krow < K) atomicAdd(&C[(size_t)krow * N + ncol], acc[t][r]);
+                    if (krow < K) { if constexpr (DET) C[(size_t)krow * N + ncol] = acc[t][r]; else atomicAdd(&C[(size_t)krow * N + ncol], acc[t][r]); }
                 }
             }
             if (kt == 0) {     // column sums of G (bias gradients), once per task and n-tile
                 const float s = csum[t] + __shfl_xor(csum[t], 32, 64);
-                if (kk == 0 && ncol < N) atomicAdd(&cs[ncol], s);
+                if (kk == 0 && ncol < N) { if constexpr (DET) cs[ncol] = s; else atomicAdd(&cs[ncol], s); }
             }
         }
     }
@@ -185,13 +192,13 @@ __device__ __forceinline__ void tn_stage_store(const float (&regs)[TN_S * 128 / 
         else lds[e] = regs[j];
     }
 }
-template <int VW>
+template <int VW, bool DET>              // DET: one writer per element of the slot, as in lsnf_tn_gemm_kernel (same tiles, same waves)
 __global__ __launch_bounds__(256) void lsnf_tn_gemm_lds_kernel(const TnArgs a) {
     const int task = blockIdx.x, blk = task / 5, which = task % 5;
     const LsnfDumpLayout dl = lsnf_dump_layout(a.B, a.nz, a.width);
     const LsnfFoldLayout fl = lsnf_fold_layout(a.nz, a.width);
     const float* dmp = a.dump + (size_t)blk * dl.per_block;
-    float* fold = a.fold + (size_t)blk * fl.per_block;
+    float* fold = a.fold + (DET ? (size_t)blockIdx.y * a.depth + blk : (size_t)blk) * fl.per_block;
     const float* yblk = (blk == a.depth - 1) ? a.z_out : a.z_saved + (size_t)blk * a.B * a.nz;
     const float* xblk = (blk == 0) ? a.z_in : a.z_saved + (size_t)(blk - 1) * a.B * a.nz;
     const float *A, *G; int lda, ldg, K, N; float *C, *cs;
@@ -261,15 +268,72 @@ __global__ __launch_bounds__(256) void lsnf_tn_gemm_lds_kernel(const TnArgs a) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int krow = 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * kk;
-                    if (krow < K) atomicAdd(&C[(size_t)krow * N + ncol], acc[t][r]);
+                    if (krow < K) { if constexpr (DET) C[(size_t)krow * N + ncol] = acc[t][r]; else atomicAdd(&C[(size_t)krow * N + ncol], acc[t][r]); }
                 }
             }
             if (kt == 0) {     // column sums of G (bias gradients), once per task and n-tile
                 const float s = csum[t] + __shfl_xor(csum[t], 32, 64);
-                if (kk == 0 && ncol < N) atomicAdd(&cs[ncol], s);
+                if (kk == 0 && ncol < N) { if constexpr (DET) cs[ncol] = s; else atomicAdd(&cs[ncol], s); }
             }
         }
     }
+}
+
+// Deterministic form, between the contraction and the unfold.  Workgroups 1.. : thread = one 16-byte group of the fold (n floats =
+// depth * per_block, a multiple of 4; fold and partials 16-byte aligned); it sums that group of the `chunks` launched chunks'
+// images of the fold (part + c * n) in chunk-index order in float64, rounds once to fp32 and writes the fold.  A wave reads 1 KiB
+// runs; eight chunks' loads in flight per thread.  No atomics: the fold's bits follow from the partials' bits.
+// Workgroup 0: G = sum_b dL/dlogdet_b (ll_scale per row in ll_mode, else g_logdet[b] or 0) in float64 in a fixed tree -- thread t
+// adds rows t, t + 256, ... in that order, then the 256 thread sums pairwise through LDS -- into doubles 0-1 of the workspace,
+// where lsnf_unfold_kernel reads it (the backward's atomic sum went to the spare floats 2-3 and is ignored).
+struct FoldReduceArgs {
+    const float* part; float* fold; double* gl_total; const float* g_logdet;
+    int n, chunks, B, ll_mode; float ll_scale;
+};
+__global__ __launch_bounds__(256) void lsnf_fold_reduce_kernel(const FoldReduceArgs a) {
+    const int tid = threadIdx.x;
+    if (blockIdx.x == 0) {
+        __shared__ double red[256];
+        double s = 0.0;
+        if (a.ll_mode) { const double v = (double)a.ll_scale; for (int b = tid; b < a.B; b += 256) s += v; }
+        else if (a.g_logdet) {
+            int b = tid;
+            for (; b + 7 * 256 < a.B; b += 8 * 256) {      // (eight rows in flight; added in row order)
+                float v[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = a.g_logdet[b + 256 * j];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) s += (double)v[j];
+            }
+            for (; b < a.B; b += 256) s += (double)a.g_logdet[b];
+        }
+        red[tid] = s;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if (tid < o) red[tid] += red[tid + o];
+            __syncthreads();
+        }
+        if (tid == 0) a.gl_total[0] = red[0];
+        return;
+    }
+    const size_t e = ((size_t)(blockIdx.x - 1) * 256 + tid) * 4;
+    if (e >= (size_t)a.n) return;
+    const float* p = a.part + e;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    int c = 0;
+    for (; c + 8 <= a.chunks; c += 8) {
+        f32x4v v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = *reinterpret_cast<const f32x4v*>(p + (size_t)(c + j) * a.n);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { s0 += (double)v[j][0]; s1 += (double)v[j][1]; s2 += (double)v[j][2]; s3 += (double)v[j][3]; }
+    }
+    for (; c < a.chunks; ++c) {
+        const f32x4v v = *reinterpret_cast<const f32x4v*>(p + (size_t)c * a.n);
+        s0 += (double)v[0]; s1 += (double)v[1]; s2 += (double)v[2]; s3 += (double)v[3];
+    }
+    const f32x4v r = {(float)s0, (float)s1, (float)s2, (float)s3};
+    *reinterpret_cast<f32x4v*>(a.fold + e) = r;
 }
 
 // raw-parameter gradients from the folded ones.  grid = (depth, UNFOLD_SECTIONS): the sections of one block share
@@ -402,17 +466,38 @@ hipError_t lsnf_launch_params_contract(const LsnfContractCall& c, int contractio
     static const int knob_chunk = [] { const char* e = getenv("LSNF_TN_CHUNK"); return e ? atoi(e) : 0; }();
     t.abl = knob_abl;
     if (knob_chunk > 0) t.chunk = knob_chunk;
+    if (c.det) {      // the partials area behind the tag word; chunking by (B, depth, kind) alone: no knobs
+        t.fold = c.workspace + lsnf_params_det_partials(g.nz, g.width, g.depth, c.B);
+        t.abl = 0; t.chunk = lsnf_det_chunk_rows(c.B, g.depth, 0);
+    }
     const dim3 grid(g.depth * 5, (unsigned)((c.B + t.chunk - 1) / t.chunk));
     hipError_t e = hipSuccess;
-    switch (contraction) {
-    case LSNF_CONTRACT_X3: e = lsnf_launch_contract_x3(c, knob_chunk); break;
-    case LSNF_CONTRACT_LDS4: hipLaunchKernelGGL(lsnf_tn_gemm_lds_kernel<4>, grid, dim3(256), 0, stream, t); break;
-    case LSNF_CONTRACT_LDS2: hipLaunchKernelGGL(lsnf_tn_gemm_lds_kernel<2>, grid, dim3(256), 0, stream, t); break;
-    case LSNF_CONTRACT_LDS1: hipLaunchKernelGGL(lsnf_tn_gemm_lds_kernel<1>, grid, dim3(256), 0, stream, t); break;
-    default: hipLaunchKernelGGL(lsnf_tn_gemm_kernel, grid, dim3(256), 0, stream, t); break;
+    if (c.det) {
+        switch (contraction) {
+        case LSNF_CONTRACT_X3: e = lsnf_launch_contract_x3(c, 0); break;
+        case LSNF_CONTRACT_LDS4: hipLaunchKernelGGL((lsnf_tn_gemm_lds_kernel<4, true>), grid, dim3(256), 0, stream, t); break;
+        case LSNF_CONTRACT_LDS2: hipLaunchKernelGGL((lsnf_tn_gemm_lds_kernel<2, true>), grid, dim3(256), 0, stream, t); break;
+        case LSNF_CONTRACT_LDS1: hipLaunchKernelGGL((lsnf_tn_gemm_lds_kernel<1, true>), grid, dim3(256), 0, stream, t); break;
+        default: hipLaunchKernelGGL(lsnf_tn_gemm_kernel<true>, grid, dim3(256), 0, stream, t); break;
+        }
+    } else {
+        switch (contraction) {
+        case LSNF_CONTRACT_X3: e = lsnf_launch_contract_x3(c, knob_chunk); break;
+        case LSNF_CONTRACT_LDS4: hipLaunchKernelGGL((lsnf_tn_gemm_lds_kernel<4, false>), grid, dim3(256), 0, stream, t); break;
+        case LSNF_CONTRACT_LDS2: hipLaunchKernelGGL((lsnf_tn_gemm_lds_kernel<2, false>), grid, dim3(256), 0, stream, t); break;
+        case LSNF_CONTRACT_LDS1: hipLaunchKernelGGL((lsnf_tn_gemm_lds_kernel<1, false>), grid, dim3(256), 0, stream, t); break;
+        default: hipLaunchKernelGGL(lsnf_tn_gemm_kernel<false>, grid, dim3(256), 0, stream, t); break;
+        }
     }
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) return e;
+    if (c.det) {
+        FoldReduceArgs r;
+        r.part = c.workspace + lsnf_params_det_partials(g.nz, g.width, g.depth, c.B); r.fold = fold; r.gl_total = reinterpret_cast<double*>(c.workspace); r.g_logdet = c.g_logdet;
+        r.n = g.depth * lsnf_fold_layout(g.nz, g.width).per_block; r.chunks = lsnf_det_chunks(c.B, g.depth, contraction == LSNF_CONTRACT_X3 ? 1 : 0); r.B = c.B; r.ll_mode = c.ll_mode; r.ll_scale = c.ll_scale;
+        hipLaunchKernelGGL(lsnf_fold_reduce_kernel, dim3(1 + (unsigned)((r.n / 4 + 255) / 256)), dim3(256), 0, stream, r);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
     LsnfParamPtrs pp; LsnfGradPtrs gp;
     for (int i = 0; i < LSNF_MAX_DEPTH * 12; ++i) {
         pp.p[i] = i < g.depth * 12 ? c.params_host[i] : nullptr;

@@ -14,7 +14,8 @@
 // producer waves -- 128 threads load the A rows and 128 the G rows (8 rows x 16 bytes per thread, two stages in flight in registers),
 // split them and write the three bf16 planes TRANSPOSED into LDS ([feature][32 samples], 80-byte pitch: the 16-byte writes of a stage
 // and the 16-byte operand reads of the MFMAs are both bank-conflict-free); four consumer waves split the output tiles by rows.  Results go to the zero-initialised
-// folded buffer with float atomics (LsnfFoldLayout), exactly as in lsnf_params.hip.
+// folded buffer with float atomics (LsnfFoldLayout), exactly as in lsnf_params.hip -- or, in the DET instantiation
+// (lsnf_backward_params_det), with plain stores into the workgroup's own (chunk, block) slot of the partials area.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include "lsnf_device.h"
@@ -137,7 +138,12 @@ __device__ __forceinline__ void x3_mma(f32x4 (&acc)[MPW][NTL], const char* buf, 
 // MFMAs, the atomics at the end): two waves per SIMD, one of each role, so the split's VALU work and the load waits of one run under
 // the MFMAs of the other (with all waves doing both in turn, the four parts of a stage simply added up: tools/ablate_x3.sh).
 // One barrier per stage: the producers' write of stage s + 2 follows barrier s + 1, which the consumers reach after reading stage s.
-template <int MPW, int NTL>
+// DET, one writer per element of the slot.  Tiles: consumer wave `wave` owns the rows 16 * (wave + 4 * mi) + 4 * (lane >> 4) + r and
+// the columns 16 * nt + (lane & 15): every (k < K, n < N) once (x3_run's MPW / NTL cover 16 * 4 * MPW >= K rows, 16 * NTL >= N
+// columns).  Column sums: G column n is loaded by ONE producer wave (6: the first source / columns [0, 64), 7: the rest) and there by
+// the four lanes rg = 0..3 of one column group, whose sums the two shuffles below add in a fixed order ((rg0 + rg1) + (rg2 + rg3));
+// lane rg == 0 alone writes it.
+template <int MPW, int NTL, bool DET>
 __device__ __forceinline__ void x3_task(const X3Task& t, int m_begin, int m_end, int m_end_all, char* lds) {
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int ns = (m_end - m_begin + X3_S - 1) / X3_S;
@@ -178,7 +184,10 @@ __device__ __forceinline__ void x3_task(const X3Task& t, int m_begin, int m_end,
                 v += __shfl_xor(v, 1, 64);
                 v += __shfl_xor(v, 2, 64);
                 const int n = g.feat0 + col + f;
-                if (rg == 0 && live && n < t.N) atomicAdd(n < t.nsplit ? t.cs0 + n : t.cs1 + (n - t.nsplit), v);
+                if (rg == 0 && live && n < t.N) {
+                    float* q = n < t.nsplit ? t.cs0 + n : t.cs1 + (n - t.nsplit);
+                    if constexpr (DET) *q = v; else atomicAdd(q, v);
+                }
             }
         }
         return;
@@ -206,18 +215,20 @@ __device__ __forceinline__ void x3_task(const X3Task& t, int m_begin, int m_end,
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int k = 16 * (wave + 4 * mi) + 4 * g + r;
-                    if (k < t.K && (!(X3_ABL & 1) || blockIdx.x == 0)) atomicAdd(c + (size_t)k * ldc, acc[mi][nt][r]);
+                    if (k < t.K && (!(X3_ABL & 1) || blockIdx.x == 0)) { if constexpr (DET) c[(size_t)k * ldc] = acc[mi][nt][r]; else atomicAdd(c + (size_t)k * ldc, acc[mi][nt][r]); }
                 }
             }
         }
 }
 
+template <bool DET>
 __device__ __forceinline__ void x3_run(const X3Task& t, int m_begin, int m_end, int m_end_all, char* lds) {
     const int mt = (t.K + 15) / 16, nt = (t.N + 15) / 16;          // workgroup-uniform
-    if (mt > 4) { if (nt > 4) x3_task<2, 8>(t, m_begin, m_end, m_end_all, lds); else x3_task<2, 4>(t, m_begin, m_end, m_end_all, lds); }
-    else { if (nt > 4) x3_task<1, 8>(t, m_begin, m_end, m_end_all, lds); else x3_task<1, 4>(t, m_begin, m_end, m_end_all, lds); }
+    if (mt > 4) { if (nt > 4) x3_task<2, 8, DET>(t, m_begin, m_end, m_end_all, lds); else x3_task<2, 4, DET>(t, m_begin, m_end, m_end_all, lds); }
+    else { if (nt > 4) x3_task<1, 8, DET>(t, m_begin, m_end, m_end_all, lds); else x3_task<1, 4, DET>(t, m_begin, m_end, m_end_all, lds); }
 }
 
+template <bool DET>
 __global__ __launch_bounds__(512, 1) void lsnf_contract_x3_kernel(const X3Args a) {
     extern __shared__ __attribute__((aligned(16))) char x3_lds[];
     const int blk = blockIdx.y;
@@ -225,7 +236,7 @@ __global__ __launch_bounds__(512, 1) void lsnf_contract_x3_kernel(const X3Args a
     const LsnfDumpLayout dl = lsnf_dump_layout(a.B, a.nz, a.width);
     const LsnfFoldLayout fl = lsnf_fold_layout(a.nz, a.width);
     const float* dmp = a.dump + (size_t)blk * dl.per_block;
-    float* fold = a.fold + (size_t)blk * fl.per_block;
+    float* fold = a.fold + (DET ? (size_t)blockIdx.x * a.depth + blk : (size_t)blk) * fl.per_block;      // DET: a.fold = the partials area
     const float* yblk = (blk == a.depth - 1) ? a.z_out : a.z_saved + (size_t)blk * a.B * a.nz;
     const float* xblk = (blk == 0) ? a.z_in : a.z_saved + (size_t)(blk - 1) * a.B * a.nz;
     const int h_tiled = *a.h_tag, gt_ = a.g_tiled;                     // (uniform)
@@ -235,20 +246,20 @@ __global__ __launch_bounds__(512, 1) void lsnf_contract_x3_kernel(const X3Args a
     if (gt_) { t.G0 = dmp + dl.off_gv; t.G1 = dmp + dl.off_gt; t.ldg0 = a.half; t.ldg1 = a.half; t.nsplit = a.half; }
     else { t.G0 = dmp + dl.off_gv; t.G1 = nullptr; t.ldg0 = a.nz; t.ldg1 = 0; t.nsplit = a.nz; }
     t.C0 = fold + fl.dWa; t.C1 = fold + fl.dWa + t.nsplit; t.ldc0 = a.nz; t.ldc1 = a.nz; t.cs0 = fold + fl.dca; t.cs1 = fold + fl.dca + t.nsplit;
-    x3_run(t, m_begin, m_end, a.B, x3_lds);
+    x3_run<DET>(t, m_begin, m_end, a.B, x3_lds);
     // T1: dW1' = v1^T g_a1
     t.A = yblk; t.lda = a.nz; t.K = a.half; t.G0 = dmp + dl.off_ga1; t.G1 = nullptr; t.ldg0 = a.width; t.N = a.width; t.nsplit = a.width;
     t.C0 = fold + fl.dW1; t.ldc0 = a.width; t.cs0 = fold + fl.dc1;
-    x3_run(t, m_begin, m_end, a.B, x3_lds);
+    x3_run<DET>(t, m_begin, m_end, a.B, x3_lds);
     // T2: dW2' = h1^T g_a2
     t.A = dmp + dl.off_h1; t.lda = a.width; t.K = a.width; t.a_tiled = h_tiled; t.G0 = dmp + dl.off_ga2; t.ldg0 = a.width; t.N = a.width; t.nsplit = a.width;
     t.C0 = fold + fl.dW2; t.ldc0 = a.width; t.cs0 = fold + fl.dc2;
-    x3_run(t, m_begin, m_end, a.B, x3_lds);
+    x3_run<DET>(t, m_begin, m_end, a.B, x3_lds);
     // T3: [dW3s | dW3p] = h2^T [g_t | g_p]
     t.A = dmp + dl.off_h2; t.lda = a.width; t.K = a.width; t.G0 = dmp + dl.off_gt; t.G1 = dmp + dl.off_gp; t.ldg0 = a.half; t.ldg1 = a.half;
     t.N = 2 * a.half; t.nsplit = a.half;
     t.C0 = fold + fl.dW3s; t.C1 = fold + fl.dW3p; t.ldc0 = a.half; t.ldc1 = a.half; t.cs0 = fold + fl.dc3s; t.cs1 = fold + fl.dc3p;
-    x3_run(t, m_begin, m_end, a.B, x3_lds);
+    x3_run<DET>(t, m_begin, m_end, a.B, x3_lds);
 }
 
 static_assert(X3_LDS <= 160 * 1024, "lsnf_allow_big_lds admits 160 KiB");
@@ -273,6 +284,7 @@ hipError_t lsnf_launch_contract_x3(const LsnfContractCall& c, int chunk_override
     a.h_tag = reinterpret_cast<const int*>(c.workspace + lsnf_params_workspace_tag(c.g.nz, c.g.width, depth, B));
     a.fold = c.workspace + 4;
     a.dump = a.fold + (size_t)depth * lsnf_fold_layout(c.g.nz, c.g.width).per_block;
+    if (c.det) a.fold = c.workspace + lsnf_params_det_partials(c.g.nz, c.g.width, depth, B);
     a.z_in = c.z_in; a.z_out = c.z_out; a.z_saved = c.z_saved;
     a.B = B; a.nz = c.g.nz; a.half = c.g.half; a.width = c.g.width; a.depth = depth;
     // one round of workgroups: ~256 / depth chunks of the batch, in whole stages
@@ -281,7 +293,9 @@ hipError_t lsnf_launch_contract_x3(const LsnfContractCall& c, int chunk_override
     int chunk = (B + chunks - 1) / chunks;
     chunk = (chunk + X3_S - 1) / X3_S * X3_S;
     if (chunk_override > 0) chunk = (chunk_override + X3_S - 1) / X3_S * X3_S;
+    if (c.det) chunk = lsnf_det_chunk_rows(B, depth, 1);      // (the same rule, stated once for the size query too; no override)
     a.chunk = chunk;
     chunks = (B + chunk - 1) / chunk;
-    return lsnf_launch_kernel<lsnf_contract_x3_kernel>(dim3(chunks, depth), 512, X3_LDS, c.stream, a);
+    if (c.det) return lsnf_launch_kernel<lsnf_contract_x3_kernel<true>>(dim3(chunks, depth), 512, X3_LDS, c.stream, a);
+    return lsnf_launch_kernel<lsnf_contract_x3_kernel<false>>(dim3(chunks, depth), 512, X3_LDS, c.stream, a);
 }

@@ -106,6 +106,21 @@ def _stash_floats(plan: "FlowPlan", B: int) -> Tuple[int, int]:
     return n
 
 
+_det_sizes: dict = {}         # (nz, width, depth, B) -> floats of the deterministic parameter-gradient workspace
+
+
+def _det_floats(plan: "FlowPlan", B: int) -> int:
+    """`lsnf_backward_params_det_workspace_floats` of B rows, asked once per (geometry, B) -- and only by deterministic calls: the
+    default path never enters the query."""
+    key = (plan.nz, plan.width, plan.depth, B)
+    n = _det_sizes.get(key)
+    if n is None:
+        if len(_det_sizes) >= 1024:
+            _det_sizes.clear()
+        n = _det_sizes[key] = _lib.load().lsnf_backward_params_det_workspace_floats(*key)
+    return n
+
+
 def _check_stash_out(plan: "FlowPlan", B: int, device, act_saved, params_ws):
     """The two stash buffers a forward / stash-keeping reverse fills (either may be None)."""
     if act_saved is not None:
@@ -402,9 +417,12 @@ def params_fast_path() -> bool:
     return bool(_lib.load().lsnf_params_fast_path())
 
 
-def new_params_workspace(plan: "FlowPlan", B: int, device) -> torch.Tensor:
-    """Uninitialised workspace of `backward_params` for a batch of B rows (also the `params_ws` of `forward`)."""
-    return torch.empty(max(_stash_floats(plan, int(B))[1], 4), dtype=torch.float32, device=device)
+def new_params_workspace(plan: "FlowPlan", B: int, device, deterministic: bool = False) -> torch.Tensor:
+    """Uninitialised workspace of `backward_params` for a batch of B rows (also the `params_ws` of `forward`).
+    deterministic: the larger workspace of `backward_params(..., deterministic=True)` -- the same layout followed by the
+    per-chunk partials (`lsnf_backward_params_det_workspace_floats`); it serves the forward and the default call as well."""
+    n = _det_floats(plan, int(B)) if deterministic else _stash_floats(plan, int(B))[1]
+    return torch.empty(max(n, 4), dtype=torch.float32, device=device)
 
 
 STATS_DOUBLES = 264          # include/lsnf_flow.h LSNF_STATS_DOUBLES
@@ -679,7 +697,8 @@ def backward_params(plan: FlowPlan, params: Sequence[torch.Tensor], z_in: torch.
                     z_saved: Optional[torch.Tensor], g_z1: Optional[torch.Tensor] = None,
                     g_logdet: Optional[torch.Tensor] = None, ll_scale: Optional[float] = None,
                     want_grad_z: bool = False, want_flat: bool = False, reuse_buffers: bool = False,
-                    act_saved: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+                    act_saved: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, *,
+                    deterministic: bool = False):
     """dL/dtheta for the depth*12 live tensors (train.py:406-411).  Returns a list of gradients shaped like
     `params` (and dL/dz_in as a second value if want_grad_z; and, last, the ONE flat buffer the gradients are views
     of if want_flat -- a global norm / clip is then one reduction instead of 60).  reuse_buffers: keep the flat
@@ -687,7 +706,10 @@ def backward_params(plan: FlowPlan, params: Sequence[torch.Tensor], z_in: torch.
     parameter storages and B do not change) -- the returned gradient tensors are then THE SAME objects every call,
     overwritten in place (an optimizer that consumes .grad before the next call does not notice; ~0.2 ms of host time).
     act_saved + workspace: the stash and the `params_ws` the forward of THIS evaluation was given -- the backward then runs
-    from the stash on the bf16 matrix pipe instead of recomputing the coupling MLP in fp32 (`params_fast_path()`)."""
+    from the stash on the bf16 matrix pipe instead of recomputing the coupling MLP in fp32 (`params_fast_path()`).
+    deterministic: `lsnf_backward_params_det` -- every sum over the batch in a fixed order, so the same inputs (and build, math
+    mode, small-batch threshold) give the same bits on every run, stream, graph replay and device; a `workspace` must then come from
+    `new_params_workspace(..., deterministic=True)`.  Not torch's global determinism flag: this keyword alone decides."""
     B, dev, head = _anchor(z_out, "z_out", plan), z_out.device, _plan_head(plan)
     _check_in(z_in, "z_in", B * plan.nz, dev)
     if (act_saved is None) != (workspace is None):
@@ -695,8 +717,14 @@ def backward_params(plan: FlowPlan, params: Sequence[torch.Tensor], z_in: torch.
     _check_stash(plan, B, dev, z_saved, act_saved, False)
     _check_in(g_z1, "g_z1", B * plan.nz, dev)
     _check_in(g_logdet, "g_logdet", B, dev)
-    _check_in(workspace, "workspace", _stash_floats(plan, B)[1], dev, at_least=True, hint="new_params_workspace()")
-    key = (tuple(p.data_ptr() for p in params), B, dev, want_grad_z, torch.cuda.current_stream(dev).cuda_stream)
+    deterministic = bool(deterministic)
+    ws_floats = _det_floats(plan, B) if deterministic else _stash_floats(plan, B)[1]
+    _check_in(workspace, "workspace", ws_floats, dev, at_least=True,
+              hint="new_params_workspace(deterministic=True)" if deterministic else "new_params_workspace()")
+    # (workspace is None: the kept state owns a workspace only then -- a call without one must not find the empty one that a call
+    #  with a caller-owned workspace left)
+    key = (tuple(p.data_ptr() for p in params), B, dev, want_grad_z, torch.cuda.current_stream(dev).cuda_stream, deterministic,
+           workspace is None)
     st = plan.__dict__.get("_bp_state") if reuse_buffers else None     # (keyed by stream too: a second stream re-allocates)
     if st is None or st["key"] != key:
         # the gradient views below are shaped like the tensors handed over and the kernels write what the geometry says: check them
@@ -706,7 +734,7 @@ def backward_params(plan: FlowPlan, params: Sequence[torch.Tensor], z_in: torch.
         sizes = [t.numel() for t in raw]
         flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
         grads = [g.view(t.shape) for g, t in zip(flat.split(sizes), raw)]
-        nws = _stash_floats(plan, B)[1] if workspace is None else 0
+        nws = ws_floats if workspace is None else 0
         base, o, offs = flat.data_ptr(), 0, []
         for n in sizes:
             offs.append(base + o * 4)
@@ -720,7 +748,7 @@ def backward_params(plan: FlowPlan, params: Sequence[torch.Tensor], z_in: torch.
     flat, grads, g_in, ws, parr, garr = st["flat"], st["grads"], st["g_in"], st["ws"], st["parr"], st["garr"]
     if workspace is not None:
         ws = workspace
-    _call("lsnf_backward_params", dev, head[0], parr, garr, *head[1:], B,
+    _call("lsnf_backward_params_det" if deterministic else "lsnf_backward_params", dev, head[0], parr, garr, *head[1:], B,
           _ptr(z_in), _ptr(z_out), _ptr(z_saved), _ptr(act_saved), _ptr(g_z1), _ptr(g_logdet),
           0 if ll_scale is None else 1, float(ll_scale or 0.0), _ptr(g_in), _ptr(ws))
     out = (grads,) + ((g_in,) if want_grad_z else ()) + ((flat,) if want_flat else ())

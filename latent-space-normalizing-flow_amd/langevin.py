@@ -120,7 +120,8 @@ def flow_mle_step(netF, optF, z_g_k, f_max_norm: Optional[float] = None, fused: 
     """train.py:404-415: one Adam step of the flow on the Langevin-inferred z.  Returns loss_f (detached).
     fused=False restates the reference line by line (autograd through `netF(...)`); fused=True computes the same
     loss and gradients with `netF.mle_grads` (no autograd graph, no element-wise torch launches); with a `FlowAdam` as optF it
-    runs `netF.mle_step`: the clip and the update on the device too."""
+    runs `netF.mle_step`: the clip and the update on the device too.  With `netF.deterministic_grads = True` every form takes
+    its parameter gradients from the fixed-order contraction (`lsnf_backward_params_det`): bit-reproducible from run to run."""
     import numpy as np
     from .optim import FlowAdam
     if fused and isinstance(optF, FlowAdam):       # clip + Adam on the device, the plan left current (netF.mle_step)

@@ -106,10 +106,11 @@ class revnet2d(nn.Module):
 # ---------------------------------------------------------------------------------------------
 class _Upstream:
     """Hand-over between the two autograd nodes below (filled by _FlowStackFn.backward)."""
-    __slots__ = ("g_z1", "g_logdet", "z", "z1", "saved", "plan_key", "act", "ws", "empty")
+    __slots__ = ("g_z1", "g_logdet", "z", "z1", "saved", "plan_key", "act", "ws", "det", "empty")
 
     def __init__(self):
         self.g_z1 = self.g_logdet = self.z = self.z1 = self.saved = self.plan_key = self.act = self.ws = None
+        self.det = False         # the module's deterministic_grads when the evaluation began (its workspace is sized by it)
         self.empty = False       # set by _FlowReverseFn.backward on an empty batch: the parameters get no gradient
 
 
@@ -133,7 +134,8 @@ class _ParamGate(torch.autograd.Function):
         if module._current_key() != h.plan_key:     # the LIVE parameters, not the key cached at the last _plan() call
             raise LsnfError("flow parameters were modified between forward and backward")
         grads = flow.backward_params(module._plan(), module._param_list(), h.z, h.z1, h.saved, h.g_z1, h.g_logdet,
-                                     act_saved=h.act if h.ws is not None else None, workspace=h.ws)
+                                     act_saved=h.act if h.ws is not None else None, workspace=h.ws,
+                                     deterministic=h.det)
         grads = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[2:])]
         return (None, None, *grads)
 
@@ -152,7 +154,8 @@ class _FlowStackFn(torch.autograd.Function):
         B = z.shape[0]
         for_params = bool(B) and not ctx.needs_input_grad[2] and ctx.needs_input_grad[4] and flow.params_fast_path()
         act = flow.new_act_saved(plan, B, z.device) if (B and (ctx.needs_input_grad[2] or for_params)) else None
-        ws = flow.new_params_workspace(plan, B, z.device) if for_params else None
+        ctx.det = bool(module.deterministic_grads)
+        ws = flow.new_params_workspace(plan, B, z.device, deterministic=ctx.det) if for_params else None
         if ws is not None and z.data_ptr() % 16:
             z = z.clone()        # the fast path wants 16-byte aligned rows at large B (lsnf_forward, params_workspace)
         z1, logdet, _, saved = flow.forward(plan, z, objective, want_ll=False, save_for_backward=True, act_saved=act, params_ws=ws)
@@ -178,7 +181,7 @@ class _FlowStackFn(torch.autograd.Function):
         g_tok = None
         if ctx.needs_input_grad[4]:
             h.g_z1, h.g_logdet, h.z, h.z1, h.saved, h.plan_key = g_z1, g_logdet, z, z1, saved_t, ctx.plan_key
-            h.act, h.ws = ctx.act, ctx.ws
+            h.act, h.ws, h.det = ctx.act, ctx.ws, ctx.det
             g_tok = z1.new_zeros(())
         return None, None, g_z, g_obj, g_tok
 
@@ -199,7 +202,7 @@ class _FlowReverseFn(torch.autograd.Function):
     def _keep_buffers(ctx, plan, B, want_tok):
         """(act, ws) of a stash-keeping forward: the workspace only if a parameter requires grad and the fast path is on."""
         ctx.act = flow.new_act_saved(plan, B, plan.device)
-        ctx.ws = flow.new_params_workspace(plan, B, plan.device) if (want_tok and flow.params_fast_path()) else None
+        ctx.ws = flow.new_params_workspace(plan, B, plan.device, deterministic=ctx.det) if (want_tok and flow.params_fast_path()) else None
         return ctx.act, ctx.ws
 
     @staticmethod
@@ -209,6 +212,7 @@ class _FlowReverseFn(torch.autograd.Function):
         ctx.plan_key = module._plan_key
         ctx.obj_shape = objective.shape
         ctx.set_materialize_grads(False)
+        ctx.det = bool(module.deterministic_grads)
         ctx.keeps = _FlowReverseFn._keeps(module, plan, z.shape[0])
         if ctx.keeps:
             act, ws = _FlowReverseFn._keep_buffers(ctx, plan, z.shape[0], ctx.needs_input_grad[4])
@@ -239,7 +243,7 @@ class _FlowReverseFn(torch.autograd.Function):
         else:
             for_params = need_tok and flow.params_fast_path()
             act = flow.new_act_saved(plan, B, x.device)
-            ws = flow.new_params_workspace(plan, B, x.device) if for_params else None
+            ws = flow.new_params_workspace(plan, B, x.device, deterministic=ctx.det) if for_params else None
             if ws is not None and x.data_ptr() % 16:
                 x = x.clone()        # the fast path wants 16-byte aligned rows at large B (lsnf_forward, params_workspace)
             z1, _, _, saved = flow.forward(plan, x, None, want_ll=False, save_for_backward=True, act_saved=act, params_ws=ws)
@@ -248,7 +252,7 @@ class _FlowReverseFn(torch.autograd.Function):
         if need_tok:
             h.g_z1, h.g_logdet = g_eps.neg(), (None if g_obj is None else g_obj.neg())
             h.z, h.z1, h.saved, h.plan_key = x, z1, saved, ctx.plan_key
-            h.act, h.ws = act, ws
+            h.act, h.ws, h.det = act, ws, ctx.det
             g_tok = z1.new_zeros(())
         return g_eps, g_obj, g_tok
 
@@ -270,6 +274,7 @@ class _FlowSampleFn(torch.autograd.Function):
         ctx.module, ctx.holder = module, holder
         ctx.plan_key = module._plan_key
         ctx.set_materialize_grads(False)
+        ctx.det = bool(module.deterministic_grads)
         ctx.keeps = _FlowReverseFn._keeps(module, plan, n)
         if ctx.keeps:
             act, ws = _FlowReverseFn._keep_buffers(ctx, plan, n, ctx.needs_input_grad[2])
@@ -311,6 +316,10 @@ class _netF(nn.Module):
         # lsnf_sample_keep) where flow.reverse_keep_supported -- the backward then skips the forward pass at x; elsewhere (large
         # batches, MATH_FP32) the default bridge runs.  Default False: the bridge that recomputes the forward at x.
         self.reverse_keeps_stash = False
+        # True: every route to parameter gradients -- the autograd bridges (forward, reverse, sample), mle_grads, mle_step and
+        # langevin.flow_mle_step -- uses lsnf_backward_params_det and its workspace: fixed-order sums over the batch, the same bits
+        # on every run.  Read once per evaluation, when its forward (or reverse / sample) runs.  This attribute alone decides; torch.use_deterministic_algorithms is not consulted.
+        self.deterministic_grads = False
 
     # ---- prepared weights, re-derived only when a parameter changed -------------------------------
     def _param_list(self) -> List[nn.Parameter]:
@@ -456,7 +465,8 @@ class _netF(nn.Module):
         `.grad` of the 60 live tensors -- forward (ll summed in-kernel), dump backward, batch contraction, unfold:
         5 launches and no autograd graph.  max_norm: clip the global gradient norm (train.py:413-414
         `clip_grad_norm_`) on the one flat buffer the gradients are views of (3 launches instead of a foreach over
-        60 tensors; only without `accumulate`).  reuse_buffers: the gradient tensors are the same objects every call,
+        60 tensors; only without `accumulate`).  With `deterministic_grads` the gradients are bit-reproducible.
+        reuse_buffers: the gradient tensors are the same objects every call,
         overwritten in place (`flow.backward_params`): for loops that consume `.grad` before the next call.
         Returns loss_f as a 0-dim device tensor (no host sync)."""
         plan = self._plan()
@@ -467,9 +477,10 @@ class _netF(nn.Module):
         stats = flow.new_stats(z.device)
         fast = flow.params_fast_path()         # forward keeps the stash + writes h1 / h2 for the contraction: nothing is recomputed
         bufs = plan.__dict__.get("_mle_buffers") if reuse_buffers else None
-        bkey = (B, z.device, torch.cuda.current_stream(z.device).cuda_stream)
+        det = bool(self.deterministic_grads)
+        bkey = (B, z.device, torch.cuda.current_stream(z.device).cuda_stream, det)
         if fast and (bufs is None or bufs[0] != bkey):
-            bufs = (bkey, flow.new_act_saved(plan, B, z.device), flow.new_params_workspace(plan, B, z.device))
+            bufs = (bkey, flow.new_act_saved(plan, B, z.device), flow.new_params_workspace(plan, B, z.device, deterministic=det))
             if reuse_buffers:
                 plan.__dict__["_mle_buffers"] = bufs
         act, ws = (bufs[1], bufs[2]) if fast else (None, None)
@@ -478,7 +489,8 @@ class _netF(nn.Module):
         z1, _, _, saved = flow.forward(plan, z, None, want_ll=False, save_for_backward=True, stats=stats, act_saved=act, params_ws=ws)
         params = self._param_list()
         grads, flat = flow.backward_params(plan, params, z, z1, saved, ll_scale=-1.0 / B, want_flat=True,
-                                           reuse_buffers=reuse_buffers and not accumulate, act_saved=act, workspace=ws)
+                                           reuse_buffers=reuse_buffers and not accumulate, act_saved=act, workspace=ws,
+                                           deterministic=det)
         if max_norm is not None:
             if accumulate:
                 raise LsnfError("max_norm clips the gradients of this call only: not with accumulate=True")

@@ -120,7 +120,7 @@ def collect(build_dir, match):
 
 
 def _base(name):
-    return re.sub(r", false>$", ">", name)
+    return re.sub(r"<false>$", "", re.sub(r", false>$", ">", name))      # (`kernel<false>` was plain `kernel`)
 
 
 def main():
