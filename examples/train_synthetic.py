@@ -62,7 +62,12 @@ def main():
                     "ranks SHARE one GPU -- a rehearsal of the data-parallel code path on a one-GPU box, not a measurement")
     ap.add_argument("--flow-adam", choices=("torch", "fused"), default="torch", help="the flow's optimizer: torch.optim.Adam (+ the clip in "
                     "torch), or lsnf_amd.FlowAdam -- clip and Adam on the device in two launches, one rank: netF.mle_step")
+    ap.add_argument("--flow-ema", type=float, default=None, metavar="DECAY", help="with --flow-adam fused: keep an exponential moving "
+                    "average of the flow's weights on the device, inside the optimizer's launch (FlowAdam(ema_decay=DECAY)); the JSON "
+                    "line then carries the distance between the live and the averaged weights")
     args = ap.parse_args()
+    if args.flow_ema is not None and args.flow_adam != "fused":
+        ap.error("--flow-ema needs --flow-adam fused")
     size, nz, ngf, f_width, K = GEOMETRY[args.dataset]
     step_size, sigma, nc, B = 0.1, 0.3, 3, args.batch
 
@@ -82,7 +87,7 @@ def main():
     optG = torch.optim.Adam(netG.parameters(), lr=3e-4, betas=(0.5, 0.999))
     flow_adam = args.flow_adam == "fused"
     if flow_adam:                                               # clip (train.py:413-414) and Adam in the library's two launches
-        optF = lsnf_amd.FlowAdam(netF, lr=1e-4, betas=(0.5, 0.999), max_norm=100.0)
+        optF = lsnf_amd.FlowAdam(netF, lr=1e-4, betas=(0.5, 0.999), max_norm=100.0, ema_decay=args.flow_ema)
     else:
         try:                                                    # one fused Adam kernel over the flow's 60 tensors
             optF = torch.optim.Adam(netF.parameters(), lr=1e-4, betas=(0.5, 0.999), fused=True)
@@ -196,6 +201,11 @@ def main():
                           "flow_langevin_step_ms": ms_flow, "flow_mle_step_ms": ms_mle,
                           "flow_share_of_iteration": (K * ms_flow + ms_mle) / ms_iter,
                           "loss_g": lg.item(), "loss_f": lf.item(), "warmup_iterations": args.warmup + settle,
+                          **({"flow_ema_decay": args.flow_ema, "flow_skipped_steps": int(optF.skipped_steps.item()),
+                              "flow_ema_rel_distance": (torch.sqrt(sum(((p.detach() - e) ** 2).sum() for p, e in
+                                                                       zip(netF._param_list(), optF.ema_parameters())))
+                                                        / torch.sqrt(sum((e ** 2).sum() for e in optF.ema_parameters()))).item()}
+                             if args.flow_ema is not None else {}),
                           **({"phase_median_ms": {k: float(np.median([r[k] for r in phase_log[args.warmup:]])) for k in phase_log[0]},
                               "phases_note": "--phases synchronises after every phase: ms_per_iteration of this run is not a timing"}
                              if args.phases and phase_log else {})}), flush=True)

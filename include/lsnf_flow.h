@@ -441,7 +441,7 @@ int lsnf_backward_params_det(const float* plan, const float* const* params_host,
  * With neither clipping nor a norm output the norm launch is skipped: one launch.  Asynchronous, allocates nothing, capturable.
  * LSNF_E_ARG: NULL tables / state / parameter pointer, a pointer that is not 4-byte aligned, misaligned state, lr / eps /
  * weight_decay negative or not finite, a beta outside [0, 1), max_norm NaN.  Non-finite gradients are NOT special-cased: as in
- * torch a NaN norm makes coef NaN and poisons the step -- check grad_norm_out.  Plans prepared before the call are stale
+ * torch a NaN norm makes coef NaN and poisons the step -- check grad_norm_out, or use lsnf_adam_step_ex's SKIP_NONFINITE.  Plans prepared before the call are stale
  * afterwards, as after lsnf_actnorm_init.  Added without an ABI bump (new symbols; nothing existing changed). */
 #define LSNF_ADAM_MAX_GROUPS 256
 #define LSNF_ADAM_STEP_OFFSET 0
@@ -453,6 +453,56 @@ int lsnf_adam_step(float* const* params_host, const float* const* grads_host,
                    int nz, int width, int depth, int coupling, void* state,
                    double lr, const float* lr_dev, double beta1, double beta2, double eps, double weight_decay,
                    double max_norm, float* grad_norm_out, void* stream);
+
+/* ---- variants of the optimizer step: amsgrad, maximize, AdamW's decoupled decay, non-finite skip, weight EMA ---------------
+ * lsnf_adam_step_ex is lsnf_adam_step with an options struct; with flags 0 it IS lsnf_adam_step (same kernel, same bits, same
+ * state bytes).  Per element, in this order (torch.optim.Adam / AdamW's _single_tensor_adam for the first four flags):
+ *     g   = grad;                 MAXIMIZE: g = -g
+ *     g   = coef * g                                        (clip, as above; the norm does not see the sign)
+ *     pk  = p
+ *     weight_decay != 0:          DECOUPLED: pk = p * (1 - lr * weight_decay)      (the scalar in float64, once per workgroup;
+ *                                                                                   lr = *lr_dev when given)
+ *                                 else:      g  = g + weight_decay * p             (as above)
+ *     m, v                                                  (as above)
+ *     AMSGRAD: vmax = max(vmax, v)  (the unrounded v);  den = sqrt(vmax) / sqrt(bc2) + eps        else den from v as above
+ *     p   = pk - (lr / bc1) * m / den
+ *     EMA:     e_prev = (step == 1) ? p before this update : e;      e = e_prev + (1 - ema_decay) * ((float)p - e_prev)
+ * `step` is the counter after its increment: an all-zero state stays "a fresh optimizer", and the average starts from the
+ * parameters as the first step finds them.  The average takes the STORED (rounded) new parameter, so a float64 average of the
+ * stored parameters reproduces it to half an ulp per step.  Float64 math on the stored fp32 values and one rounding per stored
+ * value, as above, for vmax and e too.  With EMA a tensor whose gradient is NULL still has its average updated (its p is
+ * loaded; its p / m / v / vmax keep their bits): a tensor that gets its first gradient later does not start from a zero
+ * average.
+ * SKIP_NONFINITE forces the norm launch.  Every workgroup folds the same partials in the same fixed order and so reaches the
+ * same verdict; if the norm is not finite, no p, m, v, vmax or e is written, no step counter advances, the int64 at
+ * LSNF_ADAM_SKIPPED_OFFSET grows by 1 (thread 0 of workgroup 0, a plain store) and the norm slot and grad_norm_out still
+ * receive the non-finite norm.  No atomics, no grid barrier; bit-for-bit reproducible and capturable like lsnf_adam_step.
+ *   state     lsnf_adam_state_bytes_ex(..., flags) bytes: header, m, v, then vmax (only with AMSGRAD), then e (only with EMA),
+ *             each the N floats m has.  With neither flag: lsnf_adam_state_bytes().  AMSGRAD and EMA fix the state's size, so
+ *             the caller passes them at EVERY call on that state; MAXIMIZE, DECOUPLED and SKIP_NONFINITE may change from call
+ *             to call.  The skipped count lives in the spare header bytes, present in every state.
+ *   options   struct_bytes = sizeof(LsnfAdamOptions); the fields are lsnf_adam_step's arguments plus flags and ema_decay
+ *             (read only with EMA).
+ * LSNF_E_ARG, before any HIP call: NULL options, a struct_bytes other than sizeof(LsnfAdamOptions), an unknown flag bit,
+ * ema_decay outside [0, 1) or NaN with EMA, and everything lsnf_adam_step refuses.  Added without an ABI bump (new symbols;
+ * nothing existing changed). */
+#define LSNF_ADAM_AMSGRAD 1u
+#define LSNF_ADAM_DECOUPLED 2u
+#define LSNF_ADAM_MAXIMIZE 4u
+#define LSNF_ADAM_EMA 8u
+#define LSNF_ADAM_SKIP_NONFINITE 16u
+#define LSNF_ADAM_SKIPPED_OFFSET 4104
+typedef struct LsnfAdamOptions {
+    unsigned struct_bytes, flags;
+    double lr;
+    const float* lr_dev;
+    double beta1, beta2, eps, weight_decay, max_norm, ema_decay;
+    float* grad_norm_out;
+} LsnfAdamOptions;
+size_t lsnf_adam_state_bytes_ex(int nz, int width, int depth, int coupling, unsigned flags);   /* 0 on bad geometry or flags */
+int lsnf_adam_step_ex(float* const* params_host, const float* const* grads_host,
+                      int nz, int width, int depth, int coupling, void* state,
+                      const LsnfAdamOptions* options, void* stream);
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,13 @@ class LsnfRng(ctypes.Structure):
     _fields_ = [("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64), ("offset_dev", c_void_p), ("row0", ctypes.c_int64)]
 
 
+class LsnfAdamOptions(ctypes.Structure):
+    """include/lsnf_flow.h `LsnfAdamOptions`: the arguments of lsnf_adam_step_ex."""
+    _fields_ = [("struct_bytes", ctypes.c_uint), ("flags", ctypes.c_uint), ("lr", c_double), ("lr_dev", c_void_p),
+                ("beta1", c_double), ("beta2", c_double), ("eps", c_double), ("weight_decay", c_double), ("max_norm", c_double),
+                ("ema_decay", c_double), ("grad_norm_out", c_void_p)]
+
+
 # name -> (restype, argtypes); mirrors include/lsnf_flow.h one to one
 _SIGNATURES = {
     "lsnf_abi_version": (c_int, []),
@@ -69,6 +76,9 @@ _SIGNATURES = {
     "lsnf_adam_state_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "lsnf_adam_step": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_void_p,
                                c_double, c_void_p, c_double, c_double, c_double, c_double, c_double, c_void_p, c_void_p]),
+    "lsnf_adam_state_bytes_ex": (c_size_t, [c_int, c_int, c_int, c_int, ctypes.c_uint]),
+    "lsnf_adam_step_ex": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_void_p,
+                                  ctypes.POINTER(LsnfAdamOptions), c_void_p]),
 }
 
 _lib = None

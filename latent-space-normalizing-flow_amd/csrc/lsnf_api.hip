@@ -485,40 +485,68 @@ int lsnf_actnorm_init(float* const* params_host, int nz, int width, int depth, i
     return LSNF_OK;
 }
 
+constexpr unsigned kAdamFlags = LSNF_ADAM_AMSGRAD | LSNF_ADAM_DECOUPLED | LSNF_ADAM_MAXIMIZE | LSNF_ADAM_EMA | LSNF_ADAM_SKIP_NONFINITE;
+
 size_t lsnf_adam_state_bytes(int nz, int width, int depth, int coupling) {
+    return lsnf_adam_state_bytes_ex(nz, width, depth, coupling, 0);
+}
+
+size_t lsnf_adam_state_bytes_ex(int nz, int width, int depth, int coupling, unsigned flags) {
     LsnfGeo g;
-    if (lsnf_geo_init(&g, nz, width, depth, coupling)) return 0;
-    return lsnf_adam_bytes(g);
+    if (lsnf_geo_init(&g, nz, width, depth, coupling) || (flags & ~kAdamFlags)) return 0;
+    return lsnf_adam_bytes(g, flags);
+}
+
+// the one body of lsnf_adam_step and lsnf_adam_step_ex; `who` names the entry point in the messages
+static int adam_step(const char* who, float* const* params_host, const float* const* grads_host, int nz, int width, int depth,
+                     int coupling, void* state, const LsnfAdamOptions& o, void* stream) {
+    LsnfGeo g;
+    if (int rc = geo_or_fail(&g, nz, width, depth, coupling)) return rc;
+    if (o.flags & ~kAdamFlags) return fail(LSNF_E_ARG, "%s: unknown flag bits 0x%x", who, o.flags & ~kAdamFlags);
+    if ((o.flags & LSNF_ADAM_EMA) && !(o.ema_decay >= 0.0 && o.ema_decay < 1.0))
+        return fail(LSNF_E_ARG, "%s: ema_decay must lie in [0, 1)", who);
+    if (!params_host || !grads_host || !state) return fail(LSNF_E_ARG, "%s: NULL argument", who);
+    if (!aligned16(state)) return fail(LSNF_E_ARG, "%s: state must be 16-byte aligned", who);
+    if (!aligned4(o.lr_dev) || !aligned4(o.grad_norm_out)) return fail(LSNF_E_ARG, "%s: lr_dev / grad_norm_out must be 4-byte aligned", who);
+    if (!std::isfinite(o.lr) || o.lr < 0.0) return fail(LSNF_E_ARG, "%s: lr must be finite and >= 0", who);
+    if (!std::isfinite(o.eps) || o.eps < 0.0) return fail(LSNF_E_ARG, "%s: eps must be finite and >= 0", who);
+    if (!std::isfinite(o.weight_decay) || o.weight_decay < 0.0) return fail(LSNF_E_ARG, "%s: weight_decay must be finite and >= 0", who);
+    if (!(o.beta1 >= 0.0 && o.beta1 < 1.0) || !(o.beta2 >= 0.0 && o.beta2 < 1.0)) return fail(LSNF_E_ARG, "%s: betas must lie in [0, 1)", who);
+    if (std::isnan(o.max_norm)) return fail(LSNF_E_ARG, "%s: max_norm is NaN", who);
+    for (int i = 0; i < depth * LSNF_PARAMS_PER_BLOCK; ++i) {
+        if (!params_host[i] || !aligned4(params_host[i]))
+            return fail(LSNF_E_ARG, "%s: parameter pointer %d (block %d, slot %d) is NULL or misaligned", who, i,
+                        i / LSNF_PARAMS_PER_BLOCK, i % LSNF_PARAMS_PER_BLOCK);
+        if (!aligned4(grads_host[i]))
+            return fail(LSNF_E_ARG, "%s: gradient pointer %d (block %d, slot %d) is misaligned", who, i,
+                        i / LSNF_PARAMS_PER_BLOCK, i % LSNF_PARAMS_PER_BLOCK);
+    }
+    LsnfAdamCall c;
+    c.g = g; c.params_host = params_host; c.grads_host = grads_host; c.state = state;
+    c.lr = o.lr; c.beta1 = o.beta1; c.beta2 = o.beta2; c.eps = o.eps; c.weight_decay = o.weight_decay; c.max_norm = o.max_norm;
+    c.ema_decay = (o.flags & LSNF_ADAM_EMA) ? o.ema_decay : 0.0; c.flags = o.flags;
+    c.lr_dev = o.lr_dev; c.grad_norm_out = o.grad_norm_out; c.stream = (hipStream_t)stream;
+    hipError_t e = lsnf_launch_adam(c);
+    if (e != hipSuccess) return hip_fail(e, "lsnf_adam_step launch");
+    return LSNF_OK;
 }
 
 int lsnf_adam_step(float* const* params_host, const float* const* grads_host, int nz, int width, int depth, int coupling,
                    void* state, double lr, const float* lr_dev, double beta1, double beta2, double eps, double weight_decay,
                    double max_norm, float* grad_norm_out, void* stream) {
-    LsnfGeo g;
-    if (int rc = geo_or_fail(&g, nz, width, depth, coupling)) return rc;
-    if (!params_host || !grads_host || !state) return fail(LSNF_E_ARG, "lsnf_adam_step: NULL argument");
-    if (!aligned16(state)) return fail(LSNF_E_ARG, "lsnf_adam_step: state must be 16-byte aligned");
-    if (!aligned4(lr_dev) || !aligned4(grad_norm_out)) return fail(LSNF_E_ARG, "lsnf_adam_step: lr_dev / grad_norm_out must be 4-byte aligned");
-    if (!std::isfinite(lr) || lr < 0.0) return fail(LSNF_E_ARG, "lsnf_adam_step: lr must be finite and >= 0");
-    if (!std::isfinite(eps) || eps < 0.0) return fail(LSNF_E_ARG, "lsnf_adam_step: eps must be finite and >= 0");
-    if (!std::isfinite(weight_decay) || weight_decay < 0.0) return fail(LSNF_E_ARG, "lsnf_adam_step: weight_decay must be finite and >= 0");
-    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(LSNF_E_ARG, "lsnf_adam_step: betas must lie in [0, 1)");
-    if (std::isnan(max_norm)) return fail(LSNF_E_ARG, "lsnf_adam_step: max_norm is NaN");
-    for (int i = 0; i < depth * LSNF_PARAMS_PER_BLOCK; ++i) {
-        if (!params_host[i] || !aligned4(params_host[i]))
-            return fail(LSNF_E_ARG, "lsnf_adam_step: parameter pointer %d (block %d, slot %d) is NULL or misaligned", i,
-                        i / LSNF_PARAMS_PER_BLOCK, i % LSNF_PARAMS_PER_BLOCK);
-        if (!aligned4(grads_host[i]))
-            return fail(LSNF_E_ARG, "lsnf_adam_step: gradient pointer %d (block %d, slot %d) is misaligned", i,
-                        i / LSNF_PARAMS_PER_BLOCK, i % LSNF_PARAMS_PER_BLOCK);
-    }
-    LsnfAdamCall c;
-    c.g = g; c.params_host = params_host; c.grads_host = grads_host; c.state = state;
-    c.lr = lr; c.beta1 = beta1; c.beta2 = beta2; c.eps = eps; c.weight_decay = weight_decay; c.max_norm = max_norm;
-    c.lr_dev = lr_dev; c.grad_norm_out = grad_norm_out; c.stream = (hipStream_t)stream;
-    hipError_t e = lsnf_launch_adam(c);
-    if (e != hipSuccess) return hip_fail(e, "lsnf_adam_step launch");
-    return LSNF_OK;
+    LsnfAdamOptions o;
+    o.struct_bytes = sizeof(o); o.flags = 0; o.lr = lr; o.lr_dev = lr_dev; o.beta1 = beta1; o.beta2 = beta2; o.eps = eps;
+    o.weight_decay = weight_decay; o.max_norm = max_norm; o.ema_decay = 0.0; o.grad_norm_out = grad_norm_out;
+    return adam_step("lsnf_adam_step", params_host, grads_host, nz, width, depth, coupling, state, o, stream);
+}
+
+int lsnf_adam_step_ex(float* const* params_host, const float* const* grads_host, int nz, int width, int depth, int coupling,
+                      void* state, const LsnfAdamOptions* options, void* stream) {
+    if (!options) return fail(LSNF_E_ARG, "lsnf_adam_step_ex: NULL options");
+    if (options->struct_bytes != sizeof(LsnfAdamOptions))
+        return fail(LSNF_E_ARG, "lsnf_adam_step_ex: options->struct_bytes is %u, expected %u", options->struct_bytes,
+                    (unsigned)sizeof(LsnfAdamOptions));
+    return adam_step("lsnf_adam_step_ex", params_host, grads_host, nz, width, depth, coupling, state, *options, stream);
 }
 
 int lsnf_params_fast_path(void) { return l16_math() ? 1 : 0; }

@@ -77,10 +77,11 @@ struct LsnfInitCall {                    // lsnf_actnorm_init
     float* const* params_host = nullptr; int B = 0; const float* z_in = nullptr; void* workspace = nullptr;
     hipStream_t stream = nullptr;
 };
-struct LsnfAdamCall {                    // lsnf_adam_step
+struct LsnfAdamCall {                    // lsnf_adam_step, lsnf_adam_step_ex
     LsnfGeo g;
     float* const* params_host = nullptr; const float* const* grads_host = nullptr; void* state = nullptr;
-    double lr = 0.0, beta1 = 0.0, beta2 = 0.0, eps = 0.0, weight_decay = 0.0, max_norm = 0.0;
+    double lr = 0.0, beta1 = 0.0, beta2 = 0.0, eps = 0.0, weight_decay = 0.0, max_norm = 0.0, ema_decay = 0.0;
+    unsigned flags = 0;                  // LSNF_ADAM_*
     const float* lr_dev = nullptr; float* grad_norm_out = nullptr;
     hipStream_t stream = nullptr;
 };
@@ -92,7 +93,7 @@ size_t lsnf_prep_scratch_bytes(int nz, int depth);
 hipError_t lsnf_launch_prepare(const LsnfPrepareCall& c);
 size_t lsnf_init_workspace_bytes(const LsnfGeo& g, int B);
 hipError_t lsnf_launch_actnorm_init(const LsnfInitCall& c);
-size_t lsnf_adam_bytes(const LsnfGeo& g);
+size_t lsnf_adam_bytes(const LsnfGeo& g, unsigned flags);       // (only LSNF_ADAM_AMSGRAD and LSNF_ADAM_EMA count)
 hipError_t lsnf_launch_adam(const LsnfAdamCall& c);
 
 hipError_t lsnf_launch_forward(const LsnfForwardCall& c);

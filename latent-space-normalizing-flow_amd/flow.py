@@ -757,18 +757,27 @@ def backward_params(plan: FlowPlan, params: Sequence[torch.Tensor], z_in: torch.
 
 # ---- optimizer step of the flow (include/lsnf_flow.h lsnf_adam_step) ---------------------------------------------------
 ADAM_MAX_GROUPS, ADAM_STEP_OFFSET, ADAM_PARTIALS_OFFSET, ADAM_NORM_OFFSET, ADAM_HEADER_BYTES = 256, 0, 2048, 4096, 4160
+ADAM_AMSGRAD, ADAM_DECOUPLED, ADAM_MAXIMIZE, ADAM_EMA, ADAM_SKIP_NONFINITE, ADAM_SKIPPED_OFFSET = 1, 2, 4, 8, 16, 4104
 _adam_tables: dict = {}       # state address -> (key, params table, grads table): the ctypes arrays of the last call on that state
 
 
-def adam_state_bytes(nz: int, width: int, depth: int, coupling: int = 1) -> int:
-    """Bytes of the optimizer state of `adam_step` (0 on an unsupported geometry)."""
-    return int(_lib.load().lsnf_adam_state_bytes(int(nz), int(width), int(depth), int(coupling)))
+def _adam_size_flags(amsgrad: bool, ema: bool) -> int:
+    return (ADAM_AMSGRAD if amsgrad else 0) | (ADAM_EMA if ema else 0)
 
 
-def new_adam_state(nz: int, width: int, depth: int, coupling: int, device) -> torch.Tensor:
+def adam_state_bytes(nz: int, width: int, depth: int, coupling: int = 1, amsgrad: bool = False, ema: bool = False) -> int:
+    """Bytes of the optimizer state of `adam_step` (0 on an unsupported geometry); amsgrad / ema: with the array each adds."""
+    geo, flags = (int(nz), int(width), int(depth), int(coupling)), _adam_size_flags(amsgrad, ema)
+    lib = _lib.load()
+    return int(lib.lsnf_adam_state_bytes_ex(*geo, flags) if flags else lib.lsnf_adam_state_bytes(*geo))
+
+
+def new_adam_state(nz: int, width: int, depth: int, coupling: int, device, amsgrad: bool = False, ema: bool = False) -> torch.Tensor:
     """A fresh (all-zero) optimizer state for `adam_step`: one float32 buffer holding the header (step counters, norm
-    partials, the last norm) followed by m and v, flat in ABI tensor order (`adam_state_views`)."""
-    need = adam_state_bytes(nz, width, depth, coupling)
+    partials, the last norm, the skipped count) followed by m and v, flat in ABI tensor order (`adam_state_views`), then vmax
+    (amsgrad) and the weight average (ema) in the same order (`adam_state_extra_views`).  A state serves the amsgrad / ema it
+    was made for: pass the same two to every `adam_step` on it."""
+    need = adam_state_bytes(nz, width, depth, coupling, amsgrad, ema)
     if need == 0:
         raise LsnfError(f"unsupported geometry nz={nz} width={width} depth={depth} coupling={coupling}")
     return torch.zeros(need // 4, dtype=torch.float32, device=device)
@@ -789,16 +798,40 @@ def adam_state_views(state: torch.Tensor, nz: int, width: int, depth: int, coupl
     return steps, norm, m, v
 
 
+def adam_state_extra_views(state, nz: int, width: int, depth: int, coupling: int = 1, amsgrad: bool = False, ema: bool = False):
+    """(vmax | None, ema | None, skipped) as views of a state made with these amsgrad / ema: vmax (amsgrad's running maximum of
+    v) and ema (the weight average) are lists of depth*12 tensors shaped like the parameters, None without the option;
+    skipped = the int64 count of steps that SKIP_NONFINITE refused (0-dim; in the header of every state).  Launches nothing."""
+    shapes = _param_shapes(nz, width, coupling) * depth
+    sizes = [a * b for a, b in shapes]
+    n4 = (sum(sizes) + 3) // 4 * 4
+    h = ADAM_HEADER_BYTES // 4
+    if state.numel() < h + (2 + bool(amsgrad) + bool(ema)) * n4:
+        raise LsnfError(f"state has {state.numel()} floats: not one of new_adam_state(amsgrad={bool(amsgrad)}, ema={bool(ema)})")
+
+    def array(k):
+        return [t.view(sh) for t, sh in zip(state[h + k * n4: h + k * n4 + sum(sizes)].split(sizes), shapes)]
+    skipped = state[ADAM_SKIPPED_OFFSET // 4: ADAM_SKIPPED_OFFSET // 4 + 2].view(torch.int64)[0]
+    return (array(2) if amsgrad else None), (array(2 + bool(amsgrad)) if ema else None), skipped
+
+
 def adam_step(params: Sequence[torch.Tensor], grads: Sequence[Optional[torch.Tensor]], state: torch.Tensor,
               nz: int, width: int, depth: int, coupling: int = 1, *, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999),
               eps: float = 1e-8, weight_decay: float = 0.0, max_norm: Optional[float] = None,
-              lr_dev: Optional[torch.Tensor] = None, want_norm: bool = False) -> Optional[torch.Tensor]:
+              lr_dev: Optional[torch.Tensor] = None, want_norm: bool = False, amsgrad: bool = False, maximize: bool = False,
+              decoupled_weight_decay: bool = False, ema_decay: Optional[float] = None,
+              skip_nonfinite: bool = False) -> Optional[torch.Tensor]:
     """Global-norm clip + Adam on the device (`lsnf_adam_step`; train.py:413-415): updates the depth*12 tensors `params` in
     place from `grads` (a None entry skips that tensor: parameter, m and v keep their bits, as torch treats `grad is None`)
-    and the moments in `state` (`new_adam_state`).  torch.optim.Adam's arithmetic (no amsgrad, L2 weight decay);
+    and the moments in `state` (`new_adam_state`).  torch.optim.Adam's arithmetic (L2 weight decay);
     max_norm: clip the global gradient norm first (`clip_grad_norm_`'s formula), None = no clipping.  lr_dev: one float32 on
     the device that replaces `lr` (schedules under a captured graph).  Returns the pre-clip global norm as a 0-dim view of the
-    state's norm slot when max_norm is given or want_norm is set (the norm launch runs only then), else None.
+    state's norm slot when max_norm is given or want_norm or skip_nonfinite is set (the norm launch runs only then), else None.
+    Variants (`lsnf_adam_step_ex`; none set: the call above, bit for bit): amsgrad, maximize, decoupled_weight_decay (AdamW:
+    p *= 1 - lr * weight_decay instead of g += weight_decay * p) as in torch; ema_decay: keep an exponential moving average of
+    the written parameters in the state (a tensor without a gradient takes part; the average starts from the parameters the
+    first step finds); skip_nonfinite: a step whose gradient norm is inf or NaN writes nothing but the norm and the state's
+    skipped count.  amsgrad and ema_decay need a state made with them and are passed at every call on it.
     One or two launches on the current stream, no synchronisation, no allocation.  Plans prepared from `params` are stale
     afterwards.  Every argument is checked before anything is launched; a bad one raises LsnfError."""
     lib = _lib.load()
@@ -809,16 +842,24 @@ def adam_step(params: Sequence[torch.Tensor], grads: Sequence[Optional[torch.Ten
         raise LsnfError(f"expected {n} parameter tensors and {n} gradients (None allowed), got {len(params)} and {len(grads)}")
     if state is None:
         raise LsnfError("state is required (new_adam_state())")
+    flags = 0
+    ema = ema_decay is not None
+    if amsgrad or maximize or decoupled_weight_decay or skip_nonfinite or ema:      # (one test on the plain step's path)
+        if ema and not 0.0 <= float(ema_decay) < 1.0:
+            raise LsnfError(f"ema_decay must lie in [0, 1) or be None (got {ema_decay})")
+        flags = (_adam_size_flags(amsgrad, ema) | (ADAM_MAXIMIZE if maximize else 0) | (ADAM_DECOUPLED if decoupled_weight_decay else 0)
+                 | (ADAM_SKIP_NONFINITE if skip_nonfinite else 0))
     # the checks and the pointer tables are kept per state buffer, keyed by the tensors' addresses (as backward_params does):
     # a training loop hands over the same storages every step
-    key = (geo, state.numel(), tuple(t.data_ptr() for t in params), tuple(0 if g is None else g.data_ptr() for g in grads))
+    key = (geo, state.numel(), tuple(t.data_ptr() for t in params), tuple(0 if g is None else g.data_ptr() for g in grads),
+           flags & (ADAM_AMSGRAD | ADAM_EMA))
     tab = _adam_tables.get(state.data_ptr())
     if tab is None or tab[0] != key:
-        need = lib.lsnf_adam_state_bytes(*geo)
+        need = adam_state_bytes(*geo, amsgrad, ema)
         if need == 0:
             raise LsnfError(f"unsupported geometry nz={nz} width={width} depth={depth} coupling={coupling}")
         dev = state.device
-        _check_out(state, "state", need // 4, dev, hint="from new_adam_state()")
+        _check_out(state, "state", need // 4, dev, hint=f"from new_adam_state({'amsgrad=True' if amsgrad else ''}{', ' if amsgrad and ema else ''}{'ema=True' if ema else ''})")
         if state.data_ptr() % 16:
             raise LsnfError("state must be 16-byte aligned")
         _check_params(params, nz, width, depth, coupling, dev, "state")
@@ -830,7 +871,13 @@ def adam_step(params: Sequence[torch.Tensor], grads: Sequence[Optional[torch.Ten
     dev = state.device
     if lr_dev is not None:
         _check_out(lr_dev, "lr_dev", 1, dev)
-    norm = state[ADAM_NORM_OFFSET // 4] if (max_norm is not None or want_norm) else None
-    _call("lsnf_adam_step", dev, tab[1], tab[2], nz, width, depth, coupling, _ptr(state), float(lr), _ptr(lr_dev),
-          float(betas[0]), float(betas[1]), float(eps), float(weight_decay), 0.0 if max_norm is None else float(max_norm), _ptr(norm))
+    norm = state[ADAM_NORM_OFFSET // 4] if (max_norm is not None or want_norm or skip_nonfinite) else None
+    mn = 0.0 if max_norm is None else float(max_norm)
+    if flags == 0:
+        _call("lsnf_adam_step", dev, tab[1], tab[2], nz, width, depth, coupling, _ptr(state), float(lr), _ptr(lr_dev),
+              float(betas[0]), float(betas[1]), float(eps), float(weight_decay), mn, _ptr(norm))
+    else:
+        opts = _lib.LsnfAdamOptions(ctypes.sizeof(_lib.LsnfAdamOptions), flags, float(lr), _ptr(lr_dev), float(betas[0]), float(betas[1]),
+                                    float(eps), float(weight_decay), mn, float(ema_decay) if ema else 0.0, _ptr(norm))
+        _call("lsnf_adam_step_ex", dev, tab[1], tab[2], nz, width, depth, coupling, _ptr(state), ctypes.byref(opts))
     return norm

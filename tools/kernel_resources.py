@@ -96,7 +96,8 @@ def kernels_of(obj):
     cur = None
     for line in notes.splitlines():
         s = line.strip()
-        if s.startswith("- "):                               # a new entry of a YAML list (kernels, or their args)
+        if s.startswith("- ") and (line.startswith("  - ") or cur is None):      # a new entry of the kernels' list: not an
+            # argument or a `.language_version` item, which sit deeper and would drop the fields read so far (AGPRs, LDS)
             if cur and ".name" in cur and ".vgpr_count" in cur:
                 out[_short(cur[".name"])] = {k: int(cur.get(f, 0)) for k, f in FIELDS}
             cur, s = {}, s[2:].strip()
@@ -120,7 +121,9 @@ def collect(build_dir, match):
 
 
 def _base(name):
-    return re.sub(r"<false>$", "", re.sub(r", false>$", ">", name))      # (`kernel<false>` was plain `kernel`)
+    while name.endswith(", false>"):                                     # (a kernel may have gained several flags at once)
+        name = name[: -len(", false>")] + ">"
+    return re.sub(r"<false>$", "", name)                                 # (`kernel<false>` was plain `kernel`)
 
 
 def main():
