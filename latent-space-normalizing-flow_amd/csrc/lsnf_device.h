@@ -105,9 +105,6 @@ __device__ __forceinline__ constexpr int lsnf_feat(int r, int h) { return (r & 3
 // Each wave-instruction moves 1 KiB (64 lanes x 16 B), destination = wave-uniform base + lane*16.
 template <int KT, int NW = LSNF_WG_WAVES>
 __device__ __forceinline__ void lsnf_issue_panel(const float* __restrict__ gsrc, float* lbuf, int wave, int lane) {
-#ifdef LSNF_ABLATE_DMA   // timing diagnostic only (wrong numbers): prices the L2 -> LDS weight stream and its power
-    return;
-#endif
     constexpr int PIECES = 4 * KT;                 // 1 KiB pieces of this panel (pair)
     constexpr int PER_WAVE = (PIECES + NW - 1) / NW;
 #pragma unroll
@@ -126,9 +123,7 @@ __device__ __forceinline__ void lsnf_issue_panel(const float* __restrict__ gsrc,
 // reading the panel that was consumed before.
 __device__ __forceinline__ void lsnf_panel_barrier() {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifndef LSNF_ABLATE_BARRIER   // timing diagnostic only (racy): prices the per-panel workgroup barrier
     __syncthreads();
-#endif
 }
 
 // ---- one panel of MFMAs: acc(32 features x 32 samples) += W_panel^T * in ----------------------
@@ -205,21 +200,9 @@ __device__ __forceinline__ void lsnf_sigmoid_log2(float p, float& sig, float& l2
 //   reference: scale = sigmoid(h[:,1::2] + 2) (model.py:413; the +2 is folded into the bias),
 //              log(scale) (model.py:418)
 __device__ __forceinline__ void lsnf_sigmoid_logsig(float p, float& sig, float& lsig) {
-#ifdef LSNF_ABLATE_EPILOGUE   // timing diagnostic only (wrong numbers): prices the transcendental epilogue
-    sig = p * 0.25f + 0.5f; lsig = p; return;
-#endif
-#ifdef LSNF_OCML_MATH               // reference build of the epilogue on OCML expf/log1pf (slow, ~110 VALU/element)
-    const float a = fabsf(p);
-    const float e = expf(-a);
-    const float r = 1.0f / (1.0f + e);
-    const float l = log1pf(e);
-    sig = (p >= 0.0f) ? r : e * r;
-    lsig = fminf(p, 0.0f) - l;
-#else
     float l2;
     lsnf_sigmoid_log2(p, sig, l2);
     lsig = -0.6931471805599453f * l2;
-#endif
 }
 
 // Lane exchanges on the vector ALU (gfx950: v_permlane16_swap / v_permlane32_swap; __shfl_xor goes through the LDS crossbar:
@@ -361,12 +344,10 @@ __device__ __forceinline__ void lsnf_panel_mma2(f32x16& acc0, f32x16& acc1, cons
     for (int H = 0; H < 2 * KT; ++H) {                       // half k-tiles: groups 2H, 2H+1
         const int kt = H >> 1, g0 = (H & 1) * 2;
         f32x4 na0 = a0, na1 = a1, nb0 = b0, nb1 = b1;
-#ifndef LSNF_ABLATE_LDSREAD   // timing diagnostic only (wrong numbers): prices the LDS fragment reads / their power
         if (H + 1 < 2 * KT) {
             na0 = wp[(2 * H + 2) * 64]; na1 = wp[(2 * H + 3) * 64];
             nb0 = wp[T1 + (2 * H + 2) * 64]; nb1 = wp[T1 + (2 * H + 3) * 64];
         }
-#endif
 #define LSNF_MFMA2(WA, WB, G)                                                                         \
         acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(WA[0], in[kt][4 * (G) + 0], acc0, 0, 0, 0);       \
         acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(WB[0], in[kt][4 * (G) + 0], acc1, 0, 0, 0);       \

@@ -83,16 +83,8 @@ __global__ __launch_bounds__(64 * FWD_WAVES, 2) void lsnf_fwd_kernel(const FwdAr
     const long row = live ? sample : (long)a.B - 1;
 
     f32x16 x[NZT];
-#ifdef LSNF_ABLATE_IO    // timing diagnostic only: no HBM reads of z (prices the exposed prologue load)
-#pragma unroll
-    for (int t = 0; t < NZT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) x[t][r] = 0.001f * (float)(lane + r + t);
-    float ell = 0.0f;
-#else
     lsnf_load_rows<HT>(x, a.z_in, row, a.nz, a.half, h, a.vec4);
     float ell = a.objective ? a.objective[row] : 0.0f;
-#endif
 
     LSNF_STAMP(1);
     const LsnfActLayout al = lsnf_act_layout(a.B, HT, WT);
@@ -178,9 +170,6 @@ __global__ __launch_bounds__(64 * FWD_WAVES, 2) void lsnf_fwd_kernel(const FwdAr
 #pragma unroll
         for (int r = 0; r < 16; ++r) ss += x[t][r] * x[t][r];
     ss = lsnf_pair_sum(ss);
-#ifdef LSNF_ABLATE_IO
-    if (ss != 123.456f) return;   // keeps the computation alive, stores (practically) never happen
-#endif
     if (live) {
         {   // second half only: the first half went out during the last block
             float* zo = a.z_out + sample * (long)a.nz;

@@ -154,25 +154,16 @@ __global__ __launch_bounds__(64 * F3_WAVES, 1) void lsnf_fwd3b_kernel(const Fwd3
                 pipe, gblk, gblk + C::OFF3_S2, v, xs, [&](int t) { return l16_bias_init(cb + 32 * t, g); }, keep);
         }
         // f_width 128 with two waves per SIMD (256 registers): the four split tiles of h1 / h2 (96 registers), four finished and two
-        // running accumulators of S3 / S4 do not fit beside v (64): hipcc spills ~49 registers to scratch there.  Tried instead
-        // (PARK, off): v1 / v2 parked in this wave's OWN z_out rows between S2's split and the end of the block -- zero scratch,
-        // but 262 MB of extra row traffic per launch at B = 65 536: 186 us against 153 us with hipcc's spills (bf16x3; fp16x2
-        // 133 vs 92; tools/ab_c5.py, two alternations on one box).  The compiler's choice of WHAT to spill is the cheaper one.
-#ifdef LSNF_PARK_V
-        constexpr bool PARK = WT == 4 && F3_WAVES == 8;
-#else
-        constexpr bool PARK = false;
-#endif
-        if (PARK || !more) {     // last block: the v1 half is final (model.py:422) -- its stores drain under the MFMAs of S2..S4
+        // running accumulators of S3 / S4 do not fit beside v (64): hipcc spills ~49 registers to scratch there.  Tried instead, and
+        // removed: v1 / v2 parked in this wave's OWN z_out rows between S2's split and the end of the block -- that had zero scratch,
+        // but 262 MB of extra row traffic per launch at B = 65 536: it measured 186 us against 153 us with hipcc's spills (bf16x3;
+        // fp16x2 133 vs 92; two alternations on one box).  The compiler's choice of WHAT to spill was the cheaper one.
+        if (!more) {     // last block: the v1 half is final (model.py:422) -- its stores drain under the MFMAs of S2..S4
 #pragma unroll
             for (int t = 0; t < HT; ++t) l16_store_tile<HT>(t, v[t], a.z_out, sample, live, a.nz, a.half, g, a.vec4);
         }
 #pragma unroll
         for (int st = 0; st < 2; ++st) { ell[st] = ell[st] + cb[32 * C::NP + 0]; ell[st] = ell[st] + cb[32 * C::NP + 1]; }
-        if constexpr (PARK) {
-#pragma unroll
-            for (int t = HT; t < NZT; ++t) l16_store_tile<HT>(t, v[t], a.z_out, sample, live, a.nz, a.half, g, a.vec4);
-        }
         // ---- S2: h1 = relu(actnorm(v1 @ W1))  (model.py:326-328,307) ----
         f32x16 h1[WT];
         {
@@ -221,10 +212,6 @@ __global__ __launch_bounds__(64 * F3_WAVES, 1) void lsnf_fwd3b_kernel(const Fwd3
             l16_gemm_stage3<C::P4, C::KT4, first_kib(C::P1, C::KT1)>(
                 pipe, gblk + C::OFF3_S4, gnext, tp, hs,
                 [&](int t) { return l16_bias_init(cb + 32 * (C::P1 + C::P2 + C::P3 + t), g); }, keep);
-        }
-        if constexpr (PARK) {        // v back from its parking place (rows of dead samples: the clamped row's values, never stored)
-#pragma unroll
-            for (int t = 0; t < NZT; ++t) v[t] = l16_load_tile<HT>(t, a.z_out, rows, a.nz, a.half, g, a.vec4);
         }
         // ---- coupling + per-sample log-scale reduction (model.py:414-418), concat (:422) ----
         float lsum[2] = {0.0f, 0.0f};

@@ -38,16 +38,8 @@
 #error "lsnf_fwd3p.hip is the three-term bf16 kernel"
 #endif
 
-#ifndef LSNF_FILLMASK
-#define LSNF_FILLMASK 0x7f   // diagnostic builds: which phases carry their vector work (register-pressure bisection)
-#endif
-
-#ifndef LSNF_PAIR_DMA_PER_STEP
-#define LSNF_PAIR_DMA_PER_STEP 6   // CU-sharing form: LDS-DMA pieces at the head of each step of a half-phase until the wave's six are out (1, 2, 3, 6)
-#endif
-#ifndef LSNF_FWD3Q_LARGE
-#define LSNF_FWD3Q_LARGE 242   // shape code of the plain forward above 32 768 rows (lsnf_launch_forward3q): 242 or 82
-#endif
+constexpr int LSNF_PAIR_DMA_PER_STEP = 6;   // CU-sharing form: LDS-DMA pieces at the head of each step of a half-phase until the wave's six are out (1, 2, 3, 6)
+constexpr int LSNF_FWD3Q_LARGE = 242;       // shape code of the plain forward above 32 768 rows (lsnf_launch_forward3q): 242 or 82
 
 namespace {
 
@@ -225,12 +217,6 @@ __device__ __forceinline__ void couple_q16(Tile16& v, const Tile16& t, const Til
 // All of them are raw BUFFER stores: one straight-line instruction each -- no branch splits the pinned schedule of a step --, and the
 // descriptor's byte count drops what must not land: rows past the batch, the tiles of a wave past the batch, and (offset 2^31) the
 // 4-feature groups past `half` of a row's padded second tile.
-#ifndef LSNF_STASH_AUX
-#define LSNF_STASH_AUX 0      // cache-policy bits of the stash stores (experiment knob: 2 = nt)
-#endif
-#ifndef LSNF_STASH_PARTS
-#define LSNF_STASH_PARTS 7    // timing diagnostics (wrong stash): 1 = ReLU masks, 2 = sigma tiles, 4 = block output rows
-#endif
 typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
 struct StashLane { unsigned zoff, soff, moff, msh, hoff; };   // per-lane byte offsets: row store, sigma tile, mask words; mask shift 4 * (g >> 1)
 // (every store below has soffset = 0: a uniform byte offset -- the second half of a row, the second sigma tile -- is a second descriptor,
@@ -246,26 +232,23 @@ __device__ __forceinline__ StashRsrc stash_rsrc(const float* p, unsigned bytes, 
 // quad q = 2*ft + st of tile t -> its 16 bytes of row `16*st + n` (the layout of store_tile16 at vec4 == 4)
 template <int HT>
 __device__ __forceinline__ void stash_row_quad(const StashRsrc& rs, const StashLane& sl, int t, int q, const Tile16& x, int nz, int half, int g) {
-    if constexpr (!(LSNF_STASH_PARTS & 4)) return;
     const int ft = q >> 1, st = q & 1, hh = t / HT, tt = t % HT;
     unsigned off = sl.zoff;
     if (st) off += (unsigned)(16 * nz * 4);
     off = (32 * tt + 16 * ft + 4 * g < half) ? off : 0x80000000u;        // (nz <= 64 runs on this HT = 2 kernel too: half < 32 pads tile 0 as well)
     // (the whole vector is cast: __builtin_bit_cast of ONE element of an ext_vector lvalue reads element 0 with this compiler)
     const u32x4s v = __builtin_bit_cast(u32x4s, x.q[q]);
-    __builtin_amdgcn_raw_buffer_store_b128(v, rs.r[hh], off + (unsigned)((32 * tt + 16 * ft) * 4), 0, LSNF_STASH_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(v, rs.r[hh], off + (unsigned)((32 * tt + 16 * ft) * 4), 0, 0);
 }
 // sigma quad q of feature tile t (l16_store_sigma's layout: [2*ft + (g >> 1)][16*st + n + 32*(g & 1)][4])
 __device__ __forceinline__ void stash_sigma_quad(const StashRsrc& rs, const StashLane& sl, int t, int q, const Tile16& sg) {
-    if constexpr (!(LSNF_STASH_PARTS & 2)) return;
     const int ft = q >> 1, st = q & 1;
     const u32x4s v = __builtin_bit_cast(u32x4s, sg.q[q]);
-    __builtin_amdgcn_raw_buffer_store_b128(v, rs.r[t], sl.soff + (unsigned)((2 * ft * 64 + 16 * st) * 16), 0, LSNF_STASH_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(v, rs.r[t], sl.soff + (unsigned)((2 * ft * 64 + 16 * st) * 16), 0, 0);
 }
 // ReLU bits of quad q of a hidden tile: bit r = (h[r] > 0).  The sign of (+0 - h) IS that predicate (-(+-0) = +0, no NaNs here), and
 // v_alignbit shifts it in: 2 VALU per value instead of compare + select + shift/or.
 __device__ __forceinline__ void mask_q16(const Tile16& h, int q, unsigned (&mk)[2][2]) {
-    if constexpr (!(LSNF_STASH_PARTS & 1)) return;
     unsigned m = 0;
 #pragma unroll
     for (int r = 3; r >= 0; --r) m = __builtin_amdgcn_alignbit(m, __builtin_bit_cast(unsigned, 0.0f - h.q[q][r]), 31);
@@ -275,7 +258,6 @@ __device__ __forceinline__ void mask_q16(const Tile16& h, int q, unsigned (&mk)[
 // the two mask words of a tile (l16_store_masks' format: bit 4*(2*ft + (g >> 1)) + r of word 16*st + n + 32*(g & 1)); all 64 lanes
 // store -- lanes l and l + 32 hold the same word after the exchange and write it to the same address
 __device__ __forceinline__ void stash_mask_words(const StashRsrc& rs, const StashLane& sl, int tile, const unsigned (&mk)[2][2]) {
-    if constexpr (!(LSNF_STASH_PARTS & 1)) return;
     const unsigned w0 = mk[0][0] | (mk[0][1] << 8), w1 = mk[1][0] | (mk[1][1] << 8);
     unsigned x = ((w0 << 16) | w1) << sl.msh;
     x = lsnf_pair_or32(x);
@@ -291,7 +273,7 @@ __device__ __forceinline__ void stash_h_quad(const StashRsrc& rs, const StashLan
 #pragma unroll
     for (int j = 0; j < 4; ++j) r[j] = fmaxf(h.q[q][j], 0.0f);         // (the same v_max as the split's: one instruction serves both)
     const unsigned off = (32 * t + 16 * ft < width) ? sl.hoff : 0x80000000u;
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4s, r), rs.r[t], off + (unsigned)((ft * 2 + st) * 1024), 0, LSNF_STASH_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4s, r), rs.r[t], off + (unsigned)((ft * 2 + st) * 1024), 0, 0);
 }
 
 template <int NM, int NV>
@@ -326,19 +308,13 @@ __device__ __forceinline__ void run_phase16(Tile16* acc, const float* bias_ptr /
             for (int p = 0; p < 3; ++p) na[p] = wp[(PH::at(i + 1).frag + p) * 64];
             if constexpr (first_touch<PH>(i + 1)) nbq = bias_quad(bias_ptr, 32 * PH::btile(PH::at(i + 1).acc) + 8 * PH::at(i + 1).s);
         }
-#ifndef LSNF_ABL_NOFILL
         fill(ic);
-#endif
         const SplitTile16& x = in[d.tile];
         constexpr bool first = first_touch<PH>(i);
 #define LSNF_Q_MMA(WI, XI) \
         acc[d.acc].q[2 * d.s + 0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[WI], __builtin_bit_cast(bf16x8, u32x4{x.d[0][XI][0], x.d[0][XI][1], x.d[0][XI][2], x.d[0][XI][3]}), (first && WI == 2 && XI == 0) ? bq : acc[d.acc].q[2 * d.s + 0], 0, 0, 0); \
         if constexpr (ST == 2) acc[d.acc].q[2 * d.s + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[WI], __builtin_bit_cast(bf16x8, u32x4{x.d[1][XI][0], x.d[1][XI][1], x.d[1][XI][2], x.d[1][XI][3]}), (first && WI == 2 && XI == 0) ? bq : acc[d.acc].q[2 * d.s + 1], 0, 0, 0);
-#ifdef LSNF_ABL_NOMFMA
-        LSNF_Q_MMA(0, 0)
-#else
         LSNF_F3_TERMS(LSNF_Q_MMA)
-#endif
 #undef LSNF_Q_MMA
         if constexpr (i + 1 < PH::N) __builtin_amdgcn_sched_group_barrier(0x100, first_touch<PH>(i + 1) ? 4 : 3, 0);
         pin_mfma<6 * ST, (PH::valu(i) * ST) / 2>();
@@ -539,15 +515,8 @@ __global__ __launch_bounds__(64 * NWAVES, PAIR ? 2 : 1) void lsnf_fwd3q_kernel(c
     // the free buffer -- no DMA under a branch; the epilogue waits for it before LDS is reused or released.
     // (STASH: `left` = the stash stores of the phase just run that may stay in flight, see stores_after())
     auto sync_issue = [&](int k, auto left) {
-#ifdef LSNF_ABL_SKIPSYNC       // timing diagnostic (racy, wrong numbers): phase boundaries (k & 3) in the mask are not synchronised at all
-        if ((LSNF_ABL_SKIPSYNC >> (k & 3)) & 1) return;
-#endif
         asm volatile("s_waitcnt vmcnt(%0)" :: "n"(decltype(left)::value) : "memory");
         __syncthreads();
-#ifdef LSNF_FWD3Q_BURST_DMA
-        static_assert(!PAIR, "the burst-DMA timing build fills whole 48 KiB buffers: the CU-sharing form has none");
-        if (k + 1 < n_phases) issue_kib<48, NWAVES>(phase_src(k + 1), buf0 + ((k + 1) & 1) * SLOT, wave, lane);
-#endif
     };
     // pieces per wave and phase; one every EVERY steps (STASH: one per step from step 0, so that the steps behind them can hold the stores)
     constexpr int PER_WAVE = 48 / NWAVES, EVERY = STASH ? 1 : 16 / PER_WAVE, LAST_DMA = (PER_WAVE - 1) * EVERY;
@@ -562,7 +531,6 @@ __global__ __launch_bounds__(64 * NWAVES, PAIR ? 2 : 1) void lsnf_fwd3q_kernel(c
         dma_dst = buf0 + ((k + 1) & 1) * SLOT;
     };
     auto dma_step = [&](auto ic) {
-#ifndef LSNF_FWD3Q_BURST_DMA
         constexpr int i = decltype(ic)::value;
         if constexpr (PAIR) {
             // this wave's chunk: six pieces, PS at the head of a step.  A half-phase is 8 steps, half the time the 8-wave form has for
@@ -574,7 +542,6 @@ __global__ __launch_bounds__(64 * NWAVES, PAIR ? 2 : 1) void lsnf_fwd3q_kernel(c
                 for (int s = i * PS; s < i * PS + PS && s < 6; ++s) issue_piece_at(dma_src, dma_dst, s, lane);
             }
         } else if constexpr (i % EVERY == 0 && i / EVERY < PER_WAVE) issue_piece<NWAVES>(dma_src, dma_dst, i / EVERY, wave, lane);
-#endif
     };
     // PAIR.  Half-phase (k, h) reads buffer h.  Barrier in front of it: my pieces of it have landed, everybody's have, and buffer h ^ 1
     // is free; its steps then carry the next half-phase's pieces -- (k, 1) behind (k, 0), (k + 1, 0) behind (k, 1).  The last half-phase

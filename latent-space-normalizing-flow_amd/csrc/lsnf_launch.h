@@ -170,11 +170,11 @@ inline auto lsnf_with_st(int st, F&& f) {
 }
 // Rows per workgroup / 16 the latency kernels WANT, by batch size: 16 rows while one round of workgroups covers the batch (<= 256
 // CUs x 16 rows), then 32, then 64 -- the weight stream per workgroup is the same, so a second round costs a whole stream while a
-// second sample tile costs its MFMAs only (`also2`: a caller's further reason to stay at 32).  LSNF_SMALL3_ST (1 / 2 / 4) forces a
-// shape (experiments, tests).  Each kernel then gives way to the next smaller shape it has.
-inline int lsnf_small3_st_wanted(int B, bool also2) {
+// second sample tile costs its MFMAs only.  LSNF_SMALL3_ST (1 / 2 / 4) forces a shape (experiments, tests).  Each kernel then gives
+// way to the next smaller shape it has.
+inline int lsnf_small3_st_wanted(int B) {
     static const char* env = getenv("LSNF_SMALL3_ST");
-    return env ? atoi(env) : (B <= 256 * 16 ? 1 : ((B <= 256 * 32 || also2) ? 2 : 4));
+    return env ? atoi(env) : (B <= 256 * 16 ? 1 : (B <= 256 * 32 ? 2 : 4));
 }
 // 8 waves (256-row workgroups) or 4 for the bf16 throughput kernels: 256-row workgroups need B > 32 768 to put one on (almost)
 // every CU; below that 128-row workgroups use twice the CUs.  LSNF_FORCE_WAVES (4 / 8): experiment knob of tools/.

@@ -34,7 +34,6 @@ struct TnArgs {
     const float* z_in; const float* z_out; const float* z_saved;
     const float* dump; float* fold;    // DET: the partials area (slot (chunk, block) at ((chunk * depth) + block) * per_block)
     int B, nz, half, width, depth, chunk;
-    int abl;                           // timing experiments only (tools/): 1 no atomics, 2 no MFMA, 4 no global loads after the first stage
 };
 
 // Output tiles (kt, nt) of a task (KT x NT tiles of 32 x 32) over the 4 waves, so that every wave (SIMD) has matrix work for every
@@ -155,9 +154,7 @@ __global__ __launch_bounds__(256) void lsnf_tn_gemm_kernel(const TnArgs a) {
 // TN_S samples of A (S x K) and G (S x N) with 16-byte row loads (each element read ONCE per workgroup), double-buffered,
 // and every wave reads its MFMA operands from LDS (one conflict-free ds_read_b32 per operand: lanes run along the
 // feature index).  Same tasks, same atomics into the folded buffer.
-#ifndef TN_S
-#define TN_S 16                         // samples per stage (32 KiB of LDS per workgroup: five workgroups per CU overlap each other's stage turnover)
-#endif
+constexpr int TN_S = 16;                 // samples per stage (32 KiB of LDS per workgroup: five workgroups per CU overlap each other's stage turnover)
 template <int VW>                       // vector width of the row loads: 4 / 2 / 1 floats (alignment of the task's A and G rows)
 __device__ __forceinline__ void tn_stage_load(float (&regs)[TN_S * 128 / 256], const float* __restrict__ src, int ld, int ncols, int m0, int m_end,
                                               int tid) {
@@ -231,7 +228,7 @@ __global__ __launch_bounds__(256) void lsnf_tn_gemm_lds_kernel(const TnArgs a) {
     int cur = 0;
     for (int m0 = m_begin; m0 < m_end; m0 += TN_S) {
         const bool more = m0 + TN_S < m_end;      // workgroup-uniform
-        if (more && !(a.abl & 4)) {                // next stage's rows in flight under this stage's MFMAs
+        if (more) {                                // next stage's rows in flight under this stage's MFMAs
             tn_stage_load<VW>(ra, A, lda, K, m0 + TN_S, m_end, tid);
             tn_stage_load<VW>(rg, G, ldg, N, m0 + TN_S, m_end, tid);
         }
@@ -246,7 +243,7 @@ __global__ __launch_bounds__(256) void lsnf_tn_gemm_lds_kernel(const TnArgs a) {
                     if ((own >> t) & 1u) {
                         const float gv = pg[u * 256 + 32 * t];
                         csum[t] += gv;
-                        if (!(a.abl & 2)) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, gv, acc[t], 0, 0, 0);
+                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, gv, acc[t], 0, 0, 0);
                     }
                 }
             }
@@ -259,7 +256,6 @@ __global__ __launch_bounds__(256) void lsnf_tn_gemm_lds_kernel(const TnArgs a) {
         cur ^= 1;
     }
     if (!kwave) return;
-    if ((a.abl & 1) && blockIdx.y != 0) return;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         if ((own >> t) & 1u) {
@@ -461,14 +457,12 @@ hipError_t lsnf_launch_params_contract(const LsnfContractCall& c, int contractio
     t.dump = fold + (size_t)g.depth * lsnf_fold_layout(g.nz, g.width).per_block;
     t.B = c.B; t.nz = g.nz; t.half = g.half; t.width = g.width; t.depth = g.depth;
     t.chunk = c.B >= 16384 ? 512 : 128;              // samples per workgroup (multiple of 16; 512: 3 200 workgroups at B = 65 536 -- measured 620 us for the whole call against 672 at 1 024 and 760 at 2 048)
-    // experiment knobs of tools/tn_probe.py (read once per process): ablation switches, samples per workgroup
-    static const int knob_abl = [] { const char* e = getenv("LSNF_TN_ABL"); return e ? atoi(e) : 0; }();
+    // experiment knob of tools/tn_probe.py (read once per process): samples per workgroup
     static const int knob_chunk = [] { const char* e = getenv("LSNF_TN_CHUNK"); return e ? atoi(e) : 0; }();
-    t.abl = knob_abl;
     if (knob_chunk > 0) t.chunk = knob_chunk;
     if (c.det) {      // the partials area behind the tag word; chunking by (B, depth, kind) alone: no knobs
         t.fold = c.workspace + lsnf_params_det_partials(g.nz, g.width, g.depth, c.B);
-        t.abl = 0; t.chunk = lsnf_det_chunk_rows(c.B, g.depth, 0);
+        t.chunk = lsnf_det_chunk_rows(c.B, g.depth, 0);
     }
     const dim3 grid(g.depth * 5, (unsigned)((c.B + t.chunk - 1) / t.chunk));
     hipError_t e = hipSuccess;

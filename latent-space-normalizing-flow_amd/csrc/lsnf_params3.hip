@@ -21,9 +21,6 @@
 #include "lsnf_device.h"
 #include "lsnf_launch.h"
 
-#ifndef X3_ABL
-#define X3_ABL 0          // timing experiments (wrong results): 1 no atomics, 2 no MFMA, 4 no global loads after the first two stages, 8 no split
-#endif
 namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -136,7 +133,7 @@ __device__ __forceinline__ void x3_mma(f32x4 (&acc)[MPW][NTL], const char* buf, 
 
 // One task.  Waves 4..7 are the PRODUCERS (global loads, split, LDS writes, column sums), waves 0..3 the CONSUMERS (operand reads,
 // MFMAs, the atomics at the end): two waves per SIMD, one of each role, so the split's VALU work and the load waits of one run under
-// the MFMAs of the other (with all waves doing both in turn, the four parts of a stage simply added up: tools/ablate_x3.sh).
+// the MFMAs of the other (with all waves doing both in turn, the four parts of a stage simply added up: DESIGN.md).
 // One barrier per stage: the producers' write of stage s + 2 follows barrier s + 1, which the consumers reach after reading stage s.
 // DET, one writer per element of the slot.  Tiles: consumer wave `wave` owns the rows 16 * (wave + 4 * mi) + 4 * (lane >> 4) + r and
 // the columns 16 * nt + (lane & 15): every (k < K, n < N) once (x3_run's MPW / NTL cover 16 * 4 * MPW >= K rows, 16 * NTL >= N
@@ -167,8 +164,8 @@ __device__ __forceinline__ void x3_task(const X3Task& t, int m_begin, int m_end,
         x3_load(r2, g, voff, jstride); voff += step;
         auto stage = [&](f32x4 (&r)[8], int s) {                       // stage s: split + write into buffer s & 1, then fetch stage s + 3
             char* w = wr + (s & 1) * X3_BUFFER;
-            if (live && (!(X3_ABL & 8) || s == 0)) { if (isg) x3_split_store<true>(r, w, cs); else x3_split_store<false>(r, w, cs); }
-            if (!(X3_ABL & 4)) { x3_load(r, g, voff, jstride); voff += step; }
+            if (live) { if (isg) x3_split_store<true>(r, w, cs); else x3_split_store<false>(r, w, cs); }
+            x3_load(r, g, voff, jstride); voff += step;
             __syncthreads();
         };
         for (int s = 0; s < ns; s += 3) {                              // (the conditions are workgroup-uniform)
@@ -199,7 +196,7 @@ __device__ __forceinline__ void x3_task(const X3Task& t, int m_begin, int m_end,
         for (int nt = 0; nt < NTL; ++nt) acc[mi][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int s = 0; s < ns; ++s) {
         __syncthreads();
-        if (!(X3_ABL & 2)) x3_mma<MPW, NTL>(acc, lds + (s & 1) * X3_BUFFER, wave, lane);
+        x3_mma<MPW, NTL>(acc, lds + (s & 1) * X3_BUFFER, wave, lane);
     }
     __syncthreads();
     // results: acc[mi][nt][r] = dM[16*(wave + 4*mi) + 4*(lane >> 4) + r][16*nt + (lane & 15)]
@@ -215,7 +212,7 @@ __device__ __forceinline__ void x3_task(const X3Task& t, int m_begin, int m_end,
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int k = 16 * (wave + 4 * mi) + 4 * g + r;
-                    if (k < t.K && (!(X3_ABL & 1) || blockIdx.x == 0)) { if constexpr (DET) c[(size_t)k * ldc] = acc[mi][nt][r]; else atomicAdd(c + (size_t)k * ldc, acc[mi][nt][r]); }
+                    if (k < t.K) { if constexpr (DET) c[(size_t)k * ldc] = acc[mi][nt][r]; else atomicAdd(c + (size_t)k * ldc, acc[mi][nt][r]); }
                 }
             }
         }

@@ -387,7 +387,7 @@ hipError_t launch_small3_bwd_st(const Small3BwdArgs& a, hipStream_t stream) {
 int lsnf_small3_backward_st(const LsnfBackwardCall& c) {
     return lsnf_with_cfg<Small3BwdCfg>(c.g, [&](auto cfg) {
         using C = decltype(cfg);
-        const int st = lsnf_small3_st_wanted(c.B, false);
+        const int st = lsnf_small3_st_wanted(c.B);
         return (st >= 4 && small3_bwd_built<C, 4>) ? 4 : (st >= 2 && small3_bwd_built<C, 2>) ? 2 : 1;
     });
 }

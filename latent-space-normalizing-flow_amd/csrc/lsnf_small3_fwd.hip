@@ -77,12 +77,9 @@ struct Small3Args {
 // (Tried: two workgroups per CU -- __launch_bounds__(256, 2), 512 32-row workgroups for 16 384 rows, so that a second wave on the
 // SIMD fills the first one's bubbles.  68 B/lane of scratch at 256 registers, and the two workgroups stream the weights twice
 // through the CU's one vector-memory path: 35.1 us at 16 384 rows against 31.9 for lsnf_fwd3q_kernel, 22.4 instead of 20.1 at
-// 8 192.  LSNF_SMALL3_WAVES2=1 rebuilds that form.)
-#ifndef LSNF_SMALL3_WAVES2
-#define LSNF_SMALL3_WAVES2 0
-#endif
+// 8 192.  Not kept.)
 template <class C, int ST, bool EXTRAS>
-__global__ __launch_bounds__(256, (LSNF_SMALL3_WAVES2 && ST <= 2 && C::WT <= 2 && !EXTRAS) ? 2 : 1) void lsnf_small3_fwd_kernel(const Small3Args a) {
+__global__ __launch_bounds__(256, 1) void lsnf_small3_fwd_kernel(const Small3Args a) {
     constexpr int HT = C::HT, WT = C::WT, NZT = C::NZT, NU2 = C::NU2;
     using L = Small3Lds<C, ST>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -546,11 +543,9 @@ hipError_t launch_small3_fwd_st(const Small3Args& a, hipStream_t stream) {
 // lsnf_small3_st_wanted asks for; a shape whose constants of n_blocks blocks do not fit in 160 KiB of LDS gives way to the next
 // smaller one.
 int lsnf_small3_forward_st(const LsnfForwardCall& c) {
-    const bool extras = c.z_saved || c.act_saved || c.hdump;
     return lsnf_with_cfg<Small3Cfg>(c.g, [&](auto cfg) {
         using C = decltype(cfg);
-        // (the plain 32-row form runs two workgroups per CU: 512 of them cover 16 384 rows in one round)
-        const int st = lsnf_small3_st_wanted(c.B, LSNF_SMALL3_WAVES2 && !extras && C::WT <= 2 && c.B <= 512 * 32);
+        const int st = lsnf_small3_st_wanted(c.B);
         if (st >= 4 && small3_fwd_built<C, 4> && small3_fwd_lds<C, 4>(c.n_blocks) <= 160 * 1024) return 4;
         if (st >= 2 && small3_fwd_built<C, 2> && small3_fwd_lds<C, 2>(c.n_blocks) <= 160 * 1024) return 2;
         if (small3_fwd_built<C, 1> && small3_fwd_lds<C, 1>(c.n_blocks) <= 160 * 1024) return 1;

@@ -366,7 +366,7 @@ hipError_t launch_small3_rbwd_st(const Args& a, hipStream_t stream) {
 int lsnf_small3_reverse_backward_st(const LsnfReverseBackwardCall& c) {
     return lsnf_with_cfg<Small3RbwdCfg>(c.g, [&](auto cfg) {
         using C = decltype(cfg);
-        const int st = lsnf_small3_st_wanted(c.B, false);
+        const int st = lsnf_small3_st_wanted(c.B);
         return (st >= 4 && small3_rbwd_built<C, 4>) ? 4 : (st >= 2 && small3_rbwd_built<C, 2>) ? 2 : 1;
     });
 }

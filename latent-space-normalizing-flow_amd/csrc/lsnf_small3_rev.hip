@@ -365,7 +365,7 @@ hipError_t launch_small3_rev(const LsnfReverseCall& c, int st, const Args& args)
 int lsnf_small3_reverse_st(const LsnfReverseCall& c) {
     return lsnf_with_cfg<Small3RevCfg>(c.g, [&](auto cfg) {
         using C = decltype(cfg);
-        const int st = lsnf_small3_st_wanted(c.B, false), depth = c.g.depth;
+        const int st = lsnf_small3_st_wanted(c.B), depth = c.g.depth;
         if (st >= 4 && small3_rev_built<C, 4> && small3_rev_lds<C, 4>(depth) <= 160 * 1024) return 4;
         if (st >= 2 && small3_rev_built<C, 2> && small3_rev_lds<C, 2>(depth) <= 160 * 1024) return 2;
         if (small3_rev_built<C, 1> && small3_rev_lds<C, 1>(depth) <= 160 * 1024) return 1;

@@ -9,6 +9,9 @@ so the batch keeps its size (hence its kernels) and the fp32 gradient of every r
 restatement of the flow agrees with the fp64 one to ~1e-6 per tensor, so 2e-5 arbitrates: a dropped or duplicated 32-row
 stage of the contraction moves a tensor by ~32 / B of its norm (5e-4 at 65 536 rows), 25x the bound."""
 import functools
+import os
+import subprocess
+import sys
 import types
 
 import pytest
@@ -234,3 +237,32 @@ def test_module_fast_path_takes_a_misaligned_z(lsnf, gpu_device):
             _check_against_oracle([named[k].grad for k in keys], [ref[k] for k in keys], keys)
     finally:
         lsnf.flow.set_math_mode(prev_mode)
+
+
+def test_library_ignores_LSNF_TN_ABL(gpu_device, tmp_path):
+    """LSNF_TN_ABL used to switch parts of the LDS-staged fp32 contraction off (only chunk 0 written, no MFMAs, no loads) in any
+    process that had it set: wrong gradients with a success code (relative L2 of 1 to 4.8 on this test's 4 224 rows).  One fresh
+    child with LSNF_TN_ABL=7 (the knob was read once per process) runs the recomputing path at 300 rows (plain contraction, three
+    128-row chunks, the last one ragged) and at 4 224 (LDS-staged contraction, 33 chunks) -- the smallest sizes at which "only
+    chunk 0" would show; its 12 tensors meet the oracle."""
+    nz, width, depth, batches = 8, 4, 1, (300, 4224)
+    out = tmp_path / "grads.pt"
+    worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "param_grads_env_worker.py")
+    proc = subprocess.Popen([sys.executable, worker, str(out), str(nz), str(width), str(depth)] + [str(B) for B in batches],
+                            env=dict(os.environ, LSNF_TN_ABL="7"), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    try:
+        log = proc.communicate(timeout=300)[0]
+    except subprocess.TimeoutExpired:
+        proc.kill()
+        raise
+    assert proc.returncode == 0, log
+    got = torch.load(str(out))
+    keys = [O.block_prefix(i) + k for i in range(depth) for k in KEYS_PER_BLOCK]
+    for B in batches:
+        _, _, n_replaced, ref, _ = _reference(nz, width, depth, 1, B)
+        assert len(got[B]) == len(keys) == 12
+        errs = [(k, _rel(g, ref[k].reshape(g.shape))) for k, g in zip(keys, got[B])]
+        print(f"\n[param-grads-oracle] LSNF_TN_ABL=7 nz{nz}-w{width}-d{depth}-B{B} rows_replaced={n_replaced} "
+              + "worst=%.2e(%s)" % max((e, k) for k, e in errs))
+        assert all(torch.isfinite(g).all() for g in got[B])
+        _check_against_oracle(got[B], [ref[k] for k in keys], keys)

@@ -1,5 +1,5 @@
-"""GPU experiment: where the batch contraction of lsnf_params.hip spends its time at B = 65 536 (env knobs LSNF_TN_ABL /
-LSNF_TN_CHUNK / LSNF_TN_PLAIN, one subprocess each)."""
+"""GPU experiment: time of the batch contraction of lsnf_params.hip at B = 65 536 by samples per workgroup and by kernel (env knobs
+LSNF_TN_CHUNK / LSNF_TN_PLAIN, one subprocess each; every row computes the same gradients)."""
 import sys
 
 import ab_harness
@@ -21,7 +21,7 @@ for _ in range(10): run()
 torch.cuda.synchronize()
 emit("%.1f us" % windows(run, 30, 1)[0])
 '''
-BUILDS = (("lds kernel", {}), ("lds, no atomics (chunk 0 only)", {"LSNF_TN_ABL": "1"}), ("lds, no MFMA", {"LSNF_TN_ABL": "2"}), ("lds, no global loads", {"LSNF_TN_ABL": "4"}),
+BUILDS = (("lds kernel", {}),
           ("lds, chunk 512", {"LSNF_TN_CHUNK": "512"}), ("lds, chunk 2048", {"LSNF_TN_CHUNK": "2048"}), ("lds, chunk 4096", {"LSNF_TN_CHUNK": "4096"}),
           ("plain kernel", {"LSNF_TN_PLAIN": "1"}), ("plain, chunk 512", {"LSNF_TN_PLAIN": "1", "LSNF_TN_CHUNK": "512"}))
 
