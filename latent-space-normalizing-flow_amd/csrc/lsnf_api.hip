@@ -39,7 +39,6 @@ int row_vector_width(const LsnfGeo& g, std::initializer_list<const void*> rows) 
     if (g.half % 2 == 0 && a8) return 2;
     return 1;
 }
-bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 // arithmetic of the GEMMs (LSNF_MATH=fp32|bf16x3|bf16x3_phased|fp16x2 overrides the default).  The two knobs are
 // process-wide settings read by every call: atomics, so that a setter on one thread and a launch on another do not race
@@ -83,12 +82,94 @@ int small_batch_max() {
 // modes whose latency / backward / reverse kernels are the bf16x3 "L16" ones
 bool l16_math() { const int m = math_mode(); return m == LSNF_MATH_BF16X3 || m == LSNF_MATH_FP16X2 || m == LSNF_MATH_BF16X3_PHASED; }
 
-int geo_or_fail(LsnfGeo* g, int nz, int width, int depth, int coupling) {
-    if (lsnf_geo_init(g, nz, width, depth, coupling))
-        return fail(LSNF_E_GEOMETRY, "unsupported geometry nz=%d width=%d depth=%d coupling=%d "
-                    "(need nz even in [2,128], width in [1,128], depth in [1,%d], coupling 0 or 1)",
-                    nz, width, depth, coupling, LSNF_MAX_DEPTH);
-    return 0;
+// ---- argument rules: each rule of the ABI is stated ONCE, in Check; an entry point is the list of the rules it applies, in the
+// order it checks them, followed by its descriptor.  A rule returns true when it refuses the call: lsnf_last_error() then reads
+// "<entry>: ..." and rc is the code to return.  The tensor names in a message are the entry point's own wording: a parameter.
+typedef std::initializer_list<const void*> Ptrs;
+bool all_aligned(Ptrs ps, uintptr_t mask) {      // (NULL is aligned: an optional tensor that is absent breaks no rule)
+    for (const void* p : ps) if (reinterpret_cast<uintptr_t>(p) & mask) return false;
+    return true;
+}
+struct Check {
+    const char* entry;
+    int rc = 0;
+    bool empty = false;                  // batch(): no rows, nothing to launch (pointers of empty tensors may be NULL)
+    LsnfGeo g;                           // geometry()
+
+    bool refused(int code, const char* fmt, ...) {
+        const int n = snprintf(g_err, sizeof(g_err), "%s: ", entry);
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(g_err + n, sizeof(g_err) - n, fmt, ap);
+        va_end(ap);
+        rc = code;
+        return true;
+    }
+    // a rule of one entry point alone (aliasing, a scalar's range): stated where it applies
+    template <class... A> bool refuse(bool violated, const char* fmt, A... a) { return violated && refused(LSNF_E_ARG, fmt, a...); }
+
+    bool geometry(int nz, int width, int depth, int coupling) {
+        if (lsnf_geo_init(&g, nz, width, depth, coupling))
+            rc = fail(LSNF_E_GEOMETRY, "unsupported geometry nz=%d width=%d depth=%d coupling=%d "
+                      "(need nz even in [2,128], width in [1,128], depth in [1,%d], coupling 0 or 1)",
+                      nz, width, depth, coupling, LSNF_MAX_DEPTH);
+        return rc != 0;
+    }
+    bool batch(int B, int least = 0) {
+        empty = B == 0;
+        return refuse(B < least || B > (1 << 28), "B=%d out of range", B);
+    }
+    bool required(bool all_given) { return refuse(!all_given, "NULL argument"); }
+    bool aligned16(const char* names, Ptrs ps) { return refuse(!all_aligned(ps, 15u), "%s must be 16-byte aligned", names); }
+    bool aligned4(const char* names, Ptrs ps) { return refuse(!all_aligned(ps, 3u), "%s must be 4-byte aligned", names); }
+    // in-kernel noise (LsnfRng): instead of a noise tensor, never beside one.  lsnf_sample and lsnf_sample_keep look at row0 first,
+    // the Langevin steps at offset_dev first.
+    bool rng(const void* noise, const LsnfRng* r, bool row0_first) {
+        if (refuse(noise && r, "pass either a noise tensor or an rng, not both")) return true;
+        if (!r) return false;
+        auto row0 = [&] { return refuse(r->row0 < 0, "rng->row0 must be >= 0"); };
+        auto offset = [&] { return refuse(!aligned8(r->offset_dev), "rng->offset_dev must be 8-byte aligned"); };
+        return row0_first ? row0() || offset() : offset() || row0();
+    }
+    // the depth * 12 parameter pointers (each given and 4-byte aligned) and, with them, the gradient pointers (a NULL one skips
+    // its tensor): one walk, so the first offending index speaks whichever table it is in
+    bool tables(const float* const* params, const float* const* grads, bool one_message) {
+        for (int i = 0; i < g.depth * LSNF_PARAMS_PER_BLOCK; ++i) {
+            const bool p_bad = !params[i] || !all_aligned({params[i]}, 3u), g_bad = grads && !all_aligned({grads[i]}, 3u);
+            const int block = i / LSNF_PARAMS_PER_BLOCK, slot = i % LSNF_PARAMS_PER_BLOCK;
+            if (one_message ? refuse(p_bad || g_bad, "parameter/gradient pointer %d is NULL or misaligned", i)
+                            : refuse(p_bad, "parameter pointer %d (block %d, slot %d) is NULL or misaligned", i, block, slot) ||
+                              refuse(g_bad, "gradient pointer %d (block %d, slot %d) is misaligned", i, block, slot))
+                return true;
+        }
+        return false;
+    }
+    // params_workspace of a forward / keeping reverse: the workspace of the lsnf_backward_params call that follows, into which the
+    // kernel dumps h1 / h2 of every block.  Returns where the dump goes (NULL: no workspace, or refused -- rc tells)
+    float* params_workspace(float* ws, bool with_companions, const char* companions) {
+        if (!ws || refuse(!l16_math(), "params_workspace needs a bf16x3-family math mode (lsnf_params_fast_path() == 1)") ||
+            refuse(!with_companions, "params_workspace goes with %s", companions) || aligned16("params_workspace", {ws}))
+            return nullptr;
+        return ws + lsnf_params_workspace_dump(g.nz, g.width, g.depth);
+    }
+    // From LSNF_X3_MIN_ROWS rows the batch contraction of lsnf_params3.hip may read the dump and asks the workspace's tag word which
+    // form h1 / h2 have: tiled (whole 1 KiB stores) when the bf16x3 throughput forward writes them, row-major otherwise
+    bool tag_workspace(float* ws, int B, int tiled, hipStream_t stream) {
+        if (!ws || B < LSNF_X3_MIN_ROWS) return false;
+        const hipDeviceptr_t tag = (hipDeviceptr_t)(ws + lsnf_params_workspace_tag(g.nz, g.width, g.depth, B));
+        return hipMemsetD32Async(tag, tiled, 1, stream) != hipSuccess && refused(LSNF_E_HIP, "hipMemsetD32Async(workspace tag) failed");
+    }
+    // a tiled dump (dump_may_tile below) is read and written with 16-byte row accesses
+    bool tiled_rows(bool tiled, const char* with, int B, Ptrs z) {
+        return refuse(tiled && !all_aligned(z, 15u), "with %s at B=%d, z_in / z_out / z_saved must be 16-byte aligned", with, B);
+    }
+    // the descriptor head; rows: every (B, nz) tensor of the call
+    void head(LsnfCall& c, const float* plan, int B, void* stream, Ptrs rows) const {
+        c.g = g; c.plan = plan; c.B = B; c.vec4 = row_vector_width(g, rows); c.stream = (hipStream_t)stream;
+    }
+};
+LsnfRngArgs rng_args(const LsnfRng* r) {
+    return r ? LsnfRngArgs{r->seed, r->offset, r->offset_dev, r->row0, 1} : LsnfRngArgs{0ull, 0ull, nullptr, 0ll, 0};
 }
 
 // ---- kernel selection: each operation decides on the host, from the kernels' coverage predicates, which kernel(s) a call
@@ -115,6 +196,8 @@ int launch_fail(hipError_t e, const char* entry, Kernel k) {
     if (k == K_NONE) return fail(LSNF_E_HIP, "%s: %s", entry, kKernelName[k]);
     return fail(LSNF_E_HIP, "%s: %s: %s", entry, kKernelName[k], hipGetErrorString(e));
 }
+// the tail of every selecting entry point: what the launch(es) of its pick answered
+int report(const char* entry, Pick p, hipError_t e) { return p.k == K_NONE || e != hipSuccess ? launch_fail(e, entry, p.k) : LSNF_OK; }
 
 // Forward.  Up to small_max rows the latency kernels (the bf16-pipe one for the bf16x3 family, 16 x ST rows per workgroup; the
 // fp32-MFMA one, 32 rows, otherwise), above it the throughput kernels (weights shared through LDS):
@@ -207,80 +290,63 @@ hipError_t launch_reverse(Pick p, const LsnfReverseCall& c) {
 bool reverse_keep_covers(const LsnfReverseCall& c) {
     return l16_math() && c.B <= small_batch_max() && lsnf_small3_reverse_st(c) != 0;
 }
-// Argument rules of lsnf_reverse / lsnf_reverse_keep and of lsnf_sample / lsnf_sample_keep, ONE copy each (`entry` names the caller in
-// the message).  Return: a negative LSNF_E_* code; 0 = checked, go on; 1 = empty batch, nothing to launch (the caller returns LSNF_OK).
-int check_reverse_args(const char* entry, LsnfGeo* g, int nz, int width, int depth, int coupling, int B, const float* plan,
-                       const float* z_in, const float* objective, const float* z_out, const float* objective_out) {
-    if (int rc = geo_or_fail(g, nz, width, depth, coupling)) return rc;
-    if (B < 0 || B > (1 << 28)) return fail(LSNF_E_ARG, "%s: B=%d out of range", entry, B);
-    if (B == 0) return 1;
-    if (!plan || !z_in || !z_out) return fail(LSNF_E_ARG, "%s: NULL argument", entry);
-    if (!aligned16(plan)) return fail(LSNF_E_ARG, "%s: plan must be 16-byte aligned", entry);
-    if (!aligned4(z_in) || !aligned4(z_out) || !aligned4(objective) || !aligned4(objective_out))
-        return fail(LSNF_E_ARG, "%s: tensors must be 4-byte aligned", entry);
-    return 0;
-}
-int check_sample_args(const char* entry, LsnfGeo* g, int nz, int width, int depth, int coupling, int B, const LsnfRng* rng,
-                      float temperature, const float* plan, const float* z_out, const float* objective_out, const float* eps_out,
-                      const float* ll_out) {
-    if (int rc = geo_or_fail(g, nz, width, depth, coupling)) return rc;
-    if (B < 0 || B > (1 << 28)) return fail(LSNF_E_ARG, "%s: B=%d out of range", entry, B);
-    if (!rng) return fail(LSNF_E_ARG, "%s: rng is required", entry);
-    if (rng->row0 < 0) return fail(LSNF_E_ARG, "%s: rng->row0 must be >= 0", entry);
-    if (rng->offset_dev && (reinterpret_cast<uintptr_t>(rng->offset_dev) & 7u))
-        return fail(LSNF_E_ARG, "%s: rng->offset_dev must be 8-byte aligned", entry);
-    if (!std::isfinite(temperature) || temperature < 0.0f)
-        return fail(LSNF_E_ARG, "%s: temperature must be finite and >= 0 (got %g)", entry, (double)temperature);
-    if (B == 0) return 1;
-    if (!plan || !z_out) return fail(LSNF_E_ARG, "%s: NULL argument", entry);
-    if (!aligned16(plan)) return fail(LSNF_E_ARG, "%s: plan must be 16-byte aligned", entry);
-    if (!aligned4(z_out) || !aligned4(objective_out) || !aligned4(eps_out) || !aligned4(ll_out))
-        return fail(LSNF_E_ARG, "%s: tensors must be 4-byte aligned", entry);
-    if (eps_out == z_out) return fail(LSNF_E_ARG, "%s: eps_out must not alias z_out", entry);
-    return 0;
-}
-// the plain selection and launch of a checked reverse / sampling call
-int reverse_select_launch(const char* entry, const LsnfReverseCall& c) {
-    const Pick p = select_reverse(c);
-    const hipError_t e = launch_reverse(p, c);
-    if (p.k == K_NONE || e != hipSuccess) return launch_fail(e, entry, p.k);
-    return LSNF_OK;
-}
-// What the two keep entry points share once the plain call's arguments are checked: the rules of the three optional tensors (as
-// lsnf_forward's), the coverage rule, the workspace tag, the launch.  The descriptor comes filled but for vec4 and the three tensors.
-int reverse_keep_launch(const char* entry, LsnfReverseCall& c, float* z_saved, float* act_saved, float* params_workspace) {
-    const LsnfGeo& g = c.g;
+// A checked reverse / sampling call (the descriptor filled but for the three tensors below) to its launch: the plain selection, or
+// -- keep: lsnf_reverse_keep, lsnf_sample_keep -- the rules of the three optional tensors (as lsnf_forward's), the coverage rule,
+// the workspace tag and the one kernel that keeps a stash.
+int reverse_launch(Check& ck, LsnfReverseCall& c, bool keep, float* z_saved, float* act_saved, float* params_workspace) {
+    if (!keep) {
+        const Pick p = select_reverse(c);
+        return report(ck.entry, p, launch_reverse(p, c));
+    }
     const float* eps_out = c.smp ? c.smp->eps_out : nullptr;
-    if (!aligned4(z_saved)) return fail(LSNF_E_ARG, "%s: tensors must be 4-byte aligned", entry);
-    if (act_saved && !aligned16(act_saved)) return fail(LSNF_E_ARG, "%s: act_saved must be 16-byte aligned", entry);
-    if (z_saved && (z_saved == c.z_in || z_saved == c.z_out || z_saved == eps_out))
-        return fail(LSNF_E_ARG, "%s: z_saved must not alias another tensor of the call", entry);
     // (an in-place call would overwrite the last block's output, which every backward must be given as z_out: the stash would be useless)
-    if ((z_saved || act_saved) && c.z_in && c.z_in == c.z_out)
-        return fail(LSNF_E_ARG, "%s: z_out must not alias z_in when z_saved / act_saved are kept (the backward reads z_in)", entry);
-    if (params_workspace) {
-        if (!l16_math()) return fail(LSNF_E_ARG, "%s: params_workspace needs a bf16x3-family math mode (lsnf_params_fast_path() == 1)", entry);
-        if (!act_saved || (g.depth > 1 && !z_saved)) return fail(LSNF_E_ARG, "%s: params_workspace goes with act_saved and z_saved", entry);
-        if (!aligned16(params_workspace)) return fail(LSNF_E_ARG, "%s: params_workspace must be 16-byte aligned", entry);
-    }
-    if (c.smp && (act_saved || z_saved) && !eps_out)
-        return fail(LSNF_E_ARG, "%s: act_saved / z_saved need eps_out (the last block's output, which the backward reads)", entry);
-    if (!reverse_keep_covers(c))
-        return fail(LSNF_E_ARG, "%s: only the latency bf16x3 reverse keeps a stash: needs a bf16x3-family math mode and B=%d <= the "
-                    "small-batch threshold %d (lsnf_reverse_keep_covers)", entry, c.B, small_batch_max());
-    c.vec4 = row_vector_width(g, {c.z_in, c.z_out, eps_out, z_saved});
+    if (ck.aligned4("tensors", {z_saved}) || ck.aligned16("act_saved", {act_saved}) ||
+        ck.refuse(z_saved && (z_saved == c.z_in || z_saved == c.z_out || z_saved == eps_out), "z_saved must not alias another tensor of the call") ||
+        ck.refuse((z_saved || act_saved) && c.z_in && c.z_in == c.z_out,
+                  "z_out must not alias z_in when z_saved / act_saved are kept (the backward reads z_in)"))
+        return ck.rc;
     c.z_saved = z_saved; c.act_saved = act_saved;
-    if (params_workspace) {
-        c.hdump = params_workspace + 4 + (size_t)g.depth * lsnf_fold_layout(g.nz, g.width).per_block;
-        // (the tag word the batch contraction of lsnf_params3.hip asks, as lsnf_forward writes it: this kernel's h1 / h2 are row-major)
-        if (c.B >= LSNF_X3_MIN_ROWS &&
-            hipMemsetD32Async((hipDeviceptr_t)(params_workspace + lsnf_params_workspace_tag(g.nz, g.width, g.depth, c.B)), 0, 1, c.stream) != hipSuccess)
-            return fail(LSNF_E_HIP, "%s: hipMemsetD32Async(workspace tag) failed", entry);
-    }
+    c.hdump = ck.params_workspace(params_workspace, act_saved && (c.g.depth == 1 || z_saved), "act_saved and z_saved");
+    if (ck.rc ||
+        ck.refuse(c.smp && (act_saved || z_saved) && !eps_out, "act_saved / z_saved need eps_out (the last block's output, which the backward reads)") ||
+        ck.refuse(!reverse_keep_covers(c), "only the latency bf16x3 reverse keeps a stash: needs a bf16x3-family math mode and B=%d <= the "
+                  "small-batch threshold %d (lsnf_reverse_keep_covers)", c.B, small_batch_max()) ||
+        ck.tag_workspace(params_workspace, c.B, /*tiled=*/0, c.stream))      // (this kernel's h1 / h2 are row-major)
+        return ck.rc;
     const Pick p = {K_SMALL3_REV, lsnf_small3_reverse_st(c)};
-    const hipError_t e = launch_reverse(p, c);
-    if (e != hipSuccess) return launch_fail(e, entry, p.k);
-    return LSNF_OK;
+    return report(ck.entry, p, launch_reverse(p, c));
+}
+// lsnf_reverse and lsnf_reverse_keep
+int reverse_entry(const char* entry, bool keep, const float* plan, int nz, int width, int depth, int coupling, int B, const float* z_in,
+                  const float* objective, float* z_out, float* objective_out, float* z_saved, float* act_saved, float* params_workspace,
+                  void* stream) {
+    Check ck{entry};
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B)) return ck.rc;
+    if (ck.empty) return LSNF_OK;
+    if (ck.required(plan && z_in && z_out) || ck.aligned16("plan", {plan}) || ck.aligned4("tensors", {z_in, z_out, objective, objective_out}))
+        return ck.rc;
+    LsnfReverseCall c;
+    ck.head(c, plan, B, stream, {z_in, z_out, z_saved});
+    c.z_in = z_in; c.objective = objective; c.z_out = z_out; c.objective_out = objective_out;
+    return reverse_launch(ck, c, keep, z_saved, act_saved, params_workspace);
+}
+// lsnf_sample and lsnf_sample_keep: the reverse's kernels in their sampling form (c.smp)
+int sample_entry(const char* entry, bool keep, const float* plan, int nz, int width, int depth, int coupling, int B, const LsnfRng* rng,
+                 float temperature, float* z_out, float* objective_out, float* eps_out, float* ll_out, float* z_saved, float* act_saved,
+                 float* params_workspace, void* stream) {
+    Check ck{entry};
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B) || ck.refuse(!rng, "rng is required") || ck.rng(nullptr, rng, /*row0_first=*/true) ||
+        ck.refuse(!std::isfinite(temperature) || temperature < 0.0f, "temperature must be finite and >= 0 (got %g)", (double)temperature))
+        return ck.rc;
+    if (ck.empty) return LSNF_OK;
+    if (ck.required(plan && z_out) || ck.aligned16("plan", {plan}) || ck.aligned4("tensors", {z_out, objective_out, eps_out, ll_out}) ||
+        ck.refuse(eps_out == z_out, "eps_out must not alias z_out"))
+        return ck.rc;
+    const LsnfSampleArgs smp = {rng_args(rng), temperature, eps_out, ll_out};
+    LsnfReverseCall c;                   // (z_in / objective stay NULL: the kernels draw the rows)
+    ck.head(c, plan, B, stream, {z_out, eps_out, z_saved});
+    c.z_out = z_out; c.objective_out = objective_out; c.smp = &smp;
+    return reverse_launch(ck, c, keep, z_saved, act_saved, params_workspace);
 }
 
 // Backward (lsnf_backward_z, lsnf_langevin_step, lsnf_backward_params): from the activation stash on the bf16 matrix pipe when
@@ -301,6 +367,10 @@ hipError_t launch_backward(Pick p, const LsnfBackwardCall& c) {
     case K_BWD: return lsnf_launch_backward_z(c);
     default: return hipSuccess;
     }
+}
+int backward_launch(const char* entry, const LsnfBackwardCall& c) {      // lsnf_backward_z, lsnf_langevin_step
+    const Pick p = select_backward(c);
+    return report(entry, p, launch_backward(p, c));
 }
 
 // Backward of the reverse pass (lsnf_reverse_backward_z): one kernel (lsnf_small3_rbwd.hip) whose bf16x3 arithmetic is not narrower
@@ -342,21 +412,13 @@ int backward_params_entry(const char* entry, int det, const float* plan, const f
                           int depth, int coupling, int B, const float* z_in, const float* z_out, const float* z_saved,
                           const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode, float ll_scale,
                           float* g_z_in, float* workspace, void* stream) {
-    LsnfGeo g;
-    if (int rc = geo_or_fail(&g, nz, width, depth, coupling)) return rc;
-    if (B < 1 || B > (1 << 28)) return fail(LSNF_E_ARG, "%s: B=%d out of range", entry, B);
-    if (!plan || !params_host || !grads_host || !z_in || !z_out || !workspace || (depth > 1 && !z_saved))
-        return fail(LSNF_E_ARG, "%s: NULL argument", entry);
-    if (!aligned16(plan) || !aligned16(workspace)) return fail(LSNF_E_ARG, "%s: plan/workspace must be 16-byte aligned", entry);
-    for (int i = 0; i < depth * LSNF_PARAMS_PER_BLOCK; ++i) {
-        if (!params_host[i] || !aligned4(params_host[i]) || !aligned4(grads_host[i]))
-            return fail(LSNF_E_ARG, "%s: parameter/gradient pointer %d is NULL or misaligned", entry, i);
-    }
-    if (!aligned4(z_in) || !aligned4(z_out) || !aligned4(z_saved) || !aligned4(g_z1) || !aligned4(g_logdet) || !aligned4(g_z_in))
-        return fail(LSNF_E_ARG, "%s: tensors must be 4-byte aligned", entry);
-    // (z_in too: the batch contraction of block 0 reads its rows with the same vector width)
-    const int vec4 = row_vector_width(g, {z_in, z_out, g_z_in, z_saved, g_z1});
-    if (act_saved && !aligned16(act_saved)) return fail(LSNF_E_ARG, "%s: act_saved must be 16-byte aligned", entry);
+    Check ck{entry};
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B, 1) ||
+        ck.required(plan && params_host && grads_host && z_in && z_out && workspace && (depth == 1 || z_saved)) ||
+        ck.aligned16("plan/workspace", {plan, workspace}) || ck.tables(params_host, grads_host, /*one_message=*/true) ||
+        ck.aligned4("tensors", {z_in, z_out, z_saved, g_z1, g_logdet, g_z_in}) || ck.aligned16("act_saved", {act_saved}))
+        return ck.rc;
+    const LsnfGeo& g = ck.g;
     // Fast path (act_saved given, bf16x3-family math): the forward of this evaluation kept the activation stash and wrote h1 / h2
     // into this workspace's dump (lsnf_forward(params_workspace)); the backward FROM THE STASH, on the bf16 matrix pipe, adds
     // g_v, g_a1, g_a2, g_t, g_p -- no recomputation of the coupling MLP (1.0x instead of 1.5x the forward's matrix work, at
@@ -365,30 +427,29 @@ int backward_params_entry(const char* entry, int det, const float* plan, const f
     // LSNF_TN_X3=0 keeps the fp32-MFMA kernels), and the throughput backward then writes its g arrays in the tiled form (whole
     // 1 KiB stores instead of 16 rows x 64 bytes; g_v as its first half only: the second half is g_t)
     if (!l16_math()) act_saved = nullptr;
-    if (act_saved && dump_may_tile(g, B, small_batch_max()) && !(aligned16(z_in) && aligned16(z_out) && aligned16(z_saved)))
-        return fail(LSNF_E_ARG, "%s: with act_saved at B=%d, z_in / z_out / z_saved must be 16-byte aligned", entry, B);
-    const hipStream_t st = (hipStream_t)stream;
+    if (ck.tiled_rows(act_saved && dump_may_tile(g, B, small_batch_max()), "act_saved", B, {z_in, z_out, z_saved})) return ck.rc;
     // workspace: G = sum_b dL/dlogdet_b (one double in floats 0-1: in float32 the per-wave atomics lost up to ~1e-5 of it, and
     // G * 3 / G * W^-T cancel against the data terms of the actnorm.logs / 1x1-conv gradients), the folded gradients (zeroed:
     // both accumulate by atomics), then the dump the backward writes
-    const size_t folded = 4 + (size_t)depth * lsnf_fold_layout(nz, width).per_block;
+    const size_t folded = lsnf_params_workspace_dump(nz, width, depth);
     LsnfBackwardCall b;
-    b.g = g; b.plan = plan; b.B = B; b.vec4 = vec4; b.stream = st;
+    // (z_in too: the batch contraction of block 0 reads its rows with the same vector width)
+    ck.head(b, plan, B, stream, {z_in, z_out, g_z_in, z_saved, g_z1});
+    LsnfContractCall c;
+    static_cast<LsnfCall&>(c) = b;       // (the same head)
     b.z_out = z_out; b.z_saved = z_saved; b.act_saved = act_saved; b.g_z1 = g_z1; b.g_logdet = g_logdet;
     b.ll_mode = ll_mode; b.ll_scale = ll_scale; b.g_z_in = g_z_in;
     // (det: G is summed in a fixed order by lsnf_fold_reduce_kernel; the kernels' atomic sum goes to the spare floats 2-3)
     b.dump = workspace + folded; b.gl_total = reinterpret_cast<double*>(workspace + (det ? 2 : 0));
-    LsnfContractCall c;
-    c.g = g; c.plan = plan; c.B = B; c.vec4 = vec4; c.stream = st;
     c.params_host = params_host; c.grads_host = grads_host; c.z_in = z_in; c.z_out = z_out; c.z_saved = z_saved; c.workspace = workspace;
     c.det = det; c.g_logdet = g_logdet; c.ll_mode = ll_mode; c.ll_scale = ll_scale;
     const Pick p = select_backward(b);
     const bool use_x3 = act_saved && lsnf_contract_x3_covers(c);
-    const int contraction = select_contraction(g, B, use_x3, vec4);
+    const int contraction = select_contraction(g, B, use_x3, b.vec4);
     b.dump_tiled = c.g_tiled = (use_x3 && p.k == K_BWD3 && lsnf_dump_can_tile(nz, width)) ? 1 : 0;
     if (p.k == K_NONE) return launch_fail(hipSuccess, entry, p.k);
     // (det: the reduce kernel writes every element of the fold; only the header is accumulated into)
-    hipError_t e = hipMemsetAsync(workspace, 0, sizeof(float) * (det ? 4 : folded), st);
+    hipError_t e = hipMemsetAsync(workspace, 0, sizeof(float) * (det ? 4 : folded), b.stream);
     if (e != hipSuccess) return hip_fail(e, det ? "lsnf_backward_params_det: hipMemsetAsync(workspace)" : "lsnf_backward_params: hipMemsetAsync(workspace)");
     e = launch_backward(p, b);
     if (e != hipSuccess) return launch_fail(e, entry, p.k);
@@ -445,16 +506,12 @@ size_t lsnf_prepare_scratch_bytes(int nz, int width, int depth) {
 
 int lsnf_prepare(const float* const* params_host, int nz, int width, int depth, int coupling, float* plan,
                  void* scratch, void* stream) {
-    LsnfGeo g;
-    if (int rc = geo_or_fail(&g, nz, width, depth, coupling)) return rc;
-    if (!params_host || !plan || !scratch) return fail(LSNF_E_ARG, "lsnf_prepare: NULL argument");
-    if (!aligned16(plan) || !aligned16(scratch)) return fail(LSNF_E_ARG, "lsnf_prepare: plan/scratch must be 16-byte aligned");
-    for (int i = 0; i < depth * LSNF_PARAMS_PER_BLOCK; ++i)
-        if (!params_host[i] || !aligned4(params_host[i]))
-            return fail(LSNF_E_ARG, "lsnf_prepare: parameter pointer %d (block %d, slot %d) is NULL or misaligned", i,
-                        i / LSNF_PARAMS_PER_BLOCK, i % LSNF_PARAMS_PER_BLOCK);
+    Check ck{"lsnf_prepare"};
+    if (ck.geometry(nz, width, depth, coupling) || ck.required(params_host && plan && scratch) ||
+        ck.aligned16("plan/scratch", {plan, scratch}) || ck.tables(params_host, nullptr, /*one_message=*/false))
+        return ck.rc;
     LsnfPrepareCall c;
-    c.g = g; c.params_host = params_host; c.plan = plan; c.scratch = scratch; c.stream = (hipStream_t)stream;
+    c.g = ck.g; c.params_host = params_host; c.plan = plan; c.scratch = scratch; c.stream = (hipStream_t)stream;
     hipError_t e = lsnf_launch_prepare(c);
     if (e != hipSuccess) return hip_fail(e, "lsnf_prepare launch");
     return LSNF_OK;
@@ -468,18 +525,12 @@ size_t lsnf_actnorm_init_workspace_bytes(int nz, int width, int depth, int coupl
 
 int lsnf_actnorm_init(float* const* params_host, int nz, int width, int depth, int coupling, int B, const float* z_in,
                       void* workspace, void* stream) {
-    LsnfGeo g;
-    if (int rc = geo_or_fail(&g, nz, width, depth, coupling)) return rc;
-    if (B < 1 || B > (1 << 28)) return fail(LSNF_E_ARG, "lsnf_actnorm_init: B=%d out of range", B);
-    if (!params_host || !z_in || !workspace) return fail(LSNF_E_ARG, "lsnf_actnorm_init: NULL argument");
-    if (!aligned16(workspace)) return fail(LSNF_E_ARG, "lsnf_actnorm_init: workspace must be 16-byte aligned");
-    if (!aligned4(z_in)) return fail(LSNF_E_ARG, "lsnf_actnorm_init: z_in must be 4-byte aligned");
-    for (int i = 0; i < depth * LSNF_PARAMS_PER_BLOCK; ++i)
-        if (!params_host[i] || !aligned4(params_host[i]))
-            return fail(LSNF_E_ARG, "lsnf_actnorm_init: parameter pointer %d (block %d, slot %d) is NULL or misaligned", i,
-                        i / LSNF_PARAMS_PER_BLOCK, i % LSNF_PARAMS_PER_BLOCK);
+    Check ck{"lsnf_actnorm_init"};
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B, 1) || ck.required(params_host && z_in && workspace) ||
+        ck.aligned16("workspace", {workspace}) || ck.aligned4("z_in", {z_in}) || ck.tables(params_host, nullptr, /*one_message=*/false))
+        return ck.rc;
     LsnfInitCall c;
-    c.g = g; c.params_host = params_host; c.B = B; c.z_in = z_in; c.workspace = workspace; c.stream = (hipStream_t)stream;
+    c.g = ck.g; c.params_host = params_host; c.B = B; c.z_in = z_in; c.workspace = workspace; c.stream = (hipStream_t)stream;
     hipError_t e = lsnf_launch_actnorm_init(c);
     if (e != hipSuccess) return hip_fail(e, "lsnf_actnorm_init launch");
     return LSNF_OK;
@@ -500,29 +551,18 @@ size_t lsnf_adam_state_bytes_ex(int nz, int width, int depth, int coupling, unsi
 // the one body of lsnf_adam_step and lsnf_adam_step_ex; `who` names the entry point in the messages
 static int adam_step(const char* who, float* const* params_host, const float* const* grads_host, int nz, int width, int depth,
                      int coupling, void* state, const LsnfAdamOptions& o, void* stream) {
-    LsnfGeo g;
-    if (int rc = geo_or_fail(&g, nz, width, depth, coupling)) return rc;
-    if (o.flags & ~kAdamFlags) return fail(LSNF_E_ARG, "%s: unknown flag bits 0x%x", who, o.flags & ~kAdamFlags);
-    if ((o.flags & LSNF_ADAM_EMA) && !(o.ema_decay >= 0.0 && o.ema_decay < 1.0))
-        return fail(LSNF_E_ARG, "%s: ema_decay must lie in [0, 1)", who);
-    if (!params_host || !grads_host || !state) return fail(LSNF_E_ARG, "%s: NULL argument", who);
-    if (!aligned16(state)) return fail(LSNF_E_ARG, "%s: state must be 16-byte aligned", who);
-    if (!aligned4(o.lr_dev) || !aligned4(o.grad_norm_out)) return fail(LSNF_E_ARG, "%s: lr_dev / grad_norm_out must be 4-byte aligned", who);
-    if (!std::isfinite(o.lr) || o.lr < 0.0) return fail(LSNF_E_ARG, "%s: lr must be finite and >= 0", who);
-    if (!std::isfinite(o.eps) || o.eps < 0.0) return fail(LSNF_E_ARG, "%s: eps must be finite and >= 0", who);
-    if (!std::isfinite(o.weight_decay) || o.weight_decay < 0.0) return fail(LSNF_E_ARG, "%s: weight_decay must be finite and >= 0", who);
-    if (!(o.beta1 >= 0.0 && o.beta1 < 1.0) || !(o.beta2 >= 0.0 && o.beta2 < 1.0)) return fail(LSNF_E_ARG, "%s: betas must lie in [0, 1)", who);
-    if (std::isnan(o.max_norm)) return fail(LSNF_E_ARG, "%s: max_norm is NaN", who);
-    for (int i = 0; i < depth * LSNF_PARAMS_PER_BLOCK; ++i) {
-        if (!params_host[i] || !aligned4(params_host[i]))
-            return fail(LSNF_E_ARG, "%s: parameter pointer %d (block %d, slot %d) is NULL or misaligned", who, i,
-                        i / LSNF_PARAMS_PER_BLOCK, i % LSNF_PARAMS_PER_BLOCK);
-        if (!aligned4(grads_host[i]))
-            return fail(LSNF_E_ARG, "%s: gradient pointer %d (block %d, slot %d) is misaligned", who, i,
-                        i / LSNF_PARAMS_PER_BLOCK, i % LSNF_PARAMS_PER_BLOCK);
-    }
+    Check ck{who};
+    auto finite_nonneg = [&](double v, const char* name) { return ck.refuse(!std::isfinite(v) || v < 0.0, "%s must be finite and >= 0", name); };
+    auto unit = [](double v) { return v >= 0.0 && v < 1.0; };
+    if (ck.geometry(nz, width, depth, coupling) || ck.refuse(o.flags & ~kAdamFlags, "unknown flag bits 0x%x", o.flags & ~kAdamFlags) ||
+        ck.refuse((o.flags & LSNF_ADAM_EMA) && !unit(o.ema_decay), "ema_decay must lie in [0, 1)") ||
+        ck.required(params_host && grads_host && state) || ck.aligned16("state", {state}) ||
+        ck.aligned4("lr_dev / grad_norm_out", {o.lr_dev, o.grad_norm_out}) || finite_nonneg(o.lr, "lr") || finite_nonneg(o.eps, "eps") ||
+        finite_nonneg(o.weight_decay, "weight_decay") || ck.refuse(!unit(o.beta1) || !unit(o.beta2), "betas must lie in [0, 1)") ||
+        ck.refuse(std::isnan(o.max_norm), "max_norm is NaN") || ck.tables(params_host, grads_host, /*one_message=*/false))
+        return ck.rc;
     LsnfAdamCall c;
-    c.g = g; c.params_host = params_host; c.grads_host = grads_host; c.state = state;
+    c.g = ck.g; c.params_host = params_host; c.grads_host = grads_host; c.state = state;
     c.lr = o.lr; c.beta1 = o.beta1; c.beta2 = o.beta2; c.eps = o.eps; c.weight_decay = o.weight_decay; c.max_norm = o.max_norm;
     c.ema_decay = (o.flags & LSNF_ADAM_EMA) ? o.ema_decay : 0.0; c.flags = o.flags;
     c.lr_dev = o.lr_dev; c.grad_norm_out = o.grad_norm_out; c.stream = (hipStream_t)stream;
@@ -554,31 +594,24 @@ int lsnf_params_fast_path(void) { return l16_math() ? 1 : 0; }
 int lsnf_forward(const float* plan, int nz, int width, int depth, int coupling, int first_block, int n_blocks, int B,
                  const float* z_in, const float* objective, float* z_out, float* logdet_out, float* ll_out,
                  float* z_saved, float* act_saved, float* params_workspace, double* stats, void* stream) {
-    LsnfGeo g;
-    if (int rc = geo_or_fail(&g, nz, width, depth, coupling)) return rc;
-    if (B < 0 || B > (1 << 28)) return fail(LSNF_E_ARG, "lsnf_forward: B=%d out of range", B);
-    if (B == 0) {   // empty batch: nothing to do (pointers of empty tensors may be NULL)
+    Check ck{"lsnf_forward"};
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B)) return ck.rc;
+    if (ck.empty) {
         if (stats && hipMemsetAsync(stats + 4, 0, 3 * sizeof(double), (hipStream_t)stream) != hipSuccess)
             return fail(LSNF_E_HIP, "lsnf_forward: hipMemsetAsync(stats) failed");
         return LSNF_OK;
     }
-    if (!plan || !z_in || !z_out || !logdet_out) return fail(LSNF_E_ARG, "lsnf_forward: NULL argument");
-    if (first_block < 0 || n_blocks < 1 || first_block + n_blocks > depth)
-        return fail(LSNF_E_ARG, "lsnf_forward: blocks [%d,%d) outside [0,%d)", first_block, first_block + n_blocks, depth);
-    if (!aligned16(plan)) return fail(LSNF_E_ARG, "lsnf_forward: plan must be 16-byte aligned");
-    if (!aligned4(z_in) || !aligned4(z_out) || !aligned4(logdet_out) || !aligned4(objective) || !aligned4(ll_out) || !aligned4(z_saved))
-        return fail(LSNF_E_ARG, "lsnf_forward: tensors must be 4-byte aligned");
-    const int vec4 = row_vector_width(g, {z_in, z_out, z_saved});
-    if (act_saved && !aligned16(act_saved)) return fail(LSNF_E_ARG, "lsnf_forward: act_saved must be 16-byte aligned");
-    if (stats && (reinterpret_cast<uintptr_t>(stats) & 7u)) return fail(LSNF_E_ARG, "lsnf_forward: stats must be 8-byte aligned");
-    float* hdump = nullptr;              // h1 / h2 of every block into the parameter-gradient workspace (lsnf_backward_params' fast path)
-    if (params_workspace) {
-        if (!l16_math()) return fail(LSNF_E_ARG, "lsnf_forward: params_workspace needs a bf16x3-family math mode (lsnf_params_fast_path() == 1)");
-        if (first_block != 0 || n_blocks != depth || !act_saved || (depth > 1 && !z_saved))
-            return fail(LSNF_E_ARG, "lsnf_forward: params_workspace goes with the whole stack, act_saved and z_saved");
-        if (!aligned16(params_workspace)) return fail(LSNF_E_ARG, "lsnf_forward: params_workspace must be 16-byte aligned");
-        hdump = params_workspace + 4 + (size_t)depth * lsnf_fold_layout(nz, width).per_block;
-    }
+    if (ck.required(plan && z_in && z_out && logdet_out) ||
+        ck.refuse(first_block < 0 || n_blocks < 1 || first_block + n_blocks > depth, "blocks [%d,%d) outside [0,%d)", first_block,
+                  first_block + n_blocks, depth) ||
+        ck.aligned16("plan", {plan}) || ck.aligned4("tensors", {z_in, z_out, logdet_out, objective, ll_out, z_saved}) ||
+        ck.aligned16("act_saved", {act_saved}) || ck.refuse(!aligned8(stats), "stats must be 8-byte aligned"))
+        return ck.rc;
+    // h1 / h2 of every block into the parameter-gradient workspace (lsnf_backward_params' fast path)
+    float* hdump = ck.params_workspace(params_workspace, first_block == 0 && n_blocks == depth && act_saved && (depth == 1 || z_saved),
+                                       "the whole stack, act_saved and z_saved");
+    if (ck.rc) return ck.rc;
+    const LsnfGeo& g = ck.g;
     const int math = math_mode();
     // Calls without a stash that the software-pipelined forward covers cross over at 8 192 rows, not at the common threshold:
     // the latency kernel puts 16 / 32 rows on a workgroup up to 4 096 / 8 192 rows (one round of <= 256 workgroups that each
@@ -590,26 +623,17 @@ int lsnf_forward(const float* plan, int nz, int width, int depth, int coupling, 
     if (z_saved == nullptr && act_saved == nullptr && small_batch_setting() == LSNF_SMALL_BATCH_AUTO && small_max > 8192 &&
         math == LSNF_MATH_BF16X3 && g.HT == 2 && g.WT == 2)
         small_max = 8192;
-    // Parameter-gradient dump: from LSNF_X3_MIN_ROWS rows the batch contraction of lsnf_params3.hip may read it and asks the workspace's
-    // tag word which form h1 / h2 have -- tiled (whole 1 KiB stores) when the bf16x3 throughput forward writes them, row-major otherwise
-    int hdump_tiled = 0;
-    if (hdump && B >= LSNF_X3_MIN_ROWS) {
-        hdump_tiled = dump_may_tile(g, B, small_max) ? 1 : 0;
-        if (hdump_tiled && !(aligned16(z_in) && aligned16(z_out) && aligned16(z_saved)))
-            return fail(LSNF_E_ARG, "lsnf_forward: with params_workspace at B=%d, z_in / z_out / z_saved must be 16-byte aligned", B);
-        if (hipMemsetD32Async((hipDeviceptr_t)(params_workspace + lsnf_params_workspace_tag(nz, width, depth, B)), hdump_tiled, 1,
-                              (hipStream_t)stream) != hipSuccess)
-            return fail(LSNF_E_HIP, "lsnf_forward: hipMemsetD32Async(workspace tag) failed");
-    }
+    const int hdump_tiled = hdump && B >= LSNF_X3_MIN_ROWS && dump_may_tile(g, B, small_max) ? 1 : 0;
+    if (ck.tiled_rows(hdump_tiled, "params_workspace", B, {z_in, z_out, z_saved}) ||
+        ck.tag_workspace(params_workspace, B, hdump_tiled, (hipStream_t)stream))
+        return ck.rc;
     LsnfForwardCall c;
-    c.g = g; c.plan = plan; c.B = B; c.vec4 = vec4; c.stream = (hipStream_t)stream;
+    ck.head(c, plan, B, stream, {z_in, z_out, z_saved});
     c.first_block = first_block; c.n_blocks = n_blocks;
     c.z_in = z_in; c.objective = objective; c.z_out = z_out; c.logdet_out = logdet_out; c.ll_out = ll_out;
     c.z_saved = z_saved; c.act_saved = act_saved; c.stats = stats; c.hdump = hdump; c.hdump_tiled = hdump_tiled;
     const Pick p = select_forward(c, small_max);
-    const hipError_t e = launch_forward(p, c);
-    if (p.k == K_NONE || e != hipSuccess) return launch_fail(e, "lsnf_forward", p.k);
-    return LSNF_OK;
+    return report(ck.entry, p, launch_forward(p, c));
 }
 
 size_t lsnf_act_saved_floats(int nz, int width, int depth, int B) {
@@ -620,16 +644,15 @@ size_t lsnf_act_saved_floats(int nz, int width, int depth, int B) {
 
 int lsnf_restash(const float* plan, int nz, int width, int depth, int coupling, int B, const float* z_out,
                  const float* z_saved, float* act_saved, void* stream) {
-    LsnfGeo g;
-    if (int rc = geo_or_fail(&g, nz, width, depth, coupling)) return rc;
-    if (B < 0 || B > (1 << 28)) return fail(LSNF_E_ARG, "lsnf_restash: B=%d out of range", B);
-    if (B == 0) return LSNF_OK;
-    if (!plan || !z_out || !act_saved || (depth > 1 && !z_saved)) return fail(LSNF_E_ARG, "lsnf_restash: NULL argument");
-    if (!aligned16(plan) || !aligned16(act_saved)) return fail(LSNF_E_ARG, "lsnf_restash: plan / act_saved must be 16-byte aligned");
-    if (!aligned4(z_out) || !aligned4(z_saved)) return fail(LSNF_E_ARG, "lsnf_restash: tensors must be 4-byte aligned");
-    if (!l16_math()) return fail(LSNF_E_ARG, "lsnf_restash: needs a bf16x3-family math mode (lsnf_params_fast_path() == 1)");
+    Check ck{"lsnf_restash"};
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B)) return ck.rc;
+    if (ck.empty) return LSNF_OK;
+    if (ck.required(plan && z_out && act_saved && (depth == 1 || z_saved)) || ck.aligned16("plan / act_saved", {plan, act_saved}) ||
+        ck.aligned4("tensors", {z_out, z_saved}) ||
+        ck.refuse(!l16_math(), "needs a bf16x3-family math mode (lsnf_params_fast_path() == 1)"))
+        return ck.rc;
     LsnfRestashCall c;
-    c.g = g; c.plan = plan; c.B = B; c.vec4 = row_vector_width(g, {z_out, z_saved}); c.stream = (hipStream_t)stream;
+    ck.head(c, plan, B, stream, {z_out, z_saved});
     c.z_out = z_out; c.z_saved = z_saved; c.act_saved = act_saved;
     const hipError_t e = lsnf_launch_small3_restash(c);
     if (e != hipSuccess) return hip_fail(e, "lsnf_restash launch");
@@ -638,23 +661,14 @@ int lsnf_restash(const float* plan, int nz, int width, int depth, int coupling, 
 
 int lsnf_reverse(const float* plan, int nz, int width, int depth, int coupling, int B, const float* z_in,
                  const float* objective, float* z_out, float* objective_out, void* stream) {
-    LsnfReverseCall c;
-    if (int rc = check_reverse_args("lsnf_reverse", &c.g, nz, width, depth, coupling, B, plan, z_in, objective, z_out, objective_out))
-        return rc < 0 ? rc : LSNF_OK;
-    c.plan = plan; c.B = B; c.vec4 = row_vector_width(c.g, {z_in, z_out}); c.stream = (hipStream_t)stream;
-    c.z_in = z_in; c.objective = objective; c.z_out = z_out; c.objective_out = objective_out;
-    return reverse_select_launch("lsnf_reverse", c);
+    return reverse_entry("lsnf_reverse", /*keep=*/false, plan, nz, width, depth, coupling, B, z_in, objective, z_out, objective_out,
+                         nullptr, nullptr, nullptr, stream);
 }
 
 int lsnf_sample(const float* plan, int nz, int width, int depth, int coupling, int B, const LsnfRng* rng, float temperature,
                 float* z_out, float* objective_out, float* eps_out, float* ll_out, void* stream) {
-    LsnfReverseCall c;                   // (z_in / objective stay NULL: the kernels draw the rows)
-    if (int rc = check_sample_args("lsnf_sample", &c.g, nz, width, depth, coupling, B, rng, temperature, plan, z_out, objective_out, eps_out, ll_out))
-        return rc < 0 ? rc : LSNF_OK;
-    const LsnfSampleArgs smp = {LsnfRngArgs{rng->seed, rng->offset, rng->offset_dev, rng->row0, 1}, temperature, eps_out, ll_out};
-    c.plan = plan; c.B = B; c.vec4 = row_vector_width(c.g, {z_out, eps_out}); c.stream = (hipStream_t)stream;
-    c.z_out = z_out; c.objective_out = objective_out; c.smp = &smp;
-    return reverse_select_launch("lsnf_sample", c);
+    return sample_entry("lsnf_sample", /*keep=*/false, plan, nz, width, depth, coupling, B, rng, temperature, z_out, objective_out, eps_out,
+                        ll_out, nullptr, nullptr, nullptr, stream);
 }
 
 int lsnf_reverse_keep_covers(int nz, int width, int depth, int coupling, int B) {
@@ -667,141 +681,98 @@ int lsnf_reverse_keep_covers(int nz, int width, int depth, int coupling, int B) 
 int lsnf_reverse_keep(const float* plan, int nz, int width, int depth, int coupling, int B, const float* z_in,
                       const float* objective, float* z_out, float* objective_out, float* z_saved, float* act_saved,
                       float* params_workspace, void* stream) {
-    LsnfReverseCall c;
-    if (int rc = check_reverse_args("lsnf_reverse_keep", &c.g, nz, width, depth, coupling, B, plan, z_in, objective, z_out, objective_out))
-        return rc < 0 ? rc : LSNF_OK;
-    c.plan = plan; c.B = B; c.stream = (hipStream_t)stream;
-    c.z_in = z_in; c.objective = objective; c.z_out = z_out; c.objective_out = objective_out;
-    return reverse_keep_launch("lsnf_reverse_keep", c, z_saved, act_saved, params_workspace);
+    return reverse_entry("lsnf_reverse_keep", /*keep=*/true, plan, nz, width, depth, coupling, B, z_in, objective, z_out, objective_out,
+                         z_saved, act_saved, params_workspace, stream);
 }
 
 int lsnf_sample_keep(const float* plan, int nz, int width, int depth, int coupling, int B, const LsnfRng* rng, float temperature,
                      float* z_out, float* objective_out, float* eps_out, float* ll_out, float* z_saved, float* act_saved,
                      float* params_workspace, void* stream) {
-    LsnfReverseCall c;                   // (z_in / objective stay NULL: the kernel draws the rows)
-    if (int rc = check_sample_args("lsnf_sample_keep", &c.g, nz, width, depth, coupling, B, rng, temperature, plan, z_out, objective_out, eps_out, ll_out))
-        return rc < 0 ? rc : LSNF_OK;
-    const LsnfSampleArgs smp = {LsnfRngArgs{rng->seed, rng->offset, rng->offset_dev, rng->row0, 1}, temperature, eps_out, ll_out};
-    c.plan = plan; c.B = B; c.stream = (hipStream_t)stream;
-    c.z_out = z_out; c.objective_out = objective_out; c.smp = &smp;
-    return reverse_keep_launch("lsnf_sample_keep", c, z_saved, act_saved, params_workspace);
+    return sample_entry("lsnf_sample_keep", /*keep=*/true, plan, nz, width, depth, coupling, B, rng, temperature, z_out, objective_out,
+                        eps_out, ll_out, z_saved, act_saved, params_workspace, stream);
 }
 
 int lsnf_backward_z(const float* plan, int nz, int width, int depth, int coupling, int B, const float* z_out,
                     const float* z_saved, const float* act_saved, const float* g_z1, const float* g_logdet, int ll_mode,
                     float ll_scale, float* g_z_in, void* stream) {
-    LsnfGeo g;
-    if (int rc = geo_or_fail(&g, nz, width, depth, coupling)) return rc;
-    if (B < 0 || B > (1 << 28)) return fail(LSNF_E_ARG, "lsnf_backward_z: B=%d out of range", B);
-    if (B == 0) return LSNF_OK;
-    if (!plan || !z_out || !g_z_in || (depth > 1 && !z_saved)) return fail(LSNF_E_ARG, "lsnf_backward_z: NULL argument");
-    if (!aligned16(plan)) return fail(LSNF_E_ARG, "lsnf_backward_z: plan must be 16-byte aligned");
-    if (!aligned4(z_out) || !aligned4(z_saved) || !aligned4(g_z1) || !aligned4(g_logdet) || !aligned4(g_z_in))
-        return fail(LSNF_E_ARG, "lsnf_backward_z: tensors must be 4-byte aligned");
-    const int vec4 = row_vector_width(g, {z_out, g_z_in, z_saved, g_z1});
-    if (act_saved && !aligned16(act_saved)) return fail(LSNF_E_ARG, "lsnf_backward_z: act_saved must be 16-byte aligned");
+    Check ck{"lsnf_backward_z"};
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B)) return ck.rc;
+    if (ck.empty) return LSNF_OK;
+    if (ck.required(plan && z_out && g_z_in && (depth == 1 || z_saved)) || ck.aligned16("plan", {plan}) ||
+        ck.aligned4("tensors", {z_out, z_saved, g_z1, g_logdet, g_z_in}) || ck.aligned16("act_saved", {act_saved}))
+        return ck.rc;
     LsnfBackwardCall c;
-    c.g = g; c.plan = plan; c.B = B; c.vec4 = vec4; c.stream = (hipStream_t)stream;
+    ck.head(c, plan, B, stream, {z_out, g_z_in, z_saved, g_z1});
     c.z_out = z_out; c.z_saved = z_saved; c.act_saved = act_saved; c.g_z1 = g_z1; c.g_logdet = g_logdet;
     c.ll_mode = ll_mode; c.ll_scale = ll_scale; c.g_z_in = g_z_in;
-    const Pick p = select_backward(c);
-    const hipError_t e = launch_backward(p, c);
-    if (p.k == K_NONE || e != hipSuccess) return launch_fail(e, "lsnf_backward_z", p.k);
-    return LSNF_OK;
+    return backward_launch(ck.entry, c);
 }
 
 int lsnf_reverse_backward_z(const float* plan, int nz, int width, int depth, int coupling, int B, const float* z_out,
                             const float* z_saved, const float* act_saved, const float* g_x, const float* g_objective,
                             float* g_z_in, void* stream) {
-    LsnfGeo g;
-    if (int rc = geo_or_fail(&g, nz, width, depth, coupling)) return rc;
-    if (B < 0 || B > (1 << 28)) return fail(LSNF_E_ARG, "lsnf_reverse_backward_z: B=%d out of range", B);
-    if (B == 0) return LSNF_OK;
-    if (!plan || !z_out || !g_z_in || (depth > 1 && !z_saved)) return fail(LSNF_E_ARG, "lsnf_reverse_backward_z: NULL argument");
-    if (!act_saved) return fail(LSNF_E_ARG, "lsnf_reverse_backward_z: act_saved is required (lsnf_forward's stash, or lsnf_restash)");
-    if (!aligned16(plan)) return fail(LSNF_E_ARG, "lsnf_reverse_backward_z: plan must be 16-byte aligned");
-    if (!aligned16(act_saved)) return fail(LSNF_E_ARG, "lsnf_reverse_backward_z: act_saved must be 16-byte aligned");
-    if (!aligned4(z_out) || !aligned4(z_saved) || !aligned4(g_x) || !aligned4(g_objective) || !aligned4(g_z_in))
-        return fail(LSNF_E_ARG, "lsnf_reverse_backward_z: tensors must be 4-byte aligned");
+    Check ck{"lsnf_reverse_backward_z"};
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B)) return ck.rc;
+    if (ck.empty) return LSNF_OK;
+    if (ck.required(plan && z_out && g_z_in && (depth == 1 || z_saved)) ||
+        ck.refuse(!act_saved, "act_saved is required (lsnf_forward's stash, or lsnf_restash)") || ck.aligned16("plan", {plan}) ||
+        ck.aligned16("act_saved", {act_saved}) || ck.aligned4("tensors", {z_out, z_saved, g_x, g_objective, g_z_in}))
+        return ck.rc;
     LsnfReverseBackwardCall c;
-    c.g = g; c.plan = plan; c.B = B; c.vec4 = row_vector_width(g, {z_out, g_z_in, z_saved, g_x}); c.stream = (hipStream_t)stream;
+    ck.head(c, plan, B, stream, {z_out, g_z_in, z_saved, g_x});
     c.z_out = z_out; c.z_saved = z_saved; c.act_saved = act_saved; c.g_x = g_x; c.g_objective = g_objective; c.g_z_in = g_z_in;
     const Pick p = select_reverse_backward(c);
-    const hipError_t e = lsnf_launch_small3_reverse_backward_z(c, p.st);
-    if (e != hipSuccess) return launch_fail(e, "lsnf_reverse_backward_z", p.k);
-    return LSNF_OK;
+    return report(ck.entry, p, lsnf_launch_small3_reverse_backward_z(c, p.st));
 }
 
 int lsnf_reverse_langevin_step(const float* plan, int nz, int width, int depth, int coupling, int B, const float* z_out,
                                const float* z_saved, const float* act_saved, const float* grad_g, const float* noise,
                                const LsnfRng* rng, float step_size, float* eps_new, float* g_eps_out, float* g_norm, float* eps_norm,
                                void* stream) {
-    LsnfGeo g;
-    if (int rc = geo_or_fail(&g, nz, width, depth, coupling)) return rc;
-    if (B < 0 || B > (1 << 28)) return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: B=%d out of range", B);
-    if (noise && rng) return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: pass either a noise tensor or an rng, not both");
-    if (rng && rng->offset_dev && (reinterpret_cast<uintptr_t>(rng->offset_dev) & 7u))
-        return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: rng->offset_dev must be 8-byte aligned");
-    if (rng && rng->row0 < 0) return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: rng->row0 must be >= 0");
-    if (!std::isfinite(step_size)) return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: step_size must be finite (got %g)", (double)step_size);
+    Check ck{"lsnf_reverse_langevin_step"};
     // eps_new may be z_out (every read of a workgroup's rows precedes its stores), g_eps_out may be grad_g (read first, as g_z_in / g_x
     // of lsnf_reverse_backward_z); nothing else the kernel reads may be what it writes, and no two outputs may be one tensor
-    if (eps_new && (eps_new == grad_g || eps_new == noise || eps_new == z_saved || eps_new == g_eps_out))
-        return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: eps_new must not alias grad_g, noise, z_saved or g_eps_out");
-    if (g_eps_out && (g_eps_out == noise || g_eps_out == z_out || g_eps_out == z_saved))
-        return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: g_eps_out must not alias noise, z_out or z_saved");
-    for (const float* nrm : {(const float*)g_norm, (const float*)eps_norm})
-        if (nrm && (nrm == z_out || nrm == z_saved || nrm == grad_g || nrm == noise || nrm == eps_new || nrm == g_eps_out ||
-                    (g_norm == eps_norm)))
-            return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: g_norm / eps_norm must not alias another tensor of the call");
-    if (B == 0) return LSNF_OK;
-    if (!plan || !z_out || !eps_new || (depth > 1 && !z_saved)) return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: NULL argument");
-    if (!act_saved)
-        return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: act_saved is required (the stash of lsnf_forward, lsnf_restash or lsnf_reverse_keep)");
-    if (!aligned16(plan)) return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: plan must be 16-byte aligned");
-    if (!aligned16(act_saved)) return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: act_saved must be 16-byte aligned");
-    if (!aligned4(z_out) || !aligned4(z_saved) || !aligned4(grad_g) || !aligned4(noise) || !aligned4(eps_new) || !aligned4(g_eps_out) ||
-        !aligned4(g_norm) || !aligned4(eps_norm))
-        return fail(LSNF_E_ARG, "lsnf_reverse_langevin_step: tensors must be 4-byte aligned");
+    auto norm_aliases = [&](const float* nrm) {
+        return nrm && (nrm == z_out || nrm == z_saved || nrm == grad_g || nrm == noise || nrm == eps_new || nrm == g_eps_out || g_norm == eps_norm);
+    };
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B) || ck.rng(noise, rng, /*row0_first=*/false) ||
+        ck.refuse(!std::isfinite(step_size), "step_size must be finite (got %g)", (double)step_size) ||
+        ck.refuse(eps_new && (eps_new == grad_g || eps_new == noise || eps_new == z_saved || eps_new == g_eps_out),
+                  "eps_new must not alias grad_g, noise, z_saved or g_eps_out") ||
+        ck.refuse(g_eps_out && (g_eps_out == noise || g_eps_out == z_out || g_eps_out == z_saved),
+                  "g_eps_out must not alias noise, z_out or z_saved") ||
+        ck.refuse(norm_aliases(g_norm) || norm_aliases(eps_norm), "g_norm / eps_norm must not alias another tensor of the call"))
+        return ck.rc;
+    if (ck.empty) return LSNF_OK;
+    if (ck.required(plan && z_out && eps_new && (depth == 1 || z_saved)) ||
+        ck.refuse(!act_saved, "act_saved is required (the stash of lsnf_forward, lsnf_restash or lsnf_reverse_keep)") ||
+        ck.aligned16("plan", {plan}) || ck.aligned16("act_saved", {act_saved}) ||
+        ck.aligned4("tensors", {z_out, z_saved, grad_g, noise, eps_new, g_eps_out, g_norm, eps_norm}))
+        return ck.rc;
     LsnfReverseLangevinCall c;           // (no g_x / g_objective: the upstream gradient is grad_g)
-    c.g = g; c.plan = plan; c.B = B; c.vec4 = row_vector_width(g, {z_out, z_saved, grad_g, noise, eps_new, g_eps_out}); c.stream = (hipStream_t)stream;
+    ck.head(c, plan, B, stream, {z_out, z_saved, grad_g, noise, eps_new, g_eps_out});
     c.z_out = z_out; c.z_saved = z_saved; c.act_saved = act_saved; c.g_z_in = g_eps_out;
     c.grad_g = grad_g; c.noise = noise; c.step = step_size; c.eps_new = eps_new; c.g_norm = g_norm; c.eps_norm = eps_norm;
-    if (rng) c.rng = LsnfRngArgs{rng->seed, rng->offset, rng->offset_dev, rng->row0, 1};
+    c.rng = rng_args(rng);
     const Pick p = select_reverse_langevin(c);
-    const hipError_t e = lsnf_launch_small3_reverse_langevin(c, p.st);
-    if (e != hipSuccess) return launch_fail(e, "lsnf_reverse_langevin_step", p.k);
-    return LSNF_OK;
+    return report(ck.entry, p, lsnf_launch_small3_reverse_langevin(c, p.st));
 }
 
 int lsnf_langevin_step(const float* plan, int nz, int width, int depth, int coupling, int B, const float* z_cur,
                        const float* z_out, const float* z_saved, const float* act_saved, const float* grad_g,
                        const float* noise, const LsnfRng* rng, float step_size, float* z_new, float* gf_norm, float* gg_norm, void* stream) {
-    LsnfGeo g;
-    if (int rc = geo_or_fail(&g, nz, width, depth, coupling)) return rc;
-    if (B < 0 || B > (1 << 28)) return fail(LSNF_E_ARG, "lsnf_langevin_step: B=%d out of range", B);
-    if (B == 0) return LSNF_OK;
-    if (!plan || !z_cur || !z_out || !z_new || (depth > 1 && !z_saved)) return fail(LSNF_E_ARG, "lsnf_langevin_step: NULL argument");
-    if (!aligned16(plan)) return fail(LSNF_E_ARG, "lsnf_langevin_step: plan must be 16-byte aligned");
-    if (!aligned4(z_cur) || !aligned4(z_out) || !aligned4(z_saved) || !aligned4(grad_g) || !aligned4(noise) || !aligned4(z_new) ||
-        !aligned4(gf_norm) || !aligned4(gg_norm))
-        return fail(LSNF_E_ARG, "lsnf_langevin_step: tensors must be 4-byte aligned");
-    const int vec4 = row_vector_width(g, {z_out, z_saved, z_cur, grad_g, noise, z_new});
-    if (act_saved && !aligned16(act_saved)) return fail(LSNF_E_ARG, "lsnf_langevin_step: act_saved must be 16-byte aligned");
-    if (noise && rng) return fail(LSNF_E_ARG, "lsnf_langevin_step: pass either a noise tensor or an rng, not both");
-    if (rng && rng->offset_dev && (reinterpret_cast<uintptr_t>(rng->offset_dev) & 7u))
-        return fail(LSNF_E_ARG, "lsnf_langevin_step: rng->offset_dev must be 8-byte aligned");
-    if (rng && rng->row0 < 0) return fail(LSNF_E_ARG, "lsnf_langevin_step: rng->row0 must be >= 0");
-    LsnfLangevinArgs lv = {z_cur, grad_g, noise, z_new, gf_norm, gg_norm, step_size,
-                           rng ? LsnfRngArgs{rng->seed, rng->offset, rng->offset_dev, rng->row0, 1}
-                               : LsnfRngArgs{0ull, 0ull, nullptr, 0ll, 0}};
+    Check ck{"lsnf_langevin_step"};
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B)) return ck.rc;
+    if (ck.empty) return LSNF_OK;        // (before the rng rules, unlike lsnf_reverse_langevin_step and lsnf_sample)
+    if (ck.required(plan && z_cur && z_out && z_new && (depth == 1 || z_saved)) || ck.aligned16("plan", {plan}) ||
+        ck.aligned4("tensors", {z_cur, z_out, z_saved, grad_g, noise, z_new, gf_norm, gg_norm}) || ck.aligned16("act_saved", {act_saved}) ||
+        ck.rng(noise, rng, /*row0_first=*/false))
+        return ck.rc;
+    const LsnfLangevinArgs lv = {z_cur, grad_g, noise, z_new, gf_norm, gg_norm, step_size, rng_args(rng)};
     LsnfBackwardCall c;                  // (no g_z1 / g_logdet / g_z_in: the gradient of -log p, consumed by the update)
-    c.g = g; c.plan = plan; c.B = B; c.vec4 = vec4; c.stream = (hipStream_t)stream;
+    ck.head(c, plan, B, stream, {z_out, z_saved, z_cur, grad_g, noise, z_new});
     c.z_out = z_out; c.z_saved = z_saved; c.act_saved = act_saved; c.ll_mode = 1; c.ll_scale = -1.0f; c.lv = &lv;
-    const Pick p = select_backward(c);
-    const hipError_t e = launch_backward(p, c);
-    if (p.k == K_NONE || e != hipSuccess) return launch_fail(e, "lsnf_langevin_step", p.k);
-    return LSNF_OK;
+    return backward_launch(ck.entry, c);
 }
 
 size_t lsnf_backward_params_workspace_floats(int nz, int width, int depth, int B) {

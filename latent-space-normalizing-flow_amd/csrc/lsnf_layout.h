@@ -209,10 +209,13 @@ static inline LsnfFoldLayout lsnf_fold_layout(int nz, int width) {
     f.per_block = (o + 3) & ~3;
     return f;
 }
+static inline size_t lsnf_params_workspace_dump(int nz, int width, int depth) {      // where the dump starts: behind G and the folded gradients
+    return 4 + (size_t)depth * lsnf_fold_layout(nz, width).per_block;
+}
 // ... + 4 floats behind the dump: word 0 = the layout of the h1 / h2 arrays the forward of this evaluation wrote (0 row-major,
 // 1 tiled), set by lsnf_forward for the batch sizes at which the contraction of lsnf_params3.hip may run
 static inline size_t lsnf_params_workspace_tag(int nz, int width, int depth, int B) {
-    return 4 + (size_t)depth * lsnf_fold_layout(nz, width).per_block + (size_t)depth * lsnf_dump_layout(B, nz, width).per_block;
+    return lsnf_params_workspace_dump(nz, width, depth) + (size_t)depth * lsnf_dump_layout(B, nz, width).per_block;
 }
 static inline size_t lsnf_params_workspace_floats(int nz, int width, int depth, int B) {
     return lsnf_params_workspace_tag(nz, width, depth, B) + 4;
