@@ -81,6 +81,15 @@ _SIGNATURES = {
                                   ctypes.POINTER(LsnfAdamOptions), c_void_p]),
 }
 
+# the extensions of include/lsnf_flow_mcmc.h: exported by the same library, outside the core ABI's symbol set
+_EXT_SIGNATURES = {
+    "lsnf_mala_step": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, ctypes.POINTER(LsnfRng), c_float, ctypes.c_uint,
+                               c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
 _lib = None
 
 
@@ -90,6 +99,10 @@ class LsnfError(RuntimeError):
 
 def exported_symbols():
     return sorted(_SIGNATURES)
+
+
+def extension_symbols():
+    return sorted(_EXT_SIGNATURES)
 
 
 def load():
@@ -102,7 +115,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C latent-space-normalizing-flow_amd/csrc`). There is no CPU/PyTorch fallback.")
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_LOCAL)
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -46,6 +46,12 @@ struct LsnfBackwardCall : LsnfCall {     // lsnf_backward_z, lsnf_langevin_step 
     const LsnfLangevinArgs* lv = nullptr;
     float* dump = nullptr; double* gl_total = nullptr; int dump_tiled = 0;
 };
+struct LsnfMalaCall : LsnfBackwardCall {  // lsnf_mala_step: ll_mode 1 / ll_scale -1 at the proposal; lv holds z_prop (z_cur), grad_g,
+    const float* ll_prop = nullptr; const float* energy_g = nullptr; const float* uniform = nullptr;      // noise, z_next (z_new), step, rng
+    float* z_acc = nullptr; float* grad_acc = nullptr; float* u_acc = nullptr;
+    float* accept_out = nullptr; float* log_alpha_out = nullptr;
+    unsigned flags = 0;                  // LSNF_MALA_*
+};
 struct LsnfReverseBackwardCall : LsnfCall {      // lsnf_reverse_backward_z
     const float* z_out = nullptr; const float* z_saved = nullptr; const float* act_saved = nullptr;
     const float* g_x = nullptr; const float* g_objective = nullptr;
@@ -126,6 +132,7 @@ bool lsnf_small_backward_covers(const LsnfBackwardCall& c);
 hipError_t lsnf_launch_small_backward_z(const LsnfBackwardCall& c);
 int lsnf_small3_backward_st(const LsnfBackwardCall& c);
 hipError_t lsnf_launch_small3_backward_z(const LsnfBackwardCall& c, int st);
+hipError_t lsnf_launch_small3_mala(const LsnfMalaCall& c, int st);          // st: lsnf_small3_backward_st of the call
 int lsnf_small3_reverse_backward_st(const LsnfReverseBackwardCall& c);
 hipError_t lsnf_launch_small3_reverse_backward_z(const LsnfReverseBackwardCall& c, int st);
 hipError_t lsnf_launch_small3_reverse_langevin(const LsnfReverseLangevinCall& c, int st);      // st: of the same predicate

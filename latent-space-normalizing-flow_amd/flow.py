@@ -881,3 +881,7 @@ def adam_step(params: Sequence[torch.Tensor], grads: Sequence[Optional[torch.Ten
                                     float(eps), float(weight_decay), mn, float(ema_decay) if ema else 0.0, _ptr(norm))
         _call("lsnf_adam_step_ex", dev, tab[1], tab[2], nz, width, depth, coupling, _ptr(state), ctypes.byref(opts))
     return norm
+
+
+# ---- Markov-chain extensions (include/lsnf_flow_mcmc.h): defined in mcmc.py on this file's checking path, used as flow.mala_step etc.
+from .mcmc import MALA_INIT, MalaState, new_mala_state, mala_step  # noqa: E402,F401

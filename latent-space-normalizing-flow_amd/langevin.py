@@ -2,6 +2,7 @@
 restated (they are closures inside train.py and cannot be imported) on top of the fused kernels.
 
   sample_langevin_post_z_with_flow  <- train.py:307-335 (training) / :602-634 (testing: 20x steps, no noise)
+  sample_mala_post_z_with_flow         the same chain Metropolis-adjusted (exact at any step size; per-row acceptance rate)
   sample_langevin_post_eps_with_flow   the same sampler in the flow's base space (eps, with z = f^-1(eps)); not in the reference
   flow_mle_step                     <- train.py:404-415
   sample_x                          <- train.py:472-478 (prior samples for the FID evaluation)
@@ -48,6 +49,36 @@ def sample_langevin_post_z_with_flow(z, x, netG: nn.Module, netF, *, g_l_steps: 
     if philox is not None and g_l_with_noise:
         philox.advance(g_l_steps)
     return z.detach(), gg_norm, gf_norm, f_log_lkhd
+
+
+def sample_mala_post_z_with_flow(z, x, netG: nn.Module, netF, *, g_l_steps: int, g_l_step_size: float, g_llhd_sigma: float, philox):
+    """The sampler above Metropolis-adjusted (MALA): the same proposal z' = z - s^2/2 grad U(z) + s xi, accepted with probability
+    min(1, pi(z') q(z|z') / (pi(z) q(z'|z))), so the chain is exact for p(z|x) ~ p_flow(z) p(x|G(z)) at any step size and its
+    acceptance rate tells whether g_l_step_size is sound.  U = |x - G(z)|^2 / (2 sigma^2) - ll(z) per row; the generator's energy and
+    gradient come from torch autograd as in train.py:312-314 (the sum over pixels kept per row), the flow's part, the decision and
+    the next proposal from `netF.mala_step`.  K = g_l_steps proposals take K + 1 evaluations: call 0 starts the chain at z, calls
+    1 .. K-1 decide a proposal and make the next, call K decides only.  `philox` (a `flow.PhiloxNoise`, required) gives call j its
+    uniform and its noise at offset + j and is ADVANCED by K + 1 on return.
+    Returns (z_k (B, nz, 1, 1), accept_rate (B) = accepted proposals / K, U(z_k) (B)); g_l_steps = 0 or an empty batch returns the
+    input (and None, None)."""
+    from . import flow
+    B, nz = z.shape[0], z.shape[1]
+    if g_l_steps < 1 or B == 0:
+        return z.detach().clone().view(B, nz, 1, 1), None, None
+    K, c = int(g_l_steps), 1.0 / (2.0 * g_llhd_sigma * g_llhd_sigma)
+    z_prop = z.detach().reshape(B, nz).contiguous().clone()
+    state = flow.new_mala_state(netF._plan(), B, z_prop.device)
+    accepted = torch.zeros(B, dtype=torch.float32, device=z_prop.device)
+    for j in range(K + 1):
+        zr = z_prop.view(B, nz, 1, 1).detach().requires_grad_(True)
+        energy = c * ((netG(zr) - x) ** 2).flatten(1).sum(1)                                 # train.py:312-313, per row
+        grad_g = torch.autograd.grad(energy.sum(), zr)[0].reshape(B, nz).contiguous()        # train.py:314
+        _, acc, _, _ = netF.mala_step(z_prop, grad_g, energy.detach(), state, philox.step(j), g_l_step_size, init=j == 0,
+                                      propose=j < K, inplace=True, reuse_buffers=True)
+        if j:
+            accepted += acc
+    philox.advance(K + 1)
+    return state.z.view(B, nz, 1, 1), accepted / K, state.energy
 
 
 def sample_langevin_post_eps_with_flow(eps, x, netG: nn.Module, netF, *, g_l_steps: int, g_l_step_size: float,

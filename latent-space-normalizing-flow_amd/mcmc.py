@@ -1,0 +1,74 @@
+"""Markov-chain extensions of the functional host API (C: include/lsnf_flow_mcmc.h), re-exported by flow.py -- use them as
+`flow.mala_step`, `flow.MalaState`, `flow.new_mala_state`.  Every tensor goes through flow.py's one checking path before anything is
+launched; like there, all functions raise on CPU tensors: there is no CPU path."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+
+from ._lib import LsnfError
+from .flow import (FlowPlan, PhiloxNoise, _anchor, _call, _check_in, _check_like, _check_out, _check_stash, _noise_args, _plan_head,  # noqa: F401
+                   _ptr, _stream_buffers, forward, new_act_saved)
+
+
+MALA_INIT = 1                 # include/lsnf_flow_mcmc.h LSNF_MALA_INIT
+
+
+@dataclass
+class MalaState:
+    """The kept state of a Metropolis-adjusted chain (`mala_step`): z (B, nz) the accepted points, grad (B, nz) = grad U(z),
+    energy (B) = U(z), with U = energy_g - ll.  Written by an init=True call, updated in place by every later one."""
+    z: torch.Tensor
+    grad: torch.Tensor
+    energy: torch.Tensor
+
+
+def new_mala_state(plan: FlowPlan, B: int, device) -> MalaState:
+    """A zeroed chain state of B rows for `mala_step` (the init=True call fills it)."""
+    f32 = dict(dtype=torch.float32, device=device)
+    return MalaState(torch.zeros((int(B), plan.nz), **f32), torch.zeros((int(B), plan.nz), **f32), torch.zeros(int(B), **f32))
+
+
+def mala_step(plan: FlowPlan, z_prop: torch.Tensor, grad_g: Optional[torch.Tensor], energy_g: Optional[torch.Tensor],
+              state: MalaState, noise, step_size: float, *, init: bool = False, uniform: Optional[torch.Tensor] = None,
+              propose: bool = True, inplace: bool = False, reuse_buffers: bool = False):
+    """One Metropolis-adjusted Langevin call (include/lsnf_flow_mcmc.h `lsnf_mala_step`) in two launches: the forward at the
+    proposal `z_prop` (ll, block outputs, stash) and the backward whose output section DECIDES z_prop against `state` -- target
+    p(z) ~ exp(-U), U = energy_g - ll -- updates the state in place and, with propose, writes the next proposal
+    z_next = z_state - 0.5 s^2 grad_state + s * xi.  grad_g (B, nz) / energy_g (B): the caller's gradient and per-row energy at
+    z_prop (None = 0).  init=True starts a chain at z_prop: every row accepted, the state written without being read.
+    `noise`: a `PhiloxNoise` (the uniform and xi are drawn inside the kernel: xi is `langevin_step`'s draw at the same offset, the
+    uniform a stream of its own), or a (B, nz) tensor of N(0,1) draws together with uniform= (B) draws in (0, 1) -- the tensor is
+    left out (None) with propose=False, the uniform may be with init=True.  K proposals are K + 1 calls: init, K - 1 deciding and
+    proposing calls, one with propose=False.
+    Returns (z_next or None, accepted (B) of 1.0 / 0.0, log_alpha (B), ll_prop (B)).  inplace: z_next is z_prop itself.
+    reuse_buffers: as `langevin_step`'s -- the last three are then overwritten by the next call."""
+    B, dev = _anchor(z_prop, "z_prop", plan), z_prop.device
+    _check_like(grad_g, "grad_g", z_prop, "z_prop")
+    _check_in(energy_g, "energy_g", B, dev)
+    if not isinstance(state, MalaState):
+        raise LsnfError("state must be a flow.MalaState (new_mala_state())")
+    _check_out(state.z, "state.z", B * plan.nz, dev)
+    _check_out(state.grad, "state.grad", B * plan.nz, dev)
+    _check_out(state.energy, "state.energy", B, dev)
+    noise, rng = _noise_args(noise, z_prop, "z_prop", dev)
+    _check_in(uniform, "uniform", B, dev)
+    if rng is not None and uniform is not None:
+        raise LsnfError("pass either a PhiloxNoise or the tensors (noise, uniform=), not both")
+
+    def make():
+        f32 = dict(dtype=torch.float32, device=dev)
+        return {"act": new_act_saved(plan, B, dev), "out": (torch.empty_like(z_prop), torch.empty(B, **f32), torch.empty(B, **f32)),
+                "saved": torch.empty((plan.depth - 1, B, plan.nz), **f32) if plan.depth > 1 else None,
+                "acc": torch.empty(B, **f32), "la": torch.empty(B, **f32)}
+    bufs = _stream_buffers(plan, "_mala_buffers", B, dev, make) if reuse_buffers else make()
+    act, saved = bufs["act"], bufs["saved"]
+    _check_stash(plan, B, dev, saved, act, True)
+    z1, _, ll, _ = forward(plan, z_prop, None, want_ll=True, out=bufs["out"], act_saved=act, z_saved_out=saved)
+    z_next = None if not propose else z_prop if inplace else torch.empty_like(z_prop)
+    _call("lsnf_mala_step", dev, *_plan_head(plan), B, _ptr(z_prop), _ptr(z1), _ptr(saved), _ptr(act), _ptr(ll), _ptr(grad_g),
+          _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(noise), _ptr(uniform), rng, float(step_size),
+          MALA_INIT if init else 0, _ptr(z_next), _ptr(bufs["acc"]), _ptr(bufs["la"]))
+    return z_next, bufs["acc"], bufs["la"], ll

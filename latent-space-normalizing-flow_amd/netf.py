@@ -460,6 +460,15 @@ class _netF(nn.Module):
                                   None if grad_g is None else grad_g.detach().contiguous(), noise, step_size,
                                   inplace=inplace, reuse_buffers=reuse_buffers)
 
+    def mala_step(self, z_prop, grad_g=None, energy_g=None, state=None, noise=None, step_size=0.1, *, init=False, uniform=None,
+                  propose=True, inplace=False, reuse_buffers=False):
+        """One Metropolis-adjusted Langevin call at the proposal z_prop against the kept chain `state` (`flow.mala_step`: the
+        forward at z_prop, then the backward that decides, updates the state and proposes again).
+        Returns (z_next or None, accepted, log_alpha, ll_prop)."""
+        det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t
+        return flow.mala_step(self._plan(), det(z_prop), det(grad_g), det(energy_g), state, det(noise), step_size, init=init,
+                              uniform=det(uniform), propose=propose, inplace=inplace, reuse_buffers=reuse_buffers)
+
     def mle_grads(self, z, accumulate: bool = False, max_norm: Optional[float] = None, reuse_buffers: bool = False):
         """Fused flow-MLE gradients (train.py:404-411): loss_f = -mean_b ll(z_b) and d loss_f / d theta written to
         `.grad` of the 60 live tensors -- forward (ll summed in-kernel), dump backward, batch contraction, unfold:
