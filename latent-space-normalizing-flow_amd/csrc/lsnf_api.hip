@@ -181,7 +181,7 @@ enum Kernel {
     K_NONE, K_FWD, K_FWD3, K_FWD3Q, K_FWD2H_FIXUP, K_SMALL_FWD, K_SMALL3_FWD,
     K_REV, K_REV3, K_REV2H_FIXUP, K_SMALL_REV, K_SMALL3_REV,
     K_BWD, K_BWD3, K_SMALL_BWD, K_SMALL3_BWD,
-    K_SMALL3_RBWD, K_SMALL3_RLV, K_SMALL3_MALA,
+    K_SMALL3_RBWD, K_SMALL3_RLV, K_SMALL3_MALA, K_SMALL3_RMALA,
 };
 const char* const kKernelName[] = {
     "no kernel takes this call", "lsnf_fwd_kernel", "lsnf_fwd3b_kernel", "lsnf_fwd3q_kernel",
@@ -189,7 +189,7 @@ const char* const kKernelName[] = {
     "lsnf_rev_kernel", "lsnf_rev3_kernel", "lsnf_rev2h_kernel + lsnf_rev3_kernel fix-up", "lsnf_small_rev_kernel",
     "lsnf_small3_rev_kernel",
     "lsnf_bwd_z_kernel", "lsnf_bwd3_kernel", "lsnf_small_bwd_kernel", "lsnf_small3_bwd_kernel",
-    "lsnf_small3_rbwd_kernel", "lsnf_small3_rbwd_kernel (update form)", "lsnf_small3_mala_kernel",
+    "lsnf_small3_rbwd_kernel", "lsnf_small3_rbwd_kernel (update form)", "lsnf_small3_mala_kernel", "lsnf_small3_rmala_kernel",
 };
 struct Pick { Kernel k; int st = 0; };     // st: rows per workgroup / 16 of the small3 kernels
 
@@ -384,6 +384,9 @@ Pick select_reverse_langevin(const LsnfReverseLangevinCall& c) { return {K_SMALL
 // The Metropolis-adjusted step (lsnf_mala_step) is the latency bf16x3 backward with the accept / reject tail as its output section
 // (lsnf_small3_mala.hip): like the two above, one kernel under every math mode and batch size, whatever the small-batch threshold.
 Pick select_mala(const LsnfMalaCall& c) { return {K_SMALL3_MALA, lsnf_small3_backward_st(c)}; }
+// Its base-space form (lsnf_reverse_mala_step) is the reverse-backward with that tail (lsnf_small3_rmala.hip): one kernel again, the
+// workgroup shape of the plain reverse-backward of the call.
+Pick select_reverse_mala(const LsnfReverseMalaCall& c) { return {K_SMALL3_RMALA, lsnf_small3_reverse_backward_st(c)}; }
 
 // Batch contraction of the parameter gradients (LsnfContraction): on the bf16 matrix pipe where lsnf_params3.hip covers the
 // call (use_x3); from 4 096 rows the fp32-MFMA kernel through LDS, with the widest row loads the rows allow -- every row the
@@ -831,6 +834,59 @@ int lsnf_mala_step(const float* plan, int nz, int width, int depth, int coupling
     c.accept_out = accept_out; c.log_alpha_out = log_alpha_out; c.flags = flags;
     const Pick p = select_mala(c);
     return report(ck.entry, p, lsnf_launch_small3_mala(c, p.st));
+}
+
+int lsnf_reverse_mala_step(const float* plan, int nz, int width, int depth, int coupling, int B, const float* eps_prop,
+                           const float* z_saved, const float* act_saved, const float* grad_g, const float* energy_g, float* eps_acc,
+                           float* grad_acc, float* u_acc, const float* noise, const float* uniform, const LsnfRng* rng, float step_size,
+                           unsigned flags, float* eps_next, float* accept_out, float* log_alpha_out, void* stream) {
+    Check ck{"lsnf_reverse_mala_step"};
+    struct Named { const char* name; const void* p; };
+    const Named reads[] = {{"plan", plan}, {"eps_prop", eps_prop}, {"z_saved", z_saved}, {"act_saved", act_saved}, {"grad_g", grad_g},
+                           {"energy_g", energy_g}, {"noise", noise}, {"uniform", uniform}};
+    const Named writes[] = {{"eps_acc", eps_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc}, {"eps_next", eps_next}, {"accept_out", accept_out},
+                            {"log_alpha_out", log_alpha_out}};
+    // eps_next may be eps_prop (every read of a workgroup's rows precedes its stores); no other output may be a tensor the call
+    // reads, or another output
+    auto aliases = [&] {
+        for (const Named& w : writes) {
+            if (!w.p) continue;
+            for (const Named& r : reads)
+                if (w.p == r.p && !(&w == &writes[3] && &r == &reads[1])) return ck.refuse(true, "%s must not alias %s", w.name, r.name);
+            for (const Named& o : writes)
+                if (&o != &w && w.p == o.p) return ck.refuse(true, "%s must not alias %s", w.name, o.name);
+        }
+        return false;
+    };
+    const bool init = (flags & LSNF_MALA_INIT) != 0;
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B) ||
+        ck.refuse(uniform && rng, "pass either a uniform tensor or an rng, not both") || ck.rng(noise, rng, /*row0_first=*/false) ||
+        ck.refuse(!std::isfinite(step_size) || step_size == 0.0f, "step_size must be finite and non-zero (got %g)", (double)step_size) ||
+        ck.refuse(flags & ~LSNF_MALA_INIT, "unknown flag bits 0x%x", flags & ~LSNF_MALA_INIT) || aliases())
+        return ck.rc;
+    if (ck.empty) return LSNF_OK;
+    const Named needed[] = {{"plan", plan}, {"eps_prop", eps_prop}, {"eps_acc", eps_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc}};
+    for (const Named& r : needed)
+        if (ck.refuse(!r.p, "%s is required (NULL)", r.name)) return ck.rc;
+    if (ck.refuse(!act_saved, "act_saved is required (the stash of lsnf_forward, lsnf_restash or lsnf_reverse_keep)") ||
+        ck.refuse(depth > 1 && !z_saved, "z_saved is required (NULL) for depth > 1") ||
+        ck.refuse(!rng && !init && !uniform, "uniform is required without an rng (unless LSNF_MALA_INIT)") ||
+        ck.refuse(!rng && eps_next && !noise, "noise is required with eps_next when no rng is given") ||
+        ck.refuse(!rng && !eps_next && noise, "noise goes with eps_next: nothing is proposed without it") ||
+        ck.aligned16("plan", {plan}) || ck.aligned16("act_saved", {act_saved}))
+        return ck.rc;
+    for (const Named& r : reads)
+        if (ck.aligned4(r.name, {r.p})) return ck.rc;
+    for (const Named& w : writes)
+        if (ck.aligned4(w.name, {w.p})) return ck.rc;
+    LsnfReverseMalaCall c;               // (no g_x / g_objective / g_z_in: the gradient at the proposal is consumed by the tail)
+    ck.head(c, plan, B, stream, {eps_prop, z_saved, grad_g, noise, eps_next, eps_acc, grad_acc});
+    c.z_out = eps_prop; c.z_saved = z_saved; c.act_saved = act_saved;
+    c.grad_g = grad_g; c.noise = noise; c.step = step_size; c.eps_new = eps_next; c.rng = rng_args(rng);
+    c.energy_g = energy_g; c.uniform = uniform; c.eps_acc = eps_acc; c.grad_acc = grad_acc; c.u_acc = u_acc;
+    c.accept_out = accept_out; c.log_alpha_out = log_alpha_out; c.flags = flags;
+    const Pick p = select_reverse_mala(c);
+    return report(ck.entry, p, lsnf_launch_small3_reverse_mala(c, p.st));
 }
 
 size_t lsnf_backward_params_workspace_floats(int nz, int width, int depth, int B) {

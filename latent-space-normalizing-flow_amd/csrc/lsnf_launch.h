@@ -63,6 +63,12 @@ struct LsnfReverseLangevinCall : LsnfReverseBackwardCall {      // lsnf_reverse_
     float step = 0.f;
     float* eps_new = nullptr; float* g_norm = nullptr; float* eps_norm = nullptr;
 };
+struct LsnfReverseMalaCall : LsnfReverseLangevinCall {      // lsnf_reverse_mala_step: z_out is the proposal eps_prop, eps_new the next
+    const float* energy_g = nullptr; const float* uniform = nullptr;       // proposal eps_next (may be NULL); g_z_in and the norms stay NULL
+    float* eps_acc = nullptr; float* grad_acc = nullptr; float* u_acc = nullptr;
+    float* accept_out = nullptr; float* log_alpha_out = nullptr;
+    unsigned flags = 0;                  // LSNF_MALA_*
+};
 struct LsnfContractCall : LsnfCall {     // steps (2), (3) of lsnf_backward_params: batch contraction of the dump, chain rule
     const float* const* params_host = nullptr; float* const* grads_host = nullptr;
     const float* z_in = nullptr; const float* z_out = nullptr; const float* z_saved = nullptr;
@@ -136,6 +142,7 @@ hipError_t lsnf_launch_small3_mala(const LsnfMalaCall& c, int st);          // s
 int lsnf_small3_reverse_backward_st(const LsnfReverseBackwardCall& c);
 hipError_t lsnf_launch_small3_reverse_backward_z(const LsnfReverseBackwardCall& c, int st);
 hipError_t lsnf_launch_small3_reverse_langevin(const LsnfReverseLangevinCall& c, int st);      // st: of the same predicate
+hipError_t lsnf_launch_small3_reverse_mala(const LsnfReverseMalaCall& c, int st);              // st: of the same predicate
 
 bool lsnf_contract_x3_covers(const LsnfContractCall& c);                   // (also asked with NULL tensors: lsnf_api.hip dump_may_tile)
 hipError_t lsnf_launch_contract_x3(const LsnfContractCall& c, int chunk_override);

@@ -883,5 +883,5 @@ def adam_step(params: Sequence[torch.Tensor], grads: Sequence[Optional[torch.Ten
     return norm
 
 
-# ---- Markov-chain extensions (include/lsnf_flow_mcmc.h): defined in mcmc.py on this file's checking path, used as flow.mala_step etc.
-from .mcmc import MALA_INIT, MalaState, new_mala_state, mala_step  # noqa: E402,F401
+# ---- Markov-chain extensions (include/lsnf_flow_mcmc.h): defined in mcmc.py on this file's checking path, used as flow.mala_step, flow.reverse_mala_step etc.
+from .mcmc import MALA_INIT, MalaState, new_mala_state, mala_step, reverse_mala_step  # noqa: E402,F401

@@ -4,6 +4,7 @@ restated (they are closures inside train.py and cannot be imported) on top of th
   sample_langevin_post_z_with_flow  <- train.py:307-335 (training) / :602-634 (testing: 20x steps, no noise)
   sample_mala_post_z_with_flow         the same chain Metropolis-adjusted (exact at any step size; per-row acceptance rate)
   sample_langevin_post_eps_with_flow   the same sampler in the flow's base space (eps, with z = f^-1(eps)); not in the reference
+  sample_mala_post_eps_with_flow       the base-space chain Metropolis-adjusted (per-row acceptance rate)
   flow_mle_step                     <- train.py:404-415
   sample_x                          <- train.py:472-478 (prior samples for the FID evaluation)
 
@@ -145,6 +146,54 @@ def sample_langevin_post_eps_with_flow(eps, x, netG: nn.Module, netF, *, g_l_ste
     if philox is not None and noise:
         philox.advance(g_l_steps)
     return eps, z.view(B, nz, 1, 1), gg_norm, gf_norm
+
+
+def sample_mala_post_eps_with_flow(eps, x, netG: nn.Module, netF, *, g_l_steps: int, g_l_step_size: float, g_llhd_sigma: float, philox):
+    """The base-space sampler above Metropolis-adjusted (MALA): target p(eps | x) ~ N(eps; 0, I) * p(x | G(f^-1(eps))), i.e.
+    U(eps) = |eps|^2 / 2 + |x - G(z)|^2 / (2 sigma^2) with z = f^-1(eps) (the flow's log-determinant cancels), the proposal
+    eps' = eps - s^2/2 grad U(eps) + s xi of `flow.reverse_langevin_step`, accepted with probability
+    min(1, pi(eps') q(eps|eps') / (pi(eps) q(eps'|eps))): exact at the large steps the flow's preconditioning permits, and the
+    acceptance rate tells whether g_l_step_size is sound.  K = g_l_steps proposals take K + 1 evaluations; call j:
+        z      = f^-1(eps_prop)                      the reverse launch, keeping its backward's stash where
+                                                     `flow.reverse_keep_supported` (else reverse + forward at z)
+        energy, grad_g                               torch autograd through netG, per row, as `sample_mala_post_z_with_flow`
+        `netF.reverse_mala_step`                     decides eps_prop, updates the state, proposes again (j < K), in place
+    with `philox` (a `flow.PhiloxNoise`, required) giving call j its uniform and its noise at offset + j; it is ADVANCED by K + 1
+    on return.  eps: (B, nz) or (B, nz, 1, 1).
+    Returns (eps_k (B, nz), z_k = f^-1(eps_k) (B, nz, 1, 1) from one final reverse at the state, accept_rate (B) = accepted
+    proposals / K, U(eps_k) (B)).  g_l_steps = 0 or an empty batch returns the input without a launch, with None rates:
+    (eps, None, None, None), an empty batch with its empty z."""
+    from . import flow
+    B, nz = eps.shape[0], eps.shape[1]
+    eps_prop = eps.detach().reshape(B, nz).contiguous().clone()
+    if B == 0:
+        return eps_prop, eps_prop.view(0, nz, 1, 1), None, None
+    if g_l_steps < 1:
+        return eps_prop, None, None, None
+    plan = netF._plan()
+    K, c = int(g_l_steps), 1.0 / (2.0 * g_llhd_sigma * g_llhd_sigma)
+    keeps = flow.reverse_keep_supported(plan, B)
+    act = flow.new_act_saved(plan, B, eps_prop.device)
+    state = flow.new_mala_state(plan, B, eps_prop.device)
+    accepted = torch.zeros(B, dtype=torch.float32, device=eps_prop.device)
+    with torch.no_grad():
+        for j in range(K + 1):
+            if keeps:
+                z, _, saved = flow.reverse(plan, eps_prop, None, save_for_backward=True, act_saved=act)
+            else:
+                z, _ = flow.reverse(plan, eps_prop, None)
+                saved = flow.forward(plan, z, None, want_ll=False, save_for_backward=True, act_saved=act)[3]
+            with torch.enable_grad():
+                zr = z.view(B, nz, 1, 1).requires_grad_(True)
+                energy = c * ((netG(zr) - x) ** 2).flatten(1).sum(1)                                 # train.py:312-313, per row
+                grad_g = torch.autograd.grad(energy.sum(), zr)[0].reshape(B, nz).contiguous()        # train.py:314
+            _, acc, _ = netF.reverse_mala_step(eps_prop, saved, act, grad_g, energy.detach(), state, philox.step(j), g_l_step_size,
+                                               init=j == 0, propose=j < K, inplace=True, reuse_buffers=True)
+            if j:
+                accepted += acc
+        z = flow.reverse(plan, state.z, None)[0]
+    philox.advance(K + 1)
+    return state.z, z.view(B, nz, 1, 1), accepted / K, state.energy
 
 
 def flow_mle_step(netF, optF, z_g_k, f_max_norm: Optional[float] = None, fused: bool = False):

@@ -1,5 +1,5 @@
 """Markov-chain extensions of the functional host API (C: include/lsnf_flow_mcmc.h), re-exported by flow.py -- use them as
-`flow.mala_step`, `flow.MalaState`, `flow.new_mala_state`.  Every tensor goes through flow.py's one checking path before anything is
+`flow.mala_step`, `flow.reverse_mala_step`, `flow.MalaState`, `flow.new_mala_state`.  Every tensor goes through flow.py's one checking path before anything is
 launched; like there, all functions raise on CPU tensors: there is no CPU path."""
 from __future__ import annotations
 
@@ -19,7 +19,9 @@ MALA_INIT = 1                 # include/lsnf_flow_mcmc.h LSNF_MALA_INIT
 @dataclass
 class MalaState:
     """The kept state of a Metropolis-adjusted chain (`mala_step`): z (B, nz) the accepted points, grad (B, nz) = grad U(z),
-    energy (B) = U(z), with U = energy_g - ll.  Written by an init=True call, updated in place by every later one."""
+    energy (B) = U(z), with U = energy_g - ll.  Written by an init=True call, updated in place by every later one.
+    For the base-space chain of `reverse_mala_step` the same three arrays hold its state: z = the accepted points eps,
+    grad = grad U(eps) = eps + J_{f^-1}(eps)^T grad_g, energy = U(eps) = |eps|^2 / 2 + energy_g."""
     z: torch.Tensor
     grad: torch.Tensor
     energy: torch.Tensor
@@ -72,3 +74,49 @@ def mala_step(plan: FlowPlan, z_prop: torch.Tensor, grad_g: Optional[torch.Tenso
           _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(noise), _ptr(uniform), rng, float(step_size),
           MALA_INIT if init else 0, _ptr(z_next), _ptr(bufs["acc"]), _ptr(bufs["la"]))
     return z_next, bufs["acc"], bufs["la"], ll
+
+
+def reverse_mala_step(plan: FlowPlan, eps_prop: torch.Tensor, z_saved: Optional[torch.Tensor], act_saved: torch.Tensor,
+                      grad_g: Optional[torch.Tensor], energy_g: Optional[torch.Tensor], state: MalaState, noise, step_size: float, *,
+                      init: bool = False, uniform: Optional[torch.Tensor] = None, propose: bool = True, inplace: bool = False,
+                      reuse_buffers: bool = False):
+    """One Metropolis-adjusted Langevin call in the flow's base space (include/lsnf_flow_mcmc.h `lsnf_reverse_mala_step`) in ONE
+    launch: with x = reverse(eps_prop)[0], target pi(eps) ~ exp(-U), U = |eps|^2 / 2 + energy_g, grad U = eps + g,
+    g = J_{f^-1}(eps)^T grad_g (`reverse_backward_z(plan, eps_prop, z_saved, act_saved, grad_g)`'s bits).  The reverse-backward's output
+    section DECIDES eps_prop against `state` (z = eps, grad = eps + g, energy = U), updates the state in place and, with propose,
+    writes the next proposal eps_next = fma(s, xi, fma(-0.5 s^2, grad_state, eps_state)) (`reverse_langevin_step`'s arithmetic).
+    eps_prop / z_saved / act_saved: the reverse's input, the block outputs and the stash of the forward AT x -- kept by
+    `reverse(plan, eps_prop, save_for_backward=True, act_saved=...)`, or from `forward(plan, x, ...)`.  Unlike `mala_step` this
+    call runs no flow pass itself: the caller's generator sits between the reverse and it, as with `reverse_langevin_step`.
+    grad_g (B, nz) / energy_g (B): the caller's gradient and per-row energy at x (None = 0: the chain samples N(0, I)).
+    init=True starts a chain at eps_prop: every row accepted, the state written without being read.  `noise`: a `PhiloxNoise`
+    (the uniform and xi are drawn inside the kernel: xi is `reverse_langevin_step`'s draw at the same offset, the uniform
+    `mala_step`'s), or a (B, nz) tensor of N(0,1) draws together with uniform= (B) draws in (0, 1) -- the tensor is left out (None)
+    with propose=False, the uniform may be with init=True.  K proposals are K + 1 calls: init, K - 1 deciding and proposing calls,
+    one with propose=False.
+    Returns (eps_next or None, accepted (B) of 1.0 / 0.0, log_alpha (B)).  inplace: eps_next is eps_prop itself.  reuse_buffers:
+    the last two live on the plan and are overwritten by the next call.  Asynchronous on the current stream; nothing but the
+    launch, so it can be captured in a graph."""
+    B, dev = _anchor(eps_prop, "eps_prop", plan), eps_prop.device
+    _check_stash(plan, B, dev, z_saved, act_saved, True)
+    _check_like(grad_g, "grad_g", eps_prop, "eps_prop")
+    _check_in(energy_g, "energy_g", B, dev)
+    if not isinstance(state, MalaState):
+        raise LsnfError("state must be a flow.MalaState (new_mala_state())")
+    _check_out(state.z, "state.z", B * plan.nz, dev)
+    _check_out(state.grad, "state.grad", B * plan.nz, dev)
+    _check_out(state.energy, "state.energy", B, dev)
+    noise, rng = _noise_args(noise, eps_prop, "eps_prop", dev)
+    _check_in(uniform, "uniform", B, dev)
+    if rng is not None and uniform is not None:
+        raise LsnfError("pass either a PhiloxNoise or the tensors (noise, uniform=), not both")
+
+    def make():
+        f32 = dict(dtype=torch.float32, device=dev)
+        return {"acc": torch.empty(B, **f32), "la": torch.empty(B, **f32)}
+    bufs = _stream_buffers(plan, "_rmala_buffers", B, dev, make) if reuse_buffers else make()
+    eps_next = None if not propose else eps_prop if inplace else torch.empty_like(eps_prop)
+    _call("lsnf_reverse_mala_step", dev, *_plan_head(plan), B, _ptr(eps_prop), _ptr(z_saved), _ptr(act_saved), _ptr(grad_g),
+          _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(noise), _ptr(uniform), rng, float(step_size),
+          MALA_INIT if init else 0, _ptr(eps_next), _ptr(bufs["acc"]), _ptr(bufs["la"]))
+    return eps_next, bufs["acc"], bufs["la"]

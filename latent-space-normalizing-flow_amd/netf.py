@@ -469,6 +469,16 @@ class _netF(nn.Module):
         return flow.mala_step(self._plan(), det(z_prop), det(grad_g), det(energy_g), state, det(noise), step_size, init=init,
                               uniform=det(uniform), propose=propose, inplace=inplace, reuse_buffers=reuse_buffers)
 
+    def reverse_mala_step(self, eps_prop, z_saved, act_saved, grad_g=None, energy_g=None, state=None, noise=None, step_size=0.1, *,
+                          init=False, uniform=None, propose=True, inplace=False, reuse_buffers=False):
+        """One Metropolis-adjusted Langevin call in the base space at the proposal eps_prop against the kept chain `state`
+        (`flow.reverse_mala_step`: ONE launch on the stash of the reverse at eps_prop; the caller's generator ran in between).
+        Returns (eps_next or None, accepted, log_alpha)."""
+        det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t
+        return flow.reverse_mala_step(self._plan(), det(eps_prop), det(z_saved), det(act_saved), det(grad_g), det(energy_g), state,
+                                      det(noise), step_size, init=init, uniform=det(uniform), propose=propose, inplace=inplace,
+                                      reuse_buffers=reuse_buffers)
+
     def mle_grads(self, z, accumulate: bool = False, max_norm: Optional[float] = None, reuse_buffers: bool = False):
         """Fused flow-MLE gradients (train.py:404-411): loss_f = -mean_b ll(z_b) and d loss_f / d theta written to
         `.grad` of the 60 live tensors -- forward (ll summed in-kernel), dump backward, batch contraction, unfold:
