@@ -36,7 +36,8 @@ def _short(mangled):
         return mangled
     name = m.group(2)[: int(m.group(1))]
     rest = mangled[m.start(2) + int(m.group(1)):]
-    targs = rest.split("EEv", 1)[0] if rest.startswith("I") else ""
+    # (`...ILi32EEv...` of a kernel outside a namespace: the split takes the last argument's own `E` with it, so it is put back)
+    targs = rest.split("EEv", 1)[0] + "E" if rest.startswith("I") else ""
     vals = [v if k == "i" else ("true" if v == "1" else "false") for k, v in re.findall(r"L([ib])(\d+)E", targs)]
     return f"{name}<{', '.join(vals)}>" if vals else name
 
