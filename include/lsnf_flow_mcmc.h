@@ -72,7 +72,49 @@
  *   alignment as lsnf_reverse_backward_z: plan and act_saved 16 bytes, every other tensor 4
  * One kernel (lsnf_small3_rmala_kernel) under every lsnf_set_math_mode and for every B (more rounds of workgroups above 16 384 rows),
  * independent of lsnf_set_small_batch_max; a row's decision and bits do not depend on B, the workgroup shape or rng->row0 sharding.
- * B = 0 succeeds without a launch.  Every refusal is LSNF_E_ARG / LSNF_E_GEOMETRY, made before any HIP call. */
+ * B = 0 succeeds without a launch.  Every refusal is LSNF_E_ARG / LSNF_E_GEOMETRY, made before any HIP call.
+ *
+ * ---- Hamiltonian Monte Carlo in z: L leapfrog steps per accept / reject (lsnf_hmc_step) ------------------------------------------
+ * The target of lsnf_mala_step, p(z) ~ exp(-U(z)), U = energy_g - ll, with a momentum p ~ N(0, I), step s and L >= 1 leapfrog steps
+ * per trajectory.  As there, grad U at a point is known only after a forward and a backward AT that point, so one call finishes the
+ * work at the point z_prop it is given (lsnf_forward's outputs at z_prop, the caller's grad_g / energy_g at z_prop) and produces the
+ * next point.  From a state (z_s, g_s = grad U(z_s), u_s = U(z_s)), every line in fp32 with the operations and the order written,
+ * no fused multiply-add (hs = 0.5f * s: exact):
+ *   begin  (inside the call that owns the state: LSNF_HMC_INIT, or an end call with z_next)
+ *           kin0 = 0.5f * sum_c xi^2;   ph = xi - hs * g_s;   z_next = z_s + s * ph;   mom <- ph
+ *   inner  (LSNF_HMC_INNER, the calls at z_1 .. z_{L-1})
+ *           g = grad_g + d(-ll)/dz(z_prop);   ph = mom - s * g;   z_next = z_prop + s * ph;   mom <- ph
+ *   end    (flags 0, the call at z_L)
+ *           g_prop = grad_g + d(-ll)/dz(z_prop);   U_prop = energy_g - ll_prop;   pL = mom - hs * g_prop;   kinL = 0.5f * sum_c pL^2
+ *           log_alpha = (u_acc - U_prop) + (kin0 - kinL)
+ *           accept iff ln(u) < log_alpha        (a NaN log_alpha rejects, +inf accepts)
+ *           accepted rows: z_acc <- z_prop, grad_acc <- g_prop, u_acc <- U_prop;  rejected rows keep their state bits
+ *           z_next given: begin the next trajectory from the (updated) state;  z_next NULL: mom <- pL (the full-step momentum at
+ *           the proposal is left readable), nothing else is proposed and kin0 is left as it is
+ * The sums over a row's columns: a lane adds the squares of its 8 columns in column order, lsnf_mala_step's reduction adds the
+ * lanes of a wave and the four waves' partials are added in wave order.
+ * K trajectories of L steps are K L + 1 calls: one LSNF_HMC_INIT call at the chain's start (every row accepted, the state written
+ * without being read, log_alpha_out = +0, the first trajectory begun; without z_next it writes the state alone and leaves mom and
+ * kin0 as they are), L - 1 LSNF_HMC_INNER calls per trajectory, K end calls, the last one with z_next NULL.  With L = 1 there are no
+ * inner calls and the chain is lsnf_mala_step's in exact arithmetic (kinL = A / (2 s^2), kin0 = Bq / (2 s^2) in its notation).
+ *
+ *   the arguments shared with lsnf_mala_step follow its rules (z_prop .. energy_g, z_acc / grad_acc / u_acc, step_size, accept_out,
+ *   log_alpha_out, the 16-byte alignment of plan and act_saved and the 4-byte alignment of every tensor), except as stated below
+ *   mom (B,nz): the momentum, read AND written by the same call (written only by INIT when z_next is NULL);  kin0 (B): the kinetic
+ *       energy the running trajectory began with, written by a call that begins one, read by an end call.  Both are required
+ *   xi: a row of `noise` (B,nz), or lsnf_langevin_step's LsnfRng draw at the call's (seed, offset, row, column)
+ *   u:  lsnf_mala_step's: `uniform` (B), or with rng word 0 of Philox at field value 2 of the noise's counter
+ *   flags: 0, LSNF_HMC_INIT or LSNF_HMC_INNER; both together and unknown bits are refused
+ *   an LSNF_HMC_INNER call draws and decides nothing: it requires z_next, refuses noise, uniform and rng, wants accept_out and
+ *       log_alpha_out NULL, neither reads nor writes z_acc, grad_acc, u_acc or kin0 (they are still required), and the library never
+ *       reads ll_prop or energy_g (ll_prop may be NULL there)
+ *   INIT and end calls: rng and a tensor (noise or uniform) exclude each other; without rng, `noise` is required iff z_next is
+ *       given and `uniform` is required unless LSNF_HMC_INIT
+ *   z_next (B,nz) or NULL; may be z_prop (a lane stores the columns it loaded, after the barrier).  No other output (z_acc,
+ *   grad_acc, u_acc, mom, kin0, z_next, accept_out, log_alpha_out) may alias anything the call reads, or another output
+ * One kernel (lsnf_small3_hmc_kernel) under every lsnf_set_math_mode, for every B and every phase, independent of
+ * lsnf_set_small_batch_max; a row's bits do not depend on B, the workgroup shape or rng->row0 sharding.  B = 0 succeeds without a
+ * launch.  Every refusal is LSNF_E_ARG / LSNF_E_GEOMETRY, made before any HIP call. */
 #ifndef LSNF_FLOW_MCMC_H
 #define LSNF_FLOW_MCMC_H
 
@@ -95,6 +137,14 @@ int lsnf_reverse_mala_step(const float* plan, int nz, int width, int depth, int 
                            float* eps_acc, float* grad_acc, float* u_acc,
                            const float* noise, const float* uniform, const LsnfRng* rng, float step_size, unsigned flags,
                            float* eps_next, float* accept_out, float* log_alpha_out, void* stream);
+#define LSNF_HMC_INIT  1u
+#define LSNF_HMC_INNER 2u
+int lsnf_hmc_step(const float* plan, int nz, int width, int depth, int coupling, int B,
+                  const float* z_prop, const float* z_out, const float* z_saved, const float* act_saved,
+                  const float* ll_prop, const float* grad_g, const float* energy_g,
+                  float* z_acc, float* grad_acc, float* u_acc, float* mom, float* kin0,
+                  const float* noise, const float* uniform, const LsnfRng* rng, float step_size, unsigned flags,
+                  float* z_next, float* accept_out, float* log_alpha_out, void* stream);
 
 #ifdef __cplusplus
 }

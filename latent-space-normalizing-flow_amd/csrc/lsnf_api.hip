@@ -181,7 +181,7 @@ enum Kernel {
     K_NONE, K_FWD, K_FWD3, K_FWD3Q, K_FWD2H_FIXUP, K_SMALL_FWD, K_SMALL3_FWD,
     K_REV, K_REV3, K_REV2H_FIXUP, K_SMALL_REV, K_SMALL3_REV,
     K_BWD, K_BWD3, K_SMALL_BWD, K_SMALL3_BWD,
-    K_SMALL3_RBWD, K_SMALL3_RLV, K_SMALL3_MALA, K_SMALL3_RMALA,
+    K_SMALL3_RBWD, K_SMALL3_RLV, K_SMALL3_MALA, K_SMALL3_RMALA, K_SMALL3_HMC,
 };
 const char* const kKernelName[] = {
     "no kernel takes this call", "lsnf_fwd_kernel", "lsnf_fwd3b_kernel", "lsnf_fwd3q_kernel",
@@ -190,6 +190,7 @@ const char* const kKernelName[] = {
     "lsnf_small3_rev_kernel",
     "lsnf_bwd_z_kernel", "lsnf_bwd3_kernel", "lsnf_small_bwd_kernel", "lsnf_small3_bwd_kernel",
     "lsnf_small3_rbwd_kernel", "lsnf_small3_rbwd_kernel (update form)", "lsnf_small3_mala_kernel", "lsnf_small3_rmala_kernel",
+    "lsnf_small3_hmc_kernel",
 };
 struct Pick { Kernel k; int st = 0; };     // st: rows per workgroup / 16 of the small3 kernels
 
@@ -387,6 +388,9 @@ Pick select_mala(const LsnfMalaCall& c) { return {K_SMALL3_MALA, lsnf_small3_bac
 // Its base-space form (lsnf_reverse_mala_step) is the reverse-backward with that tail (lsnf_small3_rmala.hip): one kernel again, the
 // workgroup shape of the plain reverse-backward of the call.
 Pick select_reverse_mala(const LsnfReverseMalaCall& c) { return {K_SMALL3_RMALA, lsnf_small3_reverse_backward_st(c)}; }
+// Hamiltonian Monte Carlo in z (lsnf_hmc_step) is the same backward with the leapfrog tail (lsnf_small3_hmc.hip): one kernel under
+// every math mode, batch size and phase of a trajectory, the workgroup shape of the plain backward of the call.
+Pick select_hmc(const LsnfHmcCall& c) { return {K_SMALL3_HMC, lsnf_small3_backward_st(c)}; }
 
 // Batch contraction of the parameter gradients (LsnfContraction): on the bf16 matrix pipe where lsnf_params3.hip covers the
 // call (use_x3); from 4 096 rows the fp32-MFMA kernel through LDS, with the widest row loads the rows allow -- every row the
@@ -887,6 +891,70 @@ int lsnf_reverse_mala_step(const float* plan, int nz, int width, int depth, int 
     c.accept_out = accept_out; c.log_alpha_out = log_alpha_out; c.flags = flags;
     const Pick p = select_reverse_mala(c);
     return report(ck.entry, p, lsnf_launch_small3_reverse_mala(c, p.st));
+}
+
+int lsnf_hmc_step(const float* plan, int nz, int width, int depth, int coupling, int B, const float* z_prop, const float* z_out,
+                  const float* z_saved, const float* act_saved, const float* ll_prop, const float* grad_g, const float* energy_g,
+                  float* z_acc, float* grad_acc, float* u_acc, float* mom, float* kin0, const float* noise, const float* uniform,
+                  const LsnfRng* rng, float step_size, unsigned flags, float* z_next, float* accept_out, float* log_alpha_out, void* stream) {
+    Check ck{"lsnf_hmc_step"};
+    struct Named { const char* name; const void* p; };
+    const Named reads[] = {{"plan", plan}, {"z_prop", z_prop}, {"z_out", z_out}, {"z_saved", z_saved}, {"act_saved", act_saved},
+                           {"ll_prop", ll_prop}, {"grad_g", grad_g}, {"energy_g", energy_g}, {"noise", noise}, {"uniform", uniform}};
+    // (mom is read and written by the same call: it is listed with the outputs, so it may be neither another input nor another output)
+    const Named writes[] = {{"z_acc", z_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc}, {"z_next", z_next}, {"accept_out", accept_out},
+                            {"log_alpha_out", log_alpha_out}, {"mom", mom}, {"kin0", kin0}};
+    // z_next may be z_prop (a lane stores the columns it loaded, after the barrier); no other output may be a tensor the call reads,
+    // or another output
+    auto aliases = [&] {
+        for (const Named& w : writes) {
+            if (!w.p) continue;
+            for (const Named& r : reads)
+                if (w.p == r.p && !(&w == &writes[3] && &r == &reads[1])) return ck.refuse(true, "%s must not alias %s", w.name, r.name);
+            for (const Named& o : writes)
+                if (&o != &w && w.p == o.p) return ck.refuse(true, "%s must not alias %s", w.name, o.name);
+        }
+        return false;
+    };
+    const unsigned known = LSNF_HMC_INIT | LSNF_HMC_INNER;
+    const bool init = (flags & LSNF_HMC_INIT) != 0, inner = (flags & LSNF_HMC_INNER) != 0;
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B) ||
+        ck.refuse(uniform && rng, "pass either a uniform tensor or an rng, not both") || ck.rng(noise, rng, /*row0_first=*/false) ||
+        ck.refuse(!std::isfinite(step_size) || step_size == 0.0f, "step_size must be finite and non-zero (got %g)", (double)step_size) ||
+        ck.refuse(flags & ~known, "unknown flag bits 0x%x", flags & ~known) ||
+        ck.refuse(init && inner, "flags: LSNF_HMC_INIT and LSNF_HMC_INNER exclude each other") ||
+        // an inner leapfrog step draws nothing and decides nothing
+        ck.refuse(inner && noise, "noise is not taken with LSNF_HMC_INNER (an inner step draws nothing)") ||
+        ck.refuse(inner && uniform, "uniform is not taken with LSNF_HMC_INNER (an inner step draws nothing)") ||
+        ck.refuse(inner && rng, "rng is not taken with LSNF_HMC_INNER (an inner step draws nothing)") ||
+        ck.refuse(inner && accept_out, "accept_out must be NULL with LSNF_HMC_INNER (an inner step decides nothing)") ||
+        ck.refuse(inner && log_alpha_out, "log_alpha_out must be NULL with LSNF_HMC_INNER (an inner step decides nothing)") || aliases())
+        return ck.rc;
+    if (ck.empty) return LSNF_OK;
+    const Named needed[] = {{"plan", plan}, {"z_prop", z_prop}, {"z_out", z_out}, {"act_saved", act_saved}, {"z_acc", z_acc},
+                            {"grad_acc", grad_acc}, {"u_acc", u_acc}, {"mom", mom}, {"kin0", kin0}};
+    for (const Named& r : needed)
+        if (ck.refuse(!r.p, "%s is required (NULL)", r.name)) return ck.rc;
+    if (ck.refuse(!inner && !ll_prop, "ll_prop is required (NULL) unless LSNF_HMC_INNER") ||
+        ck.refuse(depth > 1 && !z_saved, "z_saved is required (NULL) for depth > 1") ||
+        ck.refuse(inner && !z_next, "z_next is required (NULL) with LSNF_HMC_INNER") ||
+        ck.refuse(!inner && !rng && !init && !uniform, "uniform is required without an rng (unless LSNF_HMC_INIT or LSNF_HMC_INNER)") ||
+        ck.refuse(!inner && !rng && z_next && !noise, "noise is required with z_next when no rng is given") ||
+        ck.refuse(!inner && !rng && !z_next && noise, "noise goes with z_next: nothing is proposed without it") ||
+        ck.aligned16("plan", {plan}) || ck.aligned16("act_saved", {act_saved}))
+        return ck.rc;
+    for (const Named& r : reads)
+        if (ck.aligned4(r.name, {r.p})) return ck.rc;
+    for (const Named& w : writes)
+        if (ck.aligned4(w.name, {w.p})) return ck.rc;
+    const LsnfLangevinArgs lv = {z_prop, grad_g, noise, z_next, nullptr, nullptr, step_size, rng_args(rng)};
+    LsnfHmcCall c;                       // (no g_z1 / g_logdet / g_z_in: the gradient of -log p at the point, consumed by the tail)
+    ck.head(c, plan, B, stream, {z_prop, z_out, z_saved, grad_g, noise, z_next, z_acc, grad_acc, mom});
+    c.z_out = z_out; c.z_saved = z_saved; c.act_saved = act_saved; c.ll_mode = 1; c.ll_scale = -1.0f; c.lv = &lv;
+    c.ll_prop = ll_prop; c.energy_g = energy_g; c.uniform = uniform; c.z_acc = z_acc; c.grad_acc = grad_acc; c.u_acc = u_acc;
+    c.accept_out = accept_out; c.log_alpha_out = log_alpha_out; c.flags = flags; c.mom = mom; c.kin0 = kin0;
+    const Pick p = select_hmc(c);
+    return report(ck.entry, p, lsnf_launch_small3_hmc(c, p.st));
 }
 
 size_t lsnf_backward_params_workspace_floats(int nz, int width, int depth, int B) {

@@ -52,6 +52,9 @@ struct LsnfMalaCall : LsnfBackwardCall {  // lsnf_mala_step: ll_mode 1 / ll_scal
     float* accept_out = nullptr; float* log_alpha_out = nullptr;
     unsigned flags = 0;                  // LSNF_MALA_*
 };
+struct LsnfHmcCall : LsnfMalaCall {      // lsnf_hmc_step: the MALA call's tensors at a point of a trajectory; flags: LSNF_HMC_*
+    float* mom = nullptr; float* kin0 = nullptr;      // the momentum (B, nz; read and written), the kinetic energy the trajectory began with (B)
+};
 struct LsnfReverseBackwardCall : LsnfCall {      // lsnf_reverse_backward_z
     const float* z_out = nullptr; const float* z_saved = nullptr; const float* act_saved = nullptr;
     const float* g_x = nullptr; const float* g_objective = nullptr;
@@ -139,6 +142,7 @@ hipError_t lsnf_launch_small_backward_z(const LsnfBackwardCall& c);
 int lsnf_small3_backward_st(const LsnfBackwardCall& c);
 hipError_t lsnf_launch_small3_backward_z(const LsnfBackwardCall& c, int st);
 hipError_t lsnf_launch_small3_mala(const LsnfMalaCall& c, int st);          // st: lsnf_small3_backward_st of the call
+hipError_t lsnf_launch_small3_hmc(const LsnfHmcCall& c, int st);            // st: lsnf_small3_backward_st of the call
 int lsnf_small3_reverse_backward_st(const LsnfReverseBackwardCall& c);
 hipError_t lsnf_launch_small3_reverse_backward_z(const LsnfReverseBackwardCall& c, int st);
 hipError_t lsnf_launch_small3_reverse_langevin(const LsnfReverseLangevinCall& c, int st);      // st: of the same predicate

@@ -1,10 +1,11 @@
 // lsnf_small3_bwd_kernel.h -- the kernel text of the latency backward from the stash (lsnf_small3_bwd.hip: the stages, the LDS map, the
-// plain output section), included by the two translation units that instantiate it.  The includer defines, before the #include:
+// plain output section), included by the translation units that instantiate it.  The includer defines, before the #include:
 //   LSNF_S3B_KERNEL  the kernel template's name          lsnf_small3_bwd_kernel            | lsnf_small3_mala_kernel
 //   LSNF_S3B_ARGS    its argument struct                  Small3BwdArgs                     | Small3MalaArgs
 //   LSNF_S3B_TAIL    statements in front of the output    (nothing)                         | the accept / reject tail and `return;`
 //                    section, with the kernel's locals in scope
-// lsnf_small3_bwd.hip gives the first column and is compiled from the same tokens as before this file existed; lsnf_small3_mala.hip the second.
+// lsnf_small3_bwd.hip gives the first column and is compiled from the same tokens as before this file existed; lsnf_small3_mala.hip the second;
+// lsnf_small3_hmc.hip a third (lsnf_small3_hmc_kernel, Small3HmcArgs, the leapfrog tail and `return;`).
 #pragma once
 
 namespace {
@@ -50,6 +51,11 @@ struct Small3MalaArgs : Small3BwdArgs {
     const float* ll_prop; const float* energy_g; const float* uniform;
     float* z_acc; float* grad_acc; float* u_acc; float* accept_out; float* log_alpha_out;
     unsigned flags;                                // LSNF_MALA_INIT (1): accept every row, the state is not read
+};
+// HMC form (lsnf_small3_hmc.hip): the MALA form's arrays plus the momentum (B, nz; read and written) and the kinetic energy a
+// trajectory started with (B); flags: LSNF_HMC_INIT (1) as above, LSNF_HMC_INNER (2): a leapfrog step inside a trajectory
+struct Small3HmcArgs : Small3MalaArgs {
+    float* mom; float* kin0;
 };
 
 __device__ __forceinline__ f32x4 mask4(f32x4 a, unsigned nib) {

@@ -3,6 +3,7 @@ restated (they are closures inside train.py and cannot be imported) on top of th
 
   sample_langevin_post_z_with_flow  <- train.py:307-335 (training) / :602-634 (testing: 20x steps, no noise)
   sample_mala_post_z_with_flow         the same chain Metropolis-adjusted (exact at any step size; per-row acceptance rate)
+  sample_hmc_post_z_with_flow          Hamiltonian Monte Carlo on the same target: L leapfrog steps per accept / reject
   sample_langevin_post_eps_with_flow   the same sampler in the flow's base space (eps, with z = f^-1(eps)); not in the reference
   sample_mala_post_eps_with_flow       the base-space chain Metropolis-adjusted (per-row acceptance rate)
   flow_mle_step                     <- train.py:404-415
@@ -77,6 +78,43 @@ def sample_mala_post_z_with_flow(z, x, netG: nn.Module, netF, *, g_l_steps: int,
         _, acc, _, _ = netF.mala_step(z_prop, grad_g, energy.detach(), state, philox.step(j), g_l_step_size, init=j == 0,
                                       propose=j < K, inplace=True, reuse_buffers=True)
         if j:
+            accepted += acc
+    philox.advance(K + 1)
+    return state.z.view(B, nz, 1, 1), accepted / K, state.energy
+
+
+def sample_hmc_post_z_with_flow(z, x, netG: nn.Module, netF, *, g_l_steps: int, leapfrog_steps: int, g_l_step_size: float,
+                                g_llhd_sigma: float, philox):
+    """Hamiltonian Monte Carlo on the target of `sample_mala_post_z_with_flow`: K = g_l_steps trajectories of L = leapfrog_steps
+    leapfrog steps of size g_l_step_size, one accept / reject per trajectory -- L times the distance of a MALA proposal for one
+    decision (L = 1 is that chain in exact arithmetic).  U = |x - G(z)|^2 / (2 sigma^2) - ll(z) per row; the generator's energy and
+    gradient come from torch autograd at every one of the K L + 1 points, exactly as there, the flow's part, the leapfrog
+    arithmetic, the decision and the next trajectory's start from `netF.hmc_step`: one "init" call, then per trajectory L - 1
+    "inner" calls and one "end" call, the last of which proposes nothing.  `philox` (a `flow.PhiloxNoise`, required) gives the call
+    that starts trajectory t + 1 -- the init call is t = 0, end call t is 1 .. K -- its uniform and its momentum draw at offset + t;
+    inner calls take no generator; it is ADVANCED by K + 1 on return.
+    Returns (z_k (B, nz, 1, 1), accept_rate (B) = accepted trajectories / K, U(z_k) (B)); g_l_steps = 0 or an empty batch returns
+    the input (and None, None); leapfrog_steps < 1 raises ValueError."""
+    from . import flow
+    K, L = int(g_l_steps), int(leapfrog_steps)
+    if L < 1:
+        raise ValueError(f"leapfrog_steps must be >= 1 (got {leapfrog_steps})")
+    B, nz = z.shape[0], z.shape[1]
+    if K < 1 or B == 0:
+        return z.detach().clone().view(B, nz, 1, 1), None, None
+    c = 1.0 / (2.0 * g_llhd_sigma * g_llhd_sigma)
+    z_prop = z.detach().reshape(B, nz).contiguous().clone()
+    state = flow.new_hmc_state(netF._plan(), B, z_prop.device)
+    accepted = torch.zeros(B, dtype=torch.float32, device=z_prop.device)
+    for j in range(K * L + 1):
+        zr = z_prop.view(B, nz, 1, 1).detach().requires_grad_(True)
+        energy = c * ((netG(zr) - x) ** 2).flatten(1).sum(1)                                 # train.py:312-313, per row
+        grad_g = torch.autograd.grad(energy.sum(), zr)[0].reshape(B, nz).contiguous()        # train.py:314
+        t, inner = j // L, j % L != 0
+        _, acc, _, _ = netF.hmc_step(z_prop, grad_g, energy.detach(), state, None if inner else philox.step(t), g_l_step_size,
+                                     phase="inner" if inner else "end" if j else "init", propose=j < K * L, inplace=True,
+                                     reuse_buffers=True)
+        if j and not inner:
             accepted += acc
     philox.advance(K + 1)
     return state.z.view(B, nz, 1, 1), accepted / K, state.energy

@@ -1,5 +1,6 @@
 """Markov-chain extensions of the functional host API (C: include/lsnf_flow_mcmc.h), re-exported by flow.py -- use them as
-`flow.mala_step`, `flow.reverse_mala_step`, `flow.MalaState`, `flow.new_mala_state`.  Every tensor goes through flow.py's one checking path before anything is
+`flow.mala_step`, `flow.reverse_mala_step`, `flow.MalaState`, `flow.new_mala_state`, `flow.hmc_step`, `flow.HmcState`,
+`flow.new_hmc_state`.  Every tensor goes through flow.py's one checking path before anything is
 launched; like there, all functions raise on CPU tensors: there is no CPU path."""
 from __future__ import annotations
 
@@ -120,3 +121,82 @@ def reverse_mala_step(plan: FlowPlan, eps_prop: torch.Tensor, z_saved: Optional[
           _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(noise), _ptr(uniform), rng, float(step_size),
           MALA_INIT if init else 0, _ptr(eps_next), _ptr(bufs["acc"]), _ptr(bufs["la"]))
     return eps_next, bufs["acc"], bufs["la"]
+
+
+HMC_INIT, HMC_INNER = 1, 2    # include/lsnf_flow_mcmc.h LSNF_HMC_INIT, LSNF_HMC_INNER
+_HMC_PHASES = {"init": HMC_INIT, "inner": HMC_INNER, "end": 0}
+
+
+@dataclass
+class HmcState:
+    """The kept state of a Hamiltonian Monte Carlo chain (`hmc_step`): `MalaState`'s z (B, nz), grad (B, nz) = grad U(z) and
+    energy (B) = U(z), plus mom (B, nz), the momentum of the running trajectory (read and written by every call), and kin (B),
+    the kinetic energy 0.5 |xi|^2 that trajectory began with."""
+    z: torch.Tensor
+    grad: torch.Tensor
+    energy: torch.Tensor
+    mom: torch.Tensor
+    kin: torch.Tensor
+
+
+def new_hmc_state(plan: FlowPlan, B: int, device) -> HmcState:
+    """A zeroed chain state of B rows for `hmc_step` (the phase="init" call fills it)."""
+    f32 = dict(dtype=torch.float32, device=device)
+    rows, one = (lambda: torch.zeros((int(B), plan.nz), **f32)), (lambda: torch.zeros(int(B), **f32))
+    return HmcState(rows(), rows(), one(), rows(), one())
+
+
+def hmc_step(plan: FlowPlan, z_prop: torch.Tensor, grad_g: Optional[torch.Tensor], energy_g: Optional[torch.Tensor],
+             state: HmcState, noise, step_size: float, *, phase: str = "end", uniform: Optional[torch.Tensor] = None,
+             propose: bool = True, inplace: bool = False, reuse_buffers: bool = False):
+    """One call of Hamiltonian Monte Carlo in z (include/lsnf_flow_mcmc.h `lsnf_hmc_step`) in two launches: the forward at the
+    point `z_prop` of a trajectory (ll, block outputs, stash) and the backward whose output section is the leapfrog tail -- target
+    p(z) ~ exp(-U), U = energy_g - ll, momentum ~ N(0, I), step s.  grad_g (B, nz) / energy_g (B): the caller's gradient and per-row
+    energy at z_prop (None = 0).  phase:
+      "init"   starts a chain at z_prop (every row accepted, the state written without being read) and begins the first trajectory:
+               mom = xi - s/2 grad, z_next = z + s mom, kin = |xi|^2 / 2;
+      "inner"  a leapfrog step inside a trajectory: mom -= s grad U(z_prop), z_next = z_prop + s mom.  It draws and decides nothing:
+               noise and uniform must be None, propose True; state.z / grad / energy / kin are not touched;
+      "end"    finishes the trajectory at z_prop (mom -= s/2 grad U), decides it against `state` with
+               log_alpha = (U_state - U_prop) + (kin - |mom|^2 / 2), updates the state in place and, with propose, begins the next
+               trajectory from it; with propose=False the full-step momentum at z_prop is left in state.mom.
+    `noise`: a `PhiloxNoise` (the uniform and xi are drawn inside the kernel, as `mala_step`'s), or a (B, nz) tensor of N(0,1) draws
+    together with uniform= (B) draws in (0, 1) -- the tensor is left out (None) with propose=False, the uniform may be with "init".
+    K trajectories of L leapfrog steps are K L + 1 calls: "init", then K times (L - 1 "inner", one "end"), the last with
+    propose=False.  Returns (z_next or None, accepted (B) of 1.0 / 0.0, log_alpha (B), ll_prop (B)); accepted and log_alpha are None
+    for an inner call.  inplace: z_next is z_prop itself.  reuse_buffers: as `mala_step`'s."""
+    if phase not in _HMC_PHASES:
+        raise LsnfError(f"phase must be one of 'init', 'inner', 'end' (got {phase!r})")
+    inner = phase == "inner"
+    B, dev = _anchor(z_prop, "z_prop", plan), z_prop.device
+    _check_like(grad_g, "grad_g", z_prop, "z_prop")
+    _check_in(energy_g, "energy_g", B, dev)
+    if not isinstance(state, HmcState):
+        raise LsnfError("state must be a flow.HmcState (new_hmc_state())")
+    _check_out(state.z, "state.z", B * plan.nz, dev)
+    _check_out(state.grad, "state.grad", B * plan.nz, dev)
+    _check_out(state.energy, "state.energy", B, dev)
+    _check_out(state.mom, "state.mom", B * plan.nz, dev)
+    _check_out(state.kin, "state.kin", B, dev)
+    noise, rng = _noise_args(noise, z_prop, "z_prop", dev)
+    _check_in(uniform, "uniform", B, dev)
+    if rng is not None and uniform is not None:
+        raise LsnfError("pass either a PhiloxNoise or the tensors (noise, uniform=), not both")
+    if inner and (noise is not None or rng is not None or uniform is not None or not propose):
+        raise LsnfError("an inner leapfrog step draws and decides nothing: noise and uniform must be None, propose True")
+
+    def make():
+        f32 = dict(dtype=torch.float32, device=dev)
+        return {"act": new_act_saved(plan, B, dev), "out": (torch.empty_like(z_prop), torch.empty(B, **f32), torch.empty(B, **f32)),
+                "saved": torch.empty((plan.depth - 1, B, plan.nz), **f32) if plan.depth > 1 else None,
+                "acc": torch.empty(B, **f32), "la": torch.empty(B, **f32)}
+    bufs = _stream_buffers(plan, "_hmc_buffers", B, dev, make) if reuse_buffers else make()
+    act, saved = bufs["act"], bufs["saved"]
+    _check_stash(plan, B, dev, saved, act, True)
+    z1, _, ll, _ = forward(plan, z_prop, None, want_ll=True, out=bufs["out"], act_saved=act, z_saved_out=saved)
+    z_next = None if not propose else z_prop if inplace else torch.empty_like(z_prop)
+    acc, la = (None, None) if inner else (bufs["acc"], bufs["la"])
+    _call("lsnf_hmc_step", dev, *_plan_head(plan), B, _ptr(z_prop), _ptr(z1), _ptr(saved), _ptr(act), _ptr(ll), _ptr(grad_g),
+          _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(state.mom), _ptr(state.kin), _ptr(noise),
+          _ptr(uniform), rng, float(step_size), _HMC_PHASES[phase], _ptr(z_next), _ptr(acc), _ptr(la))
+    return z_next, acc, la, ll

@@ -469,6 +469,15 @@ class _netF(nn.Module):
         return flow.mala_step(self._plan(), det(z_prop), det(grad_g), det(energy_g), state, det(noise), step_size, init=init,
                               uniform=det(uniform), propose=propose, inplace=inplace, reuse_buffers=reuse_buffers)
 
+    def hmc_step(self, z_prop, grad_g=None, energy_g=None, state=None, noise=None, step_size=0.1, *, phase="end", uniform=None,
+                 propose=True, inplace=False, reuse_buffers=False):
+        """One Hamiltonian Monte Carlo call at the point z_prop of a trajectory against the kept chain `state` (`flow.hmc_step`:
+        the forward at z_prop, then the backward with the leapfrog tail; phase "init", "inner" or "end").
+        Returns (z_next or None, accepted, log_alpha, ll_prop); accepted and log_alpha are None for an inner call."""
+        det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t
+        return flow.hmc_step(self._plan(), det(z_prop), det(grad_g), det(energy_g), state, det(noise), step_size, phase=phase,
+                             uniform=det(uniform), propose=propose, inplace=inplace, reuse_buffers=reuse_buffers)
+
     def reverse_mala_step(self, eps_prop, z_saved, act_saved, grad_g=None, energy_g=None, state=None, noise=None, step_size=0.1, *,
                           init=False, uniform=None, propose=True, inplace=False, reuse_buffers=False):
         """One Metropolis-adjusted Langevin call in the base space at the proposal eps_prop against the kept chain `state`
