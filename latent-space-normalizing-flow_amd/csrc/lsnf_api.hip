@@ -173,6 +173,61 @@ LsnfRngArgs rng_args(const LsnfRng* r) {
     return r ? LsnfRngArgs{r->seed, r->offset, r->offset_dev, r->row0, 1} : LsnfRngArgs{0ull, 0ull, nullptr, 0ll, 0};
 }
 
+// ---- the rules of a Markov-chain step (lsnf_mala_step, lsnf_reverse_mala_step, lsnf_hmc_step), stated once: an entry point describes
+// its call -- its tensors under its own names -- and applies scalars(), its own rules, aliases(), the empty-batch return, pointers().
+struct Named { const char* name; const void* p; };
+struct Needed { const char* name; const void* p; bool when = true; const char* why = "(NULL)"; };      // "<name> is required <why>", when `when`
+template <class T>
+struct Table {                           // a view of a table of the entry point
+    const T* first; const T* last;
+    template <size_t N> Table(const T (&t)[N]) : first(t), last(t + N) {}
+    const T* begin() const { return first; }
+    const T* end() const { return last; }
+};
+struct ChainStep {
+    Table<Named> reads, writes;          // every tensor the call reads / writes (a tensor it does both to: with the writes)
+    const Named* next; const Named* point;       // the one pair that may alias: the next point (of writes) over the point (of reads)
+    Table<Needed> needed;                // the pointers a non-empty call must bring, in the order they are asked for
+    unsigned known;                      // the flags the entry point knows
+    bool init, inner;                    // init: no uniform is needed; inner: the call draws and decides nothing
+    const char* unless;                  // the flags under which no uniform is needed, by name
+    const void* plan; const void* act_saved; const void* noise; const void* uniform; const LsnfRng* rng;
+    float step_size; unsigned flags;
+
+    bool scalars(Check& ck) const {
+        return ck.refuse(uniform && rng, "pass either a uniform tensor or an rng, not both") || ck.rng(noise, rng, /*row0_first=*/false) ||
+               ck.refuse(!std::isfinite(step_size) || step_size == 0.0f, "step_size must be finite and non-zero (got %g)", (double)step_size) ||
+               ck.refuse(flags & ~known, "unknown flag bits 0x%x", flags & ~known);
+    }
+    // no output may be a tensor the call reads, or another output -- but the next point may be the point (every read of a workgroup's
+    // rows precedes its stores, and a lane stores the columns it loaded)
+    bool aliases(Check& ck) const {
+        for (const Named& w : writes) {
+            if (!w.p) continue;
+            for (const Named& r : reads)
+                if (w.p == r.p && !(&w == next && &r == point)) return ck.refuse(true, "%s must not alias %s", w.name, r.name);
+            for (const Named& o : writes)
+                if (&o != &w && w.p == o.p) return ck.refuse(true, "%s must not alias %s", w.name, o.name);
+        }
+        return false;
+    }
+    bool pointers(Check& ck) const {
+        for (const Needed& n : needed)
+            if (ck.refuse(n.when && !n.p, "%s is required %s", n.name, n.why)) return true;
+        const bool tensors = !inner && !rng;     // the call draws from tensors: the uniform, and the noise iff it proposes
+        if (ck.refuse(tensors && !init && !uniform, "uniform is required without an rng (unless %s)", unless) ||
+            ck.refuse(tensors && next->p && !noise, "noise is required with %s when no rng is given", next->name) ||
+            ck.refuse(tensors && !next->p && noise, "noise goes with %s: nothing is proposed without it", next->name) ||
+            ck.aligned16("plan", {plan}) || ck.aligned16("act_saved", {act_saved}))
+            return true;
+        for (const Named& r : reads)
+            if (ck.aligned4(r.name, {r.p})) return true;
+        for (const Named& w : writes)
+            if (ck.aligned4(w.name, {w.p})) return true;
+        return false;
+    }
+};
+
 // ---- kernel selection: each operation decides on the host, from the kernels' coverage predicates, which kernel(s) a call
 // runs, BEFORE anything is launched; the entry point then launches exactly that.  A launcher reached outside what it covers
 // is a selection bug and fails the call (LSNF_E_HIP, the kernel named in lsnf_last_error()); nothing falls through to another
@@ -791,51 +846,22 @@ int lsnf_mala_step(const float* plan, int nz, int width, int depth, int coupling
                    float* z_acc, float* grad_acc, float* u_acc, const float* noise, const float* uniform, const LsnfRng* rng,
                    float step_size, unsigned flags, float* z_next, float* accept_out, float* log_alpha_out, void* stream) {
     Check ck{"lsnf_mala_step"};
-    struct Named { const char* name; const void* p; };
     const Named reads[] = {{"plan", plan}, {"z_prop", z_prop}, {"z_out", z_out}, {"z_saved", z_saved}, {"act_saved", act_saved},
                            {"ll_prop", ll_prop}, {"grad_g", grad_g}, {"energy_g", energy_g}, {"noise", noise}, {"uniform", uniform}};
     const Named writes[] = {{"z_acc", z_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc}, {"z_next", z_next}, {"accept_out", accept_out},
                             {"log_alpha_out", log_alpha_out}};
-    // z_next may be z_prop (every read of a workgroup's rows precedes its stores); no other output may be a tensor the call reads,
-    // or another output
-    auto aliases = [&] {
-        for (const Named& w : writes) {
-            if (!w.p) continue;
-            for (const Named& r : reads)
-                if (w.p == r.p && !(w.p == z_next && r.p == z_prop && &w == &writes[3] && &r == &reads[1]))
-                    return ck.refuse(true, "%s must not alias %s", w.name, r.name);
-            for (const Named& o : writes)
-                if (&o != &w && w.p == o.p) return ck.refuse(true, "%s must not alias %s", w.name, o.name);
-        }
-        return false;
-    };
-    const bool init = (flags & LSNF_MALA_INIT) != 0;
-    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B) ||
-        ck.refuse(uniform && rng, "pass either a uniform tensor or an rng, not both") || ck.rng(noise, rng, /*row0_first=*/false) ||
-        ck.refuse(!std::isfinite(step_size) || step_size == 0.0f, "step_size must be finite and non-zero (got %g)", (double)step_size) ||
-        ck.refuse(flags & ~LSNF_MALA_INIT, "unknown flag bits 0x%x", flags & ~LSNF_MALA_INIT) || aliases())
-        return ck.rc;
+    const Needed needed[] = {{"plan", plan}, {"z_prop", z_prop}, {"z_out", z_out}, {"act_saved", act_saved}, {"ll_prop", ll_prop},
+                             {"z_acc", z_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc}, {"z_saved", z_saved, depth > 1, "(NULL) for depth > 1"}};
+    const ChainStep s = {reads, writes, /*next=*/&writes[3], /*point=*/&reads[1], needed, LSNF_MALA_INIT, (flags & LSNF_MALA_INIT) != 0,
+                         /*inner=*/false, "LSNF_MALA_INIT", plan, act_saved, noise, uniform, rng, step_size, flags};
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B) || s.scalars(ck) || s.aliases(ck)) return ck.rc;
     if (ck.empty) return LSNF_OK;
-    const Named needed[] = {{"plan", plan}, {"z_prop", z_prop}, {"z_out", z_out}, {"act_saved", act_saved}, {"ll_prop", ll_prop},
-                            {"z_acc", z_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc}};
-    for (const Named& r : needed)
-        if (ck.refuse(!r.p, "%s is required (NULL)", r.name)) return ck.rc;
-    if (ck.refuse(depth > 1 && !z_saved, "z_saved is required (NULL) for depth > 1") ||
-        ck.refuse(!rng && !init && !uniform, "uniform is required without an rng (unless LSNF_MALA_INIT)") ||
-        ck.refuse(!rng && z_next && !noise, "noise is required with z_next when no rng is given") ||
-        ck.refuse(!rng && !z_next && noise, "noise goes with z_next: nothing is proposed without it") ||
-        ck.aligned16("plan", {plan}) || ck.aligned16("act_saved", {act_saved}))
-        return ck.rc;
-    for (const Named& r : reads)
-        if (ck.aligned4(r.name, {r.p})) return ck.rc;
-    for (const Named& w : writes)
-        if (ck.aligned4(w.name, {w.p})) return ck.rc;
+    if (s.pointers(ck)) return ck.rc;
     const LsnfLangevinArgs lv = {z_prop, grad_g, noise, z_next, nullptr, nullptr, step_size, rng_args(rng)};
     LsnfMalaCall c;                      // (no g_z1 / g_logdet / g_z_in: the gradient of -log p at the proposal, consumed by the tail)
     ck.head(c, plan, B, stream, {z_prop, z_out, z_saved, grad_g, noise, z_next, z_acc, grad_acc});
-    c.z_out = z_out; c.z_saved = z_saved; c.act_saved = act_saved; c.ll_mode = 1; c.ll_scale = -1.0f; c.lv = &lv;
-    c.ll_prop = ll_prop; c.energy_g = energy_g; c.uniform = uniform; c.z_acc = z_acc; c.grad_acc = grad_acc; c.u_acc = u_acc;
-    c.accept_out = accept_out; c.log_alpha_out = log_alpha_out; c.flags = flags;
+    c.z_out = z_out; c.z_saved = z_saved; c.act_saved = act_saved; c.ll_mode = 1; c.ll_scale = -1.0f; c.lv = &lv; c.ll_prop = ll_prop;
+    c.chain = {energy_g, uniform, z_acc, grad_acc, u_acc, accept_out, log_alpha_out, flags};
     const Pick p = select_mala(c);
     return report(ck.entry, p, lsnf_launch_small3_mala(c, p.st));
 }
@@ -845,50 +871,23 @@ int lsnf_reverse_mala_step(const float* plan, int nz, int width, int depth, int 
                            float* grad_acc, float* u_acc, const float* noise, const float* uniform, const LsnfRng* rng, float step_size,
                            unsigned flags, float* eps_next, float* accept_out, float* log_alpha_out, void* stream) {
     Check ck{"lsnf_reverse_mala_step"};
-    struct Named { const char* name; const void* p; };
     const Named reads[] = {{"plan", plan}, {"eps_prop", eps_prop}, {"z_saved", z_saved}, {"act_saved", act_saved}, {"grad_g", grad_g},
                            {"energy_g", energy_g}, {"noise", noise}, {"uniform", uniform}};
     const Named writes[] = {{"eps_acc", eps_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc}, {"eps_next", eps_next}, {"accept_out", accept_out},
                             {"log_alpha_out", log_alpha_out}};
-    // eps_next may be eps_prop (every read of a workgroup's rows precedes its stores); no other output may be a tensor the call
-    // reads, or another output
-    auto aliases = [&] {
-        for (const Named& w : writes) {
-            if (!w.p) continue;
-            for (const Named& r : reads)
-                if (w.p == r.p && !(&w == &writes[3] && &r == &reads[1])) return ck.refuse(true, "%s must not alias %s", w.name, r.name);
-            for (const Named& o : writes)
-                if (&o != &w && w.p == o.p) return ck.refuse(true, "%s must not alias %s", w.name, o.name);
-        }
-        return false;
-    };
-    const bool init = (flags & LSNF_MALA_INIT) != 0;
-    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B) ||
-        ck.refuse(uniform && rng, "pass either a uniform tensor or an rng, not both") || ck.rng(noise, rng, /*row0_first=*/false) ||
-        ck.refuse(!std::isfinite(step_size) || step_size == 0.0f, "step_size must be finite and non-zero (got %g)", (double)step_size) ||
-        ck.refuse(flags & ~LSNF_MALA_INIT, "unknown flag bits 0x%x", flags & ~LSNF_MALA_INIT) || aliases())
-        return ck.rc;
+    const Needed needed[] = {{"plan", plan}, {"eps_prop", eps_prop}, {"eps_acc", eps_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc},
+                             {"act_saved", act_saved, true, "(the stash of lsnf_forward, lsnf_restash or lsnf_reverse_keep)"},
+                             {"z_saved", z_saved, depth > 1, "(NULL) for depth > 1"}};
+    const ChainStep s = {reads, writes, /*next=*/&writes[3], /*point=*/&reads[1], needed, LSNF_MALA_INIT, (flags & LSNF_MALA_INIT) != 0,
+                         /*inner=*/false, "LSNF_MALA_INIT", plan, act_saved, noise, uniform, rng, step_size, flags};
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B) || s.scalars(ck) || s.aliases(ck)) return ck.rc;
     if (ck.empty) return LSNF_OK;
-    const Named needed[] = {{"plan", plan}, {"eps_prop", eps_prop}, {"eps_acc", eps_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc}};
-    for (const Named& r : needed)
-        if (ck.refuse(!r.p, "%s is required (NULL)", r.name)) return ck.rc;
-    if (ck.refuse(!act_saved, "act_saved is required (the stash of lsnf_forward, lsnf_restash or lsnf_reverse_keep)") ||
-        ck.refuse(depth > 1 && !z_saved, "z_saved is required (NULL) for depth > 1") ||
-        ck.refuse(!rng && !init && !uniform, "uniform is required without an rng (unless LSNF_MALA_INIT)") ||
-        ck.refuse(!rng && eps_next && !noise, "noise is required with eps_next when no rng is given") ||
-        ck.refuse(!rng && !eps_next && noise, "noise goes with eps_next: nothing is proposed without it") ||
-        ck.aligned16("plan", {plan}) || ck.aligned16("act_saved", {act_saved}))
-        return ck.rc;
-    for (const Named& r : reads)
-        if (ck.aligned4(r.name, {r.p})) return ck.rc;
-    for (const Named& w : writes)
-        if (ck.aligned4(w.name, {w.p})) return ck.rc;
+    if (s.pointers(ck)) return ck.rc;
     LsnfReverseMalaCall c;               // (no g_x / g_objective / g_z_in: the gradient at the proposal is consumed by the tail)
     ck.head(c, plan, B, stream, {eps_prop, z_saved, grad_g, noise, eps_next, eps_acc, grad_acc});
     c.z_out = eps_prop; c.z_saved = z_saved; c.act_saved = act_saved;
     c.grad_g = grad_g; c.noise = noise; c.step = step_size; c.eps_new = eps_next; c.rng = rng_args(rng);
-    c.energy_g = energy_g; c.uniform = uniform; c.eps_acc = eps_acc; c.grad_acc = grad_acc; c.u_acc = u_acc;
-    c.accept_out = accept_out; c.log_alpha_out = log_alpha_out; c.flags = flags;
+    c.chain = {energy_g, uniform, eps_acc, grad_acc, u_acc, accept_out, log_alpha_out, flags};
     const Pick p = select_reverse_mala(c);
     return report(ck.entry, p, lsnf_launch_small3_reverse_mala(c, p.st));
 }
@@ -898,61 +897,34 @@ int lsnf_hmc_step(const float* plan, int nz, int width, int depth, int coupling,
                   float* z_acc, float* grad_acc, float* u_acc, float* mom, float* kin0, const float* noise, const float* uniform,
                   const LsnfRng* rng, float step_size, unsigned flags, float* z_next, float* accept_out, float* log_alpha_out, void* stream) {
     Check ck{"lsnf_hmc_step"};
-    struct Named { const char* name; const void* p; };
     const Named reads[] = {{"plan", plan}, {"z_prop", z_prop}, {"z_out", z_out}, {"z_saved", z_saved}, {"act_saved", act_saved},
                            {"ll_prop", ll_prop}, {"grad_g", grad_g}, {"energy_g", energy_g}, {"noise", noise}, {"uniform", uniform}};
     // (mom is read and written by the same call: it is listed with the outputs, so it may be neither another input nor another output)
     const Named writes[] = {{"z_acc", z_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc}, {"z_next", z_next}, {"accept_out", accept_out},
                             {"log_alpha_out", log_alpha_out}, {"mom", mom}, {"kin0", kin0}};
-    // z_next may be z_prop (a lane stores the columns it loaded, after the barrier); no other output may be a tensor the call reads,
-    // or another output
-    auto aliases = [&] {
-        for (const Named& w : writes) {
-            if (!w.p) continue;
-            for (const Named& r : reads)
-                if (w.p == r.p && !(&w == &writes[3] && &r == &reads[1])) return ck.refuse(true, "%s must not alias %s", w.name, r.name);
-            for (const Named& o : writes)
-                if (&o != &w && w.p == o.p) return ck.refuse(true, "%s must not alias %s", w.name, o.name);
-        }
-        return false;
-    };
-    const unsigned known = LSNF_HMC_INIT | LSNF_HMC_INNER;
     const bool init = (flags & LSNF_HMC_INIT) != 0, inner = (flags & LSNF_HMC_INNER) != 0;
-    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B) ||
-        ck.refuse(uniform && rng, "pass either a uniform tensor or an rng, not both") || ck.rng(noise, rng, /*row0_first=*/false) ||
-        ck.refuse(!std::isfinite(step_size) || step_size == 0.0f, "step_size must be finite and non-zero (got %g)", (double)step_size) ||
-        ck.refuse(flags & ~known, "unknown flag bits 0x%x", flags & ~known) ||
+    const Needed needed[] = {{"plan", plan}, {"z_prop", z_prop}, {"z_out", z_out}, {"act_saved", act_saved}, {"z_acc", z_acc},
+                             {"grad_acc", grad_acc}, {"u_acc", u_acc}, {"mom", mom}, {"kin0", kin0},
+                             {"ll_prop", ll_prop, !inner, "(NULL) unless LSNF_HMC_INNER"}, {"z_saved", z_saved, depth > 1, "(NULL) for depth > 1"},
+                             {"z_next", z_next, inner, "(NULL) with LSNF_HMC_INNER"}};
+    const ChainStep s = {reads, writes, /*next=*/&writes[3], /*point=*/&reads[1], needed, LSNF_HMC_INIT | LSNF_HMC_INNER, init, inner,
+                         "LSNF_HMC_INIT or LSNF_HMC_INNER", plan, act_saved, noise, uniform, rng, step_size, flags};
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B) || s.scalars(ck) ||
         ck.refuse(init && inner, "flags: LSNF_HMC_INIT and LSNF_HMC_INNER exclude each other") ||
         // an inner leapfrog step draws nothing and decides nothing
         ck.refuse(inner && noise, "noise is not taken with LSNF_HMC_INNER (an inner step draws nothing)") ||
         ck.refuse(inner && uniform, "uniform is not taken with LSNF_HMC_INNER (an inner step draws nothing)") ||
         ck.refuse(inner && rng, "rng is not taken with LSNF_HMC_INNER (an inner step draws nothing)") ||
         ck.refuse(inner && accept_out, "accept_out must be NULL with LSNF_HMC_INNER (an inner step decides nothing)") ||
-        ck.refuse(inner && log_alpha_out, "log_alpha_out must be NULL with LSNF_HMC_INNER (an inner step decides nothing)") || aliases())
+        ck.refuse(inner && log_alpha_out, "log_alpha_out must be NULL with LSNF_HMC_INNER (an inner step decides nothing)") || s.aliases(ck))
         return ck.rc;
     if (ck.empty) return LSNF_OK;
-    const Named needed[] = {{"plan", plan}, {"z_prop", z_prop}, {"z_out", z_out}, {"act_saved", act_saved}, {"z_acc", z_acc},
-                            {"grad_acc", grad_acc}, {"u_acc", u_acc}, {"mom", mom}, {"kin0", kin0}};
-    for (const Named& r : needed)
-        if (ck.refuse(!r.p, "%s is required (NULL)", r.name)) return ck.rc;
-    if (ck.refuse(!inner && !ll_prop, "ll_prop is required (NULL) unless LSNF_HMC_INNER") ||
-        ck.refuse(depth > 1 && !z_saved, "z_saved is required (NULL) for depth > 1") ||
-        ck.refuse(inner && !z_next, "z_next is required (NULL) with LSNF_HMC_INNER") ||
-        ck.refuse(!inner && !rng && !init && !uniform, "uniform is required without an rng (unless LSNF_HMC_INIT or LSNF_HMC_INNER)") ||
-        ck.refuse(!inner && !rng && z_next && !noise, "noise is required with z_next when no rng is given") ||
-        ck.refuse(!inner && !rng && !z_next && noise, "noise goes with z_next: nothing is proposed without it") ||
-        ck.aligned16("plan", {plan}) || ck.aligned16("act_saved", {act_saved}))
-        return ck.rc;
-    for (const Named& r : reads)
-        if (ck.aligned4(r.name, {r.p})) return ck.rc;
-    for (const Named& w : writes)
-        if (ck.aligned4(w.name, {w.p})) return ck.rc;
+    if (s.pointers(ck)) return ck.rc;
     const LsnfLangevinArgs lv = {z_prop, grad_g, noise, z_next, nullptr, nullptr, step_size, rng_args(rng)};
     LsnfHmcCall c;                       // (no g_z1 / g_logdet / g_z_in: the gradient of -log p at the point, consumed by the tail)
     ck.head(c, plan, B, stream, {z_prop, z_out, z_saved, grad_g, noise, z_next, z_acc, grad_acc, mom});
-    c.z_out = z_out; c.z_saved = z_saved; c.act_saved = act_saved; c.ll_mode = 1; c.ll_scale = -1.0f; c.lv = &lv;
-    c.ll_prop = ll_prop; c.energy_g = energy_g; c.uniform = uniform; c.z_acc = z_acc; c.grad_acc = grad_acc; c.u_acc = u_acc;
-    c.accept_out = accept_out; c.log_alpha_out = log_alpha_out; c.flags = flags; c.mom = mom; c.kin0 = kin0;
+    c.z_out = z_out; c.z_saved = z_saved; c.act_saved = act_saved; c.ll_mode = 1; c.ll_scale = -1.0f; c.lv = &lv; c.ll_prop = ll_prop;
+    c.chain = {energy_g, uniform, z_acc, grad_acc, u_acc, accept_out, log_alpha_out, flags}; c.mom = mom; c.kin0 = kin0;
     const Pick p = select_hmc(c);
     return report(ck.entry, p, lsnf_launch_small3_hmc(c, p.st));
 }

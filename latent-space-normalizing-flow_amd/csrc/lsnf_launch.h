@@ -46,11 +46,15 @@ struct LsnfBackwardCall : LsnfCall {     // lsnf_backward_z, lsnf_langevin_step 
     const LsnfLangevinArgs* lv = nullptr;
     float* dump = nullptr; double* gl_total = nullptr; int dump_tiled = 0;
 };
-struct LsnfMalaCall : LsnfBackwardCall {  // lsnf_mala_step: ll_mode 1 / ll_scale -1 at the proposal; lv holds z_prop (z_cur), grad_g,
-    const float* ll_prop = nullptr; const float* energy_g = nullptr; const float* uniform = nullptr;      // noise, z_next (z_new), step, rng
-    float* z_acc = nullptr; float* grad_acc = nullptr; float* u_acc = nullptr;
+struct LsnfChainArgs {                   // what every Metropolis-adjusted step has: the caller's energy, the uniform, the kept state
+    const float* energy_g = nullptr; const float* uniform = nullptr;      // (acc = the accepted points), the decision, the flags
+    float* acc = nullptr; float* grad_acc = nullptr; float* u_acc = nullptr;
     float* accept_out = nullptr; float* log_alpha_out = nullptr;
-    unsigned flags = 0;                  // LSNF_MALA_*
+    unsigned flags = 0;                  // LSNF_MALA_* / LSNF_HMC_*
+};
+struct LsnfMalaCall : LsnfBackwardCall {  // lsnf_mala_step: ll_mode 1 / ll_scale -1 at the proposal; lv holds z_prop (z_cur), grad_g,
+    const float* ll_prop = nullptr;      // noise, z_next (z_new), step, rng
+    LsnfChainArgs chain;                 // (acc: z_acc)
 };
 struct LsnfHmcCall : LsnfMalaCall {      // lsnf_hmc_step: the MALA call's tensors at a point of a trajectory; flags: LSNF_HMC_*
     float* mom = nullptr; float* kin0 = nullptr;      // the momentum (B, nz; read and written), the kinetic energy the trajectory began with (B)
@@ -67,10 +71,7 @@ struct LsnfReverseLangevinCall : LsnfReverseBackwardCall {      // lsnf_reverse_
     float* eps_new = nullptr; float* g_norm = nullptr; float* eps_norm = nullptr;
 };
 struct LsnfReverseMalaCall : LsnfReverseLangevinCall {      // lsnf_reverse_mala_step: z_out is the proposal eps_prop, eps_new the next
-    const float* energy_g = nullptr; const float* uniform = nullptr;       // proposal eps_next (may be NULL); g_z_in and the norms stay NULL
-    float* eps_acc = nullptr; float* grad_acc = nullptr; float* u_acc = nullptr;
-    float* accept_out = nullptr; float* log_alpha_out = nullptr;
-    unsigned flags = 0;                  // LSNF_MALA_*
+    LsnfChainArgs chain;                 // proposal eps_next (may be NULL); g_z_in and the norms stay NULL.  (acc: eps_acc)
 };
 struct LsnfContractCall : LsnfCall {     // steps (2), (3) of lsnf_backward_params: batch contraction of the dump, chain rule
     const float* const* params_host = nullptr; float* const* grads_host = nullptr;
@@ -248,4 +249,18 @@ inline void lsnf_fill_backward(A& a, const LsnfBackwardCall& c) {
     a.dump = c.dump; a.gl_total = c.gl_total; a.width = c.g.width;
     lsnf_fill_langevin(a, c.lv);
     a.ll_scale = c.ll_scale; a.ll_mode = c.ll_mode; a.B = c.B; a.nz = c.g.nz; a.half = c.g.half; a.depth = c.g.depth; a.vec4 = c.vec4;
+}
+// the chain state of a Metropolis-adjusted form, but for the accepted points: the caller stores ch.acc under its kernel's name for them
+template <class A>
+inline void lsnf_fill_chain(A& a, const LsnfChainArgs& ch) {
+    a.energy_g = ch.energy_g; a.uniform = ch.uniform; a.grad_acc = ch.grad_acc; a.u_acc = ch.u_acc;
+    a.accept_out = ch.accept_out; a.log_alpha_out = ch.log_alpha_out; a.flags = ch.flags;
+}
+// the MALA form of the latency bf16x3 backward (Small3MalaArgs and what derives from it)
+template <class A>
+inline void lsnf_fill_mala(A& a, const LsnfMalaCall& c) {
+    lsnf_fill_backward(a, c);
+    a.panels = c.plan + c.g.off_b3b_panels;
+    a.ll_prop = c.ll_prop; a.z_acc = c.chain.acc;
+    lsnf_fill_chain(a, c.chain);
 }

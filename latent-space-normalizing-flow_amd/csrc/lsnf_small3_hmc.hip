@@ -193,16 +193,12 @@ hipError_t launch_small3_hmc_st(const Small3HmcArgs& a, hipStream_t stream) {
 
 // the HMC form (lsnf_hmc_step): the same stages, the leapfrog tail as the output section; st: lsnf_small3_backward_st of the call
 hipError_t lsnf_launch_small3_hmc(const LsnfHmcCall& c, int st) {
-    const bool inner = (c.flags & 2u) != 0;
-    if (!c.act_saved || !c.lv || c.dump || c.g_z_in || c.B < 1 || !c.mom || !c.kin0 || (c.lv->rng.enabled && (c.lv->noise || c.uniform)) ||
-        (inner && (!c.lv->z_new || c.lv->noise || c.uniform || c.lv->rng.enabled || (c.flags & 1u))))
+    const bool inner = (c.chain.flags & 2u) != 0;
+    if (!c.act_saved || !c.lv || c.dump || c.g_z_in || c.B < 1 || !c.mom || !c.kin0 || (c.lv->rng.enabled && (c.lv->noise || c.chain.uniform)) ||
+        (inner && (!c.lv->z_new || c.lv->noise || c.chain.uniform || c.lv->rng.enabled || (c.chain.flags & 1u))))
         return hipErrorInvalidValue;                    // (a selection bug)
     Small3HmcArgs a;
-    lsnf_fill_backward(a, c);
-    a.panels = c.plan + c.g.off_b3b_panels;
-    a.ll_prop = c.ll_prop; a.energy_g = c.energy_g; a.uniform = c.uniform;
-    a.z_acc = c.z_acc; a.grad_acc = c.grad_acc; a.u_acc = c.u_acc; a.accept_out = c.accept_out; a.log_alpha_out = c.log_alpha_out;
-    a.flags = c.flags;
+    lsnf_fill_mala(a, c);
     a.mom = c.mom; a.kin0 = c.kin0;
     return lsnf_with_cfg<Small3BwdCfg>(c.g, [&](auto cfg) {
         return lsnf_with_st(st, [&](auto s) { return launch_small3_hmc_st<decltype(cfg), decltype(s)::value>(a, c.stream); });

@@ -146,14 +146,10 @@ hipError_t launch_small3_mala_st(const Small3MalaArgs& a, hipStream_t stream) {
 
 // the MALA form (lsnf_mala_step): the same stages, the accept / reject tail as the output section; st: lsnf_small3_backward_st of the call
 hipError_t lsnf_launch_small3_mala(const LsnfMalaCall& c, int st) {
-    if (!c.act_saved || !c.lv || c.dump || c.g_z_in || c.B < 1 || (c.lv->rng.enabled && (c.lv->noise || c.uniform)))
+    if (!c.act_saved || !c.lv || c.dump || c.g_z_in || c.B < 1 || (c.lv->rng.enabled && (c.lv->noise || c.chain.uniform)))
         return hipErrorInvalidValue;                    // (a selection bug)
     Small3MalaArgs a;
-    lsnf_fill_backward(a, c);
-    a.panels = c.plan + c.g.off_b3b_panels;
-    a.ll_prop = c.ll_prop; a.energy_g = c.energy_g; a.uniform = c.uniform;
-    a.z_acc = c.z_acc; a.grad_acc = c.grad_acc; a.u_acc = c.u_acc; a.accept_out = c.accept_out; a.log_alpha_out = c.log_alpha_out;
-    a.flags = c.flags;
+    lsnf_fill_mala(a, c);
     return lsnf_with_cfg<Small3BwdCfg>(c.g, [&](auto cfg) {
         return lsnf_with_st(st, [&](auto s) { return launch_small3_mala_st<decltype(cfg), decltype(s)::value>(a, c.stream); });
     });

@@ -150,8 +150,8 @@ hipError_t launch_small3_rmala_st(const Small3RmalaArgs& a, hipStream_t stream) 
 // the MALA form (lsnf_reverse_mala_step): the same stages, the accept / reject tail as the output section; st:
 // lsnf_small3_reverse_backward_st of the call
 hipError_t lsnf_launch_small3_reverse_mala(const LsnfReverseMalaCall& c, int st) {
-    if (!c.act_saved || !c.eps_acc || !c.grad_acc || !c.u_acc || c.g_z_in || c.g_norm || c.eps_norm || c.B < 1 ||
-        (c.rng.enabled && (c.noise || c.uniform)))
+    if (!c.act_saved || !c.chain.acc || !c.chain.grad_acc || !c.chain.u_acc || c.g_z_in || c.g_norm || c.eps_norm || c.B < 1 ||
+        (c.rng.enabled && (c.noise || c.chain.uniform)))
         return hipErrorInvalidValue;                    // (a selection bug)
     Small3RmalaArgs a;
     a.panels = c.plan + c.g.off_b3b_panels;
@@ -159,8 +159,8 @@ hipError_t lsnf_launch_small3_reverse_mala(const LsnfReverseMalaCall& c, int st)
     a.z_out = c.z_out; a.z_saved = c.z_saved; a.act_saved = c.act_saved; a.g_x = c.grad_g; a.g_obj = nullptr; a.g_z_in = nullptr;
     a.B = c.B; a.nz = c.g.nz; a.half = c.g.half; a.depth = c.g.depth; a.vec4 = c.vec4;
     a.noise = c.noise; a.eps_new = c.eps_new; a.g_norm = nullptr; a.eps_norm = nullptr; a.step = c.step; a.rng = c.rng;
-    a.energy_g = c.energy_g; a.uniform = c.uniform; a.eps_acc = c.eps_acc; a.grad_acc = c.grad_acc; a.u_acc = c.u_acc;
-    a.accept_out = c.accept_out; a.log_alpha_out = c.log_alpha_out; a.flags = c.flags;
+    a.eps_acc = c.chain.acc;
+    lsnf_fill_chain(a, c.chain);
     return lsnf_with_cfg<Small3RbwdCfg>(c.g, [&](auto cfg) {
         return lsnf_with_st(st, [&](auto s) { return launch_small3_rmala_st<decltype(cfg), decltype(s)::value>(a, c.stream); });
     });

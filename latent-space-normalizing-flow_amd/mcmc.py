@@ -4,7 +4,7 @@
 launched; like there, all functions raise on CPU tensors: there is no CPU path."""
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, fields
 from typing import Optional
 
 import torch
@@ -34,6 +34,40 @@ def new_mala_state(plan: FlowPlan, B: int, device) -> MalaState:
     return MalaState(torch.zeros((int(B), plan.nz), **f32), torch.zeros((int(B), plan.nz), **f32), torch.zeros(int(B), **f32))
 
 
+def _check_chain(plan, point, name, grad_g, energy_g, state, state_cls, noise, uniform, stash=None):
+    """The argument checks every chain step makes, in the order a bad argument is reported: the point (the anchor of the call; `name`
+    in the messages), the caller's stash (z_saved, act_saved) where the step takes one, grad_g, energy_g, the state (a `state_cls`,
+    every array of it), the noise and the uniform.  Returns (B, device, noise tensor or None, rng or None)."""
+    B, dev = _anchor(point, name, plan), point.device
+    if stash is not None:
+        _check_stash(plan, B, dev, *stash, True)
+    _check_like(grad_g, "grad_g", point, name)
+    _check_in(energy_g, "energy_g", B, dev)
+    if not isinstance(state, state_cls):
+        raise LsnfError(f"state must be a flow.{state_cls.__name__} ({_NEW_STATE[state_cls]}())")
+    for f in fields(state_cls):          # (B, nz) arrays, but for the per-row scalars energy / kin
+        _check_out(getattr(state, f.name), "state." + f.name, B if f.name in ("energy", "kin") else B * plan.nz, dev)
+    noise, rng = _noise_args(noise, point, name, dev)
+    _check_in(uniform, "uniform", B, dev)
+    if rng is not None and uniform is not None:
+        raise LsnfError("pass either a PhiloxNoise or the tensors (noise, uniform=), not both")
+    return B, dev, noise, rng
+
+
+def _forward_at(plan, z_prop, B, dev, key, reuse_buffers):
+    """The first launch of `mala_step` / `hmc_step`: their buffer set (on the plan under `key` with reuse_buffers) and the forward at
+    z_prop into it.  Returns (buffers, z1, ll)."""
+    def make():
+        f32 = dict(dtype=torch.float32, device=dev)
+        return {"act": new_act_saved(plan, B, dev), "out": (torch.empty_like(z_prop), torch.empty(B, **f32), torch.empty(B, **f32)),
+                "saved": torch.empty((plan.depth - 1, B, plan.nz), **f32) if plan.depth > 1 else None,
+                "acc": torch.empty(B, **f32), "la": torch.empty(B, **f32)}
+    bufs = _stream_buffers(plan, key, B, dev, make) if reuse_buffers else make()
+    _check_stash(plan, B, dev, bufs["saved"], bufs["act"], True)
+    z1, _, ll, _ = forward(plan, z_prop, None, want_ll=True, out=bufs["out"], act_saved=bufs["act"], z_saved_out=bufs["saved"])
+    return bufs, z1, ll
+
+
 def mala_step(plan: FlowPlan, z_prop: torch.Tensor, grad_g: Optional[torch.Tensor], energy_g: Optional[torch.Tensor],
               state: MalaState, noise, step_size: float, *, init: bool = False, uniform: Optional[torch.Tensor] = None,
               propose: bool = True, inplace: bool = False, reuse_buffers: bool = False):
@@ -48,30 +82,10 @@ def mala_step(plan: FlowPlan, z_prop: torch.Tensor, grad_g: Optional[torch.Tenso
     proposing calls, one with propose=False.
     Returns (z_next or None, accepted (B) of 1.0 / 0.0, log_alpha (B), ll_prop (B)).  inplace: z_next is z_prop itself.
     reuse_buffers: as `langevin_step`'s -- the last three are then overwritten by the next call."""
-    B, dev = _anchor(z_prop, "z_prop", plan), z_prop.device
-    _check_like(grad_g, "grad_g", z_prop, "z_prop")
-    _check_in(energy_g, "energy_g", B, dev)
-    if not isinstance(state, MalaState):
-        raise LsnfError("state must be a flow.MalaState (new_mala_state())")
-    _check_out(state.z, "state.z", B * plan.nz, dev)
-    _check_out(state.grad, "state.grad", B * plan.nz, dev)
-    _check_out(state.energy, "state.energy", B, dev)
-    noise, rng = _noise_args(noise, z_prop, "z_prop", dev)
-    _check_in(uniform, "uniform", B, dev)
-    if rng is not None and uniform is not None:
-        raise LsnfError("pass either a PhiloxNoise or the tensors (noise, uniform=), not both")
-
-    def make():
-        f32 = dict(dtype=torch.float32, device=dev)
-        return {"act": new_act_saved(plan, B, dev), "out": (torch.empty_like(z_prop), torch.empty(B, **f32), torch.empty(B, **f32)),
-                "saved": torch.empty((plan.depth - 1, B, plan.nz), **f32) if plan.depth > 1 else None,
-                "acc": torch.empty(B, **f32), "la": torch.empty(B, **f32)}
-    bufs = _stream_buffers(plan, "_mala_buffers", B, dev, make) if reuse_buffers else make()
-    act, saved = bufs["act"], bufs["saved"]
-    _check_stash(plan, B, dev, saved, act, True)
-    z1, _, ll, _ = forward(plan, z_prop, None, want_ll=True, out=bufs["out"], act_saved=act, z_saved_out=saved)
+    B, dev, noise, rng = _check_chain(plan, z_prop, "z_prop", grad_g, energy_g, state, MalaState, noise, uniform)
+    bufs, z1, ll = _forward_at(plan, z_prop, B, dev, "_mala_buffers", reuse_buffers)
     z_next = None if not propose else z_prop if inplace else torch.empty_like(z_prop)
-    _call("lsnf_mala_step", dev, *_plan_head(plan), B, _ptr(z_prop), _ptr(z1), _ptr(saved), _ptr(act), _ptr(ll), _ptr(grad_g),
+    _call("lsnf_mala_step", dev, *_plan_head(plan), B, _ptr(z_prop), _ptr(z1), _ptr(bufs["saved"]), _ptr(bufs["act"]), _ptr(ll), _ptr(grad_g),
           _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(noise), _ptr(uniform), rng, float(step_size),
           MALA_INIT if init else 0, _ptr(z_next), _ptr(bufs["acc"]), _ptr(bufs["la"]))
     return z_next, bufs["acc"], bufs["la"], ll
@@ -98,19 +112,8 @@ def reverse_mala_step(plan: FlowPlan, eps_prop: torch.Tensor, z_saved: Optional[
     Returns (eps_next or None, accepted (B) of 1.0 / 0.0, log_alpha (B)).  inplace: eps_next is eps_prop itself.  reuse_buffers:
     the last two live on the plan and are overwritten by the next call.  Asynchronous on the current stream; nothing but the
     launch, so it can be captured in a graph."""
-    B, dev = _anchor(eps_prop, "eps_prop", plan), eps_prop.device
-    _check_stash(plan, B, dev, z_saved, act_saved, True)
-    _check_like(grad_g, "grad_g", eps_prop, "eps_prop")
-    _check_in(energy_g, "energy_g", B, dev)
-    if not isinstance(state, MalaState):
-        raise LsnfError("state must be a flow.MalaState (new_mala_state())")
-    _check_out(state.z, "state.z", B * plan.nz, dev)
-    _check_out(state.grad, "state.grad", B * plan.nz, dev)
-    _check_out(state.energy, "state.energy", B, dev)
-    noise, rng = _noise_args(noise, eps_prop, "eps_prop", dev)
-    _check_in(uniform, "uniform", B, dev)
-    if rng is not None and uniform is not None:
-        raise LsnfError("pass either a PhiloxNoise or the tensors (noise, uniform=), not both")
+    B, dev, noise, rng = _check_chain(plan, eps_prop, "eps_prop", grad_g, energy_g, state, MalaState, noise, uniform,
+                                      stash=(z_saved, act_saved))
 
     def make():
         f32 = dict(dtype=torch.float32, device=dev)
@@ -146,6 +149,9 @@ def new_hmc_state(plan: FlowPlan, B: int, device) -> HmcState:
     return HmcState(rows(), rows(), one(), rows(), one())
 
 
+_NEW_STATE = {MalaState: "new_mala_state", HmcState: "new_hmc_state"}      # (named where a step is given another state)
+
+
 def hmc_step(plan: FlowPlan, z_prop: torch.Tensor, grad_g: Optional[torch.Tensor], energy_g: Optional[torch.Tensor],
              state: HmcState, noise, step_size: float, *, phase: str = "end", uniform: Optional[torch.Tensor] = None,
              propose: bool = True, inplace: bool = False, reuse_buffers: bool = False):
@@ -168,35 +174,13 @@ def hmc_step(plan: FlowPlan, z_prop: torch.Tensor, grad_g: Optional[torch.Tensor
     if phase not in _HMC_PHASES:
         raise LsnfError(f"phase must be one of 'init', 'inner', 'end' (got {phase!r})")
     inner = phase == "inner"
-    B, dev = _anchor(z_prop, "z_prop", plan), z_prop.device
-    _check_like(grad_g, "grad_g", z_prop, "z_prop")
-    _check_in(energy_g, "energy_g", B, dev)
-    if not isinstance(state, HmcState):
-        raise LsnfError("state must be a flow.HmcState (new_hmc_state())")
-    _check_out(state.z, "state.z", B * plan.nz, dev)
-    _check_out(state.grad, "state.grad", B * plan.nz, dev)
-    _check_out(state.energy, "state.energy", B, dev)
-    _check_out(state.mom, "state.mom", B * plan.nz, dev)
-    _check_out(state.kin, "state.kin", B, dev)
-    noise, rng = _noise_args(noise, z_prop, "z_prop", dev)
-    _check_in(uniform, "uniform", B, dev)
-    if rng is not None and uniform is not None:
-        raise LsnfError("pass either a PhiloxNoise or the tensors (noise, uniform=), not both")
+    B, dev, noise, rng = _check_chain(plan, z_prop, "z_prop", grad_g, energy_g, state, HmcState, noise, uniform)
     if inner and (noise is not None or rng is not None or uniform is not None or not propose):
         raise LsnfError("an inner leapfrog step draws and decides nothing: noise and uniform must be None, propose True")
-
-    def make():
-        f32 = dict(dtype=torch.float32, device=dev)
-        return {"act": new_act_saved(plan, B, dev), "out": (torch.empty_like(z_prop), torch.empty(B, **f32), torch.empty(B, **f32)),
-                "saved": torch.empty((plan.depth - 1, B, plan.nz), **f32) if plan.depth > 1 else None,
-                "acc": torch.empty(B, **f32), "la": torch.empty(B, **f32)}
-    bufs = _stream_buffers(plan, "_hmc_buffers", B, dev, make) if reuse_buffers else make()
-    act, saved = bufs["act"], bufs["saved"]
-    _check_stash(plan, B, dev, saved, act, True)
-    z1, _, ll, _ = forward(plan, z_prop, None, want_ll=True, out=bufs["out"], act_saved=act, z_saved_out=saved)
+    bufs, z1, ll = _forward_at(plan, z_prop, B, dev, "_hmc_buffers", reuse_buffers)
     z_next = None if not propose else z_prop if inplace else torch.empty_like(z_prop)
     acc, la = (None, None) if inner else (bufs["acc"], bufs["la"])
-    _call("lsnf_hmc_step", dev, *_plan_head(plan), B, _ptr(z_prop), _ptr(z1), _ptr(saved), _ptr(act), _ptr(ll), _ptr(grad_g),
+    _call("lsnf_hmc_step", dev, *_plan_head(plan), B, _ptr(z_prop), _ptr(z1), _ptr(bufs["saved"]), _ptr(bufs["act"]), _ptr(ll), _ptr(grad_g),
           _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(state.mom), _ptr(state.kin), _ptr(noise),
           _ptr(uniform), rng, float(step_size), _HMC_PHASES[phase], _ptr(z_next), _ptr(acc), _ptr(la))
     return z_next, acc, la, ll

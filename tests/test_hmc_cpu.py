@@ -162,6 +162,60 @@ def test_depth_one_and_the_optional_pointers_pass_the_pointer_rules():
     assert refused("act_saved must be 16-byte", flags=INNER, noise=None, uniform=None, nz=64, w=32, d=1, saved=None, act=bad_act)
 
 
+def test_every_rule_speaks_word_for_word():
+    """One call per rule and phase it applies in: the first violated rule speaks, and lsnf_last_error() is this text to the letter."""
+    lib = lsnf_amd.load_library()
+    call, _, P, Rng = _caller(lib)
+    inner = dict(flags=INNER, noise=None, uniform=None)
+    table = (
+        (dict(B=-1), 'lsnf_hmc_step: B=-1 out of range'),
+        (dict(B=0, noise=None, rng=Rng(1, 0, None, 0)), 'lsnf_hmc_step: pass either a uniform tensor or an rng, not both'),
+        (dict(uniform=None, rng=Rng(1, 0, None, 0)), 'lsnf_hmc_step: pass either a noise tensor or an rng, not both'),
+        (dict(B=0, noise=None, uniform=None, rng=Rng(1, 0, None, -1)), 'lsnf_hmc_step: rng->row0 must be >= 0'),
+        (dict(noise=None, uniform=None, rng=Rng(1, 0, 0x30004, 0)), 'lsnf_hmc_step: rng->offset_dev must be 8-byte aligned'),
+        (dict(step=float('nan')), 'lsnf_hmc_step: step_size must be finite and non-zero (got nan)'),
+        (dict(B=0, step=0.0), 'lsnf_hmc_step: step_size must be finite and non-zero (got 0)'),
+        (dict(inner, step=0.0), 'lsnf_hmc_step: step_size must be finite and non-zero (got 0)'),
+        (dict(flags=4), 'lsnf_hmc_step: unknown flag bits 0x4'),
+        (dict(B=0, flags=0x80000003), 'lsnf_hmc_step: unknown flag bits 0x80000000'),
+        (dict(flags=INIT | INNER, noise=None, uniform=None), 'lsnf_hmc_step: flags: LSNF_HMC_INIT and LSNF_HMC_INNER exclude each other'),
+        (dict(B=0, flags=INIT | INNER), 'lsnf_hmc_step: flags: LSNF_HMC_INIT and LSNF_HMC_INNER exclude each other'),
+        (dict(flags=INNER, uniform=None), 'lsnf_hmc_step: noise is not taken with LSNF_HMC_INNER (an inner step draws nothing)'),
+        (dict(B=0, flags=INNER, noise=None), 'lsnf_hmc_step: uniform is not taken with LSNF_HMC_INNER (an inner step draws nothing)'),
+        (dict(inner, rng=Rng(1, 0, None, 0)), 'lsnf_hmc_step: rng is not taken with LSNF_HMC_INNER (an inner step draws nothing)'),
+        (dict(inner, accept=P['accept']), 'lsnf_hmc_step: accept_out must be NULL with LSNF_HMC_INNER (an inner step decides nothing)'),
+        (dict(inner, B=0, la=P['la']), 'lsnf_hmc_step: log_alpha_out must be NULL with LSNF_HMC_INNER (an inner step decides nothing)'),
+        (dict(z_acc=P['grad_g']), 'lsnf_hmc_step: z_acc must not alias grad_g'),
+        (dict(B=0, z_next=P['z_out'], flags=INIT), 'lsnf_hmc_step: z_next must not alias z_out'),
+        (dict(kin0=P['uniform']), 'lsnf_hmc_step: kin0 must not alias uniform'),
+        (dict(mom=P['z_next']), 'lsnf_hmc_step: z_next must not alias mom'),
+        (dict(inner, mom=P['grad_g']), 'lsnf_hmc_step: mom must not alias grad_g'),
+        (dict(inner, z_next=P['mom']), 'lsnf_hmc_step: z_next must not alias mom'),
+        (dict(accept=P['la'], la=P['la']), 'lsnf_hmc_step: accept_out must not alias log_alpha_out'),
+        (dict(plan=None), 'lsnf_hmc_step: plan is required (NULL)'),
+        (dict(mom=None, flags=INIT), 'lsnf_hmc_step: mom is required (NULL)'),
+        (dict(inner, kin0=None), 'lsnf_hmc_step: kin0 is required (NULL)'),
+        (dict(ll=None), 'lsnf_hmc_step: ll_prop is required (NULL) unless LSNF_HMC_INNER'),
+        (dict(ll=None, flags=INIT), 'lsnf_hmc_step: ll_prop is required (NULL) unless LSNF_HMC_INNER'),
+        (dict(ll=None, saved=None), 'lsnf_hmc_step: ll_prop is required (NULL) unless LSNF_HMC_INNER'),
+        (dict(saved=None), 'lsnf_hmc_step: z_saved is required (NULL) for depth > 1'),
+        (dict(inner, saved=None, z_next=None), 'lsnf_hmc_step: z_saved is required (NULL) for depth > 1'),
+        (dict(inner, z_next=None), 'lsnf_hmc_step: z_next is required (NULL) with LSNF_HMC_INNER'),
+        (dict(uniform=None), 'lsnf_hmc_step: uniform is required without an rng (unless LSNF_HMC_INIT or LSNF_HMC_INNER)'),
+        (dict(noise=None), 'lsnf_hmc_step: noise is required with z_next when no rng is given'),
+        (dict(noise=None, flags=INIT, uniform=None), 'lsnf_hmc_step: noise is required with z_next when no rng is given'),
+        (dict(z_next=None), 'lsnf_hmc_step: noise goes with z_next: nothing is proposed without it'),
+        (dict(z_next=None, flags=INIT), 'lsnf_hmc_step: noise goes with z_next: nothing is proposed without it'),
+        (dict(plan=ctypes.c_void_p(0x10004)), 'lsnf_hmc_step: plan must be 16-byte aligned'),
+        (dict(inner, act=ctypes.c_void_p(0x50008), ll=None, energy=None), 'lsnf_hmc_step: act_saved must be 16-byte aligned'),
+        (dict(inner, mom=ctypes.c_void_p(0xF00002)), 'lsnf_hmc_step: mom must be 4-byte aligned'),
+        (dict(grad_g=ctypes.c_void_p(0xF00002)), 'lsnf_hmc_step: grad_g must be 4-byte aligned'),
+        (dict(la=ctypes.c_void_p(0xF00002)), 'lsnf_hmc_step: log_alpha_out must be 4-byte aligned'),
+    )
+    for kw, message in table:
+        assert call(**kw) == LSNF_E_ARG and lib.lsnf_last_error().decode() == message, (kw, lib.lsnf_last_error())
+
+
 def test_python_wrappers_have_no_cpu_path():
     F = lsnf_amd.flow
     plan = F.FlowPlan(8, 4, 2, 1, torch.zeros(1), torch.zeros(1, dtype=torch.float64))

@@ -148,6 +148,42 @@ def test_depth_one_and_init_pass_the_pointer_rules():
     assert refused("act_saved must be 16-byte", grad_g=None, energy=None, act=bad_act)               # the prior alone
 
 
+def test_every_rule_speaks_word_for_word():
+    """One call per rule: the first violated rule speaks, and lsnf_last_error() is this text to the letter."""
+    lib = lsnf_amd.load_library()
+    call, _, P, Rng = _caller(lib)
+    table = (
+        (dict(B=-1), 'lsnf_mala_step: B=-1 out of range'),
+        (dict(B=0, noise=None, rng=Rng(1, 0, None, 0)), 'lsnf_mala_step: pass either a uniform tensor or an rng, not both'),
+        (dict(uniform=None, rng=Rng(1, 0, None, 0)), 'lsnf_mala_step: pass either a noise tensor or an rng, not both'),
+        (dict(B=0, noise=None, uniform=None, rng=Rng(1, 0, None, -1)), 'lsnf_mala_step: rng->row0 must be >= 0'),
+        (dict(noise=None, uniform=None, rng=Rng(1, 0, 0x30004, 0)), 'lsnf_mala_step: rng->offset_dev must be 8-byte aligned'),
+        (dict(step=float('nan')), 'lsnf_mala_step: step_size must be finite and non-zero (got nan)'),
+        (dict(B=0, step=0.0), 'lsnf_mala_step: step_size must be finite and non-zero (got 0)'),
+        (dict(flags=2), 'lsnf_mala_step: unknown flag bits 0x2'),
+        (dict(B=0, flags=0x80000003), 'lsnf_mala_step: unknown flag bits 0x80000002'),
+        (dict(z_acc=P['grad_g']), 'lsnf_mala_step: z_acc must not alias grad_g'),
+        (dict(B=0, z_next=P['z_out']), 'lsnf_mala_step: z_next must not alias z_out'),
+        (dict(u_acc=P['uniform']), 'lsnf_mala_step: u_acc must not alias uniform'),
+        (dict(g_acc=P['z_next']), 'lsnf_mala_step: grad_acc must not alias z_next'),
+        (dict(accept=P['la'], la=P['la']), 'lsnf_mala_step: accept_out must not alias log_alpha_out'),
+        (dict(la=P['z_acc']), 'lsnf_mala_step: z_acc must not alias log_alpha_out'),
+        (dict(plan=None), 'lsnf_mala_step: plan is required (NULL)'),
+        (dict(ll=None), 'lsnf_mala_step: ll_prop is required (NULL)'),
+        (dict(u_acc=None), 'lsnf_mala_step: u_acc is required (NULL)'),
+        (dict(saved=None), 'lsnf_mala_step: z_saved is required (NULL) for depth > 1'),
+        (dict(uniform=None), 'lsnf_mala_step: uniform is required without an rng (unless LSNF_MALA_INIT)'),
+        (dict(noise=None), 'lsnf_mala_step: noise is required with z_next when no rng is given'),
+        (dict(z_next=None), 'lsnf_mala_step: noise goes with z_next: nothing is proposed without it'),
+        (dict(plan=ctypes.c_void_p(0x10004)), 'lsnf_mala_step: plan must be 16-byte aligned'),
+        (dict(act=ctypes.c_void_p(0x50008)), 'lsnf_mala_step: act_saved must be 16-byte aligned'),
+        (dict(grad_g=ctypes.c_void_p(0xF00002)), 'lsnf_mala_step: grad_g must be 4-byte aligned'),
+        (dict(la=ctypes.c_void_p(0xF00002)), 'lsnf_mala_step: log_alpha_out must be 4-byte aligned'),
+    )
+    for kw, message in table:
+        assert call(**kw) == LSNF_E_ARG and lib.lsnf_last_error().decode() == message, (kw, lib.lsnf_last_error())
+
+
 def test_python_wrappers_have_no_cpu_path():
     F = lsnf_amd.flow
     plan = F.FlowPlan(8, 4, 2, 1, torch.zeros(1), torch.zeros(1, dtype=torch.float64))

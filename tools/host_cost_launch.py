@@ -7,10 +7,11 @@
 An argument is a build of liblsnf_flow.so (run under this checkout's Python, LSNF_LIB_PATH) or a checkout directory: the child
 then runs with that directory as its working directory -- that tree's Python layer and that tree's built library.
 The builds alternate in fresh child processes, the order within a pair swapped from round to round (use an
-even number of rounds: a build against a copy of itself shows the second child of a pair ~0.1-0.5 us slower).  A child times the ENQUEUE of eight calls -- no synchronisation
+even number of rounds: a build against a copy of itself shows the second child of a pair ~0.1-0.5 us slower).  A child times the ENQUEUE of eleven calls -- no synchronisation
 inside a timed region, as tools/host_rate.py -- in REGIONS regions of CALLS calls each (queue drained between regions):
   forward(B=64), forward(B=64, stash), langevin_step(B=100), sample(B=100), BoundForward(B=8192),
-  backward_z(B=100), reverse_backward_z(B=100), backward_params(B=100, reuse_buffers) -- the last three from the forward's stash.
+  backward_z(B=100), reverse_backward_z(B=100), backward_params(B=100, reuse_buffers) -- these three from the forward's stash --,
+  mala_step(B=100), reverse_mala_step(B=100) from that stash, hmc_step(B=100, phase="inner").
 Per build and call: median and p10 / p90 over every region of every round, and the medians of the rounds.  The first build is
 the reference: the second one's median may exceed its median by at most the reference's own p10-p90 width; exit status 1 if
 a call does."""
@@ -22,7 +23,8 @@ import ab_harness
 
 REGIONS, CALLS = 15, 300
 NAMES = ("forward B=64", "forward B=64 +stash", "langevin_step B=100", "sample B=100", "BoundForward B=8192",
-         "backward_z B=100", "reverse_backward_z B=100", "backward_params B=100")
+         "backward_z B=100", "reverse_backward_z B=100", "backward_params B=100",
+         "mala_step B=100", "reverse_mala_step B=100", "hmc_step inner B=100")
 
 CHILD = r'''
 import os, sys, time, torch
@@ -45,6 +47,11 @@ bound = F.BoundForward(plan, z8k, o8k)
 act100, ws100 = F.new_act_saved(plan, 100, dev), F.new_params_workspace(plan, 100, dev)
 z1, _, _, sav100 = F.forward(plan, z100, save_for_backward=True, act_saved=act100, params_ws=ws100)
 gz, gld = torch.randn(100, bench.NZ, generator=gen).to(dev), torch.randn(100, generator=gen).to(dev)
+mala, rmala, hmc = F.new_mala_state(plan, 100, dev), F.new_mala_state(plan, 100, dev), F.new_hmc_state(plan, 100, dev)
+zm, zh = z100.clone(), z100.clone()
+F.mala_step(plan, zm, None, None, mala, rng, 0.1, init=True, propose=False)
+F.reverse_mala_step(plan, z1, sav100, act100, None, None, rmala, rng, 0.1, init=True, propose=False)
+F.hmc_step(plan, zh, None, None, hmc, rng, 0.1, phase="init", inplace=True, reuse_buffers=True)
 calls = (
     lambda: F.forward(plan, z64, out=o64),
     lambda: F.forward(plan, z64, out=o64, act_saved=act64, z_saved_out=sav64),
@@ -54,6 +61,9 @@ calls = (
     lambda: F.backward_z(plan, z1, sav100, gz, gld, act_saved=act100),
     lambda: F.reverse_backward_z(plan, z1, sav100, act100, gz, gld),
     lambda: F.backward_params(plan, params, z100, z1, sav100, gz, gld, reuse_buffers=True, act_saved=act100, workspace=ws100),
+    lambda: F.mala_step(plan, zm, None, None, mala, rng, 0.1, inplace=True, reuse_buffers=True),
+    lambda: F.reverse_mala_step(plan, z1, sav100, act100, None, None, rmala, rng, 0.1, propose=False, reuse_buffers=True),
+    lambda: F.hmc_step(plan, zh, None, None, hmc, None, 1e-3, phase="inner", inplace=True, reuse_buffers=True),
 )
 res = []
 for fn in calls:
