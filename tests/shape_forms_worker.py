@@ -83,7 +83,7 @@ def small3_st(env, geo):
     lsnf_small3_st_wanted; below 4 096 rows the default is 1).  lsnf_small3_*_st: a shape that is not instantiated, or whose LDS does
     not fit, gives way to the next smaller one -- the <2, 4> geometry (f_width 128) has ST = 1 and 2 only."""
     want = int(env.get("LSNF_SMALL3_ST", "1"))
-    return want, (min(want, 2) if GEOS[geo][1] > 64 else want)
+    return want, (min(want, 2) if geo_of(geo)[1] > 64 else want)
 
 
 def small3_rows(env, geo):
@@ -99,7 +99,14 @@ def tn_rows(env):
     return edge_rows(min(chunk, 128)), LDS_ROWS, X3_ROWS
 
 
-MALA_GEOS = ("C3", "C5", "tiny")
+# The MALA probes: three geometries of GEOS, and from tests/chain_geometries.py a ragged half (33) and a second half-tile that is
+# entirely padding, both <2, 2>.  The two are kept out of GEOS, whose sorted order seeds the inputs of every other probe.
+CHAIN_GEOS = {"half33": (66, 33, 2, 1), "pad10": (10, 40, 2, 1)}
+MALA_GEOS = ("C3", "C5", "tiny") + tuple(CHAIN_GEOS)
+
+
+def geo_of(name):
+    return GEOS[name] if name in GEOS else CHAIN_GEOS[name]
 
 
 def mala_rows(env, geo):
@@ -287,7 +294,7 @@ class Child:
         import test_gpu_rmala as RMt
         for probe, T in (("s.mala", ZM), ("s.rmala", RMt)):
             self.start(probe, geo, B)
-            s = T.Setup(self.L, self.dev, *GEOS[geo], B, "default")
+            s = T.Setup(self.L, self.dev, *geo_of(geo), B, "default")
             st = s.c.steps[0]
             r = T.run(self.L, s, st, st.noise.to(self.dev), st.u.to(self.dev))
             state, out = r[0], r[-1]

@@ -10,7 +10,8 @@ and one end call (the CPU computes the whole trajectory; the device is not given
 rows whose float64 log_alpha is within the gate of ln u, and rows with oracle.relu_margin <= 2e-5 at the call's point, are set aside
 (at most 10 % of a case, 2 rows for B <= 33: asserted on the CPU and again with the device's figures).  Every call that proposes:
 z_next rel-L2 <= 1e-5, |mom - fp64| <= 1e-5 (|mom_in or xi| + s |g|), kin0 relative <= 1e-5 per row, each widened to 3 x the fp32
-restatement's own error where that exceeds a third of it (printed).  Step sizes are chosen per nz on the CPU from the float64
+restatement's own error where that exceeds a third of it (printed).  Step sizes are chosen per nz (per geometry for the entries of
+tests/chain_geometries.py -- ragged halves, whole tiles of padding -- which CASES, PHILOX_CASES and FORMS append) on the CPU from the float64
 restatement alone so that the two-trajectory cases accept between 15 % and 85 % of their decisions (asserted).  Everything else is
 bit identity between call forms, or the device against itself."""
 import functools
@@ -20,6 +21,7 @@ import pytest
 import torch
 
 from oracle import flow_oracle as O
+import chain_geometries as G
 import hmc_restated as H
 import test_gpu_reverse_keep as K
 from test_gpu_langevin import ToyG
@@ -29,10 +31,17 @@ pytestmark = pytest.mark.gpu
 C3, C5, TINY = K.C3, K.C5, K.TINY
 CASES = [C3 + (B,) for B in (1, 17, 33, 100, 4100, 8200, 16400)] + \
         [TINY + (33,), C5 + (33,), (126, 127, 2, 1, 33), (2, 1, 3, 1, 33), (64, 32, 1, 1, 33), (20, 12, 16, 1, 33), (20, 12, 5, 0, 33)]
+CASES += G.CASES + G.LARGE                                   # the geometry classes of tests/chain_geometries.py
 RUNS = [c + ("default",) for c in CASES] + [C3 + (100, "fp32")]
 L_STEPS = 3
 # step size by nz, chosen on the CPU from the float64 restatement alone (tests/hmc_restated.py, L = 3)
 STEP = {128: 0.8, 126: 0.84, 100: 0.9, 64: 1.0, 20: 1.0, 8: 1.2, 2: 0.48}
+# The geometries of tests/chain_geometries.py are keyed whole (nz 66 and 128 occur with two widths), chosen the same way: Case.rate of
+# the two-trajectory case of 33 rows scanned over s = 0.30, 0.35, ... 1.50; the step whose rate is nearest one half (the smaller of
+# two).  At nz >= 124 the rate falls from 0.9 to nothing within 0.2 of step size.  Rates found, in the table's order: 0.39 / 0.36 /
+# 0.64 / 0.62 / 0.61 / 0.38 / 0.50 / 0.62 / 0.68 (profiles/chain_geometries.txt).
+STEP_GEO = {(62, 31, 2, 1): 1.05, (66, 33, 2, 1): 1.05, (124, 63, 3, 1): 0.8, (66, 33, 3, 0): 0.95, (10, 40, 2, 1): 1.25, (70, 8, 2, 1): 1.05,
+            (12, 100, 2, 1): 1.2, (66, 65, 2, 1): 1.0, (128, 128, 2, 1): 0.8}
 # seed offset of a case's generator, to be chosen on the CPU (float64 / float32 restatements alone) should the default draws leave a
 # two-trajectory case outside 15 % .. 85 % (B = 1 has two decisions: exactly one must accept) or set aside more rows than allowed
 # (Case asserts the latter): none needed with the steps above
@@ -41,8 +50,8 @@ STEP_L1 = {128: 0.9, 8: 1.2}                                 # L = 1 against mal
 QUAD_SCALE = {2: 2.0}                                        # (tests/test_gpu_mala.py: at nz = 2 the u_acc bound needs an energy of order 1)
 
 
-def step_of(nz):
-    return float(np.float32(STEP[nz]))                       # the fp32 step the kernel sees
+def step_of(nz, geo=None):
+    return float(np.float32(STEP_GEO[geo] if geo in STEP_GEO else STEP[nz]))      # the fp32 step the kernel sees
 
 
 @pytest.fixture(scope="module")
@@ -69,7 +78,7 @@ class Case:
         self.geo, self.B, self.nz, self.depth = (nz, w, depth, coupling), B, nz, depth
         p = O.init_params(nz, w, depth, seed=3)
         self.p = K.additive(p) if coupling == 0 else p
-        self.s, self.L = step_of(nz), L_STEPS
+        self.s, self.L = step_of(nz, self.geo), L_STEPS
         self.n_traj = 2 if B <= 100 else 1
         self.quad = H.Quadratic(nz, QUAD_SCALE.get(nz, 0.1), seed=7 + nz)
         g = torch.Generator().manual_seed(7 + B + SEED.get(self.geo + (B,), 0))
@@ -249,6 +258,8 @@ def test_every_call_follows_float64(lsnf, gpu_device, math, nz, w, depth, coupli
 
 
 SMALL = [C3 + (33,), C3 + (4100,), C3 + (8200,), TINY + (33,)]
+PHILOX_CASES = SMALL + G.CASES                               # the in-kernel draw against the tensor form
+FORMS = SMALL + G.FORMS                                      # in place, 4 bytes off, NULL optionals
 
 
 def end_call(c):
@@ -346,7 +357,7 @@ def test_a_trajectory_is_reversible_on_the_device(lsnf, gpu_device, nz, w, depth
 # ---------------------------------------------------------------------------------------------
 # 4. bit identities
 # ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("nz,w,depth,coupling,B", SMALL)
+@pytest.mark.parametrize("nz,w,depth,coupling,B", PHILOX_CASES)
 def test_philox_is_the_tensors_of_the_same_draws(lsnf, gpu_device, nz, w, depth, coupling, B):
     s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B)
     F, dev, c = lsnf.flow, gpu_device, s.c
@@ -356,7 +367,15 @@ def test_philox_is_the_tensors_of_the_same_draws(lsnf, gpu_device, nz, w, depth,
             xi = F.sample(s.plan, B, rng, want_eps=True)[2]
             u = None if r.phase == "init" else torch.from_numpy(H.uniform_draws(B, 1234, 40, row0)).to(dev)
             got, ref = run(lsnf, s, r, rng, None, propose=True), run(lsnf, s, r, xi, u, propose=True)
+            # kin0 is 1/2 sum xi^2 over the nz real columns: the draw of a padding column (a half that is no multiple of 4) is not in it
+            x64 = xi.cpu().double()
+            kin64, kin32 = 0.5 * (x64 ** 2).sum(1), 0.5 * (xi.cpu() ** 2).sum(1)
+            bound, _ = widened(1e-5 * kin64, (kin32.double() - kin64).abs())              # Case's kin_bound, at these draws
+            kin_err = (got[0].kin.cpu().double() - kin64).abs()
+            print(f"[hmc] {c.geo} B{B} {r.phase} row0 {row0}: in-kernel draw, worst kin0 error / bound = {fig(kin_err / bound):.3f}, "
+                  f"kin0 the tensor form's bits: {bits(got[0].kin, ref[0].kin)}")
             assert same(got, ref)
+            assert xi.shape == (B, nz) and bool((kin_err <= bound).all())
             assert r.phase == "init" or 0 < int(got[1][1].sum()) < B or B < 8      # both outcomes occur
         assert rng.offset == 40                                             # the call does not advance the generator
         ctr = torch.full((1,), 3, dtype=torch.int64, device=dev)
@@ -373,7 +392,7 @@ def test_philox_is_the_tensors_of_the_same_draws(lsnf, gpu_device, nz, w, depth,
 
 # (64 rows per workgroup; the <1, 1> geometry at 32 and at 64 rows; f_width > 64 at 32 rows, its largest shape: with the cases above,
 # every instantiation of lsnf_small3_hmc_kernel that the default dispatch can reach)
-@pytest.mark.parametrize("nz,w,depth,coupling,B", [C3 + (8200,), TINY + (4100,), TINY + (8200,), C5 + (4100,)])
+@pytest.mark.parametrize("nz,w,depth,coupling,B", [C3 + (8200,), TINY + (4100,), TINY + (8200,), C5 + (4100,)] + G.LARGE)
 def test_rows_do_not_depend_on_the_batch_or_the_sharding(lsnf, gpu_device, nz, w, depth, coupling, B):
     s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B)
     F, c = lsnf.flow, s.c
@@ -396,7 +415,7 @@ def test_rows_do_not_depend_on_the_batch_or_the_sharding(lsnf, gpu_device, nz, w
             assert not bits(wrong[1][0], part[1][0][40:100])
 
 
-@pytest.mark.parametrize("nz,w,depth,coupling,B", SMALL)
+@pytest.mark.parametrize("nz,w,depth,coupling,B", FORMS)
 def test_in_place_and_four_bytes_off_a_16_byte_boundary(lsnf, gpu_device, nz, w, depth, coupling, B):
     s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B)
     F, dev, c = lsnf.flow, gpu_device, s.c
@@ -436,7 +455,7 @@ def test_in_place_and_four_bytes_off_a_16_byte_boundary(lsnf, gpu_device, nz, w,
         F.hmc_step(s.plan, zp, r.ge.float().to(dev), r.e.float().to(dev), F.HmcState(zp, st.grad, st.energy, st.mom, st.kin), noise, c.s, uniform=u)
 
 
-@pytest.mark.parametrize("nz,w,depth,coupling,B", SMALL)
+@pytest.mark.parametrize("nz,w,depth,coupling,B", FORMS)
 def test_null_gradient_and_energy_are_zeros(lsnf, gpu_device, nz, w, depth, coupling, B):
     s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B)
     F, dev, c = lsnf.flow, gpu_device, s.c

@@ -9,7 +9,8 @@ CPU (oracle.smooth_batch's rule, mala_restated.smooth_proposal), so the kink all
 (the project's log-prob / dz gate on the terms summed; the rule of tests/test_gpu_reverse_autograd.py, computed here on the CPU).
 Rows whose float64 log_alpha is within the gate of ln u, and rows with oracle.relu_margin(p, z_prop) <= 2e-5, are set aside (at most
 10 % of a case, 2 rows for B <= 33: asserted).  Step sizes are chosen so that the float64 chain accepts between 15 % and 85 % of its
-decisions (asserted for the 3-step cases).  Everything else is bit identity between call forms."""
+decisions (asserted for the 3-step cases).  Everything else is bit identity between call forms.  The geometry classes of
+tests/chain_geometries.py (ragged halves, whole tiles of padding) are appended to the case lists, under the same gates."""
 import functools
 
 import numpy as np
@@ -17,6 +18,7 @@ import pytest
 import torch
 
 from oracle import flow_oracle as O
+import chain_geometries as G
 import mala_restated as M
 import test_gpu_reverse_keep as K
 from test_gpu_langevin import ToyG
@@ -29,10 +31,20 @@ C3, C5, TINY = K.C3, K.C5, K.TINY
 # 16, additive.
 CASES = [C3 + (B,) for B in (1, 17, 33, 100, 4100, 8200, 16400)] + \
         [TINY + (33,), C5 + (33,), (126, 127, 2, 1, 33), (2, 1, 3, 1, 33), (64, 32, 1, 1, 33), (20, 12, 16, 1, 33), (20, 12, 5, 0, 33)]
+# ... and the geometry classes of tests/chain_geometries.py: every instantiation at a ragged half, with a whole tile of padding, with
+# none; two of them at 32 and 64 rows per workgroup (single calls)
+CASES += G.CASES + G.LARGE
 RUNS = [c + ("default",) for c in CASES] + [C3 + (100, "fp32")]
+PHILOX_CASES = [C3 + (33,), C3 + (4100,), C3 + (8200,), TINY + (33,)] + G.CASES          # the in-kernel draw against the tensor form
 # step size by nz, chosen on the CPU from the float64 restatement alone (tests/mala_restated.py): between a quarter and three quarters
 # of the decisions accepted (at the reference's 0.1 everything is accepted, which shows nothing)
 STEP = {128: 0.9, 126: 0.85, 100: 0.9, 64: 1.0, 20: 1.1, 8: 1.2, 2: 0.5}
+# The geometries of tests/chain_geometries.py are keyed whole (nz 66 and 128 occur with two widths), chosen the same way: the 3-step
+# float64 chain of 33 rows (Case.rate) scanned over s = 0.30, 0.35, ... 1.50; the step whose rate is nearest one half (the smaller
+# of two), no step setting aside more than its 2 rows.  Rates found, in the table's order: 0.48 / 0.58 / 0.56 / 0.53 / 0.49 / 0.44 /
+# 0.49 / 0.46 / 0.44 (profiles/chain_geometries.txt).
+STEP_GEO = {(62, 31, 2, 1): 1.0, (66, 33, 2, 1): 1.0, (124, 63, 3, 1): 0.85, (66, 33, 3, 0): 0.95, (10, 40, 2, 1): 1.2, (70, 8, 2, 1): 1.1,
+            (12, 100, 2, 1): 1.15, (66, 65, 2, 1): 1.05, (128, 128, 2, 1): 0.85}
 
 
 # scale of the quadratic's A = scale * randn.  u_acc is held to 1e-5 * (|e| + |ll|); at nz = 2 ll = -|z1|^2 / 2 + log 2 pi + logdet crosses
@@ -42,8 +54,8 @@ STEP = {128: 0.9, 126: 0.85, 100: 0.9, 64: 1.0, 20: 1.1, 8: 1.2, 2: 0.5}
 QUAD_SCALE = {2: 2.0}
 
 
-def step_of(nz):
-    return float(np.float32(STEP[nz]))                       # the fp32 step the kernel sees
+def step_of(nz, geo=None):
+    return float(np.float32(STEP_GEO[geo] if geo in STEP_GEO else STEP[nz]))      # the fp32 step the kernel sees
 
 
 @pytest.fixture(scope="module")
@@ -60,7 +72,7 @@ class Case:
         self.geo, self.B, self.nz, self.depth = (nz, w, depth, coupling), B, nz, depth
         p = O.init_params(nz, w, depth, seed=3)
         self.p = K.additive(p) if coupling == 0 else p
-        self.s = step_of(nz)
+        self.s = step_of(nz, self.geo)
         self.n_steps = 3 if B <= 100 else 1
         self.quad = M.Quadratic(nz, QUAD_SCALE.get(nz, 0.1), seed=7 + nz)
         g = torch.Generator().manual_seed(7 + B)
@@ -213,7 +225,7 @@ def run(lsnf, s, st, noise, uniform=None, rows=slice(None), **kw):
     return state, out
 
 
-@pytest.mark.parametrize("nz,w,depth,coupling,B", [C3 + (33,), C3 + (4100,), C3 + (8200,), TINY + (33,)])
+@pytest.mark.parametrize("nz,w,depth,coupling,B", PHILOX_CASES)
 def test_philox_is_the_tensors_of_the_same_draws(lsnf, gpu_device, nz, w, depth, coupling, B):
     s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B)
     F, dev, st = lsnf.flow, gpu_device, s.c.steps[0]
@@ -238,7 +250,15 @@ def test_philox_is_the_tensors_of_the_same_draws(lsnf, gpu_device, nz, w, depth,
 # 4. a row's result does not depend on the batch, the workgroup shape or the sharding
 # ---------------------------------------------------------------------------------------------
 def test_rows_do_not_depend_on_the_batch_or_the_sharding(lsnf, gpu_device):
-    s = setup_of(lsnf, gpu_device, *C3, 8200)                # 64 rows per workgroup
+    rows_are_their_own(lsnf, setup_of(lsnf, gpu_device, *C3, 8200))                # 64 rows per workgroup
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", G.LARGE)      # 32 rows per workgroup at a ragged half, 64 at an empty half-tile
+def test_rows_do_not_depend_on_the_workgroup_shape_at_a_ragged_half(lsnf, gpu_device, nz, w, depth, coupling, B):
+    rows_are_their_own(lsnf, setup_of(lsnf, gpu_device, nz, w, depth, coupling, B))
+
+
+def rows_are_their_own(lsnf, s):
     F, st = lsnf.flow, s.c.steps[0]
     rng = F.PhiloxNoise(99, 7, 0)
     whole = run(lsnf, s, st, rng)
@@ -257,7 +277,7 @@ def test_rows_do_not_depend_on_the_batch_or_the_sharding(lsnf, gpu_device):
 # ---------------------------------------------------------------------------------------------
 # 5. in place, 4-byte offsets, NULL grad_g / energy_g
 # ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("nz,w,depth,coupling,B", [C3 + (33,), C3 + (4100,), C3 + (8200,), TINY + (33,), (126, 127, 2, 1, 33), (64, 32, 1, 1, 33)])
+@pytest.mark.parametrize("nz,w,depth,coupling,B", [C3 + (33,), C3 + (4100,), C3 + (8200,), TINY + (33,), (126, 127, 2, 1, 33), (64, 32, 1, 1, 33)] + G.FORMS)
 def test_next_proposal_over_the_proposal(lsnf, gpu_device, nz, w, depth, coupling, B):
     s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B)
     F, dev, st = lsnf.flow, gpu_device, s.c.steps[0]
@@ -271,7 +291,7 @@ def test_next_proposal_over_the_proposal(lsnf, gpu_device, nz, w, depth, couplin
         F.mala_step(s.plan, zp, st.ge.float().to(dev), st.e.float().to(dev), F.MalaState(zp, state.grad, state.energy), noise, s.c.s)
 
 
-@pytest.mark.parametrize("nz,w,depth,coupling,B", [C3 + (33,), C3 + (4100,), TINY + (33,)])
+@pytest.mark.parametrize("nz,w,depth,coupling,B", [C3 + (33,), C3 + (4100,), TINY + (33,)] + G.FORMS)
 def test_every_tensor_four_bytes_off_a_16_byte_boundary(lsnf, gpu_device, nz, w, depth, coupling, B):
     s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B)
     F, dev, st = lsnf.flow, gpu_device, s.c.steps[0]
@@ -289,7 +309,7 @@ def test_every_tensor_four_bytes_off_a_16_byte_boundary(lsnf, gpu_device, nz, w,
     assert same((state, out), ref)
 
 
-@pytest.mark.parametrize("nz,w,depth,coupling,B", [C3 + (100,), TINY + (33,)])
+@pytest.mark.parametrize("nz,w,depth,coupling,B", [C3 + (100,), TINY + (33,)] + G.FORMS)
 def test_null_gradient_and_energy_are_zeros(lsnf, gpu_device, nz, w, depth, coupling, B):
     s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B)
     F, dev, st = lsnf.flow, gpu_device, s.c.steps[0]

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from oracle.philox_oracle import langevin_noise
+import chain_geometries as G
 import reverse_restated as R
 import test_gpu_reverse_keep as K
 
@@ -22,6 +23,8 @@ C3, C5, TINY, C1 = K.C3, K.C5, K.TINY, K.C1
 # ragged); 16 400 (a second round of workgroups).  Then HT = 1, WT = 4, odd sizes, the smallest geometry, depth 1 and 16, additive.
 CASES = [C3 + (B,) for B in (1, 17, 33, 100, 4100, 8200, 16400)] + \
         [TINY + (33,), C5 + (33,), (126, 127, 2, 1, 33), (2, 1, 3, 1, 33), (64, 32, 1, 1, 33), (20, 12, 16, 1, 33), (20, 12, 5, 0, 33)]
+CASES += G.CASES + G.LARGE                                 # the geometry classes of tests/chain_geometries.py
+PHILOX_CASES = [C3 + (33,), C3 + (4100,), C3 + (8200,), TINY + (33,)] + G.CASES         # the in-kernel draw against the tensor form
 RUNS = [c + ("default",) for c in CASES] + [C3 + (100, "fp32")]
 STEP = float(np.float32(0.1))                              # the fp32 step the kernel sees
 
@@ -124,7 +127,7 @@ def test_update_arithmetic(lsnf, gpu_device, nz, w, depth, coupling, B, mode):
 # ---------------------------------------------------------------------------------------------
 # 3. Philox: the in-kernel draw is lsnf_sample's eps at temperature 1, through the same instructions
 # ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("nz,w,depth,coupling,B", [C3 + (33,), C3 + (4100,), C3 + (8200,), TINY + (33,)])
+@pytest.mark.parametrize("nz,w,depth,coupling,B", PHILOX_CASES)
 def test_philox_is_the_tensor_of_the_same_draw(lsnf, gpu_device, nz, w, depth, coupling, B):
     s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B)
     F = lsnf.flow
@@ -172,11 +175,19 @@ def test_row_sharding_with_row0(lsnf, gpu_device):
 # 4. a row's result does not depend on the batch size or the workgroup shape
 # ---------------------------------------------------------------------------------------------
 def test_rows_do_not_depend_on_the_workgroup_shape(lsnf, gpu_device):
-    s = setup_of(lsnf, gpu_device, *C3, 8200)                # 64 rows per workgroup
+    rows_are_their_own(lsnf, setup_of(lsnf, gpu_device, *C3, 8200), (100, 4100))         # 64 rows per workgroup against 16 and 32
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", G.LARGE)      # 32 rows per workgroup at a ragged half, 64 at an empty half-tile
+def test_rows_do_not_depend_on_the_workgroup_shape_at_a_ragged_half(lsnf, gpu_device, nz, w, depth, coupling, B):
+    rows_are_their_own(lsnf, setup_of(lsnf, gpu_device, nz, w, depth, coupling, B), [n for n in (100, 4100) if n < B])
+
+
+def rows_are_their_own(lsnf, s, smaller):
     F = lsnf.flow
     rng = F.PhiloxNoise(99, 7, 0)
     whole = s.step(lsnf, rng, want_g=True)
-    for n in (100, 4100):                                   # 16 and 32 rows per workgroup
+    for n in smaller:
         e, saved, act, gx = shard(lsnf, s, 0, n)
         part = F.reverse_langevin_step(s.plan, e, saved, act, gx, rng, STEP, want_g=True)
         for a, b in zip(whole, part):
@@ -209,7 +220,7 @@ def test_norms(lsnf, gpu_device, math, nz, w, depth, coupling, B, mode):
 # ---------------------------------------------------------------------------------------------
 # 6. in place, the scalar path, g_eps over grad_g
 # ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("nz,w,depth,coupling,B", [C3 + (33,), C3 + (4100,), C3 + (8200,), TINY + (33,), (126, 127, 2, 1, 33), (64, 32, 1, 1, 33)])
+@pytest.mark.parametrize("nz,w,depth,coupling,B", [C3 + (33,), C3 + (4100,), C3 + (8200,), TINY + (33,), (126, 127, 2, 1, 33), (64, 32, 1, 1, 33)] + G.FORMS)
 def test_in_place_and_aliases(lsnf, gpu_device, nz, w, depth, coupling, B):
     s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B)
     F = lsnf.flow
@@ -235,7 +246,7 @@ def test_in_place_and_aliases(lsnf, gpu_device, nz, w, depth, coupling, B):
         F.reverse_langevin_step(s.plan, s.e, s.saved, s.act, s.gx, s.noise, STEP, inplace=True, out=(torch.empty_like(s.e), None, None, None))
 
 
-@pytest.mark.parametrize("nz,w,depth,coupling,B", [C3 + (33,), C3 + (4100,), TINY + (33,)])
+@pytest.mark.parametrize("nz,w,depth,coupling,B", [C3 + (33,), C3 + (4100,), TINY + (33,)] + G.FORMS)
 def test_every_tensor_four_bytes_off_a_16_byte_boundary(lsnf, gpu_device, nz, w, depth, coupling, B):
     s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B)
     dev, F = gpu_device, lsnf.flow

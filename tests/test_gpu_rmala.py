@@ -20,6 +20,7 @@ import pytest
 import torch
 
 from oracle import flow_oracle as O
+import chain_geometries as G
 import mala_restated as M
 import rmala_restated as RM
 import test_gpu_mala as ZM
@@ -29,7 +30,8 @@ from test_gpu_langevin import ToyG
 pytestmark = pytest.mark.gpu
 
 C3, C5, TINY = K.C3, K.C5, K.TINY
-RUNS = [c + ("default",) for c in ZM.CASES] + [C3 + (100, "fp32")]
+RUNS = [c + ("default",) for c in ZM.CASES] + [C3 + (100, "fp32")]            # (with the geometry classes of tests/chain_geometries.py)
+PHILOX_CASES = [C3 + (33,), C3 + (4100,), C3 + (8200,), TINY + (33,)] + G.CASES   # the in-kernel draw against the tensor form
 # Step size by nz, chosen on the CPU from the float64 restatement alone: tests/rmala_restated.py's 3-step chain of 33 rows (Case.rate)
 # scanned over s = 0.3, 0.4, ... 2.1 and then in steps of 0.05 around the step at which about half of the decisions are accepted.  The
 # z-space table of tests/test_gpu_mala.py does not carry over: there 0.9 serves nz 128, here 0.9 accepts nothing at nz >= 100 and the
@@ -40,10 +42,16 @@ STEP = {128: 0.5, 100: 0.55, 126: 0.65, 64: 0.9, 20: 0.4, 8: 1.0, 2: 1.7}
 # nz = 20 comes in two flows, and no one step serves both: depth 16 accepts 0.51 at s = 0.4 and 0.10 at 0.55, the additive depth-5
 # flow still 0.90 at 0.5 and 0.82 at 0.7.  The additive geometry gets its own entry.
 STEP_GEO = {(20, 12, 5, 0): 0.7}
+# The geometries of tests/chain_geometries.py are keyed whole (nz 66 and 128 occur with two widths): Case.rate at 33 rows scanned over
+# s = 0.30, 0.35, ... 1.50; the step whose rate is nearest one half (the smaller of two), no step setting aside more than its 2 rows.
+# Rates found, in the table's order: 0.52 / 0.49 / 0.57 / 0.51 / 0.51 / 0.60 / 0.54 / 0.56 / 0.34 (at (128, 128) 0.65 still accepts
+# 0.66; profiles/chain_geometries.txt).
+STEP_GEO.update({(62, 31, 2, 1): 0.8, (66, 33, 2, 1): 0.8, (124, 63, 3, 1): 0.6, (66, 33, 3, 0): 0.85, (10, 40, 2, 1): 1.25, (70, 8, 2, 1): 0.85,
+                 (12, 100, 2, 1): 1.1, (66, 65, 2, 1): 0.8, (128, 128, 2, 1): 0.7})
 
 
 def step_of(nz, geo=None):
-    return float(np.float32(STEP_GEO.get(geo, STEP[nz])))    # the fp32 step the kernel sees
+    return float(np.float32(STEP_GEO[geo] if geo in STEP_GEO else STEP[nz]))      # the fp32 step the kernel sees
 
 
 @pytest.fixture(scope="module")
@@ -221,7 +229,7 @@ def test_init_form_is_the_plain_step(lsnf, gpu_device, nz, w, depth, coupling, B
 # ---------------------------------------------------------------------------------------------
 # 3. PhiloxNoise against the tensors of the same draws
 # ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("nz,w,depth,coupling,B", [C3 + (33,), C3 + (4100,), C3 + (8200,), TINY + (33,)])
+@pytest.mark.parametrize("nz,w,depth,coupling,B", PHILOX_CASES)
 def test_philox_is_the_tensors_of_the_same_draws(lsnf, gpu_device, nz, w, depth, coupling, B):
     s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B)
     F, dev, st = lsnf.flow, gpu_device, s.c.steps[0]
@@ -246,12 +254,20 @@ def test_philox_is_the_tensors_of_the_same_draws(lsnf, gpu_device, nz, w, depth,
 # 4. a row's result does not depend on the batch, the workgroup shape or the sharding
 # ---------------------------------------------------------------------------------------------
 def test_rows_do_not_depend_on_the_batch_or_the_sharding(lsnf, gpu_device):
-    s = setup_of(lsnf, gpu_device, *C3, 8200)
+    rows_are_their_own(lsnf, setup_of(lsnf, gpu_device, *C3, 8200), (slice(0, 8200), slice(0, 4100)))
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", G.LARGE)      # 32 rows per workgroup at a ragged half, 64 at an empty half-tile
+def test_rows_do_not_depend_on_the_workgroup_shape_at_a_ragged_half(lsnf, gpu_device, nz, w, depth, coupling, B):
+    rows_are_their_own(lsnf, setup_of(lsnf, gpu_device, nz, w, depth, coupling, B), [slice(0, n) for n in sorted({B, 4100})])
+
+
+def rows_are_their_own(lsnf, s, larger):
     F, st = lsnf.flow, s.c.steps[0]
     rng = F.PhiloxNoise(99, 7, 0)
     flat = lambda r: (r[0].z, r[0].grad, r[0].energy) + tuple(r[2])
     part = run(lsnf, s, st, rng, rows=slice(0, 100))                    # 16 rows per workgroup
-    for rows in (slice(0, 8200), slice(0, 4100)):                       # 64 (ST = 4) and 32 (ST = 2) rows per workgroup
+    for rows in larger:                                                 # 64 (ST = 4) and 32 (ST = 2) rows per workgroup
         for a, b in zip(flat(run(lsnf, s, st, rng, rows=rows)), flat(part)):
             assert bits(a[:100], b)
     lo = run(lsnf, s, st, F.PhiloxNoise(99, 7, 0), rows=slice(0, 40))
@@ -277,7 +293,7 @@ def test_stash_of_the_reverse_and_of_the_forward_decide_alike(lsnf, gpu_device, 
     assert bool(((kept[2][2].cpu().double() - fwd[2][2].cpu().double()).abs() <= 2.0 * st.gate)[st.smooth].all())
 
 
-@pytest.mark.parametrize("nz,w,depth,coupling,B", [C3 + (33,), C3 + (4100,), C3 + (8200,), TINY + (33,), (126, 127, 2, 1, 33), (64, 32, 1, 1, 33)])
+@pytest.mark.parametrize("nz,w,depth,coupling,B", [C3 + (33,), C3 + (4100,), C3 + (8200,), TINY + (33,), (126, 127, 2, 1, 33), (64, 32, 1, 1, 33)] + G.FORMS)
 def test_next_proposal_over_the_proposal(lsnf, gpu_device, nz, w, depth, coupling, B):
     s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B)
     F, dev, st = lsnf.flow, gpu_device, s.c.steps[0]
@@ -293,7 +309,7 @@ def test_next_proposal_over_the_proposal(lsnf, gpu_device, nz, w, depth, couplin
         F.reverse_mala_step(s.plan, ep, saved, act, cast(st.ge), cast(st.e), F.MalaState(ep, state.grad, state.energy), noise, s.c.s)
 
 
-@pytest.mark.parametrize("nz,w,depth,coupling,B", [C3 + (33,), C3 + (4100,), TINY + (33,)])
+@pytest.mark.parametrize("nz,w,depth,coupling,B", [C3 + (33,), C3 + (4100,), TINY + (33,)] + G.FORMS)
 def test_every_tensor_four_bytes_off_a_16_byte_boundary(lsnf, gpu_device, nz, w, depth, coupling, B):
     s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B)
     F, dev, st = lsnf.flow, gpu_device, s.c.steps[0]
@@ -314,7 +330,7 @@ def test_every_tensor_four_bytes_off_a_16_byte_boundary(lsnf, gpu_device, nz, w,
     assert same((state, None, out), ref)
 
 
-@pytest.mark.parametrize("nz,w,depth,coupling,B", [C3 + (100,), TINY + (33,)])
+@pytest.mark.parametrize("nz,w,depth,coupling,B", [C3 + (100,), TINY + (33,)] + G.FORMS)
 def test_null_gradient_and_energy_are_zeros(lsnf, gpu_device, nz, w, depth, coupling, B):
     s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B)
     F, dev, st = lsnf.flow, gpu_device, s.c.steps[0]

@@ -293,7 +293,7 @@ def test_mala_steps_follow_float64(got, child):
             continue
         n += 1
         T = ZM if probe == "s.mala" else RMt
-        c = T.case(*W.GEOS[geo], B)
+        c = T.case(*W.geo_of(geo), B)
         st = c.steps[0]
         la, acc = _t(a["la"]).double(), _t(a["acc"])
         za, ga, ua, nxt = _t(a["state_z"]), _t(a["state_grad"]), _t(a["state_energy"]), _t(a["z_next"])

@@ -41,6 +41,27 @@ def test_rows_per_workgroup_follow_the_knob_value():
     assert [B % 4096 for B in W.tn_rows({"LSNF_TN_CHUNK": "4096"})[1]] == [0, 1, 17]
 
 
+def test_the_mala_probes_meet_a_ragged_half_and_an_empty_half_tile():
+    """The forced LSNF_SMALL3_ST forms of the two MALA kernels run entries of tests/chain_geometries.py too: a ragged half and a
+    second half-tile that is entirely padding, under every ST (both are <2, 2>, which has all three), at the batch sizes of the
+    other MALA probes.  They are not in GEOS: its sorted order seeds the inputs of every other probe."""
+    import chain_geometries as G
+    assert not set(W.CHAIN_GEOS) & set(W.GEOS) and set(W.MALA_GEOS) == {"C3", "C5", "tiny"} | set(W.CHAIN_GEOS)
+    geos = set(W.CHAIN_GEOS.values())
+    assert geos <= set(G.GEOS) and all(G.pick_tiles(nz // 2, w) == (2, 2) for nz, w, _, _ in geos)
+    assert any(G.draw_straddles(g) and not G.second_half_tile_empty(g) for g in geos) and any(G.second_half_tile_empty(g) for g in geos)
+    for name in W.MALA_GEOS:
+        assert W.geo_of(name) == (W.GEOS[name] if name in W.GEOS else W.CHAIN_GEOS[name])
+    sts = set()
+    for name in W.CHAIN_GEOS:
+        for _, env in W.CHILDREN:
+            if "small3" in W.groups_of(env):
+                want, runs = W.small3_st(env, name)
+                assert want == runs and {1, 17, 97} <= set(W.mala_rows(env, name))
+                sts.add(runs)
+    assert sts == {1, 2, 4}
+
+
 def test_the_latency_shapes_of_the_table_are_those_the_recorded_run_launched():
     """small3_st restates the give-way rule of lsnf_small3_*_st (a shape that is not built, or whose LDS does not fit, gives way to
     the next smaller one).  profiles/shape_forms_kernel_calls.csv is what the module's children really launched: per latency kernel
