@@ -114,7 +114,57 @@
  *   grad_acc, u_acc, mom, kin0, z_next, accept_out, log_alpha_out) may alias anything the call reads, or another output
  * One kernel (lsnf_small3_hmc_kernel) under every lsnf_set_math_mode, for every B and every phase, independent of
  * lsnf_set_small_batch_max; a row's bits do not depend on B, the workgroup shape or rng->row0 sharding.  B = 0 succeeds without a
- * launch.  Every refusal is LSNF_E_ARG / LSNF_E_GEOMETRY, made before any HIP call. */
+ * launch.  Every refusal is LSNF_E_ARG / LSNF_E_GEOMETRY, made before any HIP call.
+ *
+ * ---- Hamiltonian Monte Carlo in the flow's base space (lsnf_reverse_hmc_step) ------------------------------------------------------
+ * The target and the gradient of lsnf_reverse_mala_step -- pi(eps) ~ exp(-U(eps)), U(eps) = |eps|^2 / 2 + energy_g, grad U = eps + g,
+ * g = J_{f^-1}(eps)^T grad_g with the bits of lsnf_reverse_backward_z(g_x = grad_g, g_objective = NULL) -- with a momentum p ~ N(0, I):
+ * the flow has whitened the prior, so the identity mass matrix is the right one.  eps_prop / z_saved / act_saved are the reverse's
+ * input, the block outputs and the stash AT x = f^-1(eps_prop) (lsnf_reverse_keep, lsnf_forward at x or lsnf_restash); the caller's
+ * generator runs between the reverse and this ONE launch, which finishes the work at the point eps_prop of a trajectory and produces
+ * the next point.  From a state (e_s, t_s = grad U(e_s), u_s = U(e_s)), every line in fp32 with the operations and the order written,
+ * no fused multiply-add (hs = 0.5f * s: exact); in every phase that forms a gradient t_prop = eps_prop + g is ONE fp32 add
+ * (lsnf_reverse_mala_step's t_prop: grad_acc has that function's bits):
+ *   begin  (inside the call that owns the state: LSNF_HMC_INIT, or an end call with eps_next)
+ *           kin0 = 0.5f * sum_c xi^2;   ph = xi - hs * t_s;   eps_next = e_s + s * ph;   mom <- ph
+ *   inner  (LSNF_HMC_INNER, the calls at eps_1 .. eps_{L-1})
+ *           ph = mom - s * t_prop;   eps_next = eps_prop + s * ph;   mom <- ph
+ *   end    (flags 0, the call at eps_L)
+ *           U_prop = energy_g + 0.5f * sum_c eps_prop^2;   pL = mom - hs * t_prop;   kinL = 0.5f * sum_c pL^2
+ *           log_alpha = (u_acc - U_prop) + (kin0 - kinL)
+ *           accept iff ln(u) < log_alpha        (a NaN log_alpha rejects, +inf accepts)
+ *           accepted rows: eps_acc <- eps_prop, grad_acc <- t_prop, u_acc <- U_prop;  rejected rows keep their state bits
+ *           eps_next given: begin the next trajectory from the (updated) state;  eps_next NULL: mom <- pL (the full-step momentum at
+ *           the proposal is left readable), nothing else is proposed and kin0 is left as it is
+ * The sums over a row's columns: sum eps_prop^2 in lsnf_reverse_mala_step's order (an LSNF_HMC_INIT call writes that function's
+ * LSNF_MALA_INIT state -- eps_acc, grad_acc, u_acc -- bit for bit); sum pL^2 and sum xi^2 in lsnf_hmc_step's: a lane adds the squares
+ * of its 8 columns in column order, the wave reduction adds the lanes of a wave and the four waves' partials are added in wave order.
+ * A draw for a padding column is not counted.
+ * K trajectories of L steps are K L + 1 calls: one LSNF_HMC_INIT call at the chain's start (every row accepted, the state written
+ * without being read, log_alpha_out = +0, the first trajectory begun; without eps_next it writes the state alone and leaves mom and
+ * kin0 as they are), L - 1 LSNF_HMC_INNER calls per trajectory, K end calls, the last one with eps_next NULL.  With L = 1 there are no
+ * inner calls and the chain is lsnf_reverse_mala_step's in exact arithmetic (kinL = A / (2 s^2), kin0 = Bq / (2 s^2) in its notation).
+ *
+ *   the arguments shared with lsnf_reverse_mala_step follow its rules (eps_prop .. energy_g, eps_acc / grad_acc / u_acc, step_size,
+ *   accept_out, log_alpha_out, the 16-byte alignment of plan and act_saved and the 4-byte alignment of every tensor; act_saved is
+ *   required, z_saved for depth > 1), except as stated below -- the rules of lsnf_hmc_step, word for word where they apply
+ *   mom (B,nz): the momentum, read AND written by the same call (written only by INIT when eps_next is NULL);  kin0 (B): the kinetic
+ *       energy the running trajectory began with, written by a call that begins one, read by an end call.  Both are required
+ *   xi: a row of `noise` (B,nz), or lsnf_reverse_mala_step's LsnfRng draw (lsnf_sample's eps at temperature 1) at the call's (seed,
+ *       offset, global row, column)
+ *   u:  lsnf_mala_step's: `uniform` (B), or with rng word 0 of Philox at field value 2 of the noise's counter
+ *   flags: 0, LSNF_HMC_INIT or LSNF_HMC_INNER; both together and unknown bits are refused
+ *   an LSNF_HMC_INNER call draws and decides nothing: it requires eps_next, refuses noise, uniform and rng, wants accept_out and
+ *       log_alpha_out NULL, neither reads nor writes eps_acc, grad_acc, u_acc or kin0 (they are still required), and the library never
+ *       reads energy_g
+ *   INIT and end calls: rng and a tensor (noise or uniform) exclude each other; without rng, `noise` is required iff eps_next is
+ *       given and `uniform` is required unless LSNF_HMC_INIT
+ *   step_size: finite and non-zero
+ *   eps_next (B,nz) or NULL; may be eps_prop (a lane stores the columns it loaded, after the barrier).  No other output (eps_acc,
+ *   grad_acc, u_acc, mom, kin0, eps_next, accept_out, log_alpha_out) may alias anything the call reads, or another output
+ * One kernel (lsnf_small3_rhmc_kernel) under every lsnf_set_math_mode, for every B (more rounds of workgroups above 16 384 rows) and
+ * every phase, independent of lsnf_set_small_batch_max; a row's bits do not depend on B, the workgroup shape or rng->row0 sharding.
+ * B = 0 succeeds without a launch.  Every refusal is LSNF_E_ARG / LSNF_E_GEOMETRY, made before any HIP call. */
 #ifndef LSNF_FLOW_MCMC_H
 #define LSNF_FLOW_MCMC_H
 
@@ -145,6 +195,12 @@ int lsnf_hmc_step(const float* plan, int nz, int width, int depth, int coupling,
                   float* z_acc, float* grad_acc, float* u_acc, float* mom, float* kin0,
                   const float* noise, const float* uniform, const LsnfRng* rng, float step_size, unsigned flags,
                   float* z_next, float* accept_out, float* log_alpha_out, void* stream);
+int lsnf_reverse_hmc_step(const float* plan, int nz, int width, int depth, int coupling, int B,
+                          const float* eps_prop, const float* z_saved, const float* act_saved,
+                          const float* grad_g, const float* energy_g,
+                          float* eps_acc, float* grad_acc, float* u_acc, float* mom, float* kin0,
+                          const float* noise, const float* uniform, const LsnfRng* rng, float step_size, unsigned flags,
+                          float* eps_next, float* accept_out, float* log_alpha_out, void* stream);
 
 #ifdef __cplusplus
 }

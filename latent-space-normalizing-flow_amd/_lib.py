@@ -98,6 +98,11 @@ _EXT_SIGNATURES = {
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_void_p, ctypes.POINTER(LsnfRng), c_float, ctypes.c_uint,
                               c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lsnf_reverse_hmc_step": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, ctypes.POINTER(LsnfRng), c_float, ctypes.c_uint,
+                                      c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -173,8 +173,9 @@ LsnfRngArgs rng_args(const LsnfRng* r) {
     return r ? LsnfRngArgs{r->seed, r->offset, r->offset_dev, r->row0, 1} : LsnfRngArgs{0ull, 0ull, nullptr, 0ll, 0};
 }
 
-// ---- the rules of a Markov-chain step (lsnf_mala_step, lsnf_reverse_mala_step, lsnf_hmc_step), stated once: an entry point describes
-// its call -- its tensors under its own names -- and applies scalars(), its own rules, aliases(), the empty-batch return, pointers().
+// ---- the rules of a Markov-chain step (lsnf_mala_step, lsnf_reverse_mala_step, lsnf_hmc_step, lsnf_reverse_hmc_step), stated once: an
+// entry point describes its call -- its tensors under its own names -- and applies scalars(), its own rules (the two HMC entries:
+// phases()), aliases(), the empty-batch return, pointers().
 struct Named { const char* name; const void* p; };
 struct Needed { const char* name; const void* p; bool when = true; const char* why = "(NULL)"; };      // "<name> is required <why>", when `when`
 template <class T>
@@ -211,6 +212,16 @@ struct ChainStep {
         }
         return false;
     }
+    // the phases of a trajectory (LSNF_HMC_INIT, LSNF_HMC_INNER; `init` / `inner` above): an inner leapfrog step draws nothing and
+    // decides nothing
+    bool phases(Check& ck, const void* accept_out, const void* log_alpha_out) const {
+        return ck.refuse(init && inner, "flags: LSNF_HMC_INIT and LSNF_HMC_INNER exclude each other") ||
+               ck.refuse(inner && noise, "noise is not taken with LSNF_HMC_INNER (an inner step draws nothing)") ||
+               ck.refuse(inner && uniform, "uniform is not taken with LSNF_HMC_INNER (an inner step draws nothing)") ||
+               ck.refuse(inner && rng, "rng is not taken with LSNF_HMC_INNER (an inner step draws nothing)") ||
+               ck.refuse(inner && accept_out, "accept_out must be NULL with LSNF_HMC_INNER (an inner step decides nothing)") ||
+               ck.refuse(inner && log_alpha_out, "log_alpha_out must be NULL with LSNF_HMC_INNER (an inner step decides nothing)");
+    }
     bool pointers(Check& ck) const {
         for (const Needed& n : needed)
             if (ck.refuse(n.when && !n.p, "%s is required %s", n.name, n.why)) return true;
@@ -236,7 +247,7 @@ enum Kernel {
     K_NONE, K_FWD, K_FWD3, K_FWD3Q, K_FWD2H_FIXUP, K_SMALL_FWD, K_SMALL3_FWD,
     K_REV, K_REV3, K_REV2H_FIXUP, K_SMALL_REV, K_SMALL3_REV,
     K_BWD, K_BWD3, K_SMALL_BWD, K_SMALL3_BWD,
-    K_SMALL3_RBWD, K_SMALL3_RLV, K_SMALL3_MALA, K_SMALL3_RMALA, K_SMALL3_HMC,
+    K_SMALL3_RBWD, K_SMALL3_RLV, K_SMALL3_MALA, K_SMALL3_RMALA, K_SMALL3_HMC, K_SMALL3_RHMC,
 };
 const char* const kKernelName[] = {
     "no kernel takes this call", "lsnf_fwd_kernel", "lsnf_fwd3b_kernel", "lsnf_fwd3q_kernel",
@@ -245,7 +256,7 @@ const char* const kKernelName[] = {
     "lsnf_small3_rev_kernel",
     "lsnf_bwd_z_kernel", "lsnf_bwd3_kernel", "lsnf_small_bwd_kernel", "lsnf_small3_bwd_kernel",
     "lsnf_small3_rbwd_kernel", "lsnf_small3_rbwd_kernel (update form)", "lsnf_small3_mala_kernel", "lsnf_small3_rmala_kernel",
-    "lsnf_small3_hmc_kernel",
+    "lsnf_small3_hmc_kernel", "lsnf_small3_rhmc_kernel",
 };
 struct Pick { Kernel k; int st = 0; };     // st: rows per workgroup / 16 of the small3 kernels
 
@@ -446,6 +457,9 @@ Pick select_reverse_mala(const LsnfReverseMalaCall& c) { return {K_SMALL3_RMALA,
 // Hamiltonian Monte Carlo in z (lsnf_hmc_step) is the same backward with the leapfrog tail (lsnf_small3_hmc.hip): one kernel under
 // every math mode, batch size and phase of a trajectory, the workgroup shape of the plain backward of the call.
 Pick select_hmc(const LsnfHmcCall& c) { return {K_SMALL3_HMC, lsnf_small3_backward_st(c)}; }
+// Its base-space form (lsnf_reverse_hmc_step) is the reverse-backward with the leapfrog tail (lsnf_small3_rhmc.hip): one kernel under
+// every math mode, batch size and phase, the workgroup shape of the plain reverse-backward of the call.
+Pick select_reverse_hmc(const LsnfReverseHmcCall& c) { return {K_SMALL3_RHMC, lsnf_small3_reverse_backward_st(c)}; }
 
 // Batch contraction of the parameter gradients (LsnfContraction): on the bf16 matrix pipe where lsnf_params3.hip covers the
 // call (use_x3); from 4 096 rows the fp32-MFMA kernel through LDS, with the widest row loads the rows allow -- every row the
@@ -909,14 +923,7 @@ int lsnf_hmc_step(const float* plan, int nz, int width, int depth, int coupling,
                              {"z_next", z_next, inner, "(NULL) with LSNF_HMC_INNER"}};
     const ChainStep s = {reads, writes, /*next=*/&writes[3], /*point=*/&reads[1], needed, LSNF_HMC_INIT | LSNF_HMC_INNER, init, inner,
                          "LSNF_HMC_INIT or LSNF_HMC_INNER", plan, act_saved, noise, uniform, rng, step_size, flags};
-    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B) || s.scalars(ck) ||
-        ck.refuse(init && inner, "flags: LSNF_HMC_INIT and LSNF_HMC_INNER exclude each other") ||
-        // an inner leapfrog step draws nothing and decides nothing
-        ck.refuse(inner && noise, "noise is not taken with LSNF_HMC_INNER (an inner step draws nothing)") ||
-        ck.refuse(inner && uniform, "uniform is not taken with LSNF_HMC_INNER (an inner step draws nothing)") ||
-        ck.refuse(inner && rng, "rng is not taken with LSNF_HMC_INNER (an inner step draws nothing)") ||
-        ck.refuse(inner && accept_out, "accept_out must be NULL with LSNF_HMC_INNER (an inner step decides nothing)") ||
-        ck.refuse(inner && log_alpha_out, "log_alpha_out must be NULL with LSNF_HMC_INNER (an inner step decides nothing)") || s.aliases(ck))
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B) || s.scalars(ck) || s.phases(ck, accept_out, log_alpha_out) || s.aliases(ck))
         return ck.rc;
     if (ck.empty) return LSNF_OK;
     if (s.pointers(ck)) return ck.rc;
@@ -927,6 +934,37 @@ int lsnf_hmc_step(const float* plan, int nz, int width, int depth, int coupling,
     c.chain = {energy_g, uniform, z_acc, grad_acc, u_acc, accept_out, log_alpha_out, flags}; c.mom = mom; c.kin0 = kin0;
     const Pick p = select_hmc(c);
     return report(ck.entry, p, lsnf_launch_small3_hmc(c, p.st));
+}
+
+int lsnf_reverse_hmc_step(const float* plan, int nz, int width, int depth, int coupling, int B, const float* eps_prop,
+                          const float* z_saved, const float* act_saved, const float* grad_g, const float* energy_g, float* eps_acc,
+                          float* grad_acc, float* u_acc, float* mom, float* kin0, const float* noise, const float* uniform,
+                          const LsnfRng* rng, float step_size, unsigned flags, float* eps_next, float* accept_out, float* log_alpha_out,
+                          void* stream) {
+    Check ck{"lsnf_reverse_hmc_step"};
+    const Named reads[] = {{"plan", plan}, {"eps_prop", eps_prop}, {"z_saved", z_saved}, {"act_saved", act_saved}, {"grad_g", grad_g},
+                           {"energy_g", energy_g}, {"noise", noise}, {"uniform", uniform}};
+    // (mom is read and written by the same call: it is listed with the outputs, so it may be neither another input nor another output)
+    const Named writes[] = {{"eps_acc", eps_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc}, {"eps_next", eps_next}, {"accept_out", accept_out},
+                            {"log_alpha_out", log_alpha_out}, {"mom", mom}, {"kin0", kin0}};
+    const bool init = (flags & LSNF_HMC_INIT) != 0, inner = (flags & LSNF_HMC_INNER) != 0;
+    const Needed needed[] = {{"plan", plan}, {"eps_prop", eps_prop}, {"eps_acc", eps_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc},
+                             {"mom", mom}, {"kin0", kin0},
+                             {"act_saved", act_saved, true, "(the stash of lsnf_forward, lsnf_restash or lsnf_reverse_keep)"},
+                             {"z_saved", z_saved, depth > 1, "(NULL) for depth > 1"}, {"eps_next", eps_next, inner, "(NULL) with LSNF_HMC_INNER"}};
+    const ChainStep s = {reads, writes, /*next=*/&writes[3], /*point=*/&reads[1], needed, LSNF_HMC_INIT | LSNF_HMC_INNER, init, inner,
+                         "LSNF_HMC_INIT or LSNF_HMC_INNER", plan, act_saved, noise, uniform, rng, step_size, flags};
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B) || s.scalars(ck) || s.phases(ck, accept_out, log_alpha_out) || s.aliases(ck))
+        return ck.rc;
+    if (ck.empty) return LSNF_OK;
+    if (s.pointers(ck)) return ck.rc;
+    LsnfReverseHmcCall c;                // (no g_x / g_objective / g_z_in: the gradient at the point is consumed by the tail)
+    ck.head(c, plan, B, stream, {eps_prop, z_saved, grad_g, noise, eps_next, eps_acc, grad_acc, mom});
+    c.z_out = eps_prop; c.z_saved = z_saved; c.act_saved = act_saved;
+    c.grad_g = grad_g; c.noise = noise; c.step = step_size; c.eps_new = eps_next; c.rng = rng_args(rng);
+    c.chain = {energy_g, uniform, eps_acc, grad_acc, u_acc, accept_out, log_alpha_out, flags}; c.mom = mom; c.kin0 = kin0;
+    const Pick p = select_reverse_hmc(c);
+    return report(ck.entry, p, lsnf_launch_small3_reverse_hmc(c, p.st));
 }
 
 size_t lsnf_backward_params_workspace_floats(int nz, int width, int depth, int B) {

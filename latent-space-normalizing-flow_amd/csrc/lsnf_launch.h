@@ -73,6 +73,9 @@ struct LsnfReverseLangevinCall : LsnfReverseBackwardCall {      // lsnf_reverse_
 struct LsnfReverseMalaCall : LsnfReverseLangevinCall {      // lsnf_reverse_mala_step: z_out is the proposal eps_prop, eps_new the next
     LsnfChainArgs chain;                 // proposal eps_next (may be NULL); g_z_in and the norms stay NULL.  (acc: eps_acc)
 };
+struct LsnfReverseHmcCall : LsnfReverseMalaCall {      // lsnf_reverse_hmc_step: the base-space MALA call's tensors at a point of a
+    float* mom = nullptr; float* kin0 = nullptr;      // trajectory; flags: LSNF_HMC_*.  mom (B, nz; read and written), kin0 (B)
+};
 struct LsnfContractCall : LsnfCall {     // steps (2), (3) of lsnf_backward_params: batch contraction of the dump, chain rule
     const float* const* params_host = nullptr; float* const* grads_host = nullptr;
     const float* z_in = nullptr; const float* z_out = nullptr; const float* z_saved = nullptr;
@@ -148,6 +151,7 @@ int lsnf_small3_reverse_backward_st(const LsnfReverseBackwardCall& c);
 hipError_t lsnf_launch_small3_reverse_backward_z(const LsnfReverseBackwardCall& c, int st);
 hipError_t lsnf_launch_small3_reverse_langevin(const LsnfReverseLangevinCall& c, int st);      // st: of the same predicate
 hipError_t lsnf_launch_small3_reverse_mala(const LsnfReverseMalaCall& c, int st);              // st: of the same predicate
+hipError_t lsnf_launch_small3_reverse_hmc(const LsnfReverseHmcCall& c, int st);                // st: of the same predicate
 
 bool lsnf_contract_x3_covers(const LsnfContractCall& c);                   // (also asked with NULL tensors: lsnf_api.hip dump_may_tile)
 hipError_t lsnf_launch_contract_x3(const LsnfContractCall& c, int chunk_override);

@@ -214,6 +214,26 @@ __device__ __forceinline__ unsigned pair_or32(unsigned u) { return lsnf_pair_or3
 // sum over the 4 lane groups of a per-sample value (lanes n, n + 16, n + 32, n + 48)
 __device__ __forceinline__ float group_sum(float v) { return lsnf_pair_add32(lsnf_pair_add16(v)); }
 
+// ---- the draws of the Markov-chain tails (lsnf_small3_mala.hip, lsnf_small3_rmala.hip, lsnf_small3_hmc.hip, lsnf_small3_rhmc.hip) ----
+// the row's uniform in (0, 1): word 0 of Philox at field value 2 of the noise's counter (the noise draws use 0 and 1 there),
+// ((x0 >> 8) + 0.5) * 2^-24 in fp32 -- a pure function of (seed, offset, global row)
+__device__ __forceinline__ float chain_uniform(const LsnfRngState& rs, long long row0, long sample) {
+    const unsigned long long grow = (unsigned long long)(row0 + sample);
+    unsigned c0 = 2u << 16, c1 = (unsigned)grow, c2 = rs.c2, c3 = rs.c3hi ^ (unsigned)(grow >> 32);
+    lsnf_philox4x32_10(c0, c1, c2, c3, rs.k0, rs.k1);
+    return ((float)(c0 >> 8) + 0.5f) * 5.9604644775390625e-08f;
+}
+// xi of one half-unit (tile t = hs * HT + nt1): a row of the noise tensor, or the in-kernel draw at (seed, offset, global row, column)
+// -- lsnf_sample's eps at temperature 1 (lsnf_device.h) --; a padding column (beyond nz / 2 of its half) is 0; neither: 0
+template <int HT>
+__device__ __forceinline__ f32x4 chain_xi(const float* noise, const LsnfRngState& rs, long long row0, int nz, int half, int hs, int nt1, int ft1,
+                                          int g, long row, long sample, int vec4) {
+    if (noise) return load_row_half<HT>(hs * HT + nt1, ft1, noise + row * (long)nz, half, g, vec4);
+    if (!rs.on) return f32x4{0.f, 0.f, 0.f, 0.f};
+    float unused = 0.0f;
+    return lsnf_sample4(hs, 32 * nt1 + 16 * ft1 + 4 * g, half, (unsigned long long)(row0 + sample), rs, 1.0f, unused);
+}
+
 // ---- the activation stash (lsnf_layout.h LsnfActLayout) as the 16-row latency kernels write it: the forward and the stash-keeping reverse ----
 // stash addressing of a workgroup's ST sample tiles: 16-row tile q = blockIdx.x * ST + st is half (q & 1) of the 32-sample stash tile q >> 1
 struct StashTile { size_t wtile; int lane32; bool ok; };     // ok: a 16-row tile past the batch has no stash tile, nothing of it is stored

@@ -1,13 +1,14 @@
 // lsnf_small3_rbwd_kernel.h -- the kernel text of the latency reverse-backward (lsnf_small3_rbwd.hip: the stages, the LDS map, the
-// plain and the UPDATE output section), included by the two translation units that instantiate it.  The includer defines, before
+// plain and the UPDATE output section), included by the three translation units that instantiate it.  The includer defines, before
 // the #include:
-//   LSNF_S3R_KERNEL  the kernel template's name          lsnf_small3_rbwd_kernel           | lsnf_small3_rmala_kernel
-//   LSNF_S3R_ARGS    its argument struct (may name       Small3RbwdArgs, or Small3RlvArgs  | Small3RmalaArgs
+//   LSNF_S3R_KERNEL  the kernel template's name          lsnf_small3_rbwd_kernel           | lsnf_small3_rmala_kernel               | lsnf_small3_rhmc_kernel
+//   LSNF_S3R_ARGS    its argument struct (may name       Small3RbwdArgs, or Small3RlvArgs  | Small3RmalaArgs                        | Small3RhmcArgs
 //                    the template parameter UPDATE)      with UPDATE
-//   LSNF_S3R_TAIL    statements in front of the output   (nothing)                         | the accept / reject tail and `return;`
+//   LSNF_S3R_TAIL    statements in front of the output   (nothing)                         | the accept / reject tail and `return;` | the leapfrog tail and `return;`
 //                    section, with the kernel's locals in scope
 // lsnf_small3_rbwd.hip gives the first column and is compiled from the same tokens as before this file existed; lsnf_small3_rmala.hip
-// the second, with UPDATE = false (its tail loads e1, the first half of eps, itself: in front of its own barrier).
+// the second and lsnf_small3_rhmc.hip the third, both with UPDATE = false (their tails load e1, the first half of eps, themselves: in
+// front of their own barrier).
 #pragma once
 
 namespace {
@@ -56,6 +57,10 @@ struct Small3RmalaArgs : Small3RlvArgs {
     const float* energy_g; const float* uniform;
     float* eps_acc; float* grad_acc; float* u_acc; float* accept_out; float* log_alpha_out;
     unsigned flags;                                // LSNF_MALA_INIT (1): accept every row, the state is not read
+};
+// HMC form (lsnf_reverse_hmc_step): the MALA form's tensors at a point eps_prop of a trajectory; flags: LSNF_HMC_INIT (1), LSNF_HMC_INNER (2)
+struct Small3RhmcArgs : Small3RmalaArgs {
+    float* mom; float* kin0;                       // the momentum (read and written), the kinetic energy the trajectory began with
 };
 
 __device__ __forceinline__ f32x4 rb_mask4(f32x4 a, unsigned nib) {

@@ -6,6 +6,7 @@ restated (they are closures inside train.py and cannot be imported) on top of th
   sample_hmc_post_z_with_flow          Hamiltonian Monte Carlo on the same target: L leapfrog steps per accept / reject
   sample_langevin_post_eps_with_flow   the same sampler in the flow's base space (eps, with z = f^-1(eps)); not in the reference
   sample_mala_post_eps_with_flow       the base-space chain Metropolis-adjusted (per-row acceptance rate)
+  sample_hmc_post_eps_with_flow        Hamiltonian Monte Carlo in the base space: L leapfrog steps per accept / reject
   flow_mle_step                     <- train.py:404-415
   sample_x                          <- train.py:472-478 (prior samples for the FID evaluation)
 
@@ -228,6 +229,62 @@ def sample_mala_post_eps_with_flow(eps, x, netG: nn.Module, netF, *, g_l_steps: 
             _, acc, _ = netF.reverse_mala_step(eps_prop, saved, act, grad_g, energy.detach(), state, philox.step(j), g_l_step_size,
                                                init=j == 0, propose=j < K, inplace=True, reuse_buffers=True)
             if j:
+                accepted += acc
+        z = flow.reverse(plan, state.z, None)[0]
+    philox.advance(K + 1)
+    return state.z, z.view(B, nz, 1, 1), accepted / K, state.energy
+
+
+def sample_hmc_post_eps_with_flow(eps, x, netG: nn.Module, netF, *, g_l_steps: int, leapfrog_steps: int, g_l_step_size: float,
+                                  g_llhd_sigma: float, philox):
+    """Hamiltonian Monte Carlo on the target of `sample_mala_post_eps_with_flow`, U(eps) = |eps|^2 / 2 + |x - G(z)|^2 / (2 sigma^2)
+    with z = f^-1(eps): K = g_l_steps trajectories of L = leapfrog_steps leapfrog steps of size g_l_step_size, one accept / reject
+    per trajectory (L = 1 is that chain in exact arithmetic).  The flow has whitened the prior, so the identity mass matrix of the
+    momentum is the right one and long trajectories stay stable at steps the z-space chain cannot take.  Each of the K L + 1 points:
+        z      = f^-1(eps_prop)                      the reverse launch, keeping its backward's stash where
+                                                     `flow.reverse_keep_supported` (else reverse + forward at z)
+        energy, grad_g                               torch autograd through netG, per row, as `sample_mala_post_eps_with_flow`
+        `netF.reverse_hmc_step`                      the leapfrog arithmetic, the decision and the next trajectory's start, in place:
+                                                     one "init" call, then per trajectory L - 1 "inner" calls and one "end" call,
+                                                     the last of which proposes nothing
+    `philox` (a `flow.PhiloxNoise`, required) gives the call that starts trajectory t + 1 -- the init call is t = 0, end call t is
+    1 .. K -- its uniform and its momentum draw at offset + t; inner calls take no generator; it is ADVANCED by K + 1 on return.
+    eps: (B, nz) or (B, nz, 1, 1).
+    Returns (eps_k (B, nz), z_k = f^-1(eps_k) (B, nz, 1, 1) from one final reverse at the state, accept_rate (B) = accepted
+    trajectories / K, U(eps_k) (B)).  g_l_steps = 0 or an empty batch returns the input without a launch, with None rates:
+    (eps, None, None, None), an empty batch with its empty z; leapfrog_steps < 1 raises ValueError."""
+    from . import flow
+    K, L = int(g_l_steps), int(leapfrog_steps)
+    if L < 1:
+        raise ValueError(f"leapfrog_steps must be >= 1 (got {leapfrog_steps})")
+    B, nz = eps.shape[0], eps.shape[1]
+    eps_prop = eps.detach().reshape(B, nz).contiguous().clone()
+    if B == 0:
+        return eps_prop, eps_prop.view(0, nz, 1, 1), None, None
+    if K < 1:
+        return eps_prop, None, None, None
+    plan = netF._plan()
+    c = 1.0 / (2.0 * g_llhd_sigma * g_llhd_sigma)
+    keeps = flow.reverse_keep_supported(plan, B)
+    act = flow.new_act_saved(plan, B, eps_prop.device)
+    state = flow.new_hmc_state(plan, B, eps_prop.device)
+    accepted = torch.zeros(B, dtype=torch.float32, device=eps_prop.device)
+    with torch.no_grad():
+        for j in range(K * L + 1):
+            if keeps:
+                z, _, saved = flow.reverse(plan, eps_prop, None, save_for_backward=True, act_saved=act)
+            else:
+                z, _ = flow.reverse(plan, eps_prop, None)
+                saved = flow.forward(plan, z, None, want_ll=False, save_for_backward=True, act_saved=act)[3]
+            with torch.enable_grad():
+                zr = z.view(B, nz, 1, 1).requires_grad_(True)
+                energy = c * ((netG(zr) - x) ** 2).flatten(1).sum(1)                                 # train.py:312-313, per row
+                grad_g = torch.autograd.grad(energy.sum(), zr)[0].reshape(B, nz).contiguous()        # train.py:314
+            t, inner = j // L, j % L != 0
+            _, acc, _ = netF.reverse_hmc_step(eps_prop, saved, act, grad_g, energy.detach(), state, None if inner else philox.step(t),
+                                              g_l_step_size, phase="inner" if inner else "end" if j else "init", propose=j < K * L,
+                                              inplace=True, reuse_buffers=True)
+            if j and not inner:
                 accepted += acc
         z = flow.reverse(plan, state.z, None)[0]
     philox.advance(K + 1)

@@ -1,6 +1,6 @@
 """Markov-chain extensions of the functional host API (C: include/lsnf_flow_mcmc.h), re-exported by flow.py -- use them as
-`flow.mala_step`, `flow.reverse_mala_step`, `flow.MalaState`, `flow.new_mala_state`, `flow.hmc_step`, `flow.HmcState`,
-`flow.new_hmc_state`.  Every tensor goes through flow.py's one checking path before anything is
+`flow.mala_step`, `flow.reverse_mala_step`, `flow.MalaState`, `flow.new_mala_state`, `flow.hmc_step`, `flow.reverse_hmc_step`,
+`flow.HmcState`, `flow.new_hmc_state`.  Every tensor goes through flow.py's one checking path before anything is
 launched; like there, all functions raise on CPU tensors: there is no CPU path."""
 from __future__ import annotations
 
@@ -134,7 +134,9 @@ _HMC_PHASES = {"init": HMC_INIT, "inner": HMC_INNER, "end": 0}
 class HmcState:
     """The kept state of a Hamiltonian Monte Carlo chain (`hmc_step`): `MalaState`'s z (B, nz), grad (B, nz) = grad U(z) and
     energy (B) = U(z), plus mom (B, nz), the momentum of the running trajectory (read and written by every call), and kin (B),
-    the kinetic energy 0.5 |xi|^2 that trajectory began with."""
+    the kinetic energy 0.5 |xi|^2 that trajectory began with.
+    For the base-space chain of `reverse_hmc_step` the same five arrays hold its state, as `MalaState` does for `reverse_mala_step`:
+    z = the accepted points eps, grad = grad U(eps) = eps + J_{f^-1}(eps)^T grad_g, energy = U(eps) = |eps|^2 / 2 + energy_g."""
     z: torch.Tensor
     grad: torch.Tensor
     energy: torch.Tensor
@@ -143,7 +145,7 @@ class HmcState:
 
 
 def new_hmc_state(plan: FlowPlan, B: int, device) -> HmcState:
-    """A zeroed chain state of B rows for `hmc_step` (the phase="init" call fills it)."""
+    """A zeroed chain state of B rows for `hmc_step` / `reverse_hmc_step` (the phase="init" call fills it)."""
     f32 = dict(dtype=torch.float32, device=device)
     rows, one = (lambda: torch.zeros((int(B), plan.nz), **f32)), (lambda: torch.zeros(int(B), **f32))
     return HmcState(rows(), rows(), one(), rows(), one())
@@ -184,3 +186,49 @@ def hmc_step(plan: FlowPlan, z_prop: torch.Tensor, grad_g: Optional[torch.Tensor
           _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(state.mom), _ptr(state.kin), _ptr(noise),
           _ptr(uniform), rng, float(step_size), _HMC_PHASES[phase], _ptr(z_next), _ptr(acc), _ptr(la))
     return z_next, acc, la, ll
+
+
+def reverse_hmc_step(plan: FlowPlan, eps_prop: torch.Tensor, z_saved: Optional[torch.Tensor], act_saved: torch.Tensor,
+                     grad_g: Optional[torch.Tensor], energy_g: Optional[torch.Tensor], state: HmcState, noise, step_size: float, *,
+                     phase: str = "end", uniform: Optional[torch.Tensor] = None, propose: bool = True, inplace: bool = False,
+                     reuse_buffers: bool = False):
+    """One call of Hamiltonian Monte Carlo in the flow's base space (include/lsnf_flow_mcmc.h `lsnf_reverse_hmc_step`) in ONE launch:
+    with x = reverse(eps_prop)[0], target pi(eps) ~ exp(-U), U = |eps|^2 / 2 + energy_g, grad U = eps + g, g = J_{f^-1}(eps)^T grad_g
+    (`reverse_backward_z(plan, eps_prop, z_saved, act_saved, grad_g)`'s bits), momentum ~ N(0, I) -- the flow has whitened the prior,
+    so the identity mass matrix is the right one --, step s.  The reverse-backward's output section is the leapfrog tail at the point
+    eps_prop of a trajectory.  eps_prop / z_saved / act_saved: the reverse's input, the block outputs and the stash of the forward
+    AT x, as `reverse_mala_step`'s; like it this call runs no flow pass itself (the caller's generator sits between the reverse and
+    it) and can be captured in a graph.  grad_g (B, nz) / energy_g (B): the caller's gradient and per-row energy at x (None = 0: the
+    chain samples N(0, I)).  `state`: an `HmcState` (z = eps, grad = eps + g, energy = U, mom, kin).  phase:
+      "init"   starts a chain at eps_prop (every row accepted, the state written without being read: `reverse_mala_step(init=True)`'s
+               bits) and begins the first trajectory: mom = xi - s/2 grad, eps_next = eps + s mom, kin = |xi|^2 / 2;
+      "inner"  a leapfrog step inside a trajectory: mom -= s grad U(eps_prop), eps_next = eps_prop + s mom.  It draws and decides
+               nothing: noise and uniform must be None, propose True; state.z / grad / energy / kin are not touched;
+      "end"    finishes the trajectory at eps_prop (mom -= s/2 grad U), decides it against `state` with
+               log_alpha = (U_state - U_prop) + (kin - |mom|^2 / 2), updates the state in place and, with propose, begins the next
+               trajectory from it; with propose=False the full-step momentum at eps_prop is left in state.mom.
+    `noise`: a `PhiloxNoise` (the uniform and xi are drawn inside the kernel, as `reverse_mala_step`'s), or a (B, nz) tensor of N(0,1)
+    draws together with uniform= (B) draws in (0, 1) -- the tensor is left out (None) with propose=False, the uniform may be with
+    "init".  K trajectories of L leapfrog steps are K L + 1 calls: "init", then K times (L - 1 "inner", one "end"), the last with
+    propose=False; L = 1 is `reverse_mala_step`'s chain in exact arithmetic.
+    Returns (eps_next or None, accepted (B) of 1.0 / 0.0, log_alpha (B)); accepted and log_alpha are None for an inner call.
+    inplace: eps_next is eps_prop itself.  reuse_buffers: the last two live on the plan and are overwritten by the next call."""
+    if phase not in _HMC_PHASES:
+        raise LsnfError(f"phase must be one of 'init', 'inner', 'end' (got {phase!r})")
+    inner = phase == "inner"
+    B, dev, noise, rng = _check_chain(plan, eps_prop, "eps_prop", grad_g, energy_g, state, HmcState, noise, uniform,
+                                      stash=(z_saved, act_saved))
+    if inner and (noise is not None or rng is not None or uniform is not None or not propose):
+        raise LsnfError("an inner leapfrog step draws and decides nothing: noise and uniform must be None, propose True")
+    acc = la = None
+    if not inner:
+        def make():
+            f32 = dict(dtype=torch.float32, device=dev)
+            return {"acc": torch.empty(B, **f32), "la": torch.empty(B, **f32)}
+        bufs = _stream_buffers(plan, "_rhmc_buffers", B, dev, make) if reuse_buffers else make()
+        acc, la = bufs["acc"], bufs["la"]
+    eps_next = None if not propose else eps_prop if inplace else torch.empty_like(eps_prop)
+    _call("lsnf_reverse_hmc_step", dev, *_plan_head(plan), B, _ptr(eps_prop), _ptr(z_saved), _ptr(act_saved), _ptr(grad_g), _ptr(energy_g),
+          _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(state.mom), _ptr(state.kin), _ptr(noise), _ptr(uniform), rng,
+          float(step_size), _HMC_PHASES[phase], _ptr(eps_next), _ptr(acc), _ptr(la))
+    return eps_next, acc, la

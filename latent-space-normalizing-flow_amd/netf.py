@@ -488,6 +488,17 @@ class _netF(nn.Module):
                                       det(noise), step_size, init=init, uniform=det(uniform), propose=propose, inplace=inplace,
                                       reuse_buffers=reuse_buffers)
 
+    def reverse_hmc_step(self, eps_prop, z_saved, act_saved, grad_g=None, energy_g=None, state=None, noise=None, step_size=0.1, *,
+                         phase="end", uniform=None, propose=True, inplace=False, reuse_buffers=False):
+        """One Hamiltonian Monte Carlo call in the base space at the point eps_prop of a trajectory against the kept chain `state`
+        (`flow.reverse_hmc_step`: ONE launch on the stash of the reverse at eps_prop, the leapfrog tail as its output section; phase
+        "init", "inner" or "end"; the caller's generator ran in between).
+        Returns (eps_next or None, accepted, log_alpha); accepted and log_alpha are None for an inner call."""
+        det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t
+        return flow.reverse_hmc_step(self._plan(), det(eps_prop), det(z_saved), det(act_saved), det(grad_g), det(energy_g), state,
+                                     det(noise), step_size, phase=phase, uniform=det(uniform), propose=propose, inplace=inplace,
+                                     reuse_buffers=reuse_buffers)
+
     def mle_grads(self, z, accumulate: bool = False, max_norm: Optional[float] = None, reuse_buffers: bool = False):
         """Fused flow-MLE gradients (train.py:404-411): loss_f = -mean_b ll(z_b) and d loss_f / d theta written to
         `.grad` of the 60 live tensors -- forward (ll summed in-kernel), dump backward, batch contraction, unfold:

@@ -1,4 +1,5 @@
-// CPU: the argument rules of lsnf_mala_step, lsnf_reverse_mala_step and lsnf_hmc_step under the host sanitizers.  Refused calls only:
+// CPU: the argument rules of lsnf_mala_step, lsnf_reverse_mala_step, lsnf_hmc_step and lsnf_reverse_hmc_step under the host sanitizers.  Refused
+// calls only:
 // every refusal returns before any HIP call, so no device is needed and the addresses below are never dereferenced.
 //
 //   cd latent-space-normalizing-flow_amd/csrc && make                         # the plain objects
@@ -39,13 +40,18 @@ int hmc(const Args& a) {
                          a.grad_acc, a.u_acc, a.mom, a.kin0, a.noise, a.uniform, a.rng, a.step, a.flags, a.next, a.accept_out, a.log_alpha_out,
                          nullptr);
 }
+int rhmc(const Args& a) {
+    return lsnf_reverse_hmc_step(a.plan, a.nz, a.width, a.depth, 1, a.B, a.point, a.z_saved, a.act_saved, a.grad_g, a.energy_g, a.acc, a.grad_acc,
+                                 a.u_acc, a.mom, a.kin0, a.noise, a.uniform, a.rng, a.step, a.flags, a.next, a.accept_out, a.log_alpha_out, nullptr);
+}
 }  // namespace
 
 int main() {
     const LsnfRng ok = {1ull, 0ull, nullptr, 0ll}, neg = {1ull, 0ull, nullptr, -1ll};
     const LsnfRng odd = {1ull, 0ull, reinterpret_cast<const unsigned long long*>(0x30004ul), 0ll};
     struct Entry { const char* name; int (*call)(const Args&); unsigned unknown, inner; } const entries[] = {
-        {"lsnf_mala_step", mala, 2u, 0u}, {"lsnf_reverse_mala_step", rmala, 2u, 0u}, {"lsnf_hmc_step", hmc, 4u, LSNF_HMC_INNER}};
+        {"lsnf_mala_step", mala, 2u, 0u}, {"lsnf_reverse_mala_step", rmala, 2u, 0u}, {"lsnf_hmc_step", hmc, 4u, LSNF_HMC_INNER},
+        {"lsnf_reverse_hmc_step", rhmc, 4u, LSNF_HMC_INNER}};
     int refusals = 0, unexpected = 0;
     for (const Entry& e : entries) {
         auto refused = [&](const char* what, Args a) {
@@ -55,7 +61,7 @@ int main() {
             printf("%s %-40s rc %d  %s\n", fine ? "  " : "!!", what, rc, msg);
             ++refusals; unexpected += !fine;
         };
-        for (int k = 0; k < (e.inner ? 2 : 1); ++k) {     // (the HMC entry: the rules again for an inner call, where they apply)
+        for (int k = 0; k < (e.inner ? 2 : 1); ++k) {     // (the HMC entries: the rules again for an inner call, where they apply)
             const unsigned phase = k ? e.inner : 0u;
             Args base;
             base.flags = phase;
