@@ -38,7 +38,6 @@
 #error "lsnf_fwd3p.hip is the three-term bf16 kernel"
 #endif
 
-constexpr int LSNF_PAIR_DMA_PER_STEP = 6;   // CU-sharing form: LDS-DMA pieces at the head of each step of a half-phase until the wave's six are out (1, 2, 3, 6)
 constexpr int LSNF_FWD3Q_LARGE = 242;       // shape code of the plain forward above 32 768 rows (lsnf_launch_forward3q): 242 or 82
 
 namespace {
@@ -173,6 +172,16 @@ template <class T> struct TypeTag { using type = T; };
 template <int ST> __device__ __forceinline__ constexpr int unit_quad(int q) { return ST == 2 ? q : (q & ~1); }
 template <int ST> __device__ __forceinline__ constexpr int unit_pair0(int q) { return ST == 2 ? 0 : (q & 1); }
 template <int ST> __device__ __forceinline__ constexpr int unit_st(int q) { return ST == 2 ? (q & 1) : 0; }
+// ReLU as ONE VALU instruction: the signed-integer maximum of the bit pattern and 0 (v_max_i32).  Every float with its sign bit
+// set, -0 included, is a negative integer and becomes +0; every other pattern is kept -- bit for bit fmaxf(x, 0.0f) on non-NaN
+// input.  fmaxf itself compiles to two v_max_f32 here (a canonicalise of its argument first).  A NaN with a clear sign bit stays
+// NaN, where fmaxf gave 0: such a row is already NaN in all of v (S1 mixes every input feature into every output).  The same holds
+// for the h dump of the STASH == 2 form (stash_h_quad): only a row that is NaN already can get other bits there, and its share of
+// the parameter gradients is NaN with either value (its g is NaN); the ReLU mask words come from mask_q16, which is unchanged.
+__device__ __forceinline__ float relu_bits(float x) {
+    const int b = __builtin_bit_cast(int, x);
+    return __builtin_bit_cast(float, b > 0 ? b : 0);
+}
 // unit q (optionally through ReLU) -> its dwords of the B operands: 22 (26) VALU per quad
 template <bool RELU, int ST>
 __device__ __forceinline__ void split_q16(const Tile16& x, int q, SplitTile16& out) {
@@ -185,7 +194,7 @@ __device__ __forceinline__ void split_q16(const Tile16& x, int q, SplitTile16& o
     for (int jj = 0; jj < ST; ++jj) {
         const int j = unit_pair0<ST>(q) + jj;
         float a = x.q[qr][2 * j], b = x.q[qr][2 * j + 1];
-        if (RELU) { a = fmaxf(a, 0.0f); b = fmaxf(b, 0.0f); }
+        if (RELU) { a = relu_bits(a); b = relu_bits(b); }
         const unsigned p1 = pk_bf16(a, b);
         a -= __builtin_bit_cast(float, p1 << 16); b -= __builtin_bit_cast(float, p1 & 0xffff0000u);
         const unsigned p2 = pk_bf16(a, b);
@@ -271,7 +280,7 @@ __device__ __forceinline__ void stash_h_quad(const StashRsrc& rs, const StashLan
     const int ft = q >> 1, st = q & 1;
     f32x4v r;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) r[j] = fmaxf(h.q[q][j], 0.0f);         // (the same v_max as the split's: one instruction serves both)
+    for (int j = 0; j < 4; ++j) r[j] = relu_bits(h.q[q][j]);           // (the same v_max as the split's: one instruction serves both)
     const unsigned off = (32 * t + 16 * ft < width) ? sl.hoff : 0x80000000u;
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4s, r), rs.r[t], off + (unsigned)((ft * 2 + st) * 1024), 0, 0);
 }
@@ -465,14 +474,24 @@ template <class PH, int KIND, int H> struct FirstTouch<HalfPh<PH, KIND, H>> {   
 static_assert(HalfPh<QhS1a, 0, 0>::resident() && HalfPh<QhS1a, 0, 1>::resident() && HalfPh<QhS1b, 0, 0>::resident() && HalfPh<QhS1b, 0, 1>::resident() &&
               HalfPh<QhS23, 1, 0>::resident() && HalfPh<QhS23, 1, 1>::resident() && HalfPh<QhS4, 2, 0>::resident() && HalfPh<QhS4, 2, 1>::resident(),
               "the step order of a half-phase stays inside its four fragments");
-// one 1 KiB LDS-DMA piece at a byte offset the caller formed (issue_piece of lsnf_l16.h without its wave-interleaved segment rule)
-__device__ __forceinline__ void issue_piece_at(const float* __restrict__ gsrc, float* lbuf, int kib, int lane) {
-    const char* sb = reinterpret_cast<const char*>(gsrc) + (size_t)kib * 1024u;
-    const unsigned m0v = (unsigned)(size_t)((LSNF_AS3 char*)lbuf) + (unsigned)kib * 1024u;
+// The six 1 KiB LDS-DMA pieces of one 6 KiB chunk (PAIR), at a byte address the caller formed, in ONE statement.  The instruction's
+// immediate offset moves the global AND the LDS address, so the pieces 0-3 share one base and one m0; the field is 13 bits signed, so
+// the pieces 4, 5 take a second pair (base + 4 KiB, formed on the scalar unit).  m0 is saved and restored once for the six, not once
+// each: the compiler does use m0 itself in this file (the lane index of the v_writelane that builds the stash descriptors), so the
+// statement hands it back.  (Six statements with six 64-bit adds and six m0 hand-overs were 36 scalar instructions behind every
+// barrier, in front of the half-phase's first MFMA; this is 8.)
+__device__ __forceinline__ void issue_chunk_at(const char* sb, float* lbuf, int lane) {
+    const char* sb4 = sb + 4096;
+    const unsigned m0v = (unsigned)(size_t)((LSNF_AS3 char*)lbuf), m0v4 = m0v + 4096u;
     const unsigned lane_off = (unsigned)lane * 16u;
     unsigned keep_m0;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep_m0) : "v"(lane_off), "s"(sb), "s"(m0v) : "memory");
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\t"
+                 "global_load_lds_dwordx4 %1, %2\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\t"
+                 "global_load_lds_dwordx4 %1, %2 offset:2048\n\tglobal_load_lds_dwordx4 %1, %2 offset:3072\n\t"
+                 "s_mov_b32 m0, %5\n\ts_nop 0\n\t"
+                 "global_load_lds_dwordx4 %1, %3\n\tglobal_load_lds_dwordx4 %1, %3 offset:1024\n\t"
+                 "s_mov_b32 m0, %0"
+                 : "=&s"(keep_m0) : "v"(lane_off), "s"(sb), "s"(sb4), "s"(m0v), "s"(m0v4) : "memory");
 }
 
 // STASH: 0 plain, 1 block outputs + activation stash, 2 also the tiled h dump.  PAIR: the CU-sharing form above (plain, 4 waves x 32 rows)
@@ -503,11 +522,8 @@ __global__ __launch_bounds__(64 * NWAVES, PAIR ? 2 : 1) void lsnf_fwd3q_kernel(c
     P_STAMP(0, "s_memtime");
     P_STAMP(50, "s_memrealtime");
     const int n_phases = 4 * a.n_blocks;
-    auto phase_src = [&](int k) -> const float* {
-        const float* gb = a.panels3 + (size_t)(k >> 2) * C::BLOCK3;
-        const int j = k & 3;
-        return gb + (j == 0 ? 0 : (j == 1 ? 2 * 4 * F : (j == 2 ? C::OFF3_S2 : C::OFF3_S4)));
-    };
+    auto phase_off = [](int j) { return j == 0 ? 0 : (j == 1 ? 2 * 4 * F : (j == 2 ? C::OFF3_S2 : C::OFF3_S4)); };     // floats into the block's panels
+    auto phase_src = [&](int k) -> const float* { return a.panels3 + (size_t)(k >> 2) * C::BLOCK3 + phase_off(k & 3); };
     // Barrier k: my pieces of phase k's weights have landed (vmcnt), everybody's have (barrier), and buffer (k + 1) & 1 is free.
     // The next phase's 48 KiB are NOT issued here in one burst (12 / 6 LDS-DMA instructions per wave, each with its m0
     // hand-over: ~1 200 cycles per phase with one wave per SIMD, tools/stamps_fwd3p.py at 16 384 rows) but one piece at the head
@@ -533,30 +549,35 @@ __global__ __launch_bounds__(64 * NWAVES, PAIR ? 2 : 1) void lsnf_fwd3q_kernel(c
     auto dma_step = [&](auto ic) {
         constexpr int i = decltype(ic)::value;
         if constexpr (PAIR) {
-            // this wave's chunk: six pieces, PS at the head of a step.  A half-phase is 8 steps, half the time the 8-wave form has for
+            // this wave's chunk: six pieces, all at the head of step 0.  A half-phase is 8 steps, half the time the 8-wave form has for
             // a piece to land before the next barrier's vmcnt(0): measured at 65 536 rows, three streams, with the pieces over steps
             // 0-5 / 0-2 / 0-1 / all at step 0: 84.6 / 84.7 / 84.5 / 84.3 us per step (8-wave form 87.2; profiles/fwd3q_pair_ab.txt)
-            constexpr int PS = LSNF_PAIR_DMA_PER_STEP;
-            if constexpr (i * PS < 6) {
-#pragma unroll
-                for (int s = i * PS; s < i * PS + PS && s < 6; ++s) issue_piece_at(dma_src, dma_dst, s, lane);
-            }
+            if constexpr (i == 0) issue_chunk_at(reinterpret_cast<const char*>(dma_src), dma_dst, lane);
         } else if constexpr (i % EVERY == 0 && i / EVERY < PER_WAVE) issue_piece<NWAVES>(dma_src, dma_dst, i / EVERY, wave, lane);
     };
     // PAIR.  Half-phase (k, h) reads buffer h.  Barrier in front of it: my pieces of it have landed, everybody's have, and buffer h ^ 1
     // is free; its steps then carry the next half-phase's pieces -- (k, 1) behind (k, 0), (k + 1, 0) behind (k, 1).  The last half-phase
     // of the call re-fetches its own chunks into the free buffer (no DMA under a branch; the epilogue waits for it).
+    // Where this wave's chunk of the NEXT half-phase lies depends on the wave and on (phase, half), not on the block: the eight offsets
+    // into a block's panels are formed once, here (nxt_off[2 * J + H]: what half H of phase J carries; behind S4's second half, phase 0
+    // of the next block), and held in scalar registers -- opaque, or the compiler forms them again behind every barrier, ~20 scalar
+    // instructions that no MFMA of the wave overlaps.  The head of a half-phase is then one 64-bit add onto the block's panels.
     auto pair_chunk = [&](unsigned packed) { return (int)((packed >> (4 * wave)) & 7u); };       // (scalar unit: wave is uniform)
+    unsigned nxt_off[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    if constexpr (PAIR) {
+        lsnf_static_for<8>([&](auto ec) {
+            constexpr int e = decltype(ec)::value, JN = (e >> 1) + (e & 1), HN = (e & 1) ^ 1;
+            nxt_off[e] = (unsigned)((JN == 4 ? C::BLOCK3 : phase_off(JN)) + pair_chunk(PairMap::packed(PairMap::kind(JN & 3), HN)) * F);
+            asm volatile("" : "+s"(nxt_off[e]));
+        });
+    }
+    const float* blk_panels = a.panels3;                                 // the panels of the block being run
     auto pair_arm = [&](auto jc, auto hc, int k) {                       // jc: phase of the block (0..3), hc: half about to run
         constexpr int J = decltype(jc)::value, H = decltype(hc)::value;
-        if constexpr (H == 0) {
-            dma_src = phase_src(k) + pair_chunk(PairMap::packed(PairMap::kind(J), 1)) * F;
-            dma_dst = buf0 + HSLOT + wave * F;
-        } else {
-            const bool last = k + 1 >= n_phases;
-            dma_src = phase_src(last ? k : k + 1) + pair_chunk(last ? PairMap::packed(PairMap::kind(J), 1) : PairMap::packed(PairMap::kind((J + 1) & 3), 0)) * F;
-            dma_dst = buf0 + wave * F;
-        }
+        unsigned off = nxt_off[2 * J + H];
+        if constexpr (J == 3 && H == 1) off = (k + 1 >= n_phases) ? nxt_off[6] : off;        // (the last one: its own chunk again)
+        dma_src = blk_panels + off;
+        dma_dst = buf0 + (H == 0 ? HSLOT : 0) + wave * F;
     };
     // one phase of the block: phase table PH, phase jc of the block, global phase index k.  Its opening barrier is the caller's.
     auto run_phase = [&](auto ph, auto jc, int k, Tile16* acc, const float* bv, const SplitTile16* in, auto&& fill) {
@@ -591,7 +612,8 @@ __global__ __launch_bounds__(64 * NWAVES, PAIR ? 2 : 1) void lsnf_fwd3q_kernel(c
     float lsum[2] = {0.0f, 0.0f};
     {
         // the row loads go out FIRST: the constant blocks below travel through registers (load, wait, LDS store), and with that
-        // copy in front the rows were requested one memory round trip (~2 us) later than necessary
+        // copy in front the rows were requested one memory round trip (~2 us) later than necessary.  (The constants as 1 KiB LDS-DMA
+        // pieces beside the weights, no registers and no wait: measured, no faster -- profiles/fwd3q_issue_slots_ab.txt.)
         const Tile16 x0 = load_tile16<HT, ST>(0, a.z_in, rows, a.nz, a.half, g, a.vec4);
         const Tile16 x1 = load_tile16<HT, ST>(1, a.z_in, rows, a.nz, a.half, g, a.vec4);
         v[2] = load_tile16<HT, ST>(2, a.z_in, rows, a.nz, a.half, g, a.vec4);
@@ -599,8 +621,7 @@ __global__ __launch_bounds__(64 * NWAVES, PAIR ? 2 : 1) void lsnf_fwd3q_kernel(c
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (PAIR) {                       // the first half of S1a: this wave's chunk
             const float* src0 = phase_src(0) + pair_chunk(PairMap::packed(0, 0)) * F;
-#pragma unroll
-            for (int s = 0; s < 6; ++s) issue_piece_at(src0, buf0 + wave * F, s, lane);
+            issue_chunk_at(reinterpret_cast<const char*>(src0), buf0 + wave * F, lane);
         } else issue_kib<48, NWAVES>(phase_src(0), buf0, wave, lane);
         for (int i = tid; i < a.n_blocks * C::CONST_FLOATS; i += THREADS) cst[i] = a.consts[i];
 #pragma unroll
@@ -635,6 +656,7 @@ __global__ __launch_bounds__(64 * NWAVES, PAIR ? 2 : 1) void lsnf_fwd3q_kernel(c
 
     for (int blk = 0; blk < a.n_blocks; ++blk) {
         const float* cb = cst + blk * C::CONST_FLOATS;
+        blk_panels = a.panels3 + (size_t)blk * C::BLOCK3;
         const bool more = blk + 1 < a.n_blocks;
         const int k0 = 4 * blk;
         SplitTile16 vh[4];                          // S2+S3 inputs: split v[0], v[1], h1[0], h1[1]
