@@ -164,7 +164,39 @@
  *   grad_acc, u_acc, mom, kin0, eps_next, accept_out, log_alpha_out) may alias anything the call reads, or another output
  * One kernel (lsnf_small3_rhmc_kernel) under every lsnf_set_math_mode, for every B (more rounds of workgroups above 16 384 rows) and
  * every phase, independent of lsnf_set_small_batch_max; a row's bits do not depend on B, the workgroup shape or rng->row0 sharding.
- * B = 0 succeeds without a launch.  Every refusal is LSNF_E_ARG / LSNF_E_GEOMETRY, made before any HIP call. */
+ * B = 0 succeeds without a launch.  Every refusal is LSNF_E_ARG / LSNF_E_GEOMETRY, made before any HIP call.
+ *
+ * ---- A step per row, adapted on the device (lsnf_hmc_step_rows, lsnf_reverse_hmc_step_rows) ------------------------------------------
+ * Every row of a batch targets a posterior of its own, so every row may run at a step of its own.  The two entry points are
+ * lsnf_hmc_step and lsnf_reverse_hmc_step with `float step_size` replaced by `float* step_rows, float* adapt, const LsnfDualAvg* da`;
+ * every other argument, rule, draw and refusal is the scalar call's, word for word (there is no step_size rule: the steps are
+ * device memory and are not looked at on the host; a row whose step is zero or not finite gets what the arithmetic gives it).
+ *   step_rows (B): row b's step for the RUNNING trajectory.  Every phase reads it; only an LSNF_HMC_ADAPT end call writes it.
+ *   adapt (B,4), 16-byte aligned: {log_step_bar, hbar, count, mu} per row, the state of the dual averaging (Hoffman & Gelman 2014,
+ *       algorithm 5).  mu is the caller's, log(10 * the first step); a fresh row has log_step_bar = hbar = count = 0.  With
+ *       LSNF_HMC_ADAPT adapt and da are required; without it both must be NULL.
+ *   da: the update's constants (host memory, read during the call only): all finite, target_accept in (0,1), gamma > 0, t0 + 1 > 0,
+ *       step_min > 0, step_max >= step_min.  Stan's: 0.8, 0.05, 10, 0.75.
+ *   flags: 0, LSNF_HMC_INIT or LSNF_HMC_INNER as in the scalar call; LSNF_HMC_ADAPT with an end call only (refused with INIT or
+ *       INNER), LSNF_HMC_ADAPT_LAST with LSNF_HMC_ADAPT only; unknown bits are refused
+ *   step_rows and adapt are outputs in the sense of the aliasing rule: they may alias nothing else the call touches
+ * (1) Without LSNF_HMC_ADAPT row b's outputs are the scalar call's at step_size = step_rows[b], bit for bit, in every phase: the
+ *     operations and the order written above with s read per row.
+ * (2) An end call with LSNF_HMC_ADAPT finishes and decides the trajectory with the old step_rows[b], then, per row, in fp32 with the
+ *     operations and the order written and no fused multiply-add (la: the row's log_alpha; LAST: LSNF_HMC_ADAPT_LAST):
+ *         a    = (la == la) ? fminf(1, expf(la)) : 0          (a NaN log_alpha counts as a rejection)
+ *         t    = count + 1;  eta = 1 / (t + t0)
+ *         hbar = (1 - eta) * hbar + eta * (target_accept - a)
+ *         ls   = clamp(mu - (sqrtf(t) / gamma) * hbar, logf(step_min), logf(step_max))      (the two logs taken on the host)
+ *         w    = powf(t, -kappa);  lsb = w * ls + (1 - w) * lsb
+ *         s'   = expf(LAST ? lsb : ls)
+ *     stores adapt = {lsb, hbar, t, mu} and step_rows[b] = s', and, if z_next / eps_next is given, begins the next trajectory with
+ *     s' (hs = 0.5f * s').  mom, with z_next / eps_next NULL, is the full-step momentum at the OLD step.  This keeps the chain valid:
+ *     a row's step is fixed before its momentum is drawn and is constant within a trajectory.  While steps adapt the chain is not
+ *     exactly invariant; it is from the call with LSNF_HMC_ADAPT_LAST on, which leaves the averaged step for the calls that follow.
+ * Kernels: lsnf_small3_hmcr_kernel / lsnf_small3_rhmcr_kernel, the scalar kernels' stages with the per-row tail, the same
+ * instantiations and workgroup shapes; a row's bits -- its new step and adapt included -- do not depend on B, the workgroup shape
+ * or rng->row0 sharding.  With L = 1 the calls are the adaptive MALA step in exact arithmetic, as the scalar calls are MALA's. */
 #ifndef LSNF_FLOW_MCMC_H
 #define LSNF_FLOW_MCMC_H
 
@@ -201,6 +233,25 @@ int lsnf_reverse_hmc_step(const float* plan, int nz, int width, int depth, int c
                           float* eps_acc, float* grad_acc, float* u_acc, float* mom, float* kin0,
                           const float* noise, const float* uniform, const LsnfRng* rng, float step_size, unsigned flags,
                           float* eps_next, float* accept_out, float* log_alpha_out, void* stream);
+
+/* dual averaging of the rows' steps (Hoffman & Gelman 2014, algorithm 5); Stan's constants: 0.8, 0.05, 10, 0.75 */
+typedef struct LsnfDualAvg { float target_accept, gamma, t0, kappa, step_min, step_max; } LsnfDualAvg;
+#define LSNF_HMC_ADAPT      4u   /* end calls only: update the rows' adaptation state from this decision */
+#define LSNF_HMC_ADAPT_LAST 8u   /* with ADAPT: the step written is exp(log_step_bar), the averaged one */
+int lsnf_hmc_step_rows(const float* plan, int nz, int width, int depth, int coupling, int B,
+                       const float* z_prop, const float* z_out, const float* z_saved, const float* act_saved,
+                       const float* ll_prop, const float* grad_g, const float* energy_g,
+                       float* z_acc, float* grad_acc, float* u_acc, float* mom, float* kin0,
+                       const float* noise, const float* uniform, const LsnfRng* rng,
+                       float* step_rows, float* adapt, const LsnfDualAvg* da, unsigned flags,
+                       float* z_next, float* accept_out, float* log_alpha_out, void* stream);
+int lsnf_reverse_hmc_step_rows(const float* plan, int nz, int width, int depth, int coupling, int B,
+                               const float* eps_prop, const float* z_saved, const float* act_saved,
+                               const float* grad_g, const float* energy_g,
+                               float* eps_acc, float* grad_acc, float* u_acc, float* mom, float* kin0,
+                               const float* noise, const float* uniform, const LsnfRng* rng,
+                               float* step_rows, float* adapt, const LsnfDualAvg* da, unsigned flags,
+                               float* eps_next, float* accept_out, float* log_alpha_out, void* stream);
 
 #ifdef __cplusplus
 }

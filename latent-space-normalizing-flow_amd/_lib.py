@@ -20,6 +20,12 @@ class LsnfRng(ctypes.Structure):
     _fields_ = [("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64), ("offset_dev", c_void_p), ("row0", ctypes.c_int64)]
 
 
+class LsnfDualAvg(ctypes.Structure):
+    """include/lsnf_flow_mcmc.h `LsnfDualAvg`: the constants of the dual averaging of lsnf_hmc_step_rows' steps."""
+    _fields_ = [("target_accept", c_float), ("gamma", c_float), ("t0", c_float), ("kappa", c_float), ("step_min", c_float),
+                ("step_max", c_float)]
+
+
 class LsnfAdamOptions(ctypes.Structure):
     """include/lsnf_flow.h `LsnfAdamOptions`: the arguments of lsnf_adam_step_ex."""
     _fields_ = [("struct_bytes", ctypes.c_uint), ("flags", ctypes.c_uint), ("lr", c_double), ("lr_dev", c_void_p),
@@ -103,6 +109,18 @@ _EXT_SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, ctypes.POINTER(LsnfRng), c_float, ctypes.c_uint,
                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lsnf_hmc_step_rows": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, ctypes.POINTER(LsnfRng),
+                                   c_void_p, c_void_p, ctypes.POINTER(LsnfDualAvg), ctypes.c_uint,
+                                   c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lsnf_reverse_hmc_step_rows": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, ctypes.POINTER(LsnfRng),
+                                           c_void_p, c_void_p, ctypes.POINTER(LsnfDualAvg), ctypes.c_uint,
+                                           c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

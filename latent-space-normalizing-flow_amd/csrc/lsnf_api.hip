@@ -239,6 +239,37 @@ struct ChainStep {
     }
 };
 
+// The rules a step per row adds (lsnf_hmc_step_rows, lsnf_reverse_hmc_step_rows), stated once.  flags(): with the scalars, before the
+// empty-batch return (da is host memory); pointers(): with the pointers of a non-empty call.
+struct RowSteps {
+    const float* step_rows; const float* adapt; const LsnfDualAvg* da; unsigned flags;
+    bool adapting() const { return (flags & LSNF_HMC_ADAPT) != 0; }
+    bool scalars(Check& ck) const {
+        if (ck.refuse(adapting() && (flags & (LSNF_HMC_INIT | LSNF_HMC_INNER)),
+                      "flags: LSNF_HMC_ADAPT goes with an end call (neither LSNF_HMC_INIT nor LSNF_HMC_INNER)") ||
+            ck.refuse((flags & LSNF_HMC_ADAPT_LAST) && !adapting(), "flags: LSNF_HMC_ADAPT_LAST goes with LSNF_HMC_ADAPT") ||
+            ck.refuse(adapting() && !da, "da is required with LSNF_HMC_ADAPT") ||
+            ck.refuse(!adapting() && (adapt || da), "adapt and da must be NULL without LSNF_HMC_ADAPT"))
+            return true;
+        if (!da) return false;
+        const float f[] = {da->target_accept, da->gamma, da->t0, da->kappa, da->step_min, da->step_max};
+        for (float v : f)
+            if (ck.refuse(!std::isfinite(v), "da: every field must be finite (got %g)", (double)v)) return true;
+        return ck.refuse(!(da->target_accept > 0.0f && da->target_accept < 1.0f), "da->target_accept must lie in (0, 1) (got %g)", (double)da->target_accept) ||
+               ck.refuse(!(da->gamma > 0.0f), "da->gamma must be positive (got %g)", (double)da->gamma) ||
+               ck.refuse(!(da->t0 + 1.0f > 0.0f), "da->t0 + 1 must be positive (got t0 = %g)", (double)da->t0) ||
+               ck.refuse(!(da->step_min > 0.0f), "da->step_min must be positive (got %g)", (double)da->step_min) ||
+               ck.refuse(da->step_max < da->step_min, "da->step_max must not be below da->step_min (got %g < %g)", (double)da->step_max, (double)da->step_min);
+    }
+    bool pointers(Check& ck) const {
+        return ck.refuse(adapting() && !adapt, "adapt is required with LSNF_HMC_ADAPT") || ck.aligned16("adapt", {adapt});
+    }
+    LsnfDualAvgArgs args() const {
+        return da ? LsnfDualAvgArgs{da->target_accept, da->gamma, da->t0, da->kappa, logf(da->step_min), logf(da->step_max)}
+                  : LsnfDualAvgArgs{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    }
+};
+
 // ---- kernel selection: each operation decides on the host, from the kernels' coverage predicates, which kernel(s) a call
 // runs, BEFORE anything is launched; the entry point then launches exactly that.  A launcher reached outside what it covers
 // is a selection bug and fails the call (LSNF_E_HIP, the kernel named in lsnf_last_error()); nothing falls through to another
@@ -248,6 +279,7 @@ enum Kernel {
     K_REV, K_REV3, K_REV2H_FIXUP, K_SMALL_REV, K_SMALL3_REV,
     K_BWD, K_BWD3, K_SMALL_BWD, K_SMALL3_BWD,
     K_SMALL3_RBWD, K_SMALL3_RLV, K_SMALL3_MALA, K_SMALL3_RMALA, K_SMALL3_HMC, K_SMALL3_RHMC,
+    K_SMALL3_HMCR, K_SMALL3_RHMCR,
 };
 const char* const kKernelName[] = {
     "no kernel takes this call", "lsnf_fwd_kernel", "lsnf_fwd3b_kernel", "lsnf_fwd3q_kernel",
@@ -257,6 +289,7 @@ const char* const kKernelName[] = {
     "lsnf_bwd_z_kernel", "lsnf_bwd3_kernel", "lsnf_small_bwd_kernel", "lsnf_small3_bwd_kernel",
     "lsnf_small3_rbwd_kernel", "lsnf_small3_rbwd_kernel (update form)", "lsnf_small3_mala_kernel", "lsnf_small3_rmala_kernel",
     "lsnf_small3_hmc_kernel", "lsnf_small3_rhmc_kernel",
+    "lsnf_small3_hmcr_kernel", "lsnf_small3_rhmcr_kernel",
 };
 struct Pick { Kernel k; int st = 0; };     // st: rows per workgroup / 16 of the small3 kernels
 
@@ -460,6 +493,10 @@ Pick select_hmc(const LsnfHmcCall& c) { return {K_SMALL3_HMC, lsnf_small3_backwa
 // Its base-space form (lsnf_reverse_hmc_step) is the reverse-backward with the leapfrog tail (lsnf_small3_rhmc.hip): one kernel under
 // every math mode, batch size and phase, the workgroup shape of the plain reverse-backward of the call.
 Pick select_reverse_hmc(const LsnfReverseHmcCall& c) { return {K_SMALL3_RHMC, lsnf_small3_reverse_backward_st(c)}; }
+// The two with a step per row (lsnf_hmc_step_rows, lsnf_reverse_hmc_step_rows): the same kernel texts with the per-row tail
+// (lsnf_small3_hmcr.hip, lsnf_small3_rhmcr.hip), the same instantiations, the same rule for the workgroup shape.
+Pick select_hmc_rows(const LsnfHmcRowsCall& c) { return {K_SMALL3_HMCR, lsnf_small3_backward_st(c)}; }
+Pick select_reverse_hmc_rows(const LsnfReverseHmcRowsCall& c) { return {K_SMALL3_RHMCR, lsnf_small3_reverse_backward_st(c)}; }
 
 // Batch contraction of the parameter gradients (LsnfContraction): on the bf16 matrix pipe where lsnf_params3.hip covers the
 // call (use_x3); from 4 096 rows the fp32-MFMA kernel through LDS, with the widest row loads the rows allow -- every row the
@@ -965,6 +1002,76 @@ int lsnf_reverse_hmc_step(const float* plan, int nz, int width, int depth, int c
     c.chain = {energy_g, uniform, eps_acc, grad_acc, u_acc, accept_out, log_alpha_out, flags}; c.mom = mom; c.kin0 = kin0;
     const Pick p = select_reverse_hmc(c);
     return report(ck.entry, p, lsnf_launch_small3_reverse_hmc(c, p.st));
+}
+
+// The two HMC entries with a step per row: the scalar entries' tables and rules, step_rows and adapt among the outputs (so that they
+// alias nothing else of the call), no step_size rule (the steps are device memory), the flags and LsnfDualAvg rules of RowSteps.
+int lsnf_hmc_step_rows(const float* plan, int nz, int width, int depth, int coupling, int B, const float* z_prop, const float* z_out,
+                       const float* z_saved, const float* act_saved, const float* ll_prop, const float* grad_g, const float* energy_g,
+                       float* z_acc, float* grad_acc, float* u_acc, float* mom, float* kin0, const float* noise, const float* uniform,
+                       const LsnfRng* rng, float* step_rows, float* adapt, const LsnfDualAvg* da, unsigned flags, float* z_next,
+                       float* accept_out, float* log_alpha_out, void* stream) {
+    Check ck{"lsnf_hmc_step_rows"};
+    const Named reads[] = {{"plan", plan}, {"z_prop", z_prop}, {"z_out", z_out}, {"z_saved", z_saved}, {"act_saved", act_saved},
+                           {"ll_prop", ll_prop}, {"grad_g", grad_g}, {"energy_g", energy_g}, {"noise", noise}, {"uniform", uniform}};
+    const Named writes[] = {{"z_acc", z_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc}, {"z_next", z_next}, {"accept_out", accept_out},
+                            {"log_alpha_out", log_alpha_out}, {"mom", mom}, {"kin0", kin0}, {"step_rows", step_rows}, {"adapt", adapt}};
+    const bool init = (flags & LSNF_HMC_INIT) != 0, inner = (flags & LSNF_HMC_INNER) != 0;
+    const Needed needed[] = {{"plan", plan}, {"z_prop", z_prop}, {"z_out", z_out}, {"act_saved", act_saved}, {"z_acc", z_acc},
+                             {"grad_acc", grad_acc}, {"u_acc", u_acc}, {"mom", mom}, {"kin0", kin0}, {"step_rows", step_rows},
+                             {"ll_prop", ll_prop, !inner, "(NULL) unless LSNF_HMC_INNER"}, {"z_saved", z_saved, depth > 1, "(NULL) for depth > 1"},
+                             {"z_next", z_next, inner, "(NULL) with LSNF_HMC_INNER"}};
+    const ChainStep s = {reads, writes, /*next=*/&writes[3], /*point=*/&reads[1], needed,
+                         LSNF_HMC_INIT | LSNF_HMC_INNER | LSNF_HMC_ADAPT | LSNF_HMC_ADAPT_LAST, init, inner,
+                         "LSNF_HMC_INIT or LSNF_HMC_INNER", plan, act_saved, noise, uniform, rng, /*step_size=*/1.0f, flags};
+    const RowSteps rows = {step_rows, adapt, da, flags};
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B) || s.scalars(ck) || s.phases(ck, accept_out, log_alpha_out) || rows.scalars(ck) ||
+        s.aliases(ck))
+        return ck.rc;
+    if (ck.empty) return LSNF_OK;
+    if (s.pointers(ck) || rows.pointers(ck)) return ck.rc;
+    const LsnfLangevinArgs lv = {z_prop, grad_g, noise, z_next, nullptr, nullptr, 0.0f, rng_args(rng)};
+    LsnfHmcRowsCall c;                   // (no g_z1 / g_logdet / g_z_in: the gradient of -log p at the point, consumed by the tail)
+    ck.head(c, plan, B, stream, {z_prop, z_out, z_saved, grad_g, noise, z_next, z_acc, grad_acc, mom});
+    c.z_out = z_out; c.z_saved = z_saved; c.act_saved = act_saved; c.ll_mode = 1; c.ll_scale = -1.0f; c.lv = &lv; c.ll_prop = ll_prop;
+    c.chain = {energy_g, uniform, z_acc, grad_acc, u_acc, accept_out, log_alpha_out, flags}; c.mom = mom; c.kin0 = kin0;
+    c.step_rows = step_rows; c.adapt = adapt; c.da = rows.args();
+    const Pick p = select_hmc_rows(c);
+    return report(ck.entry, p, lsnf_launch_small3_hmc_rows(c, p.st));
+}
+
+int lsnf_reverse_hmc_step_rows(const float* plan, int nz, int width, int depth, int coupling, int B, const float* eps_prop,
+                               const float* z_saved, const float* act_saved, const float* grad_g, const float* energy_g, float* eps_acc,
+                               float* grad_acc, float* u_acc, float* mom, float* kin0, const float* noise, const float* uniform,
+                               const LsnfRng* rng, float* step_rows, float* adapt, const LsnfDualAvg* da, unsigned flags, float* eps_next,
+                               float* accept_out, float* log_alpha_out, void* stream) {
+    Check ck{"lsnf_reverse_hmc_step_rows"};
+    const Named reads[] = {{"plan", plan}, {"eps_prop", eps_prop}, {"z_saved", z_saved}, {"act_saved", act_saved}, {"grad_g", grad_g},
+                           {"energy_g", energy_g}, {"noise", noise}, {"uniform", uniform}};
+    const Named writes[] = {{"eps_acc", eps_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc}, {"eps_next", eps_next}, {"accept_out", accept_out},
+                            {"log_alpha_out", log_alpha_out}, {"mom", mom}, {"kin0", kin0}, {"step_rows", step_rows}, {"adapt", adapt}};
+    const bool init = (flags & LSNF_HMC_INIT) != 0, inner = (flags & LSNF_HMC_INNER) != 0;
+    const Needed needed[] = {{"plan", plan}, {"eps_prop", eps_prop}, {"eps_acc", eps_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc},
+                             {"mom", mom}, {"kin0", kin0}, {"step_rows", step_rows},
+                             {"act_saved", act_saved, true, "(the stash of lsnf_forward, lsnf_restash or lsnf_reverse_keep)"},
+                             {"z_saved", z_saved, depth > 1, "(NULL) for depth > 1"}, {"eps_next", eps_next, inner, "(NULL) with LSNF_HMC_INNER"}};
+    const ChainStep s = {reads, writes, /*next=*/&writes[3], /*point=*/&reads[1], needed,
+                         LSNF_HMC_INIT | LSNF_HMC_INNER | LSNF_HMC_ADAPT | LSNF_HMC_ADAPT_LAST, init, inner,
+                         "LSNF_HMC_INIT or LSNF_HMC_INNER", plan, act_saved, noise, uniform, rng, /*step_size=*/1.0f, flags};
+    const RowSteps rows = {step_rows, adapt, da, flags};
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B) || s.scalars(ck) || s.phases(ck, accept_out, log_alpha_out) || rows.scalars(ck) ||
+        s.aliases(ck))
+        return ck.rc;
+    if (ck.empty) return LSNF_OK;
+    if (s.pointers(ck) || rows.pointers(ck)) return ck.rc;
+    LsnfReverseHmcRowsCall c;            // (no g_x / g_objective / g_z_in: the gradient at the point is consumed by the tail)
+    ck.head(c, plan, B, stream, {eps_prop, z_saved, grad_g, noise, eps_next, eps_acc, grad_acc, mom});
+    c.z_out = eps_prop; c.z_saved = z_saved; c.act_saved = act_saved;
+    c.grad_g = grad_g; c.noise = noise; c.step = 0.0f; c.eps_new = eps_next; c.rng = rng_args(rng);
+    c.chain = {energy_g, uniform, eps_acc, grad_acc, u_acc, accept_out, log_alpha_out, flags}; c.mom = mom; c.kin0 = kin0;
+    c.step_rows = step_rows; c.adapt = adapt; c.da = rows.args();
+    const Pick p = select_reverse_hmc_rows(c);
+    return report(ck.entry, p, lsnf_launch_small3_reverse_hmc_rows(c, p.st));
 }
 
 size_t lsnf_backward_params_workspace_floats(int nz, int width, int depth, int B) {

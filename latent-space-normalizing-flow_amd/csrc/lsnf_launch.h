@@ -59,6 +59,10 @@ struct LsnfMalaCall : LsnfBackwardCall {  // lsnf_mala_step: ll_mode 1 / ll_scal
 struct LsnfHmcCall : LsnfMalaCall {      // lsnf_hmc_step: the MALA call's tensors at a point of a trajectory; flags: LSNF_HMC_*
     float* mom = nullptr; float* kin0 = nullptr;      // the momentum (B, nz; read and written), the kinetic energy the trajectory began with (B)
 };
+struct LsnfHmcRowsCall : LsnfHmcCall {   // lsnf_hmc_step_rows: lv->step is not read; flags: LSNF_HMC_* with ADAPT / ADAPT_LAST
+    float* step_rows = nullptr; float* adapt = nullptr;      // each row's step (B), the rows' dual-averaging state (B, 4; ADAPT only)
+    LsnfDualAvgArgs da = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+};
 struct LsnfReverseBackwardCall : LsnfCall {      // lsnf_reverse_backward_z
     const float* z_out = nullptr; const float* z_saved = nullptr; const float* act_saved = nullptr;
     const float* g_x = nullptr; const float* g_objective = nullptr;
@@ -75,6 +79,10 @@ struct LsnfReverseMalaCall : LsnfReverseLangevinCall {      // lsnf_reverse_mala
 };
 struct LsnfReverseHmcCall : LsnfReverseMalaCall {      // lsnf_reverse_hmc_step: the base-space MALA call's tensors at a point of a
     float* mom = nullptr; float* kin0 = nullptr;      // trajectory; flags: LSNF_HMC_*.  mom (B, nz; read and written), kin0 (B)
+};
+struct LsnfReverseHmcRowsCall : LsnfReverseHmcCall {      // lsnf_reverse_hmc_step_rows: `step` is not read; flags as LsnfHmcRowsCall's
+    float* step_rows = nullptr; float* adapt = nullptr;
+    LsnfDualAvgArgs da = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 };
 struct LsnfContractCall : LsnfCall {     // steps (2), (3) of lsnf_backward_params: batch contraction of the dump, chain rule
     const float* const* params_host = nullptr; float* const* grads_host = nullptr;
@@ -147,11 +155,13 @@ int lsnf_small3_backward_st(const LsnfBackwardCall& c);
 hipError_t lsnf_launch_small3_backward_z(const LsnfBackwardCall& c, int st);
 hipError_t lsnf_launch_small3_mala(const LsnfMalaCall& c, int st);          // st: lsnf_small3_backward_st of the call
 hipError_t lsnf_launch_small3_hmc(const LsnfHmcCall& c, int st);            // st: lsnf_small3_backward_st of the call
+hipError_t lsnf_launch_small3_hmc_rows(const LsnfHmcRowsCall& c, int st);   // st: lsnf_small3_backward_st of the call
 int lsnf_small3_reverse_backward_st(const LsnfReverseBackwardCall& c);
 hipError_t lsnf_launch_small3_reverse_backward_z(const LsnfReverseBackwardCall& c, int st);
 hipError_t lsnf_launch_small3_reverse_langevin(const LsnfReverseLangevinCall& c, int st);      // st: of the same predicate
 hipError_t lsnf_launch_small3_reverse_mala(const LsnfReverseMalaCall& c, int st);              // st: of the same predicate
 hipError_t lsnf_launch_small3_reverse_hmc(const LsnfReverseHmcCall& c, int st);                // st: of the same predicate
+hipError_t lsnf_launch_small3_reverse_hmc_rows(const LsnfReverseHmcRowsCall& c, int st);       // st: of the same predicate
 
 bool lsnf_contract_x3_covers(const LsnfContractCall& c);                   // (also asked with NULL tensors: lsnf_api.hip dump_may_tile)
 hipError_t lsnf_launch_contract_x3(const LsnfContractCall& c, int chunk_override);

@@ -82,6 +82,10 @@ struct LsnfRngArgs {
     long long row0;                         // global index of this call's first row (sharded chains)
     int enabled;
 };
+// dual averaging of a per-row step size (include/lsnf_flow_mcmc.h LsnfDualAvg, the two logs taken on the host): lsnf_dual_avg.h
+struct LsnfDualAvgArgs {
+    float target_accept, gamma, t0, kappa, log_step_min, log_step_max;
+};
 struct LsnfLangevinArgs {
     const float* z_cur; const float* grad_g; const float* noise;
     float* z_new; float* gf_norm; float* gg_norm; float step;

@@ -5,7 +5,8 @@
 //   LSNF_S3B_TAIL    statements in front of the output    (nothing)                         | the accept / reject tail and `return;`
 //                    section, with the kernel's locals in scope
 // lsnf_small3_bwd.hip gives the first column and is compiled from the same tokens as before this file existed; lsnf_small3_mala.hip the second;
-// lsnf_small3_hmc.hip a third (lsnf_small3_hmc_kernel, Small3HmcArgs, the leapfrog tail and `return;`).
+// lsnf_small3_hmc.hip a third (lsnf_small3_hmc_kernel, Small3HmcArgs, the leapfrog tail and `return;`), lsnf_small3_hmcr.hip a fourth
+// (lsnf_small3_hmcr_kernel, Small3HmcRowsArgs, the per-row leapfrog tail and `return;`).
 #pragma once
 
 namespace {
@@ -56,6 +57,12 @@ struct Small3MalaArgs : Small3BwdArgs {
 // trajectory started with (B); flags: LSNF_HMC_INIT (1) as above, LSNF_HMC_INNER (2): a leapfrog step inside a trajectory
 struct Small3HmcArgs : Small3MalaArgs {
     float* mom; float* kin0;
+};
+// per-row HMC form (lsnf_small3_hmcr.hip): the HMC form's arrays, the step of each row (B; `step` is not read) and, with
+// LSNF_HMC_ADAPT (4; LSNF_HMC_ADAPT_LAST: 8), the rows' dual-averaging state (B, 4; 16-byte aligned) and its constants
+struct Small3HmcRowsArgs : Small3HmcArgs {
+    float* step_rows; float* adapt;
+    LsnfDualAvgArgs da;
 };
 
 __device__ __forceinline__ f32x4 mask4(f32x4 a, unsigned nib) {

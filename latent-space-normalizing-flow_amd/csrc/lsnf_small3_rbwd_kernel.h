@@ -8,7 +8,7 @@
 //                    section, with the kernel's locals in scope
 // lsnf_small3_rbwd.hip gives the first column and is compiled from the same tokens as before this file existed; lsnf_small3_rmala.hip
 // the second and lsnf_small3_rhmc.hip the third, both with UPDATE = false (their tails load e1, the first half of eps, themselves: in
-// front of their own barrier).
+// front of their own barrier); lsnf_small3_rhmcr.hip is the third column with a step per row (lsnf_small3_rhmcr_kernel, Small3RhmcRowsArgs).
 #pragma once
 
 namespace {
@@ -61,6 +61,12 @@ struct Small3RmalaArgs : Small3RlvArgs {
 // HMC form (lsnf_reverse_hmc_step): the MALA form's tensors at a point eps_prop of a trajectory; flags: LSNF_HMC_INIT (1), LSNF_HMC_INNER (2)
 struct Small3RhmcArgs : Small3RmalaArgs {
     float* mom; float* kin0;                       // the momentum (read and written), the kinetic energy the trajectory began with
+};
+// per-row HMC form (lsnf_reverse_hmc_step_rows, lsnf_small3_rhmcr.hip): the HMC form's tensors, the step of each row (B; `step` is
+// not read) and, with LSNF_HMC_ADAPT (4; LSNF_HMC_ADAPT_LAST: 8), the rows' dual-averaging state (B, 4; 16-byte aligned) and its constants
+struct Small3RhmcRowsArgs : Small3RhmcArgs {
+    float* step_rows; float* adapt;
+    LsnfDualAvgArgs da;
 };
 
 __device__ __forceinline__ f32x4 rb_mask4(f32x4 a, unsigned nib) {

@@ -4,9 +4,11 @@ restated (they are closures inside train.py and cannot be imported) on top of th
   sample_langevin_post_z_with_flow  <- train.py:307-335 (training) / :602-634 (testing: 20x steps, no noise)
   sample_mala_post_z_with_flow         the same chain Metropolis-adjusted (exact at any step size; per-row acceptance rate)
   sample_hmc_post_z_with_flow          Hamiltonian Monte Carlo on the same target: L leapfrog steps per accept / reject
+  sample_hmc_adaptive_post_z_with_flow    ... with a step per row, adapted on the device during a warm-up (dual averaging)
   sample_langevin_post_eps_with_flow   the same sampler in the flow's base space (eps, with z = f^-1(eps)); not in the reference
   sample_mala_post_eps_with_flow       the base-space chain Metropolis-adjusted (per-row acceptance rate)
   sample_hmc_post_eps_with_flow        Hamiltonian Monte Carlo in the base space: L leapfrog steps per accept / reject
+  sample_hmc_adaptive_post_eps_with_flow  ... with a step per row, adapted on the device during a warm-up (dual averaging)
   flow_mle_step                     <- train.py:404-415
   sample_x                          <- train.py:472-478 (prior samples for the FID evaluation)
 
@@ -119,6 +121,61 @@ def sample_hmc_post_z_with_flow(z, x, netG: nn.Module, netF, *, g_l_steps: int, 
             accepted += acc
     philox.advance(K + 1)
     return state.z.view(B, nz, 1, 1), accepted / K, state.energy
+
+
+def _adaptive_plan(g_l_steps, leapfrog_steps, warmup_steps, steps):
+    """(K, L, W) of an adaptive sampler, checked with `steps`; `mode(t)`: what end call t = 1 .. K does to the rows' steps."""
+    from . import flow
+    K, L, W = int(g_l_steps), int(leapfrog_steps), int(warmup_steps)
+    if steps is not None and not isinstance(steps, flow.HmcRowSteps):
+        raise flow.LsnfError("steps must be a flow.HmcRowSteps (new_hmc_row_steps()), or None")
+    if L < 1:
+        raise ValueError(f"leapfrog_steps must be >= 1 (got {leapfrog_steps})")
+    if W < 0 or (K >= 1 and W > K):
+        raise ValueError(f"warmup_steps must lie in 0 .. g_l_steps (got {warmup_steps} of {g_l_steps})")
+    return K, L, W, (lambda t: None if t > W else "last" if t == W else "update")
+
+
+def _row_steps(flow, steps, B, device, g_l_step_size, target_accept):
+    return flow.new_hmc_row_steps(B, device, g_l_step_size, target_accept=target_accept) if steps is None else steps
+
+
+def sample_hmc_adaptive_post_z_with_flow(z, x, netG: nn.Module, netF, *, g_l_steps: int, leapfrog_steps: int, warmup_steps: int,
+                                         g_l_step_size, g_llhd_sigma: float, philox, target_accept: float = 0.8, steps=None):
+    """`sample_hmc_post_z_with_flow` with a step per row, adapted during a warm-up: every row targets its own posterior
+    p(z | x_b), so every row gets its own leapfrog step, tuned on the device by dual averaging toward the acceptance rate
+    `target_accept` (Hoffman & Gelman 2014, as Stan and NumPyro do it) inside the kernel that decides a trajectory
+    (`netF.hmc_step_rows`) -- no host round trip, the flow's side of a step stays at its two launches.  The first `warmup_steps` of the
+    K = g_l_steps end calls adapt ("update"), the last of them writes the averaged step ("last"); the remaining K - warmup_steps
+    trajectories run at those frozen steps and are an exact chain.  g_l_step_size: the first step, a float or a (B) tensor (the
+    update's mu is log(10 * it)); `steps`: a `flow.HmcRowSteps` to go on from instead (g_l_step_size and target_accept are then
+    not read) -- it is updated in place.  Calls, draws and `philox` as `sample_hmc_post_z_with_flow`'s; with warmup_steps = 0 and a
+    float g_l_step_size the result is that sampler's, bit for bit.
+    Returns (z_k (B, nz, 1, 1), accept_rate (B) over the trajectories after the warm-up -- over all K when warmup_steps is 0 or K --,
+    U(z_k) (B), the `flow.HmcRowSteps`); g_l_steps = 0 or an empty batch returns the input (and None, None, `steps`)."""
+    from . import flow
+    K, L, W, mode = _adaptive_plan(g_l_steps, leapfrog_steps, warmup_steps, steps)
+    B, nz = z.shape[0], z.shape[1]
+    if K < 1 or B == 0:
+        return z.detach().clone().view(B, nz, 1, 1), None, None, steps
+    c = 1.0 / (2.0 * g_llhd_sigma * g_llhd_sigma)
+    z_prop = z.detach().reshape(B, nz).contiguous().clone()
+    steps = _row_steps(flow, steps, B, z_prop.device, g_l_step_size, target_accept)
+    state = flow.new_hmc_state(netF._plan(), B, z_prop.device)
+    accepted = torch.zeros(B, dtype=torch.float32, device=z_prop.device)
+    counted = K - W if W < K else K
+    for j in range(K * L + 1):
+        zr = z_prop.view(B, nz, 1, 1).detach().requires_grad_(True)
+        energy = c * ((netG(zr) - x) ** 2).flatten(1).sum(1)                                 # train.py:312-313, per row
+        grad_g = torch.autograd.grad(energy.sum(), zr)[0].reshape(B, nz).contiguous()        # train.py:314
+        t, inner = j // L, j % L != 0
+        _, acc, _, _ = netF.hmc_step_rows(z_prop, grad_g, energy.detach(), state, None if inner else philox.step(t), steps,
+                                          phase="inner" if inner else "end" if j else "init", propose=j < K * L, inplace=True,
+                                          reuse_buffers=True, adapt=None if inner or not j else mode(t))
+        if j and not inner and (t > W or counted == K):
+            accepted += acc
+    philox.advance(K + 1)
+    return state.z.view(B, nz, 1, 1), accepted / counted, state.energy, steps
 
 
 def sample_langevin_post_eps_with_flow(eps, x, netG: nn.Module, netF, *, g_l_steps: int, g_l_step_size: float,
@@ -289,6 +346,53 @@ def sample_hmc_post_eps_with_flow(eps, x, netG: nn.Module, netF, *, g_l_steps: i
         z = flow.reverse(plan, state.z, None)[0]
     philox.advance(K + 1)
     return state.z, z.view(B, nz, 1, 1), accepted / K, state.energy
+
+
+def sample_hmc_adaptive_post_eps_with_flow(eps, x, netG: nn.Module, netF, *, g_l_steps: int, leapfrog_steps: int, warmup_steps: int,
+                                           g_l_step_size, g_llhd_sigma: float, philox, target_accept: float = 0.8, steps=None):
+    """`sample_hmc_post_eps_with_flow` with a step per row, adapted during a warm-up -- the base-space twin of
+    `sample_hmc_adaptive_post_z_with_flow`, whose arguments these are: the first `warmup_steps` end calls adapt the rows' steps by dual
+    averaging inside `netF.reverse_hmc_step_rows` (the last of them writes the averaged step), the rest run at the frozen steps.
+    With warmup_steps = 0 and a float g_l_step_size the result is `sample_hmc_post_eps_with_flow`'s, bit for bit.
+    Returns (eps_k (B, nz), z_k = f^-1(eps_k) (B, nz, 1, 1), accept_rate (B) over the trajectories after the warm-up -- over all K
+    when warmup_steps is 0 or K --, U(eps_k) (B), the `flow.HmcRowSteps`).  g_l_steps = 0 or an empty batch returns the input without
+    a launch: (eps, None, None, None, `steps`), an empty batch with its empty z."""
+    from . import flow
+    K, L, W, mode = _adaptive_plan(g_l_steps, leapfrog_steps, warmup_steps, steps)
+    B, nz = eps.shape[0], eps.shape[1]
+    eps_prop = eps.detach().reshape(B, nz).contiguous().clone()
+    if B == 0:
+        return eps_prop, eps_prop.view(0, nz, 1, 1), None, None, steps
+    if K < 1:
+        return eps_prop, None, None, None, steps
+    plan = netF._plan()
+    c = 1.0 / (2.0 * g_llhd_sigma * g_llhd_sigma)
+    steps = _row_steps(flow, steps, B, eps_prop.device, g_l_step_size, target_accept)
+    keeps = flow.reverse_keep_supported(plan, B)
+    act = flow.new_act_saved(plan, B, eps_prop.device)
+    state = flow.new_hmc_state(plan, B, eps_prop.device)
+    accepted = torch.zeros(B, dtype=torch.float32, device=eps_prop.device)
+    counted = K - W if W < K else K
+    with torch.no_grad():
+        for j in range(K * L + 1):
+            if keeps:
+                z, _, saved = flow.reverse(plan, eps_prop, None, save_for_backward=True, act_saved=act)
+            else:
+                z, _ = flow.reverse(plan, eps_prop, None)
+                saved = flow.forward(plan, z, None, want_ll=False, save_for_backward=True, act_saved=act)[3]
+            with torch.enable_grad():
+                zr = z.view(B, nz, 1, 1).requires_grad_(True)
+                energy = c * ((netG(zr) - x) ** 2).flatten(1).sum(1)                                 # train.py:312-313, per row
+                grad_g = torch.autograd.grad(energy.sum(), zr)[0].reshape(B, nz).contiguous()        # train.py:314
+            t, inner = j // L, j % L != 0
+            _, acc, _ = netF.reverse_hmc_step_rows(eps_prop, saved, act, grad_g, energy.detach(), state, None if inner else philox.step(t),
+                                                   steps, phase="inner" if inner else "end" if j else "init", propose=j < K * L,
+                                                   inplace=True, reuse_buffers=True, adapt=None if inner or not j else mode(t))
+            if j and not inner and (t > W or counted == K):
+                accepted += acc
+        z = flow.reverse(plan, state.z, None)[0]
+    philox.advance(K + 1)
+    return state.z, z.view(B, nz, 1, 1), accepted / counted, state.energy, steps
 
 
 def flow_mle_step(netF, optF, z_g_k, f_max_norm: Optional[float] = None, fused: bool = False):

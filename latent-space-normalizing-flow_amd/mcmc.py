@@ -1,15 +1,18 @@
 """Markov-chain extensions of the functional host API (C: include/lsnf_flow_mcmc.h), re-exported by flow.py -- use them as
 `flow.mala_step`, `flow.reverse_mala_step`, `flow.MalaState`, `flow.new_mala_state`, `flow.hmc_step`, `flow.reverse_hmc_step`,
-`flow.HmcState`, `flow.new_hmc_state`.  Every tensor goes through flow.py's one checking path before anything is
+`flow.HmcState`, `flow.new_hmc_state`, `flow.hmc_step_rows`, `flow.reverse_hmc_step_rows`, `flow.HmcRowSteps`,
+`flow.new_hmc_row_steps`.  Every tensor goes through flow.py's one checking path before anything is
 launched; like there, all functions raise on CPU tensors: there is no CPU path."""
 from __future__ import annotations
 
 from dataclasses import dataclass, fields
 from typing import Optional
 
+import ctypes
+
 import torch
 
-from ._lib import LsnfError
+from ._lib import LsnfDualAvg, LsnfError
 from .flow import (FlowPlan, PhiloxNoise, _anchor, _call, _check_in, _check_like, _check_out, _check_stash, _noise_args, _plan_head,  # noqa: F401
                    _ptr, _stream_buffers, forward, new_act_saved)
 
@@ -231,4 +234,117 @@ def reverse_hmc_step(plan: FlowPlan, eps_prop: torch.Tensor, z_saved: Optional[t
     _call("lsnf_reverse_hmc_step", dev, *_plan_head(plan), B, _ptr(eps_prop), _ptr(z_saved), _ptr(act_saved), _ptr(grad_g), _ptr(energy_g),
           _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(state.mom), _ptr(state.kin), _ptr(noise), _ptr(uniform), rng,
           float(step_size), _HMC_PHASES[phase], _ptr(eps_next), _ptr(acc), _ptr(la))
+    return eps_next, acc, la
+
+
+HMC_ADAPT, HMC_ADAPT_LAST = 4, 8      # include/lsnf_flow_mcmc.h LSNF_HMC_ADAPT, LSNF_HMC_ADAPT_LAST
+_HMC_ADAPT = {None: 0, "update": HMC_ADAPT, "last": HMC_ADAPT | HMC_ADAPT_LAST}
+
+
+@dataclass
+class HmcRowSteps:
+    """The step of every row of a Hamiltonian Monte Carlo chain (`hmc_step_rows`, `reverse_hmc_step_rows`) and the state of its
+    adaptation: step (B), read by every call and written only by an adapting end call; adapt (B, 4) = {log_step_bar, hbar, count,
+    mu} per row, the dual-averaging state (Hoffman & Gelman 2014; mu = log(10 * the first step), set by `new_hmc_row_steps`); and
+    the update's constants (include/lsnf_flow_mcmc.h `LsnfDualAvg`)."""
+    step: torch.Tensor
+    adapt: torch.Tensor
+    target_accept: float = 0.8
+    gamma: float = 0.05
+    t0: float = 10.0
+    kappa: float = 0.75
+    step_min: float = 1e-4
+    step_max: float = 1e2
+
+
+def new_hmc_row_steps(B: int, device, step_size, target_accept: float = 0.8, gamma: float = 0.05, t0: float = 10.0, kappa: float = 0.75,
+                      step_min: float = 1e-4, step_max: float = 1e2) -> HmcRowSteps:
+    """The steps of B rows, all `step_size` (a float) or row b's `step_size[b]` (a (B) tensor), with a fresh adaptation state:
+    count = hbar = log_step_bar = 0, mu = log(10 * step) in fp32."""
+    B = int(B)
+    if isinstance(step_size, torch.Tensor):
+        if step_size.numel() != B:
+            raise LsnfError(f"step_size has {step_size.numel()} elements, the chain {B} rows")
+        step = step_size.detach().to(device=device, dtype=torch.float32).reshape(B).contiguous().clone()
+    else:
+        step = torch.full((B,), float(step_size), dtype=torch.float32, device=device)
+    adapt = torch.zeros((B, 4), dtype=torch.float32, device=device)
+    adapt[:, 3] = torch.log(10.0 * step)
+    return HmcRowSteps(step, adapt, float(target_accept), float(gamma), float(t0), float(kappa), float(step_min), float(step_max))
+
+
+def _row_step_mode(steps, phase, adapt):
+    """What the per-row calls check before `_check_chain`, tensors apart: `steps` is an `HmcRowSteps`, the phase and the adaptation
+    mode are known ones, and the mode goes with an end call.  Returns the call's flags."""
+    if phase not in _HMC_PHASES:
+        raise LsnfError(f"phase must be one of 'init', 'inner', 'end' (got {phase!r})")
+    if not isinstance(steps, HmcRowSteps):
+        raise LsnfError("steps must be a flow.HmcRowSteps (new_hmc_row_steps())")
+    if adapt not in _HMC_ADAPT:
+        raise LsnfError(f"adapt must be None, 'update' or 'last' (got {adapt!r})")
+    if adapt is not None and phase != "end":
+        raise LsnfError("the steps adapt on the decision of an end call: adapt goes with phase='end'")
+    return _HMC_PHASES[phase] | _HMC_ADAPT[adapt]
+
+
+def _row_step_args(steps, B, dev, adapt):
+    """After `_check_chain`: the two arrays of `steps` through the one checking path (B steps, B quads, on the call's device).
+    Returns the three arguments of the C call: step_rows, adapt (None unless adapting), the LsnfDualAvg (likewise)."""
+    _check_out(steps.step, "steps.step", B, dev)
+    _check_out(steps.adapt, "steps.adapt", 4 * B, dev)
+    if adapt is None:
+        return _ptr(steps.step), None, None
+    da = LsnfDualAvg(steps.target_accept, steps.gamma, steps.t0, steps.kappa, steps.step_min, steps.step_max)
+    return _ptr(steps.step), _ptr(steps.adapt), ctypes.byref(da)
+
+
+def hmc_step_rows(plan: FlowPlan, z_prop: torch.Tensor, grad_g: Optional[torch.Tensor], energy_g: Optional[torch.Tensor],
+                  state: HmcState, noise, steps: HmcRowSteps, *, phase: str = "end", uniform: Optional[torch.Tensor] = None,
+                  propose: bool = True, inplace: bool = False, reuse_buffers: bool = False, adapt: Optional[str] = None):
+    """`hmc_step` with a step per row (include/lsnf_flow_mcmc.h `lsnf_hmc_step_rows`): row b runs at steps.step[b] and, without
+    adapt, gets the bits of `hmc_step` at that scalar in every phase.  adapt (end calls only): "update" finishes and decides the
+    trajectory at the old step, then -- inside the kernel, per row, from its own log_alpha -- updates steps.adapt by dual averaging
+    toward steps.target_accept and writes the new step, with which the next trajectory begins (propose); "last" writes the
+    averaged step exp(log_step_bar) instead: the call that ends a warm-up, after which the chain is exact.  Everything else, and
+    what is returned, is `hmc_step`'s."""
+    flags, inner = _row_step_mode(steps, phase, adapt), phase == "inner"
+    B, dev, noise, rng = _check_chain(plan, z_prop, "z_prop", grad_g, energy_g, state, HmcState, noise, uniform)
+    step_ptr, adapt_ptr, da = _row_step_args(steps, B, dev, adapt)
+    if inner and (noise is not None or rng is not None or uniform is not None or not propose):
+        raise LsnfError("an inner leapfrog step draws and decides nothing: noise and uniform must be None, propose True")
+    bufs, z1, ll = _forward_at(plan, z_prop, B, dev, "_hmc_buffers", reuse_buffers)
+    z_next = None if not propose else z_prop if inplace else torch.empty_like(z_prop)
+    acc, la = (None, None) if inner else (bufs["acc"], bufs["la"])
+    _call("lsnf_hmc_step_rows", dev, *_plan_head(plan), B, _ptr(z_prop), _ptr(z1), _ptr(bufs["saved"]), _ptr(bufs["act"]), _ptr(ll),
+          _ptr(grad_g), _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(state.mom), _ptr(state.kin), _ptr(noise),
+          _ptr(uniform), rng, step_ptr, adapt_ptr, da, flags, _ptr(z_next), _ptr(acc), _ptr(la))
+    return z_next, acc, la, ll
+
+
+def reverse_hmc_step_rows(plan: FlowPlan, eps_prop: torch.Tensor, z_saved: Optional[torch.Tensor], act_saved: torch.Tensor,
+                          grad_g: Optional[torch.Tensor], energy_g: Optional[torch.Tensor], state: HmcState, noise, steps: HmcRowSteps, *,
+                          phase: str = "end", uniform: Optional[torch.Tensor] = None, propose: bool = True, inplace: bool = False,
+                          reuse_buffers: bool = False, adapt: Optional[str] = None):
+    """`reverse_hmc_step` with a step per row (include/lsnf_flow_mcmc.h `lsnf_reverse_hmc_step_rows`): row b runs at steps.step[b]
+    and, without adapt, gets the bits of `reverse_hmc_step` at that scalar in every phase.  adapt: as `hmc_step_rows`'s -- "update"
+    / "last" on an end call adapt the rows' steps by dual averaging inside the kernel, after the decision at the old step and
+    before the next trajectory begins.  ONE launch and nothing else, so an adaptive chain can be captured in a graph.  Everything
+    else, and what is returned, is `reverse_hmc_step`'s."""
+    flags, inner = _row_step_mode(steps, phase, adapt), phase == "inner"
+    B, dev, noise, rng = _check_chain(plan, eps_prop, "eps_prop", grad_g, energy_g, state, HmcState, noise, uniform,
+                                      stash=(z_saved, act_saved))
+    step_ptr, adapt_ptr, da = _row_step_args(steps, B, dev, adapt)
+    if inner and (noise is not None or rng is not None or uniform is not None or not propose):
+        raise LsnfError("an inner leapfrog step draws and decides nothing: noise and uniform must be None, propose True")
+    acc = la = None
+    if not inner:
+        def make():
+            f32 = dict(dtype=torch.float32, device=dev)
+            return {"acc": torch.empty(B, **f32), "la": torch.empty(B, **f32)}
+        bufs = _stream_buffers(plan, "_rhmc_buffers", B, dev, make) if reuse_buffers else make()
+        acc, la = bufs["acc"], bufs["la"]
+    eps_next = None if not propose else eps_prop if inplace else torch.empty_like(eps_prop)
+    _call("lsnf_reverse_hmc_step_rows", dev, *_plan_head(plan), B, _ptr(eps_prop), _ptr(z_saved), _ptr(act_saved), _ptr(grad_g),
+          _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(state.mom), _ptr(state.kin), _ptr(noise), _ptr(uniform),
+          rng, step_ptr, adapt_ptr, da, flags, _ptr(eps_next), _ptr(acc), _ptr(la))
     return eps_next, acc, la

@@ -499,6 +499,23 @@ class _netF(nn.Module):
                                      det(noise), step_size, phase=phase, uniform=det(uniform), propose=propose, inplace=inplace,
                                      reuse_buffers=reuse_buffers)
 
+    def hmc_step_rows(self, z_prop, grad_g=None, energy_g=None, state=None, noise=None, steps=None, *, phase="end", uniform=None,
+                      propose=True, inplace=False, reuse_buffers=False, adapt=None):
+        """`hmc_step` with a step per row (`flow.hmc_step_rows`; steps: a `flow.HmcRowSteps`); adapt="update" / "last" on an end
+        call adapts the rows' steps by dual averaging inside the kernel.  Returns what `hmc_step` returns."""
+        det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t
+        return flow.hmc_step_rows(self._plan(), det(z_prop), det(grad_g), det(energy_g), state, det(noise), steps, phase=phase,
+                                  uniform=det(uniform), propose=propose, inplace=inplace, reuse_buffers=reuse_buffers, adapt=adapt)
+
+    def reverse_hmc_step_rows(self, eps_prop, z_saved, act_saved, grad_g=None, energy_g=None, state=None, noise=None, steps=None, *,
+                              phase="end", uniform=None, propose=True, inplace=False, reuse_buffers=False, adapt=None):
+        """`reverse_hmc_step` with a step per row (`flow.reverse_hmc_step_rows`; steps: a `flow.HmcRowSteps`); adapt="update" /
+        "last" on an end call adapts the rows' steps by dual averaging inside the kernel.  Returns what `reverse_hmc_step` returns."""
+        det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t
+        return flow.reverse_hmc_step_rows(self._plan(), det(eps_prop), det(z_saved), det(act_saved), det(grad_g), det(energy_g), state,
+                                          det(noise), steps, phase=phase, uniform=det(uniform), propose=propose, inplace=inplace,
+                                          reuse_buffers=reuse_buffers, adapt=adapt)
+
     def mle_grads(self, z, accumulate: bool = False, max_norm: Optional[float] = None, reuse_buffers: bool = False):
         """Fused flow-MLE gradients (train.py:404-411): loss_f = -mean_b ll(z_b) and d loss_f / d theta written to
         `.grad` of the 60 live tensors -- forward (ll summed in-kernel), dump backward, batch contraction, unfold:
