@@ -119,7 +119,8 @@
  * ---- Hamiltonian Monte Carlo in the flow's base space (lsnf_reverse_hmc_step) ------------------------------------------------------
  * The target and the gradient of lsnf_reverse_mala_step -- pi(eps) ~ exp(-U(eps)), U(eps) = |eps|^2 / 2 + energy_g, grad U = eps + g,
  * g = J_{f^-1}(eps)^T grad_g with the bits of lsnf_reverse_backward_z(g_x = grad_g, g_objective = NULL) -- with a momentum p ~ N(0, I):
- * the flow has whitened the prior, so the identity mass matrix is the right one.  eps_prop / z_saved / act_saved are the reverse's
+ * the flow has whitened the prior, so the identity mass matrix is the right one for the prior alone (an informative likelihood makes
+ * the posterior in eps anisotropic again: lsnf_reverse_hmc_step_metric below).  eps_prop / z_saved / act_saved are the reverse's
  * input, the block outputs and the stash AT x = f^-1(eps_prop) (lsnf_reverse_keep, lsnf_forward at x or lsnf_restash); the caller's
  * generator runs between the reverse and this ONE launch, which finishes the work at the point eps_prop of a trajectory and produces
  * the next point.  From a state (e_s, t_s = grad U(e_s), u_s = U(e_s)), every line in fp32 with the operations and the order written,
@@ -196,7 +197,48 @@
  *     exactly invariant; it is from the call with LSNF_HMC_ADAPT_LAST on, which leaves the averaged step for the calls that follow.
  * Kernels: lsnf_small3_hmcr_kernel / lsnf_small3_rhmcr_kernel, the scalar kernels' stages with the per-row tail, the same
  * instantiations and workgroup shapes; a row's bits -- its new step and adapt included -- do not depend on B, the workgroup shape
- * or rng->row0 sharding.  With L = 1 the calls are the adaptive MALA step in exact arithmetic, as the scalar calls are MALA's. */
+ * or rng->row0 sharding.  With L = 1 the calls are the adaptive MALA step in exact arithmetic, as the scalar calls are MALA's.
+ *
+ * ---- A diagonal metric per row, estimated in warm-up windows on the device (lsnf_hmc_step_metric, lsnf_reverse_hmc_step_metric) ------
+ * Without a metric the stiffest coordinate of a row's posterior sets its step, in z and -- once the likelihood is informative -- in
+ * the base space as well (the flow whitens the prior, not the posterior).  Row b has a positive scale per column, sd[b, c]: the
+ * square root of the diagonal inverse mass (Stan's inv_e_metric, as a standard deviation).  The chain is HMC with identity mass in
+ * the coordinate y = z / sd: the momentum q ~ N(0, I) lives in that coordinate, so kin0, kinL, the reductions and the decision are the
+ * per-row call's, untouched, and the only change is one more multiply in two products.  The two entry points are the per-row calls
+ * with `float* scale_rows, float* mean_rows, float* m2_rows, float* count_rows, const LsnfMetricReg* reg` inserted between da and
+ * flags.  Everything fp32, no fused multiply-add; s is the row's step, hs = 0.5f * s; the parentheses are the rule -- sd * g and
+ * sd * qh are each ONE rounded product, formed first:
+ *   begin   kin0 = 0.5f * sum_c xi^2;   qh = xi  - hs * (sd * g_s);     z_next = z_s    + s * (sd * qh);   mom <- qh
+ *   inner   g = grad_g + d(-ll)/dz;     qh = mom - s  * (sd * g);       z_next = z_prop + s * (sd * qh);   mom <- qh
+ *   end     qL = mom - hs * (sd * g_prop);   kinL = 0.5f * sum_c qL^2;   log_alpha, accept, state update: lsnf_hmc_step_rows' lines
+ * (lsnf_reverse_hmc_step_metric: the same with t = eps + g in place of g, from lsnf_reverse_hmc_step_rows' lines.)  Hence, exactly:
+ * (1) with sd == 1.0f everywhere a row's outputs in every phase are the per-row call's, bit for bit;
+ * (2) with sd == 2^k on every column of a row, a row's outputs at step s are the per-row call's at step s * 2^k, bit for bit (every
+ *     product is then an exact scaling), wherever no intermediate overflows or becomes subnormal.
+ *   scale_rows (B,nz): sd.  Every phase reads it; only a call with LSNF_HMC_METRIC_CLOSE writes it.  Always required.
+ *   mean_rows (B,nz), m2_rows (B,nz), count_rows (B): the Welford accumulators of the row's running window (a fresh window: zeros)
+ *   reg: the close's constants (host memory, read during the call only): all finite, n0 >= 0, var0 >= 0, scale_min > 0,
+ *       scale_max >= scale_min.  Stan's: n0 = 5, var0 = 1e-3.
+ *   mean_rows, m2_rows, count_rows and reg are required with LSNF_HMC_METRIC_FOLD and must be NULL without it
+ *   flags: the per-row call's; LSNF_HMC_METRIC_FOLD with an end call only (refused with INIT or INNER), LSNF_HMC_METRIC_CLOSE with
+ *       LSNF_HMC_METRIC_FOLD only; unknown bits are refused
+ *   the four arrays are outputs in the sense of the aliasing rule: they may alias nothing else the call touches
+ *   every other argument, rule, draw and refusal is the per-row call's, word for word
+ * FOLD: the end call folds the state AFTER its decision, x = z_prop on accepted rows and z_acc on rejected ones (eps_prop / eps_acc),
+ * into the row's accumulators, before the next trajectory begins (per column; count per row):
+ *         n = count + 1;   d = x - mean;   mean' = mean + d / n;   m2' = m2 + d * (x - mean');   count' = n
+ * CLOSE: the same call, after the fold:
+ *         n >= 2:  v = (n / (n + n0)) * (m2' / (n - 1)) + var0 * (n0 / (n + n0));   sd' = fminf(fmaxf(sqrtf(v), scale_min), scale_max)
+ *         n <  2:  sd' = sd (the bits are kept)
+ *     stores sd', stores zeros for mean, m2 and count, begins the next trajectory with sd' if a next point is asked for (mom, with no
+ *     next point, is the full-step momentum at the OLD step and the OLD scale) and, with LSNF_HMC_ADAPT and without
+ *     LSNF_HMC_ADAPT_LAST, stores the dual-averaging quad as {0, 0, 0, logf(10.0f * s')}, s' the step this call's update wrote:
+ *     Stan's restart of the step adaptation at a window's end.  (A variance that is NaN closes at scale_min.)
+ * A row's scale is fixed before its momentum is drawn and constant within a trajectory, exactly as its step is.  While scales change
+ * the chain is not exactly invariant; from the last close on it is.
+ * Kernels: lsnf_small3_hmcm_kernel / lsnf_small3_rhmcm_kernel, the per-row kernels' stages, instantiations and workgroup shapes; sd,
+ * mean and m2 are read and written by the lane that owns their columns, so a row's bits -- scale and accumulators included -- do not
+ * depend on B, the workgroup shape or rng->row0 sharding.  B = 0 succeeds without a launch. */
 #ifndef LSNF_FLOW_MCMC_H
 #define LSNF_FLOW_MCMC_H
 
@@ -252,6 +294,27 @@ int lsnf_reverse_hmc_step_rows(const float* plan, int nz, int width, int depth, 
                                const float* noise, const float* uniform, const LsnfRng* rng,
                                float* step_rows, float* adapt, const LsnfDualAvg* da, unsigned flags,
                                float* eps_next, float* accept_out, float* log_alpha_out, void* stream);
+
+/* a diagonal metric per row: the regularisation of a window's variance and the clamp of the scale; Stan's n0 = 5, var0 = 1e-3 */
+typedef struct LsnfMetricReg { float n0, var0, scale_min, scale_max; } LsnfMetricReg;
+#define LSNF_HMC_METRIC_FOLD  16u   /* end calls only: fold the state after the decision into the row's window */
+#define LSNF_HMC_METRIC_CLOSE 32u   /* with METRIC_FOLD: close the window -- write the new scale, zero the accumulators */
+int lsnf_hmc_step_metric(const float* plan, int nz, int width, int depth, int coupling, int B,
+                         const float* z_prop, const float* z_out, const float* z_saved, const float* act_saved,
+                         const float* ll_prop, const float* grad_g, const float* energy_g,
+                         float* z_acc, float* grad_acc, float* u_acc, float* mom, float* kin0,
+                         const float* noise, const float* uniform, const LsnfRng* rng,
+                         float* step_rows, float* adapt, const LsnfDualAvg* da,
+                         float* scale_rows, float* mean_rows, float* m2_rows, float* count_rows, const LsnfMetricReg* reg, unsigned flags,
+                         float* z_next, float* accept_out, float* log_alpha_out, void* stream);
+int lsnf_reverse_hmc_step_metric(const float* plan, int nz, int width, int depth, int coupling, int B,
+                                 const float* eps_prop, const float* z_saved, const float* act_saved,
+                                 const float* grad_g, const float* energy_g,
+                                 float* eps_acc, float* grad_acc, float* u_acc, float* mom, float* kin0,
+                                 const float* noise, const float* uniform, const LsnfRng* rng,
+                                 float* step_rows, float* adapt, const LsnfDualAvg* da,
+                                 float* scale_rows, float* mean_rows, float* m2_rows, float* count_rows, const LsnfMetricReg* reg, unsigned flags,
+                                 float* eps_next, float* accept_out, float* log_alpha_out, void* stream);
 
 #ifdef __cplusplus
 }

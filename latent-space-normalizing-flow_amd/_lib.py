@@ -26,6 +26,11 @@ class LsnfDualAvg(ctypes.Structure):
                 ("step_max", c_float)]
 
 
+class LsnfMetricReg(ctypes.Structure):
+    """include/lsnf_flow_mcmc.h `LsnfMetricReg`: the constants with which lsnf_hmc_step_metric closes a warm-up window."""
+    _fields_ = [("n0", c_float), ("var0", c_float), ("scale_min", c_float), ("scale_max", c_float)]
+
+
 class LsnfAdamOptions(ctypes.Structure):
     """include/lsnf_flow.h `LsnfAdamOptions`: the arguments of lsnf_adam_step_ex."""
     _fields_ = [("struct_bytes", ctypes.c_uint), ("flags", ctypes.c_uint), ("lr", c_double), ("lr_dev", c_void_p),
@@ -121,6 +126,20 @@ _EXT_SIGNATURES = {
                                            c_void_p, c_void_p, ctypes.POINTER(LsnfRng),
                                            c_void_p, c_void_p, ctypes.POINTER(LsnfDualAvg), ctypes.c_uint,
                                            c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lsnf_hmc_step_metric": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, ctypes.POINTER(LsnfRng),
+                                     c_void_p, c_void_p, ctypes.POINTER(LsnfDualAvg),
+                                     c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(LsnfMetricReg), ctypes.c_uint,
+                                     c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lsnf_reverse_hmc_step_metric": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, ctypes.POINTER(LsnfRng),
+                                             c_void_p, c_void_p, ctypes.POINTER(LsnfDualAvg),
+                                             c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(LsnfMetricReg), ctypes.c_uint,
+                                             c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -270,6 +270,36 @@ struct RowSteps {
     }
 };
 
+// The rules a metric per row adds (lsnf_hmc_step_metric, lsnf_reverse_hmc_step_metric), stated once, beside RowSteps' and applied after
+// them: scalars() before the empty-batch return (reg is host memory), pointers() with the pointers of a non-empty call.  scale_rows
+// itself is among the entry point's `needed` and `writes` (required, 4-byte aligned, an output for the aliasing rule).
+struct RowMetric {
+    const float* mean; const float* m2; const float* count; const LsnfMetricReg* reg; unsigned flags;
+    bool folding() const { return (flags & LSNF_HMC_METRIC_FOLD) != 0; }
+    bool scalars(Check& ck) const {
+        if (ck.refuse(folding() && (flags & (LSNF_HMC_INIT | LSNF_HMC_INNER)),
+                      "flags: LSNF_HMC_METRIC_FOLD goes with an end call (neither LSNF_HMC_INIT nor LSNF_HMC_INNER)") ||
+            ck.refuse((flags & LSNF_HMC_METRIC_CLOSE) && !folding(), "flags: LSNF_HMC_METRIC_CLOSE goes with LSNF_HMC_METRIC_FOLD") ||
+            ck.refuse(folding() && !reg, "reg is required with LSNF_HMC_METRIC_FOLD") ||
+            ck.refuse(!folding() && (mean || m2 || count || reg),
+                      "mean_rows, m2_rows, count_rows and reg must be NULL without LSNF_HMC_METRIC_FOLD"))
+            return true;
+        if (!reg) return false;
+        const float f[] = {reg->n0, reg->var0, reg->scale_min, reg->scale_max};
+        for (float v : f)
+            if (ck.refuse(!std::isfinite(v), "reg: every field must be finite (got %g)", (double)v)) return true;
+        return ck.refuse(!(reg->n0 >= 0.0f), "reg->n0 must not be negative (got %g)", (double)reg->n0) ||
+               ck.refuse(!(reg->var0 >= 0.0f), "reg->var0 must not be negative (got %g)", (double)reg->var0) ||
+               ck.refuse(!(reg->scale_min > 0.0f), "reg->scale_min must be positive (got %g)", (double)reg->scale_min) ||
+               ck.refuse(reg->scale_max < reg->scale_min, "reg->scale_max must not be below reg->scale_min (got %g < %g)",
+                         (double)reg->scale_max, (double)reg->scale_min);
+    }
+    bool pointers(Check& ck) const {
+        return ck.refuse(folding() && !(mean && m2 && count), "mean_rows, m2_rows and count_rows are required with LSNF_HMC_METRIC_FOLD");
+    }
+    LsnfMetricArgs args() const { return reg ? LsnfMetricArgs{reg->n0, reg->var0, reg->scale_min, reg->scale_max} : LsnfMetricArgs{0.f, 0.f, 0.f, 0.f}; }
+};
+
 // ---- kernel selection: each operation decides on the host, from the kernels' coverage predicates, which kernel(s) a call
 // runs, BEFORE anything is launched; the entry point then launches exactly that.  A launcher reached outside what it covers
 // is a selection bug and fails the call (LSNF_E_HIP, the kernel named in lsnf_last_error()); nothing falls through to another
@@ -279,7 +309,7 @@ enum Kernel {
     K_REV, K_REV3, K_REV2H_FIXUP, K_SMALL_REV, K_SMALL3_REV,
     K_BWD, K_BWD3, K_SMALL_BWD, K_SMALL3_BWD,
     K_SMALL3_RBWD, K_SMALL3_RLV, K_SMALL3_MALA, K_SMALL3_RMALA, K_SMALL3_HMC, K_SMALL3_RHMC,
-    K_SMALL3_HMCR, K_SMALL3_RHMCR,
+    K_SMALL3_HMCR, K_SMALL3_RHMCR, K_SMALL3_HMCM, K_SMALL3_RHMCM,
 };
 const char* const kKernelName[] = {
     "no kernel takes this call", "lsnf_fwd_kernel", "lsnf_fwd3b_kernel", "lsnf_fwd3q_kernel",
@@ -289,7 +319,7 @@ const char* const kKernelName[] = {
     "lsnf_bwd_z_kernel", "lsnf_bwd3_kernel", "lsnf_small_bwd_kernel", "lsnf_small3_bwd_kernel",
     "lsnf_small3_rbwd_kernel", "lsnf_small3_rbwd_kernel (update form)", "lsnf_small3_mala_kernel", "lsnf_small3_rmala_kernel",
     "lsnf_small3_hmc_kernel", "lsnf_small3_rhmc_kernel",
-    "lsnf_small3_hmcr_kernel", "lsnf_small3_rhmcr_kernel",
+    "lsnf_small3_hmcr_kernel", "lsnf_small3_rhmcr_kernel", "lsnf_small3_hmcm_kernel", "lsnf_small3_rhmcm_kernel",
 };
 struct Pick { Kernel k; int st = 0; };     // st: rows per workgroup / 16 of the small3 kernels
 
@@ -497,6 +527,9 @@ Pick select_reverse_hmc(const LsnfReverseHmcCall& c) { return {K_SMALL3_RHMC, ls
 // (lsnf_small3_hmcr.hip, lsnf_small3_rhmcr.hip), the same instantiations, the same rule for the workgroup shape.
 Pick select_hmc_rows(const LsnfHmcRowsCall& c) { return {K_SMALL3_HMCR, lsnf_small3_backward_st(c)}; }
 Pick select_reverse_hmc_rows(const LsnfReverseHmcRowsCall& c) { return {K_SMALL3_RHMCR, lsnf_small3_reverse_backward_st(c)}; }
+// The two with a metric per row (lsnf_hmc_step_metric, lsnf_reverse_hmc_step_metric): lsnf_small3_hmcm.hip, lsnf_small3_rhmcm.hip, likewise.
+Pick select_hmc_metric(const LsnfHmcMetricCall& c) { return {K_SMALL3_HMCM, lsnf_small3_backward_st(c)}; }
+Pick select_reverse_hmc_metric(const LsnfReverseHmcMetricCall& c) { return {K_SMALL3_RHMCM, lsnf_small3_reverse_backward_st(c)}; }
 
 // Batch contraction of the parameter gradients (LsnfContraction): on the bf16 matrix pipe where lsnf_params3.hip covers the
 // call (use_x3); from 4 096 rows the fp32-MFMA kernel through LDS, with the widest row loads the rows allow -- every row the
@@ -1072,6 +1105,86 @@ int lsnf_reverse_hmc_step_rows(const float* plan, int nz, int width, int depth, 
     c.step_rows = step_rows; c.adapt = adapt; c.da = rows.args();
     const Pick p = select_reverse_hmc_rows(c);
     return report(ck.entry, p, lsnf_launch_small3_reverse_hmc_rows(c, p.st));
+}
+
+// The two HMC entries with a metric per row: the per-row entries' tables and rules, the scales and the window's accumulators among the
+// outputs (so that they alias nothing else of the call) and among the row tensors that decide the row-access width, RowMetric's rules
+// after RowSteps'.
+int lsnf_hmc_step_metric(const float* plan, int nz, int width, int depth, int coupling, int B, const float* z_prop, const float* z_out,
+                         const float* z_saved, const float* act_saved, const float* ll_prop, const float* grad_g, const float* energy_g,
+                         float* z_acc, float* grad_acc, float* u_acc, float* mom, float* kin0, const float* noise, const float* uniform,
+                         const LsnfRng* rng, float* step_rows, float* adapt, const LsnfDualAvg* da, float* scale_rows, float* mean_rows,
+                         float* m2_rows, float* count_rows, const LsnfMetricReg* reg, unsigned flags, float* z_next, float* accept_out,
+                         float* log_alpha_out, void* stream) {
+    Check ck{"lsnf_hmc_step_metric"};
+    const Named reads[] = {{"plan", plan}, {"z_prop", z_prop}, {"z_out", z_out}, {"z_saved", z_saved}, {"act_saved", act_saved},
+                           {"ll_prop", ll_prop}, {"grad_g", grad_g}, {"energy_g", energy_g}, {"noise", noise}, {"uniform", uniform}};
+    const Named writes[] = {{"z_acc", z_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc}, {"z_next", z_next}, {"accept_out", accept_out},
+                            {"log_alpha_out", log_alpha_out}, {"mom", mom}, {"kin0", kin0}, {"step_rows", step_rows}, {"adapt", adapt},
+                            {"scale_rows", scale_rows}, {"mean_rows", mean_rows}, {"m2_rows", m2_rows}, {"count_rows", count_rows}};
+    const bool init = (flags & LSNF_HMC_INIT) != 0, inner = (flags & LSNF_HMC_INNER) != 0;
+    const Needed needed[] = {{"plan", plan}, {"z_prop", z_prop}, {"z_out", z_out}, {"act_saved", act_saved}, {"z_acc", z_acc},
+                             {"grad_acc", grad_acc}, {"u_acc", u_acc}, {"mom", mom}, {"kin0", kin0}, {"step_rows", step_rows},
+                             {"scale_rows", scale_rows},
+                             {"ll_prop", ll_prop, !inner, "(NULL) unless LSNF_HMC_INNER"}, {"z_saved", z_saved, depth > 1, "(NULL) for depth > 1"},
+                             {"z_next", z_next, inner, "(NULL) with LSNF_HMC_INNER"}};
+    const ChainStep s = {reads, writes, /*next=*/&writes[3], /*point=*/&reads[1], needed,
+                         LSNF_HMC_INIT | LSNF_HMC_INNER | LSNF_HMC_ADAPT | LSNF_HMC_ADAPT_LAST | LSNF_HMC_METRIC_FOLD | LSNF_HMC_METRIC_CLOSE,
+                         init, inner, "LSNF_HMC_INIT or LSNF_HMC_INNER", plan, act_saved, noise, uniform, rng, /*step_size=*/1.0f, flags};
+    const RowSteps rows = {step_rows, adapt, da, flags};
+    const RowMetric metric = {mean_rows, m2_rows, count_rows, reg, flags};
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B) || s.scalars(ck) || s.phases(ck, accept_out, log_alpha_out) || rows.scalars(ck) ||
+        metric.scalars(ck) || s.aliases(ck))
+        return ck.rc;
+    if (ck.empty) return LSNF_OK;
+    if (s.pointers(ck) || rows.pointers(ck) || metric.pointers(ck)) return ck.rc;
+    const LsnfLangevinArgs lv = {z_prop, grad_g, noise, z_next, nullptr, nullptr, 0.0f, rng_args(rng)};
+    LsnfHmcMetricCall c;                 // (no g_z1 / g_logdet / g_z_in: the gradient of -log p at the point, consumed by the tail)
+    ck.head(c, plan, B, stream, {z_prop, z_out, z_saved, grad_g, noise, z_next, z_acc, grad_acc, mom, scale_rows, mean_rows, m2_rows});
+    c.z_out = z_out; c.z_saved = z_saved; c.act_saved = act_saved; c.ll_mode = 1; c.ll_scale = -1.0f; c.lv = &lv; c.ll_prop = ll_prop;
+    c.chain = {energy_g, uniform, z_acc, grad_acc, u_acc, accept_out, log_alpha_out, flags}; c.mom = mom; c.kin0 = kin0;
+    c.step_rows = step_rows; c.adapt = adapt; c.da = rows.args();
+    c.scale = scale_rows; c.mean = mean_rows; c.m2 = m2_rows; c.count = count_rows; c.reg = metric.args();
+    const Pick p = select_hmc_metric(c);
+    return report(ck.entry, p, lsnf_launch_small3_hmc_metric(c, p.st));
+}
+
+int lsnf_reverse_hmc_step_metric(const float* plan, int nz, int width, int depth, int coupling, int B, const float* eps_prop,
+                                 const float* z_saved, const float* act_saved, const float* grad_g, const float* energy_g, float* eps_acc,
+                                 float* grad_acc, float* u_acc, float* mom, float* kin0, const float* noise, const float* uniform,
+                                 const LsnfRng* rng, float* step_rows, float* adapt, const LsnfDualAvg* da, float* scale_rows,
+                                 float* mean_rows, float* m2_rows, float* count_rows, const LsnfMetricReg* reg, unsigned flags,
+                                 float* eps_next, float* accept_out, float* log_alpha_out, void* stream) {
+    Check ck{"lsnf_reverse_hmc_step_metric"};
+    const Named reads[] = {{"plan", plan}, {"eps_prop", eps_prop}, {"z_saved", z_saved}, {"act_saved", act_saved}, {"grad_g", grad_g},
+                           {"energy_g", energy_g}, {"noise", noise}, {"uniform", uniform}};
+    const Named writes[] = {{"eps_acc", eps_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc}, {"eps_next", eps_next}, {"accept_out", accept_out},
+                            {"log_alpha_out", log_alpha_out}, {"mom", mom}, {"kin0", kin0}, {"step_rows", step_rows}, {"adapt", adapt},
+                            {"scale_rows", scale_rows}, {"mean_rows", mean_rows}, {"m2_rows", m2_rows}, {"count_rows", count_rows}};
+    const bool init = (flags & LSNF_HMC_INIT) != 0, inner = (flags & LSNF_HMC_INNER) != 0;
+    const Needed needed[] = {{"plan", plan}, {"eps_prop", eps_prop}, {"eps_acc", eps_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc},
+                             {"mom", mom}, {"kin0", kin0}, {"step_rows", step_rows}, {"scale_rows", scale_rows},
+                             {"act_saved", act_saved, true, "(the stash of lsnf_forward, lsnf_restash or lsnf_reverse_keep)"},
+                             {"z_saved", z_saved, depth > 1, "(NULL) for depth > 1"}, {"eps_next", eps_next, inner, "(NULL) with LSNF_HMC_INNER"}};
+    const ChainStep s = {reads, writes, /*next=*/&writes[3], /*point=*/&reads[1], needed,
+                         LSNF_HMC_INIT | LSNF_HMC_INNER | LSNF_HMC_ADAPT | LSNF_HMC_ADAPT_LAST | LSNF_HMC_METRIC_FOLD | LSNF_HMC_METRIC_CLOSE,
+                         init, inner, "LSNF_HMC_INIT or LSNF_HMC_INNER", plan, act_saved, noise, uniform, rng, /*step_size=*/1.0f, flags};
+    const RowSteps rows = {step_rows, adapt, da, flags};
+    const RowMetric metric = {mean_rows, m2_rows, count_rows, reg, flags};
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B) || s.scalars(ck) || s.phases(ck, accept_out, log_alpha_out) || rows.scalars(ck) ||
+        metric.scalars(ck) || s.aliases(ck))
+        return ck.rc;
+    if (ck.empty) return LSNF_OK;
+    if (s.pointers(ck) || rows.pointers(ck) || metric.pointers(ck)) return ck.rc;
+    LsnfReverseHmcMetricCall c;          // (no g_x / g_objective / g_z_in: the gradient at the point is consumed by the tail)
+    ck.head(c, plan, B, stream, {eps_prop, z_saved, grad_g, noise, eps_next, eps_acc, grad_acc, mom, scale_rows, mean_rows, m2_rows});
+    c.z_out = eps_prop; c.z_saved = z_saved; c.act_saved = act_saved;
+    c.grad_g = grad_g; c.noise = noise; c.step = 0.0f; c.eps_new = eps_next; c.rng = rng_args(rng);
+    c.chain = {energy_g, uniform, eps_acc, grad_acc, u_acc, accept_out, log_alpha_out, flags}; c.mom = mom; c.kin0 = kin0;
+    c.step_rows = step_rows; c.adapt = adapt; c.da = rows.args();
+    c.scale = scale_rows; c.mean = mean_rows; c.m2 = m2_rows; c.count = count_rows; c.reg = metric.args();
+    const Pick p = select_reverse_hmc_metric(c);
+    return report(ck.entry, p, lsnf_launch_small3_reverse_hmc_metric(c, p.st));
 }
 
 size_t lsnf_backward_params_workspace_floats(int nz, int width, int depth, int B) {

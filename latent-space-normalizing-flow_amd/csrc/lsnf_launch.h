@@ -63,6 +63,11 @@ struct LsnfHmcRowsCall : LsnfHmcCall {   // lsnf_hmc_step_rows: lv->step is not 
     float* step_rows = nullptr; float* adapt = nullptr;      // each row's step (B), the rows' dual-averaging state (B, 4; ADAPT only)
     LsnfDualAvgArgs da = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 };
+struct LsnfHmcMetricCall : LsnfHmcRowsCall {      // lsnf_hmc_step_metric; flags: LsnfHmcRowsCall's with METRIC_FOLD / METRIC_CLOSE
+    float* scale = nullptr;              // each row's scale per column (B, nz): read by every phase, written by a closing call
+    float* mean = nullptr; float* m2 = nullptr; float* count = nullptr;      // the window's Welford state (B, nz; B, nz; B): FOLD only
+    LsnfMetricArgs reg = {0.f, 0.f, 0.f, 0.f};
+};
 struct LsnfReverseBackwardCall : LsnfCall {      // lsnf_reverse_backward_z
     const float* z_out = nullptr; const float* z_saved = nullptr; const float* act_saved = nullptr;
     const float* g_x = nullptr; const float* g_objective = nullptr;
@@ -83,6 +88,10 @@ struct LsnfReverseHmcCall : LsnfReverseMalaCall {      // lsnf_reverse_hmc_step:
 struct LsnfReverseHmcRowsCall : LsnfReverseHmcCall {      // lsnf_reverse_hmc_step_rows: `step` is not read; flags as LsnfHmcRowsCall's
     float* step_rows = nullptr; float* adapt = nullptr;
     LsnfDualAvgArgs da = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+};
+struct LsnfReverseHmcMetricCall : LsnfReverseHmcRowsCall {      // lsnf_reverse_hmc_step_metric: as LsnfHmcMetricCall
+    float* scale = nullptr; float* mean = nullptr; float* m2 = nullptr; float* count = nullptr;
+    LsnfMetricArgs reg = {0.f, 0.f, 0.f, 0.f};
 };
 struct LsnfContractCall : LsnfCall {     // steps (2), (3) of lsnf_backward_params: batch contraction of the dump, chain rule
     const float* const* params_host = nullptr; float* const* grads_host = nullptr;
@@ -156,12 +165,14 @@ hipError_t lsnf_launch_small3_backward_z(const LsnfBackwardCall& c, int st);
 hipError_t lsnf_launch_small3_mala(const LsnfMalaCall& c, int st);          // st: lsnf_small3_backward_st of the call
 hipError_t lsnf_launch_small3_hmc(const LsnfHmcCall& c, int st);            // st: lsnf_small3_backward_st of the call
 hipError_t lsnf_launch_small3_hmc_rows(const LsnfHmcRowsCall& c, int st);   // st: lsnf_small3_backward_st of the call
+hipError_t lsnf_launch_small3_hmc_metric(const LsnfHmcMetricCall& c, int st);       // st: lsnf_small3_backward_st of the call
 int lsnf_small3_reverse_backward_st(const LsnfReverseBackwardCall& c);
 hipError_t lsnf_launch_small3_reverse_backward_z(const LsnfReverseBackwardCall& c, int st);
 hipError_t lsnf_launch_small3_reverse_langevin(const LsnfReverseLangevinCall& c, int st);      // st: of the same predicate
 hipError_t lsnf_launch_small3_reverse_mala(const LsnfReverseMalaCall& c, int st);              // st: of the same predicate
 hipError_t lsnf_launch_small3_reverse_hmc(const LsnfReverseHmcCall& c, int st);                // st: of the same predicate
 hipError_t lsnf_launch_small3_reverse_hmc_rows(const LsnfReverseHmcRowsCall& c, int st);       // st: of the same predicate
+hipError_t lsnf_launch_small3_reverse_hmc_metric(const LsnfReverseHmcMetricCall& c, int st);   // st: of the same predicate
 
 bool lsnf_contract_x3_covers(const LsnfContractCall& c);                   // (also asked with NULL tensors: lsnf_api.hip dump_may_tile)
 hipError_t lsnf_launch_contract_x3(const LsnfContractCall& c, int chunk_override);

@@ -86,6 +86,9 @@ struct LsnfRngArgs {
 struct LsnfDualAvgArgs {
     float target_accept, gamma, t0, kappa, log_step_min, log_step_max;
 };
+struct LsnfMetricArgs {                   // LsnfMetricReg as the kernels take it (lsnf_metric.h)
+    float n0, var0, scale_min, scale_max;
+};
 struct LsnfLangevinArgs {
     const float* z_cur; const float* grad_g; const float* noise;
     float* z_new; float* gf_norm; float* gg_norm; float step;

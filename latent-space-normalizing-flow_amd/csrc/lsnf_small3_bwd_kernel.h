@@ -6,7 +6,8 @@
 //                    section, with the kernel's locals in scope
 // lsnf_small3_bwd.hip gives the first column and is compiled from the same tokens as before this file existed; lsnf_small3_mala.hip the second;
 // lsnf_small3_hmc.hip a third (lsnf_small3_hmc_kernel, Small3HmcArgs, the leapfrog tail and `return;`), lsnf_small3_hmcr.hip a fourth
-// (lsnf_small3_hmcr_kernel, Small3HmcRowsArgs, the per-row leapfrog tail and `return;`).
+// (lsnf_small3_hmcr_kernel, Small3HmcRowsArgs, the per-row leapfrog tail and `return;`), lsnf_small3_hmcm.hip a fifth
+// (lsnf_small3_hmcm_kernel, Small3HmcMetricArgs, the per-row leapfrog tail with a diagonal metric and `return;`).
 #pragma once
 
 namespace {
@@ -63,6 +64,12 @@ struct Small3HmcArgs : Small3MalaArgs {
 struct Small3HmcRowsArgs : Small3HmcArgs {
     float* step_rows; float* adapt;
     LsnfDualAvgArgs da;
+};
+// metric HMC form (lsnf_small3_hmcm.hip): the per-row form's arrays, the rows' scales (B, nz) and, with LSNF_HMC_METRIC_FOLD (16;
+// LSNF_HMC_METRIC_CLOSE: 32), the Welford accumulators of the running window (mean, m2: B, nz; count: B) and the close's constants
+struct Small3HmcMetricArgs : Small3HmcRowsArgs {
+    float* scale; float* mean; float* m2; float* count;
+    LsnfMetricArgs reg;
 };
 
 __device__ __forceinline__ f32x4 mask4(f32x4 a, unsigned nib) {

@@ -8,7 +8,8 @@
 //                    section, with the kernel's locals in scope
 // lsnf_small3_rbwd.hip gives the first column and is compiled from the same tokens as before this file existed; lsnf_small3_rmala.hip
 // the second and lsnf_small3_rhmc.hip the third, both with UPDATE = false (their tails load e1, the first half of eps, themselves: in
-// front of their own barrier); lsnf_small3_rhmcr.hip is the third column with a step per row (lsnf_small3_rhmcr_kernel, Small3RhmcRowsArgs).
+// front of their own barrier); lsnf_small3_rhmcr.hip is the third column with a step per row (lsnf_small3_rhmcr_kernel, Small3RhmcRowsArgs),
+// lsnf_small3_rhmcm.hip that one with a diagonal metric per row (lsnf_small3_rhmcm_kernel, Small3RhmcMetricArgs).
 #pragma once
 
 namespace {
@@ -67,6 +68,12 @@ struct Small3RhmcArgs : Small3RmalaArgs {
 struct Small3RhmcRowsArgs : Small3RhmcArgs {
     float* step_rows; float* adapt;
     LsnfDualAvgArgs da;
+};
+// metric HMC form (lsnf_reverse_hmc_step_metric, lsnf_small3_rhmcm.hip): the per-row form's tensors, the rows' scales (B, nz) and, with
+// LSNF_HMC_METRIC_FOLD (16; LSNF_HMC_METRIC_CLOSE: 32), the Welford accumulators of the running window and the close's constants
+struct Small3RhmcMetricArgs : Small3RhmcRowsArgs {
+    float* scale; float* mean; float* m2; float* count;
+    LsnfMetricArgs reg;
 };
 
 __device__ __forceinline__ f32x4 rb_mask4(f32x4 a, unsigned nib) {

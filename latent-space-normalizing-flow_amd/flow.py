@@ -887,3 +887,5 @@ def adam_step(params: Sequence[torch.Tensor], grads: Sequence[Optional[torch.Ten
 from .mcmc import MALA_INIT, MalaState, new_mala_state, mala_step, reverse_mala_step  # noqa: E402,F401
 from .mcmc import HMC_INIT, HMC_INNER, HmcState, new_hmc_state, hmc_step, reverse_hmc_step  # noqa: E402,F401
 from .mcmc import HMC_ADAPT, HMC_ADAPT_LAST, HmcRowSteps, new_hmc_row_steps, hmc_step_rows, reverse_hmc_step_rows  # noqa: E402,F401
+from .mcmc import (HMC_METRIC_CLOSE, HMC_METRIC_FOLD, HmcRowMetric, new_hmc_row_metric, hmc_step_metric,  # noqa: E402,F401
+                   reverse_hmc_step_metric)

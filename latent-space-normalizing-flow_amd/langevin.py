@@ -178,6 +178,83 @@ def sample_hmc_adaptive_post_z_with_flow(z, x, netG: nn.Module, netF, *, g_l_ste
     return state.z.view(B, nz, 1, 1), accepted / counted, state.energy, steps
 
 
+def warmup_windows(W: int, init_buffer: int = 75, term_buffer: int = 50, base_window: int = 25):
+    """Stan's warm-up schedule for W trajectories, numbered 1 .. W: a fast initial buffer, a slow phase init_buffer + 1 .. W -
+    term_buffer of windows in which the metric is estimated -- the first `base_window` long, every next one twice as long, a window
+    extended to the slow phase's end when the one after it would not fit entirely --, a fast final buffer.  If the three do not fit
+    (init + base + term > W) the buffers become int(0.15 W) and int(0.1 W) and the base window the rest; W < 20 has no window.
+    Returns (first, closes): the first trajectory whose end call folds, and the trajectories whose end calls close a window
+    (None and [] without a window)."""
+    W = int(W)
+    if W < 20:
+        return None, []
+    init, term, size = int(init_buffer), int(term_buffer), int(base_window)
+    if init + size + term > W:
+        init, term = int(0.15 * W), int(0.1 * W)
+        size = W - init - term
+    end, close, closes = W - term, init + size, []
+    while True:
+        if close + 2 * size > end:          # the window after this one would not fit: this one takes the rest
+            close = end
+        closes.append(close)
+        if close >= end:
+            return init + 1, closes
+        size *= 2
+        close += size
+
+
+def _metric_plan(flow, metric, windows, W):
+    """(first, closes) of a metric sampler -- `windows` or `warmup_windows(W)` -- checked with `metric`; `window(t)`: what end call
+    t = 1 .. K does to the rows' windows."""
+    if metric is not None and not isinstance(metric, flow.HmcRowMetric):
+        raise flow.LsnfError("metric must be a flow.HmcRowMetric (new_hmc_row_metric()), or None")
+    first, closes = warmup_windows(W) if windows is None else windows
+    closes = [int(c) for c in closes]
+    if closes and (first is None or any(b <= a for a, b in zip([int(first) - 1] + closes, closes))):
+        raise ValueError(f"windows: the closes must increase from first on (got first={first}, closes={closes})")
+    last = closes[-1] if closes else 0
+    return lambda t: None if not closes or t < first or t > last else "close" if t in closes else "fold"
+
+
+def sample_hmc_metric_post_z_with_flow(z, x, netG: nn.Module, netF, *, g_l_steps: int, leapfrog_steps: int, warmup_steps: int,
+                                       g_l_step_size, g_llhd_sigma: float, philox, target_accept: float = 0.8, steps=None, metric=None,
+                                       windows=None):
+    """`sample_hmc_adaptive_post_z_with_flow` with a diagonal metric per row, estimated on the device in the warm-up's windows
+    (`netF.hmc_step_metric`; Stan's / NumPyro's warm-up): without one the stiffest coordinate of p(z | x_b) sets a row's step and the
+    chain barely moves in the soft ones.  The step adapts on every warm-up end call ("last" on the W-th); the end calls of
+    trajectories first .. the last close fold the decided state into the row's window and the closes turn a window into the row's
+    scales and restart the step adaptation (`windows` = (first, closes), default `warmup_windows(warmup_steps)`).  `metric`: a
+    `flow.HmcRowMetric` to go on from (updated in place; default a unit one).  Calls, draws and `philox` are the adaptive sampler's;
+    with windows=(None, []) and a fresh unit metric the result is that sampler's, bit for bit.
+    Returns that sampler's tuple and the `flow.HmcRowMetric`: (z_k, accept_rate, U(z_k), steps, metric)."""
+    from . import flow
+    K, L, W, mode = _adaptive_plan(g_l_steps, leapfrog_steps, warmup_steps, steps)
+    window = _metric_plan(flow, metric, windows, W)
+    B, nz = z.shape[0], z.shape[1]
+    if K < 1 or B == 0:
+        return z.detach().clone().view(B, nz, 1, 1), None, None, steps, metric
+    c = 1.0 / (2.0 * g_llhd_sigma * g_llhd_sigma)
+    z_prop = z.detach().reshape(B, nz).contiguous().clone()
+    steps = _row_steps(flow, steps, B, z_prop.device, g_l_step_size, target_accept)
+    metric = flow.new_hmc_row_metric(netF._plan(), B, z_prop.device) if metric is None else metric
+    state = flow.new_hmc_state(netF._plan(), B, z_prop.device)
+    accepted = torch.zeros(B, dtype=torch.float32, device=z_prop.device)
+    counted = K - W if W < K else K
+    for j in range(K * L + 1):
+        zr = z_prop.view(B, nz, 1, 1).detach().requires_grad_(True)
+        energy = c * ((netG(zr) - x) ** 2).flatten(1).sum(1)                                 # train.py:312-313, per row
+        grad_g = torch.autograd.grad(energy.sum(), zr)[0].reshape(B, nz).contiguous()        # train.py:314
+        t, inner = j // L, j % L != 0
+        end = bool(j) and not inner
+        _, acc, _, _ = netF.hmc_step_metric(z_prop, grad_g, energy.detach(), state, None if inner else philox.step(t), steps, metric,
+                                            phase="inner" if inner else "end" if j else "init", propose=j < K * L, inplace=True,
+                                            reuse_buffers=True, adapt=mode(t) if end else None, window=window(t) if end else None)
+        if end and (t > W or counted == K):
+            accepted += acc
+    philox.advance(K + 1)
+    return state.z.view(B, nz, 1, 1), accepted / counted, state.energy, steps, metric
+
+
 def sample_langevin_post_eps_with_flow(eps, x, netG: nn.Module, netF, *, g_l_steps: int, g_l_step_size: float,
                                        g_llhd_sigma: float, noise: bool = True, philox=None, fused: bool = False):
     """The sampler above in the flow's BASE space: Langevin on eps with z = f^-1(eps), target
@@ -296,8 +373,8 @@ def sample_hmc_post_eps_with_flow(eps, x, netG: nn.Module, netF, *, g_l_steps: i
                                   g_llhd_sigma: float, philox):
     """Hamiltonian Monte Carlo on the target of `sample_mala_post_eps_with_flow`, U(eps) = |eps|^2 / 2 + |x - G(z)|^2 / (2 sigma^2)
     with z = f^-1(eps): K = g_l_steps trajectories of L = leapfrog_steps leapfrog steps of size g_l_step_size, one accept / reject
-    per trajectory (L = 1 is that chain in exact arithmetic).  The flow has whitened the prior, so the identity mass matrix of the
-    momentum is the right one and long trajectories stay stable at steps the z-space chain cannot take.  Each of the K L + 1 points:
+    per trajectory (L = 1 is that chain in exact arithmetic).  The flow has whitened the prior, so for the prior's part the identity mass matrix of the
+    momentum is the right one (an informative likelihood: `sample_hmc_metric_post_eps_with_flow`) and long trajectories stay stable at steps the z-space chain cannot take.  Each of the K L + 1 points:
         z      = f^-1(eps_prop)                      the reverse launch, keeping its backward's stash where
                                                      `flow.reverse_keep_supported` (else reverse + forward at z)
         energy, grad_g                               torch autograd through netG, per row, as `sample_mala_post_eps_with_flow`
@@ -393,6 +470,57 @@ def sample_hmc_adaptive_post_eps_with_flow(eps, x, netG: nn.Module, netF, *, g_l
         z = flow.reverse(plan, state.z, None)[0]
     philox.advance(K + 1)
     return state.z, z.view(B, nz, 1, 1), accepted / counted, state.energy, steps
+
+
+def sample_hmc_metric_post_eps_with_flow(eps, x, netG: nn.Module, netF, *, g_l_steps: int, leapfrog_steps: int, warmup_steps: int,
+                                         g_l_step_size, g_llhd_sigma: float, philox, target_accept: float = 0.8, steps=None, metric=None,
+                                         windows=None):
+    """`sample_hmc_adaptive_post_eps_with_flow` with a diagonal metric per row -- the base-space twin of
+    `sample_hmc_metric_post_z_with_flow`, whose arguments these are (`netF.reverse_hmc_step_metric`): the flow whitens the prior, an
+    informative likelihood leaves the posterior in eps anisotropic.  With windows=(None, []) and a fresh unit metric the result is
+    `sample_hmc_adaptive_post_eps_with_flow`'s, bit for bit.
+    Returns that sampler's tuple and the `flow.HmcRowMetric`: (eps_k, z_k, accept_rate, U(eps_k), steps, metric); g_l_steps = 0 or an
+    empty batch returns the input without a launch, as there."""
+    from . import flow
+    K, L, W, mode = _adaptive_plan(g_l_steps, leapfrog_steps, warmup_steps, steps)
+    window = _metric_plan(flow, metric, windows, W)
+    B, nz = eps.shape[0], eps.shape[1]
+    eps_prop = eps.detach().reshape(B, nz).contiguous().clone()
+    if B == 0:
+        return eps_prop, eps_prop.view(0, nz, 1, 1), None, None, steps, metric
+    if K < 1:
+        return eps_prop, None, None, None, steps, metric
+    plan = netF._plan()
+    c = 1.0 / (2.0 * g_llhd_sigma * g_llhd_sigma)
+    steps = _row_steps(flow, steps, B, eps_prop.device, g_l_step_size, target_accept)
+    metric = flow.new_hmc_row_metric(plan, B, eps_prop.device) if metric is None else metric
+    keeps = flow.reverse_keep_supported(plan, B)
+    act = flow.new_act_saved(plan, B, eps_prop.device)
+    state = flow.new_hmc_state(plan, B, eps_prop.device)
+    accepted = torch.zeros(B, dtype=torch.float32, device=eps_prop.device)
+    counted = K - W if W < K else K
+    with torch.no_grad():
+        for j in range(K * L + 1):
+            if keeps:
+                z, _, saved = flow.reverse(plan, eps_prop, None, save_for_backward=True, act_saved=act)
+            else:
+                z, _ = flow.reverse(plan, eps_prop, None)
+                saved = flow.forward(plan, z, None, want_ll=False, save_for_backward=True, act_saved=act)[3]
+            with torch.enable_grad():
+                zr = z.view(B, nz, 1, 1).requires_grad_(True)
+                energy = c * ((netG(zr) - x) ** 2).flatten(1).sum(1)                                 # train.py:312-313, per row
+                grad_g = torch.autograd.grad(energy.sum(), zr)[0].reshape(B, nz).contiguous()        # train.py:314
+            t, inner = j // L, j % L != 0
+            end = bool(j) and not inner
+            _, acc, _ = netF.reverse_hmc_step_metric(eps_prop, saved, act, grad_g, energy.detach(), state, None if inner else philox.step(t),
+                                                     steps, metric, phase="inner" if inner else "end" if j else "init", propose=j < K * L,
+                                                     inplace=True, reuse_buffers=True, adapt=mode(t) if end else None,
+                                                     window=window(t) if end else None)
+            if end and (t > W or counted == K):
+                accepted += acc
+        z = flow.reverse(plan, state.z, None)[0]
+    philox.advance(K + 1)
+    return state.z, z.view(B, nz, 1, 1), accepted / counted, state.energy, steps, metric
 
 
 def flow_mle_step(netF, optF, z_g_k, f_max_norm: Optional[float] = None, fused: bool = False):

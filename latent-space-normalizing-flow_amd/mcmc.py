@@ -1,8 +1,9 @@
 """Markov-chain extensions of the functional host API (C: include/lsnf_flow_mcmc.h), re-exported by flow.py -- use them as
 `flow.mala_step`, `flow.reverse_mala_step`, `flow.MalaState`, `flow.new_mala_state`, `flow.hmc_step`, `flow.reverse_hmc_step`,
 `flow.HmcState`, `flow.new_hmc_state`, `flow.hmc_step_rows`, `flow.reverse_hmc_step_rows`, `flow.HmcRowSteps`,
-`flow.new_hmc_row_steps`.  Every tensor goes through flow.py's one checking path before anything is
-launched; like there, all functions raise on CPU tensors: there is no CPU path."""
+`flow.new_hmc_row_steps`, `flow.hmc_step_metric`, `flow.reverse_hmc_step_metric`, `flow.HmcRowMetric`, `flow.new_hmc_row_metric`.
+Every tensor goes through flow.py's one checking path before anything is launched; like there, all functions raise on CPU tensors:
+there is no CPU path."""
 from __future__ import annotations
 
 from dataclasses import dataclass, fields
@@ -12,7 +13,7 @@ import ctypes
 
 import torch
 
-from ._lib import LsnfDualAvg, LsnfError
+from ._lib import LsnfDualAvg, LsnfError, LsnfMetricReg
 from .flow import (FlowPlan, PhiloxNoise, _anchor, _call, _check_in, _check_like, _check_out, _check_stash, _noise_args, _plan_head,  # noqa: F401
                    _ptr, _stream_buffers, forward, new_act_saved)
 
@@ -198,7 +199,7 @@ def reverse_hmc_step(plan: FlowPlan, eps_prop: torch.Tensor, z_saved: Optional[t
     """One call of Hamiltonian Monte Carlo in the flow's base space (include/lsnf_flow_mcmc.h `lsnf_reverse_hmc_step`) in ONE launch:
     with x = reverse(eps_prop)[0], target pi(eps) ~ exp(-U), U = |eps|^2 / 2 + energy_g, grad U = eps + g, g = J_{f^-1}(eps)^T grad_g
     (`reverse_backward_z(plan, eps_prop, z_saved, act_saved, grad_g)`'s bits), momentum ~ N(0, I) -- the flow has whitened the prior,
-    so the identity mass matrix is the right one --, step s.  The reverse-backward's output section is the leapfrog tail at the point
+    so for the prior alone the identity mass matrix is the right one (else: `reverse_hmc_step_metric`) --, step s.  The reverse-backward's output section is the leapfrog tail at the point
     eps_prop of a trajectory.  eps_prop / z_saved / act_saved: the reverse's input, the block outputs and the stash of the forward
     AT x, as `reverse_mala_step`'s; like it this call runs no flow pass itself (the caller's generator sits between the reverse and
     it) and can be captured in a graph.  grad_g (B, nz) / energy_g (B): the caller's gradient and per-row energy at x (None = 0: the
@@ -347,4 +348,118 @@ def reverse_hmc_step_rows(plan: FlowPlan, eps_prop: torch.Tensor, z_saved: Optio
     _call("lsnf_reverse_hmc_step_rows", dev, *_plan_head(plan), B, _ptr(eps_prop), _ptr(z_saved), _ptr(act_saved), _ptr(grad_g),
           _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(state.mom), _ptr(state.kin), _ptr(noise), _ptr(uniform),
           rng, step_ptr, adapt_ptr, da, flags, _ptr(eps_next), _ptr(acc), _ptr(la))
+    return eps_next, acc, la
+
+
+HMC_METRIC_FOLD, HMC_METRIC_CLOSE = 16, 32      # include/lsnf_flow_mcmc.h LSNF_HMC_METRIC_FOLD, LSNF_HMC_METRIC_CLOSE
+_HMC_WINDOW = {None: 0, "fold": HMC_METRIC_FOLD, "close": HMC_METRIC_FOLD | HMC_METRIC_CLOSE}
+
+
+@dataclass
+class HmcRowMetric:
+    """The diagonal metric of every row of a Hamiltonian Monte Carlo chain (`hmc_step_metric`, `reverse_hmc_step_metric`): scale
+    (B, nz), the square root of the diagonal inverse mass (a standard deviation per column), read by every call and written only by
+    a closing end call; mean (B, nz), m2 (B, nz) and count (B), the Welford accumulators of the running warm-up window; and the
+    close's constants (include/lsnf_flow_mcmc.h `LsnfMetricReg`; n0 and var0 are Stan's)."""
+    scale: torch.Tensor
+    mean: torch.Tensor
+    m2: torch.Tensor
+    count: torch.Tensor
+    n0: float = 5.0
+    var0: float = 1e-3
+    scale_min: float = 1e-3
+    scale_max: float = 1e3
+
+
+def new_hmc_row_metric(plan: FlowPlan, B: int, device, scale=1.0) -> HmcRowMetric:
+    """The metric of B rows: every scale `scale` (a float) or row b's columns `scale[b]` (a (B, nz) tensor), with an empty window."""
+    B = int(B)
+    f32 = dict(dtype=torch.float32, device=device)
+    if isinstance(scale, torch.Tensor):
+        if scale.numel() != B * plan.nz:
+            raise LsnfError(f"scale has {scale.numel()} elements, the chain {B} rows of {plan.nz}")
+        sd = scale.detach().to(**f32).reshape(B, plan.nz).contiguous().clone()
+    else:
+        sd = torch.full((B, plan.nz), float(scale), **f32)
+    return HmcRowMetric(sd, torch.zeros((B, plan.nz), **f32), torch.zeros((B, plan.nz), **f32), torch.zeros(B, **f32))
+
+
+def _row_metric_mode(metric, phase, window):
+    """What the metric calls check before `_check_chain`, beside `_row_step_mode`: `metric` is an `HmcRowMetric`, the window mode is
+    a known one and goes with an end call.  Returns the window's flags."""
+    if not isinstance(metric, HmcRowMetric):
+        raise LsnfError("metric must be a flow.HmcRowMetric (new_hmc_row_metric())")
+    if window not in _HMC_WINDOW:
+        raise LsnfError(f"window must be None, 'fold' or 'close' (got {window!r})")
+    if window is not None and phase != "end":
+        raise LsnfError("a window folds the state an end call decided: window goes with phase='end'")
+    return _HMC_WINDOW[window]
+
+
+def _row_metric_args(plan, metric, B, dev, window):
+    """After `_check_chain`: the four arrays of `metric` through the one checking path.  Returns the five arguments of the C call:
+    scale_rows, then mean_rows, m2_rows, count_rows and the LsnfMetricReg (None unless folding)."""
+    _check_out(metric.scale, "metric.scale", B * plan.nz, dev)
+    _check_out(metric.mean, "metric.mean", B * plan.nz, dev)
+    _check_out(metric.m2, "metric.m2", B * plan.nz, dev)
+    _check_out(metric.count, "metric.count", B, dev)
+    if window is None:
+        return _ptr(metric.scale), None, None, None, None
+    reg = LsnfMetricReg(metric.n0, metric.var0, metric.scale_min, metric.scale_max)
+    return _ptr(metric.scale), _ptr(metric.mean), _ptr(metric.m2), _ptr(metric.count), ctypes.byref(reg)
+
+
+def hmc_step_metric(plan: FlowPlan, z_prop: torch.Tensor, grad_g: Optional[torch.Tensor], energy_g: Optional[torch.Tensor],
+                    state: HmcState, noise, steps: HmcRowSteps, metric: HmcRowMetric, *, phase: str = "end",
+                    uniform: Optional[torch.Tensor] = None, propose: bool = True, inplace: bool = False, reuse_buffers: bool = False,
+                    adapt: Optional[str] = None, window: Optional[str] = None):
+    """`hmc_step_rows` with a diagonal metric per row (include/lsnf_flow_mcmc.h `lsnf_hmc_step_metric`): HMC with identity mass in
+    y = z / metric.scale, i.e. mom -= s (scale * grad), z += s (scale * mom); with a unit scale a row gets the bits of
+    `hmc_step_rows`.  window (end calls only): "fold" folds the state after the decision into metric.mean / m2 / count; "close"
+    does that, then writes the window's regularised standard deviation to metric.scale, zeroes the accumulators, begins the next
+    trajectory with the new scale and -- with adapt="update" -- restarts the dual averaging at mu = log(10 * the new step).
+    Everything else, and what is returned, is `hmc_step_rows`'s."""
+    flags, inner = _row_step_mode(steps, phase, adapt), phase == "inner"
+    flags |= _row_metric_mode(metric, phase, window)
+    B, dev, noise, rng = _check_chain(plan, z_prop, "z_prop", grad_g, energy_g, state, HmcState, noise, uniform)
+    step_ptr, adapt_ptr, da = _row_step_args(steps, B, dev, adapt)
+    metric_args = _row_metric_args(plan, metric, B, dev, window)
+    if inner and (noise is not None or rng is not None or uniform is not None or not propose):
+        raise LsnfError("an inner leapfrog step draws and decides nothing: noise and uniform must be None, propose True")
+    bufs, z1, ll = _forward_at(plan, z_prop, B, dev, "_hmc_buffers", reuse_buffers)
+    z_next = None if not propose else z_prop if inplace else torch.empty_like(z_prop)
+    acc, la = (None, None) if inner else (bufs["acc"], bufs["la"])
+    _call("lsnf_hmc_step_metric", dev, *_plan_head(plan), B, _ptr(z_prop), _ptr(z1), _ptr(bufs["saved"]), _ptr(bufs["act"]), _ptr(ll),
+          _ptr(grad_g), _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(state.mom), _ptr(state.kin), _ptr(noise),
+          _ptr(uniform), rng, step_ptr, adapt_ptr, da, *metric_args, flags, _ptr(z_next), _ptr(acc), _ptr(la))
+    return z_next, acc, la, ll
+
+
+def reverse_hmc_step_metric(plan: FlowPlan, eps_prop: torch.Tensor, z_saved: Optional[torch.Tensor], act_saved: torch.Tensor,
+                            grad_g: Optional[torch.Tensor], energy_g: Optional[torch.Tensor], state: HmcState, noise, steps: HmcRowSteps,
+                            metric: HmcRowMetric, *, phase: str = "end", uniform: Optional[torch.Tensor] = None, propose: bool = True,
+                            inplace: bool = False, reuse_buffers: bool = False, adapt: Optional[str] = None, window: Optional[str] = None):
+    """`reverse_hmc_step_rows` with a diagonal metric per row (include/lsnf_flow_mcmc.h `lsnf_reverse_hmc_step_metric`): the flow
+    whitens the prior, not the posterior, so an informative likelihood leaves eps as anisotropic as z.  metric and window: as
+    `hmc_step_metric`'s.  ONE launch and nothing else, so a chain that adapts and folds can be captured in a graph.  Everything else,
+    and what is returned, is `reverse_hmc_step_rows`'s."""
+    flags, inner = _row_step_mode(steps, phase, adapt), phase == "inner"
+    flags |= _row_metric_mode(metric, phase, window)
+    B, dev, noise, rng = _check_chain(plan, eps_prop, "eps_prop", grad_g, energy_g, state, HmcState, noise, uniform,
+                                      stash=(z_saved, act_saved))
+    step_ptr, adapt_ptr, da = _row_step_args(steps, B, dev, adapt)
+    metric_args = _row_metric_args(plan, metric, B, dev, window)
+    if inner and (noise is not None or rng is not None or uniform is not None or not propose):
+        raise LsnfError("an inner leapfrog step draws and decides nothing: noise and uniform must be None, propose True")
+    acc = la = None
+    if not inner:
+        def make():
+            f32 = dict(dtype=torch.float32, device=dev)
+            return {"acc": torch.empty(B, **f32), "la": torch.empty(B, **f32)}
+        bufs = _stream_buffers(plan, "_rhmc_buffers", B, dev, make) if reuse_buffers else make()
+        acc, la = bufs["acc"], bufs["la"]
+    eps_next = None if not propose else eps_prop if inplace else torch.empty_like(eps_prop)
+    _call("lsnf_reverse_hmc_step_metric", dev, *_plan_head(plan), B, _ptr(eps_prop), _ptr(z_saved), _ptr(act_saved), _ptr(grad_g),
+          _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(state.mom), _ptr(state.kin), _ptr(noise), _ptr(uniform),
+          rng, step_ptr, adapt_ptr, da, *metric_args, flags, _ptr(eps_next), _ptr(acc), _ptr(la))
     return eps_next, acc, la

@@ -516,6 +516,25 @@ class _netF(nn.Module):
                                           det(noise), steps, phase=phase, uniform=det(uniform), propose=propose, inplace=inplace,
                                           reuse_buffers=reuse_buffers, adapt=adapt)
 
+    def hmc_step_metric(self, z_prop, grad_g=None, energy_g=None, state=None, noise=None, steps=None, metric=None, *, phase="end",
+                        uniform=None, propose=True, inplace=False, reuse_buffers=False, adapt=None, window=None):
+        """`hmc_step_rows` with a diagonal metric per row (`flow.hmc_step_metric`; metric: a `flow.HmcRowMetric`); window="fold" /
+        "close" on an end call folds the decided state into the row's warm-up window / closes it.  Returns what `hmc_step` returns."""
+        det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t
+        return flow.hmc_step_metric(self._plan(), det(z_prop), det(grad_g), det(energy_g), state, det(noise), steps, metric, phase=phase,
+                                    uniform=det(uniform), propose=propose, inplace=inplace, reuse_buffers=reuse_buffers, adapt=adapt,
+                                    window=window)
+
+    def reverse_hmc_step_metric(self, eps_prop, z_saved, act_saved, grad_g=None, energy_g=None, state=None, noise=None, steps=None,
+                                metric=None, *, phase="end", uniform=None, propose=True, inplace=False, reuse_buffers=False, adapt=None,
+                                window=None):
+        """`reverse_hmc_step_rows` with a diagonal metric per row (`flow.reverse_hmc_step_metric`; metric: a `flow.HmcRowMetric`);
+        window as `hmc_step_metric`'s.  Returns what `reverse_hmc_step` returns."""
+        det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t
+        return flow.reverse_hmc_step_metric(self._plan(), det(eps_prop), det(z_saved), det(act_saved), det(grad_g), det(energy_g), state,
+                                            det(noise), steps, metric, phase=phase, uniform=det(uniform), propose=propose,
+                                            inplace=inplace, reuse_buffers=reuse_buffers, adapt=adapt, window=window)
+
     def mle_grads(self, z, accumulate: bool = False, max_norm: Optional[float] = None, reuse_buffers: bool = False):
         """Fused flow-MLE gradients (train.py:404-411): loss_f = -mean_b ll(z_b) and d loss_f / d theta written to
         `.grad` of the 60 live tensors -- forward (ll summed in-kernel), dump backward, batch contraction, unfold:
