@@ -238,7 +238,52 @@
  * the chain is not exactly invariant; from the last close on it is.
  * Kernels: lsnf_small3_hmcm_kernel / lsnf_small3_rhmcm_kernel, the per-row kernels' stages, instantiations and workgroup shapes; sd,
  * mean and m2 are read and written by the lane that owns their columns, so a row's bits -- scale and accumulators included -- do not
- * depend on B, the workgroup shape or rng->row0 sharding.  B = 0 succeeds without a launch. */
+ * depend on B, the workgroup shape or rng->row0 sharding.  B = 0 succeeds without a launch.
+ *
+ * ---- A likelihood temperature per row: tempered steps with fused importance weights (lsnf_hmc_step_tempered, ------------------------
+ * ---- lsnf_reverse_hmc_step_tempered) -----------------------------------------------------------------------------------------------------
+ * The target at inverse temperature beta is p_flow(z) * p(x | G(z))^beta: the likelihood's part of the potential and of its gradient
+ * carries the weight beta, the prior's part the weight 1.  Row b has a temperature of its own in device memory.  With a common schedule
+ * 0 = beta_0 <= .. <= beta_T = 1 the calls are annealed importance sampling (Neal 2001) with HMC transitions; rows at distinct fixed
+ * temperatures are the replicas of a parallel-tempering sampler.  The two entry points are the metric calls with
+ * `float* beta_rows, const float* beta_next, float* like_grad_acc, float* like_u_acc, float* log_w` inserted between reg and flags.
+ * Everything fp32 with the operations and the order written, no fused multiply-add; each product in parentheses is ONE rounded
+ * product, formed first.  The likelihood's parts of a point are gl and el:
+ *   z space:     gl = grad_g,  el = energy_g  (NULL = 0)
+ *   base space:  gl = J_{f^-1}(eps)^T grad_g, the kernel's own back-propagated gradient, unscaled, with lsnf_reverse_backward_z's bits;
+ *                el = energy_g  (NULL = 0)
+ * In every phase that forms a gradient or a potential (beta = beta_rows[b]):
+ *   z:    g = (beta * gl) + d(-ll)/dz(z_prop);     U_prop = (beta * el) - ll_prop
+ *   eps:  t_prop = eps_prop + (beta * gl);         U_prop = (beta * el) + 0.5f * sum_c eps_prop^2
+ * Everything else of begin / inner / end is the metric call's lines: the decision, the state update, the dual averaging, the fold and
+ * the close.
+ *   beta_rows (B): row b's beta for the RUNNING trajectory.  Every phase reads it; only a call with LSNF_HMC_ANNEAL writes it.  It is
+ *       device memory and is not looked at on the host, as step_rows is.  Always required.
+ *   like_grad_acc (B,nz), like_u_acc (B): gl and el of the kept state.  They are written wherever z_acc / eps_acc is written: every
+ *       row on LSNF_HMC_INIT, accepted rows on an end call; rejected rows keep their bits.  Always required; LSNF_HMC_INNER calls
+ *       neither read nor write them.
+ *   flags: the metric call's; LSNF_HMC_ANNEAL with LSNF_HMC_INIT or an end call (refused with LSNF_HMC_INNER); unknown bits are refused
+ *   beta_next (B), log_w (B,2; 8-byte aligned): required with LSNF_HMC_ANNEAL, must be NULL without it
+ *   all five arrays are outputs in the sense of the aliasing rule: they may alias nothing else the call touches
+ *   every other argument, rule, draw and refusal is the metric call's, word for word
+ * ANNEAL runs after the decision and after the metric call's adapt / fold / close, and before the next trajectory begins.  With
+ * (g_s, u_s, gl_s, el_s) the state after the decision (the proposal's on accepted rows, the kept one on rejected rows):
+ *         d = beta_next[b] - beta
+ *         inc = -(d * el_s);   y = inc - c;   t = w + y;   c' = (t - w) - y;   w' = t      (log_w[b] = {w, c}: Kahan's sum)
+ *         u_acc <- u_s + (d * el_s);     grad_acc <- g_s + (d * gl_s)   per column          (every row, accepted or not)
+ *         beta_rows[b] <- beta_next[b]
+ *     The trajectory this call begins (if a next point is asked for) starts from the re-tempered grad_acc.  log_w[b][0] - log_w[b][1]
+ *     is the row's log importance weight, sum_t -(beta_{t+1} - beta_t) * E(state_t).  LSNF_HMC_INIT does not clear log_w: zeroing it
+ *     is the caller's job.  The kept state can be re-tempered exactly because the likelihood's part of it is kept apart.
+ * Hence, exactly:
+ * (1) with beta_rows == 1.0f everywhere and without LSNF_HMC_ANNEAL, every output a call shares with the metric call has that call's
+ *     bits, in every phase (1.0f * x is x);
+ * (2) with beta_rows[b] == 2^k, row b's outputs are the metric call's at (2^k grad_g, 2^k energy_g), bit for bit (the products are
+ *     exact scalings), wherever nothing overflows or becomes subnormal.
+ * Kernels: lsnf_small3_hmct_kernel / lsnf_small3_rhmct_kernel, the metric kernels' stages, instantiations and workgroup shapes; beta,
+ * like_u_acc and the log_w pair are row scalars read by every wave in front of the barrier and stored by one lane after it,
+ * like_grad_acc is read and written by the lane that owns its columns, so a row's bits do not depend on B, the workgroup shape or
+ * rng->row0 sharding.  B = 0 succeeds without a launch. */
 #ifndef LSNF_FLOW_MCMC_H
 #define LSNF_FLOW_MCMC_H
 
@@ -315,6 +360,27 @@ int lsnf_reverse_hmc_step_metric(const float* plan, int nz, int width, int depth
                                  float* step_rows, float* adapt, const LsnfDualAvg* da,
                                  float* scale_rows, float* mean_rows, float* m2_rows, float* count_rows, const LsnfMetricReg* reg, unsigned flags,
                                  float* eps_next, float* accept_out, float* log_alpha_out, void* stream);
+
+/* a likelihood temperature per row (tempered transitions, annealed importance sampling) */
+#define LSNF_HMC_ANNEAL 64u   /* INIT and end calls: weigh the state after the decision, re-temper it to beta_next */
+int lsnf_hmc_step_tempered(const float* plan, int nz, int width, int depth, int coupling, int B,
+                           const float* z_prop, const float* z_out, const float* z_saved, const float* act_saved,
+                           const float* ll_prop, const float* grad_g, const float* energy_g,
+                           float* z_acc, float* grad_acc, float* u_acc, float* mom, float* kin0,
+                           const float* noise, const float* uniform, const LsnfRng* rng,
+                           float* step_rows, float* adapt, const LsnfDualAvg* da,
+                           float* scale_rows, float* mean_rows, float* m2_rows, float* count_rows, const LsnfMetricReg* reg,
+                           float* beta_rows, const float* beta_next, float* like_grad_acc, float* like_u_acc, float* log_w, unsigned flags,
+                           float* z_next, float* accept_out, float* log_alpha_out, void* stream);
+int lsnf_reverse_hmc_step_tempered(const float* plan, int nz, int width, int depth, int coupling, int B,
+                                   const float* eps_prop, const float* z_saved, const float* act_saved,
+                                   const float* grad_g, const float* energy_g,
+                                   float* eps_acc, float* grad_acc, float* u_acc, float* mom, float* kin0,
+                                   const float* noise, const float* uniform, const LsnfRng* rng,
+                                   float* step_rows, float* adapt, const LsnfDualAvg* da,
+                                   float* scale_rows, float* mean_rows, float* m2_rows, float* count_rows, const LsnfMetricReg* reg,
+                                   float* beta_rows, const float* beta_next, float* like_grad_acc, float* like_u_acc, float* log_w,
+                                   unsigned flags, float* eps_next, float* accept_out, float* log_alpha_out, void* stream);
 
 #ifdef __cplusplus
 }

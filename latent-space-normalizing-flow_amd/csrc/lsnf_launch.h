@@ -68,6 +68,12 @@ struct LsnfHmcMetricCall : LsnfHmcRowsCall {      // lsnf_hmc_step_metric; flags
     float* mean = nullptr; float* m2 = nullptr; float* count = nullptr;      // the window's Welford state (B, nz; B, nz; B): FOLD only
     LsnfMetricArgs reg = {0.f, 0.f, 0.f, 0.f};
 };
+struct LsnfHmcTemperedCall : LsnfHmcMetricCall {      // lsnf_hmc_step_tempered; flags: LsnfHmcMetricCall's with ANNEAL
+    float* beta_rows = nullptr;          // each row's likelihood temperature (B): read by every phase, written by an annealing call
+    const float* beta_next = nullptr;    // the next one (B): ANNEAL only
+    float* like_grad_acc = nullptr; float* like_u_acc = nullptr;      // the likelihood's part of the kept state (B, nz; B)
+    float* log_w = nullptr;              // the Kahan pair of the rows' importance weights (B, 2; 8-byte aligned): ANNEAL only
+};
 struct LsnfReverseBackwardCall : LsnfCall {      // lsnf_reverse_backward_z
     const float* z_out = nullptr; const float* z_saved = nullptr; const float* act_saved = nullptr;
     const float* g_x = nullptr; const float* g_objective = nullptr;
@@ -92,6 +98,10 @@ struct LsnfReverseHmcRowsCall : LsnfReverseHmcCall {      // lsnf_reverse_hmc_st
 struct LsnfReverseHmcMetricCall : LsnfReverseHmcRowsCall {      // lsnf_reverse_hmc_step_metric: as LsnfHmcMetricCall
     float* scale = nullptr; float* mean = nullptr; float* m2 = nullptr; float* count = nullptr;
     LsnfMetricArgs reg = {0.f, 0.f, 0.f, 0.f};
+};
+struct LsnfReverseHmcTemperedCall : LsnfReverseHmcMetricCall {      // lsnf_reverse_hmc_step_tempered: as LsnfHmcTemperedCall
+    float* beta_rows = nullptr; const float* beta_next = nullptr; float* like_grad_acc = nullptr; float* like_u_acc = nullptr;
+    float* log_w = nullptr;
 };
 struct LsnfContractCall : LsnfCall {     // steps (2), (3) of lsnf_backward_params: batch contraction of the dump, chain rule
     const float* const* params_host = nullptr; float* const* grads_host = nullptr;
@@ -166,6 +176,7 @@ hipError_t lsnf_launch_small3_mala(const LsnfMalaCall& c, int st);          // s
 hipError_t lsnf_launch_small3_hmc(const LsnfHmcCall& c, int st);            // st: lsnf_small3_backward_st of the call
 hipError_t lsnf_launch_small3_hmc_rows(const LsnfHmcRowsCall& c, int st);   // st: lsnf_small3_backward_st of the call
 hipError_t lsnf_launch_small3_hmc_metric(const LsnfHmcMetricCall& c, int st);       // st: lsnf_small3_backward_st of the call
+hipError_t lsnf_launch_small3_hmc_tempered(const LsnfHmcTemperedCall& c, int st);   // st: lsnf_small3_backward_st of the call
 int lsnf_small3_reverse_backward_st(const LsnfReverseBackwardCall& c);
 hipError_t lsnf_launch_small3_reverse_backward_z(const LsnfReverseBackwardCall& c, int st);
 hipError_t lsnf_launch_small3_reverse_langevin(const LsnfReverseLangevinCall& c, int st);      // st: of the same predicate
@@ -173,6 +184,7 @@ hipError_t lsnf_launch_small3_reverse_mala(const LsnfReverseMalaCall& c, int st)
 hipError_t lsnf_launch_small3_reverse_hmc(const LsnfReverseHmcCall& c, int st);                // st: of the same predicate
 hipError_t lsnf_launch_small3_reverse_hmc_rows(const LsnfReverseHmcRowsCall& c, int st);       // st: of the same predicate
 hipError_t lsnf_launch_small3_reverse_hmc_metric(const LsnfReverseHmcMetricCall& c, int st);   // st: of the same predicate
+hipError_t lsnf_launch_small3_reverse_hmc_tempered(const LsnfReverseHmcTemperedCall& c, int st);   // st: of the same predicate
 
 bool lsnf_contract_x3_covers(const LsnfContractCall& c);                   // (also asked with NULL tensors: lsnf_api.hip dump_may_tile)
 hipError_t lsnf_launch_contract_x3(const LsnfContractCall& c, int chunk_override);

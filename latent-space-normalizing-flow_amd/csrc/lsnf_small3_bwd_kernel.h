@@ -7,7 +7,8 @@
 // lsnf_small3_bwd.hip gives the first column and is compiled from the same tokens as before this file existed; lsnf_small3_mala.hip the second;
 // lsnf_small3_hmc.hip a third (lsnf_small3_hmc_kernel, Small3HmcArgs, the leapfrog tail and `return;`), lsnf_small3_hmcr.hip a fourth
 // (lsnf_small3_hmcr_kernel, Small3HmcRowsArgs, the per-row leapfrog tail and `return;`), lsnf_small3_hmcm.hip a fifth
-// (lsnf_small3_hmcm_kernel, Small3HmcMetricArgs, the per-row leapfrog tail with a diagonal metric and `return;`).
+// (lsnf_small3_hmcm_kernel, Small3HmcMetricArgs, the per-row leapfrog tail with a diagonal metric and `return;`), lsnf_small3_hmct.hip a
+// sixth (lsnf_small3_hmct_kernel, Small3HmcTemperedArgs, that tail with a likelihood temperature per row and `return;`).
 #pragma once
 
 namespace {
@@ -70,6 +71,12 @@ struct Small3HmcRowsArgs : Small3HmcArgs {
 struct Small3HmcMetricArgs : Small3HmcRowsArgs {
     float* scale; float* mean; float* m2; float* count;
     LsnfMetricArgs reg;
+};
+// tempered HMC form (lsnf_small3_hmct.hip): the metric form's arrays, the rows' likelihood temperature (B), the likelihood's part of
+// the kept state (like_grad_acc: B, nz; like_u_acc: B) and, with LSNF_HMC_ANNEAL (64), the next temperature (B) and the Kahan pair
+// of the importance weight (B, 2; 8-byte aligned)
+struct Small3HmcTemperedArgs : Small3HmcMetricArgs {
+    float* beta_rows; const float* beta_next; float* like_grad_acc; float* like_u_acc; float* log_w;
 };
 
 __device__ __forceinline__ f32x4 mask4(f32x4 a, unsigned nib) {

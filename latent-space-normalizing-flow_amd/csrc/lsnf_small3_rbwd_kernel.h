@@ -9,7 +9,8 @@
 // lsnf_small3_rbwd.hip gives the first column and is compiled from the same tokens as before this file existed; lsnf_small3_rmala.hip
 // the second and lsnf_small3_rhmc.hip the third, both with UPDATE = false (their tails load e1, the first half of eps, themselves: in
 // front of their own barrier); lsnf_small3_rhmcr.hip is the third column with a step per row (lsnf_small3_rhmcr_kernel, Small3RhmcRowsArgs),
-// lsnf_small3_rhmcm.hip that one with a diagonal metric per row (lsnf_small3_rhmcm_kernel, Small3RhmcMetricArgs).
+// lsnf_small3_rhmcm.hip that one with a diagonal metric per row (lsnf_small3_rhmcm_kernel, Small3RhmcMetricArgs), lsnf_small3_rhmct.hip
+// that one with a likelihood temperature per row (lsnf_small3_rhmct_kernel, Small3RhmcTemperedArgs).
 #pragma once
 
 namespace {
@@ -74,6 +75,12 @@ struct Small3RhmcRowsArgs : Small3RhmcArgs {
 struct Small3RhmcMetricArgs : Small3RhmcRowsArgs {
     float* scale; float* mean; float* m2; float* count;
     LsnfMetricArgs reg;
+};
+// tempered HMC form (lsnf_reverse_hmc_step_tempered, lsnf_small3_rhmct.hip): the metric form's tensors, the rows' likelihood temperature
+// (B), the likelihood's part of the kept state (like_grad_acc: B, nz; like_u_acc: B) and, with LSNF_HMC_ANNEAL (64), the next
+// temperature (B) and the Kahan pair of the importance weight (B, 2; 8-byte aligned)
+struct Small3RhmcTemperedArgs : Small3RhmcMetricArgs {
+    float* beta_rows; const float* beta_next; float* like_grad_acc; float* like_u_acc; float* log_w;
 };
 
 __device__ __forceinline__ f32x4 rb_mask4(f32x4 a, unsigned nib) {

@@ -889,3 +889,4 @@ from .mcmc import HMC_INIT, HMC_INNER, HmcState, new_hmc_state, hmc_step, revers
 from .mcmc import HMC_ADAPT, HMC_ADAPT_LAST, HmcRowSteps, new_hmc_row_steps, hmc_step_rows, reverse_hmc_step_rows  # noqa: E402,F401
 from .mcmc import (HMC_METRIC_CLOSE, HMC_METRIC_FOLD, HmcRowMetric, new_hmc_row_metric, hmc_step_metric,  # noqa: E402,F401
                    reverse_hmc_step_metric)
+from .mcmc import HMC_ANNEAL, HmcRowTemper, new_hmc_row_temper, hmc_step_tempered, reverse_hmc_step_tempered  # noqa: E402,F401

@@ -523,6 +523,179 @@ def sample_hmc_metric_post_eps_with_flow(eps, x, netG: nn.Module, netF, *, g_l_s
     return state.z, z.view(B, nz, 1, 1), accepted / counted, state.energy, steps, metric
 
 
+def ais_schedule(T: int, kind: str = "sigmoid", delta: float = 4.0) -> torch.Tensor:
+    """The T + 1 inverse temperatures of an annealed-importance-sampling run, float64: beta_0 = 0, beta_T = 1, nondecreasing.
+    "sigmoid" is Wu et al.'s ("On the quantitative analysis of decoder-based generative models"): sigma(delta (2 t / T - 1)) rescaled
+    to [0, 1], which spends its steps near both ends; "linear" is t / T."""
+    T = int(T)
+    if T < 1:
+        raise ValueError(f"T must be >= 1 (got {T})")
+    t = torch.arange(T + 1, dtype=torch.float64) / T
+    if kind == "linear":
+        b = t
+    elif kind == "sigmoid":
+        s = torch.sigmoid(float(delta) * (2.0 * t - 1.0))
+        b = (s - s[0]) / (s[-1] - s[0])
+    else:
+        raise ValueError(f"kind must be 'sigmoid' or 'linear' (got {kind!r})")
+    b = b.clone()
+    b[0], b[-1] = 0.0, 1.0
+    return b
+
+
+def _ais_plan(flow, betas, chains, leapfrog_steps, steps, metric, adapt):
+    """(betas as a float64 (T + 1) tensor, T, chains, L) of an AIS run, checked."""
+    betas = torch.as_tensor(betas, dtype=torch.float64).reshape(-1).cpu()
+    T, C, L = betas.numel() - 1, int(chains), int(leapfrog_steps)
+    if L < 1:
+        raise ValueError(f"leapfrog_steps must be >= 1 (got {leapfrog_steps})")
+    if C < 1:
+        raise ValueError(f"chains must be >= 1 (got {chains})")
+    if T >= 1 and (float(betas[0]) != 0.0 or bool((betas[1:] < betas[:-1]).any())):
+        raise ValueError("betas must start at 0 (the chains start from draws of the prior) and must not decrease")
+    if steps is not None and not isinstance(steps, flow.HmcRowSteps):
+        raise flow.LsnfError("steps must be a flow.HmcRowSteps (new_hmc_row_steps()), or None")
+    if metric is not None and not isinstance(metric, flow.HmcRowMetric):
+        raise flow.LsnfError("metric must be a flow.HmcRowMetric (new_hmc_row_metric()), or None")
+    return betas, T, C, L
+
+
+def _ais_reduce(temper, N, C, D, sigma):
+    """The chain reduction of an AIS run, a few float64 ops on (N, chains): log p(x), the log weights, the effective sample size."""
+    import math
+    log_w = temper.log_weight().view(N, C)
+    lse = torch.logsumexp(log_w, dim=1)
+    log_px = lse - math.log(C) - 0.5 * D * math.log(2.0 * math.pi * sigma * sigma)
+    ess = torch.exp(2.0 * lse - torch.logsumexp(2.0 * log_w, dim=1))
+    return log_px, log_w, ess
+
+
+_AIS_DOC = """
+    betas: the T + 1 inverse temperatures (`ais_schedule`), beta_0 = 0.  The B = N * chains rows are x repeated per chain (row
+    n * chains + c is chain c of datum n).  The initial point is ONE `netF.sample(B, philox.step(0), return_eps=True)` launch -- exact
+    draws of the prior, which is what beta_0 = 0 targets.  Then the HMC samplers' loop of `netF.*_tempered` calls: one init call with
+    anneal = beta_1 (it weighs the start, log_w = -(beta_1 - beta_0) E(z_0), and begins trajectory 1 at beta_1), then per
+    t = 1 .. T, L - 1 inner calls and one end call, which for t < T anneals to beta_{t+1} inside the kernel -- the weight's
+    increment -(beta_{t+1} - beta_t) E(state_t), the re-tempered kept gradient -- and for t = T neither anneals nor proposes.  The call
+    that begins trajectory t takes philox.step(t), the last end call philox.step(T + 1) for its uniform alone; philox.step(0) is the
+    sample's and no step ever takes it (the sample's eps and a step's xi are the same function of (seed, offset, row, column): the
+    first momentum would equal the starting eps).  philox is advanced by T + 1 on return: the next run's sample at that offset draws
+    eps only, the last end call drew a uniform only.
+    steps / metric: frozen `flow.HmcRowSteps` / `flow.HmcRowMetric`, e.g. what `sample_hmc_metric_post_*_with_flow` adapted at
+    beta = 1: the posterior is the stiffest of the targets, so its step is the conservative choice for every beta (acceptance is
+    higher at the smaller ones).  Default: the float (or (B) tensor) g_l_step_size and a unit metric.  adapt=True passes
+    adapt="update" on every end call: the transitions then depend on the chain's past, and the estimator is only approximately
+    unbiased.
+    Returns (log_px (N) float64, log_w (N, chains) float64, ess (N) float64, accept_rate (B), z_T (B, nz, 1, 1), temper):
+        log_px = logsumexp_c(log_w) - log(chains) - D / 2 * log(2 pi sigma^2),   D = x[0].numel()
+        ess    = exp(2 logsumexp_c(log_w) - logsumexp_c(2 log_w))
+    a stochastic lower bound of log p(x) whose expectation of exp is exact.  Only the likelihood's energy E = |x - G(z)|^2 / (2 sigma^2)
+    enters a weight; the prior is sampled exactly and a transition is invariant under a constant in its potential, so the flow's
+    own +log(2 pi) constant in ll (and the prior's whole normaliser) cancels -- the Gaussian likelihood's normaliser is the one
+    constant added.  The chain reduction is a few float64 torch ops on (N, chains), the only torch arithmetic on the flow's side.
+    An empty batch returns empty results and T < 1 Nones, both without a launch and without advancing philox."""
+
+
+def estimate_log_px_ais_z_with_flow(x, netG: nn.Module, netF, *, betas, chains: int, leapfrog_steps: int, g_l_step_size,
+                                    g_llhd_sigma: float, philox, steps=None, metric=None, adapt: bool = False):
+    """log p(x) of the latent-variable model p_flow(z) N(x; G(z), sigma^2 I) by annealed importance sampling (Neal 2001) with HMC
+    transitions in z (Wu et al.'s evaluation protocol), every transition two launches of the flow (`netF.hmc_step_tempered`)."""
+    from . import flow
+    betas, T, C, L = _ais_plan(flow, betas, chains, leapfrog_steps, steps, metric, adapt)
+    N = x.shape[0]
+    if T < 1:
+        return None, None, None, None, None, None
+    if N == 0:
+        e = torch.zeros(0, dtype=torch.float64, device=x.device)
+        return e, e.view(0, C), e.clone(), None, None, None
+    B, D, plan = N * C, x[0].numel(), netF._plan()
+    c = 1.0 / (2.0 * g_llhd_sigma * g_llhd_sigma)
+    xs = x.detach().repeat_interleave(C, dim=0)
+    z0 = netF.sample(B, philox.step(0), return_eps=True)[0]
+    nz = z0.shape[1]
+    z_prop = z0.detach().reshape(B, nz).contiguous()
+    dev = z_prop.device
+    sched = betas.to(torch.float32).to(dev)[:, None].expand(T + 1, B).contiguous()
+    steps = _row_steps(flow, steps, B, dev, g_l_step_size, 0.8)
+    metric = flow.new_hmc_row_metric(plan, B, dev) if metric is None else metric
+    temper = flow.new_hmc_row_temper(plan, B, dev, 0.0)
+    state = flow.new_hmc_state(plan, B, dev)
+    accepted = torch.zeros(B, dtype=torch.float32, device=dev)
+    for j in range(T * L + 1):
+        zr = z_prop.view(B, nz, 1, 1).detach().requires_grad_(True)
+        energy = c * ((netG(zr) - xs) ** 2).flatten(1).sum(1)                                # train.py:312-313, per row
+        grad_g = torch.autograd.grad(energy.sum(), zr)[0].reshape(B, nz).contiguous()        # train.py:314
+        t, inner = j // L, j % L != 0
+        end = bool(j) and not inner
+        _, acc, _, _ = netF.hmc_step_tempered(z_prop, grad_g, energy.detach(), state, None if inner else philox.step(t + 1), steps, metric,
+                                              temper, phase="inner" if inner else "end" if j else "init", propose=j < T * L,
+                                              inplace=True, reuse_buffers=True, adapt="update" if adapt and end else None,
+                                              anneal=sched[t + 1] if not inner and t < T else None)
+        if end:
+            accepted += acc
+    philox.advance(T + 1)
+    log_px, log_w, ess = _ais_reduce(temper, N, C, D, float(g_llhd_sigma))
+    return log_px, log_w, ess, accepted / T, state.z.view(B, nz, 1, 1), temper
+
+
+def estimate_log_px_ais_eps_with_flow(x, netG: nn.Module, netF, *, betas, chains: int, leapfrog_steps: int, g_l_step_size,
+                                      g_llhd_sigma: float, philox, steps=None, metric=None, adapt: bool = False):
+    """`estimate_log_px_ais_z_with_flow` with the transitions in the flow's base space (`netF.reverse_hmc_step_tempered`): the chain
+    runs on eps with z = f^-1(eps), the prior is N(0, I) at every temperature and the flow's side of a transition is the reverse and
+    ONE more launch.  The starting eps_0 is the sample's own eps.  z_T = f^-1(eps_T)."""
+    from . import flow
+    betas, T, C, L = _ais_plan(flow, betas, chains, leapfrog_steps, steps, metric, adapt)
+    N = x.shape[0]
+    if T < 1:
+        return None, None, None, None, None, None
+    if N == 0:
+        e = torch.zeros(0, dtype=torch.float64, device=x.device)
+        return e, e.view(0, C), e.clone(), None, None, None
+    B, D, plan = N * C, x[0].numel(), netF._plan()
+    c = 1.0 / (2.0 * g_llhd_sigma * g_llhd_sigma)
+    xs = x.detach().repeat_interleave(C, dim=0)
+    eps0 = netF.sample(B, philox.step(0), return_eps=True)[1]
+    nz = eps0.shape[1]
+    eps_prop = eps0.detach().reshape(B, nz).contiguous()
+    dev = eps_prop.device
+    sched = betas.to(torch.float32).to(dev)[:, None].expand(T + 1, B).contiguous()
+    steps = _row_steps(flow, steps, B, dev, g_l_step_size, 0.8)
+    metric = flow.new_hmc_row_metric(plan, B, dev) if metric is None else metric
+    temper = flow.new_hmc_row_temper(plan, B, dev, 0.0)
+    keeps = flow.reverse_keep_supported(plan, B)
+    act = flow.new_act_saved(plan, B, dev)
+    state = flow.new_hmc_state(plan, B, dev)
+    accepted = torch.zeros(B, dtype=torch.float32, device=dev)
+    with torch.no_grad():
+        for j in range(T * L + 1):
+            if keeps:
+                z, _, saved = flow.reverse(plan, eps_prop, None, save_for_backward=True, act_saved=act)
+            else:
+                z, _ = flow.reverse(plan, eps_prop, None)
+                saved = flow.forward(plan, z, None, want_ll=False, save_for_backward=True, act_saved=act)[3]
+            with torch.enable_grad():
+                zr = z.view(B, nz, 1, 1).requires_grad_(True)
+                energy = c * ((netG(zr) - xs) ** 2).flatten(1).sum(1)                                # train.py:312-313, per row
+                grad_g = torch.autograd.grad(energy.sum(), zr)[0].reshape(B, nz).contiguous()        # train.py:314
+            t, inner = j // L, j % L != 0
+            end = bool(j) and not inner
+            _, acc, _ = netF.reverse_hmc_step_tempered(eps_prop, saved, act, grad_g, energy.detach(), state,
+                                                       None if inner else philox.step(t + 1), steps, metric, temper,
+                                                       phase="inner" if inner else "end" if j else "init", propose=j < T * L,
+                                                       inplace=True, reuse_buffers=True, adapt="update" if adapt and end else None,
+                                                       anneal=sched[t + 1] if not inner and t < T else None)
+            if end:
+                accepted += acc
+        z = flow.reverse(plan, state.z, None)[0]
+    philox.advance(T + 1)
+    log_px, log_w, ess = _ais_reduce(temper, N, C, D, float(g_llhd_sigma))
+    return log_px, log_w, ess, accepted / T, z.view(B, nz, 1, 1), temper
+
+
+estimate_log_px_ais_z_with_flow.__doc__ += _AIS_DOC
+estimate_log_px_ais_eps_with_flow.__doc__ += _AIS_DOC
+
+
 def flow_mle_step(netF, optF, z_g_k, f_max_norm: Optional[float] = None, fused: bool = False):
     """train.py:404-415: one Adam step of the flow on the Langevin-inferred z.  Returns loss_f (detached).
     fused=False restates the reference line by line (autograd through `netF(...)`); fused=True computes the same

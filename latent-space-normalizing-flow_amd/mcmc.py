@@ -1,7 +1,8 @@
 """Markov-chain extensions of the functional host API (C: include/lsnf_flow_mcmc.h), re-exported by flow.py -- use them as
 `flow.mala_step`, `flow.reverse_mala_step`, `flow.MalaState`, `flow.new_mala_state`, `flow.hmc_step`, `flow.reverse_hmc_step`,
 `flow.HmcState`, `flow.new_hmc_state`, `flow.hmc_step_rows`, `flow.reverse_hmc_step_rows`, `flow.HmcRowSteps`,
-`flow.new_hmc_row_steps`, `flow.hmc_step_metric`, `flow.reverse_hmc_step_metric`, `flow.HmcRowMetric`, `flow.new_hmc_row_metric`.
+`flow.new_hmc_row_steps`, `flow.hmc_step_metric`, `flow.reverse_hmc_step_metric`, `flow.HmcRowMetric`, `flow.new_hmc_row_metric`,
+`flow.hmc_step_tempered`, `flow.reverse_hmc_step_tempered`, `flow.HmcRowTemper`, `flow.new_hmc_row_temper`.
 Every tensor goes through flow.py's one checking path before anything is launched; like there, all functions raise on CPU tensors:
 there is no CPU path."""
 from __future__ import annotations
@@ -462,4 +463,125 @@ def reverse_hmc_step_metric(plan: FlowPlan, eps_prop: torch.Tensor, z_saved: Opt
     _call("lsnf_reverse_hmc_step_metric", dev, *_plan_head(plan), B, _ptr(eps_prop), _ptr(z_saved), _ptr(act_saved), _ptr(grad_g),
           _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(state.mom), _ptr(state.kin), _ptr(noise), _ptr(uniform),
           rng, step_ptr, adapt_ptr, da, *metric_args, flags, _ptr(eps_next), _ptr(acc), _ptr(la))
+    return eps_next, acc, la
+
+
+HMC_ANNEAL = 64               # include/lsnf_flow_mcmc.h LSNF_HMC_ANNEAL
+
+
+@dataclass
+class HmcRowTemper:
+    """The likelihood temperature of every row of a Hamiltonian Monte Carlo chain (`hmc_step_tempered`, `reverse_hmc_step_tempered`):
+    beta (B), read by every call and written only by an annealing one; like_grad (B, nz) and like_energy (B), the likelihood's part
+    of the kept state's gradient and potential (written wherever state.z is), from which the kept state is re-tempered when beta
+    changes; and log_w (B, 2), the Kahan pair {sum, compensation} of the row's log importance weight."""
+    beta: torch.Tensor
+    like_grad: torch.Tensor
+    like_energy: torch.Tensor
+    log_w: torch.Tensor
+
+    def log_weight(self) -> torch.Tensor:
+        """The rows' log importance weights, (B) float64: log_w[:, 0] - log_w[:, 1]."""
+        return self.log_w[:, 0].double() - self.log_w[:, 1].double()
+
+
+def new_hmc_row_temper(plan: FlowPlan, B: int, device, beta=0.0) -> HmcRowTemper:
+    """The temperatures of B rows: every one `beta` (a float) or row b's `beta[b]` (a (B) tensor); the other arrays start as zeros."""
+    B = int(B)
+    f32 = dict(dtype=torch.float32, device=device)
+    if isinstance(beta, torch.Tensor):
+        if beta.numel() != B:
+            raise LsnfError(f"beta has {beta.numel()} elements, the chain {B} rows")
+        bt = beta.detach().to(**f32).reshape(B).contiguous().clone()
+    else:
+        bt = torch.full((B,), float(beta), **f32)
+    return HmcRowTemper(bt, torch.zeros((B, plan.nz), **f32), torch.zeros(B, **f32), torch.zeros((B, 2), **f32))
+
+
+def _row_temper_mode(temper, phase, anneal):
+    """What the tempered calls check before `_check_chain`, beside `_row_metric_mode`: `temper` is an `HmcRowTemper`, and an
+    annealing call is an init or an end call.  Returns the anneal's flag."""
+    if not isinstance(temper, HmcRowTemper):
+        raise LsnfError("temper must be a flow.HmcRowTemper (new_hmc_row_temper())")
+    if anneal is not None and not isinstance(anneal, torch.Tensor):
+        raise LsnfError("anneal must be None or a (B) float32 tensor of the rows' next beta")
+    if anneal is not None and phase == "inner":
+        raise LsnfError("the temperature changes between two trajectories: anneal goes with phase='init' or 'end'")
+    return 0 if anneal is None else HMC_ANNEAL
+
+
+def _row_temper_args(plan, temper, B, dev, anneal):
+    """After `_check_chain`: the arrays of `temper` and the next temperatures through the one checking path, in the order the C call
+    names them.  Returns its five arguments: beta_rows, beta_next, like_grad_acc, like_u_acc, log_w (the second and the last None
+    unless annealing)."""
+    _check_out(temper.beta, "temper.beta", B, dev)
+    _check_in(anneal, "anneal", B, dev)
+    _check_out(temper.like_grad, "temper.like_grad", B * plan.nz, dev)
+    _check_out(temper.like_energy, "temper.like_energy", B, dev)
+    _check_out(temper.log_w, "temper.log_w", 2 * B, dev)
+    if anneal is None:
+        return _ptr(temper.beta), None, _ptr(temper.like_grad), _ptr(temper.like_energy), None
+    return _ptr(temper.beta), _ptr(anneal), _ptr(temper.like_grad), _ptr(temper.like_energy), _ptr(temper.log_w)
+
+
+def hmc_step_tempered(plan: FlowPlan, z_prop: torch.Tensor, grad_g: Optional[torch.Tensor], energy_g: Optional[torch.Tensor],
+                      state: HmcState, noise, steps: HmcRowSteps, metric: HmcRowMetric, temper: HmcRowTemper, *, phase: str = "end",
+                      uniform: Optional[torch.Tensor] = None, propose: bool = True, inplace: bool = False, reuse_buffers: bool = False,
+                      adapt: Optional[str] = None, window: Optional[str] = None, anneal: Optional[torch.Tensor] = None):
+    """`hmc_step_metric` with a likelihood temperature per row (include/lsnf_flow_mcmc.h `lsnf_hmc_step_tempered`): row b's target is
+    p_flow(z) exp(-temper.beta[b] energy_g), i.e. grad_g and energy_g enter with the weight beta[b], the prior's part with 1; with
+    beta == 1 a row gets the bits of `hmc_step_metric`.  temper.like_grad / like_energy keep grad_g / energy_g of the kept state.
+    anneal (phase "init" or "end"): a (B) float32 tensor of the rows' next beta.  After the decision (and the adapt / window) the
+    kernel adds -(anneal - beta) * like_energy of the state after the decision to temper.log_w (a compensated sum), re-tempers
+    state.grad / state.energy of EVERY row to the next beta, writes temper.beta = anneal and begins the next trajectory (propose)
+    from the re-tempered gradient: one transition of annealed importance sampling, without a torch op.  Everything else, and what is
+    returned, is `hmc_step_metric`'s."""
+    flags, inner = _row_step_mode(steps, phase, adapt), phase == "inner"
+    flags |= _row_metric_mode(metric, phase, window)
+    flags |= _row_temper_mode(temper, phase, anneal)
+    B, dev, noise, rng = _check_chain(plan, z_prop, "z_prop", grad_g, energy_g, state, HmcState, noise, uniform)
+    step_ptr, adapt_ptr, da = _row_step_args(steps, B, dev, adapt)
+    metric_args = _row_metric_args(plan, metric, B, dev, window)
+    temper_args = _row_temper_args(plan, temper, B, dev, anneal)
+    if inner and (noise is not None or rng is not None or uniform is not None or not propose):
+        raise LsnfError("an inner leapfrog step draws and decides nothing: noise and uniform must be None, propose True")
+    bufs, z1, ll = _forward_at(plan, z_prop, B, dev, "_hmc_buffers", reuse_buffers)
+    z_next = None if not propose else z_prop if inplace else torch.empty_like(z_prop)
+    acc, la = (None, None) if inner else (bufs["acc"], bufs["la"])
+    _call("lsnf_hmc_step_tempered", dev, *_plan_head(plan), B, _ptr(z_prop), _ptr(z1), _ptr(bufs["saved"]), _ptr(bufs["act"]), _ptr(ll),
+          _ptr(grad_g), _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(state.mom), _ptr(state.kin), _ptr(noise),
+          _ptr(uniform), rng, step_ptr, adapt_ptr, da, *metric_args, *temper_args, flags, _ptr(z_next), _ptr(acc), _ptr(la))
+    return z_next, acc, la, ll
+
+
+def reverse_hmc_step_tempered(plan: FlowPlan, eps_prop: torch.Tensor, z_saved: Optional[torch.Tensor], act_saved: torch.Tensor,
+                              grad_g: Optional[torch.Tensor], energy_g: Optional[torch.Tensor], state: HmcState, noise, steps: HmcRowSteps,
+                              metric: HmcRowMetric, temper: HmcRowTemper, *, phase: str = "end", uniform: Optional[torch.Tensor] = None,
+                              propose: bool = True, inplace: bool = False, reuse_buffers: bool = False, adapt: Optional[str] = None,
+                              window: Optional[str] = None, anneal: Optional[torch.Tensor] = None):
+    """`reverse_hmc_step_metric` with a likelihood temperature per row (include/lsnf_flow_mcmc.h `lsnf_reverse_hmc_step_tempered`):
+    row b's target is N(eps; 0, I) exp(-temper.beta[b] energy_g); temper.like_grad keeps the kernel's own J_{f^-1}(eps)^T grad_g of the
+    kept state, unscaled.  temper and anneal: as `hmc_step_tempered`'s.  ONE launch and nothing else, so an annealed chain can be
+    captured in a graph.  Everything else, and what is returned, is `reverse_hmc_step_metric`'s."""
+    flags, inner = _row_step_mode(steps, phase, adapt), phase == "inner"
+    flags |= _row_metric_mode(metric, phase, window)
+    flags |= _row_temper_mode(temper, phase, anneal)
+    B, dev, noise, rng = _check_chain(plan, eps_prop, "eps_prop", grad_g, energy_g, state, HmcState, noise, uniform,
+                                      stash=(z_saved, act_saved))
+    step_ptr, adapt_ptr, da = _row_step_args(steps, B, dev, adapt)
+    metric_args = _row_metric_args(plan, metric, B, dev, window)
+    temper_args = _row_temper_args(plan, temper, B, dev, anneal)
+    if inner and (noise is not None or rng is not None or uniform is not None or not propose):
+        raise LsnfError("an inner leapfrog step draws and decides nothing: noise and uniform must be None, propose True")
+    acc = la = None
+    if not inner:
+        def make():
+            f32 = dict(dtype=torch.float32, device=dev)
+            return {"acc": torch.empty(B, **f32), "la": torch.empty(B, **f32)}
+        bufs = _stream_buffers(plan, "_rhmc_buffers", B, dev, make) if reuse_buffers else make()
+        acc, la = bufs["acc"], bufs["la"]
+    eps_next = None if not propose else eps_prop if inplace else torch.empty_like(eps_prop)
+    _call("lsnf_reverse_hmc_step_tempered", dev, *_plan_head(plan), B, _ptr(eps_prop), _ptr(z_saved), _ptr(act_saved), _ptr(grad_g),
+          _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(state.mom), _ptr(state.kin), _ptr(noise), _ptr(uniform),
+          rng, step_ptr, adapt_ptr, da, *metric_args, *temper_args, flags, _ptr(eps_next), _ptr(acc), _ptr(la))
     return eps_next, acc, la

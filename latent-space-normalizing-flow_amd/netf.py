@@ -535,6 +535,28 @@ class _netF(nn.Module):
                                             det(noise), steps, metric, phase=phase, uniform=det(uniform), propose=propose,
                                             inplace=inplace, reuse_buffers=reuse_buffers, adapt=adapt, window=window)
 
+    def hmc_step_tempered(self, z_prop, grad_g=None, energy_g=None, state=None, noise=None, steps=None, metric=None, temper=None, *,
+                          phase="end", uniform=None, propose=True, inplace=False, reuse_buffers=False, adapt=None, window=None,
+                          anneal=None):
+        """`hmc_step_metric` with a likelihood temperature per row (`flow.hmc_step_tempered`; temper: a `flow.HmcRowTemper`);
+        anneal = a (B) tensor of the next beta on an init or end call weighs the decided state and re-tempers it inside the kernel.
+        Returns what `hmc_step` returns."""
+        det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t
+        return flow.hmc_step_tempered(self._plan(), det(z_prop), det(grad_g), det(energy_g), state, det(noise), steps, metric, temper,
+                                      phase=phase, uniform=det(uniform), propose=propose, inplace=inplace, reuse_buffers=reuse_buffers,
+                                      adapt=adapt, window=window, anneal=det(anneal))
+
+    def reverse_hmc_step_tempered(self, eps_prop, z_saved, act_saved, grad_g=None, energy_g=None, state=None, noise=None, steps=None,
+                                  metric=None, temper=None, *, phase="end", uniform=None, propose=True, inplace=False,
+                                  reuse_buffers=False, adapt=None, window=None, anneal=None):
+        """`reverse_hmc_step_metric` with a likelihood temperature per row (`flow.reverse_hmc_step_tempered`; temper: a
+        `flow.HmcRowTemper`); anneal as `hmc_step_tempered`'s.  Returns what `reverse_hmc_step` returns."""
+        det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t
+        return flow.reverse_hmc_step_tempered(self._plan(), det(eps_prop), det(z_saved), det(act_saved), det(grad_g), det(energy_g),
+                                              state, det(noise), steps, metric, temper, phase=phase, uniform=det(uniform),
+                                              propose=propose, inplace=inplace, reuse_buffers=reuse_buffers, adapt=adapt, window=window,
+                                              anneal=det(anneal))
+
     def mle_grads(self, z, accumulate: bool = False, max_norm: Optional[float] = None, reuse_buffers: bool = False):
         """Fused flow-MLE gradients (train.py:404-411): loss_f = -mean_b ll(z_b) and d loss_f / d theta written to
         `.grad` of the 60 live tensors -- forward (ll summed in-kernel), dump backward, batch contraction, unfold:
