@@ -283,7 +283,38 @@
  * Kernels: lsnf_small3_hmct_kernel / lsnf_small3_rhmct_kernel, the metric kernels' stages, instantiations and workgroup shapes; beta,
  * like_u_acc and the log_w pair are row scalars read by every wave in front of the barrier and stored by one lane after it,
  * like_grad_acc is read and written by the lane that owns its columns, so a row's bits do not depend on B, the workgroup shape or
- * rng->row0 sharding.  B = 0 succeeds without a launch. */
+ * rng->row0 sharding.  B = 0 succeeds without a launch.
+ *
+ * ---- Replica exchange between rows at distinct temperatures: parallel tempering (lsnf_hmc_step_exchange, -----------------------------
+ * ---- lsnf_reverse_hmc_step_exchange) -----------------------------------------------------------------------------------------------------
+ * The two entry points are the tempered calls with `int ladder, const float* swap_uniform, float* swap_out, float* log_swap_out`
+ * inserted between log_alpha_out and stream, and two more flags.  Without LSNF_HMC_SWAP every output has the tempered call's bits in
+ * every phase and the four new arguments must be 0 / NULL (ladder is not looked at).
+ *   ladder: R in {2, 4, 8, 16}, B % R == 0.  Rows [k R, (k + 1) R) are the rungs of ladder k, rung r = row % R; beta per rung is
+ *       whatever beta_rows holds (it need not be ordered).
+ *   flags: the tempered call's; LSNF_HMC_SWAP only on an end call (neither LSNF_HMC_INIT nor LSNF_HMC_INNER) and without
+ *       LSNF_HMC_ADAPT, LSNF_HMC_METRIC_FOLD, LSNF_HMC_METRIC_CLOSE and LSNF_HMC_ANNEAL; LSNF_HMC_SWAP_ODD only with LSNF_HMC_SWAP.
+ *       Even parity pairs rungs (0,1), (2,3), ..; odd parity pairs (1,2), (3,4), .. and leaves rungs 0 and R - 1 idle (R = 2: nothing
+ *       swaps).  A pair never crosses a ladder's border.
+ *   swap_uniform (B): the uniform of the pair (a, b), a the lower row, is swap_uniform[a].  It goes with the tensor form of the noise
+ *       and is then required; with an rng it must be NULL and the number is word 0 of Philox at the call's (seed, offset), at the
+ *       global row of a, at counter field value 3 (the noise draws use 0 and 1, the trajectory's uniform 2), formed as that uniform
+ *       is: a pure function of (seed, offset, global row of a), so a ladder swaps alike however the batch is sharded along whole ladders.
+ *   swap_out, log_swap_out (B): optional outputs; they may alias nothing else the call touches.
+ * The move comes after the trajectory's decision and the state update and before the next trajectory begins.  With
+ * (z_s, g_s, u_s, gl_s, el_s) a row's state after the decision, for the pair (a, b):
+ *         d = beta_a - beta_b;   e = el_s_a - el_s_b;   log_r = d * e              (one rounded product; both rows form it in this order)
+ *         the pair swaps iff logf(u) < log_r                                       (a NaN log_r rejects)
+ *     The states are exchanged, not the temperatures.  A row that swaps (p its partner, d_own = beta_own - beta_p):
+ *         z_acc <- z_s_p;   like_grad_acc <- gl_s_p;   like_u_acc <- el_s_p
+ *         grad_acc <- g_s_p + (d_own * gl_s_p)   per column;     u_acc <- u_s_p + (d_own * el_s_p)
+ *     and the trajectory this call begins (if a next point is asked for) starts from that state with the row's own step, scale and xi.
+ *     beta_rows, step_rows, scale_rows and everything of the adaptation stay with the row.
+ *         swap_out[b] = 1.0f on both rows of an exchanged pair, else 0.0f;   log_swap_out[b] = log_r on both rows of a pair, 0.0f on
+ *     an idle rung.  accept_out and log_alpha_out stay the trajectory's own.
+ * Kernels: lsnf_small3_hmcx_kernel / lsnf_small3_rhmcx_kernel, the tempered kernels' stages, instantiations and workgroup shapes.  A
+ * ladder lies inside one wave's 16-row tile, the partner's state comes over lane to lane, and every lane writes its own row only: no
+ * row reads what another row writes in the same launch.  B = 0 succeeds without a launch. */
 #ifndef LSNF_FLOW_MCMC_H
 #define LSNF_FLOW_MCMC_H
 
@@ -381,6 +412,30 @@ int lsnf_reverse_hmc_step_tempered(const float* plan, int nz, int width, int dep
                                    float* scale_rows, float* mean_rows, float* m2_rows, float* count_rows, const LsnfMetricReg* reg,
                                    float* beta_rows, const float* beta_next, float* like_grad_acc, float* like_u_acc, float* log_w,
                                    unsigned flags, float* eps_next, float* accept_out, float* log_alpha_out, void* stream);
+
+/* replica exchange between the rows of a ladder (parallel tempering) */
+#define LSNF_HMC_SWAP 128u       /* end calls: exchange the states of paired rungs after the decision */
+#define LSNF_HMC_SWAP_ODD 256u   /* with LSNF_HMC_SWAP: pair rungs (1,2), (3,4), .. instead of (0,1), (2,3), .. */
+int lsnf_hmc_step_exchange(const float* plan, int nz, int width, int depth, int coupling, int B,
+                           const float* z_prop, const float* z_out, const float* z_saved, const float* act_saved,
+                           const float* ll_prop, const float* grad_g, const float* energy_g,
+                           float* z_acc, float* grad_acc, float* u_acc, float* mom, float* kin0,
+                           const float* noise, const float* uniform, const LsnfRng* rng,
+                           float* step_rows, float* adapt, const LsnfDualAvg* da,
+                           float* scale_rows, float* mean_rows, float* m2_rows, float* count_rows, const LsnfMetricReg* reg,
+                           float* beta_rows, const float* beta_next, float* like_grad_acc, float* like_u_acc, float* log_w, unsigned flags,
+                           float* z_next, float* accept_out, float* log_alpha_out,
+                           int ladder, const float* swap_uniform, float* swap_out, float* log_swap_out, void* stream);
+int lsnf_reverse_hmc_step_exchange(const float* plan, int nz, int width, int depth, int coupling, int B,
+                                   const float* eps_prop, const float* z_saved, const float* act_saved,
+                                   const float* grad_g, const float* energy_g,
+                                   float* eps_acc, float* grad_acc, float* u_acc, float* mom, float* kin0,
+                                   const float* noise, const float* uniform, const LsnfRng* rng,
+                                   float* step_rows, float* adapt, const LsnfDualAvg* da,
+                                   float* scale_rows, float* mean_rows, float* m2_rows, float* count_rows, const LsnfMetricReg* reg,
+                                   float* beta_rows, const float* beta_next, float* like_grad_acc, float* like_u_acc, float* log_w,
+                                   unsigned flags, float* eps_next, float* accept_out, float* log_alpha_out,
+                                   int ladder, const float* swap_uniform, float* swap_out, float* log_swap_out, void* stream);
 
 #ifdef __cplusplus
 }

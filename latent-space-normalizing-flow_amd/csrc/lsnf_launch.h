@@ -74,6 +74,11 @@ struct LsnfHmcTemperedCall : LsnfHmcMetricCall {      // lsnf_hmc_step_tempered;
     float* like_grad_acc = nullptr; float* like_u_acc = nullptr;      // the likelihood's part of the kept state (B, nz; B)
     float* log_w = nullptr;              // the Kahan pair of the rows' importance weights (B, 2; 8-byte aligned): ANNEAL only
 };
+struct LsnfHmcExchangeCall : LsnfHmcTemperedCall {      // lsnf_hmc_step_exchange; flags: LsnfHmcTemperedCall's with SWAP / SWAP_ODD
+    int ladder = 0;                      // R consecutive rows aligned to R are the rungs of one ladder (2, 4, 8 or 16): SWAP only
+    const float* swap_uniform = nullptr; // the pairs' uniforms (B), read at the lower row; NULL: drawn in-kernel
+    float* swap_out = nullptr; float* log_swap_out = nullptr;      // optional (B each)
+};
 struct LsnfReverseBackwardCall : LsnfCall {      // lsnf_reverse_backward_z
     const float* z_out = nullptr; const float* z_saved = nullptr; const float* act_saved = nullptr;
     const float* g_x = nullptr; const float* g_objective = nullptr;
@@ -102,6 +107,9 @@ struct LsnfReverseHmcMetricCall : LsnfReverseHmcRowsCall {      // lsnf_reverse_
 struct LsnfReverseHmcTemperedCall : LsnfReverseHmcMetricCall {      // lsnf_reverse_hmc_step_tempered: as LsnfHmcTemperedCall
     float* beta_rows = nullptr; const float* beta_next = nullptr; float* like_grad_acc = nullptr; float* like_u_acc = nullptr;
     float* log_w = nullptr;
+};
+struct LsnfReverseHmcExchangeCall : LsnfReverseHmcTemperedCall {      // lsnf_reverse_hmc_step_exchange: as LsnfHmcExchangeCall
+    int ladder = 0; const float* swap_uniform = nullptr; float* swap_out = nullptr; float* log_swap_out = nullptr;
 };
 struct LsnfContractCall : LsnfCall {     // steps (2), (3) of lsnf_backward_params: batch contraction of the dump, chain rule
     const float* const* params_host = nullptr; float* const* grads_host = nullptr;
@@ -177,6 +185,7 @@ hipError_t lsnf_launch_small3_hmc(const LsnfHmcCall& c, int st);            // s
 hipError_t lsnf_launch_small3_hmc_rows(const LsnfHmcRowsCall& c, int st);   // st: lsnf_small3_backward_st of the call
 hipError_t lsnf_launch_small3_hmc_metric(const LsnfHmcMetricCall& c, int st);       // st: lsnf_small3_backward_st of the call
 hipError_t lsnf_launch_small3_hmc_tempered(const LsnfHmcTemperedCall& c, int st);   // st: lsnf_small3_backward_st of the call
+hipError_t lsnf_launch_small3_hmc_exchange(const LsnfHmcExchangeCall& c, int st);   // st: lsnf_small3_backward_st of the call
 int lsnf_small3_reverse_backward_st(const LsnfReverseBackwardCall& c);
 hipError_t lsnf_launch_small3_reverse_backward_z(const LsnfReverseBackwardCall& c, int st);
 hipError_t lsnf_launch_small3_reverse_langevin(const LsnfReverseLangevinCall& c, int st);      // st: of the same predicate
@@ -185,6 +194,7 @@ hipError_t lsnf_launch_small3_reverse_hmc(const LsnfReverseHmcCall& c, int st); 
 hipError_t lsnf_launch_small3_reverse_hmc_rows(const LsnfReverseHmcRowsCall& c, int st);       // st: of the same predicate
 hipError_t lsnf_launch_small3_reverse_hmc_metric(const LsnfReverseHmcMetricCall& c, int st);   // st: of the same predicate
 hipError_t lsnf_launch_small3_reverse_hmc_tempered(const LsnfReverseHmcTemperedCall& c, int st);   // st: of the same predicate
+hipError_t lsnf_launch_small3_reverse_hmc_exchange(const LsnfReverseHmcExchangeCall& c, int st);   // st: of the same predicate
 
 bool lsnf_contract_x3_covers(const LsnfContractCall& c);                   // (also asked with NULL tensors: lsnf_api.hip dump_may_tile)
 hipError_t lsnf_launch_contract_x3(const LsnfContractCall& c, int chunk_override);

@@ -8,7 +8,8 @@
 // lsnf_small3_hmc.hip a third (lsnf_small3_hmc_kernel, Small3HmcArgs, the leapfrog tail and `return;`), lsnf_small3_hmcr.hip a fourth
 // (lsnf_small3_hmcr_kernel, Small3HmcRowsArgs, the per-row leapfrog tail and `return;`), lsnf_small3_hmcm.hip a fifth
 // (lsnf_small3_hmcm_kernel, Small3HmcMetricArgs, the per-row leapfrog tail with a diagonal metric and `return;`), lsnf_small3_hmct.hip a
-// sixth (lsnf_small3_hmct_kernel, Small3HmcTemperedArgs, that tail with a likelihood temperature per row and `return;`).
+// sixth (lsnf_small3_hmct_kernel, Small3HmcTemperedArgs, that tail with a likelihood temperature per row and `return;`),
+// lsnf_small3_hmcx.hip a seventh (lsnf_small3_hmcx_kernel, Small3HmcExchangeArgs, that tail with a replica-exchange move and `return;`).
 #pragma once
 
 namespace {
@@ -77,6 +78,11 @@ struct Small3HmcMetricArgs : Small3HmcRowsArgs {
 // of the importance weight (B, 2; 8-byte aligned)
 struct Small3HmcTemperedArgs : Small3HmcMetricArgs {
     float* beta_rows; const float* beta_next; float* like_grad_acc; float* like_u_acc; float* log_w;
+};
+// exchanging HMC form (lsnf_small3_hmcx.hip): the tempered form's arrays and, with LSNF_HMC_SWAP (128), the ladder's length, the
+// pairs' uniforms (B, read at the lower row; NULL: drawn in-kernel) and the two optional outputs of the move (B each)
+struct Small3HmcExchangeArgs : Small3HmcTemperedArgs {
+    int ladder; const float* swap_uniform; float* swap_out; float* log_swap_out;
 };
 
 __device__ __forceinline__ f32x4 mask4(f32x4 a, unsigned nib) {

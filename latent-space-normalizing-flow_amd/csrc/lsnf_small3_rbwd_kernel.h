@@ -10,7 +10,8 @@
 // the second and lsnf_small3_rhmc.hip the third, both with UPDATE = false (their tails load e1, the first half of eps, themselves: in
 // front of their own barrier); lsnf_small3_rhmcr.hip is the third column with a step per row (lsnf_small3_rhmcr_kernel, Small3RhmcRowsArgs),
 // lsnf_small3_rhmcm.hip that one with a diagonal metric per row (lsnf_small3_rhmcm_kernel, Small3RhmcMetricArgs), lsnf_small3_rhmct.hip
-// that one with a likelihood temperature per row (lsnf_small3_rhmct_kernel, Small3RhmcTemperedArgs).
+// that one with a likelihood temperature per row (lsnf_small3_rhmct_kernel, Small3RhmcTemperedArgs), lsnf_small3_rhmcx.hip that one
+// with a replica-exchange move between rows (lsnf_small3_rhmcx_kernel, Small3RhmcExchangeArgs).
 #pragma once
 
 namespace {
@@ -81,6 +82,11 @@ struct Small3RhmcMetricArgs : Small3RhmcRowsArgs {
 // temperature (B) and the Kahan pair of the importance weight (B, 2; 8-byte aligned)
 struct Small3RhmcTemperedArgs : Small3RhmcMetricArgs {
     float* beta_rows; const float* beta_next; float* like_grad_acc; float* like_u_acc; float* log_w;
+};
+// exchanging HMC form (lsnf_reverse_hmc_step_exchange, lsnf_small3_rhmcx.hip): the tempered form's tensors and, with LSNF_HMC_SWAP
+// (128), the ladder's length, the pairs' uniforms (B, read at the lower row; NULL: drawn in-kernel) and the move's two optional outputs
+struct Small3RhmcExchangeArgs : Small3RhmcTemperedArgs {
+    int ladder; const float* swap_uniform; float* swap_out; float* log_swap_out;
 };
 
 __device__ __forceinline__ f32x4 rb_mask4(f32x4 a, unsigned nib) {

@@ -890,3 +890,4 @@ from .mcmc import HMC_ADAPT, HMC_ADAPT_LAST, HmcRowSteps, new_hmc_row_steps, hmc
 from .mcmc import (HMC_METRIC_CLOSE, HMC_METRIC_FOLD, HmcRowMetric, new_hmc_row_metric, hmc_step_metric,  # noqa: E402,F401
                    reverse_hmc_step_metric)
 from .mcmc import HMC_ANNEAL, HmcRowTemper, new_hmc_row_temper, hmc_step_tempered, reverse_hmc_step_tempered  # noqa: E402,F401
+from .mcmc import HMC_SWAP, HMC_SWAP_ODD, hmc_step_exchange, reverse_hmc_step_exchange  # noqa: E402,F401

@@ -696,6 +696,171 @@ estimate_log_px_ais_z_with_flow.__doc__ += _AIS_DOC
 estimate_log_px_ais_eps_with_flow.__doc__ += _AIS_DOC
 
 
+def pt_ladder(R: int, beta_min: float) -> torch.Tensor:
+    """The R inverse temperatures of a parallel-tempering ladder, float64, increasing: rung 0 is exactly beta_min, rung R - 1 exactly
+    1.0 (the posterior), geometric in between -- beta_r = beta_min^((R - 1 - r) / (R - 1)), the spacing that equalises the swap rates
+    of a Gaussian target.  beta_min = 0.0 is allowed and means the prior: rung 0 is then 0.0 and rungs 1 .. R - 1 halve downwards from
+    1.0 (beta_r = 2^(r - (R - 1))), since no geometric ladder reaches 0.  R is 2, 4, 8 or 16 (`flow.hmc_step_exchange`'s ladder)."""
+    R, beta_min = int(R), float(beta_min)
+    if R not in (2, 4, 8, 16):
+        raise ValueError(f"R must be 2, 4, 8 or 16 (got {R})")
+    if not 0.0 <= beta_min < 1.0:
+        raise ValueError(f"beta_min must lie in [0, 1) (got {beta_min})")
+    r = torch.arange(R, dtype=torch.float64)
+    if beta_min == 0.0:
+        b = torch.pow(torch.tensor(2.0, dtype=torch.float64), r - (R - 1))
+    else:
+        b = torch.pow(torch.tensor(beta_min, dtype=torch.float64), (R - 1 - r) / (R - 1))
+    b[0], b[-1] = beta_min, 1.0
+    return b
+
+
+def _pt_plan(flow, betas, g_l_steps, leapfrog_steps, swap_every, steps, metric):
+    """(betas as a float64 (R) tensor, R, K, L, swap(t) -> None | "even" | "odd" of end call t = 1 .. K) of a parallel-tempering run,
+    checked.  Every swap_every-th end call swaps, the swapping calls alternate even, odd."""
+    betas = torch.as_tensor(betas, dtype=torch.float64).reshape(-1).cpu()
+    R, K, L, E = betas.numel(), int(g_l_steps), int(leapfrog_steps), int(swap_every)
+    if R not in (2, 4, 8, 16):
+        raise ValueError(f"betas must hold 2, 4, 8 or 16 temperatures (got {R})")
+    if L < 1:
+        raise ValueError(f"leapfrog_steps must be >= 1 (got {leapfrog_steps})")
+    if E < 1:
+        raise ValueError(f"swap_every must be >= 1 (got {swap_every})")
+    if steps is not None and not isinstance(steps, flow.HmcRowSteps):
+        raise flow.LsnfError("steps must be a flow.HmcRowSteps (new_hmc_row_steps()), or None")
+    if metric is not None and not isinstance(metric, flow.HmcRowMetric):
+        raise flow.LsnfError("metric must be a flow.HmcRowMetric (new_hmc_row_metric()), or None")
+
+    def swap(t):
+        return None if t % E else ("even", "odd")[(t // E - 1) % 2]
+    return betas, R, K, L, swap
+
+
+def _pt_swap_rate(sums, calls, N, R):
+    """swap_rate (N, R - 1) of a parallel-tempering run: the mean of `swapped` over the calls that paired rungs (r, r + 1) -- those of
+    parity r % 2 --, read at the pair's lower row; 0 for a pair no call tried."""
+    rate = torch.zeros((N, R - 1), dtype=torch.float32, device=sums["even"].device)
+    for p, name in enumerate(("even", "odd")):
+        if calls[name]:
+            rate[:, p::2] = sums[name].view(N, R)[:, p:R - 1:2] / calls[name]
+    return rate
+
+
+_PT_DOC = """
+    betas: the R inverse temperatures of one ladder (`pt_ladder`), R in {2, 4, 8, 16}.  The B = N * R rows are the start and x repeated
+    per rung: row n * R + r is rung r of datum n, at betas[r] for the whole run.  The call schedule is the HMC samplers': one init
+    call, then per t = 1 .. K (g_l_steps) L - 1 inner calls and one end call (`netF.*_exchange`).  Every swap_every-th end call
+    swaps -- t = swap_every, 2 swap_every, .. -- with the parity alternating even, odd from the first of them; the exchange happens
+    inside that call's kernel, after its decision and before the trajectory it begins.  The init call takes philox.step(0) (the first
+    momentum), end call t philox.step(t): its uniform, the next momentum and, if it swaps, the pairs' uniforms (counter field 3) all
+    come from that one offset.  philox is advanced by K + 1 on return.
+    steps / metric: frozen `flow.HmcRowSteps` / `flow.HmcRowMetric` of B rows (nothing adapts here: swapping during a warm-up is not
+    built).  Default: the float (or (B) tensor) g_l_step_size and a unit metric.
+    Returns (z_k of rung R - 1 -- where `pt_ladder` puts beta = 1 -- (N, nz, 1, 1), accept_rate (B) of the trajectories, swap_rate
+    (N, R - 1) per adjacent pair (the mean of `swapped` over the calls that tried the pair), U of the kept states (B), the
+    `flow.HmcState`, the `flow.HmcRowTemper`).  Per trajectory the flow's side runs no torch op beside the two tallies of (B) floats.
+    g_l_steps = 0 or an empty batch returns (the start (N, nz, 1, 1), None, None, None, None, None) without a launch."""
+
+
+def sample_hmc_pt_post_z_with_flow(z, x, netG: nn.Module, netF, *, betas, g_l_steps: int, leapfrog_steps: int, g_l_step_size,
+                                   g_llhd_sigma: float, philox, swap_every: int = 1, steps=None, metric=None):
+    """Parallel tempering (replica exchange) of HMC chains in z on p_flow(z) p(x | G(z))^beta: R replicas per datum at the
+    temperatures `betas`, the hot ones crossing between the modes a posterior of an ambiguous x has, the swap fused into the end
+    call's kernel (`netF.hmc_step_exchange`)."""
+    from . import flow
+    betas, R, K, L, swap = _pt_plan(flow, betas, g_l_steps, leapfrog_steps, swap_every, steps, metric)
+    N, nz = z.shape[0], z.shape[1]
+    if K < 1 or N == 0:
+        return z.detach().clone().view(N, nz, 1, 1), None, None, None, None, None
+    B, plan = N * R, netF._plan()
+    c = 1.0 / (2.0 * g_llhd_sigma * g_llhd_sigma)
+    xs = x.detach().repeat_interleave(R, dim=0)
+    z_prop = z.detach().reshape(N, nz).repeat_interleave(R, dim=0).contiguous()
+    dev = z_prop.device
+    steps = _row_steps(flow, steps, B, dev, g_l_step_size, 0.8)
+    metric = flow.new_hmc_row_metric(plan, B, dev) if metric is None else metric
+    temper = flow.new_hmc_row_temper(plan, B, dev, betas.to(torch.float32).repeat(N))
+    state = flow.new_hmc_state(plan, B, dev)
+    accepted = torch.zeros(B, dtype=torch.float32, device=dev)
+    sums = {"even": torch.zeros(B, dtype=torch.float32, device=dev), "odd": torch.zeros(B, dtype=torch.float32, device=dev)}
+    calls = {"even": 0, "odd": 0}
+    for j in range(K * L + 1):
+        zr = z_prop.view(B, nz, 1, 1).detach().requires_grad_(True)
+        energy = c * ((netG(zr) - xs) ** 2).flatten(1).sum(1)                                # train.py:312-313, per row
+        grad_g = torch.autograd.grad(energy.sum(), zr)[0].reshape(B, nz).contiguous()        # train.py:314
+        t, inner = j // L, j % L != 0
+        end = bool(j) and not inner
+        parity = swap(t) if end else None
+        _, acc, _, _, swapped, _ = netF.hmc_step_exchange(z_prop, grad_g, energy.detach(), state, None if inner else philox.step(t), steps,
+                                                          metric, temper, phase="inner" if inner else "end" if j else "init",
+                                                          propose=j < K * L, inplace=True, reuse_buffers=True, swap=parity, ladder=R)
+        if end:
+            accepted += acc
+        if parity:
+            sums[parity] += swapped
+            calls[parity] += 1
+    philox.advance(K + 1)
+    z_k = state.z.view(N, R, nz)[:, R - 1].contiguous().view(N, nz, 1, 1)
+    return z_k, accepted / K, _pt_swap_rate(sums, calls, N, R), state.energy, state, temper
+
+
+def sample_hmc_pt_post_eps_with_flow(eps, x, netG: nn.Module, netF, *, betas, g_l_steps: int, leapfrog_steps: int, g_l_step_size,
+                                     g_llhd_sigma: float, philox, swap_every: int = 1, steps=None, metric=None):
+    """`sample_hmc_pt_post_z_with_flow` with the chains in the flow's base space (`netF.reverse_hmc_step_exchange`): they run on eps
+    with z = f^-1(eps), the prior is N(0, I) at every temperature and the flow's side of a leapfrog step is the reverse and ONE more
+    launch.  The start is eps (N, nz); state.z holds the replicas' eps_k; the first result is z_k = f^-1(eps_k) of rung R - 1."""
+    from . import flow
+    betas, R, K, L, swap = _pt_plan(flow, betas, g_l_steps, leapfrog_steps, swap_every, steps, metric)
+    N, nz = eps.shape[0], eps.shape[1]
+    if K < 1 or N == 0:
+        return eps.detach().clone().view(N, nz, 1, 1), None, None, None, None, None
+    B, plan = N * R, netF._plan()
+    c = 1.0 / (2.0 * g_llhd_sigma * g_llhd_sigma)
+    xs = x.detach().repeat_interleave(R, dim=0)
+    eps_prop = eps.detach().reshape(N, nz).repeat_interleave(R, dim=0).contiguous()
+    dev = eps_prop.device
+    steps = _row_steps(flow, steps, B, dev, g_l_step_size, 0.8)
+    metric = flow.new_hmc_row_metric(plan, B, dev) if metric is None else metric
+    temper = flow.new_hmc_row_temper(plan, B, dev, betas.to(torch.float32).repeat(N))
+    keeps = flow.reverse_keep_supported(plan, B)
+    act = flow.new_act_saved(plan, B, dev)
+    state = flow.new_hmc_state(plan, B, dev)
+    accepted = torch.zeros(B, dtype=torch.float32, device=dev)
+    sums = {"even": torch.zeros(B, dtype=torch.float32, device=dev), "odd": torch.zeros(B, dtype=torch.float32, device=dev)}
+    calls = {"even": 0, "odd": 0}
+    with torch.no_grad():
+        for j in range(K * L + 1):
+            if keeps:
+                z, _, saved = flow.reverse(plan, eps_prop, None, save_for_backward=True, act_saved=act)
+            else:
+                z, _ = flow.reverse(plan, eps_prop, None)
+                saved = flow.forward(plan, z, None, want_ll=False, save_for_backward=True, act_saved=act)[3]
+            with torch.enable_grad():
+                zr = z.view(B, nz, 1, 1).requires_grad_(True)
+                energy = c * ((netG(zr) - xs) ** 2).flatten(1).sum(1)                                # train.py:312-313, per row
+                grad_g = torch.autograd.grad(energy.sum(), zr)[0].reshape(B, nz).contiguous()        # train.py:314
+            t, inner = j // L, j % L != 0
+            end = bool(j) and not inner
+            parity = swap(t) if end else None
+            _, acc, _, swapped, _ = netF.reverse_hmc_step_exchange(eps_prop, saved, act, grad_g, energy.detach(), state,
+                                                                   None if inner else philox.step(t), steps, metric, temper,
+                                                                   phase="inner" if inner else "end" if j else "init",
+                                                                   propose=j < K * L, inplace=True, reuse_buffers=True, swap=parity,
+                                                                   ladder=R)
+            if end:
+                accepted += acc
+            if parity:
+                sums[parity] += swapped
+                calls[parity] += 1
+        z = flow.reverse(plan, state.z.view(N, R, nz)[:, R - 1].contiguous(), None)[0]
+    philox.advance(K + 1)
+    return z.view(N, nz, 1, 1), accepted / K, _pt_swap_rate(sums, calls, N, R), state.energy, state, temper
+
+
+sample_hmc_pt_post_z_with_flow.__doc__ += _PT_DOC
+sample_hmc_pt_post_eps_with_flow.__doc__ += _PT_DOC
+
+
 def flow_mle_step(netF, optF, z_g_k, f_max_norm: Optional[float] = None, fused: bool = False):
     """train.py:404-415: one Adam step of the flow on the Langevin-inferred z.  Returns loss_f (detached).
     fused=False restates the reference line by line (autograd through `netF(...)`); fused=True computes the same

@@ -2,7 +2,8 @@
 `flow.mala_step`, `flow.reverse_mala_step`, `flow.MalaState`, `flow.new_mala_state`, `flow.hmc_step`, `flow.reverse_hmc_step`,
 `flow.HmcState`, `flow.new_hmc_state`, `flow.hmc_step_rows`, `flow.reverse_hmc_step_rows`, `flow.HmcRowSteps`,
 `flow.new_hmc_row_steps`, `flow.hmc_step_metric`, `flow.reverse_hmc_step_metric`, `flow.HmcRowMetric`, `flow.new_hmc_row_metric`,
-`flow.hmc_step_tempered`, `flow.reverse_hmc_step_tempered`, `flow.HmcRowTemper`, `flow.new_hmc_row_temper`.
+`flow.hmc_step_tempered`, `flow.reverse_hmc_step_tempered`, `flow.HmcRowTemper`, `flow.new_hmc_row_temper`,
+`flow.hmc_step_exchange`, `flow.reverse_hmc_step_exchange`.
 Every tensor goes through flow.py's one checking path before anything is launched; like there, all functions raise on CPU tensors:
 there is no CPU path."""
 from __future__ import annotations
@@ -585,3 +586,112 @@ def reverse_hmc_step_tempered(plan: FlowPlan, eps_prop: torch.Tensor, z_saved: O
           _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(state.mom), _ptr(state.kin), _ptr(noise), _ptr(uniform),
           rng, step_ptr, adapt_ptr, da, *metric_args, *temper_args, flags, _ptr(eps_next), _ptr(acc), _ptr(la))
     return eps_next, acc, la
+
+
+HMC_SWAP, HMC_SWAP_ODD = 128, 256     # include/lsnf_flow_mcmc.h LSNF_HMC_SWAP, LSNF_HMC_SWAP_ODD
+
+
+def _row_exchange_mode(swap, ladder, phase, adapt, window, anneal):
+    """What the exchanging calls check before `_check_chain`, beside `_row_temper_mode`: swap is None, "even" or "odd"; a swapping
+    call is an end call that neither adapts, folds, closes nor anneals, and its ladder is 2, 4, 8 or 16.  Returns the swap's flags."""
+    if swap is None:
+        return 0
+    if swap not in ("even", "odd"):
+        raise LsnfError(f"swap must be None, 'even' or 'odd' (got {swap!r})")
+    if phase != "end" or adapt is not None or window is not None or anneal is not None:
+        raise LsnfError("replicas are exchanged between two trajectories of a frozen chain: swap goes with phase='end', "
+                        "without adapt, window and anneal")
+    if ladder not in (2, 4, 8, 16):
+        raise LsnfError(f"ladder must be 2, 4, 8 or 16 (got {ladder!r})")
+    return HMC_SWAP | (HMC_SWAP_ODD if swap == "odd" else 0)
+
+
+def _row_exchange_args(plan, swap, ladder, swap_uniform, rng, B, dev, reuse_buffers):
+    """After `_check_chain`: the swap's uniforms through the one checking path and its two outputs.  Returns (the four arguments in the
+    order the C call names them: ladder, swap_uniform, swap_out, log_swap_out; swapped; log_swap) -- the last two None without swap."""
+    _check_in(swap_uniform, "swap_uniform", B, dev)
+    if swap is None:
+        if swap_uniform is not None:
+            raise LsnfError("swap_uniform goes with swap='even' or 'odd'")
+        return (0, None, None, None), None, None
+    if B % ladder:
+        raise LsnfError(f"the chain's {B} rows are not a multiple of ladder={ladder}")
+    if (rng is None) != (swap_uniform is not None):
+        raise LsnfError("the swap draws as the trajectory does: swap_uniform with the tensors (noise, uniform=), none with a PhiloxNoise")
+
+    def make():
+        f32 = dict(dtype=torch.float32, device=dev)
+        return {"swapped": torch.empty(B, **f32), "log_swap": torch.empty(B, **f32)}
+    bufs = _stream_buffers(plan, "_hmcx_buffers", B, dev, make) if reuse_buffers else make()
+    return (int(ladder), _ptr(swap_uniform), _ptr(bufs["swapped"]), _ptr(bufs["log_swap"])), bufs["swapped"], bufs["log_swap"]
+
+
+def hmc_step_exchange(plan: FlowPlan, z_prop: torch.Tensor, grad_g: Optional[torch.Tensor], energy_g: Optional[torch.Tensor],
+                      state: HmcState, noise, steps: HmcRowSteps, metric: HmcRowMetric, temper: HmcRowTemper, *, phase: str = "end",
+                      uniform: Optional[torch.Tensor] = None, propose: bool = True, inplace: bool = False, reuse_buffers: bool = False,
+                      adapt: Optional[str] = None, window: Optional[str] = None, anneal: Optional[torch.Tensor] = None,
+                      swap: Optional[str] = None, ladder: int = 0, swap_uniform: Optional[torch.Tensor] = None):
+    """`hmc_step_tempered` with a replica-exchange move between the rows of a ladder (include/lsnf_flow_mcmc.h
+    `lsnf_hmc_step_exchange`): parallel tempering.  Rows [k * ladder, (k + 1) * ladder) are the rungs of ladder k at the temperatures
+    temper.beta holds; ladder is 2, 4, 8 or 16 and divides B.
+    swap (phase "end" only, without adapt / window / anneal): "even" pairs rungs (0,1), (2,3), ..; "odd" pairs (1,2), (3,4), .. and
+    leaves the end rungs idle.  After the trajectory's decision the pair (a, b) swaps iff log(u) < (beta_a - beta_b) * (E_a - E_b),
+    E the kept state's like_energy, u = swap_uniform[a] (with tensor noise) or drawn in-kernel (PhiloxNoise).  The STATES are
+    exchanged: a swapping row takes the partner's state.z / like_grad / like_energy and its state.grad / state.energy re-tempered to
+    the row's own beta, and begins the next trajectory (propose) from them; beta, step, scale and the adaptation stay with the row.
+    Without swap this is `hmc_step_tempered` to the bit.  Returns that call's tuple plus (swapped, log_swap), both (B) -- 1.0 on both
+    rows of an exchanged pair, and the pair's log ratio (0.0 on an idle rung) -- or (None, None) without swap."""
+    flags, inner = _row_step_mode(steps, phase, adapt), phase == "inner"
+    flags |= _row_metric_mode(metric, phase, window)
+    flags |= _row_temper_mode(temper, phase, anneal)
+    flags |= _row_exchange_mode(swap, ladder, phase, adapt, window, anneal)
+    B, dev, noise, rng = _check_chain(plan, z_prop, "z_prop", grad_g, energy_g, state, HmcState, noise, uniform)
+    step_ptr, adapt_ptr, da = _row_step_args(steps, B, dev, adapt)
+    metric_args = _row_metric_args(plan, metric, B, dev, window)
+    temper_args = _row_temper_args(plan, temper, B, dev, anneal)
+    exchange_args, swapped, log_swap = _row_exchange_args(plan, swap, ladder, swap_uniform, rng, B, dev, reuse_buffers)
+    if inner and (noise is not None or rng is not None or uniform is not None or not propose):
+        raise LsnfError("an inner leapfrog step draws and decides nothing: noise and uniform must be None, propose True")
+    bufs, z1, ll = _forward_at(plan, z_prop, B, dev, "_hmc_buffers", reuse_buffers)
+    z_next = None if not propose else z_prop if inplace else torch.empty_like(z_prop)
+    acc, la = (None, None) if inner else (bufs["acc"], bufs["la"])
+    _call("lsnf_hmc_step_exchange", dev, *_plan_head(plan), B, _ptr(z_prop), _ptr(z1), _ptr(bufs["saved"]), _ptr(bufs["act"]), _ptr(ll),
+          _ptr(grad_g), _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(state.mom), _ptr(state.kin), _ptr(noise),
+          _ptr(uniform), rng, step_ptr, adapt_ptr, da, *metric_args, *temper_args, flags, _ptr(z_next), _ptr(acc), _ptr(la), *exchange_args)
+    return z_next, acc, la, ll, swapped, log_swap
+
+
+def reverse_hmc_step_exchange(plan: FlowPlan, eps_prop: torch.Tensor, z_saved: Optional[torch.Tensor], act_saved: torch.Tensor,
+                              grad_g: Optional[torch.Tensor], energy_g: Optional[torch.Tensor], state: HmcState, noise, steps: HmcRowSteps,
+                              metric: HmcRowMetric, temper: HmcRowTemper, *, phase: str = "end", uniform: Optional[torch.Tensor] = None,
+                              propose: bool = True, inplace: bool = False, reuse_buffers: bool = False, adapt: Optional[str] = None,
+                              window: Optional[str] = None, anneal: Optional[torch.Tensor] = None, swap: Optional[str] = None,
+                              ladder: int = 0, swap_uniform: Optional[torch.Tensor] = None):
+    """`reverse_hmc_step_tempered` with a replica-exchange move between the rows of a ladder (include/lsnf_flow_mcmc.h
+    `lsnf_reverse_hmc_step_exchange`); swap, ladder and swap_uniform: as `hmc_step_exchange`'s, with the state (eps, eps + beta *
+    like_grad, |eps|^2 / 2 + beta * like_energy).  ONE launch and nothing else, so a swapping end call can be captured in a graph.
+    Returns `reverse_hmc_step_tempered`'s tuple plus (swapped, log_swap), (None, None) without swap."""
+    flags, inner = _row_step_mode(steps, phase, adapt), phase == "inner"
+    flags |= _row_metric_mode(metric, phase, window)
+    flags |= _row_temper_mode(temper, phase, anneal)
+    flags |= _row_exchange_mode(swap, ladder, phase, adapt, window, anneal)
+    B, dev, noise, rng = _check_chain(plan, eps_prop, "eps_prop", grad_g, energy_g, state, HmcState, noise, uniform,
+                                      stash=(z_saved, act_saved))
+    step_ptr, adapt_ptr, da = _row_step_args(steps, B, dev, adapt)
+    metric_args = _row_metric_args(plan, metric, B, dev, window)
+    temper_args = _row_temper_args(plan, temper, B, dev, anneal)
+    exchange_args, swapped, log_swap = _row_exchange_args(plan, swap, ladder, swap_uniform, rng, B, dev, reuse_buffers)
+    if inner and (noise is not None or rng is not None or uniform is not None or not propose):
+        raise LsnfError("an inner leapfrog step draws and decides nothing: noise and uniform must be None, propose True")
+    acc = la = None
+    if not inner:
+        def make():
+            f32 = dict(dtype=torch.float32, device=dev)
+            return {"acc": torch.empty(B, **f32), "la": torch.empty(B, **f32)}
+        bufs = _stream_buffers(plan, "_rhmc_buffers", B, dev, make) if reuse_buffers else make()
+        acc, la = bufs["acc"], bufs["la"]
+    eps_next = None if not propose else eps_prop if inplace else torch.empty_like(eps_prop)
+    _call("lsnf_reverse_hmc_step_exchange", dev, *_plan_head(plan), B, _ptr(eps_prop), _ptr(z_saved), _ptr(act_saved), _ptr(grad_g),
+          _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(state.mom), _ptr(state.kin), _ptr(noise), _ptr(uniform),
+          rng, step_ptr, adapt_ptr, da, *metric_args, *temper_args, flags, _ptr(eps_next), _ptr(acc), _ptr(la), *exchange_args)
+    return eps_next, acc, la, swapped, log_swap

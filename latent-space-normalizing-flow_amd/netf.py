@@ -557,6 +557,29 @@ class _netF(nn.Module):
                                               propose=propose, inplace=inplace, reuse_buffers=reuse_buffers, adapt=adapt, window=window,
                                               anneal=det(anneal))
 
+    def hmc_step_exchange(self, z_prop, grad_g=None, energy_g=None, state=None, noise=None, steps=None, metric=None, temper=None, *,
+                          phase="end", uniform=None, propose=True, inplace=False, reuse_buffers=False, adapt=None, window=None,
+                          anneal=None, swap=None, ladder=0, swap_uniform=None):
+        """`hmc_step_tempered` with a replica-exchange move between the rows of a ladder (`flow.hmc_step_exchange`): swap = "even" or
+        "odd" on an end call exchanges the states of paired rungs inside the kernel.  Returns what `hmc_step` returns plus
+        (swapped, log_swap)."""
+        det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t
+        return flow.hmc_step_exchange(self._plan(), det(z_prop), det(grad_g), det(energy_g), state, det(noise), steps, metric, temper,
+                                      phase=phase, uniform=det(uniform), propose=propose, inplace=inplace, reuse_buffers=reuse_buffers,
+                                      adapt=adapt, window=window, anneal=det(anneal), swap=swap, ladder=ladder,
+                                      swap_uniform=det(swap_uniform))
+
+    def reverse_hmc_step_exchange(self, eps_prop, z_saved, act_saved, grad_g=None, energy_g=None, state=None, noise=None, steps=None,
+                                  metric=None, temper=None, *, phase="end", uniform=None, propose=True, inplace=False,
+                                  reuse_buffers=False, adapt=None, window=None, anneal=None, swap=None, ladder=0, swap_uniform=None):
+        """`reverse_hmc_step_tempered` with a replica-exchange move between the rows of a ladder (`flow.reverse_hmc_step_exchange`).
+        Returns what `reverse_hmc_step` returns plus (swapped, log_swap)."""
+        det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t
+        return flow.reverse_hmc_step_exchange(self._plan(), det(eps_prop), det(z_saved), det(act_saved), det(grad_g), det(energy_g),
+                                              state, det(noise), steps, metric, temper, phase=phase, uniform=det(uniform),
+                                              propose=propose, inplace=inplace, reuse_buffers=reuse_buffers, adapt=adapt, window=window,
+                                              anneal=det(anneal), swap=swap, ladder=ladder, swap_uniform=det(swap_uniform))
+
     def mle_grads(self, z, accumulate: bool = False, max_norm: Optional[float] = None, reuse_buffers: bool = False):
         """Fused flow-MLE gradients (train.py:404-411): loss_f = -mean_b ll(z_b) and d loss_f / d theta written to
         `.grad` of the 60 live tensors -- forward (ll summed in-kernel), dump backward, batch contraction, unfold:
