@@ -10,7 +10,11 @@ every pair; pair k is meant to swap or not alternately and gets u = exp(log_r -+
 whatever u is (`forced` lets it), so a pair meant to reject is given temperatures ordered against its energies: the kept like_energy of a row is set to
 the record's energy + 2^-9 (1 + row % 3), so that el_s is within 0.006 of the record's energy whether the row accepts or not and the
 sign of e = el_s_a - el_s_b is known beforehand wherever the records differ by more.  The float64 decision is taken with the fp32 u the
-kernel is given, and no pair may be nearer to a tie than 1e-4 (1 + |log_r|) -- some fifty times what fp32 can move log(u) - log_r."""
+kernel is given, and no pair may be nearer to a tie than 1e-4 (1 + |log_r|) -- some fifty times what fp32 can move log(u) - log_r.
+
+The case lists (SWAP, NEXT, UNIFORM, FORMS) hold C3 / TINY / C5 and the geometry classes of tests/chain_geometries.py;
+tests/test_chain_geometries_cpu.py holds them to that table.  `check_swap_forms` compares call forms of a swapping call with its plain
+form.  No check here has a tolerance of its own: bit identities, and hmc_metric_gpu.gates for the next trajectory."""
 import copy
 import types
 
@@ -18,6 +22,7 @@ import numpy as np
 import torch
 
 from oracle.philox_oracle import philox4x32_10
+import chain_geometries as G
 import hmc_exchange_restated as X
 import hmc_metric_gpu as MG
 import hmc_rows_gpu as HG
@@ -36,27 +41,49 @@ IDENTITY = HG.IDENTITY                       # every instantiation of an exchang
 SWAP = [g + (R, R) for g in (C3, TINY) for R in (2, 4, 8, 16)] + [g + bR for g in (C3, TINY) for bR in ((24, 8), (32, 16), (64, 16))] + \
        [C3 + (4100, 4), C3 + (8200, 8), C3 + (16400, 16), TINY + (4100, 4), TINY + (8200, 8), HG.C5 + (32, 16), HG.C5 + (4100, 4)]
 NEXT = [C3 + (24, 8), TINY + (32, 16), C3 + (4100, 4)]
+UNIFORM = [C3 + (64, 8), TINY + (32, 16)]                   # the in-kernel uniform (`check_in_kernel_uniform`)
+# The geometry classes of tests/chain_geometries.py (a ragged half, a half 2 mod 4, halves 31 / 33 with their scalar row access, whole
+# tiles of padding, additive coupling): where nz / 2 and the width end inside the 32-column tiles decides which columns of a quad the
+# partner's lane holds, which waves own a half-unit without a real column and what the next trajectory's xi masks.  Every entry at 24
+# rows of R = 8 (one whole 16-row tile and one with a live and a dead ladder: dead lanes pair among themselves); every R at a ragged
+# half and at an empty second half-tile of <2, 2> and of <2, 4>; B = 4: two ladders in a tile of twelve dead rows; (62, 31) as one
+# ladder of 16; additive coupling; the two 4100 / 8200-row entries (32 and 64 rows per workgroup: several ladders per workgroup, 4100
+# ends in a ragged tile).
+SWAP += [g + (24, 8) for g in G.GEOS] + \
+        [(66, 33, 2, 1, 32, 16), (66, 33, 2, 1, 4, 2), (10, 40, 2, 1, 32, 16), (12, 100, 2, 1, 20, 4), (62, 31, 2, 1, 16, 16),
+         (66, 33, 3, 0, 32, 16)] + [G.LARGE[0] + (4,), G.LARGE[1] + (8,)]
+# half 62: a four-column draw straddles the end of the half under xi, mom and kin0 of the exchanged state; an empty half-tile
+NEXT += [(124, 63, 3, 1, 24, 8), (10, 40, 2, 1, 32, 16)]
+UNIFORM += [(66, 33, 2, 1, 32, 8), (10, 40, 2, 1, 32, 16)]
+FORMS = [c[:4] + (24, 8) for c in G.FORMS]                   # the call forms of a swapping end call (`check_swap_forms`)
+# Added to `design`'s seed for a case of SWAP, keyed by the case, should the default draws leave it without a swapping and a
+# non-swapping pair in some launch or put a pair within `forced`'s margin of a tie.  To be chosen on the CPU from the float64 records
+# (their energies and `kept_energy` on the rows either way, accepted or not), never from the device's answer: none needed -- every
+# launch of every case above has both kinds of pair, and the nearest pair of any case is 100 margins from a tie (profiles/hmc_exchange_geometries.txt).
+DESIGN_SEED = {}
 DELTA = 2.0 ** -9
 SWAPPED = -(len(TEMPER) + len(METRIC) + 2) - 2               # `swapped` in hmc_tempered_gpu.flat of a swapping call's result
 
 
 def run(lsnf, sp, s, r, steps, metric, temper, noise, uniform, rows=slice(None), state=None, adapt=None, window=None, propose=True,
-        anneal=None, swap=None, ladder=0, swap_uniform=None, e="record"):
+        anneal=None, swap=None, ladder=0, swap_uniform=None, e="record", ge="record", point=None, inplace=False, reuse_buffers=False):
     """The recorded call r on its rows from its inputs' casts through the exchanging wrapper: (state after, [next point, accepted,
-    log_alpha, swapped, log_swap]).  e: the record's energy_g, or another (the rows' own, already cut)."""
+    log_alpha, swapped, log_swap]).  e / ge / point: the record's energy_g / grad_g / point, or another (the rows' own, already
+    cut; None for e and ge: the NULL form)."""
     F, dev = lsnf.flow, s.dev
     cut = lambda t: None if t is None else t[rows].float().to(dev).contiguous()
     state = sp.T.state_for(lsnf, s, r, rows) if state is None else state
     kw = dict(phase=r.phase, uniform=uniform, propose=propose, adapt=adapt, window=window, anneal=anneal, swap=swap, ladder=ladder,
-              swap_uniform=swap_uniform)
-    point = cut(sp.point(r))
+              swap_uniform=swap_uniform, inplace=inplace, reuse_buffers=reuse_buffers)
+    point = cut(sp.point(r)) if point is None else point
     e = cut(r.e) if isinstance(e, str) else e
+    ge = cut(r.ge) if isinstance(ge, str) else ge
     if sp.name == "z":
-        out = F.hmc_step_exchange(s.plan, point, cut(r.ge), e, state, noise, steps, metric, temper, **kw)
+        out = F.hmc_step_exchange(s.plan, point, ge, e, state, noise, steps, metric, temper, **kw)
         out = out[:3] + out[4:]
     else:
         saved, act = sp.T.stash_at(lsnf, s.plan, point)
-        out = F.reverse_hmc_step_exchange(s.plan, point, saved, act, cut(r.ge), e, state, noise, steps, metric, temper, **kw)
+        out = F.reverse_hmc_step_exchange(s.plan, point, saved, act, ge, e, state, noise, steps, metric, temper, **kw)
     return state, list(out)
 
 
@@ -156,7 +183,7 @@ def check_swap_bits(lsnf, sp, s, R):
         for propose in (True, False):
             for first in (True, False):
                 name = f"[{sp.name} exchange] {c.geo} B{B} R{R} {parity} propose={propose} first_swaps={first}"
-                beta, want, _ = design(B, R, parity, e32, first, seed=R + (parity == "odd"))
+                beta, want, _ = design(B, R, parity, e32, first, seed=R + (parity == "odd") + DESIGN_SEED.get(c.geo + (B, R), 0))
                 beta = beta.to(dev)
                 noise, uniform = HG.draws(lsnf, sp, c, r, "tensors", dev, propose)
 
@@ -173,6 +200,7 @@ def check_swap_bits(lsnf, sp, s, R):
                 lr64 = X.log_ratio(beta.double().cpu(), ta.like_energy.double().cpu(), prt)
                 u, sw64, tie = forced(lr64, want, prt)
                 assert tie > 1.0, f"{name}: a pair is near a tie ({tie:.3g} of the margin)"
+                print(f"{name}: {int(sw64.sum())} of {int(paired.sum())} paired rows swap, the nearest pair at {tie:.3g} of the margin from a tie")
                 seen_swap, seen_stay = seen_swap or bool(sw64.any()), seen_stay or bool((~sw64 & paired).any())
                 if paired.sum() > 2:                         # (a launch with one pair cannot hold both kinds: the case does, below)
                     assert bool(sw64.any()) and bool((~sw64 & paired).any()), f"{name}: the launch needs a swapping and a non-swapping pair"
@@ -426,3 +454,102 @@ def check_samplers(lsnf, sp, K, dev, monkeypatch):
     ph = F.PhiloxNoise(7, 3, 0)
     none = fn(start, x, netG, net, philox=ph, **dict(kw, g_l_steps=0))
     assert bits(none[0].view(N, nz), start) and none[1:] == (None,) * 5 and ph.offset == 3
+
+
+# ---- 8 ----
+def check_swap_forms(lsnf, sp, s, R):
+    """The call forms of an end call with swap="odd" that proposes, each against the plain form of the same swapping call bit for
+    bit (hmc_tempered_gpu.flat plus swapped and log_swap): in place; every tensor 4 bytes off a 16-byte boundary -- swap_uniform, the
+    state, steps, metric and temper tensors among them, log_w 8 bytes off: it stays 8-byte aligned; the stash stays 16-byte aligned --,
+    which is where the scalar row access meets the lane exchange whatever the half; grad_g = energy_g = None against zeros with a
+    PhiloxNoise (the kept like_energy zero as well: log_r is +-0 and EVERY pair swaps, asserted); reuse_buffers=True, two consecutive
+    calls against two calls with fresh buffers.  The uniforms are forced as `check_swap_bits` forces them, so the plain form has a
+    swapping and a non-swapping pair.  (The wrapper always allocates swapped / log_swap: the NULL form of those two arguments of the
+    C call is not reachable from here and is not covered.)"""
+    c, dev, B, F = s.c, s.dev, s.c.B, lsnf.flow
+    r = sp.end_calls(c)[0]
+    parity, name = "odd", f"[{sp.name} exchange] {c.geo} B{B} R{R} odd forms"
+    e32 = r.e.float()
+    sd = MG.column_scale(B, c.nz, 5, spread=1.0)
+    prt = X.partner(B, R, parity)
+    paired = prt != torch.arange(B)
+    beta, want, _ = design(B, R, parity, e32, True, seed=90 + R)
+    beta = beta.to(dev)
+    noise, uniform = HG.draws(lsnf, sp, c, r, "tensors", dev, True)
+    swap = dict(swap=parity, ladder=R)
+
+    def fresh(kept=None):
+        steps, metric = MG.same_steps(lsnf, sp, c, B, dev, 7), MG.new_metric(lsnf, s, B, sd)
+        temper = TG.new_temper(lsnf, s, B, beta, "old")
+        temper.like_energy.copy_(kept_energy(e32.to(dev)) if kept is None else kept)
+        return steps, metric, temper
+
+    def whole(res, steps, metric, temper):
+        state, out = res
+        return TG.flat((state, out[:3]), steps, metric, temper) + [out[3], out[4]]
+
+    def same(got, ref, form):
+        assert len(got) == len(ref)
+        for k, (a, b) in enumerate(zip(got, ref)):
+            assert bits(a, b), f"{name}: {form}: output {k} differs from the plain form's"
+
+    def off(t, floats=1):
+        if t is None:
+            return None
+        t = t.float().to(dev)
+        b = torch.empty(t.numel() + 4, dtype=torch.float32, device=dev)
+        v = b[floats: floats + t.numel()].view(t.shape)
+        v.copy_(t)
+        assert v.data_ptr() % 16 == 4 * floats
+        return v
+    # the uniforms, from the float64 log_r of the call without the swap
+    steps, metric, temper = fresh()
+    run(lsnf, sp, s, r, steps, metric, temper, noise, uniform)
+    torch.cuda.synchronize()
+    u, sw64, tie = forced(X.log_ratio(beta.double().cpu(), temper.like_energy.double().cpu(), prt), want, prt)
+    assert tie > 1.0 and bool(sw64.any()) and bool((~sw64 & paired).any()), f"{name}: the call needs a swapping and a non-swapping pair"
+    u = u.to(dev)
+    steps, metric, temper = fresh()
+    ref = whole(run(lsnf, sp, s, r, steps, metric, temper, noise, uniform, swap_uniform=u, **swap), steps, metric, temper)
+    assert bits(ref[-2], sw64.float().to(dev)), f"{name}: swapped is not the float64 decision"
+    # in place: the next point over the point
+    steps, metric, temper = fresh()
+    point = sp.point(r).float().to(dev).contiguous()
+    res = run(lsnf, sp, s, r, steps, metric, temper, noise, uniform, point=point, inplace=True, swap_uniform=u, **swap)
+    assert res[1][0].data_ptr() == point.data_ptr()
+    same(whole(res, steps, metric, temper), ref, "in place")
+    # every tensor off its 16-byte boundary
+    steps, metric, temper = fresh()
+    steps = F.HmcRowSteps(off(steps.step), steps.adapt)
+    metric = F.HmcRowMetric(off(metric.scale), off(metric.mean), off(metric.m2), off(metric.count))
+    temper = F.HmcRowTemper(off(temper.beta), off(temper.like_grad), off(temper.like_energy), off(temper.log_w, 2))
+    assert temper.log_w.data_ptr() % 16 == 8
+    st = sp.T.state_for(lsnf, s, r)
+    state = F.HmcState(*(off(getattr(st, f)) for f in FIELDS))
+    res = run(lsnf, sp, s, r, steps, metric, temper, off(noise), off(uniform), state=state, point=off(sp.point(r)), ge=off(r.ge), e=off(r.e),
+              inplace=True, swap_uniform=off(u), **swap)
+    same(whole(res, steps, metric, temper), ref, "4 bytes off")
+    # NULL gradient and energy are zeros; with the kept like_energy zero too every el_s is 0, log_r = +-0 and every pair swaps
+    rng, both = F.PhiloxNoise(8, 9, 0), []
+    for gg, e in ((None, None), (torch.zeros(B, c.nz, device=dev), torch.zeros(B, device=dev))):
+        steps, metric, temper = fresh(torch.zeros(B, device=dev))
+        both.append(whole(run(lsnf, sp, s, r, steps, metric, temper, rng, None, ge=gg, e=e, **swap), steps, metric, temper))
+    same(both[0], both[1], "NULL grad_g / energy_g")
+    swapped, log_swap = both[0][-2].cpu(), both[0][-1].cpu()
+    assert bool((swapped[paired] == 1.0).all()) and bool((swapped[~paired] == 0.0).all()) and bool((log_swap == 0.0).all()), \
+        f"{name}: with a null likelihood every pair swaps"
+    # reuse_buffers: two consecutive calls (the second from the first one's state) against the same two with fresh buffers
+    def twice(reuse):
+        steps, metric, temper = fresh()
+        state, outs, ptrs = sp.T.state_for(lsnf, s, r), [], []
+        for _ in range(2):
+            res = run(lsnf, sp, s, r, steps, metric, temper, noise, uniform, state=state, swap_uniform=u, reuse_buffers=reuse, **swap)
+            outs.append([t.clone() for t in whole(res, steps, metric, temper)])
+            ptrs.append(res[1][3].data_ptr())
+        return outs, ptrs
+    (a1, a2), kept_ptrs = twice(True)
+    (b1, b2), _ = twice(False)
+    assert kept_ptrs[0] == kept_ptrs[1]                      # (swapped lives on the plan: the second call wrote over the first one's)
+    same(a1, ref, "reuse_buffers, first call"); same(b1, ref, "fresh buffers, first call")
+    same(a2, b2, "reuse_buffers, second call")
+    assert not all(bits(x, y) for x, y in zip(a2, a1))       # (the second call is another computation: it starts from the first one's state)

@@ -63,3 +63,28 @@ def test_the_four_modules_run_the_table():
         assert set(G.CASES) <= set(T.PHILOX_CASES), T.__name__
     for T in (ZM, RMt, TH):                         # a step for every entry, keyed by the geometry
         assert set(G.GEOS) <= set(T.STEP_GEO), T.__name__
+
+
+def test_the_row_metric_tempered_and_exchange_lists_run_the_table():
+    """Importing the shared GPU check modules needs no device.  The metric and tempered calls run every entry; the replica-exchange
+    swap runs every geometry and both large entries, every ladder size at a straddling half, an empty second half-tile in <2, 2> and
+    in <2, 4> and additive coupling; the next trajectory and the in-kernel uniform of a swapping call each run a straddling half and
+    an empty half-tile."""
+    import hmc_exchange_gpu as XG
+    import hmc_metric_gpu as MG
+    import hmc_tempered_gpu as TG
+    assert set(G.CASES + G.LARGE) <= set(MG.COLUMN) and set(G.CASES + G.LARGE) <= set(TG.GENERAL)
+    swap_geos = {c[:4] for c in XG.SWAP}
+    assert set(G.GEOS) <= swap_geos
+    for large in G.LARGE:
+        assert any(c[:5] == large for c in XG.SWAP), large
+    for R in (2, 4, 8, 16):
+        assert any(c[5] == R and G.draw_straddles(c[:4]) for c in XG.SWAP), R
+    for tiles in ((2, 2), (2, 4)):
+        assert any(G.second_half_tile_empty(c[:4]) and G.pick_tiles(c[0] // 2, c[1]) == tiles for c in XG.SWAP), tiles
+    assert any(c[3] == 0 for c in XG.SWAP)
+    for cases in (XG.NEXT, XG.UNIFORM):
+        assert any(G.draw_straddles(c[:4]) for c in cases) and any(G.second_half_tile_empty(c[:4]) for c in cases)
+    for nz, w, depth, coupling, B, R in XG.SWAP + XG.NEXT + XG.UNIFORM + XG.FORMS:
+        assert R in (2, 4, 8, 16) and B % R == 0, (nz, w, depth, coupling, B, R)
+    assert {c[:4] for c in XG.FORMS} == {c[:4] for c in G.FORMS} and len(set(XG.SWAP)) == len(XG.SWAP)

@@ -3,7 +3,8 @@ Carlo in the flow's base space (lsnf_reverse_hmc_step_exchange, lsnf_small3_rhmc
 `_netF.reverse_hmc_step_exchange` and `langevin.sample_hmc_pt_post_eps_with_flow`.  The checks are tests/hmc_exchange_gpu.py's, shared
 with tests/test_gpu_hmc_exchange.py (whose docstring lists them); the cases, their teacher-forcing records and their steps are
 tests/test_gpu_rhmc.py's.  The state is (eps, eps + beta like_grad, |eps|^2 / 2 + beta like_energy) with like_grad the kernel's own
-J_{f^-1}(eps)^T grad_g.  Here as well:
+J_{f^-1}(eps)^T grad_g.  The swap, its next trajectory, the in-kernel uniform and the call forms of a swapping call run the same case lists
+(tests/hmc_exchange_gpu.py SWAP, NEXT, UNIFORM, FORMS: C3, TINY, C5 and the geometry classes of tests/chain_geometries.py).  Here as well:
 
 7. one swapping end call that draws in-kernel, captured in a graph and replayed, gives the eager call's bits -- state, likelihood
    parts, swapped and log_swap included."""
@@ -43,7 +44,7 @@ def test_next_trajectory_of_a_swapping_call_follows_float64(lsnf, gpu_device, nz
     XG.check_next_trajectory_follows_float64(lsnf, SP, TR.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B), R)
 
 
-@pytest.mark.parametrize("nz,w,depth,coupling,B,R", [XG.C3 + (64, 8), XG.TINY + (32, 16)])
+@pytest.mark.parametrize("nz,w,depth,coupling,B,R", XG.UNIFORM)
 def test_in_kernel_swap_uniform_is_philox_field_3_of_the_lower_row(lsnf, gpu_device, nz, w, depth, coupling, B, R):
     XG.check_in_kernel_uniform(lsnf, SP, TR.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B), R)
 
@@ -88,6 +89,11 @@ def test_captured_swapping_end_call_replays_to_the_same_bits(lsnf, gpu_device):
     assert all(bits(a, b) for a, b in zip(out, eager)) and all(bits(a, b) for a, b in zip(bg.tensors(), be.tensors()))
     assert 0 < int(eager[3].sum()) < B and 0 < int(eager[1].sum()) < B     # some pairs swapped, some trajectories were accepted
     assert not bits(be.state.z, start[0])
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B,R", XG.FORMS)
+def test_swapping_call_in_place_four_bytes_off_null_optionals_and_reused_buffers(lsnf, gpu_device, nz, w, depth, coupling, B, R):
+    XG.check_swap_forms(lsnf, SP, TR.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B), R)
 
 
 def test_sampler_is_the_hand_written_loop(lsnf, gpu_device, monkeypatch):
