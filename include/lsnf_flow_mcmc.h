@@ -314,7 +314,53 @@
  *     an idle rung.  accept_out and log_alpha_out stay the trajectory's own.
  * Kernels: lsnf_small3_hmcx_kernel / lsnf_small3_rhmcx_kernel, the tempered kernels' stages, instantiations and workgroup shapes.  A
  * ladder lies inside one wave's 16-row tile, the partner's state comes over lane to lane, and every lane writes its own row only: no
- * row reads what another row writes in the same launch.  B = 0 succeeds without a launch. */
+ * row reads what another row writes in the same launch.  B = 0 succeeds without a launch.
+ *
+ * ---- Resampling between the rows of a group on an annealing end call: a sequential Monte Carlo sampler (lsnf_hmc_step_resample, ------
+ * ---- lsnf_reverse_hmc_step_resample) -----------------------------------------------------------------------------------------------------
+ * The two entry points are the tempered calls with `int group, float ess_frac, const float* resample_uniform, float* ancestor_out,
+ * float* ess_out` inserted between log_alpha_out and stream, and one more flag (LSNF_HMC_SWAP is not among theirs).  Without
+ * LSNF_HMC_RESAMPLE every output has the tempered call's bits in every phase and the three pointers must be NULL (group and ess_frac
+ * are not looked at).
+ *   group: P in {2, 4, 8, 16}, B % P == 0.  Rows [k P, (k + 1) P) are the particles of group k, rung r = row % P.
+ *   ess_frac: the group resamples iff its effective sample size is below ess_frac * P.  <= 0: never; > 1: always.
+ *   flags: the tempered call's; LSNF_HMC_RESAMPLE only on an end call (neither LSNF_HMC_INIT nor LSNF_HMC_INNER) WITH LSNF_HMC_ANNEAL
+ *       and without LSNF_HMC_ADAPT, LSNF_HMC_METRIC_FOLD and LSNF_HMC_METRIC_CLOSE: the chain is frozen.
+ *   resample_uniform (B): the group's ONE uniform u, in [0, 1), is resample_uniform[first row of the group].  It goes with the tensor
+ *       form of the noise and is then required; with an rng it must be NULL and the number is word 0 of Philox at the call's (seed,
+ *       offset), at the global row of the group's first row, at counter field value 4 (the noise draws use 0 and 1, the trajectory's
+ *       uniform 2, the swap's 3), formed as those uniforms are: a pure function of (seed, offset, that global row), so a group
+ *       resamples alike however the batch is sharded along whole groups.
+ *   ancestor_out, ess_out (B): optional outputs; they may alias nothing else the call touches.
+ * The move comes after the trajectory's decision, the state update and the ANNEAL lines above, and before the next trajectory begins.
+ * With {w_i, c_i} row i's Kahan pair after the increment, beta'_i = beta_next[i], and (z_s, g_s', u_s', gl_s, el_s) row i's state after
+ * the decision with g_s' and u_s' re-tempered to beta'_i by the ANNEAL lines; i, j run over the group's rungs 0 .. P - 1.  Every line
+ * is one fp32 operation, rounded once:
+ *         l_i = w_i - c_i
+ *         m = max_i l_i                                          (fmaxf, in rung order: a NaN is passed over)
+ *         e_i = expf(l_i - m)
+ *         S1 = ((e_0 + e_1) + ..) + e_{P-1};   q_i = e_i * e_i;   S2 = ((q_0 + q_1) + ..) + q_{P-1}       (from 0.0f, in rung order)
+ *         ess = (S1 * S1) / S2
+ *         the group resamples iff ess < ess_frac * P             (a NaN anywhere makes this false: the group is left alone)
+ *     Systematic resampling of a group that resamples, for rung k (P as a float is a power of two, so / P is exact):
+ *         tau_k = (((float)k + u) / P) * S1
+ *         cum_j = ((e_0 + e_1) + ..) + e_j                       (S1's partial sums)
+ *         a_k = min(#{ j : cum_j <= tau_k }, P - 1)              (the clamp matters only where tau_k reaches S1: u = 1.0f, which the
+ *                                                                 in-kernel number's last rounding can give, or a rounding of tau_k)
+ *         log_w[k] <- { m + logf(S1 / P), 0.0f }                 (every row of the group; S1 / P first)
+ *     A row with a_k != k takes its ancestor's state (a = a_k, d_own = beta'_k - beta'_a) over what the update stored:
+ *         z_acc <- z_s_a;   like_grad_acc <- gl_s_a;   like_u_acc <- el_s_a
+ *         grad_acc <- g_s'_a + (d_own * gl_s_a)   per column;     u_acc <- u_s'_a + (d_own * el_s_a)
+ *     and the trajectory this call begins (if a next point is asked for) starts from that state with the row's own step, scale and xi.
+ *     beta_rows, step_rows, scale_rows and everything of the adaptation stay with the row.  Rows with a_k == k keep the tempered
+ *     call's bits but for log_w; a group that does not resample keeps them everywhere.
+ *         ancestor_out[b] = (float)a_k in a group that resamples, else (float)k;   ess_out[b] = ess on every row of the group.
+ *     accept_out and log_alpha_out stay the trajectory's own.  The mean of exp(log_w) over a group is unchanged by the move up to
+ *     rounding, so logsumexp over the rows minus log(rows) remains the unbiased estimate of the normalising constant.
+ * Kernels: lsnf_small3_hmcs_kernel / lsnf_small3_rhmcs_kernel, the tempered kernels' stages, instantiations and workgroup shapes.  A
+ * group lies inside one wave's 16-row tile, every lane of every wave forms the sums from the same values in the same order, the
+ * ancestor's state comes over lane to lane, and every lane writes its own row only: no row reads what another row writes in the same
+ * launch.  B = 0 succeeds without a launch. */
 #ifndef LSNF_FLOW_MCMC_H
 #define LSNF_FLOW_MCMC_H
 
@@ -436,6 +482,30 @@ int lsnf_reverse_hmc_step_exchange(const float* plan, int nz, int width, int dep
                                    float* beta_rows, const float* beta_next, float* like_grad_acc, float* like_u_acc, float* log_w,
                                    unsigned flags, float* eps_next, float* accept_out, float* log_alpha_out,
                                    int ladder, const float* swap_uniform, float* swap_out, float* log_swap_out, void* stream);
+
+/* resampling between the rows of a group (sequential Monte Carlo) */
+#define LSNF_HMC_RESAMPLE 512u   /* annealing end calls: resample the group's states when its effective sample size is low */
+int lsnf_hmc_step_resample(const float* plan, int nz, int width, int depth, int coupling, int B,
+                           const float* z_prop, const float* z_out, const float* z_saved, const float* act_saved,
+                           const float* ll_prop, const float* grad_g, const float* energy_g,
+                           float* z_acc, float* grad_acc, float* u_acc, float* mom, float* kin0,
+                           const float* noise, const float* uniform, const LsnfRng* rng,
+                           float* step_rows, float* adapt, const LsnfDualAvg* da,
+                           float* scale_rows, float* mean_rows, float* m2_rows, float* count_rows, const LsnfMetricReg* reg,
+                           float* beta_rows, const float* beta_next, float* like_grad_acc, float* like_u_acc, float* log_w, unsigned flags,
+                           float* z_next, float* accept_out, float* log_alpha_out,
+                           int group, float ess_frac, const float* resample_uniform, float* ancestor_out, float* ess_out, void* stream);
+int lsnf_reverse_hmc_step_resample(const float* plan, int nz, int width, int depth, int coupling, int B,
+                                   const float* eps_prop, const float* z_saved, const float* act_saved,
+                                   const float* grad_g, const float* energy_g,
+                                   float* eps_acc, float* grad_acc, float* u_acc, float* mom, float* kin0,
+                                   const float* noise, const float* uniform, const LsnfRng* rng,
+                                   float* step_rows, float* adapt, const LsnfDualAvg* da,
+                                   float* scale_rows, float* mean_rows, float* m2_rows, float* count_rows, const LsnfMetricReg* reg,
+                                   float* beta_rows, const float* beta_next, float* like_grad_acc, float* like_u_acc, float* log_w,
+                                   unsigned flags, float* eps_next, float* accept_out, float* log_alpha_out,
+                                   int group, float ess_frac, const float* resample_uniform, float* ancestor_out, float* ess_out,
+                                   void* stream);
 
 #ifdef __cplusplus
 }

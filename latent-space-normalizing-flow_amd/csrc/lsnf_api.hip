@@ -342,6 +342,32 @@ struct RowExchange {
     }
 };
 
+// The rules a resampling move adds (lsnf_hmc_step_resample, lsnf_reverse_hmc_step_resample), stated once, beside RowTemper's and
+// applied after them: scalars() before the empty-batch return, pointers() with the pointers of a non-empty call.  resample_uniform is
+// among the entry point's `reads`, ancestor_out and ess_out among its `writes`.  (LSNF_HMC_SWAP is not among these entries' flags.)
+struct RowResample {
+    int group; int B; const float* resample_uniform; const float* ancestor_out; const float* ess_out; const LsnfRng* rng; unsigned flags;
+    bool resampling() const { return (flags & LSNF_HMC_RESAMPLE) != 0; }
+    bool scalars(Check& ck) const {
+        return ck.refuse(resampling() && (flags & (LSNF_HMC_INIT | LSNF_HMC_INNER)),
+                         "flags: LSNF_HMC_RESAMPLE goes with an end call (neither LSNF_HMC_INIT nor LSNF_HMC_INNER)") ||
+               ck.refuse(resampling() && !(flags & LSNF_HMC_ANNEAL), "flags: LSNF_HMC_RESAMPLE goes with LSNF_HMC_ANNEAL") ||
+               ck.refuse(resampling() && (flags & (LSNF_HMC_ADAPT | LSNF_HMC_METRIC_FOLD | LSNF_HMC_METRIC_CLOSE)),
+                         "flags: LSNF_HMC_RESAMPLE excludes LSNF_HMC_ADAPT, LSNF_HMC_METRIC_FOLD and LSNF_HMC_METRIC_CLOSE") ||
+               ck.refuse(resampling() && !(group == 2 || group == 4 || group == 8 || group == 16),
+                         "group must be 2, 4, 8 or 16 with LSNF_HMC_RESAMPLE (got %d)", group) ||
+               ck.refuse(resampling() && B % group != 0, "B=%d is not a multiple of group=%d", B, group) ||
+               ck.refuse(!resampling() && (resample_uniform || ancestor_out || ess_out),
+                         "resample_uniform, ancestor_out and ess_out must be NULL without LSNF_HMC_RESAMPLE") ||
+               ck.refuse(resample_uniform && rng,
+                         "resample_uniform goes with a noise tensor, not with an rng (the group's uniform is drawn in-kernel)");
+    }
+    bool pointers(Check& ck) const {
+        return ck.refuse(resampling() && !rng && !resample_uniform,
+                         "resample_uniform is required with LSNF_HMC_RESAMPLE when no rng is given");
+    }
+};
+
 // ---- kernel selection: each operation decides on the host, from the kernels' coverage predicates, which kernel(s) a call
 // runs, BEFORE anything is launched; the entry point then launches exactly that.  A launcher reached outside what it covers
 // is a selection bug and fails the call (LSNF_E_HIP, the kernel named in lsnf_last_error()); nothing falls through to another
@@ -352,6 +378,7 @@ enum Kernel {
     K_BWD, K_BWD3, K_SMALL_BWD, K_SMALL3_BWD,
     K_SMALL3_RBWD, K_SMALL3_RLV, K_SMALL3_MALA, K_SMALL3_RMALA, K_SMALL3_HMC, K_SMALL3_RHMC,
     K_SMALL3_HMCR, K_SMALL3_RHMCR, K_SMALL3_HMCM, K_SMALL3_RHMCM, K_SMALL3_HMCT, K_SMALL3_RHMCT, K_SMALL3_HMCX, K_SMALL3_RHMCX,
+    K_SMALL3_HMCS, K_SMALL3_RHMCS,
 };
 const char* const kKernelName[] = {
     "no kernel takes this call", "lsnf_fwd_kernel", "lsnf_fwd3b_kernel", "lsnf_fwd3q_kernel",
@@ -363,6 +390,7 @@ const char* const kKernelName[] = {
     "lsnf_small3_hmc_kernel", "lsnf_small3_rhmc_kernel",
     "lsnf_small3_hmcr_kernel", "lsnf_small3_rhmcr_kernel", "lsnf_small3_hmcm_kernel", "lsnf_small3_rhmcm_kernel",
     "lsnf_small3_hmct_kernel", "lsnf_small3_rhmct_kernel", "lsnf_small3_hmcx_kernel", "lsnf_small3_rhmcx_kernel",
+    "lsnf_small3_hmcs_kernel", "lsnf_small3_rhmcs_kernel",
 };
 struct Pick { Kernel k; int st = 0; };     // st: rows per workgroup / 16 of the small3 kernels
 
@@ -581,6 +609,10 @@ Pick select_reverse_hmc_tempered(const LsnfReverseHmcTemperedCall& c) { return {
 // lsnf_small3_rhmcx.hip, likewise.
 Pick select_hmc_exchange(const LsnfHmcExchangeCall& c) { return {K_SMALL3_HMCX, lsnf_small3_backward_st(c)}; }
 Pick select_reverse_hmc_exchange(const LsnfReverseHmcExchangeCall& c) { return {K_SMALL3_RHMCX, lsnf_small3_reverse_backward_st(c)}; }
+// The two with a resampling move (lsnf_hmc_step_resample, lsnf_reverse_hmc_step_resample): lsnf_small3_hmcs.hip,
+// lsnf_small3_rhmcs.hip, likewise.
+Pick select_hmc_resample(const LsnfHmcResampleCall& c) { return {K_SMALL3_HMCS, lsnf_small3_backward_st(c)}; }
+Pick select_reverse_hmc_resample(const LsnfReverseHmcResampleCall& c) { return {K_SMALL3_RHMCS, lsnf_small3_reverse_backward_st(c)}; }
 
 // Batch contraction of the parameter gradients (LsnfContraction): on the bf16 matrix pipe where lsnf_params3.hip covers the
 // call (use_x3); from 4 096 rows the fp32-MFMA kernel through LDS, with the widest row loads the rows allow -- every row the
@@ -1432,6 +1464,109 @@ int lsnf_reverse_hmc_step_exchange(const float* plan, int nz, int width, int dep
     c.ladder = ladder; c.swap_uniform = swap_uniform; c.swap_out = swap_out; c.log_swap_out = log_swap_out;
     const Pick p = select_reverse_hmc_exchange(c);
     return report(ck.entry, p, lsnf_launch_small3_reverse_hmc_exchange(c, p.st));
+}
+
+// The two HMC entries with a resampling move: the tempered entries' tables and rules, resample_uniform among the reads, ancestor_out
+// and ess_out among the outputs, RowResample's rules after RowTemper's.
+int lsnf_hmc_step_resample(const float* plan, int nz, int width, int depth, int coupling, int B, const float* z_prop, const float* z_out,
+                           const float* z_saved, const float* act_saved, const float* ll_prop, const float* grad_g, const float* energy_g,
+                           float* z_acc, float* grad_acc, float* u_acc, float* mom, float* kin0, const float* noise, const float* uniform,
+                           const LsnfRng* rng, float* step_rows, float* adapt, const LsnfDualAvg* da, float* scale_rows, float* mean_rows,
+                           float* m2_rows, float* count_rows, const LsnfMetricReg* reg, float* beta_rows, const float* beta_next,
+                           float* like_grad_acc, float* like_u_acc, float* log_w, unsigned flags, float* z_next, float* accept_out,
+                           float* log_alpha_out, int group, float ess_frac, const float* resample_uniform, float* ancestor_out,
+                           float* ess_out, void* stream) {
+    Check ck{"lsnf_hmc_step_resample"};
+    const Named reads[] = {{"plan", plan}, {"z_prop", z_prop}, {"z_out", z_out}, {"z_saved", z_saved}, {"act_saved", act_saved},
+                           {"ll_prop", ll_prop}, {"grad_g", grad_g}, {"energy_g", energy_g}, {"noise", noise}, {"uniform", uniform},
+                           {"resample_uniform", resample_uniform}};
+    const Named writes[] = {{"z_acc", z_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc}, {"z_next", z_next}, {"accept_out", accept_out},
+                            {"log_alpha_out", log_alpha_out}, {"mom", mom}, {"kin0", kin0}, {"step_rows", step_rows}, {"adapt", adapt},
+                            {"scale_rows", scale_rows}, {"mean_rows", mean_rows}, {"m2_rows", m2_rows}, {"count_rows", count_rows},
+                            {"beta_rows", beta_rows}, {"beta_next", beta_next}, {"like_grad_acc", like_grad_acc},
+                            {"like_u_acc", like_u_acc}, {"log_w", log_w}, {"ancestor_out", ancestor_out}, {"ess_out", ess_out}};
+    const bool init = (flags & LSNF_HMC_INIT) != 0, inner = (flags & LSNF_HMC_INNER) != 0;
+    const Needed needed[] = {{"plan", plan}, {"z_prop", z_prop}, {"z_out", z_out}, {"act_saved", act_saved}, {"z_acc", z_acc},
+                             {"grad_acc", grad_acc}, {"u_acc", u_acc}, {"mom", mom}, {"kin0", kin0}, {"step_rows", step_rows},
+                             {"scale_rows", scale_rows}, {"beta_rows", beta_rows}, {"like_grad_acc", like_grad_acc},
+                             {"like_u_acc", like_u_acc},
+                             {"ll_prop", ll_prop, !inner, "(NULL) unless LSNF_HMC_INNER"}, {"z_saved", z_saved, depth > 1, "(NULL) for depth > 1"},
+                             {"z_next", z_next, inner, "(NULL) with LSNF_HMC_INNER"}};
+    const ChainStep s = {reads, writes, /*next=*/&writes[3], /*point=*/&reads[1], needed,
+                         LSNF_HMC_INIT | LSNF_HMC_INNER | LSNF_HMC_ADAPT | LSNF_HMC_ADAPT_LAST | LSNF_HMC_METRIC_FOLD | LSNF_HMC_METRIC_CLOSE |
+                             LSNF_HMC_ANNEAL | LSNF_HMC_RESAMPLE,
+                         init, inner, "LSNF_HMC_INIT or LSNF_HMC_INNER", plan, act_saved, noise, uniform, rng, /*step_size=*/1.0f, flags};
+    const RowSteps rows = {step_rows, adapt, da, flags};
+    const RowMetric metric = {mean_rows, m2_rows, count_rows, reg, flags};
+    const RowTemper temper = {beta_next, log_w, flags};
+    const RowResample resample = {group, B, resample_uniform, ancestor_out, ess_out, rng, flags};
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B) || s.scalars(ck) || s.phases(ck, accept_out, log_alpha_out) || rows.scalars(ck) ||
+        metric.scalars(ck) || temper.scalars(ck) || resample.scalars(ck) || s.aliases(ck))
+        return ck.rc;
+    if (ck.empty) return LSNF_OK;
+    if (s.pointers(ck) || rows.pointers(ck) || metric.pointers(ck) || temper.pointers(ck) || resample.pointers(ck))
+        return ck.rc;
+    const LsnfLangevinArgs lv = {z_prop, grad_g, noise, z_next, nullptr, nullptr, 0.0f, rng_args(rng)};
+    LsnfHmcResampleCall c;               // (no g_z1 / g_logdet / g_z_in: the gradient of -log p at the point, consumed by the tail)
+    ck.head(c, plan, B, stream, {z_prop, z_out, z_saved, grad_g, noise, z_next, z_acc, grad_acc, mom, scale_rows, mean_rows, m2_rows, like_grad_acc});
+    c.z_out = z_out; c.z_saved = z_saved; c.act_saved = act_saved; c.ll_mode = 1; c.ll_scale = -1.0f; c.lv = &lv; c.ll_prop = ll_prop;
+    c.chain = {energy_g, uniform, z_acc, grad_acc, u_acc, accept_out, log_alpha_out, flags}; c.mom = mom; c.kin0 = kin0;
+    c.step_rows = step_rows; c.adapt = adapt; c.da = rows.args();
+    c.scale = scale_rows; c.mean = mean_rows; c.m2 = m2_rows; c.count = count_rows; c.reg = metric.args();
+    c.beta_rows = beta_rows; c.beta_next = beta_next; c.like_grad_acc = like_grad_acc; c.like_u_acc = like_u_acc; c.log_w = log_w;
+    c.group = group; c.ess_frac = ess_frac; c.resample_uniform = resample_uniform; c.ancestor_out = ancestor_out; c.ess_out = ess_out;
+    const Pick p = select_hmc_resample(c);
+    return report(ck.entry, p, lsnf_launch_small3_hmc_resample(c, p.st));
+}
+
+int lsnf_reverse_hmc_step_resample(const float* plan, int nz, int width, int depth, int coupling, int B, const float* eps_prop,
+                                   const float* z_saved, const float* act_saved, const float* grad_g, const float* energy_g, float* eps_acc,
+                                   float* grad_acc, float* u_acc, float* mom, float* kin0, const float* noise, const float* uniform,
+                                   const LsnfRng* rng, float* step_rows, float* adapt, const LsnfDualAvg* da, float* scale_rows,
+                                   float* mean_rows, float* m2_rows, float* count_rows, const LsnfMetricReg* reg, float* beta_rows,
+                                   const float* beta_next, float* like_grad_acc, float* like_u_acc, float* log_w, unsigned flags,
+                                   float* eps_next, float* accept_out, float* log_alpha_out, int group, float ess_frac,
+                                   const float* resample_uniform, float* ancestor_out, float* ess_out, void* stream) {
+    Check ck{"lsnf_reverse_hmc_step_resample"};
+    const Named reads[] = {{"plan", plan}, {"eps_prop", eps_prop}, {"z_saved", z_saved}, {"act_saved", act_saved}, {"grad_g", grad_g},
+                           {"energy_g", energy_g}, {"noise", noise}, {"uniform", uniform},
+                           {"resample_uniform", resample_uniform}};
+    const Named writes[] = {{"eps_acc", eps_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc}, {"eps_next", eps_next}, {"accept_out", accept_out},
+                            {"log_alpha_out", log_alpha_out}, {"mom", mom}, {"kin0", kin0}, {"step_rows", step_rows}, {"adapt", adapt},
+                            {"scale_rows", scale_rows}, {"mean_rows", mean_rows}, {"m2_rows", m2_rows}, {"count_rows", count_rows},
+                            {"beta_rows", beta_rows}, {"beta_next", beta_next}, {"like_grad_acc", like_grad_acc},
+                            {"like_u_acc", like_u_acc}, {"log_w", log_w}, {"ancestor_out", ancestor_out}, {"ess_out", ess_out}};
+    const bool init = (flags & LSNF_HMC_INIT) != 0, inner = (flags & LSNF_HMC_INNER) != 0;
+    const Needed needed[] = {{"plan", plan}, {"eps_prop", eps_prop}, {"eps_acc", eps_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc},
+                             {"mom", mom}, {"kin0", kin0}, {"step_rows", step_rows}, {"scale_rows", scale_rows}, {"beta_rows", beta_rows},
+                             {"like_grad_acc", like_grad_acc}, {"like_u_acc", like_u_acc},
+                             {"act_saved", act_saved, true, "(the stash of lsnf_forward, lsnf_restash or lsnf_reverse_keep)"},
+                             {"z_saved", z_saved, depth > 1, "(NULL) for depth > 1"}, {"eps_next", eps_next, inner, "(NULL) with LSNF_HMC_INNER"}};
+    const ChainStep s = {reads, writes, /*next=*/&writes[3], /*point=*/&reads[1], needed,
+                         LSNF_HMC_INIT | LSNF_HMC_INNER | LSNF_HMC_ADAPT | LSNF_HMC_ADAPT_LAST | LSNF_HMC_METRIC_FOLD | LSNF_HMC_METRIC_CLOSE |
+                             LSNF_HMC_ANNEAL | LSNF_HMC_RESAMPLE,
+                         init, inner, "LSNF_HMC_INIT or LSNF_HMC_INNER", plan, act_saved, noise, uniform, rng, /*step_size=*/1.0f, flags};
+    const RowSteps rows = {step_rows, adapt, da, flags};
+    const RowMetric metric = {mean_rows, m2_rows, count_rows, reg, flags};
+    const RowTemper temper = {beta_next, log_w, flags};
+    const RowResample resample = {group, B, resample_uniform, ancestor_out, ess_out, rng, flags};
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B) || s.scalars(ck) || s.phases(ck, accept_out, log_alpha_out) || rows.scalars(ck) ||
+        metric.scalars(ck) || temper.scalars(ck) || resample.scalars(ck) || s.aliases(ck))
+        return ck.rc;
+    if (ck.empty) return LSNF_OK;
+    if (s.pointers(ck) || rows.pointers(ck) || metric.pointers(ck) || temper.pointers(ck) || resample.pointers(ck))
+        return ck.rc;
+    LsnfReverseHmcResampleCall c;        // (no g_x / g_objective / g_z_in: the gradient at the point is consumed by the tail)
+    ck.head(c, plan, B, stream, {eps_prop, z_saved, grad_g, noise, eps_next, eps_acc, grad_acc, mom, scale_rows, mean_rows, m2_rows, like_grad_acc});
+    c.z_out = eps_prop; c.z_saved = z_saved; c.act_saved = act_saved;
+    c.grad_g = grad_g; c.noise = noise; c.step = 0.0f; c.eps_new = eps_next; c.rng = rng_args(rng);
+    c.chain = {energy_g, uniform, eps_acc, grad_acc, u_acc, accept_out, log_alpha_out, flags}; c.mom = mom; c.kin0 = kin0;
+    c.step_rows = step_rows; c.adapt = adapt; c.da = rows.args();
+    c.scale = scale_rows; c.mean = mean_rows; c.m2 = m2_rows; c.count = count_rows; c.reg = metric.args();
+    c.beta_rows = beta_rows; c.beta_next = beta_next; c.like_grad_acc = like_grad_acc; c.like_u_acc = like_u_acc; c.log_w = log_w;
+    c.group = group; c.ess_frac = ess_frac; c.resample_uniform = resample_uniform; c.ancestor_out = ancestor_out; c.ess_out = ess_out;
+    const Pick p = select_reverse_hmc_resample(c);
+    return report(ck.entry, p, lsnf_launch_small3_reverse_hmc_resample(c, p.st));
 }
 
 size_t lsnf_backward_params_workspace_floats(int nz, int width, int depth, int B) {

@@ -79,6 +79,12 @@ struct LsnfHmcExchangeCall : LsnfHmcTemperedCall {      // lsnf_hmc_step_exchang
     const float* swap_uniform = nullptr; // the pairs' uniforms (B), read at the lower row; NULL: drawn in-kernel
     float* swap_out = nullptr; float* log_swap_out = nullptr;      // optional (B each)
 };
+struct LsnfHmcResampleCall : LsnfHmcTemperedCall {      // lsnf_hmc_step_resample; flags: LsnfHmcTemperedCall's with RESAMPLE
+    int group = 0;                       // P consecutive rows aligned to P are the particles of one group (2, 4, 8 or 16): RESAMPLE only
+    float ess_frac = 0.0f;               // a group resamples iff its effective sample size is below ess_frac * P
+    const float* resample_uniform = nullptr;   // the groups' uniforms (B), read at the group's first row; NULL: drawn in-kernel
+    float* ancestor_out = nullptr; float* ess_out = nullptr;       // optional (B each)
+};
 struct LsnfReverseBackwardCall : LsnfCall {      // lsnf_reverse_backward_z
     const float* z_out = nullptr; const float* z_saved = nullptr; const float* act_saved = nullptr;
     const float* g_x = nullptr; const float* g_objective = nullptr;
@@ -110,6 +116,9 @@ struct LsnfReverseHmcTemperedCall : LsnfReverseHmcMetricCall {      // lsnf_reve
 };
 struct LsnfReverseHmcExchangeCall : LsnfReverseHmcTemperedCall {      // lsnf_reverse_hmc_step_exchange: as LsnfHmcExchangeCall
     int ladder = 0; const float* swap_uniform = nullptr; float* swap_out = nullptr; float* log_swap_out = nullptr;
+};
+struct LsnfReverseHmcResampleCall : LsnfReverseHmcTemperedCall {      // lsnf_reverse_hmc_step_resample: as LsnfHmcResampleCall
+    int group = 0; float ess_frac = 0.0f; const float* resample_uniform = nullptr; float* ancestor_out = nullptr; float* ess_out = nullptr;
 };
 struct LsnfContractCall : LsnfCall {     // steps (2), (3) of lsnf_backward_params: batch contraction of the dump, chain rule
     const float* const* params_host = nullptr; float* const* grads_host = nullptr;
@@ -186,6 +195,7 @@ hipError_t lsnf_launch_small3_hmc_rows(const LsnfHmcRowsCall& c, int st);   // s
 hipError_t lsnf_launch_small3_hmc_metric(const LsnfHmcMetricCall& c, int st);       // st: lsnf_small3_backward_st of the call
 hipError_t lsnf_launch_small3_hmc_tempered(const LsnfHmcTemperedCall& c, int st);   // st: lsnf_small3_backward_st of the call
 hipError_t lsnf_launch_small3_hmc_exchange(const LsnfHmcExchangeCall& c, int st);   // st: lsnf_small3_backward_st of the call
+hipError_t lsnf_launch_small3_hmc_resample(const LsnfHmcResampleCall& c, int st);   // st: lsnf_small3_backward_st of the call
 int lsnf_small3_reverse_backward_st(const LsnfReverseBackwardCall& c);
 hipError_t lsnf_launch_small3_reverse_backward_z(const LsnfReverseBackwardCall& c, int st);
 hipError_t lsnf_launch_small3_reverse_langevin(const LsnfReverseLangevinCall& c, int st);      // st: of the same predicate
@@ -195,6 +205,7 @@ hipError_t lsnf_launch_small3_reverse_hmc_rows(const LsnfReverseHmcRowsCall& c, 
 hipError_t lsnf_launch_small3_reverse_hmc_metric(const LsnfReverseHmcMetricCall& c, int st);   // st: of the same predicate
 hipError_t lsnf_launch_small3_reverse_hmc_tempered(const LsnfReverseHmcTemperedCall& c, int st);   // st: of the same predicate
 hipError_t lsnf_launch_small3_reverse_hmc_exchange(const LsnfReverseHmcExchangeCall& c, int st);   // st: of the same predicate
+hipError_t lsnf_launch_small3_reverse_hmc_resample(const LsnfReverseHmcResampleCall& c, int st);   // st: of the same predicate
 
 bool lsnf_contract_x3_covers(const LsnfContractCall& c);                   // (also asked with NULL tensors: lsnf_api.hip dump_may_tile)
 hipError_t lsnf_launch_contract_x3(const LsnfContractCall& c, int chunk_override);

@@ -9,7 +9,8 @@
 // (lsnf_small3_hmcr_kernel, Small3HmcRowsArgs, the per-row leapfrog tail and `return;`), lsnf_small3_hmcm.hip a fifth
 // (lsnf_small3_hmcm_kernel, Small3HmcMetricArgs, the per-row leapfrog tail with a diagonal metric and `return;`), lsnf_small3_hmct.hip a
 // sixth (lsnf_small3_hmct_kernel, Small3HmcTemperedArgs, that tail with a likelihood temperature per row and `return;`),
-// lsnf_small3_hmcx.hip a seventh (lsnf_small3_hmcx_kernel, Small3HmcExchangeArgs, that tail with a replica-exchange move and `return;`).
+// lsnf_small3_hmcx.hip a seventh (lsnf_small3_hmcx_kernel, Small3HmcExchangeArgs, that tail with a replica-exchange move and `return;`),
+// lsnf_small3_hmcs.hip an eighth (lsnf_small3_hmcs_kernel, Small3HmcResampleArgs, that tail with a resampling move and `return;`).
 #pragma once
 
 namespace {
@@ -83,6 +84,12 @@ struct Small3HmcTemperedArgs : Small3HmcMetricArgs {
 // pairs' uniforms (B, read at the lower row; NULL: drawn in-kernel) and the two optional outputs of the move (B each)
 struct Small3HmcExchangeArgs : Small3HmcTemperedArgs {
     int ladder; const float* swap_uniform; float* swap_out; float* log_swap_out;
+};
+// resampling HMC form (lsnf_small3_hmcs.hip): the tempered form's arrays and, with LSNF_HMC_RESAMPLE (512), the group's length, the
+// threshold as a fraction of it, the groups' uniforms (B, read at the group's first row; NULL: drawn in-kernel) and the two optional
+// outputs of the move (B each)
+struct Small3HmcResampleArgs : Small3HmcTemperedArgs {
+    int group; float ess_frac; const float* resample_uniform; float* ancestor_out; float* ess_out;
 };
 
 __device__ __forceinline__ f32x4 mask4(f32x4 a, unsigned nib) {

@@ -11,7 +11,8 @@
 // front of their own barrier); lsnf_small3_rhmcr.hip is the third column with a step per row (lsnf_small3_rhmcr_kernel, Small3RhmcRowsArgs),
 // lsnf_small3_rhmcm.hip that one with a diagonal metric per row (lsnf_small3_rhmcm_kernel, Small3RhmcMetricArgs), lsnf_small3_rhmct.hip
 // that one with a likelihood temperature per row (lsnf_small3_rhmct_kernel, Small3RhmcTemperedArgs), lsnf_small3_rhmcx.hip that one
-// with a replica-exchange move between rows (lsnf_small3_rhmcx_kernel, Small3RhmcExchangeArgs).
+// with a replica-exchange move between rows (lsnf_small3_rhmcx_kernel, Small3RhmcExchangeArgs), lsnf_small3_rhmcs.hip the tempered one
+// with a resampling move between rows (lsnf_small3_rhmcs_kernel, Small3RhmcResampleArgs).
 #pragma once
 
 namespace {
@@ -87,6 +88,12 @@ struct Small3RhmcTemperedArgs : Small3RhmcMetricArgs {
 // (128), the ladder's length, the pairs' uniforms (B, read at the lower row; NULL: drawn in-kernel) and the move's two optional outputs
 struct Small3RhmcExchangeArgs : Small3RhmcTemperedArgs {
     int ladder; const float* swap_uniform; float* swap_out; float* log_swap_out;
+};
+// resampling HMC form (lsnf_reverse_hmc_step_resample, lsnf_small3_rhmcs.hip): the tempered form's tensors and, with LSNF_HMC_RESAMPLE
+// (512), the group's length, the threshold as a fraction of it, the groups' uniforms (B, read at the group's first row; NULL: drawn
+// in-kernel) and the move's two optional outputs
+struct Small3RhmcResampleArgs : Small3RhmcTemperedArgs {
+    int group; float ess_frac; const float* resample_uniform; float* ancestor_out; float* ess_out;
 };
 
 __device__ __forceinline__ f32x4 rb_mask4(f32x4 a, unsigned nib) {

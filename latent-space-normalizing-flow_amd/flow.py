@@ -891,3 +891,4 @@ from .mcmc import (HMC_METRIC_CLOSE, HMC_METRIC_FOLD, HmcRowMetric, new_hmc_row_
                    reverse_hmc_step_metric)
 from .mcmc import HMC_ANNEAL, HmcRowTemper, new_hmc_row_temper, hmc_step_tempered, reverse_hmc_step_tempered  # noqa: E402,F401
 from .mcmc import HMC_SWAP, HMC_SWAP_ODD, hmc_step_exchange, reverse_hmc_step_exchange  # noqa: E402,F401
+from .mcmc import HMC_RESAMPLE, hmc_step_resample, reverse_hmc_step_resample  # noqa: E402,F401

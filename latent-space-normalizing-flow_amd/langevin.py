@@ -696,6 +696,139 @@ estimate_log_px_ais_z_with_flow.__doc__ += _AIS_DOC
 estimate_log_px_ais_eps_with_flow.__doc__ += _AIS_DOC
 
 
+def _smc_plan(flow, betas, chains, particles, leapfrog_steps, steps, metric):
+    """`_ais_plan`'s checks and the groups' geometry: particles is 2, 4, 8 or 16 and divides chains."""
+    betas, T, C, L = _ais_plan(flow, betas, chains, leapfrog_steps, steps, metric, False)
+    P = int(particles)
+    if P not in (2, 4, 8, 16) or C % P:
+        raise ValueError(f"particles must be 2, 4, 8 or 16 and divide chains={C} (got {particles})")
+    return betas, T, C, L, P
+
+
+_SMC_DOC = """
+    The loop, the draws and the Philox offsets are `estimate_log_px_ais_*_with_flow`'s (which see for betas, steps, metric and the
+    reduction); every launch is the resampling call, and the end call of every t < T carries resample=particles: after its weight
+    increment and before trajectory t + 1 begins, each group of `particles` consecutive chains of a datum whose effective sample size
+    is below ess_threshold * particles is resampled systematically inside the kernel (one uniform per group, Philox field 4 of the
+    group's first row) and its rows continue from the group's mean weight.  More chains than particles are independent islands;
+    since resampling keeps a group's mean weight, logsumexp_c(log_w) - log(chains) is still the unbiased estimate.  The init call
+    weighs the prior's draws and does not resample.  The chain is frozen: there is no adapt=.
+    Returns the AIS tuple plus `resampled`, (N, chains / particles) float32: at how many of the T - 1 resampling end calls each group
+    resampled -- accumulated on the device from the calls' ess output, without a host synchronisation inside the loop."""
+
+
+def estimate_log_px_smc_z_with_flow(x, netG: nn.Module, netF, *, betas, chains: int, particles: int, leapfrog_steps: int,
+                                    g_l_step_size, g_llhd_sigma: float, philox, ess_threshold: float = 0.5, steps=None, metric=None):
+    """log p(x) of the latent-variable model p_flow(z) N(x; G(z), sigma^2 I) by a sequential Monte Carlo sampler (Del Moral, Doucet &
+    Jasra 2006) with HMC transitions in z: annealed importance sampling whose particles are resampled when their weights degenerate,
+    every transition two launches of the flow (`netF.hmc_step_resample`)."""
+    from . import flow
+    betas, T, C, L, P = _smc_plan(flow, betas, chains, particles, leapfrog_steps, steps, metric)
+    N = x.shape[0]
+    if T < 1:
+        return None, None, None, None, None, None, None
+    if N == 0:
+        e = torch.zeros(0, dtype=torch.float64, device=x.device)
+        return e, e.view(0, C), e.clone(), None, None, None, None
+    B, D, plan = N * C, x[0].numel(), netF._plan()
+    c = 1.0 / (2.0 * g_llhd_sigma * g_llhd_sigma)
+    xs = x.detach().repeat_interleave(C, dim=0)
+    z0 = netF.sample(B, philox.step(0), return_eps=True)[0]
+    nz = z0.shape[1]
+    z_prop = z0.detach().reshape(B, nz).contiguous()
+    dev = z_prop.device
+    sched = betas.to(torch.float32).to(dev)[:, None].expand(T + 1, B).contiguous()
+    steps = _row_steps(flow, steps, B, dev, g_l_step_size, 0.8)
+    metric = flow.new_hmc_row_metric(plan, B, dev) if metric is None else metric
+    temper = flow.new_hmc_row_temper(plan, B, dev, 0.0)
+    state = flow.new_hmc_state(plan, B, dev)
+    accepted = torch.zeros(B, dtype=torch.float32, device=dev)
+    resampled = torch.zeros(N, C // P, dtype=torch.float32, device=dev)
+    edge = torch.tensor(float(ess_threshold), dtype=torch.float32, device=dev) * P
+    for j in range(T * L + 1):
+        zr = z_prop.view(B, nz, 1, 1).detach().requires_grad_(True)
+        energy = c * ((netG(zr) - xs) ** 2).flatten(1).sum(1)                                # train.py:312-313, per row
+        grad_g = torch.autograd.grad(energy.sum(), zr)[0].reshape(B, nz).contiguous()        # train.py:314
+        t, inner = j // L, j % L != 0
+        end = bool(j) and not inner
+        move = end and t < T
+        _, acc, _, _, _, ess = netF.hmc_step_resample(z_prop, grad_g, energy.detach(), state, None if inner else philox.step(t + 1), steps,
+                                                      metric, temper, phase="inner" if inner else "end" if j else "init",
+                                                      propose=j < T * L, inplace=True, reuse_buffers=True,
+                                                      anneal=sched[t + 1] if not inner and t < T else None,
+                                                      resample=P if move else None, ess_threshold=ess_threshold)
+        if end:
+            accepted += acc
+        if move:
+            resampled += (ess.view(N, C // P, P)[:, :, 0] < edge).float()
+    philox.advance(T + 1)
+    log_px, log_w, ess = _ais_reduce(temper, N, C, D, float(g_llhd_sigma))
+    return log_px, log_w, ess, accepted / T, state.z.view(B, nz, 1, 1), temper, resampled
+
+
+def estimate_log_px_smc_eps_with_flow(x, netG: nn.Module, netF, *, betas, chains: int, particles: int, leapfrog_steps: int,
+                                      g_l_step_size, g_llhd_sigma: float, philox, ess_threshold: float = 0.5, steps=None, metric=None):
+    """`estimate_log_px_smc_z_with_flow` with the transitions in the flow's base space (`netF.reverse_hmc_step_resample`): the chain
+    runs on eps with z = f^-1(eps), and the flow's side of a transition is the reverse and ONE more launch.  z_T = f^-1(eps_T)."""
+    from . import flow
+    betas, T, C, L, P = _smc_plan(flow, betas, chains, particles, leapfrog_steps, steps, metric)
+    N = x.shape[0]
+    if T < 1:
+        return None, None, None, None, None, None, None
+    if N == 0:
+        e = torch.zeros(0, dtype=torch.float64, device=x.device)
+        return e, e.view(0, C), e.clone(), None, None, None, None
+    B, D, plan = N * C, x[0].numel(), netF._plan()
+    c = 1.0 / (2.0 * g_llhd_sigma * g_llhd_sigma)
+    xs = x.detach().repeat_interleave(C, dim=0)
+    eps0 = netF.sample(B, philox.step(0), return_eps=True)[1]
+    nz = eps0.shape[1]
+    eps_prop = eps0.detach().reshape(B, nz).contiguous()
+    dev = eps_prop.device
+    sched = betas.to(torch.float32).to(dev)[:, None].expand(T + 1, B).contiguous()
+    steps = _row_steps(flow, steps, B, dev, g_l_step_size, 0.8)
+    metric = flow.new_hmc_row_metric(plan, B, dev) if metric is None else metric
+    temper = flow.new_hmc_row_temper(plan, B, dev, 0.0)
+    keeps = flow.reverse_keep_supported(plan, B)
+    act = flow.new_act_saved(plan, B, dev)
+    state = flow.new_hmc_state(plan, B, dev)
+    accepted = torch.zeros(B, dtype=torch.float32, device=dev)
+    resampled = torch.zeros(N, C // P, dtype=torch.float32, device=dev)
+    edge = torch.tensor(float(ess_threshold), dtype=torch.float32, device=dev) * P
+    with torch.no_grad():
+        for j in range(T * L + 1):
+            if keeps:
+                z, _, saved = flow.reverse(plan, eps_prop, None, save_for_backward=True, act_saved=act)
+            else:
+                z, _ = flow.reverse(plan, eps_prop, None)
+                saved = flow.forward(plan, z, None, want_ll=False, save_for_backward=True, act_saved=act)[3]
+            with torch.enable_grad():
+                zr = z.view(B, nz, 1, 1).requires_grad_(True)
+                energy = c * ((netG(zr) - xs) ** 2).flatten(1).sum(1)                                # train.py:312-313, per row
+                grad_g = torch.autograd.grad(energy.sum(), zr)[0].reshape(B, nz).contiguous()        # train.py:314
+            t, inner = j // L, j % L != 0
+            end = bool(j) and not inner
+            move = end and t < T
+            _, acc, _, _, ess = netF.reverse_hmc_step_resample(eps_prop, saved, act, grad_g, energy.detach(), state,
+                                                               None if inner else philox.step(t + 1), steps, metric, temper,
+                                                               phase="inner" if inner else "end" if j else "init", propose=j < T * L,
+                                                               inplace=True, reuse_buffers=True,
+                                                               anneal=sched[t + 1] if not inner and t < T else None,
+                                                               resample=P if move else None, ess_threshold=ess_threshold)
+            if end:
+                accepted += acc
+            if move:
+                resampled += (ess.view(N, C // P, P)[:, :, 0] < edge).float()
+        z = flow.reverse(plan, state.z, None)[0]
+    philox.advance(T + 1)
+    log_px, log_w, ess = _ais_reduce(temper, N, C, D, float(g_llhd_sigma))
+    return log_px, log_w, ess, accepted / T, z.view(B, nz, 1, 1), temper, resampled
+
+
+estimate_log_px_smc_z_with_flow.__doc__ += _SMC_DOC
+estimate_log_px_smc_eps_with_flow.__doc__ += _SMC_DOC
+
+
 def pt_ladder(R: int, beta_min: float) -> torch.Tensor:
     """The R inverse temperatures of a parallel-tempering ladder, float64, increasing: rung 0 is exactly beta_min, rung R - 1 exactly
     1.0 (the posterior), geometric in between -- beta_r = beta_min^((R - 1 - r) / (R - 1)), the spacing that equalises the swap rates

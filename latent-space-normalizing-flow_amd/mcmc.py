@@ -3,7 +3,7 @@
 `flow.HmcState`, `flow.new_hmc_state`, `flow.hmc_step_rows`, `flow.reverse_hmc_step_rows`, `flow.HmcRowSteps`,
 `flow.new_hmc_row_steps`, `flow.hmc_step_metric`, `flow.reverse_hmc_step_metric`, `flow.HmcRowMetric`, `flow.new_hmc_row_metric`,
 `flow.hmc_step_tempered`, `flow.reverse_hmc_step_tempered`, `flow.HmcRowTemper`, `flow.new_hmc_row_temper`,
-`flow.hmc_step_exchange`, `flow.reverse_hmc_step_exchange`.
+`flow.hmc_step_exchange`, `flow.reverse_hmc_step_exchange`, `flow.hmc_step_resample`, `flow.reverse_hmc_step_resample`.
 Every tensor goes through flow.py's one checking path before anything is launched; like there, all functions raise on CPU tensors:
 there is no CPU path."""
 from __future__ import annotations
@@ -695,3 +695,115 @@ def reverse_hmc_step_exchange(plan: FlowPlan, eps_prop: torch.Tensor, z_saved: O
           _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(state.mom), _ptr(state.kin), _ptr(noise), _ptr(uniform),
           rng, step_ptr, adapt_ptr, da, *metric_args, *temper_args, flags, _ptr(eps_next), _ptr(acc), _ptr(la), *exchange_args)
     return eps_next, acc, la, swapped, log_swap
+
+
+HMC_RESAMPLE = 512     # include/lsnf_flow_mcmc.h LSNF_HMC_RESAMPLE
+
+
+def _row_resample_mode(resample, phase, adapt, window, anneal):
+    """What the resampling calls check before `_check_chain`, beside `_row_temper_mode`: resample is None or the group's length P;
+    a resampling call is an annealing end call that neither adapts, folds nor closes, and P is 2, 4, 8 or 16.  Returns the move's
+    flag."""
+    if resample is None:
+        return 0
+    if resample not in (2, 4, 8, 16):
+        raise LsnfError(f"resample must be None, 2, 4, 8 or 16 (got {resample!r})")
+    if phase != "end" or adapt is not None or window is not None or anneal is None:
+        raise LsnfError("particles are resampled between the weight increment and the next trajectory of a frozen chain: resample "
+                        "goes with phase='end' and anneal=, without adapt and window")
+    return HMC_RESAMPLE
+
+
+def _row_resample_args(plan, resample, ess_threshold, resample_uniform, rng, B, dev, reuse_buffers):
+    """After `_check_chain`: the move's uniforms through the one checking path and its two outputs.  Returns (the five arguments in the
+    order the C call names them: group, ess_frac, resample_uniform, ancestor_out, ess_out; ancestor; ess) -- the last two None without
+    resample."""
+    _check_in(resample_uniform, "resample_uniform", B, dev)
+    if resample is None:
+        if resample_uniform is not None:
+            raise LsnfError("resample_uniform goes with resample=P")
+        return (0, 0.0, None, None, None), None, None
+    if B % resample:
+        raise LsnfError(f"the chain's {B} rows are not a multiple of resample={resample}")
+    if (rng is None) != (resample_uniform is not None):
+        raise LsnfError("the move draws as the trajectory does: resample_uniform with the tensors (noise, uniform=), none with a "
+                        "PhiloxNoise")
+
+    def make():
+        f32 = dict(dtype=torch.float32, device=dev)
+        return {"ancestor": torch.empty(B, **f32), "ess": torch.empty(B, **f32)}
+    bufs = _stream_buffers(plan, "_hmcs_buffers", B, dev, make) if reuse_buffers else make()
+    return ((int(resample), float(ess_threshold), _ptr(resample_uniform), _ptr(bufs["ancestor"]), _ptr(bufs["ess"])),
+            bufs["ancestor"], bufs["ess"])
+
+
+def hmc_step_resample(plan: FlowPlan, z_prop: torch.Tensor, grad_g: Optional[torch.Tensor], energy_g: Optional[torch.Tensor],
+                      state: HmcState, noise, steps: HmcRowSteps, metric: HmcRowMetric, temper: HmcRowTemper, *, phase: str = "end",
+                      uniform: Optional[torch.Tensor] = None, propose: bool = True, inplace: bool = False, reuse_buffers: bool = False,
+                      adapt: Optional[str] = None, window: Optional[str] = None, anneal: Optional[torch.Tensor] = None,
+                      resample: Optional[int] = None, ess_threshold: float = 0.5, resample_uniform: Optional[torch.Tensor] = None):
+    """`hmc_step_tempered` with a resampling move between the rows of a group (include/lsnf_flow_mcmc.h `lsnf_hmc_step_resample`): the
+    step of a sequential Monte Carlo sampler.  Rows [k * P, (k + 1) * P) are the particles of group k; P = resample is 2, 4, 8 or 16
+    and divides B.
+    resample (phase "end" with anneal=, without adapt / window): after the trajectory's decision and the weight increment, a group
+    whose effective sample size (sum w)^2 / sum w^2 is below ess_threshold * P is resampled systematically with ONE uniform, u =
+    resample_uniform[first row of the group] (with tensor noise) or drawn in-kernel (PhiloxNoise).  A row whose ancestor is another
+    row takes that row's state.z / like_grad / like_energy and its state.grad / state.energy re-tempered to the row's own beta, and
+    begins the next trajectory (propose) from them; every row of the group gets the group's mean weight, log_w = {log mean w, 0}.
+    beta, step, scale and the adaptation stay with the row.  Without resample this is `hmc_step_tempered` to the bit.  Returns that
+    call's tuple plus (ancestor, ess), both (B) -- the rung a row's state came from (its own where nothing moved), and the group's
+    effective sample size -- or (None, None) without resample."""
+    flags, inner = _row_step_mode(steps, phase, adapt), phase == "inner"
+    flags |= _row_metric_mode(metric, phase, window)
+    flags |= _row_temper_mode(temper, phase, anneal)
+    flags |= _row_resample_mode(resample, phase, adapt, window, anneal)
+    B, dev, noise, rng = _check_chain(plan, z_prop, "z_prop", grad_g, energy_g, state, HmcState, noise, uniform)
+    step_ptr, adapt_ptr, da = _row_step_args(steps, B, dev, adapt)
+    metric_args = _row_metric_args(plan, metric, B, dev, window)
+    temper_args = _row_temper_args(plan, temper, B, dev, anneal)
+    resample_args, ancestor, ess = _row_resample_args(plan, resample, ess_threshold, resample_uniform, rng, B, dev, reuse_buffers)
+    if inner and (noise is not None or rng is not None or uniform is not None or not propose):
+        raise LsnfError("an inner leapfrog step draws and decides nothing: noise and uniform must be None, propose True")
+    bufs, z1, ll = _forward_at(plan, z_prop, B, dev, "_hmc_buffers", reuse_buffers)
+    z_next = None if not propose else z_prop if inplace else torch.empty_like(z_prop)
+    acc, la = (None, None) if inner else (bufs["acc"], bufs["la"])
+    _call("lsnf_hmc_step_resample", dev, *_plan_head(plan), B, _ptr(z_prop), _ptr(z1), _ptr(bufs["saved"]), _ptr(bufs["act"]), _ptr(ll),
+          _ptr(grad_g), _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(state.mom), _ptr(state.kin), _ptr(noise),
+          _ptr(uniform), rng, step_ptr, adapt_ptr, da, *metric_args, *temper_args, flags, _ptr(z_next), _ptr(acc), _ptr(la), *resample_args)
+    return z_next, acc, la, ll, ancestor, ess
+
+
+def reverse_hmc_step_resample(plan: FlowPlan, eps_prop: torch.Tensor, z_saved: Optional[torch.Tensor], act_saved: torch.Tensor,
+                              grad_g: Optional[torch.Tensor], energy_g: Optional[torch.Tensor], state: HmcState, noise, steps: HmcRowSteps,
+                              metric: HmcRowMetric, temper: HmcRowTemper, *, phase: str = "end", uniform: Optional[torch.Tensor] = None,
+                              propose: bool = True, inplace: bool = False, reuse_buffers: bool = False, adapt: Optional[str] = None,
+                              window: Optional[str] = None, anneal: Optional[torch.Tensor] = None, resample: Optional[int] = None,
+                              ess_threshold: float = 0.5, resample_uniform: Optional[torch.Tensor] = None):
+    """`reverse_hmc_step_tempered` with a resampling move between the rows of a group (include/lsnf_flow_mcmc.h
+    `lsnf_reverse_hmc_step_resample`); resample, ess_threshold and resample_uniform: as `hmc_step_resample`'s, with the state (eps,
+    eps + beta * like_grad, |eps|^2 / 2 + beta * like_energy).  ONE launch and nothing else, so a resampling end call can be captured
+    in a graph.  Returns `reverse_hmc_step_tempered`'s tuple plus (ancestor, ess), (None, None) without resample."""
+    flags, inner = _row_step_mode(steps, phase, adapt), phase == "inner"
+    flags |= _row_metric_mode(metric, phase, window)
+    flags |= _row_temper_mode(temper, phase, anneal)
+    flags |= _row_resample_mode(resample, phase, adapt, window, anneal)
+    B, dev, noise, rng = _check_chain(plan, eps_prop, "eps_prop", grad_g, energy_g, state, HmcState, noise, uniform,
+                                      stash=(z_saved, act_saved))
+    step_ptr, adapt_ptr, da = _row_step_args(steps, B, dev, adapt)
+    metric_args = _row_metric_args(plan, metric, B, dev, window)
+    temper_args = _row_temper_args(plan, temper, B, dev, anneal)
+    resample_args, ancestor, ess = _row_resample_args(plan, resample, ess_threshold, resample_uniform, rng, B, dev, reuse_buffers)
+    if inner and (noise is not None or rng is not None or uniform is not None or not propose):
+        raise LsnfError("an inner leapfrog step draws and decides nothing: noise and uniform must be None, propose True")
+    acc = la = None
+    if not inner:
+        def make():
+            f32 = dict(dtype=torch.float32, device=dev)
+            return {"acc": torch.empty(B, **f32), "la": torch.empty(B, **f32)}
+        bufs = _stream_buffers(plan, "_rhmc_buffers", B, dev, make) if reuse_buffers else make()
+        acc, la = bufs["acc"], bufs["la"]
+    eps_next = None if not propose else eps_prop if inplace else torch.empty_like(eps_prop)
+    _call("lsnf_reverse_hmc_step_resample", dev, *_plan_head(plan), B, _ptr(eps_prop), _ptr(z_saved), _ptr(act_saved), _ptr(grad_g),
+          _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(state.mom), _ptr(state.kin), _ptr(noise), _ptr(uniform),
+          rng, step_ptr, adapt_ptr, da, *metric_args, *temper_args, flags, _ptr(eps_next), _ptr(acc), _ptr(la), *resample_args)
+    return eps_next, acc, la, ancestor, ess

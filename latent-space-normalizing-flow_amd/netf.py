@@ -580,6 +580,31 @@ class _netF(nn.Module):
                                               propose=propose, inplace=inplace, reuse_buffers=reuse_buffers, adapt=adapt, window=window,
                                               anneal=det(anneal), swap=swap, ladder=ladder, swap_uniform=det(swap_uniform))
 
+    def hmc_step_resample(self, z_prop, grad_g=None, energy_g=None, state=None, noise=None, steps=None, metric=None, temper=None, *,
+                          phase="end", uniform=None, propose=True, inplace=False, reuse_buffers=False, adapt=None, window=None,
+                          anneal=None, resample=None, ess_threshold=0.5, resample_uniform=None):
+        """`hmc_step_tempered` with a resampling move between the rows of a group (`flow.hmc_step_resample`): resample = P on an
+        annealing end call resamples, inside the kernel, every group of P rows whose effective sample size is below
+        ess_threshold * P.  Returns what `hmc_step` returns plus (ancestor, ess)."""
+        det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t
+        return flow.hmc_step_resample(self._plan(), det(z_prop), det(grad_g), det(energy_g), state, det(noise), steps, metric, temper,
+                                      phase=phase, uniform=det(uniform), propose=propose, inplace=inplace, reuse_buffers=reuse_buffers,
+                                      adapt=adapt, window=window, anneal=det(anneal), resample=resample, ess_threshold=ess_threshold,
+                                      resample_uniform=det(resample_uniform))
+
+    def reverse_hmc_step_resample(self, eps_prop, z_saved, act_saved, grad_g=None, energy_g=None, state=None, noise=None, steps=None,
+                                  metric=None, temper=None, *, phase="end", uniform=None, propose=True, inplace=False,
+                                  reuse_buffers=False, adapt=None, window=None, anneal=None, resample=None, ess_threshold=0.5,
+                                  resample_uniform=None):
+        """`reverse_hmc_step_tempered` with a resampling move between the rows of a group (`flow.reverse_hmc_step_resample`).
+        Returns what `reverse_hmc_step` returns plus (ancestor, ess)."""
+        det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t
+        return flow.reverse_hmc_step_resample(self._plan(), det(eps_prop), det(z_saved), det(act_saved), det(grad_g), det(energy_g),
+                                              state, det(noise), steps, metric, temper, phase=phase, uniform=det(uniform),
+                                              propose=propose, inplace=inplace, reuse_buffers=reuse_buffers, adapt=adapt, window=window,
+                                              anneal=det(anneal), resample=resample, ess_threshold=ess_threshold,
+                                              resample_uniform=det(resample_uniform))
+
     def mle_grads(self, z, accumulate: bool = False, max_norm: Optional[float] = None, reuse_buffers: bool = False):
         """Fused flow-MLE gradients (train.py:404-411): loss_f = -mean_b ll(z_b) and d loss_f / d theta written to
         `.grad` of the 60 live tensors -- forward (ll summed in-kernel), dump backward, batch contraction, unfold:
