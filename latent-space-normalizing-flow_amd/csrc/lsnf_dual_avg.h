@@ -1,5 +1,5 @@
 // lsnf_dual_avg.h -- device: the dual-averaging update of a row's step size (include/lsnf_flow_mcmc.h, LSNF_HMC_ADAPT), shared by the
-// per-row tails of lsnf_small3_hmcr.hip and lsnf_small3_rhmcr.hip.  fp32, the operations and the order of the header, no contraction.
+// two tails (lsnf_hmc_tail.h, lsnf_rhmc_tail.h) from their ROWS level up.  fp32, the operations and the order of the header, no contraction.
 #pragma once
 #include "lsnf_small3.h"
 

@@ -1,5 +1,5 @@
 // lsnf_exchange.h -- device: the replica-exchange move of the tempered HMC steps (include/lsnf_flow_mcmc.h, lsnf_hmc_step_exchange /
-// lsnf_reverse_hmc_step_exchange, LSNF_HMC_SWAP), shared by the tails of lsnf_small3_hmcx.hip and lsnf_small3_rhmcx.hip: the partner-lane
+// lsnf_reverse_hmc_step_exchange, LSNF_HMC_SWAP), shared by the two tails (lsnf_hmc_tail.h, lsnf_rhmc_tail.h): the partner-lane
 // rule, the pair's log ratio, its uniform and the cross-lane move.  fp32, the operations and the order of the header, no contraction.
 // A lane is g * 16 + n and row n of a 16-row tile is held by lane index n of every column group g and of every wave, so the partner
 // of a row of a ladder of R <= 16 aligned rows is another lane of the same wave with the same g: a swap moves registers, and every

@@ -1,5 +1,5 @@
 // lsnf_metric.h -- device: the per-row diagonal metric of the HMC steps (include/lsnf_flow_mcmc.h, LSNF_HMC_METRIC_FOLD / _CLOSE), shared
-// by the tails of lsnf_small3_hmcm.hip and lsnf_small3_rhmcm.hip.  fp32, the operations and the order of the header, no contraction.
+// by the two tails (lsnf_hmc_tail.h, lsnf_rhmc_tail.h).  fp32, the operations and the order of the header, no contraction.
 // A lane owns the four columns of a half-unit from load to store, so everything here is lane-local.
 #pragma once
 #include "lsnf_small3.h"
@@ -12,6 +12,12 @@ __device__ __forceinline__ f32x4 lsnf_metric_mul(const f32x4& sd, const f32x4& v
 #pragma unroll
     for (int j = 0; j < 4; ++j) r[j] = sd[j] * v[j];
     return r;
+}
+// a tail's product at its level (lsnf_hmc_launch.h): without a metric there is no sd and v stays what it is
+template <bool METRIC>
+__device__ __forceinline__ f32x4 lsnf_metric_mul_if(const f32x4& sd, const f32x4& v) {
+    if constexpr (METRIC) return lsnf_metric_mul(sd, v);
+    else return v;
 }
 // Welford's fold of the state x into (mean, m2), in place; n = count + 1, the row's new count
 __device__ __forceinline__ void lsnf_metric_fold(f32x4& mean, f32x4& m2, const f32x4& x, float n) {

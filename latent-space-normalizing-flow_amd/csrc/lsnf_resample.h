@@ -1,5 +1,5 @@
 // lsnf_resample.h -- device: the resampling move of the annealing HMC end calls (include/lsnf_flow_mcmc.h, lsnf_hmc_step_resample /
-// lsnf_reverse_hmc_step_resample, LSNF_HMC_RESAMPLE), shared by the tails of lsnf_small3_hmcs.hip and lsnf_small3_rhmcs.hip: the
+// lsnf_reverse_hmc_step_resample, LSNF_HMC_RESAMPLE), shared by the two tails (lsnf_hmc_tail.h, lsnf_rhmc_tail.h): the
 // group's effective sample size, its systematic ancestors and its uniform.  fp32, the operations and the order of the header, no
 // contraction.  A group of P <= 16 aligned rows lies inside one wave's 16-row tile (lsnf_exchange.h: a lane is g * 16 + n), so
 // rung j's numbers are the registers of lane (lane & 48) | (first tile row of the group + j): every lane of every wave forms the

@@ -1,0 +1,358 @@
+// lsnf_rhmc_tail.h -- device: the leapfrog tail of Hamiltonian Monte Carlo in the flow's base space (lsnf_reverse_hmc_step and its
+// levels, include/lsnf_flow_mcmc.h): the output section that lsnf_small3_rhmc.hip / _rhmcr / _rhmcm / _rhmct / _rhmcx / _rhmcs give the
+// latency bf16x3 reverse-backward (lsnf_small3_rbwd_kernel.h), one translation unit and one kernel name per level F
+// (lsnf_hmc_level.h), so that no other kernel's text changes with a level.  The levels are lsnf_hmc_tail.h's and what is said there
+// about a level's flags, its row scalars, its re-reads in phase 2 and its move holds here; the two tails stay apart because the spaces
+// differ in most lines (e1 / y2, t_prop, the third sum).
+//
+// The stages T1 / CB' / B4 / B3 / B2 run at a point eps_prop of a trajectory (= z_out: the reverse's input, the point the stash of
+// x = f^-1(eps_prop) belongs to) and leave g = J_{f^-1}(eps_prop)^T grad_g in registers, next to the second half of the rows of
+// eps_prop (the last block's y2; the first half, e1, is one more load_row_half in the tail, as in lsnf_small3_rmala.hip and for its
+// reason).  Target pi(eps) ~ exp(-U), U = |eps|^2 / 2 + beta energy_g, grad U = eps + beta g.  Every phase forms t_prop = eps_prop +
+// (beta * g) (one fp32 add: lsnf_reverse_mala_step's grad_acc); the phase is a kernel-uniform branch:
+//   INNER        a leapfrog step inside a trajectory: ph = mom - s sd t_prop, eps_next = eps_prop + s sd ph, mom <- ph.  Per lane and
+//                column: no cross-wave sum, no barrier; a lane stores the columns it loaded, so eps_next may be eps_prop.
+//   INIT / end   two phases around one barrier, as the MALA tail.  (1) every wave with a unit of its own loads its half-units of mom /
+//                eps_acc / grad_acc, draws or loads its half-units of xi (xi does not depend on the decision) and leaves its partial
+//                row sums of sum pL^2 (pL = mom - (s/2) sd t_prop), sum xi^2 and sum eps_prop^2 in the three RED slots per row and
+//                wave (the dead GTP tiles); every wave loads the rows' scalars; (2) every wave adds the four partials of its rows in
+//                wave order -- the same numbers in the same order, so the four waves decide alike --, forms U_prop = beta energy_g +
+//                |eps_prop|^2 / 2 and log_alpha = (u_acc - U_prop) + (kin0 - kinL), draws (or has loaded) the row's uniform, and stores
+//                its half-units of the state (accepted rows only) and of the next trajectory's first half-kick ph = xi - (s/2) sd
+//                t_state, eps_next = eps_state + s sd ph, mom <- ph.  Wave 0 stores the row scalars.  All loads of a workgroup's rows
+//                precede the barrier and a lane stores the columns it loaded.
+// sum eps_prop^2 is accumulated as lsnf_small3_rmala.hip accumulates it (an INIT call writes that kernel's INIT state bit for bit), the
+// other two sums as lsnf_hmc_tail.h's.  The uniform is lsnf_mala_step's (chain_uniform), xi lsnf_reverse_mala_step's draw (chain_xi: a
+// padding column, beyond nz / 2 of its half, is 0 and so not counted in sum xi^2).  Everything here is fp32 without fp contraction.
+#pragma once
+#include "lsnf_small3.h"
+#include "lsnf_dual_avg.h"
+#include "lsnf_metric.h"
+#include "lsnf_temper.h"
+#include "lsnf_exchange.h"
+#include "lsnf_resample.h"
+#include "lsnf_hmc_level.h"
+
+namespace {
+// a: the level's Small3Rhmc*Args; g1 / g2: this wave's half-units of g -- without a temperature replaced by t_prop, with one kept: gl
+// of the state --; y2: its second-half unit of eps_prop; the rest: the kernel's locals of the same names.
+template <class F, int HT, int ST, class A>
+__device__ __forceinline__ void small3_rhmc_tail(const A& a, f32x4 (&g1)[ST], f32x4 (&g2)[ST], const f32x4 (&y2)[ST],
+                                                 const long (&sample)[ST], const bool (&live)[ST], const long (&row)[ST], float* RED,
+                                                 bool has1, int nt1, int ft1, int wave, int g, int n, int vec4) {
+#pragma clang fp contract(off)
+    constexpr bool MOVE = F::EXCHANGE || F::RESAMPLE;
+    const bool init = (a.flags & 1u) != 0, inner = (a.flags & 2u) != 0, adapt = F::ROWS && (a.flags & 4u) != 0;      // kernel-uniform
+    const bool fold = F::METRIC && (a.flags & 16u) != 0, close = F::METRIC && (a.flags & 32u) != 0, anneal = F::TEMPER && (a.flags & 64u) != 0;
+    const bool swap = F::EXCHANGE && (a.flags & 128u) != 0, resample = F::RESAMPLE && (a.flags & 512u) != 0;
+    int xlane = 0, pl = 0, rk = 0, P = 1;                              // (the lanes of a move: lsnf_hmc_tail.h)
+    bool paired = false, lower = false;
+    if constexpr (MOVE) xlane = lsnf_exchange_lane();
+    if constexpr (F::EXCHANGE) {
+        const int xn = xlane & 15;                                     // (n and g again, from the lane index itself)
+        const int pn = swap ? lsnf_exchange_partner(xn, a.ladder, (a.flags & 256u) != 0) : xn;     // the partner's tile row (SWAP)
+        paired = pn != xn; lower = pn > xn;
+        pl = (xlane & 48) | pn;                                        // the partner's lane: the same wave, the same columns
+    }
+    if constexpr (F::RESAMPLE) {
+        P = resample ? a.group : 1;                                    // the group's length (RESAMPLE)
+        rk = xlane & (P - 1);                                          // the row's rung: 16 % P == 0, so it is (global row) % P
+    }
+    float s[ST], hs2[ST], bt[ST];                                      // per row: fixed before the momentum is drawn, constant in a trajectory
+#pragma unroll
+    for (int st = 0; st < ST; ++st) {
+        if constexpr (F::ROWS) s[st] = a.step_rows[row[st]];
+        else s[st] = a.step;
+        hs2[st] = 0.5f * s[st];
+        bt[st] = 0.0f;
+        if constexpr (F::TEMPER) bt[st] = a.beta_rows[row[st]];
+    }
+    if (inner) {                                                       // ---- a leapfrog step inside a trajectory ----
+        if (!has1) return;
+#pragma unroll
+        for (int st = 0; st < ST; ++st) {
+            const long ro = row[st] * (long)a.nz, so = sample[st] * (long)a.nz;
+            const f32x4 e1 = load_row_half<HT>(nt1, ft1, a.z_out + ro, a.half, g, vec4);
+#pragma unroll
+            for (int hs = 0; hs < 2; ++hs) {
+                const int t = hs * HT + nt1;
+                const f32x4 pm = load_row_half<HT>(t, ft1, a.mom + ro, a.half, g, vec4);
+                f32x4 sd = f32x4{0.f, 0.f, 0.f, 0.f};
+                if constexpr (F::METRIC) sd = load_row_half<HT>(t, ft1, a.scale + ro, a.half, g, vec4);
+                const f32x4 ec = hs ? y2[st] : e1;
+                const f32x4 bg = lsnf_temper_mul_if<F::TEMPER>(bt[st], hs ? g2[st] : g1[st]);
+                f32x4 tp, ph, en;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) tp[r] = __fadd_rn(ec[r], bg[r]);      // t_prop = eps_prop + (beta * g)
+                const f32x4 sg = lsnf_metric_mul_if<F::METRIC>(sd, tp);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) ph[r] = pm[r] - s[st] * sg[r];
+                const f32x4 sq = lsnf_metric_mul_if<F::METRIC>(sd, ph);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) en[r] = ec[r] + s[st] * sq[r];
+                if (live[st]) {
+                    store_row_half<HT>(t, ft1, ph, a.mom + so, a.half, g, vec4);
+                    store_row_half<HT>(t, ft1, en, a.eps_new + so, a.half, g, vec4);
+                }
+            }
+        }
+        return;
+    }
+    // ---- INIT / end of a trajectory ----
+    const LsnfRngState rs = a.rng.enabled ? lsnf_rng_state(a.rng) : LsnfRngState{0u, 0u, 0u, 0u, 0};
+    f32x4 e1[ST], ea[ST][2], ga[ST][2], xi[ST][2];                     // e1: the first half of this wave's unit of eps_prop (the second is y2)
+    // per row; read by every wave before the barrier, through the clamped row[st]: wave 0 (lane g == 0) stores them after it
+    float en_g[ST], u_old[ST], k_old[ST], uni[ST];
+    f32x4 ad[ST];                                                      // ROWS: the rows' {log_step_bar, hbar, count, mu}
+    float cnt[ST];                                                     // METRIC: the window's count
+    float el_old[ST], bn[ST], lw[ST], lc[ST];                          // TEMPER: like_u_acc (el of the kept state), beta_next, the Kahan pair log_w
+    float su[ST];                                                      // EXCHANGE: the swap's uniform
+    // phase 1: this wave's half-units of the rows, its partial sums into RED
+#pragma unroll
+    for (int st = 0; st < ST; ++st) {
+        float sl = 0.0f, sx = 0.0f, se = 0.0f;
+        en_g[st] = a.energy_g ? a.energy_g[row[st]] : 0.0f;
+        u_old[st] = init ? 0.0f : a.u_acc[row[st]];
+        k_old[st] = init ? 0.0f : a.kin0[row[st]];
+        uni[st] = (a.uniform && !init) ? a.uniform[row[st]] : 0.5f;
+        if constexpr (F::METRIC) cnt[st] = fold ? a.count[row[st]] : 0.0f;
+        if constexpr (F::TEMPER) {
+            el_old[st] = ((anneal || swap) && !init) ? a.like_u_acc[row[st]] : 0.0f;
+            // the pair's uniform is read at its lower row (B >= ladder: in bounds)
+            if constexpr (F::EXCHANGE) su[st] = (paired && a.swap_uniform) ? a.swap_uniform[lower ? row[st] : row[st] - 1] : 0.5f;
+            bn[st] = anneal ? a.beta_next[row[st]] : 0.0f;
+            lw[st] = 0.0f; lc[st] = 0.0f;
+            if (anneal) { const float2 p = reinterpret_cast<const float2*>(a.log_w)[row[st]]; lw[st] = p.x; lc[st] = p.y; }
+        }
+        if constexpr (F::ROWS) {
+            ad[st] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (adapt) ad[st] = reinterpret_cast<const f32x4*>(a.adapt)[row[st]];
+        }
+        e1[st] = load_row_half<HT>(nt1, ft1, a.z_out + row[st] * (long)a.nz, a.half, g, vec4);
+#pragma unroll
+        for (int hs = 0; hs < 2; ++hs) {
+            const int t = hs * HT + nt1;
+            const long ro = row[st] * (long)a.nz;
+            ea[st][hs] = f32x4{0.f, 0.f, 0.f, 0.f}; ga[st][hs] = f32x4{0.f, 0.f, 0.f, 0.f};
+            f32x4 pm = f32x4{0.f, 0.f, 0.f, 0.f}, sd = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (!init && has1) {                                       // (a wave without a unit repeats unit 0: counted once, by wave 0)
+                ea[st][hs] = load_row_half<HT>(t, ft1, a.eps_acc + ro, a.half, g, vec4);
+                ga[st][hs] = load_row_half<HT>(t, ft1, a.grad_acc + ro, a.half, g, vec4);
+                pm = load_row_half<HT>(t, ft1, a.mom + ro, a.half, g, vec4);
+                if constexpr (F::METRIC) sd = load_row_half<HT>(t, ft1, a.scale + ro, a.half, g, vec4);
+            }
+            xi[st][hs] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (a.eps_new && has1)          // (lsnf_reverse_mala_step's draw)
+                xi[st][hs] = chain_xi<HT>(a.noise, rs, a.rng.row0, a.nz, a.half, hs, nt1, ft1, g, row[st], sample[st], vec4);
+            const f32x4 ec = hs ? y2[st] : e1[st];
+            f32x4& gq = hs ? g2[st] : g1[st];
+            const f32x4 bg = lsnf_temper_mul_if<F::TEMPER>(bt[st], gq);
+            f32x4 tp;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) tp[r] = __fadd_rn(ec[r], bg[r]);            // t_prop = eps_prop + (beta * g)
+            if constexpr (!F::TEMPER) gq = tp;                         // (phase 2 reads it back; with a temperature it needs gl and forms t_prop again)
+            const f32x4 sg = lsnf_metric_mul_if<F::METRIC>(sd, tp);
+            f32x4 pL;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                pL[r] = pm[r] - hs2[st] * sg[r];
+                sl += pL[r] * pL[r]; se += ec[r] * ec[r];
+                sx += xi[st][hs][r] * xi[st][hs][r];
+            }
+            // nothing is proposed: the full-step momentum at the proposal is left readable (this lane loaded these columns)
+            if (!init && !a.eps_new && has1 && live[st]) store_row_half<HT>(t, ft1, pL, a.mom + sample[st] * (long)a.nz, a.half, g, vec4);
+        }
+        if (!has1) { sl = 0.0f; sx = 0.0f; se = 0.0f; }
+        sl = group_sum(sl); sx = group_sum(sx); se = group_sum(se);
+        if (g == 0) {
+            float* slot = RED + ((st * 4 + wave) * 16 + n) * 3;
+            slot[0] = sl; slot[1] = sx; slot[2] = se;
+        }
+    }
+    __syncthreads();
+    // phase 2: every wave decides its rows (the same sums in the same order: the same decision, the same new step, the same move),
+    // then stores its half-units
+#pragma unroll
+    for (int st = 0; st < ST; ++st) {
+        float s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const float* slot = RED + ((st * 4 + w) * 16 + n) * 3;
+            s1 += slot[0]; s2 += slot[1]; s3 += slot[2];
+        }
+        const float u_prop = lsnf_temper_mul_if<F::TEMPER>(bt[st], en_g[st]) + 0.5f * s3;
+        float la = 0.0f;
+        bool acc = true;
+        if (!init) {
+            const float kin_l = 0.5f * s1;
+            la = (u_old[st] - u_prop) + (k_old[st] - kin_l);
+            float u = uni[st];
+            if (!a.uniform) u = chain_uniform(rs, a.rng.row0, sample[st]);
+            acc = logf(u) < la;                                        // (a NaN log_alpha rejects)
+        }
+        float sn = s[st], hn = hs2[st];                                // the step of the trajectory this call begins
+        if constexpr (F::ROWS) {
+            if (adapt) {
+                sn = lsnf_dual_average(ad[st], la, a.da, (a.flags & 8u) != 0);
+                hn = 0.5f * sn;
+                if (close && !(a.flags & 8u)) ad[st] = f32x4{0.f, 0.f, 0.f, logf(10.0f * sn)};      // the window's end restarts the averaging
+            }
+        }
+        float nf = 0.0f, d = 0.0f;
+        if constexpr (F::METRIC) nf = cnt[st] + 1.0f;                  // the row's count after the fold
+        if constexpr (F::TEMPER) d = bn[st] - bt[st];                  // (ANNEAL) the change of the row's temperature
+        // the move's decision (lsnf_hmc_tail.h): ml: the lane of the row whose state comes to this row, mv: it does; ep / up: that
+        // row's el_s / u_s, dn: what re-tempers its state to this row's temperature, uf: its u_s there
+        float ep = 0.0f, up = 0.0f, dn = 0.0f, uf = 0.0f, lr = 0.0f;
+        int ml = xlane;
+        bool mv = false;
+        if constexpr (F::EXCHANGE) {
+            ml = pl;
+            if (swap) {                                                // the pair's decision: the whole wave is active here
+                const float els = acc ? en_g[st] : el_old[st], us = acc ? u_prop : u_old[st];
+                const float bp = lsnf_exchange_take(bt[st], pl);
+                ep = lsnf_exchange_take(els, pl); up = lsnf_exchange_take(us, pl);
+                if (paired) lr = lower ? lsnf_exchange_log_ratio(bt[st], bp, els, ep) : lsnf_exchange_log_ratio(bp, bt[st], ep, els);
+                float u = su[st];
+                if (!a.swap_uniform) u = lsnf_exchange_uniform(rs, a.rng.row0, lower ? sample[st] : sample[st] - 1);
+                mv = paired && logf(u) < lr;                           // (a NaN log_r rejects)
+                dn = bt[st] - bp;
+            }
+        }
+        if constexpr (F::RESAMPLE) {
+            if (resample) {                                            // the group's decision: the whole wave is active here
+                const float els = acc ? en_g[st] : el_old[st];
+                const float us = lsnf_retemper(acc ? u_prop : u_old[st], d, els);      // what the ANNEAL lines below store, formed by every lane
+                float nw = lw[st], nc = lc[st];
+                lsnf_temper_weigh(nw, nc, d, els);
+                // the group's uniform, read here and not in front of the barrier: held across it, it is a register that
+                // lsnf_small3_rhmcs_kernel<2, 4, 1> does not have (12 bytes of scratch); (B >= group: row - rk is in bounds)
+                const float u = a.resample_uniform ? a.resample_uniform[row[st] - rk] : lsnf_resample_uniform(rs, a.rng.row0, sample[st] - rk);
+                const LsnfResample rv = lsnf_resample_decide(nw - nc, u, P, a.ess_frac, xlane);
+                ml = xlane - rk + rv.ancestor;
+                const float ba = lsnf_exchange_take(bn[st], ml);
+                up = lsnf_exchange_take(us, ml);
+                ep = lsnf_exchange_take(els, ml);
+                dn = bn[st] - ba;                                      // (the ancestor's state comes to this row's beta_next)
+                uf = lsnf_retemper(up, dn, ep);
+                lw[st] = rv.on ? rv.lw : nw; lc[st] = rv.on ? 0.0f : nc;   // the pair the ANNEAL lines below store (they do not weigh again)
+                if (wave == 0 && g == 0 && live[st]) {                 // (stored here: nothing of the decision but ml stays live)
+                    if (a.ancestor_out) a.ancestor_out[sample[st]] = (float)rv.ancestor;
+                    if (a.ess_out) a.ess_out[sample[st]] = rv.ess;
+                }
+            }
+            mv = ml != xlane;
+        }
+        if (has1 && (MOVE || live[st])) {                              // (with a move: the whole wave, lsnf_hmc_tail.h)
+            const bool lv = MOVE ? live[st] : true;                    // (without a move the entry has settled it: lsnf_hmc_tail.h)
+#pragma unroll
+            for (int hs = 0; hs < 2; ++hs) {
+                const int t = hs * HT + nt1;
+                const long so = sample[st] * (long)a.nz;
+                f32x4 es = f32x4{0.f, 0.f, 0.f, 0.f}, gs = es, gls = es, sd = es;      // (a dead row's: zeros nobody uses)
+                if (lv) {                                              // (so is the row's own offset)
+                    const f32x4 ec = hs ? y2[st] : e1[st];
+                    gls = hs ? g2[st] : g1[st];                         // TEMPER: gl of the state after the decision: g, or the kept one
+                    f32x4 tp = gls;                                    // (without a temperature: phase 1 left t_prop there)
+                    if constexpr (F::TEMPER) {
+                        const f32x4 bg = lsnf_temper_mul(bt[st], gls);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) tp[r] = __fadd_rn(ec[r], bg[r]);    // t_prop again: phase 1's bits
+                    }
+                    es = acc ? ec : ea[st][hs];                         // the state after the decision
+                    if (acc) {
+                        store_row_half<HT>(t, ft1, ec, a.eps_acc + so, a.half, g, vec4);
+                        if constexpr (F::TEMPER) store_row_half<HT>(t, ft1, gls, a.like_grad_acc + so, a.half, g, vec4);
+                        if (!anneal) store_row_half<HT>(t, ft1, tp, a.grad_acc + so, a.half, g, vec4);
+                    } else if constexpr (F::TEMPER) {
+                        if (anneal || swap) gls = load_row_half<HT>(t, ft1, a.like_grad_acc + so, a.half, g, vec4);
+                    }
+                    if constexpr (F::METRIC) {
+                        sd = load_row_half<HT>(t, ft1, a.scale + so, a.half, g, vec4);
+                        if (fold) {
+                            f32x4 mean = load_row_half<HT>(t, ft1, a.mean + so, a.half, g, vec4);
+                            f32x4 m2 = load_row_half<HT>(t, ft1, a.m2 + so, a.half, g, vec4);
+                            lsnf_metric_fold(mean, m2, es, nf);
+                            if (close) {
+                                sd = lsnf_metric_close(sd, m2, nf, a.reg);
+                                store_row_half<HT>(t, ft1, sd, a.scale + so, a.half, g, vec4);
+                                mean = f32x4{0.f, 0.f, 0.f, 0.f}; m2 = f32x4{0.f, 0.f, 0.f, 0.f};
+                            }
+                            store_row_half<HT>(t, ft1, mean, a.mean + so, a.half, g, vec4);
+                            store_row_half<HT>(t, ft1, m2, a.m2 + so, a.half, g, vec4);
+                        }
+                    }
+                    gs = acc ? tp : ga[st][hs];
+                    if constexpr (F::TEMPER) {
+                        if (anneal) {                                  // every row, accepted or not: the kept gradient at beta_next
+                            gs = lsnf_retemper(gs, d, gls);
+                            store_row_half<HT>(t, ft1, gs, a.grad_acc + so, a.half, g, vec4);
+                        }
+                    }
+                }
+                if constexpr (MOVE) {
+                    if (swap || resample) {                            // the other row's quads of the same columns, lane to lane
+                        const f32x4 eq = lsnf_exchange_take(es, ml), gq = lsnf_exchange_take(gs, ml), lq = lsnf_exchange_take(gls, ml);
+                        if (lv && mv) {                                // over what the update stored, to the row's own row
+                            es = eq; gs = lsnf_retemper(gq, dn, lq);
+                            store_row_half<HT>(t, ft1, es, a.eps_acc + so, a.half, g, vec4);
+                            store_row_half<HT>(t, ft1, gs, a.grad_acc + so, a.half, g, vec4);
+                            store_row_half<HT>(t, ft1, lq, a.like_grad_acc + so, a.half, g, vec4);
+                        }
+                    }
+                }
+                if (a.eps_new && lv) {                                 // begin the next trajectory from the (updated, moved) state
+                    const f32x4 sg = lsnf_metric_mul_if<F::METRIC>(sd, gs);
+                    f32x4 ph, en;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) ph[r] = xi[st][hs][r] - hn * sg[r];
+                    const f32x4 sq = lsnf_metric_mul_if<F::METRIC>(sd, ph);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) en[r] = es[r] + sn * sq[r];
+                    store_row_half<HT>(t, ft1, ph, a.mom + so, a.half, g, vec4);
+                    store_row_half<HT>(t, ft1, en, a.eps_new + so, a.half, g, vec4);
+                }
+            }
+        }
+        if (wave == 0 && g == 0 && live[st]) {
+            if constexpr (F::TEMPER)
+                if (acc) a.like_u_acc[sample[st]] = en_g[st];
+            if (anneal) {
+                if constexpr (F::TEMPER) {
+                    const float els = acc ? en_g[st] : el_old[st];
+                    a.u_acc[sample[st]] = lsnf_retemper(acc ? u_prop : u_old[st], d, els);
+                    if (!resample) lsnf_temper_weigh(lw[st], lc[st], d, els);
+                    reinterpret_cast<float2*>(a.log_w)[sample[st]] = float2{lw[st], lc[st]};
+                    a.beta_rows[sample[st]] = bn[st];
+                }
+            } else if (acc) {
+                a.u_acc[sample[st]] = u_prop;
+            }
+            if (a.eps_new) a.kin0[sample[st]] = 0.5f * s2;
+            if (a.accept_out) a.accept_out[sample[st]] = acc ? 1.0f : 0.0f;
+            if (a.log_alpha_out) a.log_alpha_out[sample[st]] = la;
+            if constexpr (F::ROWS) {
+                if (adapt) {
+                    reinterpret_cast<f32x4*>(a.adapt)[sample[st]] = ad[st];
+                    a.step_rows[sample[st]] = sn;
+                }
+            }
+            if constexpr (F::METRIC)
+                if (fold) a.count[sample[st]] = close ? 0.0f : nf;
+            if constexpr (MOVE) {
+                if (mv) {                                              // (after the update's own stores of the same words)
+                    if constexpr (F::EXCHANGE) uf = lsnf_retemper(up, dn, ep);
+                    a.like_u_acc[sample[st]] = ep;
+                    a.u_acc[sample[st]] = uf;
+                }
+            }
+            if constexpr (F::EXCHANGE) {
+                if (swap) {
+                    if (a.swap_out) a.swap_out[sample[st]] = mv ? 1.0f : 0.0f;
+                    if (a.log_swap_out) a.log_swap_out[sample[st]] = lr;
+                }
+            }
+        }
+    }
+}
+}  // namespace

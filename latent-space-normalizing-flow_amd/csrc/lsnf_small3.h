@@ -214,7 +214,7 @@ __device__ __forceinline__ unsigned pair_or32(unsigned u) { return lsnf_pair_or3
 // sum over the 4 lane groups of a per-sample value (lanes n, n + 16, n + 32, n + 48)
 __device__ __forceinline__ float group_sum(float v) { return lsnf_pair_add32(lsnf_pair_add16(v)); }
 
-// ---- the draws of the Markov-chain tails (lsnf_small3_mala.hip, lsnf_small3_rmala.hip, lsnf_small3_hmc.hip, lsnf_small3_rhmc.hip) ----
+// ---- the draws of the Markov-chain tails (lsnf_small3_mala.hip, lsnf_small3_rmala.hip, lsnf_hmc_tail.h, lsnf_rhmc_tail.h) ----
 // the row's uniform in (0, 1): word 0 of Philox at field value 2 of the noise's counter (the noise draws use 0 and 1 there),
 // ((x0 >> 8) + 0.5) * 2^-24 in fp32 -- a pure function of (seed, offset, global row)
 __device__ __forceinline__ float chain_uniform(const LsnfRngState& rs, long long row0, long sample) {

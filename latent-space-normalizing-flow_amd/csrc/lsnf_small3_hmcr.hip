@@ -1,7 +1,9 @@
 // lsnf_small3_hmcr.hip -- Hamiltonian Monte Carlo in z with a step per row and dual-averaging adaptation of it (lsnf_hmc_step_rows,
-// include/lsnf_flow_mcmc.h): the kernel text of lsnf_small3_bwd_kernel.h with the leapfrog tail of lsnf_small3_hmc.hip, the step
-// read per row, as a translation unit of its own, so that the kernels of lsnf_small3_hmc.o are compiled from the text they always
-// were.  The tail is that file's, statement for statement, with these differences:
+// include/lsnf_flow_mcmc.h): the kernel text of lsnf_small3_bwd_kernel.h with a per-row leapfrog tail OF ITS OWN as the output section.
+// The other eleven HMC units take their tail from lsnf_hmc_tail.h / lsnf_rhmc_tail.h; this level was measured 1 % (INNER) and 2 % (end
+// call) slower at 100 rows from that tail's ROWS level in three jobs, with the split and with the column-by-column statement shape
+// (profiles/hmc_one_tail_ab.txt), so it keeps the text its kernels were always compiled from.  What lsnf_hmc_tail.h says about the
+// phases holds here; against the scalar level (that tail at LSNF_LEVEL_SCALAR) this one differs in:
 //   s, hs2       row scalars (step_rows[row], 0.5f * that: exact) in place of the kernel-uniform a.step.  Like u_acc / kin0 every wave
 //                loads them through the clamped row[st] in front of the barrier (inner calls: in front of their loads).
 //   ADAPT        (flags & 4, end calls only, kernel-uniform) every wave loads the row's quad {log_step_bar, hbar, count, mu} in phase
@@ -9,14 +11,16 @@
 //                instructions on the four waves, as the decision itself, because the new step s' feeds every wave's half-units of
 //                the next trajectory's first half-kick.  Wave 0 alone stores the quad and s', for live rows, after the barrier.
 // Without ADAPT a row's outputs are lsnf_small3_hmc_kernel's at step_size = step_rows[row], bit for bit: the same operations in the
-// same order.  Everything here is fp32 without fp contraction.
+// same order (tests/test_gpu_hmc_rows.py).  A fix to the shared tail has to be made here as well.  Everything here is fp32 without fp
+// contraction.
 #include <stdlib.h>
 #include "lsnf_small3.h"
 #include "lsnf_dual_avg.h"
 #include "lsnf_launch.h"
 
 namespace {
-// xi of one half-unit (lsnf_small3_hmc.hip hmc_xi): a row of the noise tensor, or the in-kernel draw; padding columns are 0
+// xi of one half-unit (chain_xi of lsnf_small3.h, in the text this unit always had): a row of the noise tensor, or the in-kernel draw;
+// padding columns are 0
 template <int HT, class A>
 __device__ __forceinline__ f32x4 hmcr_xi(const A& a, const LsnfRngState& rs, int hs, int t, int nt1, int ft1, int g, long row, long sample, int vec4) {
     if (a.noise) return load_row_half<HT>(t, ft1, a.noise + row * (long)a.nz, a.half, g, vec4);

@@ -35,6 +35,8 @@ template <class C, int ST>
 struct Small3RbwdLds {
     static constexpr int TP = 2 * C::HT * S3_BTILE_FLOATS, HL = C::WT * S3_BTILE_FLOATS, GH = C::HT * S3_BTILE_FLOATS;
     static_assert(C::WT <= 2 * C::HT, "g_a1 is kept in the front of the g_t | g_p tiles");
+    // (lsnf_rhmc_tail.h: three partial row sums per wave and row, in these tiles once they are dead after the last block's barrier)
+    static_assert(4 * 16 * 3 <= TP, "the partial sums of the HMC tail live in GTP");
     static constexpr int L_GTP = 0;
     static constexpr int L_GA2 = L_GTP + ST * TP;
     static constexpr int L_GVA = L_GA2 + ST * HL;

@@ -8,7 +8,7 @@ where the half (nz / 2) and the width end inside the 32-column tiles of the inst
 lsnf_pick_tiles selects.  An entry is (nz, f_width, depth, coupling), tagged with that <HT, WT> and with what it stresses."""
 
 TILE = 32                                    # csrc/lsnf_layout.h LSNF_TILE
-DRAW = 4                                     # columns of one in-kernel Philox draw (csrc/lsnf_small3_hmc.hip hmc_xi: f0 .. f0 + 3)
+DRAW = 4                                     # columns of one in-kernel Philox draw (csrc/lsnf_small3.h chain_xi: f0 .. f0 + 3)
 
 
 def pick_tiles(half, width):
