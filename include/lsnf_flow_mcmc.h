@@ -360,7 +360,42 @@
  * Kernels: lsnf_small3_hmcs_kernel / lsnf_small3_rhmcs_kernel, the tempered kernels' stages, instantiations and workgroup shapes.  A
  * group lies inside one wave's 16-row tile, every lane of every wave forms the sums from the same values in the same order, the
  * ancestor's state comes over lane to lane, and every lane writes its own row only: no row reads what another row writes in the same
- * launch.  B = 0 succeeds without a launch. */
+ * launch.  B = 0 succeeds without a launch.
+ *
+ * ---- The next temperature chosen in the annealing call: adaptive tempering (lsnf_hmc_step_schedule, -----------------------------------
+ * ---- lsnf_reverse_hmc_step_schedule) -----------------------------------------------------------------------------------------------------
+ * The two entry points are the resampling calls with `float cess_frac, float min_step` inserted between ess_out and stream, and one
+ * more flag.  Without LSNF_HMC_SCHEDULE every output has the resampling call's bits in every phase (cess_frac and min_step are not
+ * looked at).  With it beta_next is not the groups' next temperature but its CEILING: the call steps each group of P rows to the
+ * temperature at which the conditional effective sample size of the incremental weights (Zhou, Johansen & Aston 2016) is cess_frac * P,
+ * found by twelve halvings, and no further than the ceiling.
+ *   group: P in {2, 4, 8, 16}, B % P == 0, whenever LSNF_HMC_SCHEDULE or LSNF_HMC_RESAMPLE is set: one argument serves both.
+ *   cess_frac: 0 < cess_frac < 1.   min_step: finite and >= 0; with min_step > 0 a group needs at most 1 / min_step calls to arrive.
+ *   flags: the resampling call's; LSNF_HMC_SCHEDULE goes WITH LSNF_HMC_ANNEAL, on an LSNF_HMC_INIT call or an end call (never with
+ *       LSNF_HMC_INNER) and without LSNF_HMC_ADAPT, LSNF_HMC_METRIC_FOLD and LSNF_HMC_METRIC_CLOSE; with or without LSNF_HMC_RESAMPLE,
+ *       which stays refused on an INIT call.
+ *   beta_rows, beta_next: the search reads them at the group's rung 0; the caller keeps both equal on the rows of a group.
+ * The search runs after the trajectory's decision and before the ANNEAL lines.  With {w_i, c_i} row i's Kahan pair BEFORE the increment
+ * and el_s_i the likelihood energy of its state after the decision (an INIT call: the point's), i over the group's rungs.  Every line
+ * is one fp32 operation, rounded once, no contraction.  `tree` is the xor-butterfly over the rungs, t1_i = x_i o x_{i^1}, t2_i = t1_i o
+ * t1_{i^2}, .. (log2 P levels): +, fmaxf and fminf commute, so every row of the group holds the same bits.
+ *         b = beta_rows[rung 0];  cap = beta_next[rung 0];  D = cap - b
+ *         l_i = w_i - c_i;  m = tree fmaxf l_i;  W_i = expf(l_i - m);  S0 = tree + W_i
+ *         emin = tree fminf el_s_i;  r_i = el_s_i - emin
+ *         cess(x):  a_i = x * r_i;  v_i = expf(-a_i);  t_i = W_i * v_i;  q_i = t_i * v_i
+ *                   N1 = tree + t_i;  N2 = tree + q_i;  cess = (N1 * N1) / (N2 * S0)
+ *         if !(D > 0):                  beta' = b            (at or past its ceiling, or NaN: nothing moves)
+ *         else if cess(D) >= cess_frac: beta' = cap          (exactly: the ceiling is reached)
+ *         else lo = 0, hi = D;  12 times: mid = 0.5f * (lo + hi);  cess(mid) >= cess_frac ? lo = mid : hi = mid
+ *              delta = fmaxf(lo, min_step);  beta' = fminf(b + delta, cap)
+ *     (cess here is the conditional effective sample size over P, in (0, 1].)  Every row b of the group then runs the ANNEAL lines
+ *     above with beta' in the place of beta_next[b] -- d = beta' - beta_rows[b], the weight increment, the re-tempering, beta_rows[b] <-
+ *     beta' -- and the resampling move follows, unchanged, if its flag is set.  beta_next is not written.  A NaN in a row's el_s or
+ *     weight makes every comparison false: the group advances by min_step and the resampling rule leaves it alone.  Twelve halvings
+ *     resolve 1 / 4096 of the remaining span D.
+ * Kernels: lsnf_small3_hmca_kernel / lsnf_small3_rhmca_kernel, the resampling kernels' stages, instantiations and workgroup shapes.  The
+ * search is thirteen evaluations of cess, each two butterflies of log2 P lane exchanges, in the wave that holds the group's tile: no row
+ * reads what another row writes in the same launch.  B = 0 succeeds without a launch. */
 #ifndef LSNF_FLOW_MCMC_H
 #define LSNF_FLOW_MCMC_H
 
@@ -506,6 +541,31 @@ int lsnf_reverse_hmc_step_resample(const float* plan, int nz, int width, int dep
                                    unsigned flags, float* eps_next, float* accept_out, float* log_alpha_out,
                                    int group, float ess_frac, const float* resample_uniform, float* ancestor_out, float* ess_out,
                                    void* stream);
+
+/* the groups' next temperature searched in the annealing call (adaptive tempering) */
+#define LSNF_HMC_SCHEDULE 1024u  /* INIT and end calls with ANNEAL: beta_next is the ceiling, the step is found from the particles */
+int lsnf_hmc_step_schedule(const float* plan, int nz, int width, int depth, int coupling, int B,
+                           const float* z_prop, const float* z_out, const float* z_saved, const float* act_saved,
+                           const float* ll_prop, const float* grad_g, const float* energy_g,
+                           float* z_acc, float* grad_acc, float* u_acc, float* mom, float* kin0,
+                           const float* noise, const float* uniform, const LsnfRng* rng,
+                           float* step_rows, float* adapt, const LsnfDualAvg* da,
+                           float* scale_rows, float* mean_rows, float* m2_rows, float* count_rows, const LsnfMetricReg* reg,
+                           float* beta_rows, const float* beta_next, float* like_grad_acc, float* like_u_acc, float* log_w, unsigned flags,
+                           float* z_next, float* accept_out, float* log_alpha_out,
+                           int group, float ess_frac, const float* resample_uniform, float* ancestor_out, float* ess_out,
+                           float cess_frac, float min_step, void* stream);
+int lsnf_reverse_hmc_step_schedule(const float* plan, int nz, int width, int depth, int coupling, int B,
+                                   const float* eps_prop, const float* z_saved, const float* act_saved,
+                                   const float* grad_g, const float* energy_g,
+                                   float* eps_acc, float* grad_acc, float* u_acc, float* mom, float* kin0,
+                                   const float* noise, const float* uniform, const LsnfRng* rng,
+                                   float* step_rows, float* adapt, const LsnfDualAvg* da,
+                                   float* scale_rows, float* mean_rows, float* m2_rows, float* count_rows, const LsnfMetricReg* reg,
+                                   float* beta_rows, const float* beta_next, float* like_grad_acc, float* like_u_acc, float* log_w,
+                                   unsigned flags, float* eps_next, float* accept_out, float* log_alpha_out,
+                                   int group, float ess_frac, const float* resample_uniform, float* ancestor_out, float* ess_out,
+                                   float cess_frac, float min_step, void* stream);
 
 #ifdef __cplusplus
 }

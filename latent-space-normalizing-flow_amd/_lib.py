@@ -192,6 +192,24 @@ _EXT_SIGNATURES = {
                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint,
                                                c_void_p, c_void_p, c_void_p,
                                                c_int, ctypes.c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lsnf_hmc_step_schedule": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, ctypes.POINTER(LsnfRng),
+                                       c_void_p, c_void_p, ctypes.POINTER(LsnfDualAvg),
+                                       c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(LsnfMetricReg),
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint,
+                                       c_void_p, c_void_p, c_void_p,
+                                       c_int, ctypes.c_float, c_void_p, c_void_p, c_void_p, ctypes.c_float, ctypes.c_float, c_void_p]),
+    "lsnf_reverse_hmc_step_schedule": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, ctypes.POINTER(LsnfRng),
+                                               c_void_p, c_void_p, ctypes.POINTER(LsnfDualAvg),
+                                               c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(LsnfMetricReg),
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint,
+                                               c_void_p, c_void_p, c_void_p,
+                                               c_int, ctypes.c_float, c_void_p, c_void_p, c_void_p, ctypes.c_float, ctypes.c_float, c_void_p]),
 }
 
 _lib = None

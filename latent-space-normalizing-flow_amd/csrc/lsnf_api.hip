@@ -368,6 +368,28 @@ struct RowResample {
     }
 };
 
+// The rules a schedule search adds (lsnf_hmc_step_schedule, lsnf_reverse_hmc_step_schedule), stated once, beside RowResample's and
+// applied after them: all of them are scalars, refused before the empty-batch return.  `group` serves the search and the resampling
+// move; RowResample's own rules (LSNF_HMC_RESAMPLE not on LSNF_HMC_INIT among them) hold unchanged.
+struct RowSchedule {
+    int group; int B; float cess_frac; float min_step; unsigned flags;
+    bool scheduling() const { return (flags & LSNF_HMC_SCHEDULE) != 0; }
+    bool scalars(Check& ck) const {
+        return ck.refuse(scheduling() && (flags & LSNF_HMC_INNER),
+                         "flags: LSNF_HMC_SCHEDULE goes with LSNF_HMC_INIT or an end call, not with LSNF_HMC_INNER") ||
+               ck.refuse(scheduling() && !(flags & LSNF_HMC_ANNEAL), "flags: LSNF_HMC_SCHEDULE goes with LSNF_HMC_ANNEAL") ||
+               ck.refuse(scheduling() && (flags & (LSNF_HMC_ADAPT | LSNF_HMC_METRIC_FOLD | LSNF_HMC_METRIC_CLOSE)),
+                         "flags: LSNF_HMC_SCHEDULE excludes LSNF_HMC_ADAPT, LSNF_HMC_METRIC_FOLD and LSNF_HMC_METRIC_CLOSE") ||
+               ck.refuse(scheduling() && !(group == 2 || group == 4 || group == 8 || group == 16),
+                         "group must be 2, 4, 8 or 16 with LSNF_HMC_SCHEDULE (got %d)", group) ||
+               ck.refuse(scheduling() && B % group != 0, "B=%d is not a multiple of group=%d", B, group) ||
+               ck.refuse(scheduling() && !(cess_frac > 0.0f && cess_frac < 1.0f),
+                         "cess_frac must lie in (0, 1) with LSNF_HMC_SCHEDULE (got %g)", (double)cess_frac) ||
+               ck.refuse(scheduling() && !(std::isfinite(min_step) && min_step >= 0.0f),
+                         "min_step must be finite and not negative with LSNF_HMC_SCHEDULE (got %g)", (double)min_step);
+    }
+};
+
 // ---- kernel selection: each operation decides on the host, from the kernels' coverage predicates, which kernel(s) a call
 // runs, BEFORE anything is launched; the entry point then launches exactly that.  A launcher reached outside what it covers
 // is a selection bug and fails the call (LSNF_E_HIP, the kernel named in lsnf_last_error()); nothing falls through to another
@@ -378,7 +400,7 @@ enum Kernel {
     K_BWD, K_BWD3, K_SMALL_BWD, K_SMALL3_BWD,
     K_SMALL3_RBWD, K_SMALL3_RLV, K_SMALL3_MALA, K_SMALL3_RMALA, K_SMALL3_HMC, K_SMALL3_RHMC,
     K_SMALL3_HMCR, K_SMALL3_RHMCR, K_SMALL3_HMCM, K_SMALL3_RHMCM, K_SMALL3_HMCT, K_SMALL3_RHMCT, K_SMALL3_HMCX, K_SMALL3_RHMCX,
-    K_SMALL3_HMCS, K_SMALL3_RHMCS,
+    K_SMALL3_HMCS, K_SMALL3_RHMCS, K_SMALL3_HMCA, K_SMALL3_RHMCA,
 };
 const char* const kKernelName[] = {
     "no kernel takes this call", "lsnf_fwd_kernel", "lsnf_fwd3b_kernel", "lsnf_fwd3q_kernel",
@@ -390,7 +412,7 @@ const char* const kKernelName[] = {
     "lsnf_small3_hmc_kernel", "lsnf_small3_rhmc_kernel",
     "lsnf_small3_hmcr_kernel", "lsnf_small3_rhmcr_kernel", "lsnf_small3_hmcm_kernel", "lsnf_small3_rhmcm_kernel",
     "lsnf_small3_hmct_kernel", "lsnf_small3_rhmct_kernel", "lsnf_small3_hmcx_kernel", "lsnf_small3_rhmcx_kernel",
-    "lsnf_small3_hmcs_kernel", "lsnf_small3_rhmcs_kernel",
+    "lsnf_small3_hmcs_kernel", "lsnf_small3_rhmcs_kernel", "lsnf_small3_hmca_kernel", "lsnf_small3_rhmca_kernel",
 };
 struct Pick { Kernel k; int st = 0; };     // st: rows per workgroup / 16 of the small3 kernels
 
@@ -613,6 +635,9 @@ Pick select_reverse_hmc_exchange(const LsnfReverseHmcExchangeCall& c) { return {
 // lsnf_small3_rhmcs.hip, likewise.
 Pick select_hmc_resample(const LsnfHmcResampleCall& c) { return {K_SMALL3_HMCS, lsnf_small3_backward_st(c)}; }
 Pick select_reverse_hmc_resample(const LsnfReverseHmcResampleCall& c) { return {K_SMALL3_RHMCS, lsnf_small3_reverse_backward_st(c)}; }
+// The two with a schedule search (lsnf_hmc_step_schedule, lsnf_reverse_hmc_step_schedule): lsnf_small3_hmca.hip, lsnf_small3_rhmca.hip.
+Pick select_hmc_schedule(const LsnfHmcScheduleCall& c) { return {K_SMALL3_HMCA, lsnf_small3_backward_st(c)}; }
+Pick select_reverse_hmc_schedule(const LsnfReverseHmcScheduleCall& c) { return {K_SMALL3_RHMCA, lsnf_small3_reverse_backward_st(c)}; }
 
 // Batch contraction of the parameter gradients (LsnfContraction): on the bf16 matrix pipe where lsnf_params3.hip covers the
 // call (use_x3); from 4 096 rows the fp32-MFMA kernel through LDS, with the widest row loads the rows allow -- every row the
@@ -1567,6 +1592,114 @@ int lsnf_reverse_hmc_step_resample(const float* plan, int nz, int width, int dep
     c.group = group; c.ess_frac = ess_frac; c.resample_uniform = resample_uniform; c.ancestor_out = ancestor_out; c.ess_out = ess_out;
     const Pick p = select_reverse_hmc_resample(c);
     return report(ck.entry, p, lsnf_launch_small3_reverse_hmc_resample(c, p.st));
+}
+
+// The two HMC entries with a schedule search: the resampling entries' tables and rules, cess_frac and min_step behind ess_out,
+// RowSchedule's rules after RowResample's.
+int lsnf_hmc_step_schedule(const float* plan, int nz, int width, int depth, int coupling, int B, const float* z_prop, const float* z_out,
+                           const float* z_saved, const float* act_saved, const float* ll_prop, const float* grad_g, const float* energy_g,
+                           float* z_acc, float* grad_acc, float* u_acc, float* mom, float* kin0, const float* noise, const float* uniform,
+                           const LsnfRng* rng, float* step_rows, float* adapt, const LsnfDualAvg* da, float* scale_rows, float* mean_rows,
+                           float* m2_rows, float* count_rows, const LsnfMetricReg* reg, float* beta_rows, const float* beta_next,
+                           float* like_grad_acc, float* like_u_acc, float* log_w, unsigned flags, float* z_next, float* accept_out,
+                           float* log_alpha_out, int group, float ess_frac, const float* resample_uniform, float* ancestor_out,
+                           float* ess_out, float cess_frac, float min_step, void* stream) {
+    Check ck{"lsnf_hmc_step_schedule"};
+    const Named reads[] = {{"plan", plan}, {"z_prop", z_prop}, {"z_out", z_out}, {"z_saved", z_saved}, {"act_saved", act_saved},
+                           {"ll_prop", ll_prop}, {"grad_g", grad_g}, {"energy_g", energy_g}, {"noise", noise}, {"uniform", uniform},
+                           {"resample_uniform", resample_uniform}};
+    const Named writes[] = {{"z_acc", z_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc}, {"z_next", z_next}, {"accept_out", accept_out},
+                            {"log_alpha_out", log_alpha_out}, {"mom", mom}, {"kin0", kin0}, {"step_rows", step_rows}, {"adapt", adapt},
+                            {"scale_rows", scale_rows}, {"mean_rows", mean_rows}, {"m2_rows", m2_rows}, {"count_rows", count_rows},
+                            {"beta_rows", beta_rows}, {"beta_next", beta_next}, {"like_grad_acc", like_grad_acc},
+                            {"like_u_acc", like_u_acc}, {"log_w", log_w}, {"ancestor_out", ancestor_out}, {"ess_out", ess_out}};
+    const bool init = (flags & LSNF_HMC_INIT) != 0, inner = (flags & LSNF_HMC_INNER) != 0;
+    const Needed needed[] = {{"plan", plan}, {"z_prop", z_prop}, {"z_out", z_out}, {"act_saved", act_saved}, {"z_acc", z_acc},
+                             {"grad_acc", grad_acc}, {"u_acc", u_acc}, {"mom", mom}, {"kin0", kin0}, {"step_rows", step_rows},
+                             {"scale_rows", scale_rows}, {"beta_rows", beta_rows}, {"like_grad_acc", like_grad_acc},
+                             {"like_u_acc", like_u_acc},
+                             {"ll_prop", ll_prop, !inner, "(NULL) unless LSNF_HMC_INNER"}, {"z_saved", z_saved, depth > 1, "(NULL) for depth > 1"},
+                             {"z_next", z_next, inner, "(NULL) with LSNF_HMC_INNER"}};
+    const ChainStep s = {reads, writes, /*next=*/&writes[3], /*point=*/&reads[1], needed,
+                         LSNF_HMC_INIT | LSNF_HMC_INNER | LSNF_HMC_ADAPT | LSNF_HMC_ADAPT_LAST | LSNF_HMC_METRIC_FOLD | LSNF_HMC_METRIC_CLOSE |
+                             LSNF_HMC_ANNEAL | LSNF_HMC_RESAMPLE | LSNF_HMC_SCHEDULE,
+                         init, inner, "LSNF_HMC_INIT or LSNF_HMC_INNER", plan, act_saved, noise, uniform, rng, /*step_size=*/1.0f, flags};
+    const RowSteps rows = {step_rows, adapt, da, flags};
+    const RowMetric metric = {mean_rows, m2_rows, count_rows, reg, flags};
+    const RowTemper temper = {beta_next, log_w, flags};
+    const RowResample resample = {group, B, resample_uniform, ancestor_out, ess_out, rng, flags};
+    const RowSchedule schedule = {group, B, cess_frac, min_step, flags};
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B) || s.scalars(ck) || s.phases(ck, accept_out, log_alpha_out) || rows.scalars(ck) ||
+        metric.scalars(ck) || temper.scalars(ck) || resample.scalars(ck) || schedule.scalars(ck) || s.aliases(ck))
+        return ck.rc;
+    if (ck.empty) return LSNF_OK;
+    if (s.pointers(ck) || rows.pointers(ck) || metric.pointers(ck) || temper.pointers(ck) || resample.pointers(ck))
+        return ck.rc;
+    const LsnfLangevinArgs lv = {z_prop, grad_g, noise, z_next, nullptr, nullptr, 0.0f, rng_args(rng)};
+    LsnfHmcScheduleCall c;               // (no g_z1 / g_logdet / g_z_in: the gradient of -log p at the point, consumed by the tail)
+    ck.head(c, plan, B, stream, {z_prop, z_out, z_saved, grad_g, noise, z_next, z_acc, grad_acc, mom, scale_rows, mean_rows, m2_rows, like_grad_acc});
+    c.z_out = z_out; c.z_saved = z_saved; c.act_saved = act_saved; c.ll_mode = 1; c.ll_scale = -1.0f; c.lv = &lv; c.ll_prop = ll_prop;
+    c.chain = {energy_g, uniform, z_acc, grad_acc, u_acc, accept_out, log_alpha_out, flags}; c.mom = mom; c.kin0 = kin0;
+    c.step_rows = step_rows; c.adapt = adapt; c.da = rows.args();
+    c.scale = scale_rows; c.mean = mean_rows; c.m2 = m2_rows; c.count = count_rows; c.reg = metric.args();
+    c.beta_rows = beta_rows; c.beta_next = beta_next; c.like_grad_acc = like_grad_acc; c.like_u_acc = like_u_acc; c.log_w = log_w;
+    c.group = group; c.ess_frac = ess_frac; c.resample_uniform = resample_uniform; c.ancestor_out = ancestor_out; c.ess_out = ess_out;
+    c.cess_frac = cess_frac; c.min_step = min_step;
+    const Pick p = select_hmc_schedule(c);
+    return report(ck.entry, p, lsnf_launch_small3_hmc_schedule(c, p.st));
+}
+
+int lsnf_reverse_hmc_step_schedule(const float* plan, int nz, int width, int depth, int coupling, int B, const float* eps_prop,
+                                   const float* z_saved, const float* act_saved, const float* grad_g, const float* energy_g, float* eps_acc,
+                                   float* grad_acc, float* u_acc, float* mom, float* kin0, const float* noise, const float* uniform,
+                                   const LsnfRng* rng, float* step_rows, float* adapt, const LsnfDualAvg* da, float* scale_rows,
+                                   float* mean_rows, float* m2_rows, float* count_rows, const LsnfMetricReg* reg, float* beta_rows,
+                                   const float* beta_next, float* like_grad_acc, float* like_u_acc, float* log_w, unsigned flags,
+                                   float* eps_next, float* accept_out, float* log_alpha_out, int group, float ess_frac,
+                                   const float* resample_uniform, float* ancestor_out, float* ess_out, float cess_frac,
+                                   float min_step, void* stream) {
+    Check ck{"lsnf_reverse_hmc_step_schedule"};
+    const Named reads[] = {{"plan", plan}, {"eps_prop", eps_prop}, {"z_saved", z_saved}, {"act_saved", act_saved}, {"grad_g", grad_g},
+                           {"energy_g", energy_g}, {"noise", noise}, {"uniform", uniform},
+                           {"resample_uniform", resample_uniform}};
+    const Named writes[] = {{"eps_acc", eps_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc}, {"eps_next", eps_next}, {"accept_out", accept_out},
+                            {"log_alpha_out", log_alpha_out}, {"mom", mom}, {"kin0", kin0}, {"step_rows", step_rows}, {"adapt", adapt},
+                            {"scale_rows", scale_rows}, {"mean_rows", mean_rows}, {"m2_rows", m2_rows}, {"count_rows", count_rows},
+                            {"beta_rows", beta_rows}, {"beta_next", beta_next}, {"like_grad_acc", like_grad_acc},
+                            {"like_u_acc", like_u_acc}, {"log_w", log_w}, {"ancestor_out", ancestor_out}, {"ess_out", ess_out}};
+    const bool init = (flags & LSNF_HMC_INIT) != 0, inner = (flags & LSNF_HMC_INNER) != 0;
+    const Needed needed[] = {{"plan", plan}, {"eps_prop", eps_prop}, {"eps_acc", eps_acc}, {"grad_acc", grad_acc}, {"u_acc", u_acc},
+                             {"mom", mom}, {"kin0", kin0}, {"step_rows", step_rows}, {"scale_rows", scale_rows}, {"beta_rows", beta_rows},
+                             {"like_grad_acc", like_grad_acc}, {"like_u_acc", like_u_acc},
+                             {"act_saved", act_saved, true, "(the stash of lsnf_forward, lsnf_restash or lsnf_reverse_keep)"},
+                             {"z_saved", z_saved, depth > 1, "(NULL) for depth > 1"}, {"eps_next", eps_next, inner, "(NULL) with LSNF_HMC_INNER"}};
+    const ChainStep s = {reads, writes, /*next=*/&writes[3], /*point=*/&reads[1], needed,
+                         LSNF_HMC_INIT | LSNF_HMC_INNER | LSNF_HMC_ADAPT | LSNF_HMC_ADAPT_LAST | LSNF_HMC_METRIC_FOLD | LSNF_HMC_METRIC_CLOSE |
+                             LSNF_HMC_ANNEAL | LSNF_HMC_RESAMPLE | LSNF_HMC_SCHEDULE,
+                         init, inner, "LSNF_HMC_INIT or LSNF_HMC_INNER", plan, act_saved, noise, uniform, rng, /*step_size=*/1.0f, flags};
+    const RowSteps rows = {step_rows, adapt, da, flags};
+    const RowMetric metric = {mean_rows, m2_rows, count_rows, reg, flags};
+    const RowTemper temper = {beta_next, log_w, flags};
+    const RowResample resample = {group, B, resample_uniform, ancestor_out, ess_out, rng, flags};
+    const RowSchedule schedule = {group, B, cess_frac, min_step, flags};
+    if (ck.geometry(nz, width, depth, coupling) || ck.batch(B) || s.scalars(ck) || s.phases(ck, accept_out, log_alpha_out) || rows.scalars(ck) ||
+        metric.scalars(ck) || temper.scalars(ck) || resample.scalars(ck) || schedule.scalars(ck) || s.aliases(ck))
+        return ck.rc;
+    if (ck.empty) return LSNF_OK;
+    if (s.pointers(ck) || rows.pointers(ck) || metric.pointers(ck) || temper.pointers(ck) || resample.pointers(ck))
+        return ck.rc;
+    LsnfReverseHmcScheduleCall c;        // (no g_x / g_objective / g_z_in: the gradient at the point is consumed by the tail)
+    ck.head(c, plan, B, stream, {eps_prop, z_saved, grad_g, noise, eps_next, eps_acc, grad_acc, mom, scale_rows, mean_rows, m2_rows, like_grad_acc});
+    c.z_out = eps_prop; c.z_saved = z_saved; c.act_saved = act_saved;
+    c.grad_g = grad_g; c.noise = noise; c.step = 0.0f; c.eps_new = eps_next; c.rng = rng_args(rng);
+    c.chain = {energy_g, uniform, eps_acc, grad_acc, u_acc, accept_out, log_alpha_out, flags}; c.mom = mom; c.kin0 = kin0;
+    c.step_rows = step_rows; c.adapt = adapt; c.da = rows.args();
+    c.scale = scale_rows; c.mean = mean_rows; c.m2 = m2_rows; c.count = count_rows; c.reg = metric.args();
+    c.beta_rows = beta_rows; c.beta_next = beta_next; c.like_grad_acc = like_grad_acc; c.like_u_acc = like_u_acc; c.log_w = log_w;
+    c.group = group; c.ess_frac = ess_frac; c.resample_uniform = resample_uniform; c.ancestor_out = ancestor_out; c.ess_out = ess_out;
+    c.cess_frac = cess_frac; c.min_step = min_step;
+    const Pick p = select_reverse_hmc_schedule(c);
+    return report(ck.entry, p, lsnf_launch_small3_reverse_hmc_schedule(c, p.st));
 }
 
 size_t lsnf_backward_params_workspace_floats(int nz, int width, int depth, int B) {

@@ -1,4 +1,4 @@
-// lsnf_hmc_launch.h -- host: what the launchers of the twelve HMC translation units refuse and how they fill their kernels' arguments,
+// lsnf_hmc_launch.h -- host: what the launchers of the fourteen HMC translation units refuse and how they fill their kernels' arguments,
 // stated once for every level (lsnf_hmc_level.h) and both spaces.
 #pragma once
 #include "lsnf_launch.h"
@@ -27,6 +27,12 @@ static inline bool lsnf_hmc_levels_ok(const C& c, bool rng_on) {
         if ((swap && (!ladder_ok || (f & (1u | 2u | 4u | 16u | 32u | 64u)))) || ((f & 256u) && !swap) ||
             (!swap && (c.swap_uniform || c.swap_out || c.log_swap_out)) ||
             (swap && (rng_on ? c.swap_uniform != nullptr : c.swap_uniform == nullptr)))
+            return false;
+    }
+    if constexpr (F::SCHEDULE) {                                       // (`group` serves SCHEDULE and RESAMPLE)
+        const bool group_ok = (c.group == 2 || c.group == 4 || c.group == 8 || c.group == 16) && c.B % c.group == 0;
+        if ((f & 1024u) && (!group_ok || !anneal || inner || (f & (4u | 16u | 32u)) || !(c.cess_frac > 0.0f && c.cess_frac < 1.0f) ||
+                            !(c.min_step >= 0.0f && c.min_step <= 3.4028234663852886e38f)))
             return false;
     }
     if constexpr (F::RESAMPLE) {
@@ -72,6 +78,7 @@ static inline void lsnf_fill_hmc_levels(A& a, const C& c) {
     if constexpr (F::RESAMPLE) {
         a.group = c.group; a.ess_frac = c.ess_frac; a.resample_uniform = c.resample_uniform; a.ancestor_out = c.ancestor_out; a.ess_out = c.ess_out;
     }
+    if constexpr (F::SCHEDULE) { a.cess_frac = c.cess_frac; a.min_step = c.min_step; }
 }
 // z space: Small3HmcArgs or what derives from it
 template <class F, class A, class C>

@@ -1,5 +1,5 @@
 // lsnf_hmc_tail.h -- device: the leapfrog tail of Hamiltonian Monte Carlo in z (lsnf_hmc_step and its levels, include/lsnf_flow_mcmc.h):
-// the output section that lsnf_small3_hmc.hip / _hmcm / _hmct / _hmcx / _hmcs give the latency bf16x3 backward
+// the output section that lsnf_small3_hmc.hip / _hmcm / _hmct / _hmcx / _hmcs / _hmca give the latency bf16x3 backward
 // (lsnf_small3_bwd_kernel.h), one translation unit and one kernel name per level F (lsnf_hmc_level.h), so that no other kernel's text
 // changes with a level.  (lsnf_small3_hmcr.hip, the per-row level in z, keeps a tail of its own: from this one its kernels were 1 - 2 %
 // slower at 100 rows, profiles/hmc_one_tail_ab.txt.  The ROWS switches below serve the levels above it.)
@@ -20,8 +20,8 @@
 //
 // Each level's products are one rounded product each, formed first (sd * g, sd * ph, beta * gl, beta * el), and 1.0f * x is x: with
 // sd == 1 a METRIC row's outputs are the ROWS level's bit for bit, with beta == 1 and without ANNEAL a TEMPER row's the METRIC level's,
-// without its move an EXCHANGE or RESAMPLE row's the TEMPER level's, and without ADAPT a ROWS row's the scalar level's at step_size =
-// step_rows[row].
+// without its move an EXCHANGE or RESAMPLE row's the TEMPER level's, without its search a SCHEDULE row's the RESAMPLE level's, and
+// without ADAPT a ROWS row's the scalar level's at step_size = step_rows[row].
 #pragma once
 #include "lsnf_small3.h"
 #include "lsnf_dual_avg.h"
@@ -29,6 +29,7 @@
 #include "lsnf_temper.h"
 #include "lsnf_exchange.h"
 #include "lsnf_resample.h"
+#include "lsnf_schedule.h"
 #include "lsnf_hmc_level.h"
 
 namespace {
@@ -44,6 +45,7 @@ __device__ __forceinline__ void small3_hmc_tail(const A& a, f32x4 (&gx1)[ST], f3
     const bool init = (a.flags & 1u) != 0, inner = (a.flags & 2u) != 0, adapt = F::ROWS && (a.flags & 4u) != 0;
     const bool fold = F::METRIC && (a.flags & 16u) != 0, close = F::METRIC && (a.flags & 32u) != 0, anneal = F::TEMPER && (a.flags & 64u) != 0;
     const bool swap = F::EXCHANGE && (a.flags & 128u) != 0, resample = F::RESAMPLE && (a.flags & 512u) != 0;
+    const bool schedule = F::SCHEDULE && (a.flags & 1024u) != 0;      // (SCHEDULE: INIT and end calls with ANNEAL, without ADAPT / FOLD / CLOSE)
     // A move's other row is a tile row of the same ladder / group, i.e. a lane of the same wave and column group: its scalars and
     // quads come over by ds_bpermute (lsnf_exchange.h).  A ladder or group is live or not as a whole since B % its length == 0; a
     // dead lane's registers are zeros that only dead lanes receive.
@@ -210,6 +212,12 @@ __device__ __forceinline__ void small3_hmc_tail(const A& a, f32x4 (&gx1)[ST], f3
                 hn = 0.5f * sn;
                 if (close && !(a.flags & 8u)) ad[st] = f32x4{0.f, 0.f, 0.f, logf(10.0f * sn)};      // the window's end restarts the averaging
             }
+        }
+        // SCHEDULE: the group's next temperature (lsnf_schedule.h) from its rows' log weights before the increment and el_s of their
+        // states after the decision, in the place of beta_next, which is its ceiling: the same value on every row of the group and on
+        // every wave.  The ANNEAL lines and the resampling move below read it as they read beta_next.  The whole wave is active here.
+        if constexpr (F::SCHEDULE) {
+            if (schedule) bn[st] = lsnf_schedule_next(bt[st], bn[st], lw[st] - lc[st], acc ? el[st] : el_old[st], a.group, a.cess_frac, a.min_step, xlane);
         }
         float nf = 0.0f, d = 0.0f;
         if constexpr (F::METRIC) nf = cnt[st] + 1.0f;                  // the row's count after the fold

@@ -85,6 +85,10 @@ struct LsnfHmcResampleCall : LsnfHmcTemperedCall {      // lsnf_hmc_step_resampl
     const float* resample_uniform = nullptr;   // the groups' uniforms (B), read at the group's first row; NULL: drawn in-kernel
     float* ancestor_out = nullptr; float* ess_out = nullptr;       // optional (B each)
 };
+struct LsnfHmcScheduleCall : LsnfHmcResampleCall {      // lsnf_hmc_step_schedule; flags: LsnfHmcResampleCall's with SCHEDULE
+    float cess_frac = 0.0f;              // a searching group steps to where its conditional effective sample size is cess_frac * P
+    float min_step = 0.0f;               // and by no less than this (`group` is the length for SCHEDULE and RESAMPLE alike)
+};
 struct LsnfReverseBackwardCall : LsnfCall {      // lsnf_reverse_backward_z
     const float* z_out = nullptr; const float* z_saved = nullptr; const float* act_saved = nullptr;
     const float* g_x = nullptr; const float* g_objective = nullptr;
@@ -119,6 +123,9 @@ struct LsnfReverseHmcExchangeCall : LsnfReverseHmcTemperedCall {      // lsnf_re
 };
 struct LsnfReverseHmcResampleCall : LsnfReverseHmcTemperedCall {      // lsnf_reverse_hmc_step_resample: as LsnfHmcResampleCall
     int group = 0; float ess_frac = 0.0f; const float* resample_uniform = nullptr; float* ancestor_out = nullptr; float* ess_out = nullptr;
+};
+struct LsnfReverseHmcScheduleCall : LsnfReverseHmcResampleCall {      // lsnf_reverse_hmc_step_schedule: as LsnfHmcScheduleCall
+    float cess_frac = 0.0f; float min_step = 0.0f;
 };
 struct LsnfContractCall : LsnfCall {     // steps (2), (3) of lsnf_backward_params: batch contraction of the dump, chain rule
     const float* const* params_host = nullptr; float* const* grads_host = nullptr;
@@ -196,6 +203,7 @@ hipError_t lsnf_launch_small3_hmc_metric(const LsnfHmcMetricCall& c, int st);   
 hipError_t lsnf_launch_small3_hmc_tempered(const LsnfHmcTemperedCall& c, int st);   // st: lsnf_small3_backward_st of the call
 hipError_t lsnf_launch_small3_hmc_exchange(const LsnfHmcExchangeCall& c, int st);   // st: lsnf_small3_backward_st of the call
 hipError_t lsnf_launch_small3_hmc_resample(const LsnfHmcResampleCall& c, int st);   // st: lsnf_small3_backward_st of the call
+hipError_t lsnf_launch_small3_hmc_schedule(const LsnfHmcScheduleCall& c, int st);   // st: lsnf_small3_backward_st of the call
 int lsnf_small3_reverse_backward_st(const LsnfReverseBackwardCall& c);
 hipError_t lsnf_launch_small3_reverse_backward_z(const LsnfReverseBackwardCall& c, int st);
 hipError_t lsnf_launch_small3_reverse_langevin(const LsnfReverseLangevinCall& c, int st);      // st: of the same predicate
@@ -206,6 +214,7 @@ hipError_t lsnf_launch_small3_reverse_hmc_metric(const LsnfReverseHmcMetricCall&
 hipError_t lsnf_launch_small3_reverse_hmc_tempered(const LsnfReverseHmcTemperedCall& c, int st);   // st: of the same predicate
 hipError_t lsnf_launch_small3_reverse_hmc_exchange(const LsnfReverseHmcExchangeCall& c, int st);   // st: of the same predicate
 hipError_t lsnf_launch_small3_reverse_hmc_resample(const LsnfReverseHmcResampleCall& c, int st);   // st: of the same predicate
+hipError_t lsnf_launch_small3_reverse_hmc_schedule(const LsnfReverseHmcScheduleCall& c, int st);   // st: of the same predicate
 
 bool lsnf_contract_x3_covers(const LsnfContractCall& c);                   // (also asked with NULL tensors: lsnf_api.hip dump_may_tile)
 hipError_t lsnf_launch_contract_x3(const LsnfContractCall& c, int chunk_override);

@@ -1,5 +1,5 @@
 // lsnf_rhmc_tail.h -- device: the leapfrog tail of Hamiltonian Monte Carlo in the flow's base space (lsnf_reverse_hmc_step and its
-// levels, include/lsnf_flow_mcmc.h): the output section that lsnf_small3_rhmc.hip / _rhmcr / _rhmcm / _rhmct / _rhmcx / _rhmcs give the
+// levels, include/lsnf_flow_mcmc.h): the output section that lsnf_small3_rhmc.hip / _rhmcr / _rhmcm / _rhmct / _rhmcx / _rhmcs / _rhmca give the
 // latency bf16x3 reverse-backward (lsnf_small3_rbwd_kernel.h), one translation unit and one kernel name per level F
 // (lsnf_hmc_level.h), so that no other kernel's text changes with a level.  The levels are lsnf_hmc_tail.h's and what is said there
 // about a level's flags, its row scalars, its re-reads in phase 2 and its move holds here; the two tails stay apart because the spaces
@@ -31,6 +31,7 @@
 #include "lsnf_temper.h"
 #include "lsnf_exchange.h"
 #include "lsnf_resample.h"
+#include "lsnf_schedule.h"
 #include "lsnf_hmc_level.h"
 
 namespace {
@@ -45,6 +46,7 @@ __device__ __forceinline__ void small3_rhmc_tail(const A& a, f32x4 (&g1)[ST], f3
     const bool init = (a.flags & 1u) != 0, inner = (a.flags & 2u) != 0, adapt = F::ROWS && (a.flags & 4u) != 0;      // kernel-uniform
     const bool fold = F::METRIC && (a.flags & 16u) != 0, close = F::METRIC && (a.flags & 32u) != 0, anneal = F::TEMPER && (a.flags & 64u) != 0;
     const bool swap = F::EXCHANGE && (a.flags & 128u) != 0, resample = F::RESAMPLE && (a.flags & 512u) != 0;
+    const bool schedule = F::SCHEDULE && (a.flags & 1024u) != 0;      // (SCHEDULE: INIT and end calls with ANNEAL, without ADAPT / FOLD / CLOSE)
     int xlane = 0, pl = 0, rk = 0, P = 1;                              // (the lanes of a move: lsnf_hmc_tail.h)
     bool paired = false, lower = false;
     if constexpr (MOVE) xlane = lsnf_exchange_lane();
@@ -197,6 +199,12 @@ __device__ __forceinline__ void small3_rhmc_tail(const A& a, f32x4 (&g1)[ST], f3
                 hn = 0.5f * sn;
                 if (close && !(a.flags & 8u)) ad[st] = f32x4{0.f, 0.f, 0.f, logf(10.0f * sn)};      // the window's end restarts the averaging
             }
+        }
+        // SCHEDULE: the group's next temperature (lsnf_schedule.h) from its rows' log weights before the increment and el_s of their
+        // states after the decision, in the place of beta_next, which is its ceiling: the same value on every row of the group and on
+        // every wave.  The ANNEAL lines and the resampling move below read it as they read beta_next.  The whole wave is active here.
+        if constexpr (F::SCHEDULE) {
+            if (schedule) bn[st] = lsnf_schedule_next(bt[st], bn[st], lw[st] - lc[st], acc ? en_g[st] : el_old[st], a.group, a.cess_frac, a.min_step, xlane);
         }
         float nf = 0.0f, d = 0.0f;
         if constexpr (F::METRIC) nf = cnt[st] + 1.0f;                  // the row's count after the fold

@@ -10,7 +10,8 @@
 // (lsnf_small3_hmcm_kernel, Small3HmcMetricArgs, the per-row leapfrog tail with a diagonal metric and `return;`), lsnf_small3_hmct.hip a
 // sixth (lsnf_small3_hmct_kernel, Small3HmcTemperedArgs, that tail with a likelihood temperature per row and `return;`),
 // lsnf_small3_hmcx.hip a seventh (lsnf_small3_hmcx_kernel, Small3HmcExchangeArgs, that tail with a replica-exchange move and `return;`),
-// lsnf_small3_hmcs.hip an eighth (lsnf_small3_hmcs_kernel, Small3HmcResampleArgs, that tail with a resampling move and `return;`).
+// lsnf_small3_hmcs.hip an eighth (lsnf_small3_hmcs_kernel, Small3HmcResampleArgs, that tail with a resampling move and `return;`),
+// lsnf_small3_hmca.hip a ninth (lsnf_small3_hmca_kernel, Small3HmcScheduleArgs, that tail with the schedule search and `return;`).
 #pragma once
 
 namespace {
@@ -90,6 +91,11 @@ struct Small3HmcExchangeArgs : Small3HmcTemperedArgs {
 // outputs of the move (B each)
 struct Small3HmcResampleArgs : Small3HmcTemperedArgs {
     int group; float ess_frac; const float* resample_uniform; float* ancestor_out; float* ess_out;
+};
+// scheduling HMC form (lsnf_small3_hmca.hip): the resampling form's arrays and, with LSNF_HMC_SCHEDULE (1024), the target of the
+// conditional effective sample size as a fraction and the least step of a group that searches (`group` serves both moves)
+struct Small3HmcScheduleArgs : Small3HmcResampleArgs {
+    float cess_frac, min_step;
 };
 
 __device__ __forceinline__ f32x4 mask4(f32x4 a, unsigned nib) {

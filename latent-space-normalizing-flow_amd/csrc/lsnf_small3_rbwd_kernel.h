@@ -12,7 +12,8 @@
 // lsnf_small3_rhmcm.hip that one with a diagonal metric per row (lsnf_small3_rhmcm_kernel, Small3RhmcMetricArgs), lsnf_small3_rhmct.hip
 // that one with a likelihood temperature per row (lsnf_small3_rhmct_kernel, Small3RhmcTemperedArgs), lsnf_small3_rhmcx.hip that one
 // with a replica-exchange move between rows (lsnf_small3_rhmcx_kernel, Small3RhmcExchangeArgs), lsnf_small3_rhmcs.hip the tempered one
-// with a resampling move between rows (lsnf_small3_rhmcs_kernel, Small3RhmcResampleArgs).
+// with a resampling move between rows (lsnf_small3_rhmcs_kernel, Small3RhmcResampleArgs), lsnf_small3_rhmca.hip that one with the
+// schedule search (lsnf_small3_rhmca_kernel, Small3RhmcScheduleArgs).
 #pragma once
 
 namespace {
@@ -96,6 +97,11 @@ struct Small3RhmcExchangeArgs : Small3RhmcTemperedArgs {
 // in-kernel) and the move's two optional outputs
 struct Small3RhmcResampleArgs : Small3RhmcTemperedArgs {
     int group; float ess_frac; const float* resample_uniform; float* ancestor_out; float* ess_out;
+};
+// scheduling HMC form (lsnf_reverse_hmc_step_schedule, lsnf_small3_rhmca.hip): the resampling form's tensors and, with
+// LSNF_HMC_SCHEDULE (1024), the target of the conditional effective sample size as a fraction and the least step of a searching group
+struct Small3RhmcScheduleArgs : Small3RhmcResampleArgs {
+    float cess_frac, min_step;
 };
 
 __device__ __forceinline__ f32x4 rb_mask4(f32x4 a, unsigned nib) {

@@ -892,3 +892,4 @@ from .mcmc import (HMC_METRIC_CLOSE, HMC_METRIC_FOLD, HmcRowMetric, new_hmc_row_
 from .mcmc import HMC_ANNEAL, HmcRowTemper, new_hmc_row_temper, hmc_step_tempered, reverse_hmc_step_tempered  # noqa: E402,F401
 from .mcmc import HMC_SWAP, HMC_SWAP_ODD, hmc_step_exchange, reverse_hmc_step_exchange  # noqa: E402,F401
 from .mcmc import HMC_RESAMPLE, hmc_step_resample, reverse_hmc_step_resample  # noqa: E402,F401
+from .mcmc import HMC_SCHEDULE, hmc_step_schedule, reverse_hmc_step_schedule  # noqa: E402,F401

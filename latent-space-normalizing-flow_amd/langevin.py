@@ -17,6 +17,7 @@ MIOpen, is out of scope of this build and used as is); its z-gradient comes from
 reference, the flow's comes from `lsnf_langevin_step` (two launches per step instead of ~750 eager kernels)."""
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import torch
@@ -543,20 +544,27 @@ def ais_schedule(T: int, kind: str = "sigmoid", delta: float = 4.0) -> torch.Ten
     return b
 
 
-def _ais_plan(flow, betas, chains, leapfrog_steps, steps, metric, adapt):
-    """(betas as a float64 (T + 1) tensor, T, chains, L) of an AIS run, checked."""
-    betas = torch.as_tensor(betas, dtype=torch.float64).reshape(-1).cpu()
-    T, C, L = betas.numel() - 1, int(chains), int(leapfrog_steps)
+def _chains_plan(flow, chains, leapfrog_steps, steps, metric):
+    """(chains, L) of a run of annealed chains, checked, with its frozen steps and metric."""
+    C, L = int(chains), int(leapfrog_steps)
     if L < 1:
         raise ValueError(f"leapfrog_steps must be >= 1 (got {leapfrog_steps})")
     if C < 1:
         raise ValueError(f"chains must be >= 1 (got {chains})")
-    if T >= 1 and (float(betas[0]) != 0.0 or bool((betas[1:] < betas[:-1]).any())):
-        raise ValueError("betas must start at 0 (the chains start from draws of the prior) and must not decrease")
     if steps is not None and not isinstance(steps, flow.HmcRowSteps):
         raise flow.LsnfError("steps must be a flow.HmcRowSteps (new_hmc_row_steps()), or None")
     if metric is not None and not isinstance(metric, flow.HmcRowMetric):
         raise flow.LsnfError("metric must be a flow.HmcRowMetric (new_hmc_row_metric()), or None")
+    return C, L
+
+
+def _ais_plan(flow, betas, chains, leapfrog_steps, steps, metric, adapt):
+    """(betas as a float64 (T + 1) tensor, T, chains, L) of an AIS run, checked."""
+    betas = torch.as_tensor(betas, dtype=torch.float64).reshape(-1).cpu()
+    T = betas.numel() - 1
+    C, L = _chains_plan(flow, chains, leapfrog_steps, steps, metric)
+    if T >= 1 and (float(betas[0]) != 0.0 or bool((betas[1:] < betas[:-1]).any())):
+        raise ValueError("betas must start at 0 (the chains start from draws of the prior) and must not decrease")
     return betas, T, C, L
 
 
@@ -696,13 +704,18 @@ estimate_log_px_ais_z_with_flow.__doc__ += _AIS_DOC
 estimate_log_px_ais_eps_with_flow.__doc__ += _AIS_DOC
 
 
-def _smc_plan(flow, betas, chains, particles, leapfrog_steps, steps, metric):
-    """`_ais_plan`'s checks and the groups' geometry: particles is 2, 4, 8 or 16 and divides chains."""
-    betas, T, C, L = _ais_plan(flow, betas, chains, leapfrog_steps, steps, metric, False)
+def _particles_plan(chains, particles):
+    """The groups' geometry: particles is 2, 4, 8 or 16 and divides chains."""
     P = int(particles)
-    if P not in (2, 4, 8, 16) or C % P:
-        raise ValueError(f"particles must be 2, 4, 8 or 16 and divide chains={C} (got {particles})")
-    return betas, T, C, L, P
+    if P not in (2, 4, 8, 16) or chains % P:
+        raise ValueError(f"particles must be 2, 4, 8 or 16 and divide chains={chains} (got {particles})")
+    return P
+
+
+def _smc_plan(flow, betas, chains, particles, leapfrog_steps, steps, metric):
+    """`_ais_plan`'s checks and the groups' geometry."""
+    betas, T, C, L = _ais_plan(flow, betas, chains, leapfrog_steps, steps, metric, False)
+    return betas, T, C, L, _particles_plan(C, particles)
 
 
 _SMC_DOC = """
@@ -827,6 +840,185 @@ def estimate_log_px_smc_eps_with_flow(x, netG: nn.Module, netF, *, betas, chains
 
 estimate_log_px_smc_z_with_flow.__doc__ += _SMC_DOC
 estimate_log_px_smc_eps_with_flow.__doc__ += _SMC_DOC
+
+
+_SMC_ADAPTIVE_DOC = """
+    The loop, the draws and the Philox offsets are `estimate_log_px_smc_*_with_flow`'s with max_steps in the place of T and no
+    schedule from the host: every launch is the scheduling call.  The init call and every end call t < max_steps - 1 carry
+    schedule=particles with a ceiling of 1: inside the kernel each group of `particles` consecutive chains of a datum steps to the
+    temperature at which the conditional effective sample size (CESS) of its incremental weights is cess_target * particles (twelve
+    halvings; Zhou, Johansen & Aston 2016), by at least min_step (None: 1 / (4 max_steps)).  End calls t < max_steps carry
+    resample=particles as the fixed-schedule sampler's do (ess_threshold <= 0: never -- adaptive AIS within groups).  The end call
+    that anneals into the last transition carries no schedule: it goes to beta = 1 in one plain step, so a group that has not arrived
+    by then still gets a valid estimate.  A group that has reached 1 goes on with plain HMC at beta = 1; its increments are zero.
+    check_every = k > 0 reads beta.min() after every k-th end call and, once every group is at 1, makes the next transition the last
+    one: the only host synchronisation; the default of 0 has none and runs all max_steps transitions.  philox is advanced by the
+    transitions run + 1.
+    The temperatures now depend on the particles, so the estimate is consistent in the number of particles but no longer exactly
+    unbiased (Beskos, Jasra, Kantas & Thiery 2016); the fixed-schedule samplers stay the unbiased ones.
+    Returns the SMC tuple -- the AIS six and `resampled`, (N, chains / particles) float32: at how many of its resampling end calls each
+    group resampled -- plus `steps_used`, (N, chains / particles) float32: the annealing calls each group entered below beta = 1; both
+    accumulated on the device; with return_schedule also `schedule`, (annealing calls, N, chains / particles) float32: every group's
+    beta after every annealing call."""
+
+
+def _smc_adaptive_plan(flow, max_steps, chains, particles, leapfrog_steps, steps, metric, cess_target, min_step, check_every):
+    """`_smc_plan`'s checks with max_steps in the place of the schedule, and the search's scalars."""
+    K = int(max_steps)
+    if K < 0:
+        raise ValueError(f"max_steps must not be negative (got {max_steps})")
+    C, L = _chains_plan(flow, chains, leapfrog_steps, steps, metric)
+    P = _particles_plan(C, particles)
+    if not 0.0 < float(cess_target) < 1.0:
+        raise ValueError(f"cess_target must lie in (0, 1) (got {cess_target})")
+    ms = 1.0 / (4.0 * max(K, 1)) if min_step is None else float(min_step)
+    if not (math.isfinite(ms) and ms >= 0.0):
+        raise ValueError(f"min_step must be finite and not negative (got {min_step})")
+    if int(check_every) < 0:
+        raise ValueError(f"check_every must not be negative (got {check_every})")
+    return K, C, L, P, ms, int(check_every)
+
+
+def estimate_log_px_smc_adaptive_z_with_flow(x, netG: nn.Module, netF, *, max_steps: int, chains: int, particles: int, leapfrog_steps: int,
+                                             g_l_step_size, g_llhd_sigma: float, philox, cess_target: float = 0.95,
+                                             ess_threshold: float = 0.5, min_step=None, check_every: int = 0, steps=None, metric=None,
+                                             return_schedule: bool = False):
+    """`estimate_log_px_smc_z_with_flow` without a temperature schedule: every group's next temperature is chosen from its particles
+    inside the annealing call (`netF.hmc_step_schedule`), so that data whose likelihood is sharp take many small steps and data whose
+    likelihood is flat few."""
+    from . import flow
+    T, C, L, P, ms, every = _smc_adaptive_plan(flow, max_steps, chains, particles, leapfrog_steps, steps, metric, cess_target, min_step,
+                                               check_every)
+    N, extra = x.shape[0], (None,) if return_schedule else ()
+    if T < 1:
+        return (None,) * 8 + extra
+    if N == 0:
+        e = torch.zeros(0, dtype=torch.float64, device=x.device)
+        return (e, e.view(0, C), e.clone(), None, None, None, None, None) + extra
+    B, D, plan = N * C, x[0].numel(), netF._plan()
+    c = 1.0 / (2.0 * g_llhd_sigma * g_llhd_sigma)
+    xs = x.detach().repeat_interleave(C, dim=0)
+    z0 = netF.sample(B, philox.step(0), return_eps=True)[0]
+    nz = z0.shape[1]
+    z_prop = z0.detach().reshape(B, nz).contiguous()
+    dev = z_prop.device
+    ceiling = torch.ones(B, dtype=torch.float32, device=dev)
+    steps = _row_steps(flow, steps, B, dev, g_l_step_size, 0.8)
+    metric = flow.new_hmc_row_metric(plan, B, dev) if metric is None else metric
+    temper = flow.new_hmc_row_temper(plan, B, dev, 0.0)
+    state = flow.new_hmc_state(plan, B, dev)
+    accepted = torch.zeros(B, dtype=torch.float32, device=dev)
+    steps_used = torch.zeros(N, C // P, dtype=torch.float32, device=dev)
+    resampled = torch.zeros(N, C // P, dtype=torch.float32, device=dev)
+    edge = torch.tensor(float(ess_threshold), dtype=torch.float32, device=dev) * P
+    trace = []
+    j = 0
+    while j < T * L + 1:
+        zr = z_prop.view(B, nz, 1, 1).detach().requires_grad_(True)
+        energy = c * ((netG(zr) - xs) ** 2).flatten(1).sum(1)                                # train.py:312-313, per row
+        grad_g = torch.autograd.grad(energy.sum(), zr)[0].reshape(B, nz).contiguous()        # train.py:314
+        t, inner = j // L, j % L != 0
+        end = bool(j) and not inner
+        anneals = not inner and t < T
+        if anneals:
+            steps_used += (temper.beta.view(N, C // P, P)[:, :, 0] < 1.0).float()
+        _, acc, _, _, _, ess = netF.hmc_step_schedule(z_prop, grad_g, energy.detach(), state, None if inner else philox.step(t + 1), steps,
+                                                    metric, temper, phase="inner" if inner else "end" if j else "init",
+                                                    propose=j < T * L, inplace=True, reuse_buffers=True,
+                                                    anneal=ceiling if anneals else None, resample=P if end and t < T else None,
+                                                    ess_threshold=ess_threshold, schedule=P if anneals and t < T - 1 else None,
+                                                    cess_target=cess_target, min_step=ms)
+        if end:
+            accepted += acc
+        if end and t < T:
+            resampled += (ess.view(N, C // P, P)[:, :, 0] < edge).float()
+        if anneals and return_schedule:
+            trace.append(temper.beta.view(N, C // P, P)[:, :, 0].clone())
+        if every and end and t % every == 0 and t + 1 < T and float(temper.beta.min()) >= 1.0:
+            T = t + 1                                         # (every weight is final: the next transition is the last)
+        j += 1
+    philox.advance(T + 1)
+    log_px, log_w, ess = _ais_reduce(temper, N, C, D, float(g_llhd_sigma))
+    out = (log_px, log_w, ess, accepted / T, state.z.view(B, nz, 1, 1), temper, resampled, steps_used)
+    return out + ((torch.stack(trace),) if return_schedule else ())
+
+
+def estimate_log_px_smc_adaptive_eps_with_flow(x, netG: nn.Module, netF, *, max_steps: int, chains: int, particles: int,
+                                               leapfrog_steps: int, g_l_step_size, g_llhd_sigma: float, philox, cess_target: float = 0.95,
+                                               ess_threshold: float = 0.5, min_step=None, check_every: int = 0, steps=None, metric=None,
+                                               return_schedule: bool = False):
+    """`estimate_log_px_smc_adaptive_z_with_flow` with the transitions in the flow's base space (`netF.reverse_hmc_step_schedule`): the
+    chain runs on eps with z = f^-1(eps), and the flow's side of a transition is the reverse and ONE more launch.  z_T = f^-1(eps_T)."""
+    from . import flow
+    T, C, L, P, ms, every = _smc_adaptive_plan(flow, max_steps, chains, particles, leapfrog_steps, steps, metric, cess_target, min_step,
+                                               check_every)
+    N, extra = x.shape[0], (None,) if return_schedule else ()
+    if T < 1:
+        return (None,) * 8 + extra
+    if N == 0:
+        e = torch.zeros(0, dtype=torch.float64, device=x.device)
+        return (e, e.view(0, C), e.clone(), None, None, None, None, None) + extra
+    B, D, plan = N * C, x[0].numel(), netF._plan()
+    c = 1.0 / (2.0 * g_llhd_sigma * g_llhd_sigma)
+    xs = x.detach().repeat_interleave(C, dim=0)
+    eps0 = netF.sample(B, philox.step(0), return_eps=True)[1]
+    nz = eps0.shape[1]
+    eps_prop = eps0.detach().reshape(B, nz).contiguous()
+    dev = eps_prop.device
+    ceiling = torch.ones(B, dtype=torch.float32, device=dev)
+    steps = _row_steps(flow, steps, B, dev, g_l_step_size, 0.8)
+    metric = flow.new_hmc_row_metric(plan, B, dev) if metric is None else metric
+    temper = flow.new_hmc_row_temper(plan, B, dev, 0.0)
+    keeps = flow.reverse_keep_supported(plan, B)
+    act = flow.new_act_saved(plan, B, dev)
+    state = flow.new_hmc_state(plan, B, dev)
+    accepted = torch.zeros(B, dtype=torch.float32, device=dev)
+    steps_used = torch.zeros(N, C // P, dtype=torch.float32, device=dev)
+    resampled = torch.zeros(N, C // P, dtype=torch.float32, device=dev)
+    edge = torch.tensor(float(ess_threshold), dtype=torch.float32, device=dev) * P
+    trace = []
+    with torch.no_grad():
+        j = 0
+        while j < T * L + 1:
+            if keeps:
+                z, _, saved = flow.reverse(plan, eps_prop, None, save_for_backward=True, act_saved=act)
+            else:
+                z, _ = flow.reverse(plan, eps_prop, None)
+                saved = flow.forward(plan, z, None, want_ll=False, save_for_backward=True, act_saved=act)[3]
+            with torch.enable_grad():
+                zr = z.view(B, nz, 1, 1).requires_grad_(True)
+                energy = c * ((netG(zr) - xs) ** 2).flatten(1).sum(1)                                # train.py:312-313, per row
+                grad_g = torch.autograd.grad(energy.sum(), zr)[0].reshape(B, nz).contiguous()        # train.py:314
+            t, inner = j // L, j % L != 0
+            end = bool(j) and not inner
+            anneals = not inner and t < T
+            if anneals:
+                steps_used += (temper.beta.view(N, C // P, P)[:, :, 0] < 1.0).float()
+            _, acc, _, _, ess = netF.reverse_hmc_step_schedule(eps_prop, saved, act, grad_g, energy.detach(), state,
+                                                             None if inner else philox.step(t + 1), steps, metric, temper,
+                                                             phase="inner" if inner else "end" if j else "init", propose=j < T * L,
+                                                             inplace=True, reuse_buffers=True, anneal=ceiling if anneals else None,
+                                                             resample=P if end and t < T else None, ess_threshold=ess_threshold,
+                                                             schedule=P if anneals and t < T - 1 else None, cess_target=cess_target,
+                                                             min_step=ms)
+            if end:
+                accepted += acc
+            if end and t < T:
+                resampled += (ess.view(N, C // P, P)[:, :, 0] < edge).float()
+            if anneals and return_schedule:
+                trace.append(temper.beta.view(N, C // P, P)[:, :, 0].clone())
+            if every and end and t % every == 0 and t + 1 < T and float(temper.beta.min()) >= 1.0:
+                T = t + 1                                     # (every weight is final: the next transition is the last)
+            j += 1
+        z = flow.reverse(plan, state.z, None)[0]
+    philox.advance(T + 1)
+    log_px, log_w, ess = _ais_reduce(temper, N, C, D, float(g_llhd_sigma))
+    out = (log_px, log_w, ess, accepted / T, z.view(B, nz, 1, 1), temper, resampled, steps_used)
+    return out + ((torch.stack(trace),) if return_schedule else ())
+
+
+estimate_log_px_smc_adaptive_z_with_flow.__doc__ += _SMC_ADAPTIVE_DOC
+estimate_log_px_smc_adaptive_eps_with_flow.__doc__ += _SMC_ADAPTIVE_DOC
 
 
 def pt_ladder(R: int, beta_min: float) -> torch.Tensor:

@@ -3,7 +3,8 @@
 `flow.HmcState`, `flow.new_hmc_state`, `flow.hmc_step_rows`, `flow.reverse_hmc_step_rows`, `flow.HmcRowSteps`,
 `flow.new_hmc_row_steps`, `flow.hmc_step_metric`, `flow.reverse_hmc_step_metric`, `flow.HmcRowMetric`, `flow.new_hmc_row_metric`,
 `flow.hmc_step_tempered`, `flow.reverse_hmc_step_tempered`, `flow.HmcRowTemper`, `flow.new_hmc_row_temper`,
-`flow.hmc_step_exchange`, `flow.reverse_hmc_step_exchange`, `flow.hmc_step_resample`, `flow.reverse_hmc_step_resample`.
+`flow.hmc_step_exchange`, `flow.reverse_hmc_step_exchange`, `flow.hmc_step_resample`, `flow.reverse_hmc_step_resample`,
+`flow.hmc_step_schedule`, `flow.reverse_hmc_step_schedule`.
 Every tensor goes through flow.py's one checking path before anything is launched; like there, all functions raise on CPU tensors:
 there is no CPU path."""
 from __future__ import annotations
@@ -12,6 +13,7 @@ from dataclasses import dataclass, fields
 from typing import Optional
 
 import ctypes
+import math
 
 import torch
 
@@ -698,31 +700,49 @@ def reverse_hmc_step_exchange(plan: FlowPlan, eps_prop: torch.Tensor, z_saved: O
 
 
 HMC_RESAMPLE = 512     # include/lsnf_flow_mcmc.h LSNF_HMC_RESAMPLE
+HMC_SCHEDULE = 1024    # include/lsnf_flow_mcmc.h LSNF_HMC_SCHEDULE
 
 
-def _row_resample_mode(resample, phase, adapt, window, anneal):
-    """What the resampling calls check before `_check_chain`, beside `_row_temper_mode`: resample is None or the group's length P;
-    a resampling call is an annealing end call that neither adapts, folds nor closes, and P is 2, 4, 8 or 16.  Returns the move's
-    flag."""
+def _row_resample_mode(resample, phase, adapt, window, anneal, schedule=None, cess_target=0.95, min_step=0.0):
+    """What the resampling and the scheduling calls check before `_check_chain`, beside `_row_temper_mode`: resample is None or the
+    group's length P; a resampling call is an annealing end call that neither adapts, folds nor closes, and P is 2, 4, 8 or 16.
+    schedule (the scheduling calls only) is None or the group's length as well: a scheduling call is an annealing init or end call
+    that neither adapts, folds nor closes; with resample both lengths are equal.  Returns the moves' flags."""
+    flags = 0
+    if schedule is not None:
+        if schedule not in (2, 4, 8, 16):
+            raise LsnfError(f"schedule must be None, 2, 4, 8 or 16 (got {schedule!r})")
+        if phase == "inner" or adapt is not None or window is not None or anneal is None:
+            raise LsnfError("the next temperature is searched where a frozen chain anneals: schedule goes with phase='init' or 'end' "
+                            "and anneal= (the ceiling), without adapt and window")
+        if resample is not None and resample != schedule:
+            raise LsnfError(f"schedule={schedule!r} and resample={resample!r} name the same groups: they must be equal")
+        if not 0.0 < float(cess_target) < 1.0:
+            raise LsnfError(f"cess_target must lie in (0, 1) (got {cess_target!r})")
+        if not (math.isfinite(float(min_step)) and float(min_step) >= 0.0):
+            raise LsnfError(f"min_step must be finite and not negative (got {min_step!r})")
+        flags |= HMC_SCHEDULE
     if resample is None:
-        return 0
+        return flags
     if resample not in (2, 4, 8, 16):
         raise LsnfError(f"resample must be None, 2, 4, 8 or 16 (got {resample!r})")
     if phase != "end" or adapt is not None or window is not None or anneal is None:
         raise LsnfError("particles are resampled between the weight increment and the next trajectory of a frozen chain: resample "
                         "goes with phase='end' and anneal=, without adapt and window")
-    return HMC_RESAMPLE
+    return flags | HMC_RESAMPLE
 
 
-def _row_resample_args(plan, resample, ess_threshold, resample_uniform, rng, B, dev, reuse_buffers):
+def _row_resample_args(plan, resample, ess_threshold, resample_uniform, rng, B, dev, reuse_buffers, schedule=None):
     """After `_check_chain`: the move's uniforms through the one checking path and its two outputs.  Returns (the five arguments in the
     order the C call names them: group, ess_frac, resample_uniform, ancestor_out, ess_out; ancestor; ess) -- the last two None without
-    resample."""
+    resample.  schedule (the scheduling calls only): the group's length where the call searches and does not resample."""
     _check_in(resample_uniform, "resample_uniform", B, dev)
+    if schedule is not None and B % schedule:
+        raise LsnfError(f"the chain's {B} rows are not a multiple of schedule={schedule}")
     if resample is None:
         if resample_uniform is not None:
             raise LsnfError("resample_uniform goes with resample=P")
-        return (0, 0.0, None, None, None), None, None
+        return (0 if schedule is None else int(schedule), 0.0, None, None, None), None, None
     if B % resample:
         raise LsnfError(f"the chain's {B} rows are not a multiple of resample={resample}")
     if (rng is None) != (resample_uniform is not None):
@@ -753,23 +773,35 @@ def hmc_step_resample(plan: FlowPlan, z_prop: torch.Tensor, grad_g: Optional[tor
     beta, step, scale and the adaptation stay with the row.  Without resample this is `hmc_step_tempered` to the bit.  Returns that
     call's tuple plus (ancestor, ess), both (B) -- the rung a row's state came from (its own where nothing moved), and the group's
     effective sample size -- or (None, None) without resample."""
+    return _hmc_step_group("lsnf_hmc_step_resample", plan, z_prop, grad_g, energy_g, state, noise, steps, metric, temper,
+                           phase=phase, uniform=uniform, propose=propose, inplace=inplace, reuse_buffers=reuse_buffers, adapt=adapt,
+                           window=window, anneal=anneal, resample=resample, ess_threshold=ess_threshold, resample_uniform=resample_uniform)
+
+
+def _hmc_step_group(entry, plan, z_prop, grad_g, energy_g, state, noise, steps, metric, temper, *, phase, uniform, propose, inplace,
+                    reuse_buffers, adapt, window, anneal, resample, ess_threshold, resample_uniform, search=None):
+    """The body of `hmc_step_resample` and `hmc_step_schedule`: entry is the C call; search: None, or the scheduling entry's
+    (schedule, cess_target, min_step), whose last two the C call takes behind ess_out."""
+    schedule, cess_target, min_step = (None, 0.95, 0.0) if search is None else search
+    tail = () if search is None else (float(cess_target), float(min_step))
     flags, inner = _row_step_mode(steps, phase, adapt), phase == "inner"
     flags |= _row_metric_mode(metric, phase, window)
     flags |= _row_temper_mode(temper, phase, anneal)
-    flags |= _row_resample_mode(resample, phase, adapt, window, anneal)
+    flags |= _row_resample_mode(resample, phase, adapt, window, anneal, schedule, cess_target, min_step)
     B, dev, noise, rng = _check_chain(plan, z_prop, "z_prop", grad_g, energy_g, state, HmcState, noise, uniform)
     step_ptr, adapt_ptr, da = _row_step_args(steps, B, dev, adapt)
     metric_args = _row_metric_args(plan, metric, B, dev, window)
     temper_args = _row_temper_args(plan, temper, B, dev, anneal)
-    resample_args, ancestor, ess = _row_resample_args(plan, resample, ess_threshold, resample_uniform, rng, B, dev, reuse_buffers)
+    resample_args, ancestor, ess = _row_resample_args(plan, resample, ess_threshold, resample_uniform, rng, B, dev, reuse_buffers, schedule)
     if inner and (noise is not None or rng is not None or uniform is not None or not propose):
         raise LsnfError("an inner leapfrog step draws and decides nothing: noise and uniform must be None, propose True")
     bufs, z1, ll = _forward_at(plan, z_prop, B, dev, "_hmc_buffers", reuse_buffers)
     z_next = None if not propose else z_prop if inplace else torch.empty_like(z_prop)
     acc, la = (None, None) if inner else (bufs["acc"], bufs["la"])
-    _call("lsnf_hmc_step_resample", dev, *_plan_head(plan), B, _ptr(z_prop), _ptr(z1), _ptr(bufs["saved"]), _ptr(bufs["act"]), _ptr(ll),
+    _call(entry, dev, *_plan_head(plan), B, _ptr(z_prop), _ptr(z1), _ptr(bufs["saved"]), _ptr(bufs["act"]), _ptr(ll),
           _ptr(grad_g), _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(state.mom), _ptr(state.kin), _ptr(noise),
-          _ptr(uniform), rng, step_ptr, adapt_ptr, da, *metric_args, *temper_args, flags, _ptr(z_next), _ptr(acc), _ptr(la), *resample_args)
+          _ptr(uniform), rng, step_ptr, adapt_ptr, da, *metric_args, *temper_args, flags, _ptr(z_next), _ptr(acc), _ptr(la), *resample_args,
+          *tail)
     return z_next, acc, la, ll, ancestor, ess
 
 
@@ -783,16 +815,28 @@ def reverse_hmc_step_resample(plan: FlowPlan, eps_prop: torch.Tensor, z_saved: O
     `lsnf_reverse_hmc_step_resample`); resample, ess_threshold and resample_uniform: as `hmc_step_resample`'s, with the state (eps,
     eps + beta * like_grad, |eps|^2 / 2 + beta * like_energy).  ONE launch and nothing else, so a resampling end call can be captured
     in a graph.  Returns `reverse_hmc_step_tempered`'s tuple plus (ancestor, ess), (None, None) without resample."""
+    return _reverse_hmc_step_group("lsnf_reverse_hmc_step_resample", plan, eps_prop, z_saved, act_saved, grad_g, energy_g, state, noise, steps,
+                                   metric, temper, phase=phase, uniform=uniform, propose=propose, inplace=inplace,
+                                   reuse_buffers=reuse_buffers, adapt=adapt, window=window, anneal=anneal, resample=resample,
+                                   ess_threshold=ess_threshold, resample_uniform=resample_uniform)
+
+
+def _reverse_hmc_step_group(entry, plan, eps_prop, z_saved, act_saved, grad_g, energy_g, state, noise, steps, metric, temper, *, phase,
+                            uniform, propose, inplace, reuse_buffers, adapt, window, anneal, resample, ess_threshold, resample_uniform,
+                            search=None):
+    """The body of `reverse_hmc_step_resample` and `reverse_hmc_step_schedule`, as `_hmc_step_group`."""
+    schedule, cess_target, min_step = (None, 0.95, 0.0) if search is None else search
+    tail = () if search is None else (float(cess_target), float(min_step))
     flags, inner = _row_step_mode(steps, phase, adapt), phase == "inner"
     flags |= _row_metric_mode(metric, phase, window)
     flags |= _row_temper_mode(temper, phase, anneal)
-    flags |= _row_resample_mode(resample, phase, adapt, window, anneal)
+    flags |= _row_resample_mode(resample, phase, adapt, window, anneal, schedule, cess_target, min_step)
     B, dev, noise, rng = _check_chain(plan, eps_prop, "eps_prop", grad_g, energy_g, state, HmcState, noise, uniform,
                                       stash=(z_saved, act_saved))
     step_ptr, adapt_ptr, da = _row_step_args(steps, B, dev, adapt)
     metric_args = _row_metric_args(plan, metric, B, dev, window)
     temper_args = _row_temper_args(plan, temper, B, dev, anneal)
-    resample_args, ancestor, ess = _row_resample_args(plan, resample, ess_threshold, resample_uniform, rng, B, dev, reuse_buffers)
+    resample_args, ancestor, ess = _row_resample_args(plan, resample, ess_threshold, resample_uniform, rng, B, dev, reuse_buffers, schedule)
     if inner and (noise is not None or rng is not None or uniform is not None or not propose):
         raise LsnfError("an inner leapfrog step draws and decides nothing: noise and uniform must be None, propose True")
     acc = la = None
@@ -803,7 +847,44 @@ def reverse_hmc_step_resample(plan: FlowPlan, eps_prop: torch.Tensor, z_saved: O
         bufs = _stream_buffers(plan, "_rhmc_buffers", B, dev, make) if reuse_buffers else make()
         acc, la = bufs["acc"], bufs["la"]
     eps_next = None if not propose else eps_prop if inplace else torch.empty_like(eps_prop)
-    _call("lsnf_reverse_hmc_step_resample", dev, *_plan_head(plan), B, _ptr(eps_prop), _ptr(z_saved), _ptr(act_saved), _ptr(grad_g),
+    _call(entry, dev, *_plan_head(plan), B, _ptr(eps_prop), _ptr(z_saved), _ptr(act_saved), _ptr(grad_g),
           _ptr(energy_g), _ptr(state.z), _ptr(state.grad), _ptr(state.energy), _ptr(state.mom), _ptr(state.kin), _ptr(noise), _ptr(uniform),
-          rng, step_ptr, adapt_ptr, da, *metric_args, *temper_args, flags, _ptr(eps_next), _ptr(acc), _ptr(la), *resample_args)
+          rng, step_ptr, adapt_ptr, da, *metric_args, *temper_args, flags, _ptr(eps_next), _ptr(acc), _ptr(la), *resample_args, *tail)
     return eps_next, acc, la, ancestor, ess
+
+
+def hmc_step_schedule(plan: FlowPlan, z_prop: torch.Tensor, grad_g: Optional[torch.Tensor], energy_g: Optional[torch.Tensor],
+                      state: HmcState, noise, steps: HmcRowSteps, metric: HmcRowMetric, temper: HmcRowTemper, *, phase: str = "end",
+                      uniform: Optional[torch.Tensor] = None, propose: bool = True, inplace: bool = False, reuse_buffers: bool = False,
+                      adapt: Optional[str] = None, window: Optional[str] = None, anneal: Optional[torch.Tensor] = None,
+                      resample: Optional[int] = None, ess_threshold: float = 0.5, resample_uniform: Optional[torch.Tensor] = None,
+                      schedule: Optional[int] = None, cess_target: float = 0.95, min_step: float = 0.0):
+    """`hmc_step_resample` with the groups' next temperature searched inside the kernel (include/lsnf_flow_mcmc.h
+    `lsnf_hmc_step_schedule`): adaptive tempering.  schedule = P (2, 4, 8 or 16, dividing B; equal to resample where both are given)
+    on an annealing init or end call (anneal=, without adapt / window) makes anneal the groups' CEILING: every group of P rows steps
+    from temper.beta to the temperature at which the conditional effective sample size of its incremental weights is cess_target * P
+    (twelve halvings), by at least min_step and no further than the ceiling; temper.beta holds the chosen value afterwards, equal on
+    the rows of a group.  temper.beta and anneal are read at the group's first row: keep both equal within a group.  The weight
+    increment, the re-tempering and the resampling move (if asked for) then run as in `hmc_step_resample` with the chosen value.
+    Without schedule this is `hmc_step_resample` to the bit.  ONE launch and nothing else.  Returns `hmc_step_resample`'s tuple."""
+    return _hmc_step_group("lsnf_hmc_step_schedule", plan, z_prop, grad_g, energy_g, state, noise, steps, metric, temper,
+                           phase=phase, uniform=uniform, propose=propose, inplace=inplace, reuse_buffers=reuse_buffers, adapt=adapt,
+                           window=window, anneal=anneal, resample=resample, ess_threshold=ess_threshold, resample_uniform=resample_uniform,
+                           search=(schedule, cess_target, min_step))
+
+
+def reverse_hmc_step_schedule(plan: FlowPlan, eps_prop: torch.Tensor, z_saved: Optional[torch.Tensor], act_saved: torch.Tensor,
+                              grad_g: Optional[torch.Tensor], energy_g: Optional[torch.Tensor], state: HmcState, noise, steps: HmcRowSteps,
+                              metric: HmcRowMetric, temper: HmcRowTemper, *, phase: str = "end", uniform: Optional[torch.Tensor] = None,
+                              propose: bool = True, inplace: bool = False, reuse_buffers: bool = False, adapt: Optional[str] = None,
+                              window: Optional[str] = None, anneal: Optional[torch.Tensor] = None, resample: Optional[int] = None,
+                              ess_threshold: float = 0.5, resample_uniform: Optional[torch.Tensor] = None,
+                              schedule: Optional[int] = None, cess_target: float = 0.95, min_step: float = 0.0):
+    """`reverse_hmc_step_resample` with the groups' next temperature searched inside the kernel (include/lsnf_flow_mcmc.h
+    `lsnf_reverse_hmc_step_schedule`); schedule, cess_target and min_step: as `hmc_step_schedule`'s.  ONE launch and nothing else, so a
+    scheduling call can be captured in a graph.  Returns `reverse_hmc_step_resample`'s tuple."""
+    return _reverse_hmc_step_group("lsnf_reverse_hmc_step_schedule", plan, eps_prop, z_saved, act_saved, grad_g, energy_g, state, noise, steps,
+                                   metric, temper, phase=phase, uniform=uniform, propose=propose, inplace=inplace,
+                                   reuse_buffers=reuse_buffers, adapt=adapt, window=window, anneal=anneal, resample=resample,
+                                   ess_threshold=ess_threshold, resample_uniform=resample_uniform,
+                                   search=(schedule, cess_target, min_step))

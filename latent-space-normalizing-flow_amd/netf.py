@@ -605,6 +605,34 @@ class _netF(nn.Module):
                                               anneal=det(anneal), resample=resample, ess_threshold=ess_threshold,
                                               resample_uniform=det(resample_uniform))
 
+    def hmc_step_schedule(self, z_prop, grad_g=None, energy_g=None, state=None, noise=None, steps=None, metric=None, temper=None, *,
+                          phase="end", uniform=None, propose=True, inplace=False, reuse_buffers=False, adapt=None, window=None,
+                          anneal=None, resample=None, ess_threshold=0.5, resample_uniform=None, schedule=None, cess_target=0.95,
+                          min_step=0.0):
+        """`hmc_step_resample` with the groups' next temperature searched inside the kernel (`flow.hmc_step_schedule`): schedule = P
+        on an annealing init or end call makes anneal the ceiling and steps every group of P rows to where the conditional effective
+        sample size of its incremental weights is cess_target * P, by at least min_step.  Returns what `hmc_step_resample` returns."""
+        det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t
+        return flow.hmc_step_schedule(self._plan(), det(z_prop), det(grad_g), det(energy_g), state, det(noise), steps, metric, temper,
+                                      phase=phase, uniform=det(uniform), propose=propose, inplace=inplace, reuse_buffers=reuse_buffers,
+                                      adapt=adapt, window=window, anneal=det(anneal), resample=resample, ess_threshold=ess_threshold,
+                                      resample_uniform=det(resample_uniform), schedule=schedule, cess_target=cess_target,
+                                      min_step=min_step)
+
+    def reverse_hmc_step_schedule(self, eps_prop, z_saved, act_saved, grad_g=None, energy_g=None, state=None, noise=None, steps=None,
+                                  metric=None, temper=None, *, phase="end", uniform=None, propose=True, inplace=False,
+                                  reuse_buffers=False, adapt=None, window=None, anneal=None, resample=None, ess_threshold=0.5,
+                                  resample_uniform=None, schedule=None, cess_target=0.95, min_step=0.0):
+        """`reverse_hmc_step_resample` with the groups' next temperature searched inside the kernel
+        (`flow.reverse_hmc_step_schedule`).  Returns what `reverse_hmc_step_resample` returns."""
+        det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t
+        return flow.reverse_hmc_step_schedule(self._plan(), det(eps_prop), det(z_saved), det(act_saved), det(grad_g), det(energy_g),
+                                              state, det(noise), steps, metric, temper, phase=phase, uniform=det(uniform),
+                                              propose=propose, inplace=inplace, reuse_buffers=reuse_buffers, adapt=adapt, window=window,
+                                              anneal=det(anneal), resample=resample, ess_threshold=ess_threshold,
+                                              resample_uniform=det(resample_uniform), schedule=schedule, cess_target=cess_target,
+                                              min_step=min_step)
+
     def mle_grads(self, z, accumulate: bool = False, max_norm: Optional[float] = None, reuse_buffers: bool = False):
         """Fused flow-MLE gradients (train.py:404-411): loss_f = -mean_b ll(z_b) and d loss_f / d theta written to
         `.grad` of the 60 live tensors -- forward (ll summed in-kernel), dump backward, batch contraction, unfold:

@@ -1,0 +1,53 @@
+"""GPU: the groups' next temperature searched inside the annealing call of Hamiltonian Monte Carlo in the flow's base space
+(lsnf_reverse_hmc_step_schedule, lsnf_small3_rhmca_kernel), `flow.reverse_hmc_step_schedule`, `_netF.reverse_hmc_step_schedule` and
+`langevin.estimate_log_px_smc_adaptive_eps_with_flow`.  The checks are tests/hmc_schedule_gpu.py's, shared with
+tests/test_gpu_hmc_schedule.py (whose docstring lists them); the cases, their teacher-forcing records and their steps are
+tests/test_gpu_rhmc.py's."""
+import pytest
+
+import hmc_rows_gpu as HG
+import hmc_schedule_gpu as AG
+import test_gpu_rhmc as TR
+import test_gpu_reverse_keep as K
+
+pytestmark = pytest.mark.gpu
+SP = HG.Space("eps", TR)
+
+
+@pytest.fixture(scope="module")
+def lsnf():
+    import lsnf_amd
+    lsnf_amd.load_library()
+    return lsnf_amd
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", AG.IDENTITY)
+def test_without_schedule_every_phase_is_the_resampling_call_bit_for_bit(lsnf, gpu_device, nz, w, depth, coupling, B):
+    AG.check_no_schedule_is_the_resample_call(lsnf, SP, TR.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B))
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B,P", AG.MOVE)
+def test_schedule_is_the_resampling_call_at_its_own_beta_and_within_the_bound_of_float64(lsnf, gpu_device, nz, w, depth, coupling, B, P):
+    AG.check_schedule_against_itself_and_float64(lsnf, SP, TR.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B), P)
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B,P", AG.EDGE)
+def test_hand_made_edge_groups(lsnf, gpu_device, nz, w, depth, coupling, B, P):
+    AG.check_edge_groups(lsnf, SP, TR.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B), P)
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B,P", AG.FORMS)
+def test_scheduling_call_in_place_four_bytes_off_null_optionals_reused_buffers_and_sharded(lsnf, gpu_device, nz, w, depth, coupling, B, P):
+    AG.check_schedule_forms(lsnf, SP, TR.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B), P)
+
+
+def test_captured_scheduling_end_call_replays_to_the_same_bits_with_beta_advancing(lsnf, gpu_device):
+    AG.check_captured_call(lsnf, SP, TR.setup_of(lsnf, gpu_device, *AG.C3, 64))
+
+
+def test_sampler_is_the_hand_written_loop(lsnf, gpu_device, monkeypatch):
+    AG.check_samplers(lsnf, SP, K, gpu_device, monkeypatch)
+
+
+def test_sampler_lands_inside_the_cpu_experiments_band(lsnf, gpu_device):
+    AG.check_sampler_band(lsnf, SP, K, gpu_device)
