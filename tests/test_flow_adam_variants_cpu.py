@@ -225,6 +225,36 @@ def test_restated_skip_and_average():
     assert torch.equal(r["ema"][1], params[1]) and torch.equal(r["p"][1], params[1])
 
 
+def test_restated_decoupled_decay_with_an_average_and_without_amsgrad():
+    """The combination lsnf_adam_kernel<false, true, true> serves (tests/test_gpu_flow_adam_variants.py's "decoupled-ema"): the
+    restatement's p, m and v are torch.optim.AdamW's whatever the average does, no maximum is kept, the average is the recursion
+    over the parameters as stored, and both options bite."""
+    gen = torch.Generator().manual_seed(13)
+    params = [torch.randn(4, 5, generator=gen, dtype=torch.float64), torch.randn(1, 3, generator=gen, dtype=torch.float64)]
+    steps = [[torch.randn_like(t) * 0.1 for t in params] for _ in range(5)]
+    hyper = dict(lr=1e-2, betas=(0.5, 0.9), eps=1e-8, weight_decay=1e-2)
+    r = clip_adam_variants(params, steps, decoupled=True, ema_decay=0.9, **hyper)
+    live = [torch.nn.Parameter(p.clone()) for p in params]
+    opt = torch.optim.AdamW(live, foreach=False, **hyper)
+    snaps = [params]
+    for k, gs in enumerate(steps):
+        for p, g in zip(live, gs):
+            p.grad = g.clone()
+        opt.step()
+        snaps.append(clip_adam_variants(params, steps[: k + 1], decoupled=True, ema_decay=0.9, **hyper)["p"])
+    for i, q in enumerate(live):
+        for got, ref in ((r["p"][i], q.detach()), (r["m"][i], opt.state[q]["exp_avg"]), (r["v"][i], opt.state[q]["exp_avg_sq"])):
+            assert (got - ref).abs().max().item() <= 1e-12 * ref.abs().max().item()
+    assert r["vmax"] is None and r["step"] == 5
+    for a, b in zip(ema_of(snaps, 0.9), r["ema"]):
+        assert (a - b).abs().max().item() <= 1e-15
+    coupled = clip_adam_variants(params, steps, ema_decay=0.9, **hyper)
+    assert not torch.equal(coupled["p"][0], r["p"][0]) and not torch.equal(coupled["ema"][0], r["ema"][0])
+    assert not torch.equal(r["ema"][0], r["p"][0])
+    import test_gpu_flow_adam_variants as GV                     # (importing the GPU module needs no device)
+    assert GV.VARIANTS["decoupled-ema"] == (dict(decoupled=True, ema_decay=0.9), GV.WD, None) and GV.WD > 0.0
+
+
 # ---- FlowAdam's state format, on CPU tensors --------------------------------------------------------------------------------
 HPS = types.SimpleNamespace(f_n_levels=1, f_depth=2, f_flow_permutation=2, f_width=4, f_flow_coupling=1)
 NZ = 8

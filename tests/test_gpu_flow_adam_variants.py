@@ -35,6 +35,7 @@ VARIANTS = {
     "maximize": (dict(maximize=True), WD, None),
     "decoupled": (dict(decoupled=True), WD, None),
     "ema": (dict(ema_decay=0.9), 0.0, None),
+    "decoupled-ema": (dict(decoupled=True, ema_decay=0.9), WD, None),       # lsnf_adam_kernel<false, true, true>: FlowAdamW's average without amsgrad
     "skip": (dict(skip_nonfinite=True), 0.0, None),
     "amsgrad-decoupled-maximize-clip": (dict(amsgrad=True, decoupled=True, maximize=True), WD, "below"),
 }
@@ -137,8 +138,13 @@ def same_bits(a, b, keys=("p", "m", "v", "vmax", "ema")):
 def test_matches_float64_within_the_matching_torch_optimizers_error(lsnf, gpu_device, geo_name, variant, steps):
     r64, t32, mn = references(geo_name, variant, steps)
     opts, wd, _ = VARIANTS[variant]
-    got = run_fused(lsnf, geo_name, rising_case(geo_name)[1][:steps], gpu_device, wd=wd, mn=mn, rising=True, **opts)
+    got = run_fused(lsnf, geo_name, rising_case(geo_name)[1][:steps], gpu_device, wd=wd, mn=mn, rising=True,
+                    snapshots="ema_decay" in opts, **opts)
     assert got["step"] == steps and got["skipped"] == 0
+    if "ema_decay" in opts:                                   # the average of the parameters as stored: section 3's allowance
+        for i, (e, r) in enumerate(zip(got["ema"], ema_of(got["snaps"], opts["ema_decay"]))):
+            err, allow = (e.double().cpu() - r).abs().max().item(), steps * 2.0 ** -24 * r.abs().max().item()
+            assert err <= allow, f"average[{i}]: error {err:.3e} > allowance {allow:.3e}"
     for key, t in zip(("p", "m", "v", "vmax"), t32):
         assert (got[key] is None) == (t is None)
         if t is not None:

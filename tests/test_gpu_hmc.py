@@ -15,6 +15,7 @@ tests/chain_geometries.py -- ragged halves, whole tiles of padding -- which CASE
 restatement alone so that the two-trajectory cases accept between 15 % and 85 % of their decisions (asserted).  Everything else is
 bit identity between call forms, or the device against itself."""
 import functools
+import types
 
 import numpy as np
 import pytest
@@ -23,6 +24,7 @@ import torch
 from oracle import flow_oracle as O
 import chain_geometries as G
 import hmc_restated as H
+import trained_weights as T
 import test_gpu_reverse_keep as K
 from test_gpu_langevin import ToyG
 
@@ -50,7 +52,9 @@ STEP_L1 = {128: 0.9, 8: 1.2}                                 # L = 1 against mal
 QUAD_SCALE = {2: 2.0}                                        # (tests/test_gpu_mala.py: at nz = 2 the u_acc bound needs an energy of order 1)
 
 
-def step_of(nz, geo=None):
+def step_of(nz, geo=None, weights=T.INIT):
+    if weights != T.INIT:
+        return float(np.float32(T.step_of("hmc z", geo)))                          # tests/trained_weights.py
     return float(np.float32(STEP_GEO[geo] if geo in STEP_GEO else STEP[nz]))      # the fp32 step the kernel sees
 
 
@@ -74,11 +78,11 @@ def widened(bound, own):
 class Case:
     """One geometry and batch on the CPU: the float64 chain's call records, each with its fp32 restatement, gates and row sets."""
 
-    def __init__(self, nz, w, depth, coupling, B):
-        self.geo, self.B, self.nz, self.depth = (nz, w, depth, coupling), B, nz, depth
-        p = O.init_params(nz, w, depth, seed=3)
+    def __init__(self, nz, w, depth, coupling, B, weights=T.INIT, s=None, diverging=False):
+        self.geo, self.B, self.nz, self.depth, self.weights = (nz, w, depth, coupling), B, nz, depth, weights
+        p = T.params_for(O, self.geo, weights)
         self.p = K.additive(p) if coupling == 0 else p
-        self.s, self.L = step_of(nz, self.geo), L_STEPS
+        self.s, self.L = step_of(nz, self.geo, weights) if s is None else float(np.float32(s)), L_STEPS
         self.n_traj = 2 if B <= 100 else 1
         self.quad = H.Quadratic(nz, QUAD_SCALE.get(nz, 0.1), seed=7 + nz)
         g = torch.Generator().manual_seed(7 + B + SEED.get(self.geo + (B,), 0))
@@ -87,6 +91,8 @@ class Case:
         uniforms = [None] + [torch.rand(B, generator=g).clamp_min(2.0 ** -25) for _ in range(self.n_traj)]
         self.calls, _ = H.chain(self.p, self.z0, self.quad, self.s, self.L, noises, uniforms, redraw=g)
         self.allowed = 2 if B <= 33 else B // 10
+        if diverging:                                        # the records alone: no rate, gate or row set holds on a diverged trajectory
+            return
         s = self.s
         for c in self.calls:
             c.o32 = o = H.call32(self.p, c, self.quad, s)
@@ -117,21 +123,21 @@ class Case:
 
 
 @functools.lru_cache(maxsize=None)
-def case(nz, w, depth, coupling, B):
-    return Case(nz, w, depth, coupling, B)
+def case(nz, w, depth, coupling, B, weights=T.INIT):
+    return Case(nz, w, depth, coupling, B, weights)
 
 
 class Setup:
     """A case's plan on the device (made under the run's math mode, as its forward's stash will be)."""
 
-    def __init__(self, lsnf, dev, nz, w, depth, coupling, B, mode):
-        self.c, self.dev, self.mode = case(nz, w, depth, coupling, B), dev, mode
+    def __init__(self, lsnf, dev, nz, w, depth, coupling, B, mode, weights=T.INIT):
+        self.c, self.dev, self.mode = case(nz, w, depth, coupling, B, weights), dev, mode
         self.plan = K.make_plan(lsnf, self.c, dev)
 
 
 @functools.lru_cache(maxsize=None)
-def setup_of(lsnf, dev, nz, w, depth, coupling, B, mode="default"):
-    return Setup(lsnf, dev, nz, w, depth, coupling, B, mode)
+def setup_of(lsnf, dev, nz, w, depth, coupling, B, mode="default", weights=T.INIT):
+    return Setup(lsnf, dev, nz, w, depth, coupling, B, mode, weights)
 
 
 @pytest.fixture
@@ -194,12 +200,12 @@ fig = lambda t: t.max().item() if t.numel() else 0.0
 # 1. against float64, teacher-forced
 # ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nz,w,depth,coupling,B,mode", RUNS)
-def test_every_call_follows_float64(lsnf, gpu_device, math, nz, w, depth, coupling, B, mode):
+def test_every_call_follows_float64(lsnf, gpu_device, math, nz, w, depth, coupling, B, mode, weights=T.INIT):
     math(mode)
-    s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, mode)
+    s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, mode, weights)
     c = s.c
-    tag = f"[hmc] {mode} {c.geo} B{B}"
-    print(f"{tag} s={c.s:.2f} L={c.L}: float64 accepts {100 * c.rate:.0f} % of {c.n_traj} x {B} decisions")
+    tag = f"[hmc] {mode} {c.geo} B{B}" + ("" if weights == T.INIT else f" {weights}")
+    print(f"{tag} s={c.s:.3f} L={c.L}: float64 accepts {100 * c.rate:.0f} % of {c.n_traj} x {B} decisions")
     if c.n_traj > 1:
         assert 0.15 <= c.rate <= 0.85
     for j, r in enumerate(c.device_calls):
@@ -226,6 +232,10 @@ def test_every_call_follows_float64(lsnf, gpu_device, math, nz, w, depth, coupli
                 print(f"{name}: accepted {int(a64.sum())}/{B}, set aside {aside} (allowed {c.allowed}; {int((~r.smooth).sum())} near a kink), "
                       f"worst |log_alpha - fp64| / gate = {worst:.3f}, fp32 restatement worst {fig((r.o32.la.double() - r.la).abs() / r.gate):.3f}")
                 assert aside <= c.allowed
+                if weights != T.INIT:                        # the same share from the device's own log_alpha, together with the kink rows
+                    aside_dev = int((~r.smooth | ((la.cpu().double() - torch.log(r.u.double())).abs() <= r.gate)).sum())
+                    print(f"{name}: set aside by the device's log_alpha {aside_dev}")
+                    assert aside_dev <= c.allowed
                 assert bool((err <= r.gate)[r.smooth].all())
                 assert torch.equal(acc_c[d] == 1.0, a64[d])
             yes, no = d & a64, d & ~a64
@@ -255,6 +265,13 @@ def test_every_call_follows_float64(lsnf, gpu_device, math, nz, w, depth, coupli
             assert bool((e <= r.kin_bound).all())
         elif r.phase != "init":
             assert bits(state.kin, before.kin)                                    # no trajectory begun: kin0 is left as it is
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", T.CASES)
+def test_every_call_follows_float64_at_trained_weights(lsnf, gpu_device, math, nz, w, depth, coupling, B):
+    """The same calls, gates and caps on the golden trained weights (tests/trained_weights.py): a saturating sigmoid, |3 logs| up to 2,
+    |grad log p| of order 1e3, steps from the narrow window in which the float64 leapfrog is stable there."""
+    test_every_call_follows_float64(lsnf, gpu_device, math, nz, w, depth, coupling, B, "default", weights=T.TRAINED)
 
 
 SMALL = [C3 + (33,), C3 + (4100,), C3 + (8200,), TINY + (33,)]
@@ -502,6 +519,51 @@ def test_a_nan_row_is_rejected_and_alone(lsnf, gpu_device):
     assert bits(state.mom[bad], ph) and bits(z_next[bad], before.z[bad] + c.s * ph)
     for got, ref in zip([getattr(state, f) for f in FIELDS] + [z_next, acc, la, ll], [getattr(clean[0], f) for f in FIELDS] + list(clean[1])):
         assert bits(got[keep], ref[keep])
+
+
+def diverged_rows(c):
+    """The first end call of a diverging case, and the rows whose float64 log_alpha is NaN, -inf or below -100."""
+    r = c.calls[c.L]
+    return r, torch.isnan(r.la) | (r.la < -100.0)
+
+
+def diverging_call(c):
+    """That end call with the rows T.GRAFTED given the inputs of the same case at its stable step, and the diverged rows of it."""
+    stable = case(*c.geo, c.B, T.TRAINED)
+    r = T.graft(c.calls[c.L], stable.calls[stable.L])
+    return r, torch.isnan(r.la) | (r.la < -100.0)
+
+
+def test_a_diverging_trajectory_is_rejected_and_alone(lsnf, gpu_device):
+    """C3 at trained weights, step 0.2: in float64 |z| grows 13 -> 79 -> 2.9e3 over the three leapfrog steps, ll = -inf and the gradient
+    is NaN from the second inner call on, so the end call is given NaN points, infinite energies and momenta of order 1e5 on 30 rows
+    (three rows carry the stable case's inputs: tests/trained_weights.py GRAFTED).  Every diverged row is rejected with its state kept
+    to the bit, and no other row's output differs from the call on those rows alone."""
+    c = Case(*C3, 33, weights=T.TRAINED, s=T.DIVERGING_STEP["hmc z"], diverging=True)
+    r, bad = diverging_call(c)
+    assert int(bad.sum()) >= T.DIVERGING_ROWS and not bool(bad[list(T.GRAFTED)].any())
+    dev = gpu_device
+    s = types.SimpleNamespace(c=c, dev=dev, plan=K.make_plan(lsnf, c, dev))
+    state = state_for(lsnf, s, r)
+    before = clone_state(lsnf, state)
+    state, out = run(lsnf, s, r, state=state, propose=True)
+    torch.cuda.synchronize()
+    acc, la = out[1], out[2]
+    bad_d = bad.to(dev)
+    print(f"[hmc] {c.geo} B33 trained s={c.s:.2f} diverging: {int(bad.sum())} rows diverged in float64, the device accepts "
+          f"{int(acc[bad_d].sum())} of them; its log_alpha there: {int(torch.isnan(la[bad_d]).sum())} NaN, {int(torch.isinf(la[bad_d]).sum())} inf; "
+          f"the {int((~bad).sum())} other rows: accepted {int(acc[~bad_d].sum())}")
+    assert bool((acc[bad_d] == 0.0).all())
+    for f in ("z", "grad", "energy"):
+        assert bits(getattr(state, f)[bad_d], getattr(before, f)[bad_d])
+    keep = torch.nonzero(~bad).flatten()                     # the rows that did not diverge, as a batch of their own
+    assert keep.numel() == len(T.GRAFTED)
+    alone_state, alone = run(lsnf, s, r, rows=keep, propose=True)
+    whole = [getattr(state, f) for f in FIELDS] + list(out)
+    for got, ref in zip(whole, [getattr(alone_state, f) for f in FIELDS] + list(alone)):
+        assert (got is None) == (ref is None)
+        if got is not None:
+            assert bits(got[keep.to(dev)], ref) and bool(torch.isfinite(ref).all())
 
 
 # ---------------------------------------------------------------------------------------------

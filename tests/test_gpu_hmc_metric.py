@@ -26,6 +26,7 @@ import hmc_rows_gpu as HG
 import test_gpu_hmc as TH
 import test_gpu_reverse_keep as K
 from test_gpu_langevin import ToyG
+import trained_weights as TW
 
 pytestmark = pytest.mark.gpu
 SP = HG.Space("z", TH)
@@ -126,3 +127,17 @@ def test_sampler_without_windows_is_the_adaptive_sampler(lsnf, gpu_device):
     assert all(bits(getattr(metric_c, f), getattr(mm, f)) for f in MG.METRIC)
     assert not bits(metric_c.scale, torch.ones_like(metric_c.scale)) and not metric_c.count.any() and bool((steps_c.adapt[:, 2] == 1).all())
     assert not bits(z_c, z_b)
+
+
+# ---------------------------------------------------------------------------------------------
+# The golden trained weights (tests/trained_weights.py, TW): the checks above on the scalar module's trained cases, each at its own step.
+# ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", TW.SMALL)
+def test_unit_scale_is_the_per_row_call_bit_for_bit_at_trained_weights(lsnf, gpu_device, nz, w, depth, coupling, B):
+    MG.check_unit_scale_is_the_per_row_call(lsnf, SP, TH.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, weights=TW.TRAINED))
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", TW.SMALL)
+def test_column_scale_follows_float64_and_begins_to_the_bit_at_trained_weights(lsnf, gpu_device, nz, w, depth, coupling, B):
+    MG.check_column_scale_follows_float64(lsnf, SP, TH.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, weights=TW.TRAINED))

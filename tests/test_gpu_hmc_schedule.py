@@ -20,6 +20,7 @@ import hmc_rows_gpu as HG
 import hmc_schedule_gpu as AG
 import test_gpu_hmc as TH
 import test_gpu_reverse_keep as K
+import trained_weights as TW
 
 pytestmark = pytest.mark.gpu
 SP = HG.Space("z", TH)
@@ -62,3 +63,17 @@ def test_sampler_is_the_hand_written_loop(lsnf, gpu_device, monkeypatch):
 
 def test_sampler_lands_inside_the_cpu_experiments_band(lsnf, gpu_device):
     AG.check_sampler_band(lsnf, SP, K, gpu_device)
+
+
+# ---------------------------------------------------------------------------------------------
+# The golden trained weights (tests/trained_weights.py, TW): the checks above on the scalar module's trained cases, each at its own step.
+# ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", TW.SMALL)
+def test_without_schedule_every_phase_is_the_resampling_call_bit_for_bit_at_trained_weights(lsnf, gpu_device, nz, w, depth, coupling, B):
+    AG.check_no_schedule_is_the_resample_call(lsnf, SP, TH.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, weights=TW.TRAINED))
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B,R", TW.LADDERS)
+def test_schedule_is_the_resampling_call_at_its_own_beta_and_within_the_bound_of_float64_at_trained_weights(lsnf, gpu_device, nz, w, depth, coupling, B, R):
+    AG.check_schedule_against_itself_and_float64(lsnf, SP, TH.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, weights=TW.TRAINED), R)

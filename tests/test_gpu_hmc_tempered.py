@@ -23,6 +23,7 @@ import hmc_rows_gpu as HG
 import hmc_tempered_gpu as TG
 import test_gpu_hmc as TH
 import test_gpu_reverse_keep as K
+import trained_weights as TW
 
 pytestmark = pytest.mark.gpu
 SP = HG.Space("z", TH)
@@ -75,3 +76,27 @@ def test_in_place_off_the_boundary_and_null_optionals(lsnf, gpu_device, nz, w, d
 
 def test_sampler_finds_the_closed_form(lsnf, gpu_device):
     TG.check_samplers(lsnf, SP, K, gpu_device)
+
+
+# ---------------------------------------------------------------------------------------------
+# The golden trained weights (tests/trained_weights.py, TW): the checks above on the scalar module's trained cases, each at its own step.
+# ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", TW.SMALL)
+def test_unit_temperature_is_the_metric_call_bit_for_bit_at_trained_weights(lsnf, gpu_device, nz, w, depth, coupling, B):
+    TG.check_unit_temperature_is_the_metric_call(lsnf, SP, TH.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, weights=TW.TRAINED))
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", TW.SMALL)
+def test_general_temperature_follows_float64_at_trained_weights(lsnf, gpu_device, nz, w, depth, coupling, B):
+    TG.check_general_temperature_follows_float64(lsnf, SP, TH.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, weights=TW.TRAINED))
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", TW.SMALL)
+def test_anneal_lines_hold_on_the_stored_values_at_trained_weights(lsnf, gpu_device, nz, w, depth, coupling, B):
+    TG.check_anneal_lines(lsnf, SP, TH.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, weights=TW.TRAINED))
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", TW.SMALL)
+def test_fifty_anneals_sum_to_the_float64_weight_at_trained_weights(lsnf, gpu_device, nz, w, depth, coupling, B):
+    TG.check_anneal_sum(lsnf, SP, TH.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, weights=TW.TRAINED))

@@ -20,6 +20,7 @@ import torch
 from oracle import flow_oracle as O
 import chain_geometries as G
 import mala_restated as M
+import trained_weights as T
 import test_gpu_reverse_keep as K
 from test_gpu_langevin import ToyG
 
@@ -54,7 +55,9 @@ STEP_GEO = {(62, 31, 2, 1): 1.0, (66, 33, 2, 1): 1.0, (124, 63, 3, 1): 0.85, (66
 QUAD_SCALE = {2: 2.0}
 
 
-def step_of(nz, geo=None):
+def step_of(nz, geo=None, weights=T.INIT):
+    if weights != T.INIT:
+        return float(np.float32(T.step_of("mala z", geo)))                         # tests/trained_weights.py
     return float(np.float32(STEP_GEO[geo] if geo in STEP_GEO else STEP[nz]))      # the fp32 step the kernel sees
 
 
@@ -68,11 +71,11 @@ def lsnf():
 class Case:
     """One geometry and batch on the CPU: the float64 chain (teacher-forcing records) and the fp32 restatement's log_alpha."""
 
-    def __init__(self, nz, w, depth, coupling, B):
-        self.geo, self.B, self.nz, self.depth = (nz, w, depth, coupling), B, nz, depth
-        p = O.init_params(nz, w, depth, seed=3)
+    def __init__(self, nz, w, depth, coupling, B, weights=T.INIT, s=None):
+        self.geo, self.B, self.nz, self.depth, self.weights = (nz, w, depth, coupling), B, nz, depth, weights
+        p = T.params_for(O, self.geo, weights)
         self.p = K.additive(p) if coupling == 0 else p
-        self.s = step_of(nz, self.geo)
+        self.s = step_of(nz, self.geo, weights) if s is None else float(np.float32(s))
         self.n_steps = 3 if B <= 100 else 1
         self.quad = M.Quadratic(nz, QUAD_SCALE.get(nz, 0.1), seed=7 + nz)
         g = torch.Generator().manual_seed(7 + B)
@@ -94,21 +97,21 @@ class Case:
 
 
 @functools.lru_cache(maxsize=None)
-def case(nz, w, depth, coupling, B):
-    return Case(nz, w, depth, coupling, B)
+def case(nz, w, depth, coupling, B, weights=T.INIT):
+    return Case(nz, w, depth, coupling, B, weights)
 
 
 class Setup:
     """A case's plan on the device (made under the run's math mode, as its forward's stash will be)."""
 
-    def __init__(self, lsnf, dev, nz, w, depth, coupling, B, mode):
-        self.c, self.dev, self.mode = case(nz, w, depth, coupling, B), dev, mode
+    def __init__(self, lsnf, dev, nz, w, depth, coupling, B, mode, weights=T.INIT):
+        self.c, self.dev, self.mode = case(nz, w, depth, coupling, B, weights), dev, mode
         self.plan = K.make_plan(lsnf, self.c, dev)
 
 
 @functools.lru_cache(maxsize=None)
-def setup_of(lsnf, dev, nz, w, depth, coupling, B, mode="default"):
-    return Setup(lsnf, dev, nz, w, depth, coupling, B, mode)
+def setup_of(lsnf, dev, nz, w, depth, coupling, B, mode="default", weights=T.INIT):
+    return Setup(lsnf, dev, nz, w, depth, coupling, B, mode, weights)
 
 
 @pytest.fixture
@@ -147,11 +150,12 @@ def rel_rows(got, ref):
 # 1. against float64, teacher-forced
 # ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nz,w,depth,coupling,B,mode", RUNS)
-def test_decisions_and_state_follow_float64(lsnf, gpu_device, math, nz, w, depth, coupling, B, mode):
+def test_decisions_and_state_follow_float64(lsnf, gpu_device, math, nz, w, depth, coupling, B, mode, weights=T.INIT):
     math(mode)
-    s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, mode)
+    s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, mode, weights)
     c = s.c
-    print(f"[mala] {mode} {c.geo} B{B} s={c.s:.2f}: float64 accepts {100 * c.rate:.0f} % of {len(c.steps)} x {B} decisions")
+    mode = mode if weights == T.INIT else f"{mode} {weights}"
+    print(f"[mala] {mode} {c.geo} B{B} s={c.s:.3f}: float64 accepts {100 * c.rate:.0f} % of {len(c.steps)} x {B} decisions")
     if c.n_steps == 3:
         assert 0.15 <= c.rate <= 0.85
     for j, st in enumerate(c.steps):
@@ -165,6 +169,10 @@ def test_decisions_and_state_follow_float64(lsnf, gpu_device, math, nz, w, depth
               f"{int((~st.smooth).sum())} near a kink), worst |log_alpha - fp64| / gate = {worst:.3f}, "
               f"oracle-fp32 worst {((st.la32.double() - st.la).abs() / st.gate).max().item():.3f}")
         assert aside <= allowed
+        if weights != T.INIT:                                # the same share from the device's own log_alpha, together with the kink rows
+            aside_dev = int((~st.smooth | ((la.cpu().double() - torch.log(st.u.double())).abs() <= st.gate)).sum())
+            print(f"[mala] {mode} {c.geo} B{B} step {j + 1}: set aside by the device's log_alpha {aside_dev}")
+            assert aside_dev <= allowed
         assert bool((err <= st.gate)[st.smooth].all())
         d, a64 = st.decided, st.acc
         acc_c, za, ga, ua = acc.cpu(), state.z.cpu(), state.grad.cpu(), state.energy.cpu()
@@ -179,6 +187,13 @@ def test_decisions_and_state_follow_float64(lsnf, gpu_device, math, nz, w, depth
         assert bool((rel_rows(ga[yes], st.g_prop[yes]) <= 1e-5).all())
         assert bits(za[no], before.z.cpu()[no]) and bits(ga[no], before.grad.cpu()[no]) and bits(ua[no], before.energy.cpu()[no])
         assert bool((rel_rows(z_next.cpu()[d], st.z_next[d]) <= 1e-5).all())
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", T.CASES)
+def test_decisions_and_state_follow_float64_at_trained_weights(lsnf, gpu_device, math, nz, w, depth, coupling, B):
+    """The same steps, gates and caps on the golden trained weights (tests/trained_weights.py): a saturating sigmoid, |3 logs| up to 2,
+    |grad log p| of order 1e3, steps from the narrow window in which the float64 chain still accepts there."""
+    test_decisions_and_state_follow_float64(lsnf, gpu_device, math, nz, w, depth, coupling, B, "default", weights=T.TRAINED)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -16,6 +16,7 @@ import torch
 from oracle import flow_oracle as O
 from oracle.philox_oracle import langevin_noise
 import reverse_restated as R
+import trained_weights as T
 
 pytestmark = pytest.mark.gpu
 
@@ -84,9 +85,9 @@ def forward_vjp(p, x, g_z1, g_ld, dtype):
 class Case:
     """One geometry and batch: the inputs and every float64 / float32 oracle figure the tests share, each computed once on the CPU."""
 
-    def __init__(self, nz, w, depth, coupling, B):
-        self.geo, self.B, self.nz, self.depth = (nz, w, depth, coupling), B, nz, depth
-        p = O.init_params(nz, w, depth, seed=3)
+    def __init__(self, nz, w, depth, coupling, B, weights=T.INIT):
+        self.geo, self.B, self.nz, self.depth, self.weights = (nz, w, depth, coupling), B, nz, depth, weights
+        p = T.params_for(O, self.geo, weights)
         self.p = additive(p) if coupling == 0 else p
         x, _ = O.smooth_batch(self.p, B, nz, seed=B)
         self.eps = R.forward64(self.p, x)[0].float()
@@ -110,10 +111,23 @@ class Case:
         x64, _, _, x32, _, _ = self.grads
         return forward_vjp(self.p, x64, self.gx, self.go, torch.float64), forward_vjp(self.p, x32, self.gx, self.go, torch.float32)
 
+    @functools.cached_property
+    def route32(self):
+        """The parameter gradients in float32 BY THE ROUTE THE LIBRARY TAKES: x = f^-1(eps), then the forward's backward at x with the
+        upstream (-g_eps, -go) -- in exact arithmetic J_f^T J_f^-T gx, the gradients of Case.grads (float64 by this route meets them
+        to 1e-13).  Autograd of the reverse itself, Case.grads' float32, does not see this route's conditioning: block 0's actnorm.b
+        is the reverse's last operation there, d L / d b = -sum gx whatever the weights (own error 1e-7), while by this route it is
+        that sum carried through J_f^-T and back, 9e-5 in float32 on the trained C3 weights against 3e-6 on the init ones."""
+        _, _, _, x32, g32, _ = self.grads
+        q = {k: v.float().clone().requires_grad_(True) for k, v in self.p.items()}
+        z1, ld = O.flow_forward(q, x32, torch.zeros(self.B))
+        grads = torch.autograd.grad(-(z1 * g32).sum() - (ld * self.go).sum(), list(q.values()), allow_unused=True)
+        return {k: g for k, g in zip(q, grads) if g is not None}
+
 
 @functools.lru_cache(maxsize=None)
-def case(nz, w, depth, coupling, B):
-    return Case(nz, w, depth, coupling, B)
+def case(nz, w, depth, coupling, B, weights=T.INIT):
+    return Case(nz, w, depth, coupling, B, weights)
 
 
 def make_plan(lsnf, c, dev):
@@ -143,8 +157,9 @@ def ptr(t):
 # 1 - 3. kernel level: bits, block outputs, the stash does its job
 # ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nz,w,depth,coupling,B", CASES)
-def test_keep_form_bits_block_outputs_and_stash(lsnf, mode, gpu_device, nz, w, depth, coupling, B):
-    c = case(nz, w, depth, coupling, B)
+def test_keep_form_bits_block_outputs_and_stash(lsnf, mode, gpu_device, nz, w, depth, coupling, B, weights=T.INIT):
+    c = case(nz, w, depth, coupling, B, weights)
+    mode = mode if weights == T.INIT else f"{mode} {weights}"
     dev, F, lib = gpu_device, lsnf.flow, lsnf.load_library()
     plan = make_plan(lsnf, c, dev)
     assert F.reverse_keep_supported(plan, B)
@@ -190,6 +205,12 @@ def test_keep_form_bits_block_outputs_and_stash(lsnf, mode, gpu_device, nz, w, d
     err_v = R.rel_l2(back.cpu(), v64)
     report(f"{mode} {c.geo} B{B} backward_z from the reverse's stash", err_v, max(1e-5, 3.0 * own_v), own_v)
     assert err_v <= max(1e-5, 3.0 * own_v)
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", T.CASES)
+def test_keep_form_bits_block_outputs_and_stash_at_trained_weights(lsnf, mode, gpu_device, nz, w, depth, coupling, B):
+    """The same checks and tolerances on the golden trained weights (tests/trained_weights.py)."""
+    test_keep_form_bits_block_outputs_and_stash(lsnf, mode, gpu_device, nz, w, depth, coupling, B, weights=T.TRAINED)
 
 
 @pytest.mark.parametrize("nz,w,depth,coupling,B", [C3 + (100,), C3 + (4100,), C3 + (8200,), C5 + (33,), TINY + (33,), (2, 1, 3, 1, 33)])
@@ -249,14 +270,23 @@ def test_every_tensor_four_bytes_off_a_16_byte_boundary(lsnf, mode, gpu_device):
 # ---------------------------------------------------------------------------------------------
 # 4. parameter gradients from the reverse's workspace (the h1 / h2 dump and the tag)
 # ---------------------------------------------------------------------------------------------
-def check_param_grads(lsnf, label, keys, grads, p64, p32, floor=2e-5):
-    worst = (0.0, 0.0, 0.0, "")
+TRAINED_PARAM_GATE = 1e-4                   # the plain kernels' gate per parameter tensor on the trained goldens (tests/test_gpu_module.py)
+
+
+def check_param_grads(lsnf, label, keys, grads, p64, p32, floor=2e-5, route32=None):
+    """A tensor's bound is max(floor, 3 x its float32 own error).  route32 (the trained cases alone): a second float32 restatement,
+    Case.route32; where 3 x ITS error is the larger the bound is that, but never above TRAINED_PARAM_GATE."""
+    worst = (0.0, 0.0, 0.0, "", 0.0)
     for k, g in zip(keys, grads):
         own_k = R.rel_l2(p32[k], p64[k])
+        tol_k = max(floor, 3.0 * own_k)
+        if route32 is not None:
+            route_k = R.rel_l2(route32[k].reshape(p64[k].shape), p64[k])
+            tol_k, own_k = max(tol_k, min(3.0 * route_k, TRAINED_PARAM_GATE)), max(own_k, route_k)
         err_k = R.rel_l2(g.cpu().reshape(p64[k].shape), p64[k])
-        if err_k / max(floor, 3.0 * own_k) >= worst[0]:
-            worst = (err_k / max(floor, 3.0 * own_k), err_k, own_k, k)
-    report(f"{label} d theta worst {worst[3]}", worst[1], max(floor, 3.0 * worst[2]), worst[2])
+        if err_k / tol_k >= worst[0]:
+            worst = (err_k / tol_k, err_k, own_k, k, tol_k)
+    report(f"{label} d theta worst {worst[3]}", worst[1], worst[4] if worst[3] else floor, worst[2])
     assert worst[0] <= 1.0, worst
 
 
@@ -265,8 +295,9 @@ def param_keys(lsnf, depth):
 
 
 @pytest.mark.parametrize("nz,w,depth,coupling,B", PARAM_CASES)
-def test_parameter_gradients_from_the_reverse_workspace(lsnf, mode, gpu_device, nz, w, depth, coupling, B):
-    c = case(nz, w, depth, coupling, B)
+def test_parameter_gradients_from_the_reverse_workspace(lsnf, mode, gpu_device, nz, w, depth, coupling, B, weights=T.INIT):
+    c = case(nz, w, depth, coupling, B, weights)
+    mode = mode if weights == T.INIT else f"{mode} {weights}"
     dev, F = gpu_device, lsnf.flow
     params = lsnf.params_from_state_dict(c.p, depth, dev)
     plan = lsnf.prepare(params, nz, w, depth, coupling)
@@ -277,7 +308,23 @@ def test_parameter_gradients_from_the_reverse_workspace(lsnf, mode, gpu_device, 
     grads = F.backward_params(plan, params, x, eps, saved, g_eps.neg(), go.neg(), act_saved=act, workspace=ws)
     _, _, p64, _, _, p32 = c.grads
     assert len(grads) == depth * 12
-    check_param_grads(lsnf, f"{mode} {c.geo} B{B}", param_keys(lsnf, depth), grads, p64, p32)
+    # (trained weights: the float32 restatement whose error widens a bound is the one of the route taken -- Case.route32)
+    check_param_grads(lsnf, f"{mode} {c.geo} B{B}", param_keys(lsnf, depth), grads, p64, p32, route32=None if weights == T.INIT else c.route32)
+
+
+TRAINED_PARAM_CASES = [c for c in PARAM_CASES if c in T.CASES]                 # C3 at 100 and 4100 rows, C5 at 33
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", TRAINED_PARAM_CASES)
+def test_parameter_gradients_from_the_reverse_workspace_at_trained_weights(lsnf, mode, gpu_device, nz, w, depth, coupling, B):
+    """The init-weight bound per tensor, max(2e-5, 3 x the error of float32 autograd of the reverse), fails here on one tensor: block
+    0's actnorm.b at C3 / 4100 rows, 3.9e-5 on the device with an own error of 1.2e-7.  That is the arithmetic's error on
+    ill-conditioned weights, not a defect: under autograd of the reverse that tensor is the last operation (-sum gx whatever the
+    weights), while the library's route is J_f^T J_f^-T gx -- exact to 1e-13 in float64, 9.2e-5 in a plain float32 restatement of
+    the same route on these weights (Case.route32; 3.4e-6 on the init ones).  So for the trained cases alone a tensor's bound may
+    grow to 3 x that restatement's error, capped at the plain kernels' documented gate for the parameter gradients on the trained
+    goldens, 1e-4 per tensor (TRAINED_PARAM_GATE).  No init-weight bound moves (profiles/chain_trained.txt, section 4)."""
+    test_parameter_gradients_from_the_reverse_workspace(lsnf, mode, gpu_device, nz, w, depth, coupling, B, weights=T.TRAINED)
 
 
 def test_workspace_tag_is_written_from_the_contraction_s_first_row_count(lsnf, mode, gpu_device):

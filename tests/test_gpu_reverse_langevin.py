@@ -14,6 +14,7 @@ import torch
 from oracle.philox_oracle import langevin_noise
 import chain_geometries as G
 import reverse_restated as R
+import trained_weights as T
 import test_gpu_reverse_keep as K
 
 pytestmark = pytest.mark.gpu
@@ -40,10 +41,12 @@ class Setup:
     """One case on the device: the plan, x = reverse(eps), the forward's outputs and stash at x, the upstream gradient, a noise tensor,
     and the results of the plain calls the tests compare with -- each computed once."""
 
-    def __init__(self, lsnf, dev, nz, w, depth, coupling, B, mode):
+    def __init__(self, lsnf, dev, nz, w, depth, coupling, B, mode, weights=T.INIT):
         F = lsnf.flow
-        self.c = c = K.case(nz, w, depth, coupling, B)
+        self.c = c = K.case(nz, w, depth, coupling, B, weights)
         self.geo, self.B, self.nz, self.depth, self.mode = c.geo, B, nz, depth, mode
+        # the fp32 step the kernel sees: 0.1, or the trained geometry's own (tests/trained_weights.py)
+        self.step_size = step = STEP if weights == T.INIT else float(np.float32(T.LANGEVIN_STEP[c.geo]))
         prev = F.set_math_mode(F.MATH_FP32) if mode == "fp32" else None
         try:
             self.plan = K.make_plan(lsnf, c, dev)
@@ -53,24 +56,24 @@ class Setup:
             self.gx = c.gx.to(dev)
             self.noise = torch.randn(B, nz, generator=torch.Generator().manual_seed(7 + B)).to(dev)
             self.g_ref = F.reverse_backward_z(self.plan, self.e, self.saved, self.act, self.gx, None)
-            self.plain = F.reverse_langevin_step(self.plan, self.e, self.saved, self.act, self.gx, None, STEP, want_g=True)
-            self.noisy = F.reverse_langevin_step(self.plan, self.e, self.saved, self.act, self.gx, self.noise, STEP, want_g=True)
+            self.plain = F.reverse_langevin_step(self.plan, self.e, self.saved, self.act, self.gx, None, step, want_g=True)
+            self.noisy = F.reverse_langevin_step(self.plan, self.e, self.saved, self.act, self.gx, self.noise, step, want_g=True)
             torch.cuda.synchronize()
         finally:
             if prev is not None:
                 F.set_math_mode(prev)
 
     def step(self, lsnf, noise, **kw):
-        return lsnf.flow.reverse_langevin_step(self.plan, self.e, self.saved, self.act, self.gx, noise, STEP, **kw)
+        return lsnf.flow.reverse_langevin_step(self.plan, self.e, self.saved, self.act, self.gx, noise, self.step_size, **kw)
 
 
 @functools.lru_cache(maxsize=None)
-def _setup(lsnf, dev, nz, w, depth, coupling, B, mode):
-    return Setup(lsnf, dev, nz, w, depth, coupling, B, mode)
+def _setup(lsnf, dev, nz, w, depth, coupling, B, mode, weights):
+    return Setup(lsnf, dev, nz, w, depth, coupling, B, mode, weights)
 
 
-def setup_of(lsnf, dev, nz, w, depth, coupling, B, mode="default"):
-    return _setup(lsnf, dev, nz, w, depth, coupling, B, mode)
+def setup_of(lsnf, dev, nz, w, depth, coupling, B, mode="default", weights=T.INIT):
+    return _setup(lsnf, dev, nz, w, depth, coupling, B, mode, weights)
 
 
 @pytest.fixture
@@ -92,10 +95,10 @@ def bits(a, b):
 # 1. the gradient is lsnf_reverse_backward_z's, bit for bit
 # ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nz,w,depth,coupling,B,mode", RUNS)
-def test_gradient_bits(lsnf, gpu_device, math, nz, w, depth, coupling, B, mode):
-    s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, mode)
+def test_gradient_bits(lsnf, gpu_device, math, nz, w, depth, coupling, B, mode, weights=T.INIT):
+    s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, mode, weights)
     math(mode)
-    F = lsnf.flow
+    F, STEP = lsnf.flow, s.step_size
     assert bool(torch.isfinite(s.g_ref).all())
     assert bits(s.plain[1], s.g_ref) and bits(s.noisy[1], s.g_ref)
     # grad_g = None is explicit zeros
@@ -110,8 +113,9 @@ def test_gradient_bits(lsnf, gpu_device, math, nz, w, depth, coupling, B, mode):
 # 2. the update: four fp32 roundings (and coef's own), fused or not
 # ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nz,w,depth,coupling,B,mode", RUNS)
-def test_update_arithmetic(lsnf, gpu_device, nz, w, depth, coupling, B, mode):
-    s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, mode)
+def test_update_arithmetic(lsnf, gpu_device, nz, w, depth, coupling, B, mode, weights=T.INIT):
+    s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, mode, weights)
+    STEP = s.step_size
     e, coef = s.e.double(), 0.5 * STEP * STEP
     for what, res, n in (("no noise", s.plain, torch.zeros_like(e)), ("tensor noise", s.noisy, s.noise.double())):
         g = res[1].double()                                 # the kernel's own g
@@ -119,7 +123,7 @@ def test_update_arithmetic(lsnf, gpu_device, nz, w, depth, coupling, B, mode):
         bound = 2.0 ** -23 * (e.abs() + 3.0 * coef * (e + g).abs() + 2.0 * STEP * n.abs())
         excess = ((res[0].double() - r).abs() - bound).max().item()
         worst = ((res[0].double() - r).abs() / bound.clamp_min(1e-300)).max().item()
-        print(f"[reverse-langevin] {mode} {s.geo} B{B} {what}: worst |eps_new - r| / bound = {worst:.3f}")
+        print(f"[reverse-langevin] {mode} {s.geo} B{B}{'' if weights == T.INIT else ' ' + weights} {what}: worst |eps_new - r| / bound = {worst:.3f}")
         assert bool(torch.isfinite(res[0]).all()) and excess <= 0.0
     assert not bits(s.plain[0], s.noisy[0]) or B * nz < 4
 
@@ -200,8 +204,8 @@ def rows_are_their_own(lsnf, s, smaller):
 # 5. norms
 # ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nz,w,depth,coupling,B,mode", RUNS)
-def test_norms(lsnf, gpu_device, math, nz, w, depth, coupling, B, mode):
-    s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, mode)
+def test_norms(lsnf, gpu_device, math, nz, w, depth, coupling, B, mode, weights=T.INIT):
+    s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, mode, weights)
     math(mode)
     eps_new, g, g_norm, eps_norm = s.noisy
     assert g_norm.shape == (B,) and eps_norm.shape == (B,)
@@ -209,12 +213,30 @@ def test_norms(lsnf, gpu_device, math, nz, w, depth, coupling, B, mode):
     for what, got, of in (("g_norm", g_norm, g), ("eps_norm", eps_norm, s.e)):
         ref = of.double().norm(dim=1)
         err = ((got.double() - ref).abs() / ref.clamp_min(1e-300)).max().item()
-        print(f"[reverse-langevin] {mode} {s.geo} B{B} {what}: rel {err:.3e} allowed {rel:.3e}")
+        print(f"[reverse-langevin] {mode} {s.geo} B{B}{'' if weights == T.INIT else ' ' + weights} {what}: rel {err:.3e} allowed {rel:.3e}")
         assert err <= rel
     bare = s.step(lsnf, s.noise, want_norms=False, want_g=False)
     assert bare[1] is None and bare[2] is None and bare[3] is None and bits(bare[0], eps_new)
     only_g = s.step(lsnf, s.noise, want_norms=False, want_g=True)
     assert only_g[2] is None and bits(only_g[0], eps_new) and bits(only_g[1], g)
+
+
+# ---------------------------------------------------------------------------------------------
+# 5b. the three checks above on the golden trained weights (tests/trained_weights.py), each geometry at its own step
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("nz,w,depth,coupling,B", T.CASES)
+def test_gradient_bits_at_trained_weights(lsnf, gpu_device, math, nz, w, depth, coupling, B):
+    test_gradient_bits(lsnf, gpu_device, math, nz, w, depth, coupling, B, "default", weights=T.TRAINED)
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", T.CASES)
+def test_update_arithmetic_at_trained_weights(lsnf, gpu_device, nz, w, depth, coupling, B):
+    test_update_arithmetic(lsnf, gpu_device, nz, w, depth, coupling, B, "default", weights=T.TRAINED)
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", T.CASES)
+def test_norms_at_trained_weights(lsnf, gpu_device, math, nz, w, depth, coupling, B):
+    test_norms(lsnf, gpu_device, math, nz, w, depth, coupling, B, "default", weights=T.TRAINED)
 
 
 # ---------------------------------------------------------------------------------------------

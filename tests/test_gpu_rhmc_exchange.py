@@ -16,6 +16,7 @@ import hmc_rows_gpu as HG
 import hmc_tempered_gpu as TG
 import test_gpu_rhmc as TR
 import test_gpu_reverse_keep as K
+import trained_weights as TW
 
 pytestmark = pytest.mark.gpu
 SP = HG.Space("eps", TR)
@@ -98,3 +99,22 @@ def test_swapping_call_in_place_four_bytes_off_null_optionals_and_reused_buffers
 
 def test_sampler_is_the_hand_written_loop(lsnf, gpu_device, monkeypatch):
     XG.check_samplers(lsnf, SP, K, gpu_device, monkeypatch)
+
+
+# ---------------------------------------------------------------------------------------------
+# The golden trained weights (tests/trained_weights.py, TW): the checks above on the scalar module's trained cases, each at its own step.
+# ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", TW.SMALL)
+def test_without_swap_every_phase_is_the_tempered_call_bit_for_bit_at_trained_weights(lsnf, gpu_device, nz, w, depth, coupling, B):
+    XG.check_no_swap_is_the_tempered_call(lsnf, SP, TR.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, weights=TW.TRAINED))
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B,R", TW.LADDERS)
+def test_swap_is_the_restated_exchange_of_the_plain_call_bit_for_bit_at_trained_weights(lsnf, gpu_device, nz, w, depth, coupling, B, R):
+    XG.check_swap_bits(lsnf, SP, TR.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, weights=TW.TRAINED), R)
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B,R", TW.LADDERS)
+def test_next_trajectory_of_a_swapping_call_follows_float64_at_trained_weights(lsnf, gpu_device, nz, w, depth, coupling, B, R):
+    XG.check_next_trajectory_follows_float64(lsnf, SP, TR.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, weights=TW.TRAINED), R)

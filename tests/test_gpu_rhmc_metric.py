@@ -14,6 +14,7 @@ import hmc_rows_gpu as HG
 import test_gpu_rhmc as TR
 import test_gpu_reverse_keep as K
 from test_gpu_langevin import ToyG
+import trained_weights as TW
 
 pytestmark = pytest.mark.gpu
 SP = HG.Space("eps", TR)
@@ -195,3 +196,17 @@ def test_sampler_without_windows_is_the_adaptive_sampler(lsnf, gpu_device):
                                                                              **dict(kw, warmup_steps=4))
     assert not bits(e_c, e_b) and not bits(metric_c.scale, torch.ones_like(metric_c.scale)) and not metric_c.count.any()
     assert bool((steps_c.adapt[:, 2] == 1).all())
+
+
+# ---------------------------------------------------------------------------------------------
+# The golden trained weights (tests/trained_weights.py, TW): the checks above on the scalar module's trained cases, each at its own step.
+# ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", TW.SMALL)
+def test_unit_scale_is_the_per_row_call_bit_for_bit_at_trained_weights(lsnf, gpu_device, nz, w, depth, coupling, B):
+    MG.check_unit_scale_is_the_per_row_call(lsnf, SP, TR.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, weights=TW.TRAINED))
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", TW.SMALL)
+def test_column_scale_follows_float64_and_begins_to_the_bit_at_trained_weights(lsnf, gpu_device, nz, w, depth, coupling, B):
+    MG.check_column_scale_follows_float64(lsnf, SP, TR.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, weights=TW.TRAINED))

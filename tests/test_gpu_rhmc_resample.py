@@ -15,6 +15,7 @@ import hmc_rows_gpu as HG
 import hmc_tempered_gpu as TG
 import test_gpu_rhmc as TR
 import test_gpu_reverse_keep as K
+import trained_weights as TW
 
 pytestmark = pytest.mark.gpu
 SP = HG.Space("eps", TR)
@@ -111,3 +112,17 @@ def test_sampler_is_the_hand_written_loop(lsnf, gpu_device, monkeypatch):
 
 def test_sampler_lands_inside_the_cpu_experiments_band(lsnf, gpu_device):
     SG.check_sampler_band(lsnf, SP, K, gpu_device)
+
+
+# ---------------------------------------------------------------------------------------------
+# The golden trained weights (tests/trained_weights.py, TW): the checks above on the scalar module's trained cases, each at its own step.
+# ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", TW.SMALL)
+def test_without_resample_every_phase_is_the_tempered_call_bit_for_bit_at_trained_weights(lsnf, gpu_device, nz, w, depth, coupling, B):
+    SG.check_no_resample_is_the_tempered_call(lsnf, SP, TR.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, weights=TW.TRAINED))
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B,R", TW.LADDERS)
+def test_move_is_the_restated_resampling_of_the_plain_call_bit_for_bit_at_trained_weights(lsnf, gpu_device, nz, w, depth, coupling, B, R):
+    SG.check_move_bits(lsnf, SP, TR.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, weights=TW.TRAINED), R)

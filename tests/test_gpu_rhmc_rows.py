@@ -10,6 +10,7 @@ import hmc_rows_restated as R
 import test_gpu_rhmc as TR
 import test_gpu_reverse_keep as K
 from test_gpu_langevin import ToyG
+import trained_weights as TW
 
 pytestmark = pytest.mark.gpu
 SP = HG.Space("eps", TR)
@@ -148,3 +149,17 @@ def test_sampler_frozen_phase_acceptance_lies_in_the_cpu_band(lsnf, gpu_device):
                                                                            g_llhd_sigma=1.0, philox=F.PhiloxNoise(5, 0, 0))
     torch.cuda.synchronize()
     HG.check_frozen_phase_acceptance(SP, rate.cpu(), steps)
+
+
+# ---------------------------------------------------------------------------------------------
+# The golden trained weights (tests/trained_weights.py, TW): the checks above on the scalar module's trained cases, each at its own step.
+# ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", TW.SMALL)
+def test_per_row_is_the_scalar_call_bit_for_bit_at_trained_weights(lsnf, gpu_device, nz, w, depth, coupling, B):
+    HG.check_per_row_is_the_scalar_call(lsnf, SP, TR.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, weights=TW.TRAINED))
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", TW.SMALL)
+def test_adaptation_arithmetic_at_trained_weights(lsnf, gpu_device, nz, w, depth, coupling, B):
+    HG.check_adaptation_arithmetic(lsnf, SP, TR.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, weights=TW.TRAINED))

@@ -13,6 +13,7 @@ import hmc_rows_gpu as HG
 import hmc_tempered_gpu as TG
 import test_gpu_rhmc as TR
 import test_gpu_reverse_keep as K
+import trained_weights as TW
 
 pytestmark = pytest.mark.gpu
 SP = HG.Space("eps", TR)
@@ -124,3 +125,27 @@ def test_captured_annealing_end_call_replays_with_a_rewritten_beta_next(lsnf, gp
 
 def test_sampler_finds_the_closed_form(lsnf, gpu_device):
     TG.check_samplers(lsnf, SP, K, gpu_device)
+
+
+# ---------------------------------------------------------------------------------------------
+# The golden trained weights (tests/trained_weights.py, TW): the checks above on the scalar module's trained cases, each at its own step.
+# ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", TW.SMALL)
+def test_unit_temperature_is_the_metric_call_bit_for_bit_at_trained_weights(lsnf, gpu_device, nz, w, depth, coupling, B):
+    TG.check_unit_temperature_is_the_metric_call(lsnf, SP, TR.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, weights=TW.TRAINED))
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", TW.SMALL)
+def test_general_temperature_follows_float64_at_trained_weights(lsnf, gpu_device, nz, w, depth, coupling, B):
+    TG.check_general_temperature_follows_float64(lsnf, SP, TR.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, weights=TW.TRAINED))
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", TW.SMALL)
+def test_anneal_lines_hold_on_the_stored_values_at_trained_weights(lsnf, gpu_device, nz, w, depth, coupling, B):
+    TG.check_anneal_lines(lsnf, SP, TR.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, weights=TW.TRAINED))
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", TW.SMALL)
+def test_fifty_anneals_sum_to_the_float64_weight_at_trained_weights(lsnf, gpu_device, nz, w, depth, coupling, B):
+    TG.check_anneal_sum(lsnf, SP, TR.setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, weights=TW.TRAINED))

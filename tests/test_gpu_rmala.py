@@ -23,6 +23,7 @@ from oracle import flow_oracle as O
 import chain_geometries as G
 import mala_restated as M
 import rmala_restated as RM
+import trained_weights as T
 import test_gpu_mala as ZM
 import test_gpu_reverse_keep as K
 from test_gpu_langevin import ToyG
@@ -50,7 +51,9 @@ STEP_GEO.update({(62, 31, 2, 1): 0.8, (66, 33, 2, 1): 0.8, (124, 63, 3, 1): 0.6,
                  (12, 100, 2, 1): 1.1, (66, 65, 2, 1): 0.8, (128, 128, 2, 1): 0.7})
 
 
-def step_of(nz, geo=None):
+def step_of(nz, geo=None, weights=T.INIT):
+    if weights != T.INIT:
+        return float(np.float32(T.step_of("mala eps", geo)))                       # tests/trained_weights.py
     return float(np.float32(STEP_GEO[geo] if geo in STEP_GEO else STEP[nz]))      # the fp32 step the kernel sees
 
 
@@ -64,11 +67,11 @@ def lsnf():
 class Case:
     """One geometry and batch on the CPU: the float64 chain (teacher-forcing records) and the fp32 restatement's figures."""
 
-    def __init__(self, nz, w, depth, coupling, B, s=None):
-        self.geo, self.B, self.nz, self.depth = (nz, w, depth, coupling), B, nz, depth
-        p = O.init_params(nz, w, depth, seed=3)
+    def __init__(self, nz, w, depth, coupling, B, s=None, weights=T.INIT):
+        self.geo, self.B, self.nz, self.depth, self.weights = (nz, w, depth, coupling), B, nz, depth, weights
+        p = T.params_for(O, self.geo, weights)
         self.p = K.additive(p) if coupling == 0 else p
-        self.s = step_of(nz, (nz, w, depth, coupling)) if s is None else s
+        self.s = step_of(nz, (nz, w, depth, coupling), weights) if s is None else s
         self.n_steps = 3 if B <= 100 else 1
         self.quad = M.Quadratic(nz, 0.1, seed=7 + nz)                       # (U >= |eps|^2 / 2 is of order nz / 2: no row's bound falls below fp32)
         g = torch.Generator().manual_seed(7 + B)
@@ -92,21 +95,21 @@ class Case:
 
 
 @functools.lru_cache(maxsize=None)
-def case(nz, w, depth, coupling, B):
-    return Case(nz, w, depth, coupling, B)
+def case(nz, w, depth, coupling, B, weights=T.INIT):
+    return Case(nz, w, depth, coupling, B, weights=weights)
 
 
 class Setup:
     """A case's plan on the device (made under the run's math mode, as its stash will be)."""
 
-    def __init__(self, lsnf, dev, nz, w, depth, coupling, B, mode):
-        self.c, self.dev, self.mode = case(nz, w, depth, coupling, B), dev, mode
+    def __init__(self, lsnf, dev, nz, w, depth, coupling, B, mode, weights=T.INIT):
+        self.c, self.dev, self.mode = case(nz, w, depth, coupling, B, weights), dev, mode
         self.plan = K.make_plan(lsnf, self.c, dev)
 
 
 @functools.lru_cache(maxsize=None)
-def setup_of(lsnf, dev, nz, w, depth, coupling, B, mode="default"):
-    return Setup(lsnf, dev, nz, w, depth, coupling, B, mode)
+def setup_of(lsnf, dev, nz, w, depth, coupling, B, mode="default", weights=T.INIT):
+    return Setup(lsnf, dev, nz, w, depth, coupling, B, mode, weights)
 
 
 @pytest.fixture
@@ -160,11 +163,12 @@ def rel_l2(a, b):
 # 1. against float64, teacher-forced
 # ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nz,w,depth,coupling,B,mode", RUNS)
-def test_decisions_and_state_follow_float64(lsnf, gpu_device, math, nz, w, depth, coupling, B, mode):
+def test_decisions_and_state_follow_float64(lsnf, gpu_device, math, nz, w, depth, coupling, B, mode, weights=T.INIT):
     math(mode)
-    s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, mode)
+    s = setup_of(lsnf, gpu_device, nz, w, depth, coupling, B, mode, weights)
     c = s.c
-    print(f"[rmala] {mode} {c.geo} B{B} s={c.s:.2f}: float64 accepts {100 * c.rate:.0f} % of {len(c.steps)} x {B} decisions")
+    mode = mode if weights == T.INIT else f"{mode} {weights}"
+    print(f"[rmala] {mode} {c.geo} B{B} s={c.s:.3f}: float64 accepts {100 * c.rate:.0f} % of {len(c.steps)} x {B} decisions")
     if c.n_steps == 3:
         assert 0.15 <= c.rate <= 0.85
     for j, st in enumerate(c.steps):
@@ -178,6 +182,10 @@ def test_decisions_and_state_follow_float64(lsnf, gpu_device, math, nz, w, depth
               f"{int((~st.smooth).sum())} near a kink), worst |log_alpha - fp64| / gate = {worst:.3f}, "
               f"oracle-fp32 worst {((st.la32.double() - st.la).abs() / st.gate).max().item():.3f}")
         assert aside <= allowed
+        if weights != T.INIT:                                # the same share from the device's own log_alpha, together with the kink rows
+            aside_dev = int((~st.smooth | ((la.cpu().double() - torch.log(st.u.double())).abs() <= st.gate)).sum())
+            print(f"[rmala] {mode} {c.geo} B{B} step {j + 1}: set aside by the device's log_alpha {aside_dev}")
+            assert aside_dev <= allowed
         assert bool((err <= st.gate)[st.smooth].all())
         d, a64 = st.decided, st.acc
         acc_c, ea, ga, ua = acc.cpu(), state.z.cpu(), state.grad.cpu(), state.energy.cpu()
@@ -196,6 +204,13 @@ def test_decisions_and_state_follow_float64(lsnf, gpu_device, math, nz, w, depth
             assert g_err <= g_tol
         n_err = rel_l2(e_next.cpu()[d], st.e_next[d]) if bool(d.any()) else 0.0
         assert n_err <= max(1e-5, 3.0 * rel_l2(st.t32, st.t_prop))
+
+
+@pytest.mark.parametrize("nz,w,depth,coupling,B", T.CASES)
+def test_decisions_and_state_follow_float64_at_trained_weights(lsnf, gpu_device, math, nz, w, depth, coupling, B):
+    """The same steps, gates and caps on the golden trained weights (tests/trained_weights.py): a saturating sigmoid, |3 logs| up to 2,
+    steps from the narrow window in which the float64 chain still accepts there."""
+    test_decisions_and_state_follow_float64(lsnf, gpu_device, math, nz, w, depth, coupling, B, "default", weights=T.TRAINED)
 
 
 # ---------------------------------------------------------------------------------------------
