@@ -862,6 +862,10 @@ hipError_t launch_fwd3q_w(const Fwd3pArgs& a, hipStream_t stream) {
 // in its tiled form only, with both parts of the stash, for the whole stack.  With the stash, or a part of it (STASH
 // instantiation: buffer stores of whole 16-byte groups through 32-bit offsets): rows that take 16-byte accesses, and a block of
 // rows / of stash tiles below 2 GiB.
+// (The dump's own extent rule, (B + 32) * width * 4 < 2^31, cannot fire under the dispatch of lsnf_api.hip: hdump_tiled needs
+//  dump_may_tile, hence lsnf_contract_x3_covers, which stops at 4 194 272 rows -- (B + 32) * 64 * 4 is 2^30 there --, and a dump comes
+//  with act_saved, hence the stash rule below, which at nz = 128, the one nz of this kernel whose dump may tile, stops at 4 194 304.
+//  It stays as this kernel's own statement of what its descriptors can address; tests/test_large_batch_cpu.py restates the shadowing.)
 bool lsnf_forward3q_covers(const LsnfForwardCall& c) {
     const LsnfGeo& g = c.g;
     if (g.HT != 2 || g.WT != 2 || fwd3q_lds(c.n_blocks) > 160 * 1024) return false;

@@ -464,6 +464,10 @@ hipError_t lsnf_launch_params_contract(const LsnfContractCall& c, int contractio
         t.fold = c.workspace + lsnf_params_det_partials(g.nz, g.width, g.depth, c.B);
         t.chunk = lsnf_det_chunk_rows(c.B, g.depth, 0);
     }
+    // the chunks are the grid's y extent, which a launch takes up to 65 535: beyond that many chunks (33.5 M rows at 512 rows per
+    // chunk; B goes up to 2^28) the chunk grows, in whole 16-row stages, so that there are never more
+    constexpr int kMaxGridY = 65535;
+    if ((c.B + t.chunk - 1) / t.chunk > kMaxGridY) t.chunk = ((c.B + kMaxGridY - 1) / kMaxGridY + 15) / 16 * 16;
     const dim3 grid(g.depth * 5, (unsigned)((c.B + t.chunk - 1) / t.chunk));
     hipError_t e = hipSuccess;
     if (c.det) {
